@@ -16,6 +16,11 @@ After the timed steps the query side is measured on the same engine (>= 1M rows 
 single-stream hybrid top-10 queries, p50/p99 of the wall time per query (timed with the engine's event profiler off;
 the scan kernels' timings come from a second pass over the same queries with it on).
 
+A plain run measures only that: set-up, --warmup + --steps indexing steps, the single-stream query latency, the line.
+--full adds everything else the line used to carry (the profiled query pass, batched dense / hybrid queries, queries
+from tokens and from text, recall checks, the anisotropic corpus, the other model widths, the CPU baseline).
+--dump-outputs DIR writes what the timed path computed (dump_outputs()); the inputs depend on the arguments only.
+
 Weak scaling: every rank owns its own 1M-row shard and indexes its own batches (no collective on
 the indexing path); queries merge per-shard top-k lists with one RCCL all_gather per list.
 
@@ -75,7 +80,19 @@ def parse():
     p.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo for rehearsals)")
     p.add_argument("--share-gpu", action="store_true",
                    help="rehearsal only: every rank uses GPU 0 (needs --backend gloo; RCCL refuses duplicate GPUs)")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="also measure everything outside the headline: the profiled query pass (roofline_search), batched "
+                        "dense / hybrid queries, queries from tokens, recall checks, the anisotropic corpus, the drop-in "
+                        "per-file sequence, the other model widths and the CPU baseline. Without it a run sets up, warms up, "
+                        "times the --steps indexing steps and the single-stream hybrid query latency, and prints the line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what they computed as DIR/<name>.npy (float32 / float64): the stored "
+                        "embeddings and sparse term ids of the last timed step's rows, and the rows and fused scores of the "
+                        "timed single-stream hybrid queries")
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def zipf_ids(gen, torch, n, vocab, dev, s=1.07):
@@ -524,6 +541,131 @@ def cpu_baseline(args, rng):
     }
 
 
+DUMP_BUDGET_BYTES = 60 << 20  # of the 64 MB allowed: room for the .npy headers
+
+
+def _sample(n: int, keep: int, seed: int) -> np.ndarray:
+    """All of range(n), or a fixed seeded sample of `keep` of them in ascending order."""
+    if n <= keep:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(n, size=keep, replace=False)).astype(np.int64)
+
+
+def dump_outputs(out_dir, engine, first_row, n_rows, answers, limit, suffix=""):
+    """--dump-outputs: what the timed path computed, as DIR/<name>.npy in float32 / float64 (64 MB at most; beyond
+    that a fixed, seeded sample of rows / queries, whose positions are written beside them):
+      index_last_step_embeddings    f32 [rows, dim]  the stored (cosine-preprocessed) embeddings of the last timed step
+      index_last_step_sparse_ids    f64 [rows, w]    their stored BM25 term ids, -1 padded
+      index_last_step_sample        f64 [rows]       which of the step's rows these are (0 = the step's first chunk)
+      query_hybrid_rows             f64 [q, limit]   rows of the timed single-stream hybrid top-10 queries, -1 padded
+      query_hybrid_scores           f64 [q, limit]   their fused scores, NaN padded
+      query_hybrid_sample           f64 [q]          which of the timed queries these are"""
+    os.makedirs(out_dir, exist_ok=True)
+    q_bytes = 16 * limit + 8
+    q_sel = _sample(len(answers), max(1, DUMP_BUDGET_BYTES // 4 // q_bytes), 11)
+    hyb_rows = np.full((q_sel.size, limit), -1.0)
+    hyb_scores = np.full((q_sel.size, limit), np.nan)
+    for j, i in enumerate(q_sel):
+        rows, scores = np.asarray(answers[i][0]), np.asarray(answers[i][1])
+        hyb_rows[j, : rows.size] = rows
+        hyb_scores[j, : scores.size] = scores
+    ids, _ = engine.sparse_row_ids(first_row + np.arange(n_rows, dtype=np.int64))
+    row_bytes = 4 * engine.dim + 8 * ids.shape[1] + 8
+    r_sel = _sample(n_rows, max(1, (DUMP_BUDGET_BYTES - q_sel.size * q_bytes) // row_bytes), 7)
+    arrays = {"index_last_step_embeddings": engine.get_dense(first_row + r_sel).astype(np.float32),
+              "index_last_step_sparse_ids": ids[r_sel].astype(np.float64),
+              "index_last_step_sample": r_sel.astype(np.float64),
+              "query_hybrid_rows": hyb_rows, "query_hybrid_scores": hyb_scores,
+              "query_hybrid_sample": q_sel.astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a)
+
+
+def headline(args, world, dt, chunks_per_s, tokens, n_rows, p50, p99, gemm_ms, gemm_n, gemm_flop, attn_ms, attn_n,
+             attn_flop, attn_bytes):
+    """The fields of the result line that a plain run measures: the timed indexing steps (value, ms_per_step, and the
+    GEMM / attention rooflines from the engine's event profiler over those same steps) and the single-stream hybrid
+    query latency."""
+    gemm_tf = gemm_flop / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
+    # ceiling for ALGORITHMIC FLOP/s: the f32 MFMA peak, the dense f16 peak, or a third of it (three passes)
+    gemm_peak = {"f32": PEAK_F32_MFMA_TFLOPS, "f16": PEAK_F16_MFMA_TFLOPS,
+                 "f16x3": round(PEAK_F16_MFMA_TFLOPS / 3.0, 1)}[args.precision]
+    return {
+        "metric": "chunks indexed/sec + p50 top-10 query latency @1M-chunk corpus, 1/8 MI355X",
+        "value": round(chunks_per_s, 1),
+        "unit": "chunks/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(dt / args.steps * 1e3, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": {"f32": "f32",
+                  "f16x3": "f16x3 (operands as hi+lo f16 = 22 significant bits, three f16-MFMA passes, f32 "
+                           "accumulate; measured |1-cos| ~5e-8 vs the f64 oracle)",
+                  "f16": "f16 (f16 MFMA operands, f32 accumulate; softmax, LayerNorm statistics and pooling in f32; the "
+                         "residual stream between layers is stored as f16 (LayerNorm is applied inside the GEMM epilogues from "
+                         "f32 row sums); measured |1-cos| = 1.5e-6 vs the f64 oracle on THIS code path at this scale — 2300 "
+                         "sequences / 272k tokens, 12 layers, sampled sequences incl. tile and forward-chunk edges "
+                         "(tests/test_encoder_gpu.py::test_bench_scale_f16_path_against_the_f64_oracle; 4.1e-6 at 24 layers), "
+                         "north_star tolerance 1e-4)"
+                  }[args.precision],
+        "data": "synthetic (seeded token ids / unit vectors; random-init N(0,0.02) weights of the named shape)",
+        "config": {
+            "workload": "BASELINE configs[2]: 1M-chunk corpus, bge-base-en-v1.5 shape (L12 H768 CLS) dense + "
+                        "BM25 sparse, min-max hybrid top-10 (prefetch 30), 1 MI355X per shard",
+            "chunks_per_step_per_gpu": args.batch,
+            "tokens_per_chunk_mean": round(tokens / (args.steps * args.batch), 1),
+            "corpus_rows_per_gpu": int(n_rows),
+            "queries": args.queries,
+            "fusion": "minmax (reference vector_store.py:659-689)",
+            "parallelism": f"shard{world}",
+        },
+        "p50_query_ms": round(p50, 4),
+        "p99_query_ms": round(p99, 4),
+        "query_kind": "single-stream hybrid top-10 (dense top-30 + sparse top-30 + fusion), query vector given",
+        # f32: algorithmic FLOP against the f32-MFMA peak. f16x3: every algorithmic multiply-add is
+        # three f16 MFMA multiply-adds, so the ceiling for ALGORITHMIC FLOP/s is the dense f16 peak / 3.
+        "roofline": {
+            "kernel": {"f32": "vr::gemm_f32_kernel (v_mfma_f32_32x32x2_f32)",
+                       "f16x3": "vr::gemm_f16x3_256_kernel<EPI, 3> (v_mfma_f32_16x16x32_f16, 3 passes per "
+                                "product; 256x256 tiles)",
+                       "f16": "vr::gemm_f16_pp_kernel<EPI> (v_mfma_f32_16x16x32_f16, one pass; 256x256x64 tiles, "
+                              "8 waves in two phase-shifted groups)"}[args.precision],
+            "bound": "mfma",
+            "achieved": round(gemm_tf, 2),
+            "peak": gemm_peak,
+            "unit": "TFLOP/s",
+            "frac": round(gemm_tf / gemm_peak, 4),
+            "executed_mfma_TFLOPs": round(gemm_tf * (3 if args.precision == "f16x3" else 1), 1),
+            "traffic": pmc_traffic({"f32": "gemm_f32_kernel", "f16x3": "gemm_f16x3_256_kernel",
+                                    "f16": "gemm_f16_pp_kernel"}[args.precision]),
+            "algorithmic_flop_per_launch": round(gemm_flop / max(gemm_n, 1)),
+            "launches": gemm_n,
+            "avg_launch_ms": round(gemm_ms / max(gemm_n, 1), 4),
+            "share_of_step_time": round(gemm_ms * 1e-3 / dt, 4),
+        },
+        # attention reads Q, K, V once (f16) and writes the context rows: 4 H halfs per token and launch — at the
+        # ~118-token sequences of the indexing path it is bound by that traffic, not by its 1.1 TFLOP per batch
+        "roofline_attention": {
+            "kernel": "vr::attention_seq_kernel<64> (one block per (sequence, head): K/V rows staged once, "
+                      "v_mfma_f32_16x16x32_f16 for QK^T and PV, V^T fragments from ds_read_b64_tr_b16)",
+            "bound": "hbm",
+            "achieved": round(attn_bytes / (attn_ms * 1e-3) / 1e9, 1) if attn_ms > 0 else None,
+            "peak": PEAK_HBM_GBPS,
+            "unit": "GB/s",
+            "frac": round(attn_bytes / (attn_ms * 1e-3) / 1e9 / PEAK_HBM_GBPS, 4) if attn_ms > 0 else None,
+            "algorithmic_bytes_per_launch": round(attn_bytes / max(attn_n, 1)),
+            "launches": attn_n,
+            "avg_launch_ms": round(attn_ms / max(attn_n, 1), 4),
+            "TFLOPs": round(attn_flop / (attn_ms * 1e-3) / 1e12, 2) if attn_ms > 0 else None,
+            "share_of_step_time": round(attn_ms * 1e-3 / dt, 4),
+            "traffic": pmc_traffic("attention_seq_kernel"),
+        },
+    }
+
+
 def launch_ranks(args) -> int:
     """`python bench.py --gpus N` without a launcher: start the N ranks as CHILD processes (one per GPU, the same
     command line, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in their environment — what torch.distributed.run would
@@ -620,6 +762,7 @@ def main():
         first = engine.index_batch(b[0], b[1], b[2], b[3])
         if searcher is not None:
             searcher.rows_added(np.arange(first, first + args.batch, dtype=np.int64))
+        return first
 
     # ---- indexing: W warm-up steps, then exactly K timed steps ------------------------------------
     for b in batches[: args.warmup]:
@@ -629,7 +772,7 @@ def main():
     t0 = time.perf_counter()
     tokens = 0
     for b in batches[args.warmup:]:
-        index_step(b)
+        last_first = index_step(b)
         tokens += b[4]
     barrier()
     dt = time.perf_counter() - t0
@@ -659,11 +802,33 @@ def main():
         search(i)
     barrier()
     lat = np.empty(args.queries)
+    answers = []
     for i in range(args.queries):  # the latencies: the engine's event profiler is OFF (its four event records per query
         t1 = time.perf_counter()   # cost ~10 us of the wall time they would be part of)
-        search(20 + i)
+        got = search(20 + i)
         lat[i] = time.perf_counter() - t1
+        answers.append(got)
     barrier()
+    p50, p99 = float(np.percentile(lat, 50) * 1e3), float(np.percentile(lat, 99) * 1e3)
+    if world > 1:
+        t = torch.tensor([p50, p99], dtype=torch.float64, device=comm_dev)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        p50, p99 = float(t[0]), float(t[1])
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, engine, last_first, args.batch, answers, 10,
+                     "" if world == 1 else f".rank{rank}")
+    del answers
+    if not args.full:
+        del corpus_chunks, state
+        if rank == 0:
+            print(json.dumps(headline(args, world, dt, chunks_per_s, tokens, n_rows, p50, p99, gemm_ms, gemm_n, gemm_flop,
+                                      attn_ms, attn_n, attn_flop, attn_bytes)), flush=True)
+        engine.close()
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
+    # ======== --full: everything below is outside the headline ========================================================
     engine.profile(True)           # the kernel timings of the same queries: a second pass with the profiler on
     for i in range(min(args.queries, 300)):
         search(20 + i)
@@ -671,11 +836,6 @@ def main():
     scan_ms, scan_n, scan_bytes = engine.profile_read(Engine.PROF_DENSE_SCAN)
     sp_ms, sp_n, sp_bytes = engine.profile_read(Engine.PROF_SPARSE_SCAN)
     engine.profile(False)
-    p50, p99 = float(np.percentile(lat, 50) * 1e3), float(np.percentile(lat, 99) * 1e3)
-    if world > 1:
-        t = torch.tensor([p50, p99], dtype=torch.float64, device=comm_dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        p50, p99 = float(t[0]), float(t[1])
     dense_only = [engine.search_dense(qs_host[20 + i: 21 + i], 10) for i in range(min(50, args.queries))]
 
     # ---- batched queries: all --queries dense top-10 searches in ONE call -----------
@@ -817,46 +977,10 @@ def main():
                 print(f"[bench] {m['name']} section failed: {exc!r}", file=sys.stderr, flush=True)
 
     if rank == 0:
-        gemm_tf = gemm_flop / (gemm_ms * 1e-3) / 1e12 if gemm_ms > 0 else 0.0
-        # ceiling for ALGORITHMIC FLOP/s: the f32 MFMA peak, the dense f16 peak, or a third of it (three passes)
-        gemm_peak = {"f32": PEAK_F32_MFMA_TFLOPS, "f16": PEAK_F16_MFMA_TFLOPS,
-                     "f16x3": round(PEAK_F16_MFMA_TFLOPS / 3.0, 1)}[args.precision]
         scan_gbps = scan_bytes / (scan_ms * 1e-3) / 1e9 if scan_ms > 0 else 0.0
-        out = {
-            "metric": "chunks indexed/sec + p50 top-10 query latency @1M-chunk corpus, 1/8 MI355X",
-            "value": round(chunks_per_s, 1),
-            "unit": "chunks/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(dt / args.steps * 1e3, 3),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": {"f32": "f32",
-                      "f16x3": "f16x3 (operands as hi+lo f16 = 22 significant bits, three f16-MFMA passes, f32 "
-                               "accumulate; measured |1-cos| ~5e-8 vs the f64 oracle)",
-                      "f16": "f16 (f16 MFMA operands, f32 accumulate; softmax, LayerNorm statistics and pooling in f32; the "
-                             "residual stream between layers is stored as f16 (LayerNorm is applied inside the GEMM epilogues from "
-                             "f32 row sums); measured |1-cos| = 1.5e-6 vs the f64 oracle on THIS code path at this scale — 2300 "
-                             "sequences / 272k tokens, 12 layers, sampled sequences incl. tile and forward-chunk edges "
-                             "(tests/test_encoder_gpu.py::test_bench_scale_f16_path_against_the_f64_oracle; 4.1e-6 at 24 layers), "
-                             "north_star tolerance 1e-4)"
-                      }[args.precision],
-            "data": "synthetic (seeded token ids / unit vectors; random-init N(0,0.02) weights of the named shape)",
-            "config": {
-                "workload": "BASELINE configs[2]: 1M-chunk corpus, bge-base-en-v1.5 shape (L12 H768 CLS) dense + "
-                            "BM25 sparse, min-max hybrid top-10 (prefetch 30), 1 MI355X per shard",
-                "chunks_per_step_per_gpu": args.batch,
-                "tokens_per_chunk_mean": round(tokens / (args.steps * args.batch), 1),
-                "corpus_rows_per_gpu": int(n_rows),
-                "queries": args.queries,
-                "fusion": "minmax (reference vector_store.py:659-689)",
-                "parallelism": f"shard{world}",
-            },
-            "p50_query_ms": round(p50, 4),
-            "p99_query_ms": round(p99, 4),
-            "query_kind": "single-stream hybrid top-10 (dense top-30 + sparse top-30 + fusion), query vector given",
+        out = headline(args, world, dt, chunks_per_s, tokens, n_rows, p50, p99, gemm_ms, gemm_n, gemm_flop,
+                       attn_ms, attn_n, attn_flop, attn_bytes)
+        out.update({
             "p50_query_encode_ms": None if enc_lat is None else round(enc_lat, 4),
             "p50_query_from_tokens_ms": None if full_lat is None else round(full_lat, 4),
             "query_from_tokens_kind": "the same search with the 12-token query embedded by the engine first (vr_encode + vr_search_hybrid)",
@@ -893,27 +1017,6 @@ def main():
             "p99_query_from_text_ms": None if dropin is None else round(dropin[4], 4),
             "query_from_text_kind": "embed_query(text) -> sparse embed_query(text) -> VectorStoreService.search(limit=10, hybrid) "
                                     "as mcp_server.py:469-485 calls them, StoredChunk objects out; corpus as above",
-            # f32: algorithmic FLOP against the f32-MFMA peak. f16x3: every algorithmic multiply-add is
-            # three f16 MFMA multiply-adds, so the ceiling for ALGORITHMIC FLOP/s is the dense f16 peak / 3.
-            "roofline": {
-                "kernel": {"f32": "vr::gemm_f32_kernel (v_mfma_f32_32x32x2_f32)",
-                           "f16x3": "vr::gemm_f16x3_256_kernel<EPI, 3> (v_mfma_f32_16x16x32_f16, 3 passes per "
-                                    "product; 256x256 tiles)",
-                           "f16": "vr::gemm_f16_pp_kernel<EPI> (v_mfma_f32_16x16x32_f16, one pass; 256x256x64 tiles, "
-                                  "8 waves in two phase-shifted groups)"}[args.precision],
-                "bound": "mfma",
-                "achieved": round(gemm_tf, 2),
-                "peak": gemm_peak,
-                "unit": "TFLOP/s",
-                "frac": round(gemm_tf / gemm_peak, 4),
-                "executed_mfma_TFLOPs": round(gemm_tf * (3 if args.precision == "f16x3" else 1), 1),
-                "traffic": pmc_traffic({"f32": "gemm_f32_kernel", "f16x3": "gemm_f16x3_256_kernel",
-                                        "f16": "gemm_f16_pp_kernel"}[args.precision]),
-                "algorithmic_flop_per_launch": round(gemm_flop / max(gemm_n, 1)),
-                "launches": gemm_n,
-                "avg_launch_ms": round(gemm_ms / max(gemm_n, 1), 4),
-                "share_of_step_time": round(gemm_ms * 1e-3 / dt, 4),
-            },
             "roofline_search": {
                 "kernel": ("vr::prefilter_scan_kernel (v_mfma_f32_16x16x32_f16 streaming scan of the f16 shadow "
                            if os.environ.get("VR_PREFILTER") == "f16" or MODEL["hidden"] % 64 else
@@ -952,24 +1055,7 @@ def main():
                 "share_of_call_time": round(bscan_ms * 1e-3 / batch_dt, 4) if qps_batched is not None else None,
                 "traffic": pmc_traffic("batch_scan_kernel"),
             },
-            # attention reads Q, K, V once (f16) and writes the context rows: 4 H halfs per token and launch — at the
-            # ~118-token sequences of the indexing path it is bound by that traffic, not by its 1.1 TFLOP per batch
-            "roofline_attention": {
-                "kernel": "vr::attention_seq_kernel<64> (one block per (sequence, head): K/V rows staged once, "
-                          "v_mfma_f32_16x16x32_f16 for QK^T and PV, V^T fragments from ds_read_b64_tr_b16)",
-                "bound": "hbm",
-                "achieved": round(attn_bytes / (attn_ms * 1e-3) / 1e9, 1) if attn_ms > 0 else None,
-                "peak": PEAK_HBM_GBPS,
-                "unit": "GB/s",
-                "frac": round(attn_bytes / (attn_ms * 1e-3) / 1e9 / PEAK_HBM_GBPS, 4) if attn_ms > 0 else None,
-                "algorithmic_bytes_per_launch": round(attn_bytes / max(attn_n, 1)),
-                "launches": attn_n,
-                "avg_launch_ms": round(attn_ms / max(attn_n, 1), 4),
-                "TFLOPs": round(attn_flop / (attn_ms * 1e-3) / 1e12, 2) if attn_ms > 0 else None,
-                "share_of_step_time": round(attn_ms * 1e-3 / dt, 4),
-                "traffic": pmc_traffic("attention_seq_kernel"),
-            },
-        }
+        })
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args, np.random.default_rng(3))
             out["speedup_vs_cpu_index"] = round(chunks_per_s / out["cpu_baseline"]["value"], 1)

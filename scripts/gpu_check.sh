@@ -5,7 +5,7 @@ set -o pipefail
 R=/root/repo; O=$R/gpurun_out/check; mkdir -p $O
 cd $R
 timeout -k 10 900 python -m pytest tests -m gpu -x -q > $O/gpu_tests.log 2>&1; echo "tests rc=$?" | tee $O/gpu_tests.rc; tail -5 $O/gpu_tests.log
-timeout -k 10 400 python bench.py > $O/bench_n1.json 2> $O/bench_n1.err; echo "bench rc=$?"; tail -c 1500 $O/bench_n1.err; python - <<'PY'
+timeout -k 10 400 python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err; echo "bench rc=$?"; tail -c 1500 $O/bench_n1.err; python - <<'PY'
 import json
 try:
     d = json.loads(open('/root/repo/gpurun_out/check/bench_n1.json').read().strip().splitlines()[-1])
@@ -16,7 +16,7 @@ try:
 except Exception as e:
     print("no bench line:", e)
 PY
-timeout -k 10 300 python bench.py --gpus 2 --backend gloo --share-gpu --corpus 300000 --steps 3 --warmup 1 --queries 300 > $O/bench_n2_gloo.json 2> $O/bench_n2_gloo.err; echo "rehearsal rc=$?"; tail -c 600 $O/bench_n2_gloo.err; python - <<'PY'
+timeout -k 10 300 python bench.py --full --gpus 2 --backend gloo --share-gpu --corpus 300000 --steps 3 --warmup 1 --queries 300 > $O/bench_n2_gloo.json 2> $O/bench_n2_gloo.err; echo "rehearsal rc=$?"; tail -c 600 $O/bench_n2_gloo.err; python - <<'PY'
 import json
 try:
     d = json.loads(open('/root/repo/gpurun_out/check/bench_n2_gloo.json').read().strip().splitlines()[-1])
