@@ -359,6 +359,33 @@ int vr_search_hybrid_batch(vr_engine* e, const float* q, int32_t nq, int mem,
                            int32_t limit, double sparse_weight, int32_t fusion, const vr_filter* filter,
                            int64_t* out_rows, double* out_scores, int32_t* out_from_dense, int32_t* out_counts);
 
+/* Filtered batches: every query with its own filter (the MCP search tool under multi-user load: include_folders from the
+ * user's active folders, exclude_folders, dates, limit and sparse_weight per call, mcp_server.py:374-461). Query i uses
+ * filters[filter_of_query[i]], or none when filter_of_query[i] is -1; every distinct entry is a CLASS. Row i is, bit for
+ * bit, what the single call with query i's own arguments returns. The batched dense scan reads one bit plane per class
+ * (csrc/filter.hip) instead of one shared mask, so a batch of many classes still scans the corpus once; the grouped
+ * sparse scan forms its groups of queries of one class, each reading that class's plane (collections of >= 128 index
+ * segments; otherwise, and for what the batched scans do not take, class by class on a byte mask). One class takes the
+ * unfiltered-batch path (vr_search_dense / vr_search_hybrid_batch) unchanged. VR_CLASS_PLANE_MIB (default 256) bounds
+ * the planes of one scan; a batch needing more runs in slices of classes. 
+ * filter_of_query, every filter's struct_size and n_must_folder_sets, k and every limits[i] (1..341) are checked before
+ * any device work. */
+
+/* nq dense queries, k each: rows[nq*k] (-1 padded), scores[nq*k], counts[nq] as vr_search_dense(q_i, k, filter_i). */
+int vr_search_dense_multi(vr_engine* e, const float* q, int32_t nq, int mem, int32_t k,
+                          const vr_filter* filters, int32_t n_filters, const int32_t* filter_of_query,
+                          int64_t* rows, float* scores, int32_t* counts);
+
+/* nq hybrid queries as vr_search_hybrid(q_i, sparse_i, limits[i], sparse_weights[i], fusion, filter_i); sq_off may be
+ * NULL. out_rows / out_scores / out_from_dense: nq x out_stride (out_stride >= every limit; entries beyond out_counts[i]
+ * are unspecified). */
+int vr_search_hybrid_batch_multi(vr_engine* e, const float* q, int32_t nq, int mem,
+                                 const int64_t* sq_off, const int32_t* sq_idx, const float* sq_val,
+                                 const int32_t* limits, const double* sparse_weights, int32_t fusion,
+                                 const vr_filter* filters, int32_t n_filters, const int32_t* filter_of_query,
+                                 int32_t out_stride, int64_t* out_rows, double* out_scores,
+                                 int32_t* out_from_dense, int32_t* out_counts);
+
 /* Both legs of nq hybrid queries as packed ranking keys (see vr_search_dense_keys), for a sharded caller: keys is
  * [nq][2][k] uint64 in `keys_mem` memory — per query its dense list, then its sparse list. weights_given as in
  * vr_search_sparse. The caller all-gathers the array, merges with vr_merge_keys and fuses with vr_fuse_batch

@@ -129,6 +129,10 @@ SIGNATURES = {
                                          _i64p, _fp, _i32p]),
     "vr_search_hybrid_batch": (C.c_int, [_vp, _vp, C.c_int32, C.c_int, _i64p, _i32p, _fp, C.c_int32, C.c_double,
                                          C.c_int32, C.POINTER(VrFilter), _i64p, _dp, _i32p, _i32p]),
+    "vr_search_dense_multi": (C.c_int, [_vp, _vp, C.c_int32, C.c_int, C.c_int32, C.POINTER(VrFilter), C.c_int32, _i32p,
+                                        _i64p, _fp, _i32p]),
+    "vr_search_hybrid_batch_multi": (C.c_int, [_vp, _vp, C.c_int32, C.c_int, _i64p, _i32p, _fp, _i32p, _dp, C.c_int32,
+                                               C.POINTER(VrFilter), C.c_int32, _i32p, C.c_int32, _i64p, _dp, _i32p, _i32p]),
     "vr_search_hybrid_keys": (C.c_int, [_vp, _vp, C.c_int32, C.c_int, _i64p, _i32p, _fp, C.c_int32, C.c_int32,
                                         C.POINTER(VrFilter), _vp, C.c_int]),
     "vr_merge_keys": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int, _i64p, _fp, _i32p]),

@@ -172,6 +172,10 @@ static void release_scratch(vr_engine* e) {
   e->bq_tile_ub.release();
   e->bq_pairs.release();
   e->bq_stage.release();
+  e->cls_planes.release();
+  e->cls_of_q.release();
+  e->cls_pass.release();
+  e->cls_desc.release();
   e->sq_off.release();
   e->sq_ids.release();
   e->sq_val.release();
@@ -1071,7 +1075,7 @@ int prepare_sparse_batch(const int64_t* q_off, const int32_t* q_idx, const float
 
 // Queues the batch kernel of the prepared queries on e->stream; the nq x k keys end up in e->sq_keys (device).
 int sparse_batch_launch(vr_engine* e, const SparseBatch& b, int nq, int k, bool weights_given, const uint8_t* mask,
-                        bool allow_grouped = true) {
+                        bool allow_grouped = true, const ClassPlanes* classes = nullptr) {
   const int64_t nt = static_cast<int64_t>(b.ids.size());
   VR_TRY(e->sq_off.grow(nq + 1, 0, e->stream));
   VR_TRY(e->sq_ids.grow(std::max<int64_t>(nt, 1), 0, e->stream));
@@ -1087,7 +1091,7 @@ int sparse_batch_launch(vr_engine* e, const SparseBatch& b, int nq, int k, bool 
   VR_HIP(hipMemcpyAsync(e->sq_val.p, b.vals.data(), sizeof(float) * static_cast<size_t>(nt), hipMemcpyHostToDevice, e->stream));
   return inv_scan_topk_batch(e, e->sq_off.p, e->sq_ids.p, e->sq_val.p, e->sq_w.p, nq, static_cast<int>(nt), weights_given,
                              static_cast<float>(e->n_sparse_points), mask, k, e->sq_keys.p, b.off.data(), b.ids.data(),
-                             allow_grouped);
+                             allow_grouped, classes);
 }
 
 // After the stream of sparse_batch_launch has been synchronised: the grouped scan gives up the queries whose candidate
@@ -1203,9 +1207,343 @@ int hybrid_keys_locked(vr_engine* e, const float* q, int nq, int mem, const int6
   return 0;
 }
 
+// ---- filtered batches: a filter, a limit and a sparse weight per query (vr_search_*_multi) -------------------------
+
+// The classes of a filtered batch: the distinct entries of `filters` its queries name (and "no filter"), numbered in
+// order of first appearance. Everything is validated here, before any device work.
+struct QueryClasses {
+  std::vector<int32_t> of;               // per query: its class
+  std::vector<const vr_filter*> filter;  // per class: its filter (nullptr: none)
+};
+
+int classify_queries(const vr_filter* filters, int n_filters, const int32_t* filter_of_query, int nq, QueryClasses* qc) {
+  VR_CHECK(n_filters >= 0 && (n_filters == 0 || (filters && filter_of_query)), "bad filters");
+  for (int j = 0; j < n_filters; ++j) {
+    VR_CHECK(filters[j].struct_size == static_cast<int32_t>(sizeof(vr_filter)), "filters[%d]: vr_filter size mismatch", j);
+    VR_CHECK(filters[j].n_must_folder_sets >= 0 && filters[j].n_must_folder_sets <= 2, "filters[%d]: at most 2 must-sets", j);
+  }
+  std::vector<int32_t> class_of(static_cast<size_t>(n_filters) + 1, -1);  // [n_filters]: no filter
+  qc->of.assign(static_cast<size_t>(nq), 0);
+  qc->filter.clear();
+  for (int i = 0; i < nq; ++i) {
+    const int32_t f = filter_of_query ? filter_of_query[i] : -1;
+    VR_CHECK(f >= -1 && f < n_filters, "filter_of_query[%d] = %d not in -1..%d", i, f, n_filters - 1);
+    int32_t& c = class_of[static_cast<size_t>(f < 0 ? n_filters : f)];
+    if (c < 0) {
+      c = static_cast<int32_t>(qc->filter.size());
+      qc->filter.push_back(f < 0 ? nullptr : filters + f);
+    }
+    qc->of[static_cast<size_t>(i)] = c;
+  }
+  return 0;
+}
+
+// Bytes of class planes one batched scan may use (VR_CLASS_PLANE_MIB, default 256): a batch with more classes runs in
+// slices of classes, one scan per slice.
+int64_t class_plane_budget() {
+  static const int64_t mib = getenv("VR_CLASS_PLANE_MIB") ? std::max(0, atoi(getenv("VR_CLASS_PLANE_MIB"))) : 256;
+  return mib << 20;
+}
+
+// Both legs of a filtered batch. Query i asks for its ks[i] best keys under its class's filter; they go to row i of
+// dense_host / sparse_host ([nq][kstride], zero padded; sparse_host null: dense only). q: host array, nq x D.
+//   dense   the queries of k <= kFusedMaxK share the batched scan (batch.hip), which reads each query's class plane; the
+//           queries sorted by class, so that a 128-query block column mostly sees one class. Classes go in slices whose
+//           planes fit class_plane_budget(). A slice too small to batch, the larger k and the queries over their candidate
+//           budget run class by class on the byte mask of that class (filter_mask_kernel), through search_dense_keys_locked.
+//   sparse  the queries of k <= kFusedMaxK as ONE grouped scan of the inverted index when it takes the batch (invert.hip:
+//           groups hold queries of one class and read its plane); the rest — longer queries, the larger k, queries whose
+//           candidates overflowed, batches the grouped scan does not take — class by class on the byte mask, each class's
+//           queries as one batched sparse search (search_sparse_keys_locked).
+// Every list is the exact top-k of the single call, so a list of the largest k of a group, cut to a query's own k, is
+// that query's list.
+int multi_keys_locked(vr_engine* e, const float* q, int nq, const int32_t* ks, int kstride, const QueryClasses& qc,
+                      const int64_t* sq_off, const int32_t* sq_idx, const float* sq_val, uint64_t* dense_host,
+                      uint64_t* sparse_host) {
+  const size_t bytes = sizeof(uint64_t) * static_cast<size_t>(nq) * kstride;
+  memset(dense_host, 0, bytes);
+  if (sparse_host) memset(sparse_host, 0, bytes);
+  if (e->n_rows == 0) return 0;
+  const int n_cls = static_cast<int>(qc.filter.size());
+  const int dim = e->dim;
+  auto put = [&](uint64_t* dst, int i, const uint64_t* src) {
+    memcpy(dst + static_cast<size_t>(i) * kstride, src, sizeof(uint64_t) * static_cast<size_t>(ks[i]));
+  };
+  std::vector<uint8_t> done(static_cast<size_t>(nq), 0);
+  const uint32_t* all_planes = nullptr;  // e->cls_planes while it holds the planes of every class
+  std::vector<int32_t> order;
+  int kb = 0;
+  for (int i = 0; i < nq; ++i)
+    if (ks[i] <= kFusedMaxK) {
+      order.push_back(i);
+      kb = std::max(kb, ks[i]);
+    }
+  std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return qc.of[static_cast<size_t>(a)] < qc.of[static_cast<size_t>(b)]; });
+  if (batch_usable(e, static_cast<int>(order.size()), kb)) {
+    const int64_t words = filter_plane_words(e);
+    const int per_slice = static_cast<int>(std::min<int64_t>(n_cls, std::max<int64_t>(1, class_plane_budget() / (4 * words))));
+    constexpr int kRound = 1024;  // (as search_dense_keys_locked)
+    std::vector<float> qs;
+    std::vector<int32_t> cls, over;
+    std::vector<uint64_t> keys;
+    size_t at = 0;
+    for (int c0 = 0; c0 < n_cls && at < order.size(); c0 += per_slice) {
+      const int c1 = std::min(n_cls, c0 + per_slice);
+      size_t end = at;
+      while (end < order.size() && qc.of[static_cast<size_t>(order[end])] < c1) ++end;
+      const int ns = static_cast<int>(end - at);
+      if (!batch_usable(e, ns, kb)) {  // (left to the class loop below)
+        at = end;
+        continue;
+      }
+      const uint32_t* planes = nullptr;
+      VR_TRY(filter_build_planes(e, qc.filter.data() + c0, c1 - c0, &planes));
+      all_planes = c0 == 0 && c1 == n_cls ? planes : nullptr;
+      for (int r0 = 0; r0 < ns; r0 += kRound) {
+        const int nb = std::min(kRound, ns - r0);
+        const int32_t* idx = order.data() + at + r0;
+        qs.resize(static_cast<size_t>(nb) * dim);
+        cls.resize(static_cast<size_t>(nb));
+        for (int j = 0; j < nb; ++j) {
+          memcpy(qs.data() + static_cast<size_t>(j) * dim, q + static_cast<int64_t>(idx[j]) * dim, sizeof(float) * dim);
+          cls[static_cast<size_t>(j)] = qc.of[static_cast<size_t>(idx[j])] - c0;
+        }
+        VR_TRY(e->bq_stage.grow(static_cast<int64_t>(nb) * dim, 0, e->stream));
+        VR_TRY(e->cls_of_q.grow(nb, 0, e->stream));
+        VR_HIP(hipMemcpyAsync(e->bq_stage.p, qs.data(), sizeof(float) * qs.size(), hipMemcpyHostToDevice, e->stream));
+        VR_HIP(hipMemcpyAsync(e->cls_of_q.p, cls.data(), sizeof(int32_t) * cls.size(), hipMemcpyHostToDevice, e->stream));
+        const uint64_t* keys_dev = nullptr;
+        const int32_t* over_dev = nullptr;
+        VR_TRY(batch_search(e, e->bq_stage.p, nb, kb, nullptr, &keys_dev, &over_dev, planes, e->cls_of_q.p, words));
+        keys.resize(static_cast<size_t>(nb) * kb);
+        over.resize(static_cast<size_t>(nb));
+        VR_HIP(hipMemcpyAsync(keys.data(), keys_dev, sizeof(uint64_t) * keys.size(), hipMemcpyDeviceToHost, e->stream));
+        VR_HIP(hipMemcpyAsync(over.data(), over_dev, sizeof(int32_t) * over.size(), hipMemcpyDeviceToHost, e->stream));
+        VR_HIP(hipStreamSynchronize(e->stream));  // (also: qs and cls may be reused)
+        e->stat_batched += nb;
+        for (int j = 0; j < nb; ++j) {
+          e->stat_batch_cands += std::min<int32_t>(over[static_cast<size_t>(j)], kBatchCand);
+          if (over[static_cast<size_t>(j)] > kBatchCand) {  // candidate budget exceeded: the class loop redoes it
+            ++e->stat_batch_fallback;
+            continue;
+          }
+          put(dense_host, idx[j], keys.data() + static_cast<size_t>(j) * kb);
+          done[static_cast<size_t>(idx[j])] = 1;
+        }
+      }
+      at = end;
+    }
+  }
+  std::vector<uint8_t> sparse_done(static_cast<size_t>(nq), 0);
+  if (sparse_host && sq_off && e->n_slices_dev > 0 && !order.empty() &&
+      static_cast<int64_t>(n_cls) * 4 * filter_plane_words(e) <= class_plane_budget() &&
+      inv_class_grouped_usable(e, static_cast<int>(order.size()))) {
+    const int n = static_cast<int>(order.size());
+    std::vector<int64_t> off(1, 0);
+    std::vector<int32_t> ids, cls;
+    std::vector<float> vals;
+    for (int32_t i : order) {
+      ids.insert(ids.end(), sq_idx + sq_off[i], sq_idx + sq_off[i + 1]);
+      vals.insert(vals.end(), sq_val + sq_off[i], sq_val + sq_off[i + 1]);
+      off.push_back(static_cast<int64_t>(ids.size()));
+      cls.push_back(qc.of[static_cast<size_t>(i)]);
+    }
+    SparseBatch b;
+    VR_TRY(prepare_sparse_batch(off.data(), ids.data(), vals.data(), n, true, &b));
+    if (!b.ids.empty()) {
+      const uint32_t* planes = all_planes;
+      if (!planes) VR_TRY(filter_build_planes(e, qc.filter.data(), n_cls, &planes));
+      const ClassPlanes classes{planes, filter_plane_words(e), cls.data()};
+      VR_TRY(sparse_batch_launch(e, b, n, kb, false, e->live.p, true, &classes));
+      std::vector<uint64_t> keys(static_cast<size_t>(n) * kb);
+      std::vector<int32_t> flagged(static_cast<size_t>(n), 0);
+      VR_HIP(hipMemcpyAsync(keys.data(), e->sq_keys.p, sizeof(uint64_t) * keys.size(), hipMemcpyDeviceToHost, e->stream));
+      VR_HIP(hipStreamSynchronize(e->stream));
+      if (*pin_host<int32_t>(e, kPinSparseOverflow) != 0 && e->sq_overflow_q) {  // (redone class by class below)
+        VR_HIP(hipMemcpyAsync(flagged.data(), e->sq_overflow_q, sizeof(int32_t) * flagged.size(), hipMemcpyDeviceToHost, e->stream));
+        VR_HIP(hipStreamSynchronize(e->stream));
+      }
+      std::vector<uint8_t> alone(static_cast<size_t>(n), 0);
+      for (int32_t j : b.alone) alone[static_cast<size_t>(j)] = 1;
+      for (int j = 0; j < n; ++j) {
+        if (alone[static_cast<size_t>(j)] || flagged[static_cast<size_t>(j)]) {
+          e->stat_sparse_group_redo += flagged[static_cast<size_t>(j)] != 0;
+          continue;
+        }
+        put(sparse_host, order[static_cast<size_t>(j)], keys.data() + static_cast<size_t>(j) * kb);
+        sparse_done[static_cast<size_t>(order[static_cast<size_t>(j)])] = 1;
+      }
+    }
+  }
+  // class by class: what the batched scans left
+  std::vector<std::vector<int32_t>> members(static_cast<size_t>(n_cls));
+  for (int i = 0; i < nq; ++i) members[static_cast<size_t>(qc.of[static_cast<size_t>(i)])].push_back(i);
+  const bool sparse_index = e->n_slices_dev > 0;
+  std::vector<int32_t> part;
+  std::vector<float> qs;
+  std::vector<uint64_t> keys;
+  std::vector<int64_t> off;
+  std::vector<int32_t> ids;
+  std::vector<float> vals;
+  for (int c = 0; c < n_cls; ++c) {
+    const std::vector<int32_t>& m = members[static_cast<size_t>(c)];
+    bool dense_left = false, sparse_terms = false;
+    for (int32_t i : m) {
+      dense_left |= !done[static_cast<size_t>(i)];
+      sparse_terms |= sparse_host && sq_off && sq_off[i + 1] > sq_off[i] && !sparse_done[static_cast<size_t>(i)];
+    }
+    if (!dense_left && !(sparse_terms && sparse_index)) continue;
+    const uint8_t* mask = nullptr;
+    VR_TRY(filter_build_mask(e, qc.filter[static_cast<size_t>(c)], &mask));
+    for (int big = 0; big < 2; ++big) {  // k <= kFusedMaxK, then the rest: each part at its largest k
+      part.clear();
+      int kq = 0;
+      for (int32_t i : m)
+        if ((ks[i] > kFusedMaxK) == (big != 0) && !done[static_cast<size_t>(i)]) {
+          part.push_back(i);
+          kq = std::max(kq, ks[i]);
+        }
+      if (!part.empty()) {
+        const int n = static_cast<int>(part.size());
+        qs.resize(static_cast<size_t>(n) * dim);
+        for (int j = 0; j < n; ++j)
+          memcpy(qs.data() + static_cast<size_t>(j) * dim, q + static_cast<int64_t>(part[static_cast<size_t>(j)]) * dim, sizeof(float) * dim);
+        keys.resize(static_cast<size_t>(n) * kq);
+        VR_TRY(search_dense_keys_locked(e, qs.data(), n, VR_MEM_HOST, kq, nullptr, keys.data(), nullptr, mask));
+        for (int j = 0; j < n; ++j) put(dense_host, part[static_cast<size_t>(j)], keys.data() + static_cast<size_t>(j) * kq);
+      }
+      if (!sparse_terms || !sparse_index) continue;
+      part.clear();
+      kq = 0;
+      off.assign(1, 0);
+      ids.clear();
+      vals.clear();
+      for (int32_t i : m)
+        if ((ks[i] > kFusedMaxK) == (big != 0) && !sparse_done[static_cast<size_t>(i)]) {
+          part.push_back(i);
+          kq = std::max(kq, ks[i]);
+          ids.insert(ids.end(), sq_idx + sq_off[i], sq_idx + sq_off[i + 1]);
+          vals.insert(vals.end(), sq_val + sq_off[i], sq_val + sq_off[i + 1]);
+          off.push_back(static_cast<int64_t>(ids.size()));
+        }
+      if (ids.empty()) continue;
+      const int n = static_cast<int>(part.size());
+      keys.resize(static_cast<size_t>(n) * kq);
+      VR_TRY(search_sparse_keys_locked(e, off.data(), ids.data(), vals.data(), n, kq, false, mask, keys.data()));
+      for (int j = 0; j < n; ++j) put(sparse_host, part[static_cast<size_t>(j)], keys.data() + static_cast<size_t>(j) * kq);
+    }
+  }
+  return 0;
+}
+
+// A batch's queries on the host: device queries are copied back once (the batch is gathered by class on the host).
+int multi_host_queries(vr_engine* e, const float* q, int nq, int mem, std::vector<float>* copy, const float** out) {
+  *out = q;
+  if (mem == VR_MEM_HOST) return 0;
+  copy->resize(static_cast<size_t>(nq) * e->dim);
+  VR_HIP(hipMemcpyAsync(copy->data(), q, sizeof(float) * copy->size(), hipMemcpyDeviceToHost, e->stream));
+  VR_HIP(hipStreamSynchronize(e->stream));
+  *out = copy->data();
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
+
+int vr_search_dense_multi(vr_engine* e, const float* q, int32_t nq, int mem, int32_t k, const vr_filter* filters,
+                          int32_t n_filters, const int32_t* filter_of_query, int64_t* rows, float* scores, int32_t* counts) {
+  // (the arguments are checked before the engine is touched)
+  VR_CHECK(q && rows && scores && nq >= 1, "bad arguments");
+  VR_CHECK(k >= 1 && k <= kMaxK, "k = %d not in 1..%d", k, kMaxK);
+  VR_CHECK(mem == VR_MEM_HOST || mem == VR_MEM_DEVICE, "bad mem %d", mem);
+  QueryClasses qc;
+  VR_TRY(classify_queries(filters, n_filters, filter_of_query, nq, &qc));
+  VR_TRY(check_engine(e));
+  std::vector<uint64_t> keys(static_cast<size_t>(nq) * k);
+  {
+    SearchLane lane(e);
+    VR_TRY(lane.acquire(mem == VR_MEM_DEVICE));
+    if (qc.filter.size() == 1) {  // one class: vr_search_dense
+      VR_TRY(search_dense_keys_locked(lane.L, q, nq, mem, k, qc.filter[0], keys.data(), nullptr));
+    } else {
+      std::vector<float> copy;
+      const float* qh = nullptr;
+      VR_TRY(multi_host_queries(lane.L, q, nq, mem, &copy, &qh));
+      const std::vector<int32_t> ks(static_cast<size_t>(nq), k);
+      VR_TRY(multi_keys_locked(lane.L, qh, nq, ks.data(), k, qc, nullptr, nullptr, nullptr, keys.data(), nullptr));
+    }
+  }
+  for (int i = 0; i < nq; ++i) {
+    const int64_t c = decode_keys(keys.data() + static_cast<size_t>(i) * k, k, rows + static_cast<int64_t>(i) * k,
+                                  scores + static_cast<int64_t>(i) * k);
+    if (counts) counts[i] = static_cast<int32_t>(c);
+  }
+  return 0;
+}
+
+int vr_search_hybrid_batch_multi(vr_engine* e, const float* q, int32_t nq, int mem, const int64_t* sq_off,
+                                 const int32_t* sq_idx, const float* sq_val, const int32_t* limits,
+                                 const double* sparse_weights, int32_t fusion, const vr_filter* filters, int32_t n_filters,
+                                 const int32_t* filter_of_query, int32_t out_stride, int64_t* out_rows, double* out_scores,
+                                 int32_t* out_from_dense, int32_t* out_counts) {
+  // (the arguments are checked before the engine is touched)
+  VR_CHECK(q && limits && sparse_weights && out_rows && out_scores && out_counts && nq >= 1, "bad arguments");
+  VR_CHECK(fusion == VR_FUSION_MINMAX || fusion == VR_FUSION_RRF, "unknown fusion %d", fusion);
+  VR_CHECK(mem == VR_MEM_HOST || mem == VR_MEM_DEVICE, "bad mem %d", mem);
+  int max_limit = 0;
+  for (int i = 0; i < nq; ++i) {
+    VR_CHECK(limits[i] >= 1 && limits[i] <= kMaxK / 3, "limits[%d] = %d not in 1..%d", i, limits[i], kMaxK / 3);
+    max_limit = std::max(max_limit, limits[i]);
+  }
+  VR_CHECK(out_stride >= max_limit, "out_stride = %d is below the largest limit %d", out_stride, max_limit);
+  if (sq_off) {
+    VR_CHECK(sq_off[nq] == sq_off[0] || (sq_idx && sq_val), "null sparse queries");
+    for (int i = 0; i < nq; ++i)
+      VR_CHECK(sq_off[i + 1] >= sq_off[i] && sq_off[i + 1] - sq_off[i] <= kMaxQueryTerms,
+               "sparse query %d has %lld terms (0..%d supported)", i, static_cast<long long>(sq_off[i + 1] - sq_off[i]), kMaxQueryTerms);
+  }
+  QueryClasses qc;
+  VR_TRY(classify_queries(filters, n_filters, filter_of_query, nq, &qc));
+  VR_TRY(check_engine(e));
+  const int kstride = 3 * max_limit;  // prefetch_limit, vector_store.py:636, of the largest limit
+  std::vector<int32_t> ks(static_cast<size_t>(nq));
+  for (int i = 0; i < nq; ++i) ks[static_cast<size_t>(i)] = 3 * limits[i];
+  const size_t per = static_cast<size_t>(nq) * kstride;
+  std::vector<uint64_t> dense(per), sparse(per);
+  {
+    SearchLane lane(e);
+    VR_TRY(lane.acquire(mem == VR_MEM_DEVICE));
+    if (qc.filter.size() == 1) {  // one class: vr_search_hybrid_batch's legs, at the largest k
+      VR_TRY(hybrid_keys_locked(lane.L, q, nq, mem, sq_off, sq_idx, sq_val, kstride, false, qc.filter[0], dense.data(),
+                                sparse.data()));
+    } else {
+      std::vector<float> copy;
+      const float* qh = nullptr;
+      VR_TRY(multi_host_queries(lane.L, q, nq, mem, &copy, &qh));
+      VR_TRY(multi_keys_locked(lane.L, qh, nq, ks.data(), kstride, qc, sq_off, sq_idx, sq_val, dense.data(), sparse.data()));
+    }
+  }
+  // fusion of every query on the host threads, each with its own limit and weight (vector_store.py:659-697)
+  std::atomic<int> failed{0};
+  parallel_for(nq, 8, [&](int64_t i) {
+    const int k = ks[static_cast<size_t>(i)], limit = limits[i];
+    int64_t d_rows[kMaxK], s_rows[kMaxK];
+    float d_scores[kMaxK], s_scores[kMaxK];
+    const int nd = static_cast<int>(decode_keys(dense.data() + static_cast<size_t>(i) * kstride, k, d_rows, d_scores));
+    const int ns = static_cast<int>(decode_keys(sparse.data() + static_cast<size_t>(i) * kstride, k, s_rows, s_scores));
+    const int64_t at = i * out_stride;
+    int32_t* fd = out_from_dense ? out_from_dense + at : nullptr;
+    const int rc = fusion == VR_FUSION_MINMAX
+                       ? fuse_minmax(d_rows, d_scores, nd, s_rows, s_scores, ns, limit, sparse_weights[i], 1, out_rows + at,
+                                     out_scores + at, fd, out_counts + i)
+                       : fuse_rrf(d_rows, nd, s_rows, ns, limit, sparse_weights[i], out_rows + at, out_scores + at, fd,
+                                  out_counts + i);
+    if (rc != 0) failed.store(1);
+  });
+  VR_CHECK(!failed.load(), "fusion failed");
+  return 0;
+}
 
 int vr_search_sparse_batch(vr_engine* e, const int64_t* q_off, const int32_t* q_idx, const float* q_val, int32_t nq,
                            int32_t k, int32_t weights_given, const vr_filter* filter, int64_t* rows, float* scores,

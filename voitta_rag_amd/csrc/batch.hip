@@ -180,13 +180,17 @@ __device__ __forceinline__ void glds16b(const void* src, void* lds_dst) {
 // of an item's epilogue drain under the next item's main loop (one-item blocks: 4k cycles of prologue and 2-3k of drain per
 // 39k-cycle item, phase stamps of round 3 — profiles/r03_batch_scan_stamps.txt).
 // PASS 1: best[q][128-row slab] = max lower bound (slab = row block x wave row). PASS 2: rows with upper bound >= thr[q] -> cand[q][...].
-template <int PASS>
+// MULTI (a filtered batch, vr_search_*_multi): query q passes the rows of its class's bit plane, planes + q_cls[q] * plane_words,
+// instead of the shared mask. A wave's 128 rows start on a multiple of 128, so they are four words of that plane: one
+// 16-byte load per query fragment and item, where the shared mask costs a four-byte load per tile.
+template <int PASS, bool MULTI>
 __global__ __launch_bounds__(512) void batch_scan_kernel(
     const uint4* __restrict__ corpus8, const uint4* __restrict__ img_a, const uint4* __restrict__ img_b,
     const float* __restrict__ params, const float* __restrict__ row_err, const float* __restrict__ row_scale,
     const uint8_t* __restrict__ mask, int64_t n_tiles, int n_rb, int rb_stride, int n_qc, int nq, int kb8n,
     float* __restrict__ best, const float* __restrict__ thr, int32_t* __restrict__ cand, int32_t* __restrict__ cand_cnt,
-    __half* __restrict__ tile_ub, unsigned long long* __restrict__ stamps, int n_ids) {
+    __half* __restrict__ tile_ub, unsigned long long* __restrict__ stamps, int n_ids, const uint32_t* __restrict__ planes,
+    const int32_t* __restrict__ q_cls, int64_t plane_words) {
   __shared__ uint4 lds[2 * kBStage / 16];  // the only LDS object (direct-to-LDS loads in flight beside fragment reads)
   // diagnostics (VR_BATCH_STAMPS=1): every 61st block's thread 0 writes the shader clock at the phase boundaries of its FIRST item
   bool stamping = stamps != nullptr && blockIdx.x % 61 == 0 && threadIdx.x == 0;
@@ -261,11 +265,13 @@ __global__ __launch_bounds__(512) void batch_scan_kernel(
     // the constants of this lane's two queries (needed by the epilogue only; requested now, so that they are there)
     float pa[2], pb[2], p1[2], p2[2], pthr[2];
     int qidx[2];
+    const uint32_t* qplane[2];
 #pragma unroll
     for (int f = 0; f < 2; ++f) {
       qidx[f] = qc * kBQ + (2 * wn + f) * 16 + (lane & 15);
       batch_query_consts(params + static_cast<int64_t>(std::min(qidx[f], nq - 1)) * kQParams, pa[f], pb[f], p1[f], p2[f]);
       pthr[f] = PASS == 2 ? thr[std::min(qidx[f], nq - 1)] : 0.0f;
+      if constexpr (MULTI) qplane[f] = planes + static_cast<int64_t>(q_cls[std::min(qidx[f], nq - 1)]) * plane_words;
     }
     i32x4 acc[8][2][2];  // [row tile of the wave][qfrag of the wave][part a, b]
 #pragma unroll
@@ -309,16 +315,30 @@ __global__ __launch_bounds__(512) void batch_scan_kernel(
     // tail test): as a loop with a break in it they were eight round trips to memory, one after the other.
     uchar4 m8[8];
     float4 e8[8], s8[8];
+    uint4 w4[2];  // MULTI: the wave's 128 rows in each query fragment's plane (rows past the corpus are 0 there)
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       const int64_t tile = std::min<int64_t>(tile0 + 8 * wm + i, last_tile);
       const int64_t row0 = tile * kTileRows + 4 * g;
-      m8[i] = *reinterpret_cast<const uchar4*>(mask + row0);
+      if constexpr (!MULTI) m8[i] = *reinterpret_cast<const uchar4*>(mask + row0);
       e8[i] = *reinterpret_cast<const float4*>(row_err + row0);
       s8[i] = *reinterpret_cast<const float4*>(row_scale + row0);
     }
+    if constexpr (MULTI) {
+#pragma unroll
+      for (int f = 0; f < 2; ++f) w4[f] = *reinterpret_cast<const uint4*>(qplane[f] + (tile0 + 8 * wm) * kTileRows / 32);
+    }
+    // the four plane bits of rows 4 g .. 4 g + 3 of the wave's tile i for query fragment f (tile i: half i % 2 of word i / 2)
+    auto bits4 = [&](int f, int i) -> uint32_t {
+      const uint32_t w = (i >> 1) == 0 ? w4[f].x : (i >> 1) == 1 ? w4[f].y : (i >> 1) == 2 ? w4[f].z : w4[f].w;
+      return w >> (16 * (i & 1) + 4 * g);
+    };
     float run[2] = {-__builtin_inff(), -__builtin_inff()};
-    if (stamping && (m8[7].x | 1)) VR_STAMP();  // (after the per-row words have arrived)
+    if constexpr (MULTI) {
+      if (stamping && (w4[1].w | 1)) VR_STAMP();
+    } else {
+      if (stamping && (m8[7].x | 1)) VR_STAMP();  // (after the per-row words have arrived)
+    }
     if (PASS == 1) {
       // two elements per instruction on the packed-f32 VALU: the lane's two query fragments side by side. A masked row (or
       // one behind the corpus's end) gets a bias of -inf into its score, so both of its bounds are -inf and no select is needed.
@@ -328,17 +348,34 @@ __global__ __launch_bounds__(512) void batch_scan_kernel(
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         const bool real = static_cast<int>(tile0) + 8 * wm + i <= static_cast<int>(last_tile);  // wave-uniform (tiles < 2^28)
-        const unsigned char mm[4] = {m8[i].x, m8[i].y, m8[i].z, m8[i].w};
+        unsigned char mm[4];
+        if constexpr (!MULTI) {
+          mm[0] = m8[i].x;
+          mm[1] = m8[i].y;
+          mm[2] = m8[i].z;
+          mm[3] = m8[i].w;
+        }
+        uint32_t qb[2];
+        if constexpr (MULTI) {
+          qb[0] = bits4(0, i);
+          qb[1] = bits4(1, i);
+        }
         const float ee[4] = {e8[i].x, e8[i].y, e8[i].z, e8[i].w};
         const float ss[4] = {s8[i].x, s8[i].y, s8[i].z, s8[i].w};
         f32x2 top2 = {-__builtin_inff(), -__builtin_inff()};
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const float bias = (real && mm[r]) ? 0.0f : -__builtin_inff();
+          f32x2 bias2;
+          if constexpr (MULTI) {
+            bias2 = f32x2{(real && ((qb[0] >> r) & 1u)) ? 0.0f : -__builtin_inff(), (real && ((qb[1] >> r) & 1u)) ? 0.0f : -__builtin_inff()};
+          } else {
+            const float bias = (real && mm[r]) ? 0.0f : -__builtin_inff();
+            bias2 = f32x2{bias, bias};
+          }
           const f32x2 da = {static_cast<float>(acc[i][0][0][r]), static_cast<float>(acc[i][1][0][r])};
           const f32x2 db = {static_cast<float>(acc[i][0][1][r]), static_cast<float>(acc[i][1][1][r])};
           const f32x2 t = __builtin_elementwise_fma(PB, db, PA * da);
-          const f32x2 score = __builtin_elementwise_fma(f32x2{ss[r], ss[r]}, t, f32x2{bias, bias});
+          const f32x2 score = __builtin_elementwise_fma(f32x2{ss[r], ss[r]}, t, bias2);
           const f32x2 err = __builtin_elementwise_fma(f32x2{ee[r], ee[r]}, P1, P2);
           const f32x2 lo = score - err, up = score + err;
           run2 = __builtin_elementwise_max(run2, lo);
@@ -362,20 +399,34 @@ __global__ __launch_bounds__(512) void batch_scan_kernel(
         const int64_t tile = tile0 + 8 * wm + i;
         const bool real = tile <= last_tile;  // wave-uniform
         const int64_t row0 = tile * kTileRows + 4 * g;
-        const unsigned char mm[4] = {m8[i].x, m8[i].y, m8[i].z, m8[i].w};
         const float ee[4] = {e8[i].x, e8[i].y, e8[i].z, e8[i].w};
         const float ss[4] = {s8[i].x, s8[i].y, s8[i].z, s8[i].w};
+        if constexpr (MULTI) {
 #pragma unroll
-        for (int f = 0; f < 2; ++f)
+          for (int f = 0; f < 2; ++f)
 #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            float score, err;
-            batch_bound(pa[f], pb[f], p1[f], p2[f], ss[r], ee[r], acc[i][f][0][r], acc[i][f][1][r], score, err);
-            if (real && mm[r] && score + err >= pthr[f] && qidx[f] < nq) {
-              const int slot = atomicAdd(cand_cnt + qidx[f], 1);
-              if (slot < kBatchCand) cand[static_cast<int64_t>(qidx[f]) * kBatchCand + slot] = static_cast<int32_t>(row0 + r);
+            for (int r = 0; r < 4; ++r) {
+              float score, err;
+              batch_bound(pa[f], pb[f], p1[f], p2[f], ss[r], ee[r], acc[i][f][0][r], acc[i][f][1][r], score, err);
+              if (real && ((bits4(f, i) >> r) & 1u) && score + err >= pthr[f] && qidx[f] < nq) {
+                const int slot = atomicAdd(cand_cnt + qidx[f], 1);
+                if (slot < kBatchCand) cand[static_cast<int64_t>(qidx[f]) * kBatchCand + slot] = static_cast<int32_t>(row0 + r);
+              }
             }
-          }
+        } else {
+          const unsigned char mm[4] = {m8[i].x, m8[i].y, m8[i].z, m8[i].w};
+#pragma unroll
+          for (int f = 0; f < 2; ++f)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              float score, err;
+              batch_bound(pa[f], pb[f], p1[f], p2[f], ss[r], ee[r], acc[i][f][0][r], acc[i][f][1][r], score, err);
+              if (real && mm[r] && score + err >= pthr[f] && qidx[f] < nq) {
+                const int slot = atomicAdd(cand_cnt + qidx[f], 1);
+                if (slot < kBatchCand) cand[static_cast<int64_t>(qidx[f]) * kBatchCand + slot] = static_cast<int32_t>(row0 + r);
+              }
+            }
+        }
       }
     }
     VR_STAMP();
@@ -451,12 +502,15 @@ __global__ __launch_bounds__(256) void batch_flag_kernel(const __half* __restric
   }
 }
 
+// MULTI: as batch_scan_kernel's, the query's class plane instead of the shared mask
+template <bool MULTI>
 __global__ __launch_bounds__(256) void batch_pairs_kernel(
     const uint4* __restrict__ corpus8, const uint4* __restrict__ img_a, const uint4* __restrict__ img_b,
     const float* __restrict__ params, const float* __restrict__ row_err, const float* __restrict__ row_scale,
     const uint8_t* __restrict__ mask, int64_t n_rows, int kb8n, const float* __restrict__ thr, int nq,
     const int32_t* __restrict__ pairs, const int32_t* __restrict__ pair_cnt, int32_t* __restrict__ cand,
-    int32_t* __restrict__ cand_cnt) {
+    int32_t* __restrict__ cand_cnt, const uint32_t* __restrict__ planes, const int32_t* __restrict__ q_cls,
+    int64_t plane_words) {
   const int lane = threadIdx.x & 63;
   const int r = lane & 15, ks = lane >> 4;  // the shadow's layout: lane = (k % 64) / 16 * 16 + row % 16, 16 bytes each
   const int64_t waves = static_cast<int64_t>(gridDim.x) * 4;
@@ -470,6 +524,8 @@ __global__ __launch_bounds__(256) void batch_pairs_kernel(
     // the query images: [qfrag][kb8][lane = (k % 64) / 16 * 16 + query % 16][16 bytes]
     const uint4* qa = img_a + (static_cast<int64_t>(q >> 4) * kb8n) * 64 + ks * 16 + (q & 15);
     const uint4* qb = img_b + (static_cast<int64_t>(q >> 4) * kb8n) * 64 + ks * 16 + (q & 15);
+    const uint32_t* qplane = nullptr;
+    if constexpr (MULTI) qplane = planes + static_cast<int64_t>(q_cls[q]) * plane_words;
     for (int sl = static_cast<int>(job % wpq); sl < n; sl += wpq) {
       const int64_t tile = pairs[static_cast<int64_t>(q) * kBatchCand + sl];
       const uint4* x = corpus8 + tile * kb8n * 64 + lane;
@@ -490,7 +546,12 @@ __global__ __launch_bounds__(256) void batch_pairs_kernel(
       db += __shfl_xor(db, 16);
       db += __shfl_xor(db, 32);
       const int64_t row = tile * kTileRows + r;
-      if (ks == 0 && row < n_rows && mask[row]) {
+      bool pass = false;
+      if (ks == 0 && row < n_rows) {
+        if constexpr (MULTI) pass = (qplane[row >> 5] >> (row & 31)) & 1u;
+        else pass = mask[row] != 0;
+      }
+      if (pass) {
         float score, err;
         batch_bound(pa, pb, p1, p2, row_scale[row], row_err[row], da, db, score, err);
         if (score + err >= tq) {
@@ -629,7 +690,11 @@ bool batch_usable(vr_engine* e, int nq, int k) {
 // q_dev: nq x D raw queries on the device. Leaves nq x k keys in out_keys_dev and one overflow flag per query
 // in overflow_dev (device memory owned by the engine; the caller copies both back).
 int batch_search(vr_engine* e, const float* q_dev, int nq, int k, const uint8_t* mask_dev, const uint64_t** out_keys_dev,
-                 const int32_t** overflow_dev) {
+                 const int32_t** overflow_dev, const uint32_t* planes, const int32_t* q_cls_dev, int64_t plane_words) {
+  const bool multi = planes != nullptr;
+  auto* scan1 = multi ? batch_scan_kernel<1, true> : batch_scan_kernel<1, false>;
+  auto* scan2 = multi ? batch_scan_kernel<2, true> : batch_scan_kernel<2, false>;
+  auto* pairs_k = multi ? batch_pairs_kernel<true> : batch_pairs_kernel<false>;
   hipStream_t s = e->stream;
   const int dim = e->dim, kb8n = dim / 64;
   const int64_t n_tiles = (e->n_rows + kTileRows - 1) / kTileRows;
@@ -693,11 +758,12 @@ int batch_search(vr_engine* e, const float* q_dev, int nq, int k, const uint8_t*
   }();
   static const bool persistent = !(getenv("VR_BATCH_PERSISTENT") && atoi(getenv("VR_BATCH_PERSISTENT")) == 0);
   const unsigned blocks1 = persistent ? std::min<unsigned>(grid1, static_cast<unsigned>(n_cus)) : grid1;
-  hipLaunchKernelGGL((batch_scan_kernel<1>), dim3(blocks1), dim3(512), 0, s, reinterpret_cast<const uint4*>(e->corpus16.p),
+  hipLaunchKernelGGL(scan1, dim3(blocks1), dim3(512), 0, s,
+                     reinterpret_cast<const uint4*>(e->corpus16.p),
                      reinterpret_cast<const uint4*>(img_a), reinterpret_cast<const uint4*>(img_b), e->bq_params.p,
                      e->row_err.p, e->row_scale.p, mask_dev, n_tiles, n_rb1, stride, n_qc, nq, kb8n, e->bq_best.p,
                      static_cast<const float*>(nullptr), static_cast<int32_t*>(nullptr), static_cast<int32_t*>(nullptr),
-                     tile_ub, stamps, static_cast<int>(grid1));
+                     tile_ub, stamps, static_cast<int>(grid1), planes, q_cls_dev, plane_words);
   if (stamps_on) {
     std::vector<unsigned long long> h(n_stamp_blocks * 16);
     VR_HIP(hipMemcpyAsync(h.data(), stamps, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
@@ -722,18 +788,20 @@ int batch_search(vr_engine* e, const float* q_dev, int nq, int k, const uint8_t*
   hipLaunchKernelGGL(batch_threshold_kernel, dim3(static_cast<unsigned>((nq + 255) / 256)), dim3(256), 0, s, kth, nq, k,
                      e->bq_thr.p);
   if (two_pass) {
-    hipLaunchKernelGGL((batch_scan_kernel<2>), dim3(grid), dim3(512), 0, s, reinterpret_cast<const uint4*>(e->corpus16.p),
+    hipLaunchKernelGGL(scan2, dim3(grid), dim3(512), 0, s,
+                       reinterpret_cast<const uint4*>(e->corpus16.p),
                        reinterpret_cast<const uint4*>(img_a), reinterpret_cast<const uint4*>(img_b), e->bq_params.p,
                        e->row_err.p, e->row_scale.p, mask_dev, n_tiles, n_rb, 1, n_qc, nq, kb8n, static_cast<float*>(nullptr),
                        e->bq_thr.p, e->bq_cand.p, e->bq_cnt.p, static_cast<__half*>(nullptr),
-                       static_cast<unsigned long long*>(nullptr), static_cast<int>(grid));
+                       static_cast<unsigned long long*>(nullptr), static_cast<int>(grid), planes, q_cls_dev, plane_words);
   } else {
     hipLaunchKernelGGL(batch_flag_kernel, dim3(static_cast<unsigned>((n_cells / 8 + 255) / 256)), dim3(256), 0, s, tile_ub,
                        e->bq_thr.p, n_cells, nq, static_cast<int>(nq_pad), e->bq_pairs.p, e->bq_pairs.p + pair_cap);
-    hipLaunchKernelGGL(batch_pairs_kernel, dim3(2048), dim3(256), 0, s, reinterpret_cast<const uint4*>(e->corpus16.p),
+    hipLaunchKernelGGL(pairs_k, dim3(2048), dim3(256), 0, s,
+                       reinterpret_cast<const uint4*>(e->corpus16.p),
                        reinterpret_cast<const uint4*>(img_a), reinterpret_cast<const uint4*>(img_b), e->bq_params.p,
                        e->row_err.p, e->row_scale.p, mask_dev, e->n_rows, kb8n, e->bq_thr.p, nq, e->bq_pairs.p,
-                       e->bq_pairs.p + pair_cap, e->bq_cand.p, e->bq_cnt.p);
+                       e->bq_pairs.p + pair_cap, e->bq_cand.p, e->bq_cnt.p, planes, q_cls_dev, plane_words);
   }
   prof_end(e);
   uint64_t* keys = e->bq_keys.p;

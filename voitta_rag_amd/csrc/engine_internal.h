@@ -139,6 +139,25 @@ static_assert(kPinCandCount >= kPinSparseKeys + sizeof(uint64_t) * kMaxK && kPin
 constexpr int kMaxCandTiles = 16384;
 constexpr int kMaxCandidates = kMaxCandTiles * 16;
 
+// One class of a filtered batch (filter.hip, filter_build_planes): where its pass tables start in the batch's
+// concatenated table (-1: no such condition) and its date range on one of the two timestamp columns.
+struct ClassDesc {
+  int32_t pass_folder;   // offset of max_folder_id + 1 pass bytes, or -1
+  int32_t pass_ifolder;  // offset of max_index_folder_id + 1 pass bytes, or -1
+  int32_t has_lo, has_hi;
+  int64_t lo, hi;
+  int32_t date_field;    // 0 = modified, 1 = created
+  int32_t pad;
+};
+
+// The classes of a filtered batch as the grouped sparse scan (invert.hip) takes them: the bit planes of filter_build_planes
+// and, per query of the batch, its plane (host array).
+struct ClassPlanes {
+  const uint32_t* planes;
+  int64_t plane_words;
+  const int32_t* q_cls;
+};
+
 }  // namespace vr
 
 struct vr_engine {
@@ -283,6 +302,12 @@ struct vr_engine {
   vr::DevArray<uint16_t> bq_tile_ub;  // f16 bits: per (16-row tile, query) the largest upper bound (rounded up)
   vr::DevArray<int32_t> bq_pairs;     // per query: the tiles whose bound reaches its threshold ([nq][kBatchCand]), then the counts [nq]
   vr::DevArray<float> bq_stage;  // host queries staged on the device
+  // filtered batches (vr_search_*_multi): one bit plane per class of filter ([class][plane words], bit r % 32 of word
+  // r / 32 = row r passes), the class of every query of the batch, and the classes' pass tables and descriptors
+  vr::DevArray<uint32_t> cls_planes;
+  vr::DevArray<int32_t> cls_of_q;
+  vr::DevArray<uint8_t> cls_pass;
+  vr::DevArray<vr::ClassDesc> cls_desc;
   // batched sparse search (invert.hip): the queries' terms as CSR (offsets, ascending distinct ids, raw values,
   // weights q_t * idf_t) and the nq x k result keys
   vr::DevArray<int32_t> sq_off, sq_ids;
@@ -357,8 +382,10 @@ int prefilter_search(vr_engine* e, int k, const uint8_t* mask_dev, uint64_t* out
 
 // ---- batch.hip: batched dense search (int8 MFMA GEMM + exact re-score)
 bool batch_usable(vr_engine* e, int nq, int k);
+// planes / q_cls_dev / plane_words (filter_build_planes): query i passes the rows of plane q_cls_dev[i] instead of mask_dev
 int batch_search(vr_engine* e, const float* q_dev, int nq, int k, const uint8_t* mask_dev, const uint64_t** out_keys_dev,
-                 const int32_t** overflow_dev);
+                 const int32_t** overflow_dev, const uint32_t* planes = nullptr, const int32_t* q_cls_dev = nullptr,
+                 int64_t plane_words = 0);
 
 // ---- topk.hip
 // scores: [nq][stride] f32 with -inf / masked rows excluded; result keys (descending) for each
@@ -412,10 +439,13 @@ int inv_scan_topk(vr_engine* e, const int32_t* q_idx_host, const float* q_val_ho
 // allow_grouped = false: the per-query kernels). The grouped scan may give up on a batch (a candidate buffer overflowed):
 // it then leaves 1 in the pinned word kPinSparseOverflow, to be read once the stream has been synchronised, and 1 per
 // overflowed query in e->sq_overflow_q (device) — the caller repeats THOSE queries with allow_grouped = false.
+// classes (filtered batches): query q passes the rows of plane classes->q_cls[q] (host array) instead of mask_dev; only the
+// grouped scan with sampled thresholds reads planes — ask inv_class_grouped_usable first.
 int inv_scan_topk_batch(vr_engine* e, const int32_t* q_off_dev, const int32_t* q_ids_dev, const float* q_val_dev,
                         float* q_w_dev, int nq, int n_terms, bool weights_given, float n_points, const uint8_t* mask_dev,
                         int k, uint64_t* out_keys_dev, const int32_t* q_off_host = nullptr,
-                        const int32_t* q_ids_host = nullptr, bool allow_grouped = false);
+                        const int32_t* q_ids_host = nullptr, bool allow_grouped = false, const ClassPlanes* classes = nullptr);
+bool inv_class_grouped_usable(const vr_engine* e, int nq);
 int sparse_scores(vr_engine* e, const int32_t* q_idx_host, const float* q_val_host, int nnz,
                   const uint8_t* mask_dev, bool weights_given);
 // term ids of the listed rows' sparse vectors as out_dev[i * stride + j] (-1: no such entry, dead row, no sparse
@@ -448,6 +478,10 @@ void prof_release(vr_engine* e);
 // ---- filter.hip
 // returns the device mask to use for this query (live[] when no filter is active)
 int filter_build_mask(vr_engine* e, const vr_filter* f, const uint8_t** mask_out);
+// words per class plane: every row block of the batched scan (256 rows) lies inside it; rows past n_rows read as excluded
+int64_t filter_plane_words(const vr_engine* e);
+// the bit planes of n_cls filters (filters[c] == nullptr: live rows) in e->cls_planes, [c][filter_plane_words(e)]
+int filter_build_planes(vr_engine* e, const vr_filter* const* filters, int n_cls, const uint32_t** planes_out);
 
 // ---- fusion.cpp (host only)
 int fuse_minmax(const int64_t* d_rows, const float* d_scores, int nd, const int64_t* s_rows,

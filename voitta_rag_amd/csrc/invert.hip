@@ -1149,7 +1149,7 @@ constexpr int kGrpMaxU = 64;     // union terms of a group (the host closes a gr
 constexpr int kGrpSlices = VR_GRP_SLICES;  // postings per thread and batch (two batches in flight). 4, not 8: 56 registers
                                            // instead of 79 let four blocks of a two-query group share a CU
 constexpr int kGrpPer = 2;       // ... of which a thread adds up this many together
-constexpr int kGrpHdr = 4 + 8;   // ints per group: union size, 3 spare, the (<= 8) queries' numbers (-1: none)
+constexpr int kGrpHdr = 4 + 8;   // ints per group: union size, class (filtered batches), 2 spare, the (<= 8) queries' numbers (-1: none)
 constexpr int kGrpEnt = 2 + 8;   // ints per union term: slot of the term among the batch's distinct terms, query mask,
                                  // per query the index of its weight in q_w (-1: none)
 constexpr int kGrpSearch = 4;    // terms a wave searches together
@@ -1263,13 +1263,17 @@ constexpr uint32_t kGrpUntouched = 0xFFFFFFFFu;
 // SAMPLE: the block takes segment blockIdx.y * seg_stride and, instead of the rows that reach a threshold, leaves the best
 // key of each of its waves' 512 rows per query (8 real rows with real scores per (query, sampled segment)): the k-th best
 // of a query's sample is the threshold of the full pass.
-template <int G, bool SAMPLE>
+// PLANES (filtered batches, vr_search_*_multi): every query of a group belongs to the group's class (header int 1), and the
+// pass bytes of a thread's 8 rows come from that class's bit plane (planes + class * plane_words, filter.hip) instead of
+// the shared mask. Nothing else changes, in the sample pass either: its thresholds are real keys of rows that pass.
+template <int G, bool SAMPLE, bool PLANES>
 __global__ __launch_bounds__(kGrpThreads) void sparse_inv_group_kernel(
     const InvSeg* __restrict__ segs, const uint64_t* __restrict__ keys, const float* __restrict__ vals,
     const int32_t* __restrict__ grp_hdr, const int32_t* __restrict__ grp_ent, const float* __restrict__ ent_w,
     const int2* __restrict__ bounds, int stride_u, const uint8_t* __restrict__ mask, const uint64_t* __restrict__ theta,
     uint64_t* __restrict__ cand, int32_t* __restrict__ cnt, int cap, int dbg_mode, int seg_stride,
-    uint64_t* __restrict__ spill, int32_t* __restrict__ spill_cnt, int spill_cap, int sample_tail, int n_seg_all) {
+    uint64_t* __restrict__ spill, int32_t* __restrict__ spill_cnt, int spill_cap, int sample_tail, int n_seg_all,
+    const uint32_t* __restrict__ planes, int64_t plane_words) {
   static_assert(G >= 1 && G <= 8, "group size");
   __shared__ __align__(16) float acc[G * kInvSegRows];
   __shared__ int32_t s_mask[kGrpMaxU];         // by compacted run: the queries that carry its term
@@ -1292,7 +1296,18 @@ __global__ __launch_bounds__(kGrpThreads) void sparse_inv_group_kernel(
   const int64_t gu0 = static_cast<int64_t>(grp) * stride_u;
   // the filter bytes of the 8 rows this thread will look at when the sums are complete (rows past the segment: 0)
   uint64_t pass8 = 0ull;
-  {
+  if constexpr (PLANES) {
+    const int r0 = tid * 8;
+    if (r0 < seg.nrows) {  // (a segment starts on any row: the 8 bits may straddle two words)
+      const uint32_t* pl = planes + static_cast<int64_t>(grp_hdr[static_cast<int64_t>(grp) * kGrpHdr + 1]) * plane_words;
+      const int64_t row = static_cast<int64_t>(seg.row_base) + r0, w = row >> 5;
+      const uint64_t two = pl[w] | (w + 1 < plane_words ? static_cast<uint64_t>(pl[w + 1]) << 32 : 0ull);
+      uint32_t bits = static_cast<uint32_t>(two >> (row & 31)) & 0xFFu;
+      if (r0 + 8 > seg.nrows) bits &= (1u << (seg.nrows - r0)) - 1u;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) pass8 |= static_cast<uint64_t>((bits >> j) & 1u) << (8 * j);
+    }
+  } else {
     const int r0 = tid * 8;
     const uint8_t* mp = mask + seg.row_base + r0;
     if (r0 + 8 <= seg.nrows && (reinterpret_cast<uintptr_t>(mp) & 7u) == 0) {
@@ -1524,7 +1539,9 @@ struct GroupLayout {
   int n_groups = 0, stride_u = 0, n_slots = 0;
   int64_t ent_off = 0, slot_off = 0;
 };
-static GroupLayout inv_group_queries(const int32_t* off, const int32_t* ids, int nq, int G, std::vector<int32_t>* out) {
+// q_cls (filtered batches): the class of every query; a group then holds queries of one class only (header int 1).
+static GroupLayout inv_group_queries(const int32_t* off, const int32_t* ids, int nq, int G, std::vector<int32_t>* out,
+                                     const int32_t* q_cls = nullptr) {
   std::unordered_map<int32_t, int32_t> freq;
   freq.reserve(static_cast<size_t>(off[nq]) * 2 + 16);
   for (int32_t i = off[0]; i < off[nq]; ++i) ++freq[ids[i]];
@@ -1534,6 +1551,7 @@ static GroupLayout inv_group_queries(const int32_t* off, const int32_t* ids, int
   std::sort(slots.begin(), slots.end());
   struct Q {
     int32_t q;
+    int32_t cls;
     int32_t key[6];  // (-frequency, id) of its three commonest terms
   };
   std::vector<Q> order;
@@ -1546,7 +1564,7 @@ static GroupLayout inv_group_queries(const int32_t* off, const int32_t* ids, int
     for (int j = 0; j < n; ++j) t.emplace_back(-freq[ids[off[q] + j]], ids[off[q] + j]);
     const size_t top = std::min<size_t>(3, t.size());
     std::partial_sort(t.begin(), t.begin() + static_cast<std::ptrdiff_t>(top), t.end());
-    Q e{q, {0, 0, 0, 0, 0, 0}};
+    Q e{q, q_cls ? q_cls[q] : 0, {0, 0, 0, 0, 0, 0}};
     for (size_t j = 0; j < top; ++j) {
       e.key[2 * j] = t[j].first;
       e.key[2 * j + 1] = t[j].second;
@@ -1554,31 +1572,38 @@ static GroupLayout inv_group_queries(const int32_t* off, const int32_t* ids, int
     order.push_back(e);
   }
   std::sort(order.begin(), order.end(), [](const Q& a, const Q& b) {
+    if (a.cls != b.cls) return a.cls < b.cls;
     for (int j = 0; j < 6; ++j)
       if (a.key[j] != b.key[j]) return a.key[j] < b.key[j];
     return a.q < b.q;
   });
   // the groups: members and their union of terms
   std::vector<std::vector<int32_t>> groups;
+  std::vector<int32_t> group_cls;
   std::vector<int32_t> members, uni, merged;
   size_t widest = 0;
+  int32_t cls = 0;
   for (const Q& e : order) {
     const int32_t* a = ids + off[e.q];
     const int n = off[e.q + 1] - off[e.q];
     merged.clear();
     std::set_union(uni.begin(), uni.end(), a, a + n, std::back_inserter(merged));
-    if (!members.empty() && (static_cast<int>(members.size()) >= G || static_cast<int>(merged.size()) > kGrpMaxU)) {
+    if (!members.empty() &&
+        (static_cast<int>(members.size()) >= G || static_cast<int>(merged.size()) > kGrpMaxU || e.cls != cls)) {
       widest = std::max(widest, uni.size());
       groups.push_back(members);
+      group_cls.push_back(cls);
       members.clear();
       merged.assign(a, a + n);
     }
     uni.swap(merged);
     members.push_back(e.q);
+    cls = e.cls;
   }
   if (!members.empty()) {
     widest = std::max(widest, uni.size());
     groups.push_back(members);
+    group_cls.push_back(cls);
   }
   GroupLayout lay;
   lay.n_groups = static_cast<int>(groups.size());
@@ -1616,6 +1641,7 @@ static GroupLayout inv_group_queries(const int32_t* off, const int32_t* ids, int
       i = j;
     }
     hdr[gi * kGrpHdr] = n_u;
+    hdr[gi * kGrpHdr + 1] = group_cls[gi];
     // (unused union entries keep slot -1 and, below, mask 0)
     for (int u = n_u; u < lay.stride_u; ++u) ent[(gi * static_cast<size_t>(lay.stride_u) + static_cast<size_t>(u)) * kGrpEnt + 1] = 0;
   }
@@ -1647,19 +1673,20 @@ int inv_scan_topk(vr_engine* e, const int32_t* q_idx_host, const float* q_val_ho
 // The grouped scan of a batch (see sparse_inv_group_kernel). out_keys_dev: in — the seed lists (sampled == false), out — the
 // nq x k result keys. *done = false: no query of the batch has terms (nothing was launched). Closes the profiler slot.
 static int inv_scan_grouped(vr_engine* e, const float* q_w_dev, int nq, const uint8_t* mask_dev, int k, uint64_t* out_keys_dev,
-                            const int32_t* q_off_host, const int32_t* q_ids_host, bool sampled, bool* done) {
+                            const int32_t* q_off_host, const int32_t* q_ids_host, bool sampled, bool* done,
+                            const ClassPlanes* classes) {
   // (2: 34 KB of LDS and 56 registers — four blocks = 32 waves per CU, the most a CU holds; measured best: the block is a
   // chain of dependent phases and other blocks are what hides them — 2.5 ms of kernels per 1000 queries against 3.0 for
   // groups of 4 at two blocks per CU, although those read fewer postings)
   const int want_group = std::getenv("VR_SPARSE_GROUP") ? atoi(std::getenv("VR_SPARSE_GROUP")) : 2;
-  const int group_size = want_group == 3 || want_group == 4 || want_group == 8 ? want_group : 2;
+  const int group_size = !classes && (want_group == 3 || want_group == 4 || want_group == 8) ? want_group : 2;  // (planes: pairs)
   const int dbg_mode = std::getenv("VR_SPARSE_GROUP_DBG") ? atoi(std::getenv("VR_SPARSE_GROUP_DBG")) : 0;  // timing experiments
   const int64_t n_seg = e->n_inv_seg;
   // keys per (query, segment) region: 32 at a million rows (250 segments), more while the segments are few (a region may
   // then hold most of a query's k best), <= 8192 per query in all
   const int fit_cap = static_cast<int>(std::max<int64_t>(kGrpCandCap, std::min<int64_t>(512, 8192 / std::max<int64_t>(n_seg, 1))));
   const int cand_cap = std::getenv("VR_SPARSE_GROUP_CAP") ? std::min(fit_cap, std::max(1, atoi(std::getenv("VR_SPARSE_GROUP_CAP")))) : fit_cap;
-  const GroupLayout lay = inv_group_queries(q_off_host, q_ids_host, nq, group_size, &e->sq_grp_host);
+  const GroupLayout lay = inv_group_queries(q_off_host, q_ids_host, nq, group_size, &e->sq_grp_host, classes ? classes->q_cls : nullptr);
   *done = lay.n_groups > 0;
   if (!*done) return 0;
   const int64_t n_gu = static_cast<int64_t>(lay.n_groups) * lay.stride_u;
@@ -1699,27 +1726,32 @@ static int inv_scan_grouped(vr_engine* e, const float* q_w_dev, int nq, const ui
                      dim3(static_cast<unsigned>((n_gu + 255) / 256), static_cast<unsigned>(std::min<int64_t>(n_seg, 64))), dim3(256), 0,
                      e->stream, slot_bounds, lay.n_slots, ent, static_cast<int>(n_gu), static_cast<int>(n_seg), q_w_dev, grp_bounds,
                      e->sq_entw.p);
+  const uint32_t* planes = classes ? classes->planes : nullptr;
+  const int64_t plane_words = classes ? classes->plane_words : 0;
   auto launch = [&](auto kernel, int64_t rows_y, uint64_t* cand, int32_t* cnt, int cap, int stride) {
     hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(lay.n_groups), static_cast<unsigned>(rows_y)), dim3(kGrpThreads), 0, e->stream,
                        e->inv_seg.p, e->inv_key.p, e->inv_val.p, hdr, ent, e->sq_entw.p, grp_bounds, lay.stride_u, mask_dev, theta, cand,
-                       cnt, cap, dbg_mode, stride, spill, spill_cnt, kSpillCap, kSampleTail, static_cast<int>(n_seg));
+                       cnt, cap, dbg_mode, stride, spill, spill_cnt, kSpillCap, kSampleTail, static_cast<int>(n_seg), planes,
+                       plane_words);
   };
   if (sampled) {
     // thresholds: the sampled segments scanned in full, the best key of every 512 rows kept; the k-th best of a query's
     // sample (real rows, real scores) is a lower bound of its final k-th best key
-    if (group_size == 2) launch(sparse_inv_group_kernel<2, true>, n_samp, samp_cand, samp_cnt, kSampCap, seg_stride);
-    else if (group_size == 3) launch(sparse_inv_group_kernel<3, true>, n_samp, samp_cand, samp_cnt, kSampCap, seg_stride);
-    else if (group_size == 4) launch(sparse_inv_group_kernel<4, true>, n_samp, samp_cand, samp_cnt, kSampCap, seg_stride);
-    else launch(sparse_inv_group_kernel<8, true>, n_samp, samp_cand, samp_cnt, kSampCap, seg_stride);
+    if (planes) launch(sparse_inv_group_kernel<2, true, true>, n_samp, samp_cand, samp_cnt, kSampCap, seg_stride);
+    else if (group_size == 2) launch(sparse_inv_group_kernel<2, true, false>, n_samp, samp_cand, samp_cnt, kSampCap, seg_stride);
+    else if (group_size == 3) launch(sparse_inv_group_kernel<3, true, false>, n_samp, samp_cand, samp_cnt, kSampCap, seg_stride);
+    else if (group_size == 4) launch(sparse_inv_group_kernel<4, true, false>, n_samp, samp_cand, samp_cnt, kSampCap, seg_stride);
+    else launch(sparse_inv_group_kernel<8, true, false>, n_samp, samp_cand, samp_cnt, kSampCap, seg_stride);
     VR_TRY(topk_select_regions(e, samp_cand, static_cast<int>(n_samp), kSampCap, samp_cnt, nullptr, 0, nullptr, nq, k, out_keys_dev,
                                pin_dev<int32_t>(e, kPinSparseOverflow), nullptr, nullptr));
   }
   hipLaunchKernelGGL(sparse_inv_theta_kernel, dim3(static_cast<unsigned>((lay.n_groups * 8 + 255) / 256)), dim3(256), 0, e->stream, hdr,
                      lay.n_groups, out_keys_dev, k, theta);
-  if (group_size == 2) launch(sparse_inv_group_kernel<2, false>, n_seg, e->sq_cand.p, e->sq_cnt.p, cand_cap, 1);
-  else if (group_size == 3) launch(sparse_inv_group_kernel<3, false>, n_seg, e->sq_cand.p, e->sq_cnt.p, cand_cap, 1);
-  else if (group_size == 4) launch(sparse_inv_group_kernel<4, false>, n_seg, e->sq_cand.p, e->sq_cnt.p, cand_cap, 1);
-  else launch(sparse_inv_group_kernel<8, false>, n_seg, e->sq_cand.p, e->sq_cnt.p, cand_cap, 1);
+  if (planes) launch(sparse_inv_group_kernel<2, false, true>, n_seg, e->sq_cand.p, e->sq_cnt.p, cand_cap, 1);
+  else if (group_size == 2) launch(sparse_inv_group_kernel<2, false, false>, n_seg, e->sq_cand.p, e->sq_cnt.p, cand_cap, 1);
+  else if (group_size == 3) launch(sparse_inv_group_kernel<3, false, false>, n_seg, e->sq_cand.p, e->sq_cnt.p, cand_cap, 1);
+  else if (group_size == 4) launch(sparse_inv_group_kernel<4, false, false>, n_seg, e->sq_cand.p, e->sq_cnt.p, cand_cap, 1);
+  else launch(sparse_inv_group_kernel<8, false, false>, n_seg, e->sq_cand.p, e->sq_cnt.p, cand_cap, 1);
   prof_end(e);
   VR_HIP(hipGetLastError());
   e->stat_sparse_grouped += nq;
@@ -1761,12 +1793,35 @@ static int inv_scan_grouped(vr_engine* e, const float* q_w_dev, int nq, const ui
   return 0;
 }
 
+static bool inv_seeding() {
+  static const bool on = !(std::getenv("VR_SPARSE_SEED") && atoi(std::getenv("VR_SPARSE_SEED")) == 0);
+  return on;
+}
+static bool inv_debug() {
+  static const bool on = std::getenv("VR_SPARSE_DEBUG") && atoi(std::getenv("VR_SPARSE_DEBUG")) != 0;
+  return on;
+}
+// the grouped scan can take nq queries: enough of them, and candidate regions (nq x segments x >= 16 keys) under 2 GB
+static bool inv_grouped_fits(const vr_engine* e, int nq) {
+  return nq >= 16 && e->n_inv_seg <= 65535 &&
+         static_cast<int64_t>(nq) * e->n_inv_seg * std::max<int64_t>(kGrpCandCap, std::min<int64_t>(512, 8192 / std::max<int64_t>(e->n_inv_seg, 1))) <= (int64_t{1} << 28) &&
+         !(std::getenv("VR_SPARSE_GROUPED") && atoi(std::getenv("VR_SPARSE_GROUPED")) == 0);
+}
+// ... with its thresholds from a sample of the segments, once there are enough of them
+static bool inv_sample_fits(const vr_engine* e) {
+  return e->n_inv_seg >= 128 && !(std::getenv("VR_SPARSE_GROUP_SAMPLE") && atoi(std::getenv("VR_SPARSE_GROUP_SAMPLE")) == 0);
+}
+
+bool inv_class_grouped_usable(const vr_engine* e, int nq) {
+  return inv_usable(e, 1) && inv_seeding() && !inv_debug() && inv_grouped_fits(e, nq) && inv_sample_fits(e);
+}
+
 // nq queries in device memory (CSR as sparse_inv_batch_kernel takes it, raw values in q_val_dev) -> nq x k keys in
 // out_keys_dev (device-visible). Queries with an empty term range come out as empty lists.
 int inv_scan_topk_batch(vr_engine* e, const int32_t* q_off_dev, const int32_t* q_ids_dev, const float* q_val_dev,
                         float* q_w_dev, int nq, int n_terms, bool weights_given, float n_points, const uint8_t* mask_dev,
                         int k, uint64_t* out_keys_dev, const int32_t* q_off_host, const int32_t* q_ids_host,
-                        bool allow_grouped) {
+                        bool allow_grouped, const ClassPlanes* classes) {
   VR_CHECK(nq >= 1 && k >= 1 && k <= kListLen, "bad inverted-scan shape");
   *pin_host<int32_t>(e, kPinSparseOverflow) = 0;
   e->stat_sparse_group_cands += *pin_host<int32_t>(e, kPinSparseCands);  // (of the batch before: its stream has been waited for)
@@ -1785,14 +1840,13 @@ int inv_scan_topk_batch(vr_engine* e, const int32_t* q_off_dev, const int32_t* q
   gx = std::min(gx, kScanBlocks);
   const InvForward fw{e->row_slice.p, e->slices.p, e->sp_idx.p, e->sp_val.p};
   const dim3 block(kInvWaves * 64);
-  static const bool seeding = !(std::getenv("VR_SPARSE_SEED") && atoi(std::getenv("VR_SPARSE_SEED")) == 0);
-  const bool pruned = seeding && !weights_given;  // (given weights: the engine does not know the terms' frequencies)
+  const bool pruned = inv_seeding() && !weights_given;  // (given weights: the engine does not know the terms' frequencies)
   const int gs = std::min(gx, 16);  // blocks per query of the seed pass (a few rows per segment: latency, not work)
   VR_TRY(e->sp_cand.grow(static_cast<int64_t>(nq) * std::max(gx, gs) * kListLen, 0, e->stream));
   prof_begin(e, VR_PROF_SPARSE_SCAN, 0.0);
   const uint64_t* seed_keys = nullptr;
   const int32_t* need_full = nullptr;
-  static const bool debug = std::getenv("VR_SPARSE_DEBUG") && atoi(std::getenv("VR_SPARSE_DEBUG")) != 0;
+  const bool debug = inv_debug();
   unsigned long long* dbg = nullptr;
   if (pruned && debug) {
     VR_HIP(hipMalloc(reinterpret_cast<void**>(&dbg), 8 * sizeof(unsigned long long)));
@@ -1802,11 +1856,11 @@ int inv_scan_topk_batch(vr_engine* e, const int32_t* q_off_dev, const int32_t* q
   // (inv_scan_grouped; VR_SPARSE_GROUPED=0 keeps the per-query kernels. The switches are read per call: tests compare the
   // paths, and force an overflow, in one process)
   // (its candidate regions are nq x segments x >= 16 keys: batches whose regions would pass 2 GB stay on the per-query kernels)
-  const bool grouped = pruned && !dbg && allow_grouped && q_off_host && q_ids_host && nq >= 16 && e->n_inv_seg <= 65535 &&
-                       static_cast<int64_t>(nq) * e->n_inv_seg * std::max<int64_t>(kGrpCandCap, std::min<int64_t>(512, 8192 / std::max<int64_t>(e->n_inv_seg, 1))) <= (int64_t{1} << 28) &&
-                       !(std::getenv("VR_SPARSE_GROUPED") && atoi(std::getenv("VR_SPARSE_GROUPED")) == 0);
+  const bool grouped = pruned && !dbg && allow_grouped && q_off_host && q_ids_host && inv_grouped_fits(e, nq);
   // ... with the thresholds from a sample of the segments scanned the same way, once there are enough of them
-  const bool sampled = grouped && e->n_inv_seg >= 128 && !(std::getenv("VR_SPARSE_GROUP_SAMPLE") && atoi(std::getenv("VR_SPARSE_GROUP_SAMPLE")) == 0);
+  const bool sampled = grouped && inv_sample_fits(e);
+  // (a filtered batch's classes: only the sampled grouped scan reads planes — the caller asks inv_class_grouped_usable)
+  VR_CHECK(!classes || sampled, "the grouped sparse scan cannot take this filtered batch");
   if (pruned && !sampled) {
     // 1. seed: per query the k best rows among those that carry its rarest terms, scored exactly -> out_keys_dev; the
     //    k-th of them is a lower bound of the final k-th best score (real rows, real scores)
@@ -1819,7 +1873,7 @@ int inv_scan_topk_batch(vr_engine* e, const int32_t* q_off_dev, const int32_t* q
   }
   if (grouped) {
     bool done = false;
-    VR_TRY(inv_scan_grouped(e, q_w_dev, nq, mask_dev, k, out_keys_dev, q_off_host, q_ids_host, sampled, &done));
+    VR_TRY(inv_scan_grouped(e, q_w_dev, nq, mask_dev, k, out_keys_dev, q_off_host, q_ids_host, sampled, &done, classes));
     if (done) return 0;
     VR_CHECK(!sampled, "the grouped scan found no query with terms");  // (n_terms > 0 here: cannot happen)
   }

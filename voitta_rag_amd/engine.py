@@ -46,6 +46,19 @@ class SearchFilter:
         return (self.folder_filter is None and self.include_folders is None and not self.exclude_folders
                 and not self.exclude_index_folders and self.date_start is None and self.date_end is None)
 
+    def key(self):
+        """Hashable identity of the predicate: equal keys select the same rows (the id lists are sets; the date field
+        only matters with a date bound). None for an empty filter. The filtered batches group queries by it."""
+        if self.is_empty():
+            return None
+        has_date = self.date_start is not None or self.date_end is not None
+        return (None if self.folder_filter is None else int(self.folder_filter),
+                None if self.include_folders is None else frozenset(self.include_folders),
+                frozenset(self.exclude_folders), frozenset(self.exclude_index_folders),
+                None if self.date_start is None else int(self.date_start),
+                None if self.date_end is None else int(self.date_end),
+                has_date and self.date_field == "created")
+
     def to_c(self):
         """-> (VrFilter, keepalive) ; keepalive holds the arrays the struct points into."""
         sets = []
@@ -508,6 +521,103 @@ class Engine:
                                                _ptr(val, C.c_float), limit, float(sparse_weight), fusion, fp,
                                                _ptr(rows, C.c_int64), _ptr(scores, C.c_double), _ptr(fd, C.c_int32),
                                                _ptr(counts, C.c_int32)))
+        del keep, keepq
+        if raw:
+            return rows, scores, fd, counts
+        return [(rows[i, : counts[i]].copy(), scores[i, : counts[i]].copy(), fd[i, : counts[i]].copy()) for i in range(nq)]
+
+    @staticmethod
+    def _filter_classes(filters, nq: int):
+        """One SearchFilter | None per query -> (VrFilter array of the distinct non-empty filters, their number,
+        int32 filter_of_query (-1: none), keepalive)."""
+        filters = list(filters)
+        if len(filters) != nq:
+            raise ValueError(f"{len(filters)} filters for {nq} queries")
+        index: dict = {}
+        known: dict = {}  # id(filter) -> key: a filter object shared by many queries is keyed once
+        distinct = []
+        foq = np.full(nq, -1, np.int32)
+        for i, f in enumerate(filters):
+            if f is None:
+                continue
+            key = known[id(f)] if id(f) in known else known.setdefault(id(f), f.key())
+            if key is None:
+                continue
+            j = index.get(key)
+            if j is None:
+                j = index[key] = len(distinct)
+                distinct.append(f)
+            foq[i] = j
+        # the id arrays of every distinct filter in four shared arrays, each struct pointing into them (to_c's layout;
+        # one small array per field and filter costs ~50 us a filter, the bulk of a 1000-filter batch)
+        must, must_off, nots, not_if, at = [], [], [], [], []
+        for f in distinct:
+            sets = ([[f.folder_filter]] if f.folder_filter is not None else []) + \
+                   ([f.include_folders] if f.include_folders is not None else [])
+            m0 = len(must)
+            at.append((m0, len(must_off), len(nots), len(not_if), len(sets)))
+            must_off.append(0)
+            for st in sets:
+                must.extend(st)
+                must_off.append(len(must) - m0)
+            nots.extend(f.exclude_folders)
+            not_if.extend(f.exclude_index_folders)
+        arrays = [_np(a, np.int32) for a in (must, must_off, nots, not_if)]
+        base = [a.ctypes.data for a in arrays]
+        p32 = C.POINTER(C.c_int32)
+        arr = (_lib.VrFilter * max(1, len(distinct)))()
+        for j, (f, (m0, o0, n0, i0, n_sets)) in enumerate(zip(distinct, at)):
+            c = arr[j]
+            c.struct_size = C.sizeof(_lib.VrFilter)
+            c.n_must_folder_sets = n_sets
+            c.must_folder_ids = C.cast(base[0] + 4 * m0, p32)
+            c.must_folder_off = C.cast(base[1] + 4 * o0, p32)
+            c.not_folder_ids = C.cast(base[2] + 4 * n0, p32)
+            c.n_not_folder = len(f.exclude_folders)
+            c.n_not_index_folder = len(f.exclude_index_folders)
+            c.not_index_folder_ids = C.cast(base[3] + 4 * i0, p32)
+            c.has_date_start = int(f.date_start is not None)
+            c.has_date_end = int(f.date_end is not None)
+            c.date_start = int(f.date_start or 0)
+            c.date_end = int(f.date_end or 0)
+            c.date_field = 1 if f.date_field == "created" else 0
+        return arr, len(distinct), foq, (arr, arrays, foq)
+
+    def search_dense_multi(self, queries, k: int, filters, raw: bool = False):
+        """search_dense with a filter per query (filters: one SearchFilter | None per query) in ONE call: result i is
+        search_dense(queries[i], k, filters[i]). Equal filters form one class; the batched scan reads a bit plane per
+        class (vr_search_dense_multi)."""
+        mem, nq, qp, keepq = self._queries(queries)
+        farr, nf, foq, keep = self._filter_classes(filters, nq)
+        rows = np.empty((nq, k), np.int64)
+        scores = np.empty((nq, k), np.float32)
+        counts = np.zeros(nq, np.int32)
+        check(self._lib.vr_search_dense_multi(self._h, qp, nq, mem, k, farr, nf, _ptr(foq, C.c_int32), _ptr(rows, C.c_int64),
+                                              _ptr(scores, C.c_float), _ptr(counts, C.c_int32)))
+        del keep, keepq
+        if raw:
+            return rows, scores, counts
+        return [(rows[i, : counts[i]].copy(), scores[i, : counts[i]].copy()) for i in range(nq)]
+
+    def search_hybrid_batch_multi(self, queries, sparse_queries, limits, sparse_weights, filters,
+                                  fusion: int = VR_FUSION_MINMAX, raw: bool = False):
+        """search_hybrid_batch with a limit, a sparse weight and a filter per query (vr_search_hybrid_batch_multi):
+        result i is search_hybrid(queries[i], *sparse_queries[i], limits[i], sparse_weights[i], fusion, filters[i]).
+        raw=True: the (nq, max(limits)) arrays and the counts instead of the list."""
+        mem, nq, qp, keepq = self._queries(queries)
+        off, idx, val = self._sparse_csr(sparse_queries, nq)
+        lim = _np(np.broadcast_to(np.asarray(limits), (nq,)), np.int32)
+        wts = _np(np.broadcast_to(np.asarray(sparse_weights, dtype=np.float64), (nq,)), np.float64)
+        farr, nf, foq, keep = self._filter_classes(filters, nq)
+        stride = max(1, int(lim.max()) if nq else 1)
+        rows = np.empty((nq, stride), np.int64)
+        scores = np.empty((nq, stride), np.float64)
+        fd = np.empty((nq, stride), np.int32)
+        counts = np.zeros(nq, np.int32)
+        check(self._lib.vr_search_hybrid_batch_multi(self._h, qp, nq, mem, _ptr(off, C.c_int64), _ptr(idx, C.c_int32),
+                                                     _ptr(val, C.c_float), _ptr(lim, C.c_int32), _ptr(wts, C.c_double),
+                                                     fusion, farr, nf, _ptr(foq, C.c_int32), stride, _ptr(rows, C.c_int64),
+                                                     _ptr(scores, C.c_double), _ptr(fd, C.c_int32), _ptr(counts, C.c_int32)))
         del keep, keepq
         if raw:
             return rows, scores, fd, counts

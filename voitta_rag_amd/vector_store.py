@@ -816,14 +816,7 @@ class VectorStoreService:
             rows, scores = self._search_consistent(col, run_text, folder_filter, include_folders, exclude_folders,
                                                    exclude_index_folders, date_start, date_end, date_field)
             return [self._chunk_from(pid, payload, s) for (pid, payload), s in zip(rows, scores) if payload is not None]
-        kept = getattr(query_embedding, "array", None) if isinstance(query_embedding, (_deferred.QueryEmbedding, _deferred.QueryRef)) else None
-        if isinstance(query_embedding, _deferred.QueryRef):
-            q = kept.reshape(self.dimension)
-        elif (kept is not None and len(query_embedding) == kept.size == self.dimension
-                and query_embedding[0] == float(kept[0]) and query_embedding[-1] == float(kept[-1])):  # (not edited since)
-            q = kept.reshape(self.dimension)  # (embed_query's own array; the list was not needed)
-        else:
-            q = np.asarray(query_embedding, dtype=np.float32).reshape(self.dimension)
+        q = self._query_array(query_embedding)
         hybrid = bool(sparse_query and self._has_sparse and sparse_query[0])
 
         def run(search_filter):
@@ -838,11 +831,27 @@ class VectorStoreService:
                                                date_start, date_end, date_field)
         return [self._chunk_from(pid, payload, s) for (pid, payload), s in zip(rows, scores) if payload is not None]
 
+    def _query_array(self, query_embedding) -> np.ndarray:
+        """The (D,) f32 query of a search: embed_query's own array when the list was not edited since, else the list."""
+        kept = getattr(query_embedding, "array", None) if isinstance(query_embedding, (_deferred.QueryEmbedding, _deferred.QueryRef)) else None
+        if isinstance(query_embedding, _deferred.QueryRef):
+            return kept.reshape(self.dimension)
+        if (kept is not None and len(query_embedding) == kept.size == self.dimension
+                and query_embedding[0] == float(kept[0]) and query_embedding[-1] == float(kept[-1])):  # (not edited since)
+            return kept.reshape(self.dimension)  # (embed_query's own array; the list was not needed)
+        return np.asarray(query_embedding, dtype=np.float32).reshape(self.dimension)
+
     _SEARCH_DEADLINE_S = float(os.environ.get("VOITTA_SEARCH_DEADLINE_S", "30"))
 
     def _search_consistent(self, col: _Collection, run, folder_filter, include_folders, exclude_folders, exclude_index_folders,
                            date_start, date_end, date_field):
-        """Runs ``run(filter) -> (rows, extra)`` against a consistent pair of engine state and host table and returns
+        """``_consistent`` of one filter built from ``search``'s arguments."""
+        return self._consistent(col, run, lambda: self._build_filter(folder_filter, include_folders, exclude_folders,
+                                                                     exclude_index_folders, date_start=date_start,
+                                                                     date_end=date_end, date_field=date_field))
+
+    def _consistent(self, col: _Collection, run, build):
+        """Runs ``run(build()) -> (rows, extra)`` against a consistent pair of engine state and host table and returns
         ([(point id, payload)] for the rows, extra). The engine call holds no Python lock (searches of several threads
         run side by side on the engine's lanes); a delete or a compaction that finished meanwhile (rows gone or
         renumbered) makes the search look again — its answer then belongs to the later state. While a compaction has
@@ -852,9 +861,8 @@ class VectorStoreService:
         deadline = time.monotonic() + self._SEARCH_DEADLINE_S
         has_generation = hasattr(self._engine, "generation")
         while True:
-            with col.lock:
-                search_filter = self._build_filter(folder_filter, include_folders, exclude_folders, exclude_index_folders,
-                                                   date_start=date_start, date_end=date_end, date_field=date_field)
+            with col.lock:  # (every filter ``build`` makes sees the same dictionaries)
+                search_filter = build()
                 version, generation = col.version, col.generation
             if has_generation and self._engine.generation() != generation:
                 if time.monotonic() > deadline:
@@ -920,6 +928,63 @@ class VectorStoreService:
             base = i * limit
             out.append([self._chunk_from(pid, payload, s) for (pid, payload), s in zip(pairs[base: base + int(counts[i])], scores[i])
                         if payload is not None])
+        return out
+
+    _FILTER_ARGS = ("folder_filter", "include_folders", "exclude_folders", "exclude_index_folders", "date_start", "date_end",
+                    "date_field")
+
+    def search_requests(self, requests: list[dict]) -> list[list[StoredChunk]]:
+        """Many independent ``search`` calls in one engine call each for the hybrid and the dense-only ones: requests[i]
+        holds the keyword arguments of ``search`` and result i is ``search(**requests[i])`` — its own filter, limit and
+        sparse weight, the same branch selection (hybrid only with sparse terms), ``limit <= 0 -> []`` and the same score
+        transport. What concurrent MCP ``search`` calls of many users (mcp_server.py:374-485) can share: the dense legs
+        scan the corpus once for all filters (vr_search_hybrid_batch_multi / vr_search_dense_multi). Every filter is built
+        under one lock, so every request sees the same state of the collection."""
+        n = len(requests)
+        out: list[list[StoredChunk]] = [[] for _ in range(n)]
+        live = [i for i in range(n) if int(requests[i].get("limit", 10)) > 0]
+        if not live:
+            return out
+        col = self._col
+        self._drain(col, surface_errors=False)
+        q = np.stack([self._query_array(requests[i]["query_embedding"]) for i in live]).astype(np.float32, copy=False)
+        limits = [int(requests[i].get("limit", 10)) for i in live]
+        sparse = []
+        for i in live:
+            sp = requests[i].get("sparse_query")
+            sparse.append((sp[0], sp[1]) if (sp and self._has_sparse and sp[0]) else None)
+        hyb = [j for j in range(len(live)) if sparse[j] is not None]
+        dns = [j for j in range(len(live)) if sparse[j] is None]
+
+        def build():
+            return [self._build_filter(**{a: requests[i].get(a) for a in self._FILTER_ARGS}) for i in live]
+
+        def run(filters):
+            rows, scores = [None] * len(live), [None] * len(live)
+            if hyb:
+                r, s, _fd, c = self._engine.search_hybrid_batch_multi(
+                    q[hyb], [sparse[j] for j in hyb], [limits[j] for j in hyb],
+                    [float(requests[live[j]].get("sparse_weight", 0.1)) for j in hyb], [filters[j] for j in hyb], raw=True)
+                for t, j in enumerate(hyb):
+                    rows[j] = r[t, : c[t]]
+                    scores[j] = [float(v) for v in s[t, : c[t]]]
+            if dns:
+                k = max(limits[j] for j in dns)  # (exact top-k lists: the first limit of k are the top limit)
+                r, s, c = self._engine.search_dense_multi(q[dns], k, [filters[j] for j in dns], raw=True)
+                for t, j in enumerate(dns):
+                    m = min(int(c[t]), limits[j])
+                    rows[j] = r[t, :m]
+                    scores[j] = [_json_float(v) for v in s[t, :m]]
+            counts = [len(x) for x in rows]
+            flat = np.concatenate([np.asarray(x, np.int64) for x in rows])
+            return flat, (counts, scores)
+
+        pairs, (counts, scores) = self._consistent(col, run, build)
+        at = 0
+        for j, i in enumerate(live):
+            mine = pairs[at: at + counts[j]]
+            at += counts[j]
+            out[i] = [self._chunk_from(pid, payload, s) for (pid, payload), s in zip(mine, scores[j]) if payload is not None]
         return out
 
     # ---- read helpers (payload only) ---------------------------------------------------------------
