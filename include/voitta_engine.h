@@ -439,6 +439,22 @@ int vr_query_text(vr_engine* e, const vr_wordpiece* tokenizer, const char* dense
                   int32_t fusion, const vr_filter* filter,
                   int64_t* out_rows, double* out_scores, int32_t* out_from_dense, int32_t* out_count, int32_t* out_hybrid);
 
+/* n questions as TEXT in one call, each with its own filter, limit and sparse weight: row i is what vr_query_text
+ * returns for question i (dense_texts[i], sparse_texts[i], limits[i], sparse_weights[i], fusion,
+ * filters[filter_of_query[i]] or none for -1), in branch and score alike. sparse_texts may be NULL, and so may an
+ * entry of it (length 0 likewise): no sparse leg for that question. One forward pass over all n questions (the
+ * embeddings are those vr_encode gives for the same tokenised list) whose rows stay in device memory and feed the
+ * filtered batch searches of vr_search_hybrid_batch_multi (questions with a stem) and vr_search_dense_multi (the
+ * others). out_rows / out_scores / out_from_dense: n x out_stride (out_stride >= every limit; entries beyond
+ * out_counts[i] are unspecified); out_hybrid[n] (may be NULL) says which branch ran; out_embeddings (n x hidden f32,
+ * host; may be NULL) receives the embeddings. Arguments are checked before any device work; n = 0 does nothing. */
+int vr_query_text_batch(vr_engine* e, const vr_wordpiece* tokenizer, int32_t n, const char* const* dense_texts,
+                        const int64_t* dense_lens, const char* const* sparse_texts, const int64_t* sparse_lens,
+                        int32_t max_len, const int32_t* limits, const double* sparse_weights, int32_t fusion,
+                        const vr_filter* filters, int32_t n_filters, const int32_t* filter_of_query, int32_t out_stride,
+                        int64_t* out_rows, double* out_scores, int32_t* out_from_dense, int32_t* out_counts,
+                        int32_t* out_hybrid, float* out_embeddings);
+
 /* Persistence. The reference's index survives a restart in Qdrant's volume
  * (docker-compose.yml:8-9; VectorStoreService._ensure_collection re-attaches, vector_store.py:75-115).
  * vr_save writes everything the device owns — tiled dense corpus, payload columns, tombstones,

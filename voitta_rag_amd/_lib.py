@@ -142,6 +142,9 @@ SIGNATURES = {
     "vr_df_apply": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int64, C.c_int32]),
     "vr_query_text": (C.c_int, [_vp, _vp, C.c_char_p, C.c_int64, C.c_char_p, C.c_int64, C.c_int32, C.c_int32, C.c_double,
                                 C.c_int32, C.POINTER(VrFilter), _i64p, _dp, _i32p, _i32p, _i32p]),
+    "vr_query_text_batch": (C.c_int, [_vp, _vp, C.c_int32, C.POINTER(C.c_char_p), _i64p, C.POINTER(C.c_char_p), _i64p,
+                                      C.c_int32, _i32p, _dp, C.c_int32, C.POINTER(VrFilter), C.c_int32, _i32p, C.c_int32,
+                                      _i64p, _dp, _i32p, _i32p, _i32p, _fp]),
 }
 
 

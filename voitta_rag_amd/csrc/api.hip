@@ -172,6 +172,9 @@ static void release_scratch(vr_engine* e) {
   e->bq_tile_ub.release();
   e->bq_pairs.release();
   e->bq_stage.release();
+  e->qt_emb.release();
+  e->qt_pick.release();
+  e->qt_gather.release();
   e->cls_planes.release();
   e->cls_of_q.release();
   e->cls_pass.release();
@@ -1447,6 +1450,58 @@ int multi_host_queries(vr_engine* e, const float* q, int nq, int mem, std::vecto
   return 0;
 }
 
+// The dense leg of a filtered batch on lane L (vr_search_dense_multi after its checks): nq x k keys to keys_host.
+int dense_multi_keys(vr_engine* L, const float* q, int nq, int mem, int k, const QueryClasses& qc, uint64_t* keys_host) {
+  if (qc.filter.size() == 1)  // one class: vr_search_dense
+    return search_dense_keys_locked(L, q, nq, mem, k, qc.filter[0], keys_host, nullptr);
+  std::vector<float> copy;
+  const float* qh = nullptr;
+  VR_TRY(multi_host_queries(L, q, nq, mem, &copy, &qh));
+  const std::vector<int32_t> ks(static_cast<size_t>(nq), k);
+  return multi_keys_locked(L, qh, nq, ks.data(), k, qc, nullptr, nullptr, nullptr, keys_host, nullptr);
+}
+
+// Both legs of a filtered hybrid batch on lane L (vr_search_hybrid_batch_multi after its checks): query i asks for
+// 3 x limits[i] keys per leg; nq x kstride keys to dense / sparse.
+int hybrid_multi_keys(vr_engine* L, const float* q, int nq, int mem, const int64_t* sq_off, const int32_t* sq_idx,
+                      const float* sq_val, const int32_t* limits, const QueryClasses& qc, int kstride, uint64_t* dense,
+                      uint64_t* sparse) {
+  if (qc.filter.size() == 1)  // one class: vr_search_hybrid_batch's legs, at the largest k
+    return hybrid_keys_locked(L, q, nq, mem, sq_off, sq_idx, sq_val, kstride, false, qc.filter[0], dense, sparse);
+  std::vector<int32_t> ks(static_cast<size_t>(nq));
+  for (int i = 0; i < nq; ++i) ks[static_cast<size_t>(i)] = 3 * limits[i];
+  std::vector<float> copy;
+  const float* qh = nullptr;
+  VR_TRY(multi_host_queries(L, q, nq, mem, &copy, &qh));
+  return multi_keys_locked(L, qh, nq, ks.data(), kstride, qc, sq_off, sq_idx, sq_val, dense, sparse);
+}
+
+// Fusion of every query of a filtered hybrid batch on the host threads, each with its own limit and weight
+// (vector_store.py:659-697). Query i's answer goes to output row out_row[i] (out_row null: row i).
+int fuse_multi(const uint64_t* dense, const uint64_t* sparse, int nq, int kstride, const int32_t* limits,
+               const double* sparse_weights, int32_t fusion, const int32_t* out_row, int32_t out_stride, int64_t* out_rows,
+               double* out_scores, int32_t* out_from_dense, int32_t* out_counts) {
+  std::atomic<int> failed{0};
+  parallel_for(nq, 8, [&](int64_t i) {
+    const int k = 3 * limits[i], limit = limits[i];
+    int64_t d_rows[kMaxK], s_rows[kMaxK];
+    float d_scores[kMaxK], s_scores[kMaxK];
+    const int nd = static_cast<int>(decode_keys(dense + static_cast<size_t>(i) * kstride, k, d_rows, d_scores));
+    const int ns = static_cast<int>(decode_keys(sparse + static_cast<size_t>(i) * kstride, k, s_rows, s_scores));
+    const int64_t r = out_row ? out_row[i] : i;
+    const int64_t at = r * out_stride;
+    int32_t* fd = out_from_dense ? out_from_dense + at : nullptr;
+    const int rc = fusion == VR_FUSION_MINMAX
+                       ? fuse_minmax(d_rows, d_scores, nd, s_rows, s_scores, ns, limit, sparse_weights[i], 1, out_rows + at,
+                                     out_scores + at, fd, out_counts + r)
+                       : fuse_rrf(d_rows, nd, s_rows, ns, limit, sparse_weights[i], out_rows + at, out_scores + at, fd,
+                                  out_counts + r);
+    if (rc != 0) failed.store(1);
+  });
+  VR_CHECK(!failed.load(), "fusion failed");
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1464,15 +1519,7 @@ int vr_search_dense_multi(vr_engine* e, const float* q, int32_t nq, int mem, int
   {
     SearchLane lane(e);
     VR_TRY(lane.acquire(mem == VR_MEM_DEVICE));
-    if (qc.filter.size() == 1) {  // one class: vr_search_dense
-      VR_TRY(search_dense_keys_locked(lane.L, q, nq, mem, k, qc.filter[0], keys.data(), nullptr));
-    } else {
-      std::vector<float> copy;
-      const float* qh = nullptr;
-      VR_TRY(multi_host_queries(lane.L, q, nq, mem, &copy, &qh));
-      const std::vector<int32_t> ks(static_cast<size_t>(nq), k);
-      VR_TRY(multi_keys_locked(lane.L, qh, nq, ks.data(), k, qc, nullptr, nullptr, nullptr, keys.data(), nullptr));
-    }
+    VR_TRY(dense_multi_keys(lane.L, q, nq, mem, k, qc, keys.data()));
   }
   for (int i = 0; i < nq; ++i) {
     const int64_t c = decode_keys(keys.data() + static_cast<size_t>(i) * k, k, rows + static_cast<int64_t>(i) * k,
@@ -1507,42 +1554,15 @@ int vr_search_hybrid_batch_multi(vr_engine* e, const float* q, int32_t nq, int m
   VR_TRY(classify_queries(filters, n_filters, filter_of_query, nq, &qc));
   VR_TRY(check_engine(e));
   const int kstride = 3 * max_limit;  // prefetch_limit, vector_store.py:636, of the largest limit
-  std::vector<int32_t> ks(static_cast<size_t>(nq));
-  for (int i = 0; i < nq; ++i) ks[static_cast<size_t>(i)] = 3 * limits[i];
   const size_t per = static_cast<size_t>(nq) * kstride;
   std::vector<uint64_t> dense(per), sparse(per);
   {
     SearchLane lane(e);
     VR_TRY(lane.acquire(mem == VR_MEM_DEVICE));
-    if (qc.filter.size() == 1) {  // one class: vr_search_hybrid_batch's legs, at the largest k
-      VR_TRY(hybrid_keys_locked(lane.L, q, nq, mem, sq_off, sq_idx, sq_val, kstride, false, qc.filter[0], dense.data(),
-                                sparse.data()));
-    } else {
-      std::vector<float> copy;
-      const float* qh = nullptr;
-      VR_TRY(multi_host_queries(lane.L, q, nq, mem, &copy, &qh));
-      VR_TRY(multi_keys_locked(lane.L, qh, nq, ks.data(), kstride, qc, sq_off, sq_idx, sq_val, dense.data(), sparse.data()));
-    }
+    VR_TRY(hybrid_multi_keys(lane.L, q, nq, mem, sq_off, sq_idx, sq_val, limits, qc, kstride, dense.data(), sparse.data()));
   }
-  // fusion of every query on the host threads, each with its own limit and weight (vector_store.py:659-697)
-  std::atomic<int> failed{0};
-  parallel_for(nq, 8, [&](int64_t i) {
-    const int k = ks[static_cast<size_t>(i)], limit = limits[i];
-    int64_t d_rows[kMaxK], s_rows[kMaxK];
-    float d_scores[kMaxK], s_scores[kMaxK];
-    const int nd = static_cast<int>(decode_keys(dense.data() + static_cast<size_t>(i) * kstride, k, d_rows, d_scores));
-    const int ns = static_cast<int>(decode_keys(sparse.data() + static_cast<size_t>(i) * kstride, k, s_rows, s_scores));
-    const int64_t at = i * out_stride;
-    int32_t* fd = out_from_dense ? out_from_dense + at : nullptr;
-    const int rc = fusion == VR_FUSION_MINMAX
-                       ? fuse_minmax(d_rows, d_scores, nd, s_rows, s_scores, ns, limit, sparse_weights[i], 1, out_rows + at,
-                                     out_scores + at, fd, out_counts + i)
-                       : fuse_rrf(d_rows, nd, s_rows, ns, limit, sparse_weights[i], out_rows + at, out_scores + at, fd,
-                                  out_counts + i);
-    if (rc != 0) failed.store(1);
-  });
-  VR_CHECK(!failed.load(), "fusion failed");
-  return 0;
+  return fuse_multi(dense.data(), sparse.data(), nq, kstride, limits, sparse_weights, fusion, nullptr, out_stride, out_rows,
+                    out_scores, out_from_dense, out_counts);
 }
 
 int vr_search_sparse_batch(vr_engine* e, const int64_t* q_off, const int32_t* q_idx, const float* q_val, int32_t nq,
@@ -1759,6 +1779,75 @@ void give_query_row(int device, float* p) {
   q.free_rows.push_back(p);
 }
 
+// WordPiece ids of n (prefixed) questions, packed: ids and n + 1 offsets as vr_encode takes them (host threads)
+int question_wordpieces(const vr_wordpiece* tokenizer, const char* const* texts, const int64_t* lens, int n, int max_len,
+                        std::vector<int32_t>* ids, std::vector<int32_t>* off32) {
+  std::vector<int64_t> off(static_cast<size_t>(n) + 1, 0);
+  ids->resize(static_cast<size_t>(n) * max_len);
+  int64_t needed = 0;
+  VR_TRY(vr_wordpiece_encode(tokenizer, texts, lens, n, max_len, off.data(), ids->data(), static_cast<int64_t>(ids->size()),
+                             &needed));
+  VR_CHECK(needed <= INT32_MAX, "%lld tokens", static_cast<long long>(needed));
+  ids->resize(static_cast<size_t>(needed));
+  off32->resize(static_cast<size_t>(n) + 1);
+  for (int i = 0; i <= n; ++i) (*off32)[static_cast<size_t>(i)] = static_cast<int32_t>(off[static_cast<size_t>(i)]);
+  return 0;
+}
+
+// The hashed BM25 stems of n raw questions (Bm25.query_embed: the SET of them, every value 1.0 — SURVEY.md a7) as a
+// CSR: per question ascending and distinct. A null text or length 0 has none. Host threads.
+int question_stems(const char* const* texts, const int64_t* lens, int n, std::vector<int64_t>* off,
+                   std::vector<int32_t>* stems) {
+  static const char kEmpty[1] = {0};
+  std::vector<const char*> t(static_cast<size_t>(n));
+  std::vector<int64_t> l(static_cast<size_t>(n));
+  int64_t cap = 0;
+  for (int i = 0; i < n; ++i) {
+    const bool some = texts && texts[i] && lens[i] > 0;
+    t[static_cast<size_t>(i)] = some ? texts[i] : kEmpty;
+    l[static_cast<size_t>(i)] = some ? lens[i] : 0;
+    cap += l[static_cast<size_t>(i)] / 2 + 2;
+  }
+  off->assign(static_cast<size_t>(n) + 1, 0);
+  stems->resize(static_cast<size_t>(cap));
+  int64_t need = 0;
+  int rc = vr_bm25_tokenize(t.data(), l.data(), n, off->data(), stems->data(), cap, &need);
+  if (rc == -2) {
+    stems->resize(static_cast<size_t>(need));
+    rc = vr_bm25_tokenize(t.data(), l.data(), n, off->data(), stems->data(), need, &need);
+  }
+  VR_TRY(rc);
+  // sort and deduplicate each question's range in place, then close the gaps
+  std::vector<int64_t> kept(static_cast<size_t>(n));
+  parallel_for(n, 64, [&](int64_t i) {
+    int32_t* b = stems->data() + (*off)[static_cast<size_t>(i)];
+    int32_t* e = stems->data() + (*off)[static_cast<size_t>(i) + 1];
+    std::sort(b, e);
+    kept[static_cast<size_t>(i)] = std::unique(b, e) - b;
+  });
+  int64_t at = 0;
+  for (int i = 0; i < n; ++i) {
+    VR_CHECK(kept[static_cast<size_t>(i)] <= kMaxQueryTerms, "query with %lld distinct terms",
+             static_cast<long long>(kept[static_cast<size_t>(i)]));
+    const int64_t from = (*off)[static_cast<size_t>(i)];
+    if (at != from) memmove(stems->data() + at, stems->data() + from, sizeof(int32_t) * static_cast<size_t>(kept[static_cast<size_t>(i)]));
+    (*off)[static_cast<size_t>(i)] = at;
+    at += kept[static_cast<size_t>(i)];
+  }
+  (*off)[static_cast<size_t>(n)] = at;
+  stems->resize(static_cast<size_t>(at));
+  return 0;
+}
+
+// rows pick[0 .. n) of src (n_src x dim) side by side in dst (n x dim); device arrays
+__global__ __launch_bounds__(256) void gather_query_rows_kernel(const float* __restrict__ src, const int32_t* __restrict__ pick,
+                                                                int64_t n, int dim, float* __restrict__ dst) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= n * dim) return;
+  const int64_t r = i / dim;
+  dst[i] = src[static_cast<int64_t>(pick[r]) * dim + (i - r * dim)];
+}
+
 }  // namespace
 
 extern "C" {
@@ -1776,29 +1865,18 @@ int vr_query_text(vr_engine* e, const vr_wordpiece* tokenizer, const char* dense
   if (out_hybrid) *out_hybrid = 0;
   // 1. host: WordPiece ids of the (prefixed) query, hashed BM25 stems of the raw query (Bm25.query_embed: the SET of
   //    them, every value 1.0 — SURVEY.md a7)
-  std::vector<int32_t> wp(static_cast<size_t>(max_len));
-  int64_t wp_off[2] = {0, 0}, needed = 0;
+  std::vector<int32_t> wp, off32;
   {
     const char* texts[1] = {dense_text};
     const int64_t lens[1] = {dense_len};
-    VR_TRY(vr_wordpiece_encode(tokenizer, texts, lens, 1, max_len, wp_off, wp.data(), max_len, &needed));
+    VR_TRY(question_wordpieces(tokenizer, texts, lens, 1, max_len, &wp, &off32));
   }
   std::vector<int32_t> stems;
-  if (sparse_text && sparse_len > 0) {
-    stems.resize(static_cast<size_t>(sparse_len / 2 + 2));
+  {
     const char* texts[1] = {sparse_text};
     const int64_t lens[1] = {sparse_len};
-    int64_t off[2] = {0, 0}, need = 0;
-    int rc = vr_bm25_tokenize(texts, lens, 1, off, stems.data(), static_cast<int64_t>(stems.size()), &need);
-    if (rc == -2) {
-      stems.resize(static_cast<size_t>(need));
-      rc = vr_bm25_tokenize(texts, lens, 1, off, stems.data(), static_cast<int64_t>(stems.size()), &need);
-    }
-    VR_TRY(rc);
-    stems.resize(static_cast<size_t>(need));
-    std::sort(stems.begin(), stems.end());
-    stems.erase(std::unique(stems.begin(), stems.end()), stems.end());
-    VR_CHECK(static_cast<int>(stems.size()) <= kMaxQueryTerms, "query with %zu distinct terms", stems.size());
+    std::vector<int64_t> off;
+    VR_TRY(question_stems(texts, lens, 1, &off, &stems));
   }
   // 2. the embedding, left in device memory (the encoder is shared with the writers: one forward pass at a time)
   VR_CHECK(encoder_hidden(e) == e->dim, "encoder width %d != store dimension %d", encoder_hidden(e), e->dim);
@@ -1809,7 +1887,6 @@ int vr_query_text(vr_engine* e, const vr_wordpiece* tokenizer, const char* dense
     float* p;
     ~Giver() { give_query_row(device, p); }
   } giver{e->device, q_dev};
-  const int32_t off32[2] = {0, static_cast<int32_t>(wp_off[1])};
   const bool hybrid = !stems.empty();
   if (out_hybrid) *out_hybrid = hybrid ? 1 : 0;
   // (VR_QUERY_TEXT_LANE_FIRST=0: the forward pass, then vr_search_hybrid as a caller would — the round's earlier form, for A/B timings)
@@ -1835,7 +1912,7 @@ int vr_query_text(vr_engine* e, const vr_wordpiece* tokenizer, const char* dense
     // holds every CU beside them slows each of them (profiles/r03_experiments.md §13).
     const bool ahead = L->n_slices_dev > 0 && k <= kFusedMaxK && getenv("VR_QUERY_TEXT_AHEAD") && atoi(getenv("VR_QUERY_TEXT_AHEAD")) != 0;
     if (ahead) VR_TRY(hybrid_sparse_ahead(L, stems.data(), ones.data(), nnz, k, mask, false));
-    VR_TRY(encoder_encode(e, wp.data(), off32, 1, VR_MEM_HOST, q_dev, VR_MEM_DEVICE));  // (returns with the stream drained)
+    VR_TRY(encoder_encode(e, wp.data(), off32.data(), 1, VR_MEM_HOST, q_dev, VR_MEM_DEVICE));  // (returns with the stream drained)
     writer.unlock();
     bool have_sparse = false;
     VR_TRY(hybrid_one_query(L, q_dev, VR_MEM_DEVICE, stems.data(), ones.data(), nnz, k, false, mask, &have_sparse, ahead));
@@ -1850,7 +1927,7 @@ int vr_query_text(vr_engine* e, const vr_wordpiece* tokenizer, const char* dense
   }
   {
     std::lock_guard<std::mutex> writer(e->wmu);
-    VR_TRY(encoder_encode(e, wp.data(), off32, 1, VR_MEM_HOST, q_dev, VR_MEM_DEVICE));  // (returns with the stream drained)
+    VR_TRY(encoder_encode(e, wp.data(), off32.data(), 1, VR_MEM_HOST, q_dev, VR_MEM_DEVICE));  // (returns with the stream drained)
   }
   if (hybrid) {
     std::vector<float> ones(stems.size(), 1.0f);
@@ -1866,6 +1943,134 @@ int vr_query_text(vr_engine* e, const vr_wordpiece* tokenizer, const char* dense
     if (out_from_dense) out_from_dense[i] = 1;
   }
   *out_count = c;
+  return 0;
+}
+
+int vr_query_text_batch(vr_engine* e, const vr_wordpiece* tokenizer, int32_t n, const char* const* dense_texts,
+                        const int64_t* dense_lens, const char* const* sparse_texts, const int64_t* sparse_lens,
+                        int32_t max_len, const int32_t* limits, const double* sparse_weights, int32_t fusion,
+                        const vr_filter* filters, int32_t n_filters, const int32_t* filter_of_query, int32_t out_stride,
+                        int64_t* out_rows, double* out_scores, int32_t* out_from_dense, int32_t* out_counts,
+                        int32_t* out_hybrid, float* out_embeddings) {
+  // (the arguments are checked before the engine is touched, as in the _multi calls)
+  VR_CHECK(n >= 0, "bad arguments");
+  if (n == 0) return 0;
+  VR_CHECK(tokenizer && dense_texts && dense_lens && limits && sparse_weights && out_rows && out_scores && out_counts,
+           "bad arguments");
+  VR_CHECK(fusion == VR_FUSION_MINMAX || fusion == VR_FUSION_RRF, "unknown fusion %d", fusion);
+  VR_CHECK(max_len >= 2 && max_len <= 4096, "max_len %d", max_len);
+  int max_limit = 0;
+  for (int i = 0; i < n; ++i) {
+    VR_CHECK(dense_texts[i] && dense_lens[i] >= 0, "dense text %d: null or negative length", i);
+    VR_CHECK(!sparse_texts || !sparse_texts[i] || (sparse_lens && sparse_lens[i] >= 0), "sparse text %d: no length", i);
+    VR_CHECK(limits[i] >= 1 && limits[i] <= kMaxK / 3, "limits[%d] = %d not in 1..%d", i, limits[i], kMaxK / 3);
+    max_limit = std::max(max_limit, limits[i]);
+  }
+  VR_CHECK(out_stride >= max_limit, "out_stride = %d is below the largest limit %d", out_stride, max_limit);
+  {
+    QueryClasses qc;
+    VR_TRY(classify_queries(filters, n_filters, filter_of_query, n, &qc));
+  }
+  VR_TRY(check_engine(e));
+  VR_CHECK(encoder_hidden(e) == e->dim, "encoder width %d != store dimension %d", encoder_hidden(e), e->dim);
+  const int dim = e->dim;
+  // 1. host: WordPiece ids of every (prefixed) question, the hashed stems of every raw one
+  std::vector<int32_t> wp, off32;
+  VR_TRY(question_wordpieces(tokenizer, dense_texts, dense_lens, n, max_len, &wp, &off32));
+  std::vector<int64_t> st_off;
+  std::vector<int32_t> stems;
+  VR_TRY(question_stems(sparse_texts, sparse_lens, n, &st_off, &stems));
+  // the questions with a stem take the hybrid branch, the others the dense one (vector_store.py:560-619); the hybrid
+  // ones' stems again as a CSR in their order, values 1.0
+  std::vector<int32_t> pick, h_lim, d_lim, h_fq, d_fq;
+  std::vector<double> h_w;
+  std::vector<int64_t> h_off(1, 0);
+  std::vector<int32_t> h_ids;
+  for (int i = 0; i < n; ++i) {
+    const int64_t a = st_off[static_cast<size_t>(i)], b = st_off[static_cast<size_t>(i) + 1];
+    if (out_hybrid) out_hybrid[i] = b > a ? 1 : 0;
+    out_counts[i] = 0;
+    if (b == a) continue;
+    pick.push_back(i);
+    h_ids.insert(h_ids.end(), stems.begin() + a, stems.begin() + b);
+    h_off.push_back(static_cast<int64_t>(h_ids.size()));
+  }
+  const int nh = static_cast<int>(pick.size());
+  for (int i = 0; i < n; ++i)
+    if (st_off[static_cast<size_t>(i) + 1] == st_off[static_cast<size_t>(i)]) pick.push_back(i);
+  const std::vector<float> ones(h_ids.size(), 1.0f);
+  for (int j = 0; j < n; ++j) {
+    const int i = pick[static_cast<size_t>(j)];
+    (j < nh ? h_lim : d_lim).push_back(limits[i]);
+    (j < nh ? h_fq : d_fq).push_back(filter_of_query ? filter_of_query[i] : -1);
+    if (j < nh) h_w.push_back(sparse_weights[i]);
+  }
+  // 2. one forward pass over all n questions, the pooled rows left in device memory. Lock order as vr_query_text: the
+  //    writers' mutex (the encoder), then the shared lock of a lane.
+  std::unique_lock<std::mutex> writer(e->wmu);
+  SearchLane lane(e);
+  VR_TRY(lane.acquire(false));
+  vr_engine* L = lane.L;
+  VR_TRY(L->qt_emb.grow(static_cast<int64_t>(n) * dim, 0, L->stream));
+  VR_TRY(encoder_encode(e, wp.data(), off32.data(), n, VR_MEM_HOST, L->qt_emb.p, VR_MEM_DEVICE));  // (stream drained)
+  writer.unlock();
+  if (out_embeddings)
+    VR_HIP(hipMemcpyAsync(out_embeddings, L->qt_emb.p, sizeof(float) * static_cast<size_t>(n) * dim, hipMemcpyDeviceToHost,
+                          L->stream));
+  // the hybrid questions first, then the dense ones, gathered on the device (nothing to do when all are hybrid)
+  const float* q = L->qt_emb.p;
+  if (nh < n) {
+    VR_TRY(L->qt_pick.grow(n, 0, L->stream));
+    VR_TRY(L->qt_gather.grow(static_cast<int64_t>(n) * dim, 0, L->stream));
+    VR_HIP(hipMemcpyAsync(L->qt_pick.p, pick.data(), sizeof(int32_t) * static_cast<size_t>(n), hipMemcpyHostToDevice, L->stream));
+    const int64_t total = static_cast<int64_t>(n) * dim;
+    hipLaunchKernelGGL(gather_query_rows_kernel, dim3(static_cast<unsigned>((total + 255) / 256)), dim3(256), 0, L->stream,
+                       L->qt_emb.p, L->qt_pick.p, static_cast<int64_t>(n), dim, L->qt_gather.p);
+    VR_HIP(hipGetLastError());
+    q = L->qt_gather.p;
+  }
+  VR_HIP(hipStreamSynchronize(L->stream));
+  // 3. the search legs in slices of questions (answers are per question: slicing changes no bits)
+  constexpr int kSlice = 4096;
+  std::vector<uint64_t> dense, sparse;
+  for (int s0 = 0; s0 < nh; s0 += kSlice) {  // hybrid: the filtered hybrid batch, fused on the host threads
+    const int ns = std::min(kSlice, nh - s0);
+    QueryClasses qc;
+    VR_TRY(classify_queries(filters, n_filters, h_fq.data() + s0, ns, &qc));
+    int ml = 0;
+    for (int j = 0; j < ns; ++j) ml = std::max(ml, h_lim[static_cast<size_t>(s0 + j)]);
+    const int kstride = 3 * ml;
+    dense.assign(static_cast<size_t>(ns) * kstride, 0);
+    sparse.assign(static_cast<size_t>(ns) * kstride, 0);
+    VR_TRY(hybrid_multi_keys(L, q + static_cast<int64_t>(s0) * dim, ns, VR_MEM_DEVICE, h_off.data() + s0, h_ids.data(),
+                             ones.data(), h_lim.data() + s0, qc, kstride, dense.data(), sparse.data()));
+    VR_TRY(fuse_multi(dense.data(), sparse.data(), ns, kstride, h_lim.data() + s0, h_w.data() + s0, fusion, pick.data() + s0,
+                      out_stride, out_rows, out_scores, out_from_dense, out_counts));
+  }
+  const int nd = n - nh;
+  for (int s0 = 0; s0 < nd; s0 += kSlice) {  // no stem: the filtered dense batch at the slice's largest limit, trimmed
+    const int ns = std::min(kSlice, nd - s0);
+    QueryClasses qc;
+    VR_TRY(classify_queries(filters, n_filters, d_fq.data() + s0, ns, &qc));
+    int k = 0;
+    for (int j = 0; j < ns; ++j) k = std::max(k, d_lim[static_cast<size_t>(s0 + j)]);
+    dense.assign(static_cast<size_t>(ns) * k, 0);
+    VR_TRY(dense_multi_keys(L, q + static_cast<int64_t>(nh + s0) * dim, ns, VR_MEM_DEVICE, k, qc, dense.data()));
+    parallel_for(ns, 64, [&](int64_t j) {
+      const int i = pick[static_cast<size_t>(nh + s0 + j)], limit = d_lim[static_cast<size_t>(s0 + j)];
+      int64_t rows[kMaxK];
+      float sc[kMaxK];
+      const int c = std::min(limit, static_cast<int>(decode_keys(dense.data() + static_cast<size_t>(j) * k, k, rows, sc)));
+      const int64_t at = static_cast<int64_t>(i) * out_stride;
+      for (int r = 0; r < c; ++r) {  // the cosines widened to f64 (vr_query_text's dense branch)
+        out_rows[at + r] = rows[r];
+        out_scores[at + r] = static_cast<double>(sc[r]);
+        if (out_from_dense) out_from_dense[at + r] = 1;
+      }
+      out_counts[i] = c;
+    });
+  }
+  if (out_embeddings) VR_HIP(hipStreamSynchronize(L->stream));
   return 0;
 }
 

@@ -2082,47 +2082,57 @@ __global__ __launch_bounds__(512) void gemm_f16_pp_kernel(
 //     gemm_f16_pp_kernel: the result is bit-identical to it, and the epilogue is the same code (direct_epilogue).
 // One tile per block, no persistence: consecutive blocks of an XCD (blockIdx % 8) take the column tiles of one
 // 256-row panel one after the other, so a panel of A is read from HBM once and then from that XCD's L2.
-constexpr int D2M = 256, D2N = 128, D2K = 32;
-constexpr int kD2StageHalfs = (D2M + D2N) * D2K;  // 24 KiB
+//
+// The MID-SIZE instantiation (WM = 1, gemm_f16_mid: 256 < M, a batch of questions or one file's chunks) is the same
+// kernel on a 128-token x 128-feature tile: TWO waves (one row of wave tiles), 48 KiB of stages, three blocks per CU.
+// At 1.6k tokens and N = 768 the 256x256 ping-pong tiles number 7 x 3 = 21 for 256 CUs; these number 13 x 6 = 78. Every
+// wave tile, fragment, K order and epilogue is the one above, so its bits are gemm_f16_pp_kernel's too.
+constexpr int D2N = 128, D2K = 32;  // (stages: 24 KiB; WM = 1: 16 KiB)
+template <int WM> constexpr int d2_rows() { return 128 * WM; }
+template <int WM> constexpr int d2_stage_halfs() { return (d2_rows<WM>() + D2N) * D2K; }
 
-template <int EPI>
-__global__ __launch_bounds__(256, 2) void gemm_f16_d2_kernel(
+template <int EPI, int WM = 2>
+__global__ __launch_bounds__(128 * WM, 2) void gemm_f16_d2_kernel(
     const half_t* __restrict__ Ah, const half_t* __restrict__ Wh, const float* __restrict__ bias,
     const float* __restrict__ R, float* __restrict__ C, half_t* __restrict__ Ch, half_t* __restrict__ Cl, int M,
     int N, int K, float unscale, const float2* __restrict__ ln_stat, const float* __restrict__ ln_g,
     const float* __restrict__ ln_b) {
-  __shared__ half_t lds[3 * kD2StageHalfs + 4 * kWaveStatHalfs];  // the only LDS object (see gemm_f16x3_256_kernel)
+  constexpr int NW = 2 * WM;                       // waves: WM rows x 2 columns of 128 x 64 wave tiles
+  constexpr int TM = d2_rows<WM>();                // token rows of the block tile
+  constexpr int kStage = d2_stage_halfs<WM>();
+  constexpr int kLoadsW = 8 / NW;                  // W image loads per wave and step (A: always 4)
+  __shared__ half_t lds[3 * kStage + NW * kWaveStatHalfs];  // the only LDS object (see gemm_f16x3_256_kernel)
   const int tiles_n = (N + D2N - 1) / D2N;
-  const int tiles_m = (M + D2M - 1) / D2M;
+  const int tiles_m = (M + TM - 1) / TM;
   const int xcd = static_cast<int>(blockIdx.x) & 7, seq = static_cast<int>(blockIdx.x) >> 3;
   const int panel = (seq / tiles_n) * 8 + xcd;
   if (panel >= tiles_m) return;  // block-uniform (the grid is padded to a multiple of 8 panels)
-  const int bm = panel * D2M, bn = (seq % tiles_n) * D2N;
+  const int bm = panel * TM, bn = (seq % tiles_n) * D2N;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
-  float2* wave_stat = reinterpret_cast<float2*>(lds + 3 * kD2StageHalfs + wave * kWaveStatHalfs);
+  float2* wave_stat = reinterpret_cast<float2*>(lds + 3 * kStage + wave * kWaveStatHalfs);
 
   // staging: one direct-to-LDS load moves 16 rows x 64 B; lane -> row (lane >> 2) of the 16, LDS chunk (lane & 3),
-  // source chunk (lane & 3) ^ ((row >> 1) & 3). Wave w stages A rows 16 (w + 4 t) + .. (t = 0..3) and W image rows
-  // 16 (w + 4 t) + .. (t = 0, 1); image row 32 P + 16 q + r holds weight row 32 P + 8 (r >> 2) + 4 q + (r & 3)
+  // source chunk (lane & 3) ^ ((row >> 1) & 3). Wave w stages A rows 16 (w + NW t) + .. (t = 0..3) and W image rows
+  // 16 (w + NW t) + .. (t < 8 / NW); image row 32 P + 16 q + r holds weight row 32 P + 8 (r >> 2) + 4 q + (r & 3)
   // (direct_epilogue: a lane then owns 8 consecutive output features).
   const int srow = lane >> 2;
   const int schunk = ((lane & 3) ^ ((srow >> 1) & 3)) * 8;
   const half_t* g_a[4];
-  const half_t* g_w[2];
+  const half_t* g_w[kLoadsW];
 #pragma unroll
   for (int t = 0; t < 4; ++t)
-    g_a[t] = Ah + static_cast<int64_t>(min(bm + 16 * (wave + 4 * t) + srow, M - 1)) * K + schunk;
+    g_a[t] = Ah + static_cast<int64_t>(min(bm + 16 * (wave + NW * t) + srow, M - 1)) * K + schunk;
 #pragma unroll
-  for (int t = 0; t < 2; ++t) {
-    const int img = 16 * (wave + 4 * t);  // first image row of the instruction: P = img >> 5, q = (img >> 4) & 1
+  for (int t = 0; t < kLoadsW; ++t) {
+    const int img = 16 * (wave + NW * t);  // first image row of the instruction: P = img >> 5, q = (img >> 4) & 1
     const int wrow = (img & ~31) + 8 * (srow >> 2) + 4 * ((img >> 4) & 1) + (srow & 3);
     g_w[t] = Wh + static_cast<int64_t>(min(bn + wrow, N - 1)) * K + schunk;
   }
-  const int da = wave * 16 * D2K;               // + 4 t * 16 * D2K
-  const int dw = D2M * D2K + wave * 16 * D2K;   // + 4 t * 16 * D2K
+  const int da = wave * 16 * D2K;               // + NW t * 16 * D2K
+  const int dw = TM * D2K + wave * 16 * D2K;    // + NW t * 16 * D2K
 
   f32x4 acc[8][4];
 #pragma unroll
@@ -2133,7 +2143,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f16_d2_kernel(
   const int frow = lane & 15;
   const int fk = ((lane >> 4) ^ ((frow >> 1) & 3)) * 8;
   const int pa = (wm * 128 + frow) * D2K + fk;
-  const int pw = D2M * D2K + (wn * 64 + frow) * D2K + fk;
+  const int pw = TM * D2K + (wn * 64 + frow) * D2K + fk;
   const int nk = K / D2K;
 #ifdef VR_GEMM_DIAG_BUILD
   const int diag_bits = __builtin_amdgcn_readfirstlane(g_gemm_diag);
@@ -2147,21 +2157,24 @@ __global__ __launch_bounds__(256, 2) void gemm_f16_d2_kernel(
   } while (0)
   auto issue = [&](half_t* stage, int k0) {
 #pragma unroll
-    for (int t = 0; t < 4; ++t) glds16(g_a[t] + k0, stage + da + t * 64 * D2K);
+    for (int t = 0; t < 4; ++t) glds16(g_a[t] + k0, stage + da + t * NW * 16 * D2K);
 #pragma unroll
-    for (int t = 0; t < 2; ++t) glds16(g_w[t] + k0, stage + dw + t * 64 * D2K);
+    for (int t = 0; t < kLoadsW; ++t) glds16(g_w[t] + k0, stage + dw + t * NW * 16 * D2K);
   };
   issue(lds, 0);
-  if (nk > 1) issue(lds + kD2StageHalfs, D2K);
+  if (nk > 1) issue(lds + kStage, D2K);
 
   auto step = [&](auto bsel, int s) {
     constexpr int B = decltype(bsel)::value;
-    const half_t* st = lds + B * kD2StageHalfs;
-    half_t* nd = lds + ((B + 2) % 3) * kD2StageHalfs;
+    const half_t* st = lds + B * kStage;
+    half_t* nd = lds + ((B + 2) % 3) * kStage;
     // the loads of step s have landed (those of step s + 1, if any, stay in flight) ...
-    if (s + 1 < nk)
-      asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    else
+    if (s + 1 < nk) {
+      if constexpr (kLoadsW == 2)
+        asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+      else
+        asm volatile("s_waitcnt vmcnt(8)" ::: "memory");  // (WM = 1: 4 + 4 loads per wave and step)
+    } else
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     VR_D2_BARRIER();  // ... every wave's; and every wave has finished with stage (s - 1) % 3 = (s + 2) % 3
     if (s + 2 < nk && !VR_DIAG(1)) issue(nd, (s + 2) * D2K);
@@ -2201,7 +2214,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f16_d2_kernel(
     return;
   }
   // (EPI_RLS_R32_O16 — layer 0 only — holds two pieces of f32 residual rows: four registers too many without branches)
-  if (EPI != EPI_RLS_R32_O16 && bm + D2M <= M && bn + D2N <= N)  // block-uniform
+  if (EPI != EPI_RLS_R32_O16 && bm + TM <= M && bn + D2N <= N)  // block-uniform
     direct_epilogue<EPI, true>(acc, bm + wm * 128, bn + wn * 64, lane, bias, R, C, Ch, Cl, M, N, unscale, ln_stat, ln_g, ln_b, wave_stat);
   else
     direct_epilogue<EPI, false>(acc, bm + wm * 128, bn + wn * 64, lane, bias, R, C, Ch, Cl, M, N, unscale, ln_stat, ln_g, ln_b, wave_stat);
@@ -2466,13 +2479,25 @@ static bool d2_usable(int N, int K) {
   return on && K % D2K == 0 && N % 8 == 0;
 }
 
+// gemm_f16_mid (gemm_f16_d2_kernel<EPI, 1>, 128x128 tiles) in place of the ping-pong kernel for 256 < M while the
+// 256x256 tiles would fill at most a quarter of the CUs. Measured on an MI355X: at 21-48 ping-pong tiles
+// (1k tokens, N = 768 / 2304 / 3072) it is 15-40 % faster; at 189 (16k tokens, N = 768) up to 35 % slower; the shapes
+// between were not measured and stay with the ping-pong kernel. VR_GEMM_MID=0 turns it off (A/B runs; the bit-identity test).
+static bool mid_usable(int M, int N, int K, int n_cu) {
+  static const bool mid_on = !(getenv("VR_GEMM_MID") && atoi(getenv("VR_GEMM_MID")) == 0);
+  if (!mid_on || K % D2K != 0 || N % 8 != 0 || M <= 256) return false;
+  const int tiles_pp = ((M + GBM - 1) / GBM) * ((N + GBN - 1) / GBN);
+  return 4 * tiles_pp <= n_cu;
+}
+
 // the kernels whose epilogue is direct_epilogue (all EPI_* variants, f16 residual stream included)
 static bool direct_usable(int N, int K) { return d2_usable(N, K) || pp_usable(N, K); }
 
+template <int WM>
 static void launch_d2(int epi, hipStream_t s, const half_t* Ah, const half_t* Wh, const float* bias, const float* R,
                       float* C, half_t* Ch, half_t* Cl, int M, int N, int K, float unscale, const float2* ln_stat,
                       const float* ln_g, const float* ln_b) {
-  const int tiles_m = (M + D2M - 1) / D2M, tiles_n = (N + D2N - 1) / D2N;
+  const int tiles_m = (M + d2_rows<WM>() - 1) / d2_rows<WM>(), tiles_n = (N + D2N - 1) / D2N;
   const int grid = (tiles_m + 7) / 8 * 8 * tiles_n;
 #ifdef VR_GEMM_DIAG_BUILD
   static bool diag_set = false;
@@ -2483,8 +2508,8 @@ static void launch_d2(int epi, hipStream_t s, const half_t* Ah, const half_t* Wh
   }
 #endif
 #define VR_LAUNCH_D2(E)                                                                                       \
-  hipLaunchKernelGGL((gemm_f16_d2_kernel<E>), dim3(grid), dim3(256), 0, s, Ah, Wh, bias, R, C, Ch, Cl, M, N, K, \
-                     unscale, ln_stat, ln_g, ln_b)
+  hipLaunchKernelGGL((gemm_f16_d2_kernel<E, WM>), dim3(grid), dim3(128 * WM), 0, s, Ah, Wh, bias, R, C, Ch, Cl, M, N, \
+                     K, unscale, ln_stat, ln_g, ln_b)
   switch (epi) {
     case EPI_BIAS: VR_LAUNCH_D2(EPI_BIAS); break;
     case EPI_BIAS_GELU: VR_LAUNCH_D2(EPI_BIAS_GELU); break;
@@ -2757,7 +2782,9 @@ static int launch_gemm_f16x3(vr_engine* e, int epi, const half_t* Ah, const half
     const int tiles = ((M + GBM - 1) / GBM) * ((N + GBN - 1) / GBN);
     const int grid256 = std::min(tiles, n_cu);
     if (passes == 1 && d2_usable(N, K))  // f16 mode: two independent half-width tiles per CU (gemm_f16_d2_kernel)
-      launch_d2(epi, s, Ah, Wh, bias, R, C, Ch, Cl, M, N, K, unscale, ln_stat, ln_g, ln_b);
+      launch_d2<2>(epi, s, Ah, Wh, bias, R, C, Ch, Cl, M, N, K, unscale, ln_stat, ln_g, ln_b);
+    else if (passes == 1 && mid_usable(M, N, K, n_cu))  // mid-size M: 128x128 tiles (gemm_f16_mid)
+      launch_d2<1>(epi, s, Ah, Wh, bias, R, C, Ch, Cl, M, N, K, unscale, ln_stat, ln_g, ln_b);
     else if (passes == 1 && pp_usable(N, K))  // the ping-pong main loop (gemm_f16_pp_kernel)
       launch_pp(epi, grid256, s, Ah, Wh, bias, R, C, Ch, Cl, M, N, K, unscale, ln_stat, ln_g, ln_b);
     else if (passes == 1)

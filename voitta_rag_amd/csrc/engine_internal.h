@@ -302,6 +302,10 @@ struct vr_engine {
   vr::DevArray<uint16_t> bq_tile_ub;  // f16 bits: per (16-row tile, query) the largest upper bound (rounded up)
   vr::DevArray<int32_t> bq_pairs;     // per query: the tiles whose bound reaches its threshold ([nq][kBatchCand]), then the counts [nq]
   vr::DevArray<float> bq_stage;  // host queries staged on the device
+  // vr_query_text_batch: the questions' embeddings (n x dim), and them gathered hybrid-first by the picks
+  vr::DevArray<float> qt_emb;
+  vr::DevArray<int32_t> qt_pick;
+  vr::DevArray<float> qt_gather;
   // filtered batches (vr_search_*_multi): one bit plane per class of filter ([class][plane words], bit r % 32 of word
   // r / 32 = row r passes), the class of every query of the batch, and the classes' pass tables and descriptors
   vr::DevArray<uint32_t> cls_planes;

@@ -213,6 +213,18 @@ class EmbeddingService:
             return _deferred.QueryRef(model, query)  # encoded when looked at — or inside the search call it goes to
         return _deferred.QueryEmbedding(model.encode(query, convert_to_numpy=True))
 
+    def query_texts(self, queries: list[str]) -> list[str]:
+        """The questions as the encoder sees them: with the e5 ``query: `` prefix, as embed_query applies it."""
+        if "e5" in self.model_name.lower():  # embedding.py:82-83
+            return [f"query: {q}" for q in queries]
+        return list(queries)
+
+    def embed_queries(self, queries: list[str]) -> list[list[float]]:
+        """embed_query for many questions in ONE forward pass (the packed batch of vr_encode)."""
+        if not queries:
+            return []
+        return self.model.encode(self.query_texts(queries), convert_to_numpy=True).tolist()
+
 
 _embedding_service: EmbeddingService | None = None
 

@@ -455,6 +455,45 @@ class Engine:
         n = int(cnt.value)
         return rows[:n], scores[:n], fd[:n], bool(hyb.value)
 
+    def query_text_batch(self, tokenizer_handle, dense_texts, sparse_texts, max_len: int, limits, sparse_weights,
+                         filters, fusion: int = VR_FUSION_MINMAX, raw: bool = False, embeddings: bool = False):
+        """n questions as text in ONE engine call (vr_query_text_batch): result i is query_text(dense_texts[i],
+        sparse_texts[i], max_len, limits[i], sparse_weights[i], fusion, filters[i]) — one forward pass over all of
+        them, then the filtered batch searches. sparse_texts: one str | None per question (None: no sparse leg).
+        -> list of (rows, scores, from_dense, hybrid); raw=True: (rows, scores, from_dense, counts, hybrid) arrays.
+        embeddings=True: also the (n, hidden) f32 embeddings, as a second return value."""
+        n = len(dense_texts)
+        assert sparse_texts is None or len(sparse_texts) == n
+        d = [t.encode("utf-8", "replace") for t in dense_texts]
+        sp = [t.encode("utf-8", "surrogatepass") if t else None for t in (sparse_texts or [None] * n)]
+        d_arr = (C.c_char_p * max(n, 1))(*d)
+        s_arr = (C.c_char_p * max(n, 1))(*sp)
+        d_len = np.array([len(t) for t in d] or [0], np.int64)
+        s_len = np.array([len(t) if t else 0 for t in sp] or [0], np.int64)
+        lim = _np(np.broadcast_to(np.asarray(limits), (n,)), np.int32)
+        wts = _np(np.broadcast_to(np.asarray(sparse_weights, dtype=np.float64), (n,)), np.float64)
+        farr, nf, foq, keep = self._filter_classes(filters, n)
+        stride = max(1, int(lim.max()) if n else 1)
+        rows = np.empty((n, stride), np.int64)
+        scores = np.empty((n, stride), np.float64)
+        fd = np.empty((n, stride), np.int32)
+        counts = np.zeros(n, np.int32)
+        hyb = np.zeros(n, np.int32)
+        emb = np.empty((n, self.dim), np.float32) if embeddings else None
+        check(self._lib.vr_query_text_batch(self._h, tokenizer_handle, n, d_arr, _ptr(d_len, C.c_int64), s_arr,
+                                            _ptr(s_len, C.c_int64), int(max_len), _ptr(lim, C.c_int32),
+                                            _ptr(wts, C.c_double), fusion, farr, nf, _ptr(foq, C.c_int32), stride,
+                                            _ptr(rows, C.c_int64), _ptr(scores, C.c_double), _ptr(fd, C.c_int32),
+                                            _ptr(counts, C.c_int32), _ptr(hyb, C.c_int32),
+                                            _ptr(emb, C.c_float) if emb is not None else None))
+        del keep
+        if raw:
+            out = (rows, scores, fd, counts, hyb.astype(bool))
+        else:
+            out = [(rows[i, : counts[i]].copy(), scores[i, : counts[i]].copy(), fd[i, : counts[i]].copy(), bool(hyb[i]))
+                   for i in range(n)]
+        return (out, emb) if embeddings else out
+
     # ---- many queries per call (BASELINE configs[4]: 1k batched hybrid queries) -----------------------------------
     @staticmethod
     def _sparse_csr(sparse_queries, nq: int):

@@ -987,6 +987,65 @@ class VectorStoreService:
             out[i] = [self._chunk_from(pid, payload, s) for (pid, payload), s in zip(mine, scores[j]) if payload is not None]
         return out
 
+    def search_questions(self, requests: list[dict]) -> list[list[StoredChunk]]:
+        """``search_requests`` for questions still as TEXT, in one engine call (vr_query_text_batch): requests[i] holds
+        ``query`` (the raw question) and any keyword argument of ``search`` but the two vectors. Result i is what
+        ``search_requests`` returns for it with ``query_embedding = embed_queries(queries)[i]`` and ``sparse_query`` =
+        the sparse ``embed_query(query)``: one forward pass over all questions, whose embeddings stay on the device and
+        feed the filtered batch searches. What an MCP server that gathers concurrent questions (mcp_server.py:469-485)
+        sends. Every filter is built under one lock, as in ``search_requests``."""
+        from .embedding import WordPieceTokenizer, get_embedding_service
+
+        n = len(requests)
+        out: list[list[StoredChunk]] = [[] for _ in range(n)]
+        live = [i for i in range(n) if int(requests[i].get("limit", 10)) > 0]
+        if not live:
+            return out
+        emb = get_embedding_service()
+        model = emb.model
+        queries = [requests[i]["query"] for i in live]
+        if not (isinstance(model.tokenizer, WordPieceTokenizer) and model.engine is self._engine
+                and int(model.desc.hidden) == self.dimension):
+            # (an encoder outside this engine: the two services, then search_requests — the definition of the answer)
+            from .sparse_embedding import _query_vector
+
+            vecs = emb.embed_queries(queries)
+            reqs = []
+            for j, i in enumerate(live):
+                r = {a: v for a, v in requests[i].items() if a != "query"}
+                reqs.append(dict(r, query_embedding=vecs[j], sparse_query=_query_vector(queries[j])))
+            res = self.search_requests(reqs)
+            for j, i in enumerate(live):
+                out[i] = res[j]
+            return out
+        col = self._col
+        self._drain(col, surface_errors=False)
+        texts = emb.query_texts(queries)
+        sparse_texts = queries if self._has_sparse else None
+        limits = [int(requests[i].get("limit", 10)) for i in live]
+        weights = [float(requests[i].get("sparse_weight", 0.1)) for i in live]
+
+        def build():
+            return [self._build_filter(**{a: requests[i].get(a) for a in self._FILTER_ARGS}) for i in live]
+
+        def run(filters):
+            r, s, _fd, c, hyb = self._engine.query_text_batch(model.tokenizer._h, texts, sparse_texts, model.max_seq_length,
+                                                              limits, weights, filters, raw=True)
+            rows = [r[j, : c[j]] for j in range(len(live))]
+            scores = [[float(v) for v in s[j, : c[j]]] if hyb[j] else [_json_float(np.float32(v)) for v in s[j, : c[j]]]
+                      for j in range(len(live))]
+            counts = [len(x) for x in rows]
+            flat = np.concatenate([np.asarray(x, np.int64) for x in rows])
+            return flat, (counts, scores)
+
+        pairs, (counts, scores) = self._consistent(col, run, build)
+        at = 0
+        for j, i in enumerate(live):
+            mine = pairs[at: at + counts[j]]
+            at += counts[j]
+            out[i] = [self._chunk_from(pid, payload, s) for (pid, payload), s in zip(mine, scores[j]) if payload is not None]
+        return out
+
     # ---- read helpers (payload only) ---------------------------------------------------------------
     def find_by_source_url(self, source_url: str) -> list[StoredChunk]:
         col = self._col
