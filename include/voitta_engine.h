@@ -181,6 +181,17 @@ void vr_wordpiece_destroy(vr_wordpiece* t);
 int vr_wordpiece_encode(const vr_wordpiece* t, const char* const* texts, const int64_t* text_lens, int64_t n_texts,
                         int32_t max_len, int64_t* out_offsets, int32_t* out_ids, int64_t capacity, int64_t* needed);
 
+/* Text PAIRS for a cross-encoder: sequence i is [CLS] A_i [SEP] B_i [SEP] with A_i / B_i tokenised as above and
+ * truncated the way HF tokenizers' TruncationStrategy.LongestFirst does to max_len ids including the 3 specials
+ * (the shorter side keeps what it can up to half, the longer side the rest). out_seg_b[i] (n entries, may be NULL) is
+ * the index inside sequence i of its first segment-B (token type 1) id: the one after the first [SEP]. Each distinct
+ * A text is tokenised once per call. out_offsets, out_ids, capacity, *needed and the -2 return as vr_wordpiece_encode;
+ * max_len >= 3. */
+int vr_wordpiece_encode_pairs(const vr_wordpiece* t, const char* const* a_texts, const int64_t* a_lens,
+                              const char* const* b_texts, const int64_t* b_lens, int64_t n, int32_t max_len,
+                              int64_t* out_offsets, int32_t* out_ids, int32_t* out_seg_b, int64_t capacity,
+                              int64_t* needed);
+
 /* ---- BM25 document side: replaces SparseTextEmbedding("Qdrant/bm25").embed's token-count / TF
  * weighting (sparse_embedding.py:25,49; scripts/build_sparse_vectors.py:124,170) -- */
 /* tok_off: n_docs+1 offsets, tok_ids: abs(murmur3) of each stemmed token in text order (`mem`).
@@ -454,6 +465,31 @@ int vr_query_text_batch(vr_engine* e, const vr_wordpiece* tokenizer, int32_t n, 
                         const vr_filter* filters, int32_t n_filters, const int32_t* filter_of_query, int32_t out_stride,
                         int64_t* out_rows, double* out_scores, int32_t* out_from_dense, int32_t* out_counts,
                         int32_t* out_hybrid, float* out_embeddings);
+
+/* ---- Cross-encoder reranking: a second BERT model in the engine, beside the embedder -------------------------------
+ * vr_reranker_load: a BertForSequenceClassification with one label (cross-encoder/ms-marco-MiniLM-L-6-v2 and the
+ * like). desc / tensors / mem as vr_encoder_load, followed by 4 more tensors: pooler.dense.weight [H,H],
+ * pooler.dense.bias [H], classifier.weight [1,H], classifier.bias [1] (5 + 16 L + 4 in all). desc->pooling must be
+ * VR_POOL_CLS and desc->normalize 0; any precision; type_vocab >= 2; H need not equal the engine's dim. The model gets
+ * its own weights, workspace and graph cache, is replaced by the next load and freed with the engine; loading it never
+ * touches the embedder. */
+int vr_reranker_load(vr_engine* e, const vr_bert_desc* desc, const void* const* tensors, int32_t n_tensors, int mem);
+
+/* One logit per (question, passage) pair: logit = wc . tanh(Wp h_CLS + bp) + bc, h_CLS the last hidden state of the
+ * pair's [CLS] token. ids / offsets as vr_encode (pair sequences, e.g. from vr_wordpiece_encode_pairs); seg_b[n_seq]
+ * int32: tokens at positions >= seg_b[i] of sequence i are segment B (token type 1), 1 <= seg_b[i] <= its length. All
+ * three in `mem`; out_logits: n_seq f32 in `out_mem`. The head runs in f32 whatever the precision, in a fixed order:
+ * the same input gives the same bits. Arguments are checked before any device work. */
+int vr_rerank(vr_engine* e, const int32_t* ids, const int32_t* offsets, const int32_t* seg_b, int32_t n_seq, int mem,
+              float* out_logits, int out_mem);
+
+/* The same from text: n_queries questions, question q paired with passages [cand_off[q], cand_off[q+1]) (cand_off:
+ * n_queries + 1 int64, cand_off[0] = 0, non-decreasing; a question may have none). Pairs are tokenised by `tokenizer`
+ * (vr_wordpiece_encode_pairs, max_len) on the host threads and scored in ONE forward pass; out_logits (host) receives
+ * cand_off[n_queries] logits in pair order, each equal to what vr_rerank gives for the same ids. */
+int vr_rerank_text(vr_engine* e, const vr_wordpiece* tokenizer, int32_t n_queries, const char* const* queries,
+                   const int64_t* query_lens, const int64_t* cand_off, const char* const* passages,
+                   const int64_t* passage_lens, int32_t max_len, float* out_logits);
 
 /* Persistence. The reference's index survives a restart in Qdrant's volume
  * (docker-compose.yml:8-9; VectorStoreService._ensure_collection re-attaches, vector_store.py:75-115).

@@ -471,6 +471,66 @@ int vr_encode(vr_engine* e, const int32_t* ids, const int32_t* offsets, int32_t 
   return encoder_encode(e, ids, offsets, n_seq, mem, out, out_mem);
 }
 
+int vr_reranker_load(vr_engine* e, const vr_bert_desc* desc, const void* const* tensors, int32_t n_tensors, int mem) {
+  VR_TRY(check_engine(e));
+  VR_CHECK(desc && tensors, "null argument");
+  VR_CHECK(mem == VR_MEM_HOST || mem == VR_MEM_DEVICE, "bad mem %d", mem);
+  std::lock_guard<std::mutex> writer(e->wmu);
+  return reranker_load(e, desc, tensors, n_tensors, mem);
+}
+
+int vr_rerank(vr_engine* e, const int32_t* ids, const int32_t* offsets, const int32_t* seg_b, int32_t n_seq, int mem,
+              float* out_logits, int out_mem) {
+  VR_CHECK(n_seq >= 0 && (n_seq == 0 || (ids && offsets && seg_b && out_logits)), "bad arguments");
+  VR_CHECK((mem == VR_MEM_HOST || mem == VR_MEM_DEVICE) && (out_mem == VR_MEM_HOST || out_mem == VR_MEM_DEVICE),
+           "bad mem");
+  VR_TRY(check_engine(e));
+  std::lock_guard<std::mutex> writer(e->wmu);
+  return encoder_rerank(e, ids, offsets, seg_b, n_seq, mem, out_logits, out_mem);
+}
+
+int vr_rerank_text(vr_engine* e, const vr_wordpiece* tokenizer, int32_t n_queries, const char* const* queries,
+                   const int64_t* query_lens, const int64_t* cand_off, const char* const* passages,
+                   const int64_t* passage_lens, int32_t max_len, float* out_logits) {
+  VR_CHECK(n_queries >= 0 && (n_queries == 0 || (tokenizer && queries && query_lens && cand_off)), "bad arguments");
+  VR_CHECK(max_len >= 3 && max_len <= 4096, "max_len %d", max_len);
+  if (n_queries == 0) return check_engine(e);
+  VR_CHECK(cand_off[0] == 0, "cand_off[0] = %lld, must be 0", static_cast<long long>(cand_off[0]));
+  for (int q = 0; q < n_queries; ++q) {
+    VR_CHECK(queries[q] && query_lens[q] >= 0, "query %d: null text or negative length", q);
+    VR_CHECK(cand_off[q + 1] >= cand_off[q], "cand_off decreases at query %d", q);
+  }
+  const int64_t n = cand_off[n_queries];
+  VR_CHECK(n <= INT32_MAX, "%lld pairs", static_cast<long long>(n));
+  VR_CHECK(n == 0 || (passages && passage_lens && out_logits), "bad arguments");
+  for (int64_t i = 0; i < n; ++i)
+    VR_CHECK(passages[i] && passage_lens[i] >= 0, "passage %lld: null text or negative length", static_cast<long long>(i));
+  VR_TRY(check_engine(e));
+  if (n == 0) return 0;
+  {
+    std::lock_guard<std::mutex> writer(e->wmu);
+    VR_CHECK(reranker_loaded(e), "no reranker loaded (vr_reranker_load)");
+  }
+  // host threads: the pairs' ids (each question tokenised once), then one forward pass over all of them
+  std::vector<const char*> a(static_cast<size_t>(n));
+  std::vector<int64_t> a_len(static_cast<size_t>(n));
+  for (int q = 0; q < n_queries; ++q)
+    for (int64_t i = cand_off[q]; i < cand_off[q + 1]; ++i) {
+      a[static_cast<size_t>(i)] = queries[q];
+      a_len[static_cast<size_t>(i)] = query_lens[q];
+    }
+  std::vector<int64_t> off(static_cast<size_t>(n) + 1);
+  std::vector<int32_t> seg(static_cast<size_t>(n)), ids(static_cast<size_t>(n) * max_len);
+  int64_t needed = 0;
+  VR_TRY(vr_wordpiece_encode_pairs(tokenizer, a.data(), a_len.data(), passages, passage_lens, n, max_len, off.data(),
+                                   ids.data(), seg.data(), static_cast<int64_t>(ids.size()), &needed));
+  VR_CHECK(needed <= INT32_MAX, "%lld tokens", static_cast<long long>(needed));
+  std::vector<int32_t> off32(static_cast<size_t>(n) + 1);
+  for (int64_t i = 0; i <= n; ++i) off32[static_cast<size_t>(i)] = static_cast<int32_t>(off[static_cast<size_t>(i)]);
+  std::lock_guard<std::mutex> writer(e->wmu);
+  return encoder_rerank(e, ids.data(), off32.data(), seg.data(), static_cast<int>(n), VR_MEM_HOST, out_logits, VR_MEM_HOST);
+}
+
 }  // extern "C"
 
 // Body of vr_upsert, also the last stage of vr_index_batch. Caller holds e->wmu and the exclusive lock.

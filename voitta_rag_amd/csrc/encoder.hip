@@ -15,6 +15,7 @@
 //                     online softmax, keys streamed through LDS 64 at a time
 //   layernorm_kernel  LayerNorm over H                               HBM bound
 //   pool_kernel       mean / CLS pooling + L2 normalise              HBM bound
+//   rerank_head_kernel cross-encoder head on the pooled [CLS] rows   one f32 logit per pair (encoder_rerank)
 // Algorithmic FLOP per token = L * (24 H^2 + 4 S H), of which the GEMMs are
 // 24 H^2 L: the dominant kernel of the indexing path.
 
@@ -57,16 +58,19 @@ struct Encoder {
   float* xs = nullptr;  // f16x3 / f16 mode: the hidden state as GEMM input ((hi, lo) or plain f16 rows)
   float* lnstat = nullptr;  // f16 mode: two arrays of per-row (mean, 1/sigma), see forward_chunk
   float* lnpart = nullptr;  // f16 mode: per (row, 64 columns) partial (sum, sum of squares) of the folded LayerNorms
-  DevArray<int32_t> ids, cu;
+  DevArray<int32_t> ids, cu, seg;
   DevArray<float> out;
+  // a cross-encoder (the reranker slot): pooler dense [H,H] + bias, classifier [1,H] + bias; the pooled [CLS] rows
+  float *pool_w = nullptr, *pool_b = nullptr, *cls_w = nullptr, *cls_b = nullptr;
+  DevArray<float> rows;
   DevArray<float> skinny_ws;  // K-slice partial sums of gemm_f16_skinny_kernel
   // hipGraphs of small forward passes (a query, a handful of sequences): ~135 launches of a few
   // microseconds of work each are launch-bound; replayed as one graph they are not
   struct GraphKey {
     int T, n_seq, max_len;
-    const void *ids, *cu, *out;
+    const void *ids, *cu, *seg, *out;
     bool operator<(const GraphKey& o) const {
-      return std::tie(T, n_seq, max_len, ids, cu, out) < std::tie(o.T, o.n_seq, o.max_len, o.ids, o.cu, o.out);
+      return std::tie(T, n_seq, max_len, ids, cu, seg, out) < std::tie(o.T, o.n_seq, o.max_len, o.ids, o.cu, o.seg, o.out);
     }
   };
   struct GraphEntry {
@@ -258,7 +262,9 @@ __device__ __forceinline__ void row_layernorm(float2 (&v)[kMaxPairs], int pairs,
     }
 }
 
-// one wave per token: x[t] = LayerNorm(word[id] + pos[p] + type[0])
+// one wave per token: x[t] = LayerNorm(word[id] + pos[p] + type[0]); SEG (a cross-encoder's pairs): type[1] for the
+// positions p >= seg_b[sequence], the segment-B tokens
+template <bool SEG>
 __global__ __launch_bounds__(256) void embed_ln_kernel(const int32_t* __restrict__ ids,
                                                        const int32_t* __restrict__ cu, int n_seq,
                                                        int tok_base, int T, int H, int vocab,
@@ -269,7 +275,7 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const int32_t* __restrict
                                                        const float* __restrict__ b, float eps,
                                                        float* __restrict__ x, half_t* __restrict__ x_hi,
                                                        half_t* __restrict__ x_lo, float* __restrict__ pre,
-                                                       float2* __restrict__ stat) {
+                                                       float2* __restrict__ stat, const int32_t* __restrict__ seg_b) {
   const int lane = threadIdx.x & 63;
   const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (t >= T) return;
@@ -283,6 +289,7 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const int32_t* __restrict
   const int p = tg - cu[lo];
   int id = ids[tg];
   id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
+  if (SEG && p >= seg_b[lo]) type += H;
   const int pairs = H / 128;
   float2 v[kMaxPairs];
 #pragma unroll
@@ -409,6 +416,50 @@ __global__ __launch_bounds__(256) void pool_kernel(const float* __restrict__ x,
     int c = threadIdx.x + 256 * j;
     if (c < H) out[static_cast<int64_t>(seq) * H + c] = vals[j] / den;
   }
+}
+
+// Cross-encoder head on n pooled [CLS] rows [n, H]: out[i] = wc . tanh(Wp h_i + bp) + bc, all f32. One block of 4 waves
+// per 16 rows: each wave takes every 4th 16-unit column tile of the pooler, a v_mfma_f32_16x16x4_f32 tile with the 16
+// rows as M and the tile's units as N (A and B read the same k permutation from float4 loads: lane quad q, step s holds
+// k0 + 4q + s), so Wp is read once per 16 rows. The sum over units is in a fixed order — per lane over its tiles, a xor
+// butterfly across the 16 lanes of a row group, then the four waves in order — with no atomics: same input, same bits.
+__global__ __launch_bounds__(256) void rerank_head_kernel(const float* __restrict__ rows, int n, int H,
+                                                          const float* __restrict__ wp, const float* __restrict__ bp,
+                                                          const float* __restrict__ wc, const float* __restrict__ bc,
+                                                          float* __restrict__ out) {
+  __shared__ float red[4][16];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int r = lane & 15, q = lane >> 4;
+  const int p0 = blockIdx.x * 16;
+  const bool live = p0 + r < n;
+  const float* a_row = rows + static_cast<int64_t>(live ? p0 + r : p0) * H;
+  float part[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  for (int jt = wave; jt < H / 16; jt += 4) {
+    const float* w_row = wp + static_cast<int64_t>(jt * 16 + r) * H;
+    f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+    for (int k0 = 0; k0 < H; k0 += 16) {
+      const float4 a = live ? *reinterpret_cast<const float4*>(a_row + k0 + 4 * q) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      const float4 b = *reinterpret_cast<const float4*>(w_row + k0 + 4 * q);
+      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, acc, 0, 0, 0);
+    }
+    const int j = jt * 16 + r;  // D: column (unit) lane & 15, row (pair) 4 q + i
+    const float bj = bp[j], cj = wc[j];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) part[i] += tanhf(acc[i] + bj) * cj;
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int off = 1; off < 16; off <<= 1) part[i] += __shfl_xor(part[i], off);
+  if (r == 0)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) red[wave][4 * q + i] = part[i];
+  __syncthreads();
+  const int t = threadIdx.x;
+  if (t < 16 && p0 + t < n) out[p0 + t] = bc[0] + red[0][t] + red[1][t] + red[2][t] + red[3][t];
 }
 
 // dst[i] = src[first token of sequence seq0 + i]; rows of `row_f4` float4s (an f32 row of H floats and
@@ -2701,7 +2752,8 @@ static int launch_skinny_ln(vr_engine* e, int epi, const float* pre, const float
 
 // passes = 3: operands are interleaved (hi, lo) rows (Al = Ah + 8, Wl = Wh + 8); passes = 1: plain f16
 // rows, Al / Wl / Cl unused.
-static int launch_gemm_f16x3(vr_engine* e, int epi, const half_t* Ah, const half_t* Al, const half_t* Wh,
+// enc: the model whose forward pass this is (its split-K scratch and graph cache)
+static int launch_gemm_f16x3(vr_engine* e, Encoder* enc, int epi, const half_t* Ah, const half_t* Al, const half_t* Wh,
                              const half_t* Wl, float unscale, const float* bias, const float* R, float* C,
                              half_t* Ch, half_t* Cl, int M, int N, int K, int passes = 3,
                              const float2* ln_stat = nullptr, const float* ln_g = nullptr, const float* ln_b = nullptr) {
@@ -2746,7 +2798,6 @@ static int launch_gemm_f16x3(vr_engine* e, int epi, const half_t* Ah, const half
     return 0;
   }
   if (passes == 1 && M <= 4 * kSkinnyM && skinny_slice(K) > 0 && N % 64 == 0) {  // K % 128 != 0: split-K, two launches
-    Encoder* enc = static_cast<Encoder*>(e->encoder);
     const int kslice = skinny_slice(K), slices = K / kslice;
     {
       const float* before = enc->skinny_ws.p;
@@ -3375,17 +3426,24 @@ static int make_split(vr_engine* e, Encoder* enc, const float* w_dev, size_t n, 
   return 0;
 }
 
-void encoder_release(vr_engine* e) {
-  Encoder* enc = static_cast<Encoder*>(e->encoder);
+static void free_encoder(void** slot) {
+  Encoder* enc = static_cast<Encoder*>(*slot);
   if (!enc) return;
   for (float* p : enc->owned) (void)hipFree(p);
   enc->ids.release();
   enc->cu.release();
+  enc->seg.release();
   enc->skinny_ws.release();
   invalidate_graphs(enc);
   enc->out.release();
+  enc->rows.release();
   delete enc;
-  e->encoder = nullptr;
+  *slot = nullptr;
+}
+
+void encoder_release(vr_engine* e) {
+  free_encoder(&e->encoder);
+  free_encoder(&e->reranker);
 }
 
 int encoder_hidden(vr_engine* e) {
@@ -3393,7 +3451,8 @@ int encoder_hidden(vr_engine* e) {
   return enc ? enc->d.hidden : 0;
 }
 
-int encoder_load(vr_engine* e, const vr_bert_desc* d, const void* const* t, int n_tensors, int mem) {
+// a model from its 5 + 16 L tensors (vr_encoder_load's order) into *slot, replacing what is there
+static int build_encoder(vr_engine* e, void** slot, const vr_bert_desc* d, const void* const* t, int n_tensors, int mem) {
   VR_CHECK(d->struct_size == static_cast<int32_t>(sizeof(vr_bert_desc)), "vr_bert_desc size mismatch");
   const int H = d->hidden, I = d->intermediate, L = d->layers;
   VR_CHECK(L >= 1 && H >= 128 && H % 128 == 0 && H <= 1024, "hidden %d must be a multiple of 128 in 128..1024", H);
@@ -3405,9 +3464,9 @@ int encoder_load(vr_engine* e, const vr_bert_desc* d, const void* const* t, int 
   VR_CHECK(d->precision == VR_PRECISION_F32 || d->precision == VR_PRECISION_F16X3 || d->precision == VR_PRECISION_F16,
            "unknown precision %d", d->precision);
   for (int i = 0; i < n_tensors; ++i) VR_CHECK(t[i] != nullptr, "tensor %d is null", i);
-  encoder_release(e);
+  free_encoder(slot);
   Encoder* enc = new Encoder();
-  e->encoder = enc;
+  *slot = enc;
   enc->d = *d;
   const size_t HH = static_cast<size_t>(H) * H;
   VR_TRY(dev_alloc_copy(e, enc, t[0], static_cast<size_t>(d->vocab) * H, mem, &enc->word));
@@ -3472,6 +3531,35 @@ int encoder_load(vr_engine* e, const vr_bert_desc* d, const void* const* t, int 
   return 0;
 }
 
+int encoder_load(vr_engine* e, const vr_bert_desc* d, const void* const* t, int n_tensors, int mem) {
+  return build_encoder(e, &e->encoder, d, t, n_tensors, mem);
+}
+
+int reranker_load(vr_engine* e, const vr_bert_desc* d, const void* const* t, int n_tensors, int mem) {
+  VR_CHECK(d->struct_size == static_cast<int32_t>(sizeof(vr_bert_desc)), "vr_bert_desc size mismatch");
+  VR_CHECK(d->pooling == VR_POOL_CLS && d->normalize == 0, "a reranker pools the [CLS] row (pooling 1) without normalising");
+  VR_CHECK(d->type_vocab >= 2, "a reranker needs two token types (type_vocab %d)", d->type_vocab);
+  VR_CHECK(d->layers >= 1 && n_tensors == 5 + 16 * d->layers + 4, "expected %d tensors, got %d", 5 + 16 * d->layers + 4,
+           n_tensors);
+  for (int i = 0; i < 4; ++i) VR_CHECK(t[n_tensors - 4 + i] != nullptr, "tensor %d is null", n_tensors - 4 + i);
+  VR_TRY(build_encoder(e, &e->reranker, d, t, n_tensors - 4, mem));
+  Encoder* enc = static_cast<Encoder*>(e->reranker);
+  const int H = d->hidden;
+  const void* const* h = t + n_tensors - 4;
+  const int rc = [&]() -> int {
+    VR_TRY(dev_alloc_copy(e, enc, h[0], static_cast<size_t>(H) * H, mem, &enc->pool_w));
+    VR_TRY(dev_alloc_copy(e, enc, h[1], H, mem, &enc->pool_b));
+    VR_TRY(dev_alloc_copy(e, enc, h[2], H, mem, &enc->cls_w));
+    VR_TRY(dev_alloc_copy(e, enc, h[3], 1, mem, &enc->cls_b));
+    VR_HIP(hipStreamSynchronize(e->stream));
+    return 0;
+  }();
+  if (rc != 0) free_encoder(&e->reranker);
+  return rc;
+}
+
+bool reranker_loaded(vr_engine* e) { return e->reranker != nullptr; }
+
 static int ensure_workspace(vr_engine* e, Encoder* enc, int64_t tokens) {
   if (tokens <= enc->ws_tokens) return 0;
   // Headroom: batches of the same chunk count differ by a per cent or two in tokens, and a workspace that fits the
@@ -3503,7 +3591,7 @@ static int ensure_workspace(vr_engine* e, Encoder* enc, int64_t tokens) {
 
 // forward of sequences [seq0, seq1) whose tokens are ids_dev[tok_base .. tok_base + T)
 static int forward_chunk(vr_engine* e, Encoder* enc, const int32_t* ids_dev, const int32_t* cu_dev,
-                         int n_seq_total, int seq0, int seq1, int tok_base, int T, int max_len,
+                         const int32_t* seg_dev, int n_seq_total, int seq0, int seq1, int tok_base, int T, int max_len,
                          double attn_flop, float* out_dev) {
   const vr_bert_desc& d = enc->d;
   const int H = d.hidden, I = d.intermediate, nh = d.heads, dh = H / nh;
@@ -3555,9 +3643,15 @@ static int forward_chunk(vr_engine* e, Encoder* enc, const int32_t* ids_dev, con
   float2* part = reinterpret_cast<float2*>(enc->lnpart);
   const int segs = H / 64;
   const unsigned fin_blocks = static_cast<unsigned>((T + 255) / 256);
-  hipLaunchKernelGGL(embed_ln_kernel, dim3(row_blocks), dim3(256), 0, s, ids_dev, cu_dev, n_seq_total,
-                     tok_base, T, H, d.vocab, enc->word, enc->pos, enc->type, enc->lng, enc->lnb, d.eps,
-                     lnfuse ? nullptr : enc->x, xh, xl, lnfuse ? enc->x : nullptr, lnfuse ? stat_b : nullptr);
+  if (seg_dev)
+    hipLaunchKernelGGL(embed_ln_kernel<true>, dim3(row_blocks), dim3(256), 0, s, ids_dev, cu_dev, n_seq_total,
+                       tok_base, T, H, d.vocab, enc->word, enc->pos, enc->type, enc->lng, enc->lnb, d.eps,
+                       lnfuse ? nullptr : enc->x, xh, xl, lnfuse ? enc->x : nullptr, lnfuse ? stat_b : nullptr, seg_dev);
+  else
+    hipLaunchKernelGGL(embed_ln_kernel<false>, dim3(row_blocks), dim3(256), 0, s, ids_dev, cu_dev, n_seq_total,
+                       tok_base, T, H, d.vocab, enc->word, enc->pos, enc->type, enc->lng, enc->lnb, d.eps,
+                       lnfuse ? nullptr : enc->x, xh, xl, lnfuse ? enc->x : nullptr, lnfuse ? stat_b : nullptr,
+                       static_cast<const int32_t*>(nullptr));
   const int qblocks = (max_len + 63) / 64;
   const float scale = 1.0f / sqrtf(static_cast<float>(dh));
   // CLS pooling reads one row per sequence, so everything after the LAST layer's attention is needed
@@ -3582,14 +3676,14 @@ static int forward_chunk(vr_engine* e, Encoder* enc, const int32_t* ids_dev, con
       VR_TRY(launch_skinny_ln(e, EPI_BIAS_F16, cur.pre, cur.g, cur.b, d.eps, const_cast<float2*>(cur.stat), w.s_qkv.hi,
                               w.s_qkv.unscale, w.bqkv, reinterpret_cast<half_t*>(enc->qkv), T, 3 * H, H));
     else if (plain && fold_big && li > 0)  // xh holds the f16 PRE-LN rows the previous FFN-down epilogue stored
-      VR_TRY(launch_gemm_f16x3(e, EPI_FOLD_F16, xh, nullptr, w.s_qkv_f.hi, nullptr, w.s_qkv_f.unscale, w.c_qkv, nullptr,
+      VR_TRY(launch_gemm_f16x3(e, enc, EPI_FOLD_F16, xh, nullptr, w.s_qkv_f.hi, nullptr, w.s_qkv_f.unscale, w.c_qkv, nullptr,
                                nullptr, reinterpret_cast<half_t*>(enc->qkv), nullptr, T, 3 * H, H, 1, cur.stat, w.cs_qkv,
                                nullptr));
     else if (plain)  // Q, K, V as plain f16 rows for attention_f16_kernel
-      VR_TRY(launch_gemm_f16x3(e, EPI_BIAS_F16, xh, xl, w.s_qkv.hi, w.s_qkv.lo, w.s_qkv.unscale, w.bqkv, nullptr,
+      VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_F16, xh, xl, w.s_qkv.hi, w.s_qkv.lo, w.s_qkv.unscale, w.bqkv, nullptr,
                                nullptr, reinterpret_cast<half_t*>(enc->qkv), nullptr, T, 3 * H, H, passes));
     else if (split)
-      VR_TRY(launch_gemm_f16x3(e, EPI_BIAS, xh, xl, w.s_qkv.hi, w.s_qkv.lo, w.s_qkv.unscale, w.bqkv, nullptr,
+      VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS, xh, xl, w.s_qkv.hi, w.s_qkv.lo, w.s_qkv.unscale, w.bqkv, nullptr,
                                enc->qkv, nullptr, nullptr, T, 3 * H, H, passes));
     else
       VR_TRY(launch_gemm(e, EPI_BIAS, enc->x, w.wqkv, w.bqkv, nullptr, enc->qkv, T, 3 * H, H));
@@ -3658,16 +3752,16 @@ static int forward_chunk(vr_engine* e, Encoder* enc, const int32_t* ids_dev, con
       half_t* cch = reinterpret_cast<half_t*>(ctxc);
       half_t* fch = reinterpret_cast<half_t*>(ffnc);
       if (split)
-        VR_TRY(launch_gemm_f16x3(e, EPI_BIAS_RESIDUAL, cch, plain ? nullptr : cch + 8, w.s_o.hi, w.s_o.lo, w.s_o.unscale, w.bo, xc, tmpc,
+        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_RESIDUAL, cch, plain ? nullptr : cch + 8, w.s_o.hi, w.s_o.lo, w.s_o.unscale, w.bo, xc, tmpc,
                                  nullptr, nullptr, n_seq, H, H, passes));
       else
         VR_TRY(launch_gemm(e, EPI_BIAS_RESIDUAL, ctxc, w.wo, w.bo, xc, tmpc, n_seq, H, H));
       hipLaunchKernelGGL(layernorm_kernel, dim3(cblocks), dim3(256), 0, s, tmpc, n_seq, H, w.ln1g, w.ln1b, d.eps, xc,
                          split ? xch : nullptr, split && !plain ? xch + 8 : nullptr, static_cast<float2*>(nullptr));
       if (split) {
-        VR_TRY(launch_gemm_f16x3(e, EPI_BIAS_GELU, xch, plain ? nullptr : xch + 8, w.s_1.hi, w.s_1.lo, w.s_1.unscale, w.b1, nullptr, nullptr,
+        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_GELU, xch, plain ? nullptr : xch + 8, w.s_1.hi, w.s_1.lo, w.s_1.unscale, w.b1, nullptr, nullptr,
                                  fch, plain ? nullptr : fch + 8, n_seq, I, H, passes));
-        VR_TRY(launch_gemm_f16x3(e, EPI_BIAS_RESIDUAL, fch, plain ? nullptr : fch + 8, w.s_2.hi, w.s_2.lo, w.s_2.unscale, w.b2, xc, tmpc,
+        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_RESIDUAL, fch, plain ? nullptr : fch + 8, w.s_2.hi, w.s_2.lo, w.s_2.unscale, w.b2, xc, tmpc,
                                  nullptr, nullptr, n_seq, H, I, passes));
       } else {
         VR_TRY(launch_gemm(e, EPI_BIAS_GELU, xc, w.w1, w.b1, nullptr, ffnc, n_seq, I, H));
@@ -3688,16 +3782,16 @@ static int forward_chunk(vr_engine* e, Encoder* enc, const int32_t* ids_dev, con
       if (res16) {
         // f16 residual stream: residual rows are f32 only in layer 0 (the embedding sum), the pre-LN rows go out
         // as f16 into xh, in place where the residual came from there
-        VR_TRY(launch_gemm_f16x3(e, cur16 ? EPI_RLS_R16_O16 : EPI_RLS_R32_O16, ch, nullptr, w.s_o.hi, nullptr,
+        VR_TRY(launch_gemm_f16x3(e, enc, cur16 ? EPI_RLS_R16_O16 : EPI_RLS_R32_O16, ch, nullptr, w.s_o.hi, nullptr,
                                  w.s_o.unscale, w.bo, cur16 ? reinterpret_cast<const float*>(xh) : cur.pre, nullptr, xh,
                                  reinterpret_cast<half_t*>(part), T, H, H, 1, cur.stat, cur.g, cur.b));
         hipLaunchKernelGGL(ln_finalize_kernel, dim3(fin_blocks), dim3(256), 0, s, part, T, segs, H, d.eps, s1);
       } else if (fold_big) {
-        VR_TRY(launch_gemm_f16x3(e, EPI_BIAS_RESIDUAL_LN_STATS, ch, nullptr, w.s_o.hi, nullptr, w.s_o.unscale, w.bo, cur.pre,
+        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_RESIDUAL_LN_STATS, ch, nullptr, w.s_o.hi, nullptr, w.s_o.unscale, w.bo, cur.pre,
                                  t1, xh, reinterpret_cast<half_t*>(part), T, H, H, 1, cur.stat, cur.g, cur.b));
         hipLaunchKernelGGL(ln_finalize_kernel, dim3(fin_blocks), dim3(256), 0, s, part, T, segs, H, d.eps, s1);
       } else
-      VR_TRY(launch_gemm_f16x3(e, EPI_BIAS_RESIDUAL_LN, ch, nullptr, w.s_o.hi, nullptr, w.s_o.unscale, w.bo, cur.pre, t1,
+      VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_RESIDUAL_LN, ch, nullptr, w.s_o.hi, nullptr, w.s_o.unscale, w.bo, cur.pre, t1,
                                nullptr, nullptr, T, H, H, 1, cur.stat, cur.g, cur.b));
       if (fold_ln || fold_big)
         ;  // the attention-output LayerNorm runs inside the FFN-up projection below
@@ -3713,20 +3807,20 @@ static int forward_chunk(vr_engine* e, Encoder* enc, const int32_t* ids_dev, con
       if (fold_ln)
         VR_TRY(launch_skinny_ln(e, EPI_BIAS_GELU, t1, w.ln1g, w.ln1b, d.eps, s1, w.s_1.hi, w.s_1.unscale, w.b1, fh, T, I, H));
       else if (fold_big)
-        VR_TRY(launch_gemm_f16x3(e, EPI_FOLD_GELU, xh, nullptr, w.s_1_f.hi, nullptr, w.s_1_f.unscale, w.c_1, nullptr, nullptr,
+        VR_TRY(launch_gemm_f16x3(e, enc, EPI_FOLD_GELU, xh, nullptr, w.s_1_f.hi, nullptr, w.s_1_f.unscale, w.c_1, nullptr, nullptr,
                                  fh, nullptr, T, I, H, 1, s1, w.cs_1, nullptr));
       else
-      VR_TRY(launch_gemm_f16x3(e, EPI_BIAS_GELU, xh, nullptr, w.s_1.hi, nullptr, w.s_1.unscale, w.b1, nullptr, nullptr, fh,
+      VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_GELU, xh, nullptr, w.s_1.hi, nullptr, w.s_1.unscale, w.b1, nullptr, nullptr, fh,
                                nullptr, T, I, H, 1));
       if (res16)  // (the last layer of a mean-pooled model also writes f32 rows: the final LayerNorm reads them)
-        VR_TRY(launch_gemm_f16x3(e, last ? EPI_RLS_R16_O32 : EPI_RLS_R16_O16, fh, nullptr, w.s_2.hi, nullptr, w.s_2.unscale,
+        VR_TRY(launch_gemm_f16x3(e, enc, last ? EPI_RLS_R16_O32 : EPI_RLS_R16_O16, fh, nullptr, w.s_2.hi, nullptr, w.s_2.unscale,
                                  w.b2, reinterpret_cast<const float*>(xh), last ? t2 : nullptr, xh,
                                  reinterpret_cast<half_t*>(part), T, H, I, 1, mid.stat, mid.g, mid.b));
       else if (fold_big)
-        VR_TRY(launch_gemm_f16x3(e, EPI_BIAS_RESIDUAL_LN_STATS, fh, nullptr, w.s_2.hi, nullptr, w.s_2.unscale, w.b2, mid.pre,
+        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_RESIDUAL_LN_STATS, fh, nullptr, w.s_2.hi, nullptr, w.s_2.unscale, w.b2, mid.pre,
                                  t2, xh, reinterpret_cast<half_t*>(part), T, H, I, 1, mid.stat, mid.g, mid.b));
       else
-      VR_TRY(launch_gemm_f16x3(e, EPI_BIAS_RESIDUAL_LN, fh, nullptr, w.s_2.hi, nullptr, w.s_2.unscale, w.b2, mid.pre, t2,
+      VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_RESIDUAL_LN, fh, nullptr, w.s_2.hi, nullptr, w.s_2.unscale, w.b2, mid.pre, t2,
                                nullptr, nullptr, T, H, I, 1, mid.stat, mid.g, mid.b));
       // the last LayerNorm of the network also stores its f32 rows (into the free buffer): pooling reads them
       if (fold_ln && !last)
@@ -3745,16 +3839,16 @@ static int forward_chunk(vr_engine* e, Encoder* enc, const int32_t* ids_dev, con
       continue;
     }
     if (split)
-      VR_TRY(launch_gemm_f16x3(e, EPI_BIAS_RESIDUAL, ch, cl, w.s_o.hi, w.s_o.lo, w.s_o.unscale, w.bo, enc->x,
+      VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_RESIDUAL, ch, cl, w.s_o.hi, w.s_o.lo, w.s_o.unscale, w.bo, enc->x,
                                enc->tmp, nullptr, nullptr, T, H, H, passes));
     else
       VR_TRY(launch_gemm(e, EPI_BIAS_RESIDUAL, enc->ctx, w.wo, w.bo, enc->x, enc->tmp, T, H, H));
     hipLaunchKernelGGL(layernorm_kernel, dim3(row_blocks), dim3(256), 0, s, enc->tmp, T, H, w.ln1g, w.ln1b,
                        d.eps, enc->x, xh, xl, static_cast<float2*>(nullptr));
     if (split) {
-      VR_TRY(launch_gemm_f16x3(e, EPI_BIAS_GELU, xh, xl, w.s_1.hi, w.s_1.lo, w.s_1.unscale, w.b1, nullptr,
+      VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_GELU, xh, xl, w.s_1.hi, w.s_1.lo, w.s_1.unscale, w.b1, nullptr,
                                nullptr, fh, fl, T, I, H, passes));
-      VR_TRY(launch_gemm_f16x3(e, EPI_BIAS_RESIDUAL, fh, fl, w.s_2.hi, w.s_2.lo, w.s_2.unscale, w.b2, enc->x,
+      VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_RESIDUAL, fh, fl, w.s_2.hi, w.s_2.lo, w.s_2.unscale, w.b2, enc->x,
                                enc->tmp, nullptr, nullptr, T, H, I, passes));
     } else {
       VR_TRY(launch_gemm(e, EPI_BIAS_GELU, enc->x, w.w1, w.b1, nullptr, enc->ffn, T, I, H));
@@ -3775,30 +3869,42 @@ static int forward_chunk(vr_engine* e, Encoder* enc, const int32_t* ids_dev, con
 // VR_CHUNK_TOKENS overrides it for experiments.
 static const int64_t kMaxChunkTokens = getenv("VR_CHUNK_TOKENS") ? atoll(getenv("VR_CHUNK_TOKENS")) : 262144;
 
-int encoder_encode(vr_engine* e, const int32_t* ids, const int32_t* offsets, int n_seq, int mem,
-                   float* out, int out_mem) {
-  Encoder* enc = static_cast<Encoder*>(e->encoder);
-  VR_CHECK(enc != nullptr, "no encoder loaded (vr_encoder_load)");
-  if (n_seq <= 0) return 0;
-  const int H = enc->d.hidden;
-  // offsets are needed on the host to cut chunks
-  std::vector<int32_t> cu_host(static_cast<size_t>(n_seq) + 1);
-  const int32_t* ids_dev = ids;
-  const int32_t* cu_dev = offsets;
+// The host copy of the offsets (needed to cut chunks), every length and segment start checked: before any work
+// is queued when the arguments are in host memory
+static int read_offsets(vr_engine* e, Encoder* enc, const int32_t* offsets, const int32_t* seg_b, int n_seq, int mem,
+                        std::vector<int32_t>* cu_host) {
+  cu_host->resize(static_cast<size_t>(n_seq) + 1);
+  std::vector<int32_t> seg_host(seg_b ? static_cast<size_t>(n_seq) : 0);
   if (mem == VR_MEM_HOST) {
-    memcpy(cu_host.data(), offsets, sizeof(int32_t) * cu_host.size());
+    memcpy(cu_host->data(), offsets, sizeof(int32_t) * cu_host->size());
+    if (seg_b) memcpy(seg_host.data(), seg_b, sizeof(int32_t) * seg_host.size());
   } else {
-    VR_HIP(hipMemcpyAsync(cu_host.data(), offsets, sizeof(int32_t) * cu_host.size(), hipMemcpyDeviceToHost,
+    VR_HIP(hipMemcpyAsync(cu_host->data(), offsets, sizeof(int32_t) * cu_host->size(), hipMemcpyDeviceToHost,
                           e->stream));
+    if (seg_b)
+      VR_HIP(hipMemcpyAsync(seg_host.data(), seg_b, sizeof(int32_t) * seg_host.size(), hipMemcpyDeviceToHost, e->stream));
     VR_HIP(hipStreamSynchronize(e->stream));
   }
-  VR_CHECK(cu_host[0] == 0, "offsets must start at 0");
-  const int64_t T_all = cu_host[static_cast<size_t>(n_seq)];
+  VR_CHECK((*cu_host)[0] == 0, "offsets must start at 0");
   for (int i = 0; i < n_seq; ++i) {
-    int len = cu_host[static_cast<size_t>(i) + 1] - cu_host[static_cast<size_t>(i)];
+    int len = (*cu_host)[static_cast<size_t>(i) + 1] - (*cu_host)[static_cast<size_t>(i)];
     VR_CHECK(len >= 1 && len <= enc->d.max_pos, "sequence %d has %d tokens (1..%d allowed)", i, len,
              enc->d.max_pos);
+    VR_CHECK(!seg_b || (seg_host[static_cast<size_t>(i)] >= 1 && seg_host[static_cast<size_t>(i)] <= len),
+             "sequence %d: seg_b %d not in 1..%d", i, seg_b ? seg_host[static_cast<size_t>(i)] : 0, len);
   }
+  return 0;
+}
+
+// The forward pass of n_seq checked sequences (cu_host: their offsets), one pooled row each into out_dev (device).
+// seg_b (or null): each sequence's first segment-B position.
+static int forward_all(vr_engine* e, Encoder* enc, const int32_t* ids, const int32_t* offsets, const int32_t* seg_b,
+                       int n_seq, int mem, const std::vector<int32_t>& cu_host, float* out_dev) {
+  const int H = enc->d.hidden;
+  const int64_t T_all = cu_host[static_cast<size_t>(n_seq)];
+  const int32_t* ids_dev = ids;
+  const int32_t* cu_dev = offsets;
+  const int32_t* seg_dev = seg_b;
   if (mem == VR_MEM_HOST) {
     VR_TRY(enc->ids.grow(T_all, 0, e->stream));
     VR_TRY(enc->cu.grow(n_seq + 1, 0, e->stream));
@@ -3808,11 +3914,12 @@ int encoder_encode(vr_engine* e, const int32_t* ids, const int32_t* offsets, int
                           e->stream));
     ids_dev = enc->ids.p;
     cu_dev = enc->cu.p;
-  }
-  float* out_dev = out;
-  if (out_mem == VR_MEM_HOST) {
-    VR_TRY(enc->out.grow(static_cast<int64_t>(n_seq) * H, 0, e->stream));
-    out_dev = enc->out.p;
+    if (seg_b) {
+      VR_TRY(enc->seg.grow(n_seq, 0, e->stream));
+      VR_HIP(hipMemcpyAsync(enc->seg.p, seg_b, sizeof(int32_t) * static_cast<size_t>(n_seq), hipMemcpyHostToDevice,
+                            e->stream));
+      seg_dev = enc->seg.p;
+    }
   }
   int seq0 = 0;
   while (seq0 < n_seq) {
@@ -3838,11 +3945,12 @@ int encoder_encode(vr_engine* e, const int32_t* ids, const int32_t* offsets, int
     bool done = false;
     if (graphable) {
       if (enc->graphs.size() > 256) invalidate_graphs(enc);  // (shapes are few in practice; start over rather than track recency)
-      Encoder::GraphEntry& g = enc->graphs[Encoder::GraphKey{static_cast<int>(T), n_seq, max_len, ids_dev, cu_dev, out_dev}];
+      Encoder::GraphEntry& g =
+          enc->graphs[Encoder::GraphKey{static_cast<int>(T), n_seq, max_len, ids_dev, cu_dev, seg_dev, out_dev}];
       if (!g.exec && !g.bad && g.seen >= 1) {
         if (hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-          const int rc = forward_chunk(e, enc, ids_dev, cu_dev, n_seq, seq0, seq1, 0, static_cast<int>(T), max_len,
-                                       4.0 * H * len2, out_dev);
+          const int rc = forward_chunk(e, enc, ids_dev, cu_dev, seg_dev, n_seq, seq0, seq1, 0, static_cast<int>(T),
+                                       max_len, 4.0 * H * len2, out_dev);
           hipGraph_t graph = nullptr;
           const hipError_t end = hipStreamEndCapture(e->stream, &graph);
           if (rc != 0 || end != hipSuccess || !graph ||
@@ -3864,18 +3972,61 @@ int encoder_encode(vr_engine* e, const int32_t* ids, const int32_t* offsets, int
       ++g.seen;
     }
     if (!done)
-      VR_TRY(forward_chunk(e, enc, ids_dev, cu_dev, n_seq, seq0, seq1, cu_host[static_cast<size_t>(seq0)],
+      VR_TRY(forward_chunk(e, enc, ids_dev, cu_dev, seg_dev, n_seq, seq0, seq1, cu_host[static_cast<size_t>(seq0)],
                            static_cast<int>(T), max_len, 4.0 * H * len2, out_dev));
     seq0 = seq1;
   }
+  return 0;
+}
+
+// n_floats results from out_dev to the caller's host `out` (out_mem == VR_MEM_HOST), or the stream drained while
+// host inputs may still be read
+static int finish(vr_engine* e, float* out, const float* out_dev, int64_t n_floats, int mem, int out_mem) {
   if (out_mem == VR_MEM_HOST) {
-    VR_HIP(hipMemcpyAsync(out, out_dev, sizeof(float) * static_cast<size_t>(n_seq) * H, hipMemcpyDeviceToHost,
-                          e->stream));
+    VR_HIP(hipMemcpyAsync(out, out_dev, sizeof(float) * static_cast<size_t>(n_floats), hipMemcpyDeviceToHost, e->stream));
     VR_HIP(hipStreamSynchronize(e->stream));
   } else if (mem == VR_MEM_HOST) {
     VR_HIP(hipStreamSynchronize(e->stream));
   }
   return 0;
+}
+
+int encoder_encode(vr_engine* e, const int32_t* ids, const int32_t* offsets, int n_seq, int mem,
+                   float* out, int out_mem) {
+  Encoder* enc = static_cast<Encoder*>(e->encoder);
+  VR_CHECK(enc != nullptr, "no encoder loaded (vr_encoder_load)");
+  if (n_seq <= 0) return 0;
+  const int H = enc->d.hidden;
+  std::vector<int32_t> cu_host;
+  VR_TRY(read_offsets(e, enc, offsets, nullptr, n_seq, mem, &cu_host));
+  float* out_dev = out;
+  if (out_mem == VR_MEM_HOST) {
+    VR_TRY(enc->out.grow(static_cast<int64_t>(n_seq) * H, 0, e->stream));
+    out_dev = enc->out.p;
+  }
+  VR_TRY(forward_all(e, enc, ids, offsets, nullptr, n_seq, mem, cu_host, out_dev));
+  return finish(e, out, out_dev, static_cast<int64_t>(n_seq) * H, mem, out_mem);
+}
+
+int encoder_rerank(vr_engine* e, const int32_t* ids, const int32_t* offsets, const int32_t* seg_b, int n_seq, int mem,
+                   float* out, int out_mem) {
+  Encoder* enc = static_cast<Encoder*>(e->reranker);
+  VR_CHECK(enc != nullptr, "no reranker loaded (vr_reranker_load)");
+  if (n_seq <= 0) return 0;
+  const int H = enc->d.hidden;
+  std::vector<int32_t> cu_host;
+  VR_TRY(read_offsets(e, enc, offsets, seg_b, n_seq, mem, &cu_host));
+  VR_TRY(enc->rows.grow(static_cast<int64_t>(n_seq) * H, 0, e->stream));
+  float* out_dev = out;
+  if (out_mem == VR_MEM_HOST) {
+    VR_TRY(enc->out.grow(n_seq, 0, e->stream));
+    out_dev = enc->out.p;
+  }
+  VR_TRY(forward_all(e, enc, ids, offsets, seg_b, n_seq, mem, cu_host, enc->rows.p));
+  hipLaunchKernelGGL(rerank_head_kernel, dim3(static_cast<unsigned>((n_seq + 15) / 16)), dim3(256), 0, e->stream,
+                     enc->rows.p, n_seq, H, enc->pool_w, enc->pool_b, enc->cls_w, enc->cls_b, out_dev);
+  VR_HIP(hipGetLastError());
+  return finish(e, out, out_dev, n_seq, mem, out_mem);
 }
 
 }  // namespace vr

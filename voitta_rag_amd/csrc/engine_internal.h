@@ -337,6 +337,7 @@ struct vr_engine {
   size_t pinned_bytes = 0;
 
   void* encoder = nullptr;   // vr::Encoder (encoder.hip)
+  void* reranker = nullptr;  // vr::Encoder of a cross-encoder (vr_reranker_load), beside the embedder
   void* profiler = nullptr;  // vr::Profiler (profile.hip)
 };
 
@@ -470,7 +471,11 @@ int sparse_lookup_df(vr_engine* e, const int32_t* ids_host, int n, int32_t* out_
 int encoder_load(vr_engine* e, const vr_bert_desc* d, const void* const* tensors, int n_tensors, int mem);
 int encoder_encode(vr_engine* e, const int32_t* ids, const int32_t* offsets, int n_seq, int mem,
                    float* out, int out_mem);
-void encoder_release(vr_engine* e);
+void encoder_release(vr_engine* e);  // the embedder and the reranker
+int reranker_load(vr_engine* e, const vr_bert_desc* d, const void* const* tensors, int n_tensors, int mem);
+bool reranker_loaded(vr_engine* e);
+int encoder_rerank(vr_engine* e, const int32_t* ids, const int32_t* offsets, const int32_t* seg_b, int n_seq, int mem,
+                   float* out, int out_mem);  // out: n_seq logits
 int encoder_hidden(vr_engine* e);  // 0 when no encoder is loaded
 
 // ---- profile.hip: HIP-event timing of one launch (no-ops unless vr_profile(e, 1))

@@ -14,7 +14,8 @@
 //                     general category P*; every punctuation character is its own word)
 //   WordPiece         greedy longest match, continuation prefix "##"; a word of more than 100
 //                     characters, or with an unmatched remainder, becomes [UNK]
-//   post              [CLS] ids... [SEP], ids truncated on the right to max_len - 2
+//   post              [CLS] ids... [SEP], ids truncated on the right to max_len - 2; a pair (vr_wordpiece_encode_pairs)
+//                     is [CLS] A [SEP] B [SEP], truncated LongestFirst to max_len - 3 ids of A and B together
 // Pinned against the HF `tokenizers` library itself on synthetic vocabularies and adversarial
 // Unicode text (tests/test_wordpiece_cpu.py).
 
@@ -22,6 +23,7 @@
 #include <cstdint>
 #include <cstring>
 #include <string>
+#include <string_view>
 #include <unordered_map>
 #include <vector>
 
@@ -256,18 +258,16 @@ void wordpiece(const vr_wordpiece& t, const u32s& text, size_t w0, size_t w1, st
   }
 }
 
-void encode_one(const vr_wordpiece& t, const char* s, size_t n, int32_t max_len, std::vector<int32_t>* ids) {
+// the WordPiece ids of one text, appended to *ids until it holds `cap` or more
+void pieces(const vr_wordpiece& t, const char* s, size_t n, size_t cap, std::vector<int32_t>* ids) {
   u32s raw, text;
   decode_utf8(s, n, &raw);
   normalize(t, raw, &text);
-  ids->clear();
-  ids->push_back(t.cls);
   std::string buf;
   std::vector<uint32_t> pos;
-  const size_t budget = max_len > 2 ? static_cast<size_t>(max_len) - 1 : 1;  // ids before [SEP]
   size_t i = 0;
   const size_t len = text.size();
-  while (i < len && ids->size() < budget + 64) {  // (+64: a word may add several pieces; trimmed below)
+  while (i < len && ids->size() < cap) {
     if (is_white_space(text[i])) {
       ++i;
       continue;
@@ -282,8 +282,30 @@ void encode_one(const vr_wordpiece& t, const char* s, size_t n, int32_t max_len,
     wordpiece(t, text, i, j, ids, &buf, &pos);
     i = j;
   }
+}
+
+void encode_one(const vr_wordpiece& t, const char* s, size_t n, int32_t max_len, std::vector<int32_t>* ids) {
+  ids->clear();
+  ids->push_back(t.cls);
+  const size_t budget = max_len > 2 ? static_cast<size_t>(max_len) - 1 : 1;  // ids before [SEP]
+  pieces(t, s, n, budget + 64, ids);  // (+64: a word may add several pieces; trimmed below)
   if (max_len >= 2 && ids->size() > budget) ids->resize(budget);
   ids->push_back(t.sep);
+}
+
+// HF tokenizers' LongestFirst truncation of a pair to m ids (the specials already taken off max_len): the shorter side
+// keeps min(n_short, m/2) or all of itself, the longer side the rest; when both exceed m/2 the longer one gets the odd id
+void longest_first(size_t* na, size_t* nb, size_t m) {
+  if (*na + *nb <= m) return;
+  const bool swap = *na > *nb;
+  size_t n1 = swap ? *nb : *na, n2 = swap ? *na : *nb;
+  n2 = n1 > m ? n1 : std::max(n1, m - n1);
+  if (n1 + n2 > m) {
+    n1 = m / 2;
+    n2 = n1 + m % 2;
+  }
+  *na = std::min(*na, swap ? n2 : n1);
+  *nb = std::min(*nb, swap ? n1 : n2);
 }
 
 }  // namespace
@@ -344,6 +366,68 @@ int vr_wordpiece_encode(const vr_wordpiece* t, const char* const* texts, const i
   if (total > capacity) {
     vr::set_error("output buffer holds %lld ids, %lld needed", static_cast<long long>(capacity), static_cast<long long>(total));
     return -2;  // offsets and *needed are valid: call again with a larger buffer
+  }
+  return 0;
+}
+
+int vr_wordpiece_encode_pairs(const vr_wordpiece* t, const char* const* a_texts, const int64_t* a_lens,
+                              const char* const* b_texts, const int64_t* b_lens, int64_t n, int32_t max_len,
+                              int64_t* out_offsets, int32_t* out_ids, int32_t* out_seg_b, int64_t capacity,
+                              int64_t* needed) {
+  VR_CHECK(t && n >= 0 && (n == 0 || (a_texts && a_lens && b_texts && b_lens)) && out_offsets && needed, "bad arguments");
+  VR_CHECK(max_len >= 3, "max_len %d cannot hold [CLS] and two [SEP]", max_len);
+  for (int64_t i = 0; i < n; ++i)
+    VR_CHECK(a_texts[i] && b_texts[i] && a_lens[i] >= 0 && b_lens[i] >= 0, "pair %lld: null text or negative length",
+             static_cast<long long>(i));
+  // every distinct A text once (a question is paired with each of its candidates)
+  std::unordered_map<std::string_view, int64_t> first;
+  std::vector<int64_t> a_of(static_cast<size_t>(n));
+  std::vector<int64_t> uniq;
+  for (int64_t i = 0; i < n; ++i) {
+    auto it = first.emplace(std::string_view(a_texts[i], static_cast<size_t>(a_lens[i])), static_cast<int64_t>(uniq.size()));
+    if (it.second) uniq.push_back(i);
+    a_of[static_cast<size_t>(i)] = it.first->second;
+  }
+  // both sides in full: where the truncation splits depends on both untruncated lengths
+  const size_t m = static_cast<size_t>(max_len) - 3;
+  std::vector<std::vector<int32_t>> a_ids(uniq.size()), b_ids(static_cast<size_t>(n));
+  vr::parallel_for(static_cast<int64_t>(uniq.size()), 16, [&](int64_t u) {
+    const int64_t i = uniq[static_cast<size_t>(u)];
+    pieces(*t, a_texts[i], static_cast<size_t>(a_lens[i]), SIZE_MAX, &a_ids[static_cast<size_t>(u)]);
+  });
+  vr::parallel_for(n, 16, [&](int64_t i) {
+    pieces(*t, b_texts[i], static_cast<size_t>(b_lens[i]), SIZE_MAX, &b_ids[static_cast<size_t>(i)]);
+  });
+  std::vector<size_t> keep_a(static_cast<size_t>(n)), keep_b(static_cast<size_t>(n));
+  int64_t total = 0;
+  out_offsets[0] = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    size_t na = a_ids[static_cast<size_t>(a_of[static_cast<size_t>(i)])].size(), nb = b_ids[static_cast<size_t>(i)].size();
+    longest_first(&na, &nb, m);
+    keep_a[static_cast<size_t>(i)] = na;
+    keep_b[static_cast<size_t>(i)] = nb;
+    total += static_cast<int64_t>(na + nb + 3);
+    out_offsets[i + 1] = total;
+    if (out_seg_b) out_seg_b[i] = static_cast<int32_t>(na + 2);
+  }
+  if (out_ids && total <= capacity)
+    vr::parallel_for(n, 256, [&](int64_t i) {
+      const std::vector<int32_t>& a = a_ids[static_cast<size_t>(a_of[static_cast<size_t>(i)])];
+      const std::vector<int32_t>& b = b_ids[static_cast<size_t>(i)];
+      const size_t na = keep_a[static_cast<size_t>(i)], nb = keep_b[static_cast<size_t>(i)];
+      int32_t* o = out_ids + out_offsets[i];
+      *o++ = t->cls;
+      std::copy(a.begin(), a.begin() + static_cast<std::ptrdiff_t>(na), o);
+      o += na;
+      *o++ = t->sep;
+      std::copy(b.begin(), b.begin() + static_cast<std::ptrdiff_t>(nb), o);
+      o += nb;
+      *o = t->sep;
+    });
+  *needed = total;
+  if (total > capacity) {
+    vr::set_error("output buffer holds %lld ids, %lld needed", static_cast<long long>(capacity), static_cast<long long>(total));
+    return -2;  // offsets, seg_b and *needed are valid: call again with a larger buffer
   }
   return 0;
 }

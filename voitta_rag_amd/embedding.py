@@ -206,12 +206,16 @@ class EmbeddingService:
         return embeddings.tolist()
 
     def embed_query(self, query: str) -> list[float]:
+        question = query
         if "e5" in self.model_name.lower():  # embedding.py:82-83
             query = f"query: {query}"
         model = self.model
         if _deferred.enabled() and isinstance(model.tokenizer, WordPieceTokenizer):
-            return _deferred.QueryRef(model, query)  # encoded when looked at — or inside the search call it goes to
-        return _deferred.QueryEmbedding(model.encode(query, convert_to_numpy=True))
+            out = _deferred.QueryRef(model, query)  # encoded when looked at — or inside the search call it goes to
+        else:
+            out = _deferred.QueryEmbedding(model.encode(query, convert_to_numpy=True))
+        out.question = question  # the raw question, for a reranking search
+        return out
 
     def query_texts(self, queries: list[str]) -> list[str]:
         """The questions as the encoder sees them: with the e5 ``query: `` prefix, as embed_query applies it."""

@@ -69,9 +69,15 @@ def tensor_names(layers: int) -> list[str]:
     return names
 
 
+# a BertForSequenceClassification's head, after the encoder's tensors (vr_reranker_load)
+HEAD_NAMES = ["pooler.dense.weight", "pooler.dense.bias", "classifier.weight", "classifier.bias"]
+
+
 def expected_shape(desc: BertDesc, name: str) -> tuple:
     """Shape of a state-dict entry as the description implies it ([out, in] layout, as HF stores it)."""
     H, inter = desc.hidden, desc.intermediate
+    if name == "classifier.weight": return (1, H)
+    if name == "classifier.bias": return (1,)
     if name.endswith("word_embeddings.weight"): return (desc.vocab, H)
     if name.endswith("position_embeddings.weight"): return (desc.max_pos, H)
     if name.endswith("token_type_embeddings.weight"): return (desc.type_vocab, H)
@@ -94,7 +100,20 @@ def _find(state: dict, suffix: str):
 def load_encoder(engine, desc: BertDesc, state: dict) -> None:
     """state: HF BertModel state dict (any key prefix), values NumPy arrays or torch tensors.
     Tensors on the engine's GPU are passed as device pointers, everything else as host memory."""
-    names = tensor_names(desc.layers)
+    _load(engine, desc, state, tensor_names(desc.layers), engine._lib.vr_encoder_load)
+    engine.encoder_desc = desc
+
+
+def load_reranker(engine, desc: BertDesc, state: dict) -> None:
+    """state: a one-label HF BertForSequenceClassification state dict (any key prefix), the encoder's tensors plus the
+    pooler and the classifier. desc: CLS pooling, no normalisation."""
+    if desc.pooling != "cls" or desc.normalize:
+        raise ValueError("a reranker pools the [CLS] row without normalising it")
+    _load(engine, desc, state, tensor_names(desc.layers) + HEAD_NAMES, engine._lib.vr_reranker_load)
+    engine.reranker_desc = desc
+
+
+def _load(engine, desc: BertDesc, state: dict, names: list[str], load_fn) -> None:
     tensors = [_find(state, n) for n in names]
     # raw pointers cross the C-ABI next: a checkpoint whose config.json disagrees with its weights (padded or
     # resized vocabulary, another max_position_embeddings, ...) must fail HERE, not read past a buffer there
@@ -120,9 +139,7 @@ def load_encoder(engine, desc: BertDesc, state: dict) -> None:
         engine._follow(keep[0])
     arr = (C.c_void_p * len(ptrs))(*ptrs)
     cdesc = desc.to_c()
-    check(engine._lib.vr_encoder_load(engine.handle, C.byref(cdesc), arr, len(ptrs),
-                                      VR_MEM_DEVICE if on_device else VR_MEM_HOST))
-    engine.encoder_desc = desc
+    check(load_fn(engine.handle, C.byref(cdesc), arr, len(ptrs), VR_MEM_DEVICE if on_device else VR_MEM_HOST))
 
 
 def encode(engine, ids, offsets, out=None):

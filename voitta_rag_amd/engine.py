@@ -494,6 +494,40 @@ class Engine:
                    for i in range(n)]
         return (out, emb) if embeddings else out
 
+    # ---- cross-encoder reranking (vr_reranker_load is driven by encoder.load_reranker) ------------------------------
+    def rerank(self, ids, offsets, seg_b) -> np.ndarray:
+        """One f32 logit per pair sequence (vr_rerank): ids / offsets as encode's, seg_b[i] the position of sequence
+        i's first segment-B token. Host arrays."""
+        ids = _np(ids, np.int32)
+        off = _np(offsets, np.int32)
+        seg = _np(seg_b, np.int32)
+        n = off.shape[0] - 1
+        if seg.shape[0] != n:
+            raise ValueError(f"{n} sequences, {seg.shape[0]} seg_b entries")
+        out = np.empty(max(n, 1), np.float32)
+        check(self._lib.vr_rerank(self._h, ids.ctypes.data, off.ctypes.data, seg.ctypes.data, n, VR_MEM_HOST,
+                                  out.ctypes.data, VR_MEM_HOST))
+        return out[:n]
+
+    def rerank_text(self, tokenizer_handle, queries, candidates, max_len: int) -> list[np.ndarray]:
+        """Question q paired with each passage of candidates[q], all pairs scored in ONE call (vr_rerank_text).
+        -> one f32 logit array per question, in candidate order (empty for a question without candidates)."""
+        nq = len(queries)
+        if len(candidates) != nq:
+            raise ValueError(f"{nq} questions, {len(candidates)} candidate lists")
+        q = [t.encode("utf-8", "replace") for t in queries]
+        p = [t.encode("utf-8", "replace") for c in candidates for t in c]
+        cand_off = np.zeros(nq + 1, np.int64)
+        cand_off[1:] = np.cumsum([len(c) for c in candidates])
+        q_arr = (C.c_char_p * max(nq, 1))(*q)
+        p_arr = (C.c_char_p * max(len(p), 1))(*p)
+        q_len = np.array([len(t) for t in q] or [0], np.int64)
+        p_len = np.array([len(t) for t in p] or [0], np.int64)
+        out = np.empty(max(len(p), 1), np.float32)
+        check(self._lib.vr_rerank_text(self._h, tokenizer_handle, nq, q_arr, _ptr(q_len, C.c_int64), _ptr(cand_off, C.c_int64),
+                                       p_arr, _ptr(p_len, C.c_int64), int(max_len), _ptr(out, C.c_float)))
+        return [out[cand_off[i]:cand_off[i + 1]].copy() for i in range(nq)]
+
     # ---- many queries per call (BASELINE configs[4]: 1k batched hybrid queries) -----------------------------------
     @staticmethod
     def _sparse_csr(sparse_queries, nq: int):

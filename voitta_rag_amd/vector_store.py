@@ -10,6 +10,7 @@ get_* helpers swallow exceptions and return 0 / {} / [] / None (vector_store.py:
 from __future__ import annotations
 
 import contextlib
+import dataclasses
 import json
 import logging
 import os
@@ -789,13 +790,64 @@ class VectorStoreService:
             flt.date_start, flt.date_end, flt.date_field = date_start, date_end, date_field
         return None if flt.is_empty() else flt
 
+    # ---- second-stage reranking (VOITTA_RERANK_MODEL) -----------------------------------------------
+    unreranked_searches = 0  # reranking searches answered without it: the question's text was not known
+
+    def _reranker(self):
+        path = get_settings().rerank_model
+        if not path:
+            return None
+        from .reranker import get_reranker
+
+        return get_reranker(self._engine, path)
+
+    @staticmethod
+    def _rerank(rr, questions: list[str], candidates: list[list[StoredChunk]], limits: list[int]) -> list[list[StoredChunk]]:
+        """Every question's candidates rescored in ONE engine call (vr_rerank_text); the best `limit` of each, with
+        score = sigmoid(logit), best first (equal scores keep the first stage's order)."""
+        from .reranker import sigmoid
+
+        logits = rr.logits(questions, [[c.text for c in cands] for cands in candidates])
+        out = []
+        for cands, lg, limit in zip(candidates, logits, limits):
+            scores = sigmoid(lg)
+            order = np.argsort(-scores, kind="stable")[:limit]
+            out.append([dataclasses.replace(cands[i], score=float(scores[i])) for i in order])
+        return out
+
     def search(self, query_embedding: list[float], limit: int = 10, folder_filter: str | None = None,
                include_folders: list[str] | None = None, exclude_folders: list[str] | None = None,
                exclude_index_folders: list[str] | None = None,
                sparse_query: tuple[list[int], list[float]] | None = None, sparse_weight: float = 0.1,
                date_start: int | None = None, date_end: int | None = None,
                date_field: str | None = None) -> list[StoredChunk]:
-        """Dense or hybrid retrieval with the reference's branch selection (vector_store.py:560-619)."""
+        """Dense or hybrid retrieval with the reference's branch selection (vector_store.py:560-619). With
+        VOITTA_RERANK_MODEL set: the top VOITTA_RERANK_CANDIDATES of that, reranked by the cross-encoder, the best
+        `limit` returned. The question's text comes from the sparse query or from embed_query's result; a bare list
+        of floats without either is answered unreranked (counted in ``unreranked_searches``)."""
+        args = dict(folder_filter=folder_filter, include_folders=include_folders, exclude_folders=exclude_folders,
+                    exclude_index_folders=exclude_index_folders, sparse_query=sparse_query, sparse_weight=sparse_weight,
+                    date_start=date_start, date_end=date_end, date_field=date_field)
+        rr = self._reranker() if limit > 0 else None
+        if rr is None:
+            return self._search_first_stage(query_embedding, limit, **args)
+        question = getattr(sparse_query, "text", None) if isinstance(sparse_query, _deferred.SparseQueryRef) else None
+        if question is None:
+            question = getattr(query_embedding, "question", None)
+        if question is None:
+            VectorStoreService.unreranked_searches += 1
+            return self._search_first_stage(query_embedding, limit, **args)
+        from .reranker import rerank_candidates
+
+        cands = self._search_first_stage(query_embedding, rerank_candidates(get_settings().rerank_candidates, limit), **args)
+        return self._rerank(rr, [question], [cands], [limit])[0]
+
+    def _search_first_stage(self, query_embedding: list[float], limit: int = 10, folder_filter: str | None = None,
+                            include_folders: list[str] | None = None, exclude_folders: list[str] | None = None,
+                            exclude_index_folders: list[str] | None = None,
+                            sparse_query: tuple[list[int], list[float]] | None = None, sparse_weight: float = 0.1,
+                            date_start: int | None = None, date_end: int | None = None,
+                            date_field: str | None = None) -> list[StoredChunk]:
         if limit <= 0:
             return []  # Qdrant answers limit=0 with no points (a caller-supplied MCP argument, mcp_server.py:376,474)
         col = self._col
@@ -993,7 +1045,20 @@ class VectorStoreService:
         ``search_requests`` returns for it with ``query_embedding = embed_queries(queries)[i]`` and ``sparse_query`` =
         the sparse ``embed_query(query)``: one forward pass over all questions, whose embeddings stay on the device and
         feed the filtered batch searches. What an MCP server that gathers concurrent questions (mcp_server.py:469-485)
-        sends. Every filter is built under one lock, as in ``search_requests``."""
+        sends. Every filter is built under one lock, as in ``search_requests``. With VOITTA_RERANK_MODEL set: each
+        question's candidates as ``search`` fetches them, all reranked in one engine call (vr_rerank_text)."""
+        rr = self._reranker()
+        if rr is not None and requests:  # first stage at the candidate count, then one rerank call for all questions
+            from .reranker import rerank_candidates
+
+            c = get_settings().rerank_candidates
+            first = self._search_questions_first_stage(
+                [dict(r, limit=rerank_candidates(c, int(r.get("limit", 10))) if int(r.get("limit", 10)) > 0 else 0)
+                 for r in requests])
+            return self._rerank(rr, [r["query"] for r in requests], first, [int(r.get("limit", 10)) for r in requests])
+        return self._search_questions_first_stage(requests)
+
+    def _search_questions_first_stage(self, requests: list[dict]) -> list[list[StoredChunk]]:
         from .embedding import WordPieceTokenizer, get_embedding_service
 
         n = len(requests)

@@ -79,3 +79,27 @@ class WordPieceTokenizer:
                                            cap, C.byref(needed))
         check(rc)
         return ids[: int(needed.value)].copy(), off
+
+    def encode_pairs(self, a_texts: list[str], b_texts: list[str]) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """Cross-encoder input: sequence i is [CLS] a_i [SEP] b_i [SEP], truncated LongestFirst to max_length ids.
+        -> (ids int32[total], offsets int64[n + 1], seg_b int32[n]: the position of each sequence's first segment-B id)."""
+        n = len(a_texts)
+        if len(b_texts) != n:
+            raise ValueError(f"{n} first texts, {len(b_texts)} second texts")
+        ra = [t.encode("utf-8", "replace") for t in a_texts]
+        rb = [t.encode("utf-8", "replace") for t in b_texts]
+        aa = (C.c_char_p * max(n, 1))(*ra)
+        ba = (C.c_char_p * max(n, 1))(*rb)
+        al = np.asarray([len(b) for b in ra] or [0], np.int64)
+        bl = np.asarray([len(b) for b in rb] or [0], np.int64)
+        off = np.zeros(n + 1, np.int64)
+        seg = np.zeros(max(n, 1), np.int32)
+        cap = n * self.max_length
+        ids = np.empty(max(cap, 1), np.int32)
+        needed = C.c_int64()
+        p64 = C.POINTER(C.c_int64)
+        p32 = C.POINTER(C.c_int32)
+        check(self._lib.vr_wordpiece_encode_pairs(self._h, aa, al.ctypes.data_as(p64), ba, bl.ctypes.data_as(p64), n,
+                                                  self.max_length, off.ctypes.data_as(p64), ids.ctypes.data_as(p32),
+                                                  seg.ctypes.data_as(p32), cap, C.byref(needed)))
+        return ids[: int(needed.value)].copy(), off, seg[:n].copy()
