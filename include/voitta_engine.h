@@ -192,6 +192,44 @@ int vr_wordpiece_encode_pairs(const vr_wordpiece* t, const char* const* a_texts,
                               int64_t* out_offsets, int32_t* out_ids, int32_t* out_seg_b, int64_t capacity,
                               int64_t* needed);
 
+/* Host-only SentencePiece Unigram tokenizer (XLM-RoBERTa: multilingual-e5, bge-reranker), matching HF tokenizers as an
+ * XLM-R tokenizer.json configures it:
+ *   1. added tokens matched in the raw text (leftmost-longest; flags VR_ADDED_LSTRIP / _RSTRIP / _SINGLE_WORD as HF
+ *      honours them), the pieces between them tokenised separately;
+ *   2. the Precompiled normalizer: `charsmap` (the sentencepiece precompiled_charsmap bytes: a darts-clone trie and
+ *      its replacement strings) applied per extended grapheme cluster; charsmap_len 0 = no normalizer;
+ *   3. replace_spaces != 0: runs of two or more ' ' become one (Replace(" {2,}", " "));
+ *   4. pre_tokenizer VR_UNIGRAM_PRE_METASPACE (Metaspace "▁") or VR_UNIGRAM_PRE_WHITESPACE_METASPACE
+ *      (Sequence[WhitespaceSplit, Metaspace]), prepend_scheme VR_PREPEND_ALWAYS / _FIRST / _NEVER;
+ *   5. Unigram Viterbi over pieces[n_pieces] (NUL-terminated UTF-8, id = index) with f64 scores; characters no piece
+ *      covers become unk_id, consecutive ones fused;
+ *   6. bos A eos (single), bos A eos eos B eos (pair); truncation as vr_wordpiece_*, with 2 / 4 specials.
+ * added[n_added] / added_ids / added_flags: the added tokens (NUL-terminated UTF-8 content, id, flags). Malformed
+ * UTF-8 bytes become U+FFFD, as in vr_wordpiece_encode. Read-only after creation and thread-safe. */
+typedef struct vr_unigram vr_unigram;
+#define VR_UNIGRAM_PRE_METASPACE 0
+#define VR_UNIGRAM_PRE_WHITESPACE_METASPACE 1
+#define VR_PREPEND_ALWAYS 0
+#define VR_PREPEND_FIRST 1
+#define VR_PREPEND_NEVER 2
+#define VR_ADDED_LSTRIP 1
+#define VR_ADDED_RSTRIP 2
+#define VR_ADDED_SINGLE_WORD 4
+int vr_unigram_create(const char* const* pieces, const double* scores, int32_t n_pieces, int32_t unk_id, int32_t bos_id,
+                      int32_t eos_id, const uint8_t* charsmap, int64_t charsmap_len, int32_t replace_spaces,
+                      int32_t pre_tokenizer, int32_t prepend_scheme, const char* const* added, const int32_t* added_ids,
+                      const int32_t* added_flags, int32_t n_added, vr_unigram** out);
+void vr_unigram_destroy(vr_unigram* t);
+/* As vr_wordpiece_encode: bos ids... eos, the ids truncated on the right to max_len - 2; max_len >= 2. */
+int vr_unigram_encode(const vr_unigram* t, const char* const* texts, const int64_t* text_lens, int64_t n_texts,
+                      int32_t max_len, int64_t* out_offsets, int32_t* out_ids, int64_t capacity, int64_t* needed);
+/* As vr_wordpiece_encode_pairs: bos A eos eos B eos, truncated LongestFirst to max_len - 4 ids of A and B together;
+ * out_seg_b[i] is the index of the first id of B; max_len >= 4. */
+int vr_unigram_encode_pairs(const vr_unigram* t, const char* const* a_texts, const int64_t* a_lens,
+                            const char* const* b_texts, const int64_t* b_lens, int64_t n, int32_t max_len,
+                            int64_t* out_offsets, int32_t* out_ids, int32_t* out_seg_b, int64_t capacity,
+                            int64_t* needed);
+
 /* ---- BM25 document side: replaces SparseTextEmbedding("Qdrant/bm25").embed's token-count / TF
  * weighting (sparse_embedding.py:25,49; scripts/build_sparse_vectors.py:124,170) -- */
 /* tok_off: n_docs+1 offsets, tok_ids: abs(murmur3) of each stemmed token in text order (`mem`).
@@ -466,19 +504,37 @@ int vr_query_text_batch(vr_engine* e, const vr_wordpiece* tokenizer, int32_t n, 
                         int64_t* out_rows, double* out_scores, int32_t* out_from_dense, int32_t* out_counts,
                         int32_t* out_hybrid, float* out_embeddings);
 
+/* vr_query_text and vr_query_text_batch with a Unigram tokenizer (XLM-R: <s> .. </s>): the same pipeline, the same
+ * arguments and results. */
+int vr_query_text_unigram(vr_engine* e, const vr_unigram* tokenizer, const char* dense_text, int64_t dense_len,
+                          const char* sparse_text, int64_t sparse_len, int32_t max_len, int32_t limit,
+                          double sparse_weight, int32_t fusion, const vr_filter* filter,
+                          int64_t* out_rows, double* out_scores, int32_t* out_from_dense, int32_t* out_count,
+                          int32_t* out_hybrid);
+int vr_query_text_batch_unigram(vr_engine* e, const vr_unigram* tokenizer, int32_t n, const char* const* dense_texts,
+                                const int64_t* dense_lens, const char* const* sparse_texts, const int64_t* sparse_lens,
+                                int32_t max_len, const int32_t* limits, const double* sparse_weights, int32_t fusion,
+                                const vr_filter* filters, int32_t n_filters, const int32_t* filter_of_query,
+                                int32_t out_stride, int64_t* out_rows, double* out_scores, int32_t* out_from_dense,
+                                int32_t* out_counts, int32_t* out_hybrid, float* out_embeddings);
+
 /* ---- Cross-encoder reranking: a second BERT model in the engine, beside the embedder -------------------------------
  * vr_reranker_load: a BertForSequenceClassification with one label (cross-encoder/ms-marco-MiniLM-L-6-v2 and the
  * like). desc / tensors / mem as vr_encoder_load, followed by 4 more tensors: pooler.dense.weight [H,H],
  * pooler.dense.bias [H], classifier.weight [1,H], classifier.bias [1] (5 + 16 L + 4 in all). desc->pooling must be
- * VR_POOL_CLS and desc->normalize 0; any precision; type_vocab >= 2; H need not equal the engine's dim. The model gets
+ * VR_POOL_CLS and desc->normalize 0; any precision; type_vocab >= 1; H need not equal the engine's dim. An XLM-R
+ * cross-encoder (XLMRobertaForSequenceClassification: out_proj(tanh(dense(h_<s>)))) loads the same way, its
+ * classifier.dense / classifier.out_proj as the four head tensors, type_vocab 1, and its position table from row
+ * pad_token_id + 1 on (max_pos = max_position_embeddings - pad_token_id - 1). The model gets
  * its own weights, workspace and graph cache, is replaced by the next load and freed with the engine; loading it never
  * touches the embedder. */
 int vr_reranker_load(vr_engine* e, const vr_bert_desc* desc, const void* const* tensors, int32_t n_tensors, int mem);
 
 /* One logit per (question, passage) pair: logit = wc . tanh(Wp h_CLS + bp) + bc, h_CLS the last hidden state of the
  * pair's [CLS] token. ids / offsets as vr_encode (pair sequences, e.g. from vr_wordpiece_encode_pairs); seg_b[n_seq]
- * int32: tokens at positions >= seg_b[i] of sequence i are segment B (token type 1), 1 <= seg_b[i] <= its length. All
- * three in `mem`; out_logits: n_seq f32 in `out_mem`. The head runs in f32 whatever the precision, in a fixed order:
+ * int32: tokens at positions >= seg_b[i] of sequence i are segment B (token type 1), 1 <= seg_b[i] <= its length. A
+ * model with one token type (type_vocab 1, XLM-R) has no segment B: seg_b may be NULL and is ignored. All three in
+ * `mem`; out_logits: n_seq f32 in `out_mem`. The head runs in f32 whatever the precision, in a fixed order:
  * the same input gives the same bits. Arguments are checked before any device work. */
 int vr_rerank(vr_engine* e, const int32_t* ids, const int32_t* offsets, const int32_t* seg_b, int32_t n_seq, int mem,
               float* out_logits, int out_mem);
@@ -490,6 +546,10 @@ int vr_rerank(vr_engine* e, const int32_t* ids, const int32_t* offsets, const in
 int vr_rerank_text(vr_engine* e, const vr_wordpiece* tokenizer, int32_t n_queries, const char* const* queries,
                    const int64_t* query_lens, const int64_t* cand_off, const char* const* passages,
                    const int64_t* passage_lens, int32_t max_len, float* out_logits);
+/* The same with a Unigram tokenizer (vr_unigram_encode_pairs, max_len >= 4). */
+int vr_rerank_text_unigram(vr_engine* e, const vr_unigram* tokenizer, int32_t n_queries, const char* const* queries,
+                           const int64_t* query_lens, const int64_t* cand_off, const char* const* passages,
+                           const int64_t* passage_lens, int32_t max_len, float* out_logits);
 
 /* Persistence. The reference's index survives a restart in Qdrant's volume
  * (docker-compose.yml:8-9; VectorStoreService._ensure_collection re-attaches, vector_store.py:75-115).

@@ -481,7 +481,11 @@ int vr_reranker_load(vr_engine* e, const vr_bert_desc* desc, const void* const* 
 
 int vr_rerank(vr_engine* e, const int32_t* ids, const int32_t* offsets, const int32_t* seg_b, int32_t n_seq, int mem,
               float* out_logits, int out_mem) {
-  VR_CHECK(n_seq >= 0 && (n_seq == 0 || (ids && offsets && seg_b && out_logits)), "bad arguments");
+  VR_CHECK(n_seq >= 0 && (n_seq == 0 || (ids && offsets && out_logits)), "bad arguments");
+  // A null seg_b is allowed for a reranker with one token type only; whether the loaded model has one is checked in
+  // encoder_rerank, under the writers' mutex. This line runs BEFORE check_engine, so that a null engine with a null
+  // seg_b still reports the argument error first, as vr_rerank always has (tests/test_rerank_cpu.py).
+  VR_CHECK(n_seq == 0 || seg_b || e, "bad arguments");
   VR_CHECK((mem == VR_MEM_HOST || mem == VR_MEM_DEVICE) && (out_mem == VR_MEM_HOST || out_mem == VR_MEM_DEVICE),
            "bad mem");
   VR_TRY(check_engine(e));
@@ -489,9 +493,12 @@ int vr_rerank(vr_engine* e, const int32_t* ids, const int32_t* offsets, const in
   return encoder_rerank(e, ids, offsets, seg_b, n_seq, mem, out_logits, out_mem);
 }
 
-int vr_rerank_text(vr_engine* e, const vr_wordpiece* tokenizer, int32_t n_queries, const char* const* queries,
-                   const int64_t* query_lens, const int64_t* cand_off, const char* const* passages,
-                   const int64_t* passage_lens, int32_t max_len, float* out_logits) {
+}  // extern "C"
+
+// vr_rerank_text and vr_rerank_text_unigram: one pipeline, whatever tokenises the pairs
+static int rerank_text(vr_engine* e, const vr::Tokenizer* tokenizer, int32_t n_queries, const char* const* queries,
+                       const int64_t* query_lens, const int64_t* cand_off, const char* const* passages,
+                       const int64_t* passage_lens, int32_t max_len, float* out_logits) {
   VR_CHECK(n_queries >= 0 && (n_queries == 0 || (tokenizer && queries && query_lens && cand_off)), "bad arguments");
   VR_CHECK(max_len >= 3 && max_len <= 4096, "max_len %d", max_len);
   if (n_queries == 0) return check_engine(e);
@@ -522,13 +529,30 @@ int vr_rerank_text(vr_engine* e, const vr_wordpiece* tokenizer, int32_t n_querie
   std::vector<int64_t> off(static_cast<size_t>(n) + 1);
   std::vector<int32_t> seg(static_cast<size_t>(n)), ids(static_cast<size_t>(n) * max_len);
   int64_t needed = 0;
-  VR_TRY(vr_wordpiece_encode_pairs(tokenizer, a.data(), a_len.data(), passages, passage_lens, n, max_len, off.data(),
-                                   ids.data(), seg.data(), static_cast<int64_t>(ids.size()), &needed));
+  VR_TRY(tokenizer->encode_pairs(a.data(), a_len.data(), passages, passage_lens, n, max_len, off.data(), ids.data(),
+                                 seg.data(), static_cast<int64_t>(ids.size()), &needed));
   VR_CHECK(needed <= INT32_MAX, "%lld tokens", static_cast<long long>(needed));
   std::vector<int32_t> off32(static_cast<size_t>(n) + 1);
   for (int64_t i = 0; i <= n; ++i) off32[static_cast<size_t>(i)] = static_cast<int32_t>(off[static_cast<size_t>(i)]);
   std::lock_guard<std::mutex> writer(e->wmu);
   return encoder_rerank(e, ids.data(), off32.data(), seg.data(), static_cast<int>(n), VR_MEM_HOST, out_logits, VR_MEM_HOST);
+}
+
+extern "C" {
+
+int vr_rerank_text(vr_engine* e, const vr_wordpiece* tokenizer, int32_t n_queries, const char* const* queries,
+                   const int64_t* query_lens, const int64_t* cand_off, const char* const* passages,
+                   const int64_t* passage_lens, int32_t max_len, float* out_logits) {
+  return rerank_text(e, vr::as_tokenizer(tokenizer), n_queries, queries, query_lens, cand_off, passages, passage_lens,
+                     max_len, out_logits);
+}
+
+int vr_rerank_text_unigram(vr_engine* e, const vr_unigram* tokenizer, int32_t n_queries, const char* const* queries,
+                           const int64_t* query_lens, const int64_t* cand_off, const char* const* passages,
+                           const int64_t* passage_lens, int32_t max_len, float* out_logits) {
+  VR_CHECK(max_len >= 4, "max_len %d cannot hold <s> and three </s>", max_len);
+  return rerank_text(e, vr::as_tokenizer(tokenizer), n_queries, queries, query_lens, cand_off, passages, passage_lens,
+                     max_len, out_logits);
 }
 
 }  // extern "C"
@@ -1839,14 +1863,13 @@ void give_query_row(int device, float* p) {
   q.free_rows.push_back(p);
 }
 
-// WordPiece ids of n (prefixed) questions, packed: ids and n + 1 offsets as vr_encode takes them (host threads)
-int question_wordpieces(const vr_wordpiece* tokenizer, const char* const* texts, const int64_t* lens, int n, int max_len,
+// token ids of n (prefixed) questions, packed: ids and n + 1 offsets as vr_encode takes them (host threads)
+int question_wordpieces(const Tokenizer* tokenizer, const char* const* texts, const int64_t* lens, int n, int max_len,
                         std::vector<int32_t>* ids, std::vector<int32_t>* off32) {
   std::vector<int64_t> off(static_cast<size_t>(n) + 1, 0);
   ids->resize(static_cast<size_t>(n) * max_len);
   int64_t needed = 0;
-  VR_TRY(vr_wordpiece_encode(tokenizer, texts, lens, n, max_len, off.data(), ids->data(), static_cast<int64_t>(ids->size()),
-                             &needed));
+  VR_TRY(tokenizer->encode(texts, lens, n, max_len, off.data(), ids->data(), static_cast<int64_t>(ids->size()), &needed));
   VR_CHECK(needed <= INT32_MAX, "%lld tokens", static_cast<long long>(needed));
   ids->resize(static_cast<size_t>(needed));
   off32->resize(static_cast<size_t>(n) + 1);
@@ -1908,14 +1931,11 @@ __global__ __launch_bounds__(256) void gather_query_rows_kernel(const float* __r
   dst[i] = src[static_cast<int64_t>(pick[r]) * dim + (i - r * dim)];
 }
 
-}  // namespace
-
-extern "C" {
-
-int vr_query_text(vr_engine* e, const vr_wordpiece* tokenizer, const char* dense_text, int64_t dense_len,
-                  const char* sparse_text, int64_t sparse_len, int32_t max_len, int32_t limit, double sparse_weight,
-                  int32_t fusion, const vr_filter* filter, int64_t* out_rows, double* out_scores, int32_t* out_from_dense,
-                  int32_t* out_count, int32_t* out_hybrid) {
+// vr_query_text(_unigram): one pipeline, whatever tokenises the question
+int query_text(vr_engine* e, const Tokenizer* tokenizer, const char* dense_text, int64_t dense_len,
+               const char* sparse_text, int64_t sparse_len, int32_t max_len, int32_t limit, double sparse_weight,
+               int32_t fusion, const vr_filter* filter, int64_t* out_rows, double* out_scores, int32_t* out_from_dense,
+               int32_t* out_count, int32_t* out_hybrid) {
   VR_TRY(check_engine(e));
   VR_CHECK(tokenizer && dense_text && dense_len >= 0 && out_rows && out_scores && out_count, "bad arguments");
   VR_CHECK(limit >= 1 && limit * 3 <= kMaxK, "limit = %d not in 1..%d", limit, kMaxK / 3);
@@ -2006,12 +2026,13 @@ int vr_query_text(vr_engine* e, const vr_wordpiece* tokenizer, const char* dense
   return 0;
 }
 
-int vr_query_text_batch(vr_engine* e, const vr_wordpiece* tokenizer, int32_t n, const char* const* dense_texts,
-                        const int64_t* dense_lens, const char* const* sparse_texts, const int64_t* sparse_lens,
-                        int32_t max_len, const int32_t* limits, const double* sparse_weights, int32_t fusion,
-                        const vr_filter* filters, int32_t n_filters, const int32_t* filter_of_query, int32_t out_stride,
-                        int64_t* out_rows, double* out_scores, int32_t* out_from_dense, int32_t* out_counts,
-                        int32_t* out_hybrid, float* out_embeddings) {
+// vr_query_text_batch(_unigram): one pipeline, whatever tokenises the questions
+int query_text_batch(vr_engine* e, const Tokenizer* tokenizer, int32_t n, const char* const* dense_texts,
+                     const int64_t* dense_lens, const char* const* sparse_texts, const int64_t* sparse_lens,
+                     int32_t max_len, const int32_t* limits, const double* sparse_weights, int32_t fusion,
+                     const vr_filter* filters, int32_t n_filters, const int32_t* filter_of_query, int32_t out_stride,
+                     int64_t* out_rows, double* out_scores, int32_t* out_from_dense, int32_t* out_counts,
+                     int32_t* out_hybrid, float* out_embeddings) {
   // (the arguments are checked before the engine is touched, as in the _multi calls)
   VR_CHECK(n >= 0, "bad arguments");
   if (n == 0) return 0;
@@ -2132,6 +2153,48 @@ int vr_query_text_batch(vr_engine* e, const vr_wordpiece* tokenizer, int32_t n, 
   }
   if (out_embeddings) VR_HIP(hipStreamSynchronize(L->stream));
   return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vr_query_text(vr_engine* e, const vr_wordpiece* tokenizer, const char* dense_text, int64_t dense_len,
+                  const char* sparse_text, int64_t sparse_len, int32_t max_len, int32_t limit, double sparse_weight,
+                  int32_t fusion, const vr_filter* filter, int64_t* out_rows, double* out_scores, int32_t* out_from_dense,
+                  int32_t* out_count, int32_t* out_hybrid) {
+  return query_text(e, as_tokenizer(tokenizer), dense_text, dense_len, sparse_text, sparse_len, max_len, limit,
+                    sparse_weight, fusion, filter, out_rows, out_scores, out_from_dense, out_count, out_hybrid);
+}
+
+int vr_query_text_unigram(vr_engine* e, const vr_unigram* tokenizer, const char* dense_text, int64_t dense_len,
+                          const char* sparse_text, int64_t sparse_len, int32_t max_len, int32_t limit,
+                          double sparse_weight, int32_t fusion, const vr_filter* filter, int64_t* out_rows,
+                          double* out_scores, int32_t* out_from_dense, int32_t* out_count, int32_t* out_hybrid) {
+  return query_text(e, as_tokenizer(tokenizer), dense_text, dense_len, sparse_text, sparse_len, max_len, limit,
+                    sparse_weight, fusion, filter, out_rows, out_scores, out_from_dense, out_count, out_hybrid);
+}
+
+int vr_query_text_batch(vr_engine* e, const vr_wordpiece* tokenizer, int32_t n, const char* const* dense_texts,
+                        const int64_t* dense_lens, const char* const* sparse_texts, const int64_t* sparse_lens,
+                        int32_t max_len, const int32_t* limits, const double* sparse_weights, int32_t fusion,
+                        const vr_filter* filters, int32_t n_filters, const int32_t* filter_of_query, int32_t out_stride,
+                        int64_t* out_rows, double* out_scores, int32_t* out_from_dense, int32_t* out_counts,
+                        int32_t* out_hybrid, float* out_embeddings) {
+  return query_text_batch(e, as_tokenizer(tokenizer), n, dense_texts, dense_lens, sparse_texts, sparse_lens, max_len,
+                          limits, sparse_weights, fusion, filters, n_filters, filter_of_query, out_stride, out_rows,
+                          out_scores, out_from_dense, out_counts, out_hybrid, out_embeddings);
+}
+
+int vr_query_text_batch_unigram(vr_engine* e, const vr_unigram* tokenizer, int32_t n, const char* const* dense_texts,
+                                const int64_t* dense_lens, const char* const* sparse_texts, const int64_t* sparse_lens,
+                                int32_t max_len, const int32_t* limits, const double* sparse_weights, int32_t fusion,
+                                const vr_filter* filters, int32_t n_filters, const int32_t* filter_of_query,
+                                int32_t out_stride, int64_t* out_rows, double* out_scores, int32_t* out_from_dense,
+                                int32_t* out_counts, int32_t* out_hybrid, float* out_embeddings) {
+  return query_text_batch(e, as_tokenizer(tokenizer), n, dense_texts, dense_lens, sparse_texts, sparse_lens, max_len,
+                          limits, sparse_weights, fusion, filters, n_filters, filter_of_query, out_stride, out_rows,
+                          out_scores, out_from_dense, out_counts, out_hybrid, out_embeddings);
 }
 
 }  // extern "C"

@@ -3538,7 +3538,8 @@ int encoder_load(vr_engine* e, const vr_bert_desc* d, const void* const* t, int 
 int reranker_load(vr_engine* e, const vr_bert_desc* d, const void* const* t, int n_tensors, int mem) {
   VR_CHECK(d->struct_size == static_cast<int32_t>(sizeof(vr_bert_desc)), "vr_bert_desc size mismatch");
   VR_CHECK(d->pooling == VR_POOL_CLS && d->normalize == 0, "a reranker pools the [CLS] row (pooling 1) without normalising");
-  VR_CHECK(d->type_vocab >= 2, "a reranker needs two token types (type_vocab %d)", d->type_vocab);
+  // two token types (BERT: segment B reads type row 1), or one (XLM-R: every token reads row 0, seg_b is not used)
+  VR_CHECK(d->type_vocab >= 1, "a reranker needs a token type (type_vocab %d)", d->type_vocab);
   VR_CHECK(d->layers >= 1 && n_tensors == 5 + 16 * d->layers + 4, "expected %d tensors, got %d", 5 + 16 * d->layers + 4,
            n_tensors);
   for (int i = 0; i < 4; ++i) VR_CHECK(t[n_tensors - 4 + i] != nullptr, "tensor %d is null", n_tensors - 4 + i);
@@ -4013,6 +4014,8 @@ int encoder_rerank(vr_engine* e, const int32_t* ids, const int32_t* offsets, con
   Encoder* enc = static_cast<Encoder*>(e->reranker);
   VR_CHECK(enc != nullptr, "no reranker loaded (vr_reranker_load)");
   if (n_seq <= 0) return 0;
+  if (enc->d.type_vocab == 1) seg_b = nullptr;  // one token type: the embed_ln_kernel<false> instantiation serves pairs
+  else VR_CHECK(seg_b != nullptr, "seg_b is required for a reranker with %d token types", enc->d.type_vocab);
   const int H = enc->d.hidden;
   std::vector<int32_t> cu_host;
   VR_TRY(read_offsets(e, enc, offsets, seg_b, n_seq, mem, &cu_host));

@@ -45,6 +45,32 @@ void set_error(const char* fmt, ...);
     if (_rc != 0) return _rc; \
   } while (0)
 
+// What the engine's text calls (vr_query_text, vr_query_text_batch, vr_rerank_text) need of a tokenizer: the packed
+// single-text and pair encodings of the C-ABI, with its output conventions (offsets, ids, -2 with *needed, seg_b).
+// vr_wordpiece (wordpiece.cpp) and vr_unigram (unigram.cpp) implement it; both are read-only after creation.
+struct Tokenizer {
+  virtual ~Tokenizer() = default;
+  virtual int encode(const char* const* texts, const int64_t* text_lens, int64_t n_texts, int32_t max_len,
+                     int64_t* out_offsets, int32_t* out_ids, int64_t capacity, int64_t* needed) const = 0;
+  virtual int encode_pairs(const char* const* a_texts, const int64_t* a_lens, const char* const* b_texts,
+                           const int64_t* b_lens, int64_t n, int32_t max_len, int64_t* out_offsets, int32_t* out_ids,
+                           int32_t* out_seg_b, int64_t capacity, int64_t* needed) const = 0;
+};
+const Tokenizer* as_tokenizer(const vr_wordpiece* t);  // (nullptr for nullptr)
+const Tokenizer* as_tokenizer(const vr_unigram* t);
+
+// Host text helpers shared by the tokenizers (wordpiece.cpp)
+// UTF-8 -> code points; a malformed byte becomes U+FFFD
+void decode_utf8(const char* s, size_t n, std::u32string* out);
+void append_utf8(uint32_t cp, std::string* out);
+// Unicode White_Space (Rust char::is_whitespace)
+inline bool is_white_space(uint32_t c) {
+  return (c >= 9 && c <= 13) || c == 0x20 || c == 0x85 || c == 0xA0 || c == 0x1680 || (c >= 0x2000 && c <= 0x200A) ||
+         c == 0x2028 || c == 0x2029 || c == 0x202F || c == 0x205F || c == 0x3000;
+}
+// HF tokenizers' LongestFirst truncation of a pair's id counts to m together (the specials already taken off max_len)
+void longest_first(size_t* na, size_t* nb, size_t m);
+
 // Growable device array. grow() keeps the first `keep` elements.
 template <class T>
 struct DevArray {

@@ -33,15 +33,29 @@
 #include "unicode_tables.inc"
 #include "wordpiece_tables.inc"
 
-struct vr_wordpiece {
+struct vr_wordpiece final : vr::Tokenizer {
   std::unordered_map<std::string, int32_t> vocab;
   int32_t unk = -1, cls = -1, sep = -1;
   bool lowercase = true, strip_accents = true, chinese = true, clean = true;
+
+  int encode(const char* const* texts, const int64_t* text_lens, int64_t n_texts, int32_t max_len, int64_t* out_offsets,
+             int32_t* out_ids, int64_t capacity, int64_t* needed) const override {
+    return vr_wordpiece_encode(this, texts, text_lens, n_texts, max_len, out_offsets, out_ids, capacity, needed);
+  }
+  int encode_pairs(const char* const* a_texts, const int64_t* a_lens, const char* const* b_texts, const int64_t* b_lens,
+                   int64_t n, int32_t max_len, int64_t* out_offsets, int32_t* out_ids, int32_t* out_seg_b,
+                   int64_t capacity, int64_t* needed) const override {
+    return vr_wordpiece_encode_pairs(this, a_texts, a_lens, b_texts, b_lens, n, max_len, out_offsets, out_ids,
+                                     out_seg_b, capacity, needed);
+  }
 };
 
 namespace {
 
 using u32s = std::u32string;
+using vr::append_utf8;
+using vr::decode_utf8;
+using vr::longest_first;
 
 template <size_t N>
 bool in_ranges(const uint32_t (&r)[N][2], uint32_t cp) {
@@ -55,10 +69,7 @@ bool in_ranges(const uint32_t (&r)[N][2], uint32_t cp) {
   return false;
 }
 
-inline bool is_white_space(uint32_t c) {  // Unicode White_Space (Rust char::is_whitespace)
-  return (c >= 9 && c <= 13) || c == 0x20 || c == 0x85 || c == 0xA0 || c == 0x1680 || (c >= 0x2000 && c <= 0x200A) ||
-         c == 0x2028 || c == 0x2029 || c == 0x202F || c == 0x205F || c == 0x3000;
-}
+using vr::is_white_space;
 inline bool is_other(uint32_t c) { return in_ranges(kOtherRanges, c); }  // Cc | Cf | Co
 inline bool is_punct(uint32_t c) {
   if (c < 128) return (c >= 33 && c <= 47) || (c >= 58 && c <= 64) || (c >= 91 && c <= 96) || (c >= 123 && c <= 126);
@@ -145,44 +156,6 @@ inline void lower_cp(uint32_t cp, u32s* out) {
       if (t) out->push_back(t);
   } else {
     out->push_back(cp);
-  }
-}
-
-// strict-enough UTF-8 decoder: malformed bytes become U+FFFD (which clean_text then removes,
-// like a Python str that was decoded with errors="replace")
-void decode_utf8(const char* s, size_t n, u32s* out) {
-  out->clear();
-  size_t i = 0;
-  while (i < n) {
-    const unsigned char c = static_cast<unsigned char>(s[i]);
-    uint32_t cp = 0xFFFD;
-    int len = 1;
-    auto cont = [&](size_t k) { return i + k < n && (static_cast<unsigned char>(s[i + k]) & 0xC0) == 0x80; };
-    if (c < 0x80) cp = c;
-    else if ((c >> 5) == 6 && cont(1)) { cp = ((c & 0x1Fu) << 6) | (s[i + 1] & 0x3Fu); len = 2; }
-    else if ((c >> 4) == 14 && cont(1) && cont(2)) { cp = ((c & 0x0Fu) << 12) | ((s[i + 1] & 0x3Fu) << 6) | (s[i + 2] & 0x3Fu); len = 3; }
-    else if ((c >> 3) == 30 && cont(1) && cont(2) && cont(3)) {
-      cp = ((c & 0x07u) << 18) | ((s[i + 1] & 0x3Fu) << 12) | ((s[i + 2] & 0x3Fu) << 6) | (s[i + 3] & 0x3Fu);
-      len = 4;
-    }
-    if (cp > 0x10FFFF || (cp >= 0xD800 && cp <= 0xDFFF)) cp = 0xFFFD;
-    out->push_back(cp);
-    i += static_cast<size_t>(len);
-  }
-}
-
-inline void append_utf8(uint32_t cp, std::string* out) {
-  if (cp < 0x80) out->push_back(static_cast<char>(cp));
-  else if (cp < 0x800) { out->push_back(static_cast<char>(0xC0 | (cp >> 6))); out->push_back(static_cast<char>(0x80 | (cp & 0x3F))); }
-  else if (cp < 0x10000) {
-    out->push_back(static_cast<char>(0xE0 | (cp >> 12)));
-    out->push_back(static_cast<char>(0x80 | ((cp >> 6) & 0x3F)));
-    out->push_back(static_cast<char>(0x80 | (cp & 0x3F)));
-  } else {
-    out->push_back(static_cast<char>(0xF0 | (cp >> 18)));
-    out->push_back(static_cast<char>(0x80 | ((cp >> 12) & 0x3F)));
-    out->push_back(static_cast<char>(0x80 | ((cp >> 6) & 0x3F)));
-    out->push_back(static_cast<char>(0x80 | (cp & 0x3F)));
   }
 }
 
@@ -293,6 +266,48 @@ void encode_one(const vr_wordpiece& t, const char* s, size_t n, int32_t max_len,
   ids->push_back(t.sep);
 }
 
+}  // namespace
+
+namespace vr {
+
+// strict-enough UTF-8 decoder: malformed bytes become U+FFFD (which clean_text then removes,
+// like a Python str that was decoded with errors="replace")
+void decode_utf8(const char* s, size_t n, std::u32string* out) {
+  out->clear();
+  size_t i = 0;
+  while (i < n) {
+    const unsigned char c = static_cast<unsigned char>(s[i]);
+    uint32_t cp = 0xFFFD;
+    int len = 1;
+    auto cont = [&](size_t k) { return i + k < n && (static_cast<unsigned char>(s[i + k]) & 0xC0) == 0x80; };
+    if (c < 0x80) cp = c;
+    else if ((c >> 5) == 6 && cont(1)) { cp = ((c & 0x1Fu) << 6) | (s[i + 1] & 0x3Fu); len = 2; }
+    else if ((c >> 4) == 14 && cont(1) && cont(2)) { cp = ((c & 0x0Fu) << 12) | ((s[i + 1] & 0x3Fu) << 6) | (s[i + 2] & 0x3Fu); len = 3; }
+    else if ((c >> 3) == 30 && cont(1) && cont(2) && cont(3)) {
+      cp = ((c & 0x07u) << 18) | ((s[i + 1] & 0x3Fu) << 12) | ((s[i + 2] & 0x3Fu) << 6) | (s[i + 3] & 0x3Fu);
+      len = 4;
+    }
+    if (cp > 0x10FFFF || (cp >= 0xD800 && cp <= 0xDFFF)) cp = 0xFFFD;
+    out->push_back(cp);
+    i += static_cast<size_t>(len);
+  }
+}
+
+void append_utf8(uint32_t cp, std::string* out) {
+  if (cp < 0x80) out->push_back(static_cast<char>(cp));
+  else if (cp < 0x800) { out->push_back(static_cast<char>(0xC0 | (cp >> 6))); out->push_back(static_cast<char>(0x80 | (cp & 0x3F))); }
+  else if (cp < 0x10000) {
+    out->push_back(static_cast<char>(0xE0 | (cp >> 12)));
+    out->push_back(static_cast<char>(0x80 | ((cp >> 6) & 0x3F)));
+    out->push_back(static_cast<char>(0x80 | (cp & 0x3F)));
+  } else {
+    out->push_back(static_cast<char>(0xF0 | (cp >> 18)));
+    out->push_back(static_cast<char>(0x80 | ((cp >> 12) & 0x3F)));
+    out->push_back(static_cast<char>(0x80 | ((cp >> 6) & 0x3F)));
+    out->push_back(static_cast<char>(0x80 | (cp & 0x3F)));
+  }
+}
+
 // HF tokenizers' LongestFirst truncation of a pair to m ids (the specials already taken off max_len): the shorter side
 // keeps min(n_short, m/2) or all of itself, the longer side the rest; when both exceed m/2 the longer one gets the odd id
 void longest_first(size_t* na, size_t* nb, size_t m) {
@@ -308,7 +323,9 @@ void longest_first(size_t* na, size_t* nb, size_t m) {
   *nb = std::min(*nb, swap ? n1 : n2);
 }
 
-}  // namespace
+const Tokenizer* as_tokenizer(const vr_wordpiece* t) { return t; }
+
+}  // namespace vr
 
 extern "C" {
 

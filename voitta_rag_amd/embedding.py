@@ -19,9 +19,78 @@ from . import deferred as _deferred
 from . import encoder as _enc
 from .config import get_settings
 from .store_registry import get_engine
+from .unigram import UnigramTokenizer, is_unigram_pipeline
 from .wordpiece import WordPieceTokenizer
 
 logger = logging.getLogger(__name__)
+
+# the longest sequence the attention kernels have run (a checkpoint that declares more is refused at load)
+MAX_SEQ = 512
+
+
+def native_tokenizer(tok) -> bool:
+    """A tokenizer of the engine itself (WordPiece or Unigram): the one-call text paths (vr_query_text(_batch), the
+    deferred write-behind) take models with one; a tokenizers-library object goes through several calls instead."""
+    return isinstance(tok, (WordPieceTokenizer, UnigramTokenizer))
+
+
+def read_encoder_config(path: str) -> dict:
+    """config.json, modules.json and sentence_bert_config.json of a sentence-transformers directory -> the encoder
+    description and how to load it: {"desc": BertDesc, "max_seq": int, "pos_start": first position-table row}.
+    BERT: max_seq = min(max_seq_length, max_position_embeddings). XLM-RoBERTa (multilingual-e5 and the like): position
+    p reads row pad_token_id + 1 + p, so the table is used from that row on (max_pos = max_position_embeddings -
+    pad_token_id - 1); one token type; max_seq = min(max_seq_length, max_pos), refused above 512."""
+    cfg = json.load(open(os.path.join(path, "config.json")))
+    kind = cfg.get("model_type", "bert")
+    if kind not in ("bert", "xlm-roberta"):
+        raise ValueError(f"unsupported model_type {kind}: BERT and XLM-RoBERTa encoders only")
+    if cfg.get("hidden_act", "gelu") != "gelu" or cfg.get("position_embedding_type", "absolute") != "absolute":
+        raise ValueError("only exact-erf GELU and absolute position embeddings are implemented")
+    pos_start = int(cfg.get("pad_token_id", 1)) + 1 if kind == "xlm-roberta" else 0
+    max_pos = int(cfg["max_position_embeddings"]) - pos_start
+    pooling, normalize, max_seq = "mean", False, max_pos
+    mod_path = os.path.join(path, "modules.json")
+    if os.path.exists(mod_path):
+        for m in json.load(open(mod_path)):
+            k = m.get("type", "")
+            if k.endswith("Pooling"):
+                pc = json.load(open(os.path.join(path, m["path"], "config.json")))
+                if pc.get("pooling_mode_cls_token"):
+                    pooling = "cls"
+                elif not pc.get("pooling_mode_mean_tokens", True):
+                    raise ValueError("only CLS and mean pooling are implemented")
+            elif k.endswith("Normalize"):
+                normalize = True
+    sb = os.path.join(path, "sentence_bert_config.json")
+    if os.path.exists(sb):
+        max_seq = int(json.load(open(sb)).get("max_seq_length", max_seq))
+    max_seq = min(max_seq, max_pos)
+    if kind == "xlm-roberta" and max_seq > MAX_SEQ:
+        raise ValueError(f"{path} uses sequences of up to {max_seq} tokens; the engine runs at most {MAX_SEQ}: set "
+                         f"max_seq_length <= {MAX_SEQ} in its sentence_bert_config.json")
+    desc = _enc.BertDesc(layers=cfg["num_hidden_layers"], hidden=cfg["hidden_size"],
+                         heads=cfg["num_attention_heads"], intermediate=cfg["intermediate_size"],
+                         vocab=cfg["vocab_size"], max_pos=max_pos,
+                         type_vocab=cfg.get("type_vocab_size", 2), pooling=pooling, normalize=normalize,
+                         eps=cfg.get("layer_norm_eps", 1e-12),
+                         # f16 (default): f16 MFMA operands, f32 accumulate, |1 - cos| < 1e-6 vs f64
+                         # (north_star allows 1e-4); f16x3: (hi, lo) f16 operands, three passes,
+                         # |1 - cos| ~5e-8, 1.8x slower; f32: the f32-input MFMA, 5x slower
+                         precision=os.environ.get("VOITTA_ENCODER_PRECISION", "f16"))
+    return {"desc": desc, "max_seq": max_seq, "pos_start": pos_start, "config": cfg}
+
+
+def slice_positions(state: dict, pos_start: int) -> dict:
+    """The state dict with its position table from row pos_start on (XLM-R's rows for positions 0, 1, ...)."""
+    if not pos_start:
+        return state
+    key = "embeddings.position_embeddings.weight"
+    hits = [k for k in state if k == key or k.endswith("." + key)]
+    if len(hits) != 1:
+        raise KeyError(f"weight '{key}' not found (or ambiguous) in state dict: {hits[:3]}")
+    out = dict(state)
+    out[hits[0]] = state[hits[0]][pos_start:]
+    return out
 
 
 class NativeSentenceEncoder:
@@ -32,7 +101,7 @@ class NativeSentenceEncoder:
         self.desc = desc
         self.tokenizer = tokenizer
         self.max_seq_length = min(max_seq_length, desc.max_pos)
-        if isinstance(tokenizer, WordPieceTokenizer):
+        if native_tokenizer(tokenizer):
             tokenizer.max_length = self.max_seq_length
         else:
             self.tokenizer.no_padding()
@@ -46,37 +115,9 @@ class NativeSentenceEncoder:
             raise FileNotFoundError(
                 f"EMBEDDING_MODEL='{path}' is not a local checkpoint directory (hub names cannot be "
                 "downloaded here: there is no network). Point it at a sentence-transformers / HF BERT directory.")
-        cfg = json.load(open(os.path.join(path, "config.json")))
-        if cfg.get("model_type", "bert") != "bert":
-            raise ValueError(f"unsupported model_type {cfg.get('model_type')}: BERT-family encoders only")
-        if cfg.get("hidden_act", "gelu") != "gelu" or cfg.get("position_embedding_type", "absolute") != "absolute":
-            raise ValueError("only exact-erf GELU and absolute position embeddings are implemented")
-        pooling, normalize, max_seq = "mean", False, int(cfg["max_position_embeddings"])
-        mod_path = os.path.join(path, "modules.json")
-        if os.path.exists(mod_path):
-            for m in json.load(open(mod_path)):
-                kind = m.get("type", "")
-                if kind.endswith("Pooling"):
-                    pc = json.load(open(os.path.join(path, m["path"], "config.json")))
-                    if pc.get("pooling_mode_cls_token"):
-                        pooling = "cls"
-                    elif not pc.get("pooling_mode_mean_tokens", True):
-                        raise ValueError("only CLS and mean pooling are implemented")
-                elif kind.endswith("Normalize"):
-                    normalize = True
-        sb = os.path.join(path, "sentence_bert_config.json")
-        if os.path.exists(sb):
-            max_seq = int(json.load(open(sb)).get("max_seq_length", max_seq))
-        desc = _enc.BertDesc(layers=cfg["num_hidden_layers"], hidden=cfg["hidden_size"],
-                             heads=cfg["num_attention_heads"], intermediate=cfg["intermediate_size"],
-                             vocab=cfg["vocab_size"], max_pos=cfg["max_position_embeddings"],
-                             type_vocab=cfg.get("type_vocab_size", 2), pooling=pooling, normalize=normalize,
-                             eps=cfg.get("layer_norm_eps", 1e-12),
-                             # f16 (default): f16 MFMA operands, f32 accumulate, |1 - cos| < 1e-6 vs f64
-                             # (north_star allows 1e-4); f16x3: (hi, lo) f16 operands, three passes,
-                             # |1 - cos| ~5e-8, 1.8x slower; f32: the f32-input MFMA, 5x slower
-                             precision=os.environ.get("VOITTA_ENCODER_PRECISION", "f16"))
-        return cls(engine or get_engine(), desc, cls._load_weights(path), cls._load_tokenizer(path, cfg), max_seq)
+        rc = read_encoder_config(path)
+        state = slice_positions(cls._load_weights(path), rc["pos_start"])
+        return cls(engine or get_engine(), rc["desc"], state, cls._load_tokenizer(path, rc["config"]), rc["max_seq"])
 
     @staticmethod
     def _load_weights(path: str) -> dict:
@@ -94,9 +135,16 @@ class NativeSentenceEncoder:
 
     @staticmethod
     def _load_tokenizer(path: str, cfg: dict):
-        """The native WordPiece (csrc/wordpiece.cpp) for plain BERT tokenizers; anything else that a
-        tokenizer.json may describe goes through the HF `tokenizers` library."""
+        """The native WordPiece (csrc/wordpiece.cpp) for plain BERT tokenizers, the native Unigram (csrc/unigram.cpp)
+        for the XLM-R pipeline of an XLM-R model; anything else that a tokenizer.json may describe (a BERT model with
+        a Unigram tokenizer.json among them, as before) goes through the HF `tokenizers` library."""
         tj = os.path.join(path, "tokenizer.json")
+        if os.path.exists(tj) and cfg.get("model_type") == "xlm-roberta":
+            spec = json.load(open(tj, encoding="utf-8"))
+            if (spec.get("model") or {}).get("type") == "Unigram":
+                if is_unigram_pipeline(spec):
+                    return UnigramTokenizer.from_tokenizer_json(spec)
+                logger.info("native Unigram not applicable; using the tokenizers library")
         if os.path.exists(os.path.join(path, "vocab.txt")) or os.path.exists(tj):
             try:
                 if os.path.exists(tj):
@@ -126,7 +174,7 @@ class NativeSentenceEncoder:
 
     # ---- SentenceTransformer.encode -------------------------------------------------------------
     def tokenize(self, texts: list[str]):
-        if isinstance(self.tokenizer, WordPieceTokenizer):
+        if native_tokenizer(self.tokenizer):
             ids, off = self.tokenizer.encode_batch(list(texts))
             return ids, off.astype(np.int32)
         encs = self.tokenizer.encode_batch(list(texts))
@@ -210,7 +258,7 @@ class EmbeddingService:
         if "e5" in self.model_name.lower():  # embedding.py:82-83
             query = f"query: {query}"
         model = self.model
-        if _deferred.enabled() and isinstance(model.tokenizer, WordPieceTokenizer):
+        if _deferred.enabled() and native_tokenizer(model.tokenizer):
             out = _deferred.QueryRef(model, query)  # encoded when looked at — or inside the search call it goes to
         else:
             out = _deferred.QueryEmbedding(model.encode(query, convert_to_numpy=True))

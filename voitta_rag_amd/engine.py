@@ -439,16 +439,27 @@ class Engine:
         n = int(cnt[0])
         return rows[:n].copy(), scores[:n].copy(), fd[:n].copy()
 
+    def _text_fn(self, name: str, tokenizer):
+        """The C-ABI text call for `tokenizer` and its handle: vr_<name>_unigram for a UnigramTokenizer, vr_<name> for
+        a WordPieceTokenizer or a raw vr_wordpiece handle."""
+        from .unigram import UnigramTokenizer
+
+        if isinstance(tokenizer, UnigramTokenizer):
+            return getattr(self._lib, f"vr_{name}_unigram"), tokenizer._h
+        return getattr(self._lib, f"vr_{name}"), getattr(tokenizer, "_h", tokenizer)
+
     def query_text(self, tokenizer_handle, dense_text: str, sparse_text: str | None, max_len: int, limit: int,
                    sparse_weight: float = 0.1, fusion: int = VR_FUSION_MINMAX, flt: SearchFilter | None = None):
         """A question as text in ONE engine call (vr_query_text): WordPiece + BM25 tokenise + encode + hybrid (or, when
-        no stem survives, dense) search. -> (rows int64[c], scores f64[c], from_dense int32[c], hybrid: bool)."""
+        no stem survives, dense) search. tokenizer_handle: a WordPieceTokenizer / UnigramTokenizer or a vr_wordpiece
+        handle. -> (rows int64[c], scores f64[c], from_dense int32[c], hybrid: bool)."""
+        fn, h = self._text_fn("query_text", tokenizer_handle)
         d = dense_text.encode("utf-8", "replace")
         sp = sparse_text.encode("utf-8", "surrogatepass") if sparse_text else None
         rows, scores, fd = np.empty(limit, np.int64), np.empty(limit, np.float64), np.empty(limit, np.int32)
         cnt, hyb = C.c_int32(), C.c_int32()
         fp, keep = self._filter(flt)
-        check(self._lib.vr_query_text(self._h, tokenizer_handle, d, len(d), sp, len(sp) if sp else 0, int(max_len), limit,
+        check(fn(self._h, h, d, len(d), sp, len(sp) if sp else 0, int(max_len), limit,
                                       float(sparse_weight), fusion, fp, _ptr(rows, C.c_int64), _ptr(scores, C.c_double),
                                       _ptr(fd, C.c_int32), C.byref(cnt), C.byref(hyb)))
         del keep
@@ -461,7 +472,9 @@ class Engine:
         sparse_texts[i], max_len, limits[i], sparse_weights[i], fusion, filters[i]) — one forward pass over all of
         them, then the filtered batch searches. sparse_texts: one str | None per question (None: no sparse leg).
         -> list of (rows, scores, from_dense, hybrid); raw=True: (rows, scores, from_dense, counts, hybrid) arrays.
-        embeddings=True: also the (n, hidden) f32 embeddings, as a second return value."""
+        embeddings=True: also the (n, hidden) f32 embeddings, as a second return value. tokenizer_handle: as
+        query_text's."""
+        fn, h = self._text_fn("query_text_batch", tokenizer_handle)
         n = len(dense_texts)
         assert sparse_texts is None or len(sparse_texts) == n
         d = [t.encode("utf-8", "replace") for t in dense_texts]
@@ -480,7 +493,7 @@ class Engine:
         counts = np.zeros(n, np.int32)
         hyb = np.zeros(n, np.int32)
         emb = np.empty((n, self.dim), np.float32) if embeddings else None
-        check(self._lib.vr_query_text_batch(self._h, tokenizer_handle, n, d_arr, _ptr(d_len, C.c_int64), s_arr,
+        check(fn(self._h, h, n, d_arr, _ptr(d_len, C.c_int64), s_arr,
                                             _ptr(s_len, C.c_int64), int(max_len), _ptr(lim, C.c_int32),
                                             _ptr(wts, C.c_double), fusion, farr, nf, _ptr(foq, C.c_int32), stride,
                                             _ptr(rows, C.c_int64), _ptr(scores, C.c_double), _ptr(fd, C.c_int32),
@@ -497,21 +510,23 @@ class Engine:
     # ---- cross-encoder reranking (vr_reranker_load is driven by encoder.load_reranker) ------------------------------
     def rerank(self, ids, offsets, seg_b) -> np.ndarray:
         """One f32 logit per pair sequence (vr_rerank): ids / offsets as encode's, seg_b[i] the position of sequence
-        i's first segment-B token. Host arrays."""
+        i's first segment-B token (None for a reranker with one token type, XLM-R). Host arrays."""
         ids = _np(ids, np.int32)
         off = _np(offsets, np.int32)
-        seg = _np(seg_b, np.int32)
         n = off.shape[0] - 1
-        if seg.shape[0] != n:
+        seg = None if seg_b is None else _np(seg_b, np.int32)
+        if seg is not None and seg.shape[0] != n:
             raise ValueError(f"{n} sequences, {seg.shape[0]} seg_b entries")
         out = np.empty(max(n, 1), np.float32)
-        check(self._lib.vr_rerank(self._h, ids.ctypes.data, off.ctypes.data, seg.ctypes.data, n, VR_MEM_HOST,
-                                  out.ctypes.data, VR_MEM_HOST))
+        check(self._lib.vr_rerank(self._h, ids.ctypes.data, off.ctypes.data, None if seg is None else seg.ctypes.data, n,
+                                  VR_MEM_HOST, out.ctypes.data, VR_MEM_HOST))
         return out[:n]
 
     def rerank_text(self, tokenizer_handle, queries, candidates, max_len: int) -> list[np.ndarray]:
         """Question q paired with each passage of candidates[q], all pairs scored in ONE call (vr_rerank_text).
-        -> one f32 logit array per question, in candidate order (empty for a question without candidates)."""
+        -> one f32 logit array per question, in candidate order (empty for a question without candidates).
+        tokenizer_handle: a WordPieceTokenizer / UnigramTokenizer or a vr_wordpiece handle."""
+        fn, h = self._text_fn("rerank_text", tokenizer_handle)
         nq = len(queries)
         if len(candidates) != nq:
             raise ValueError(f"{nq} questions, {len(candidates)} candidate lists")
@@ -524,7 +539,7 @@ class Engine:
         q_len = np.array([len(t) for t in q] or [0], np.int64)
         p_len = np.array([len(t) for t in p] or [0], np.int64)
         out = np.empty(max(len(p), 1), np.float32)
-        check(self._lib.vr_rerank_text(self._h, tokenizer_handle, nq, q_arr, _ptr(q_len, C.c_int64), _ptr(cand_off, C.c_int64),
+        check(fn(self._h, h, nq, q_arr, _ptr(q_len, C.c_int64), _ptr(cand_off, C.c_int64),
                                        p_arr, _ptr(p_len, C.c_int64), int(max_len), _ptr(out, C.c_float)))
         return [out[cand_off[i]:cand_off[i + 1]].copy() for i in range(nq)]
 

@@ -861,7 +861,7 @@ class VectorStoreService:
             sparse_text = sparse_query.text if (sparse_query is not None and self._has_sparse) else None
 
             def run_text(search_filter):
-                rows, scores, _fd, was_hybrid = self._engine.query_text(model.tokenizer._h, query_embedding.text, sparse_text,
+                rows, scores, _fd, was_hybrid = self._engine.query_text(model.tokenizer, query_embedding.text, sparse_text,
                                                                         model.max_seq_length, limit, sparse_weight, flt=search_filter)
                 return rows, ([float(s) for s in scores] if was_hybrid else [_json_float(np.float32(s)) for s in scores])
 
@@ -1059,7 +1059,7 @@ class VectorStoreService:
         return self._search_questions_first_stage(requests)
 
     def _search_questions_first_stage(self, requests: list[dict]) -> list[list[StoredChunk]]:
-        from .embedding import WordPieceTokenizer, get_embedding_service
+        from .embedding import get_embedding_service, native_tokenizer
 
         n = len(requests)
         out: list[list[StoredChunk]] = [[] for _ in range(n)]
@@ -1069,7 +1069,7 @@ class VectorStoreService:
         emb = get_embedding_service()
         model = emb.model
         queries = [requests[i]["query"] for i in live]
-        if not (isinstance(model.tokenizer, WordPieceTokenizer) and model.engine is self._engine
+        if not (native_tokenizer(model.tokenizer) and model.engine is self._engine
                 and int(model.desc.hidden) == self.dimension):
             # (an encoder outside this engine: the two services, then search_requests — the definition of the answer)
             from .sparse_embedding import _query_vector
@@ -1094,7 +1094,7 @@ class VectorStoreService:
             return [self._build_filter(**{a: requests[i].get(a) for a in self._FILTER_ARGS}) for i in live]
 
         def run(filters):
-            r, s, _fd, c, hyb = self._engine.query_text_batch(model.tokenizer._h, texts, sparse_texts, model.max_seq_length,
+            r, s, _fd, c, hyb = self._engine.query_text_batch(model.tokenizer, texts, sparse_texts, model.max_seq_length,
                                                               limits, weights, filters, raw=True)
             rows = [r[j, : c[j]] for j in range(len(live))]
             scores = [[float(v) for v in s[j, : c[j]]] if hyb[j] else [_json_float(np.float32(v)) for v in s[j, : c[j]]]
