@@ -451,6 +451,20 @@ int vr_search_hybrid_keys(vr_engine* e, const float* q, int32_t nq, int mem,
 int vr_merge_keys(vr_engine* e, const uint64_t* parts, int32_t n_parts, int32_t n_lists, int32_t k, int mem,
                   int64_t* out_ids, float* out_scores, int32_t* out_counts);
 
+/* MMR selection over candidate lists of stored rows. List i is rows[list_off[i] .. list_off[i+1]) with
+ * relevance[...] (f64, first-stage order), diversity[i] in [0, 1], limits[i] >= 0; list length <= 1024.
+ * out_pos: n_lists x out_stride (out_stride >= every limit), positions into list i in selection order;
+ * out_counts[i] = min(limits[i], length). All arrays are host arrays. `generation` is the VR_STAT_GENERATION the
+ * rows were read under: if the index has been renumbered since, nothing runs and VR_STALE_GENERATION (> 0) is
+ * returned. Rows outside [0, n_rows) and bad arguments are errors (< 0), checked before any device work.
+ * Selection: step 1 picks the largest (1 - d) * rel_i, every later step the largest (1 - d) * rel_i - d * (double) m_i,
+ * m_i the f32 maximum of sim(i, s) over the picks s so far, sim the f32 dense score of one stored row against another;
+ * f64 operations rounded one at a time, ties to the lower position. Tombstoned rows are allowed. */
+#define VR_STALE_GENERATION 1
+int vr_mmr_select(vr_engine* e, int32_t n_lists, const int64_t* list_off, const int64_t* rows,
+                  const double* relevance, const double* diversity, const int32_t* limits, int64_t generation,
+                  int32_t out_stride, int32_t* out_pos, int32_t* out_counts);
+
 /* The fusion arithmetic for nq pairs of lists at once, on the host threads (vector_store.py:659-697 per query; the
  * last step of a batched or sharded hybrid search). d_* / s_*: [nq][k] with counts [nq] (s_* may be NULL);
  * out_*: [nq][limit], out_counts [nq]. fusion: VR_FUSION_*; json_scores as in vr_fuse_minmax. */

@@ -71,6 +71,7 @@ VR_MEM_DEVICE = 1
 VR_TS_ABSENT = -(2**63)
 VR_FUSION_MINMAX = 0
 VR_FUSION_RRF = 1
+VR_STALE_GENERATION = 1  # vr_mmr_select: the index was renumbered since the caller read its rows
 
 _vp = C.c_void_p
 _fp = C.POINTER(C.c_float)
@@ -148,6 +149,7 @@ SIGNATURES = {
     "vr_merge_keys": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int, _i64p, _fp, _i32p]),
     "vr_fuse_batch": (C.c_int, [_i64p, _fp, _i32p, _i64p, _fp, _i32p, C.c_int32, C.c_int32, C.c_int32, C.c_double,
                                 C.c_int32, C.c_int32, _i64p, _dp, _i32p, _i32p]),
+    "vr_mmr_select": (C.c_int, [_vp, C.c_int32, _i64p, _i64p, _dp, _dp, _i32p, C.c_int64, C.c_int32, _i32p, _i32p]),
     "vr_sparse_row_ids": (C.c_int, [_vp, _i64p, C.c_int64, _vp, C.c_int64, C.c_int, _i32p, _i64p]),
     "vr_df_apply": (C.c_int, [_vp, _vp, C.c_int64, C.c_int, C.c_int64, C.c_int32]),
     "vr_query_text": (C.c_int, [_vp, _vp, C.c_char_p, C.c_int64, C.c_char_p, C.c_int64, C.c_int32, C.c_int32, C.c_double,

@@ -28,6 +28,11 @@ class Settings:
         # hybrid candidates (clamped to [limit, 341]), rescores them on the GPU and returns the best `limit`
         self.rerank_model: str = os.getenv("VOITTA_RERANK_MODEL", "")
         self.rerank_candidates: int = int(os.getenv("VOITTA_RERANK_CANDIDATES", "50"))
+        # MMR diversification of search results (opt-in): unset = off; a value in [0, 1] is the diversity d of every
+        # search. The first stage then fetches VOITTA_MMR_CANDIDATES (clamped to [limit, 341]) and MMR selects `limit`
+        mmr = os.getenv("VOITTA_MMR_DIVERSITY", "")
+        self.mmr_diversity: float | None = float(mmr) if mmr.strip() else None
+        self.mmr_candidates: int = int(os.getenv("VOITTA_MMR_CANDIDATES", "50"))
 
 
 @lru_cache

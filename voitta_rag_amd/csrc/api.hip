@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <climits>
+#include <cmath>
 #include <thread>
 
 #include "host_parallel.h"
@@ -188,6 +189,14 @@ static void release_scratch(vr_engine* e) {
   e->mg_gid.release();
   e->mg_score.release();
   e->mg_cnt.release();
+  e->mmr_ws.release();
+  e->mmr_gram.release();
+  e->mmr_rows.release();
+  e->mmr_rel.release();
+  e->mmr_lists.release();
+  e->mmr_tiles.release();
+  e->mmr_pairs.release();
+  e->mmr_out.release();
   if (e->pinned) (void)hipHostFree(e->pinned);
   e->pinned = nullptr;
   if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
@@ -1773,6 +1782,40 @@ int vr_merge_keys(vr_engine* e, const uint64_t* parts, int32_t n_parts, int32_t 
   VR_HIP(hipMemcpyAsync(cnt.data(), L->mg_cnt.p, sizeof(int32_t) * static_cast<size_t>(n_lists), hipMemcpyDeviceToHost, L->stream));
   VR_HIP(hipStreamSynchronize(L->stream));
   if (out_counts) memcpy(out_counts, cnt.data(), sizeof(int32_t) * static_cast<size_t>(n_lists));
+  return 0;
+}
+
+int vr_mmr_select(vr_engine* e, int32_t n_lists, const int64_t* list_off, const int64_t* rows, const double* relevance,
+                  const double* diversity, const int32_t* limits, int64_t generation, int32_t out_stride, int32_t* out_pos,
+                  int32_t* out_counts) {
+  VR_TRY(check_engine(e));
+  VR_CHECK(n_lists >= 0, "n_lists = %d", n_lists);
+  if (n_lists == 0) return 0;
+  VR_CHECK(list_off && diversity && limits && out_counts && out_stride >= 0, "bad arguments");
+  VR_CHECK(list_off[0] == 0, "list_off[0] = %lld, must be 0", static_cast<long long>(list_off[0]));
+  for (int32_t i = 0; i < n_lists; ++i) {
+    const int64_t len = list_off[i + 1] - list_off[i];
+    VR_CHECK(len >= 0, "list_off decreases at list %d", i);
+    VR_CHECK(len <= kMaxK, "list %d holds %lld candidates, at most %d", i, static_cast<long long>(len), kMaxK);
+    VR_CHECK(diversity[i] >= 0.0 && diversity[i] <= 1.0, "list %d: diversity %g not in [0, 1]", i, diversity[i]);
+    VR_CHECK(limits[i] >= 0 && limits[i] <= out_stride, "list %d: limit %d not in [0, out_stride = %d]", i, limits[i],
+             out_stride);
+  }
+  const int64_t n = list_off[n_lists];
+  VR_CHECK(n == 0 || (rows && relevance), "bad arguments");
+  VR_CHECK(out_pos || out_stride == 0, "bad arguments");
+  for (int64_t j = 0; j < n; ++j)
+    VR_CHECK(std::isfinite(relevance[j]), "relevance %lld is not finite", static_cast<long long>(j));
+  SearchLane lane(e);
+  VR_TRY(lane.acquire(false));
+  if (e->generation.load() != generation) return VR_STALE_GENERATION;  // (under the shared lock: no renumbering now)
+  vr_engine* L = lane.L;
+  for (int64_t j = 0; j < n; ++j)
+    VR_CHECK(rows[j] >= 0 && rows[j] < L->n_rows, "row %lld out of range [0, %lld)", static_cast<long long>(rows[j]),
+             static_cast<long long>(L->n_rows));
+  VR_TRY(mmr_select_run(L, n_lists, list_off, rows, relevance, diversity, limits, out_stride, out_pos));
+  for (int32_t i = 0; i < n_lists; ++i)
+    out_counts[i] = static_cast<int32_t>(std::min<int64_t>(limits[i], list_off[i + 1] - list_off[i]));
   return 0;
 }
 

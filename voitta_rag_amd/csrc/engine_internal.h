@@ -176,6 +176,19 @@ struct ClassDesc {
   int32_t pad;
 };
 
+// One candidate list of a slice of vr_mmr_select (mmr.hip): where its rows, workspace tiles, Gram and picks are
+struct MmrList {
+  int64_t row_off;   // first candidate in the slice's rows / relevance arrays
+  int64_t tile0;     // first workspace tile
+  int64_t gram_off;  // first Gram element (k_pad x k_pad, row-major)
+  int64_t out_off;   // first output position
+  double d;          // diversity
+  int32_t k;         // candidates
+  int32_t count;     // picks: min(limit, k)
+  int32_t ntiles;    // k_pad / 16
+  int32_t pad;
+};
+
 // The classes of a filtered batch as the grouped sparse scan (invert.hip) takes them: the bit planes of filter_build_planes
 // and, per query of the batch, its plane (host array).
 struct ClassPlanes {
@@ -355,6 +368,16 @@ struct vr_engine {
   vr::DevArray<int64_t> mg_gid;
   vr::DevArray<float> mg_score;
   vr::DevArray<int32_t> mg_cnt;
+  // vr_mmr_select (mmr.hip): the gathered candidate rows (MFMA-tiled, 16-row tiles per list), the lists' Gram matrices,
+  // the slice's rows / relevance / list descriptors / tile -> list map / (list, tile column) pairs, and the picks
+  vr::DevArray<float> mmr_ws;
+  vr::DevArray<float> mmr_gram;
+  vr::DevArray<int64_t> mmr_rows;
+  vr::DevArray<double> mmr_rel;
+  vr::DevArray<vr::MmrList> mmr_lists;
+  vr::DevArray<int32_t> mmr_tiles;
+  vr::DevArray<int2> mmr_pairs;
+  vr::DevArray<int32_t> mmr_out;
   // Pinned, device-mapped host scratch (1 MiB). Query inputs are written here by the host and
   // read by the kernels straight over PCIe, results are written here by the last kernel of a
   // search: the latency path of a query has no hipMemcpy at all.
@@ -517,6 +540,11 @@ int filter_build_mask(vr_engine* e, const vr_filter* f, const uint8_t** mask_out
 int64_t filter_plane_words(const vr_engine* e);
 // the bit planes of n_cls filters (filters[c] == nullptr: live rows) in e->cls_planes, [c][filter_plane_words(e)]
 int filter_build_planes(vr_engine* e, const vr_filter* const* filters, int n_cls, const uint32_t** planes_out);
+
+// ---- mmr.hip: MMR selection over validated candidate lists (rows in [0, n_rows), lengths <= kMaxK, d in [0, 1]);
+// positions of list i in selection order to out_pos[i * out_stride ..], min(limits[i], length) of them (host arrays)
+int mmr_select_run(vr_engine* e, int32_t n_lists, const int64_t* list_off, const int64_t* rows, const double* relevance,
+                   const double* diversity, const int32_t* limits, int32_t out_stride, int32_t* out_pos);
 
 // ---- fusion.cpp (host only)
 int fuse_minmax(const int64_t* d_rows, const float* d_scores, int nd, const int64_t* s_rows,

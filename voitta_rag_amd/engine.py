@@ -11,7 +11,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from ._lib import VR_FUSION_MINMAX, VR_FUSION_RRF, VR_MEM_DEVICE, VR_MEM_HOST, VR_TS_ABSENT, check
+from ._lib import VR_FUSION_MINMAX, VR_FUSION_RRF, VR_MEM_DEVICE, VR_MEM_HOST, VR_STALE_GENERATION, VR_TS_ABSENT, check
 
 __all__ = ["Engine", "SearchFilter", "VR_FUSION_MINMAX", "VR_FUSION_RRF", "VR_TS_ABSENT"]
 
@@ -752,6 +752,40 @@ class Engine:
                                       _ptr(counts, C.c_int32)))
         del keep
         return ids, scores, counts
+
+    def mmr_select(self, rows_lists, relevance_lists, diversities, limits, generation: int,
+                   fusion: int = VR_FUSION_MINMAX):
+        """Maximal marginal relevance over candidate lists of stored rows, all lists in ONE engine call (vr_mmr_select,
+        DESIGN §15). rows_lists[i]: the candidates' rows in first-stage order (<= 1024), relevance_lists[i] their f64
+        relevance, diversities[i] in [0, 1], limits[i] >= 0. -> per list the positions into it in selection order
+        (int32, min(limit, length) of them), or None when the index was renumbered since ``generation`` (the
+        caller's rows belong to another numbering: search again). fusion: how hybrid relevance was fused; RRF scores
+        (about 1/60) are refused, the similarity term would swamp them."""
+        if fusion == VR_FUSION_RRF:
+            raise ValueError("MMR over RRF-fused relevance is not supported: fuse with VR_FUSION_MINMAX")
+        n = len(rows_lists)
+        assert len(relevance_lists) == n and len(diversities) == n and len(limits) == n
+        if n == 0:
+            return []
+        lens = [len(r) for r in rows_lists]
+        off = np.zeros(n + 1, np.int64)
+        off[1:] = np.cumsum(lens)
+        rows = np.ascontiguousarray(np.concatenate([np.asarray(r, np.int64).reshape(-1) for r in rows_lists]), np.int64)
+        rel = np.ascontiguousarray(np.concatenate([np.asarray(v, np.float64).reshape(-1) for v in relevance_lists]),
+                                   np.float64)
+        assert rel.size == rows.size
+        div = np.ascontiguousarray(diversities, np.float64)
+        lim = np.ascontiguousarray(limits, np.int32)
+        stride = max(1, int(lim.max()))
+        pos = np.zeros((n, stride), np.int32)
+        counts = np.zeros(n, np.int32)
+        rc = self._lib.vr_mmr_select(self._h, n, _ptr(off, C.c_int64), _ptr(rows, C.c_int64), _ptr(rel, C.c_double),
+                                     _ptr(div, C.c_double), _ptr(lim, C.c_int32), int(generation), stride,
+                                     _ptr(pos, C.c_int32), _ptr(counts, C.c_int32))
+        if rc == VR_STALE_GENERATION:
+            return None
+        check(rc)
+        return [pos[i, : counts[i]].copy() for i in range(n)]
 
     # ---- collection-wide document frequencies on a sharded corpus ----------------------------------------------------
     def sparse_row_ids(self, rows, device: bool = False):

@@ -805,9 +805,14 @@ class VectorStoreService:
     def _rerank(rr, questions: list[str], candidates: list[list[StoredChunk]], limits: list[int]) -> list[list[StoredChunk]]:
         """Every question's candidates rescored in ONE engine call (vr_rerank_text); the best `limit` of each, with
         score = sigmoid(logit), best first (equal scores keep the first stage's order)."""
+        logits = rr.logits(questions, [[c.text for c in cands] for cands in candidates])
+        return VectorStoreService._rerank_order(candidates, logits, limits)
+
+    @staticmethod
+    def _rerank_order(candidates: list[list[StoredChunk]], logits, limits: list[int]) -> list[list[StoredChunk]]:
+        """The best `limit` of every list by its logits, score = sigmoid(logit) (equal scores keep the first stage's order)."""
         from .reranker import sigmoid
 
-        logits = rr.logits(questions, [[c.text for c in cands] for cands in candidates])
         out = []
         for cands, lg, limit in zip(candidates, logits, limits):
             scores = sigmoid(lg)
@@ -815,39 +820,128 @@ class VectorStoreService:
             out.append([dataclasses.replace(cands[i], score=float(scores[i])) for i in order])
         return out
 
+    # ---- MMR diversification (VOITTA_MMR_DIVERSITY) --------------------------------------------------------
+    # The first stage (dense, hybrid, text, batched or reranked) fetches the candidate pool; ONE vr_mmr_select call then
+    # picks `limit` of every list of the call, by maximal marginal relevance over the stored rows' similarities. Each
+    # chunk keeps its first-stage score and transport, so the scores of an MMR result are not monotone.
+
+    @staticmethod
+    def _mmr_spec(limit: int, mmr_diversity, mmr_candidates) -> tuple[float, int] | None:
+        """-> None (MMR off) or (diversity, candidates to fetch). None arguments fall back to the settings."""
+        settings = get_settings()
+        d = settings.mmr_diversity if mmr_diversity is None else mmr_diversity
+        if d is None or int(limit) <= 0:
+            return None
+        d = float(d)
+        if not 0.0 <= d <= 1.0:
+            raise ValueError(f"mmr_diversity {d} not in [0, 1]")
+        from .reranker import rerank_candidates
+
+        c = settings.mmr_candidates if mmr_candidates is None else int(mmr_candidates)
+        # d = 0 keeps the first stage's order, so its pool is the limit itself: a hybrid pool's min-max fusion depends on
+        # the pool's size, and d = 0 answers exactly what the plain search does
+        return d, (int(limit) if d == 0.0 else rerank_candidates(c, int(limit)))
+
+    def _generation(self) -> int:
+        return self._engine.generation() if hasattr(self._engine, "generation") else 0
+
+    def _mmr_reorder(self, generation: int, rows: list, scores: list, rels: list, picks: list):
+        """picks[j]: None (list j as it is) or (diversity, limit). Lists j with MMR are replaced by their selection, in
+        place; False when the engine reports a renumbered index (the rows belong to another numbering)."""
+        todo = [j for j, p in enumerate(picks) if p is not None]
+        if not todo:
+            return True
+        pos = self._engine.mmr_select([rows[j] for j in todo], [rels[j] for j in todo], [picks[j][0] for j in todo],
+                                      [picks[j][1] for j in todo], generation)
+        if pos is None:
+            return False
+        for j, p in zip(todo, pos):
+            rows[j] = np.asarray(rows[j], np.int64)[p]
+            scores[j] = [scores[j][i] for i in p]
+        return True
+
+    def _mmr_rerank(self, rr, questions: list[str], candidates: list[list[StoredChunk]], limits: list[int],
+                    specs: list) -> list[list[StoredChunk]]:
+        """The reranked path with MMR: every candidate rescored (one vr_rerank_text call), then, for the lists with a spec,
+        MMR over the whole pool with sigmoid(logit) as relevance; the others as _rerank returns them."""
+        from .reranker import sigmoid
+
+        logits = rr.logits(questions, [[c.text for c in cands] for cands in candidates])
+        scored = [[dataclasses.replace(c, score=float(v)) for c, v in zip(cands, sigmoid(lg))]
+                  for cands, lg in zip(candidates, logits)]
+        plain = [j for j, spec in enumerate(specs) if spec is None]  # (the lists without MMR: exactly what _rerank returns)
+        out: list = [[] for _ in specs]
+        for j, res in zip(plain, self._rerank_order([candidates[j] for j in plain], [logits[j] for j in plain],
+                                                    [limits[j] for j in plain])):
+            out[j] = res
+        todo = [j for j, spec in enumerate(specs) if spec is not None and scored[j]]
+        if not todo:
+            return out
+        col = self._col
+
+        def run(_):
+            with col.lock:  # the candidates' rows in the numbering of the host table (deleted since: dropped)
+                gen = col.generation
+                kept = [[i for i, c in enumerate(scored[j]) if c.id in col.row_of] for j in todo]
+                rows = [np.asarray([col.row_of[scored[j][i].id] for i in k], np.int64) for j, k in zip(todo, kept)]
+            rels = [np.asarray([scored[j][i].score for i in k], np.float64) for j, k in zip(todo, kept)]
+            picks = [(specs[j][0], limits[j]) for j in todo]
+            if not self._mmr_reorder(gen, rows, kept, rels, picks):
+                return None
+            return np.zeros(0, np.int64), kept
+
+        _, kept = self._consistent(col, run, lambda: None)
+        for j, k in zip(todo, kept):
+            out[j] = [scored[j][i] for i in k]
+        return out
+
     def search(self, query_embedding: list[float], limit: int = 10, folder_filter: str | None = None,
                include_folders: list[str] | None = None, exclude_folders: list[str] | None = None,
                exclude_index_folders: list[str] | None = None,
                sparse_query: tuple[list[int], list[float]] | None = None, sparse_weight: float = 0.1,
                date_start: int | None = None, date_end: int | None = None,
-               date_field: str | None = None) -> list[StoredChunk]:
+               date_field: str | None = None, mmr_diversity: float | None = None,
+               mmr_candidates: int | None = None) -> list[StoredChunk]:
         """Dense or hybrid retrieval with the reference's branch selection (vector_store.py:560-619). With
         VOITTA_RERANK_MODEL set: the top VOITTA_RERANK_CANDIDATES of that, reranked by the cross-encoder, the best
         `limit` returned. The question's text comes from the sparse query or from embed_query's result; a bare list
-        of floats without either is answered unreranked (counted in ``unreranked_searches``)."""
+        of floats without either is answered unreranked (counted in ``unreranked_searches``).
+        MMR (mmr_diversity, or VOITTA_MMR_DIVERSITY; None = the setting, unset = off): the first stage fetches
+        mmr_candidates (VOITTA_MMR_CANDIDATES, clamped to [limit, 341]) — reranked, the rerank candidates, all of them
+        rescored — and maximal marginal relevance picks `limit` of them. Every chunk keeps its first-stage
+        score: an MMR result's scores are not monotone."""
         args = dict(folder_filter=folder_filter, include_folders=include_folders, exclude_folders=exclude_folders,
                     exclude_index_folders=exclude_index_folders, sparse_query=sparse_query, sparse_weight=sparse_weight,
                     date_start=date_start, date_end=date_end, date_field=date_field)
+        spec = self._mmr_spec(limit, mmr_diversity, mmr_candidates)
         rr = self._reranker() if limit > 0 else None
         if rr is None:
-            return self._search_first_stage(query_embedding, limit, **args)
+            return self._search_mmr_or_plain(query_embedding, limit, spec, args)
         question = getattr(sparse_query, "text", None) if isinstance(sparse_query, _deferred.SparseQueryRef) else None
         if question is None:
             question = getattr(query_embedding, "question", None)
         if question is None:
             VectorStoreService.unreranked_searches += 1
-            return self._search_first_stage(query_embedding, limit, **args)
+            return self._search_mmr_or_plain(query_embedding, limit, spec, args)
         from .reranker import rerank_candidates
 
         cands = self._search_first_stage(query_embedding, rerank_candidates(get_settings().rerank_candidates, limit), **args)
+        if spec is not None:
+            return self._mmr_rerank(rr, [question], [cands], [limit], [spec])[0]
         return self._rerank(rr, [question], [cands], [limit])[0]
+
+    def _search_mmr_or_plain(self, query_embedding, limit: int, spec, args: dict) -> list[StoredChunk]:
+        if spec is None:
+            return self._search_first_stage(query_embedding, limit, **args)
+        return self._search_first_stage(query_embedding, spec[1], mmr=(spec[0], limit), **args)
 
     def _search_first_stage(self, query_embedding: list[float], limit: int = 10, folder_filter: str | None = None,
                             include_folders: list[str] | None = None, exclude_folders: list[str] | None = None,
                             exclude_index_folders: list[str] | None = None,
                             sparse_query: tuple[list[int], list[float]] | None = None, sparse_weight: float = 0.1,
                             date_start: int | None = None, date_end: int | None = None,
-                            date_field: str | None = None) -> list[StoredChunk]:
+                            date_field: str | None = None, mmr: tuple[float, int] | None = None) -> list[StoredChunk]:
+        """mmr: None, or (diversity, final limit): `limit` candidates are fetched and MMR picks the final limit of them."""
         if limit <= 0:
             return []  # Qdrant answers limit=0 with no points (a caller-supplied MCP argument, mcp_server.py:376,474)
         col = self._col
@@ -861,9 +955,12 @@ class VectorStoreService:
             sparse_text = sparse_query.text if (sparse_query is not None and self._has_sparse) else None
 
             def run_text(search_filter):
+                gen = self._generation()
                 rows, scores, _fd, was_hybrid = self._engine.query_text(model.tokenizer, query_embedding.text, sparse_text,
                                                                         model.max_seq_length, limit, sparse_weight, flt=search_filter)
-                return rows, ([float(s) for s in scores] if was_hybrid else [_json_float(np.float32(s)) for s in scores])
+                out = [float(s) for s in scores] if was_hybrid else [_json_float(np.float32(s)) for s in scores]
+                rel = np.asarray(scores, np.float64) if was_hybrid else np.asarray(scores, np.float32).astype(np.float64)
+                return self._mmr_one(gen, rows, out, rel, mmr)
 
             rows, scores = self._search_consistent(col, run_text, folder_filter, include_folders, exclude_folders,
                                                    exclude_index_folders, date_start, date_end, date_field)
@@ -872,16 +969,27 @@ class VectorStoreService:
         hybrid = bool(sparse_query and self._has_sparse and sparse_query[0])
 
         def run(search_filter):
+            gen = self._generation()
             if hybrid:
                 rows, scores, _ = self._engine.search_hybrid(q, sparse_query[0], sparse_query[1], limit, sparse_weight,
                                                             flt=search_filter)
-                return rows, [float(s) for s in scores]
+                return self._mmr_one(gen, rows, [float(s) for s in scores], np.asarray(scores, np.float64), mmr)
             rows, scores = self._engine.search_dense(q[None, :], limit, search_filter)[0]
-            return rows, [_json_float(s) for s in scores]
+            rel = np.asarray(scores, np.float32).astype(np.float64)
+            return self._mmr_one(gen, rows, [_json_float(s) for s in scores], rel, mmr)
 
         rows, scores = self._search_consistent(col, run, folder_filter, include_folders, exclude_folders, exclude_index_folders,
                                                date_start, date_end, date_field)
         return [self._chunk_from(pid, payload, s) for (pid, payload), s in zip(rows, scores) if payload is not None]
+
+    def _mmr_one(self, generation: int, rows, scores: list, rel, mmr):
+        """(rows, scores) of one first-stage list, MMR-selected when mmr is (diversity, limit); None: look again."""
+        if mmr is None:
+            return rows, scores
+        rows, scores = [rows], [scores]
+        if not self._mmr_reorder(generation, rows, scores, [rel], [mmr]):
+            return None
+        return rows[0], scores[0]
 
     def _query_array(self, query_embedding) -> np.ndarray:
         """The (D,) f32 query of a search: embed_query's own array when the list was not edited since, else the list."""
@@ -922,7 +1030,12 @@ class VectorStoreService:
                                        f"within {self._SEARCH_DEADLINE_S:.0f} s")
                 time.sleep(0.0005)
                 continue
-            rows, extra = run(search_filter)
+            result = run(search_filter)
+            if result is None:  # (an MMR step met a renumbered index: the first stage's rows are of no use)
+                if time.monotonic() > deadline:
+                    raise RuntimeError(f"search: the collection kept changing for {self._SEARCH_DEADLINE_S:.0f} s")
+                continue
+            rows, extra = result
             with col.lock:
                 unchanged = col.version == version and (not has_generation
                                                         or self._engine.generation() == col.generation == generation)
@@ -936,17 +1049,21 @@ class VectorStoreService:
                     include_folders: list[str] | None = None, exclude_folders: list[str] | None = None,
                     exclude_index_folders: list[str] | None = None, sparse_queries=None, sparse_weight: float = 0.1,
                     date_start: int | None = None, date_end: int | None = None,
-                    date_field: str | None = None) -> list[list[StoredChunk]]:
+                    date_field: str | None = None, mmr_diversity: float | None = None,
+                    mmr_candidates: int | None = None) -> list[list[StoredChunk]]:
         """``search`` for MANY queries in one engine call (BASELINE configs[4]: 1k batched queries; the MCP search tool
         under load, mcp_server.py:469-485): query_embeddings is (nq, D), sparse_queries a list of (indices, values)
         per query or None. Result i is what ``search(query_embeddings[i], ..., sparse_query=sparse_queries[i])``
         returns — same branch selection per query (vector_store.py:560-619: hybrid only with sparse terms), same
         filters, same scores — but the dense legs share one batched scan, the sparse legs one launch over the inverted
-        index, and the fusion of every query runs on the host threads (vr_search_hybrid_batch)."""
+        index, and the fusion of every query runs on the host threads (vr_search_hybrid_batch). MMR as in ``search``:
+        every query fetches the candidate pool, one vr_mmr_select call serves them all."""
         q = np.ascontiguousarray(np.asarray(query_embeddings, dtype=np.float32).reshape(-1, self.dimension))
         nq = q.shape[0]
         if limit <= 0 or nq == 0:
             return [[] for _ in range(nq)]
+        spec = self._mmr_spec(limit, mmr_diversity, mmr_candidates)
+        fetch = limit if spec is None else spec[1]
         col = self._col
         self._drain(col, surface_errors=False)
         sq = list(sparse_queries) if sparse_queries is not None and self._has_sparse else [None] * nq
@@ -955,22 +1072,33 @@ class VectorStoreService:
         any_hybrid = any(s is not None for s in sq)
 
         def run(search_filter):
+            gen = self._generation()
             if any_hybrid:
-                rows, scores, _fd, counts = self._engine.search_hybrid_batch(q, sq, limit, sparse_weight, flt=search_filter, raw=True)
+                rows, scores, _fd, counts = self._engine.search_hybrid_batch(q, sq, fetch, sparse_weight, flt=search_filter, raw=True)
             else:
-                rows, scores, counts = np.full((nq, limit), -1, np.int64), np.zeros((nq, limit)), np.zeros(nq, np.int32)
+                rows, scores, counts = np.full((nq, fetch), -1, np.int64), np.zeros((nq, fetch)), np.zeros(nq, np.int32)
             # a query without sparse terms takes the dense-only branch (:612-617): `limit` results, raw cosine scores
             dense_only = [i for i in range(nq) if sq[i] is None]
             out_scores = [[float(s) for s in scores[i, : counts[i]]] for i in range(nq)]
+            rels = [np.asarray(scores[i, : counts[i]], np.float64) for i in range(nq)]
             if dense_only:
-                res = self._engine.search_dense(q[dense_only], limit, search_filter)
+                res = self._engine.search_dense(q[dense_only], fetch, search_filter)
                 for i, (r, s) in zip(dense_only, res):
                     counts[i] = len(r)
                     rows[i, : len(r)] = r
                     rows[i, len(r):] = -1
                     out_scores[i] = [_json_float(v) for v in s]
+                    rels[i] = np.asarray(s, np.float32).astype(np.float64)
             for i in range(nq):
                 rows[i, counts[i]:] = -1
+            if spec is not None:
+                lists = [rows[i, : counts[i]] for i in range(nq)]
+                if not self._mmr_reorder(gen, lists, out_scores, rels, [(spec[0], limit)] * nq):
+                    return None
+                rows = np.full((nq, limit), -1, np.int64)
+                for i in range(nq):
+                    counts[i] = len(lists[i])
+                    rows[i, : counts[i]] = lists[i]
             return rows, (counts.copy(), out_scores)
 
         pairs, (counts, scores) = self._search_consistent(col, run, folder_filter, include_folders, exclude_folders,
@@ -991,7 +1119,9 @@ class VectorStoreService:
         sparse weight, the same branch selection (hybrid only with sparse terms), ``limit <= 0 -> []`` and the same score
         transport. What concurrent MCP ``search`` calls of many users (mcp_server.py:374-485) can share: the dense legs
         scan the corpus once for all filters (vr_search_hybrid_batch_multi / vr_search_dense_multi). Every filter is built
-        under one lock, so every request sees the same state of the collection."""
+        under one lock, so every request sees the same state of the collection. MMR per request (its keys
+        ``mmr_diversity`` / ``mmr_candidates``, None = the settings): those requests fetch their candidate pool, one
+        vr_mmr_select call serves them all; the others keep their results as without MMR."""
         n = len(requests)
         out: list[list[StoredChunk]] = [[] for _ in range(n)]
         live = [i for i in range(n) if int(requests[i].get("limit", 10)) > 0]
@@ -1000,7 +1130,10 @@ class VectorStoreService:
         col = self._col
         self._drain(col, surface_errors=False)
         q = np.stack([self._query_array(requests[i]["query_embedding"]) for i in live]).astype(np.float32, copy=False)
-        limits = [int(requests[i].get("limit", 10)) for i in live]
+        finals = [int(requests[i].get("limit", 10)) for i in live]
+        specs = [self._mmr_spec(finals[j], requests[i].get("mmr_diversity"), requests[i].get("mmr_candidates"))
+                 for j, i in enumerate(live)]
+        limits = [f if sp is None else sp[1] for f, sp in zip(finals, specs)]
         sparse = []
         for i in live:
             sp = requests[i].get("sparse_query")
@@ -1012,7 +1145,8 @@ class VectorStoreService:
             return [self._build_filter(**{a: requests[i].get(a) for a in self._FILTER_ARGS}) for i in live]
 
         def run(filters):
-            rows, scores = [None] * len(live), [None] * len(live)
+            gen = self._generation()
+            rows, scores, rels = [None] * len(live), [None] * len(live), [None] * len(live)
             if hyb:
                 r, s, _fd, c = self._engine.search_hybrid_batch_multi(
                     q[hyb], [sparse[j] for j in hyb], [limits[j] for j in hyb],
@@ -1020,6 +1154,7 @@ class VectorStoreService:
                 for t, j in enumerate(hyb):
                     rows[j] = r[t, : c[t]]
                     scores[j] = [float(v) for v in s[t, : c[t]]]
+                    rels[j] = np.asarray(s[t, : c[t]], np.float64)
             if dns:
                 k = max(limits[j] for j in dns)  # (exact top-k lists: the first limit of k are the top limit)
                 r, s, c = self._engine.search_dense_multi(q[dns], k, [filters[j] for j in dns], raw=True)
@@ -1027,6 +1162,10 @@ class VectorStoreService:
                     m = min(int(c[t]), limits[j])
                     rows[j] = r[t, :m]
                     scores[j] = [_json_float(v) for v in s[t, :m]]
+                    rels[j] = np.asarray(s[t, :m], np.float32).astype(np.float64)
+            picks = [None if sp is None else (sp[0], f) for sp, f in zip(specs, finals)]
+            if not self._mmr_reorder(gen, rows, scores, rels, picks):
+                return None
             counts = [len(x) for x in rows]
             flat = np.concatenate([np.asarray(x, np.int64) for x in rows])
             return flat, (counts, scores)
@@ -1046,16 +1185,22 @@ class VectorStoreService:
         the sparse ``embed_query(query)``: one forward pass over all questions, whose embeddings stay on the device and
         feed the filtered batch searches. What an MCP server that gathers concurrent questions (mcp_server.py:469-485)
         sends. Every filter is built under one lock, as in ``search_requests``. With VOITTA_RERANK_MODEL set: each
-        question's candidates as ``search`` fetches them, all reranked in one engine call (vr_rerank_text)."""
+        question's candidates as ``search`` fetches them, all reranked in one engine call (vr_rerank_text). MMR per
+        request as in ``search_requests`` (after the rerank, over the whole reranked pool, when a reranker is set)."""
         rr = self._reranker()
         if rr is not None and requests:  # first stage at the candidate count, then one rerank call for all questions
             from .reranker import rerank_candidates
 
             c = get_settings().rerank_candidates
             first = self._search_questions_first_stage(
-                [dict(r, limit=rerank_candidates(c, int(r.get("limit", 10))) if int(r.get("limit", 10)) > 0 else 0)
+                [dict({a: v for a, v in r.items() if a not in ("mmr_diversity", "mmr_candidates")},
+                      limit=rerank_candidates(c, int(r.get("limit", 10))) if int(r.get("limit", 10)) > 0 else 0)
                  for r in requests])
-            return self._rerank(rr, [r["query"] for r in requests], first, [int(r.get("limit", 10)) for r in requests])
+            limits = [int(r.get("limit", 10)) for r in requests]
+            specs = [self._mmr_spec(lim, r.get("mmr_diversity"), r.get("mmr_candidates")) for r, lim in zip(requests, limits)]
+            if any(sp is not None for sp in specs):
+                return self._mmr_rerank(rr, [r["query"] for r in requests], first, limits, specs)
+            return self._rerank(rr, [r["query"] for r in requests], first, limits)
         return self._search_questions_first_stage(requests)
 
     def _search_questions_first_stage(self, requests: list[dict]) -> list[list[StoredChunk]]:
@@ -1087,18 +1232,27 @@ class VectorStoreService:
         self._drain(col, surface_errors=False)
         texts = emb.query_texts(queries)
         sparse_texts = queries if self._has_sparse else None
-        limits = [int(requests[i].get("limit", 10)) for i in live]
+        finals = [int(requests[i].get("limit", 10)) for i in live]
+        specs = [self._mmr_spec(finals[j], requests[i].get("mmr_diversity"), requests[i].get("mmr_candidates"))
+                 for j, i in enumerate(live)]
+        limits = [f if sp is None else sp[1] for f, sp in zip(finals, specs)]
         weights = [float(requests[i].get("sparse_weight", 0.1)) for i in live]
 
         def build():
             return [self._build_filter(**{a: requests[i].get(a) for a in self._FILTER_ARGS}) for i in live]
 
         def run(filters):
+            gen = self._generation()
             r, s, _fd, c, hyb = self._engine.query_text_batch(model.tokenizer, texts, sparse_texts, model.max_seq_length,
                                                               limits, weights, filters, raw=True)
             rows = [r[j, : c[j]] for j in range(len(live))]
             scores = [[float(v) for v in s[j, : c[j]]] if hyb[j] else [_json_float(np.float32(v)) for v in s[j, : c[j]]]
                       for j in range(len(live))]
+            rels = [np.asarray(s[j, : c[j]], np.float64) if hyb[j] else np.asarray(s[j, : c[j]], np.float32).astype(np.float64)
+                    for j in range(len(live))]
+            picks = [None if sp is None else (sp[0], f) for sp, f in zip(specs, finals)]
+            if not self._mmr_reorder(gen, rows, scores, rels, picks):
+                return None
             counts = [len(x) for x in rows]
             flat = np.concatenate([np.asarray(x, np.int64) for x in rows])
             return flat, (counts, scores)
