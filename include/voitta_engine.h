@@ -125,13 +125,30 @@ typedef struct vr_bert_desc {
   int32_t heads;         /* H / heads must be 32 or 64 */
   int32_t intermediate;  /* multiple of 128 */
   int32_t vocab;
-  int32_t max_pos;       /* max_position_embeddings; also the longest accepted sequence */
+  int32_t max_pos;       /* max_position_embeddings; also the longest accepted sequence. VR_POS_ROTARY: the length of
+                          * the cos/sin table the engine builds, which is again the longest accepted sequence */
   int32_t type_vocab;
   int32_t pooling;       /* VR_POOL_MEAN | VR_POOL_CLS (sentence-transformers Pooling module) */
   int32_t normalize;     /* 1 = L2-normalise (sentence-transformers Normalize module) */
   float   eps;           /* layer_norm_eps */
   int32_t precision;     /* VR_PRECISION_F32 | VR_PRECISION_F16X3 | VR_PRECISION_F16 */
+  /* Added after the first release: zero in every field below is the behaviour of a description that ends at
+   * `precision` (struct_size may still be that shorter size; the missing fields are then read as zero). */
+  int32_t position;      /* VR_POS_LEARNED | VR_POS_ROTARY */
+  float   rope_theta;    /* VR_POS_ROTARY: base of the rotary frequencies, inv_freq_i = theta^(-2i/d_h); > 0 */
+  int32_t ffn;           /* VR_FFN_GELU | VR_FFN_SWIGLU | VR_FFN_GEGLU */
 } vr_bert_desc;
+
+/* position: LEARNED adds a row of the position table to every token's embedding; ROTARY has no table — the query and
+ * key of every head are rotated by the token's position inside its own sequence (rotate-half pairing: feature j with
+ * j + d_h/2, as in HF apply_rotary_pos_emb; the full head is rotated). */
+#define VR_POS_LEARNED 0
+#define VR_POS_ROTARY  1
+/* ffn: GELU is down(gelu(up(x))); the gated forms are down(act(gate(x)) * up(x)) with act = SiLU (SWIGLU) or the
+ * exact-erf GELU (GEGLU). */
+#define VR_FFN_GELU   0
+#define VR_FFN_SWIGLU 1
+#define VR_FFN_GEGLU  2
 
 /* arithmetic of the encoder's matrix products:
  *   F32    every product on the f32-input MFMA (exact f32 fma chains) — 157 TFLOP/s peak
@@ -151,6 +168,10 @@ typedef struct vr_bert_desc {
  *   then per layer: query.{weight,bias}, key.{weight,bias}, value.{weight,bias},
  *   attention.output.dense.{weight,bias}, attention.output.LayerNorm.{weight,bias},
  *   intermediate.dense.{weight,bias}, output.dense.{weight,bias}, output.LayerNorm.{weight,bias}.
+ * A gated ffn (VR_FFN_SWIGLU / VR_FFN_GEGLU) has 18 slots per layer (5 + 18*layers tensors): the 16 above, where
+ * intermediate.dense.{weight,bias} is the UP projection [I,H], followed by the GATE projection's {weight [I,H], bias}.
+ * NULL slots: any bias (read as zeros), and position_embeddings when position is VR_POS_ROTARY (ignored then).
+ * Every other slot must be non-NULL.
  * The engine copies (and re-packs) them; the caller's tensors may be freed afterwards.
  * Replaces EmbeddingService.model's lazy SentenceTransformer(...) load (embedding.py:23-42). */
 int vr_encoder_load(vr_engine* e, const vr_bert_desc* desc, const void* const* tensors,
@@ -536,7 +557,8 @@ int vr_query_text_batch_unigram(vr_engine* e, const vr_unigram* tokenizer, int32
  * vr_reranker_load: a BertForSequenceClassification with one label (cross-encoder/ms-marco-MiniLM-L-6-v2 and the
  * like). desc / tensors / mem as vr_encoder_load, followed by 4 more tensors: pooler.dense.weight [H,H],
  * pooler.dense.bias [H], classifier.weight [1,H], classifier.bias [1] (5 + 16 L + 4 in all). desc->pooling must be
- * VR_POOL_CLS and desc->normalize 0; any precision; type_vocab >= 1; H need not equal the engine's dim. An XLM-R
+ * VR_POOL_CLS and desc->normalize 0; position VR_POS_LEARNED and ffn VR_FFN_GELU (a rotary or gated description is
+ * refused and a loaded reranker stays as it is); any precision; type_vocab >= 1; H need not equal the engine's dim. An XLM-R
  * cross-encoder (XLMRobertaForSequenceClassification: out_proj(tanh(dense(h_<s>)))) loads the same way, its
  * classifier.dense / classifier.out_proj as the four head tensors, type_vocab 1, and its position table from row
  * pad_token_id + 1 on (max_pos = max_position_embeddings - pad_token_id - 1). The model gets

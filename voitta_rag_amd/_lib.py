@@ -58,12 +58,20 @@ class VrBertDesc(C.Structure):
         ("normalize", C.c_int32),
         ("eps", C.c_float),
         ("precision", C.c_int32),
+        ("position", C.c_int32),
+        ("rope_theta", C.c_float),
+        ("ffn", C.c_int32),
     ]
 
 
 VR_PRECISION_F32 = 0
 VR_PRECISION_F16X3 = 1
 VR_PRECISION_F16 = 2
+VR_POS_LEARNED = 0
+VR_POS_ROTARY = 1
+VR_FFN_GELU = 0
+VR_FFN_SWIGLU = 1
+VR_FFN_GEGLU = 2
 VR_POOL_MEAN = 0
 VR_POOL_CLS = 1
 VR_MEM_HOST = 0

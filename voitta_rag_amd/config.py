@@ -33,6 +33,10 @@ class Settings:
         mmr = os.getenv("VOITTA_MMR_DIVERSITY", "")
         self.mmr_diversity: float | None = float(mmr) if mmr.strip() else None
         self.mmr_candidates: int = int(os.getenv("VOITTA_MMR_CANDIDATES", "50"))
+        # task prefixes (opt-in, empty = none) put in front of every passage / query text before tokenisation, for models
+        # that expect them and that the reference's e5 rule does not know (nomic: "search_document: " / "search_query: ")
+        self.embed_passage_prefix: str = os.getenv("VOITTA_EMBED_PASSAGE_PREFIX", "")
+        self.embed_query_prefix: str = os.getenv("VOITTA_EMBED_QUERY_PREFIX", "")
 
 
 @lru_cache

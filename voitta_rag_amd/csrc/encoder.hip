@@ -16,6 +16,8 @@
 //   layernorm_kernel  LayerNorm over H                               HBM bound
 //   pool_kernel       mean / CLS pooling + L2 normalise              HBM bound
 //   rerank_head_kernel cross-encoder head on the pooled [CLS] rows   one f32 logit per pair (encoder_rerank)
+//   rope_kernel       rotary positions, in place on Q and K            HBM bound (VR_POS_ROTARY models only)
+//   glu_kernel        act(gate) * up of a gated FFN                    HBM bound (VR_FFN_SWIGLU / VR_FFN_GEGLU only)
 // Algorithmic FLOP per token = L * (24 H^2 + 4 S H), of which the GEMMs are
 // 24 H^2 L: the dominant kernel of the indexing path.
 
@@ -45,6 +47,16 @@ struct LayerWeights {
   // gain in front of them, their column sums and the bias with the LayerNorm shift pushed through
   SplitWeight s_qkv_f{}, s_1_f{};  // s_qkv_f: layers >= 1 only (layer 0 reads the embedding LayerNorm's output)
   float *cs_qkv = nullptr, *c_qkv = nullptr, *cs_1 = nullptr, *c_1 = nullptr;
+  // f16 mode, fused rotary / gate epilogues of the skinny kernels (EPI_ROPE_F16, EPI_*GLU_F16): the same matrices with
+  // their output rows re-ordered so that the two values an epilogue combines are neighbours. s_qkv_p: inside every
+  // head of the query and key thirds, row 2i = old row i and row 2i + 1 = old row i + d_h/2 (q.k is invariant under a
+  // common permutation inside a head; the value third is untouched). s_1_p: row 2j = gate_j, row 2j + 1 = up_j.
+  SplitWeight s_qkv_p{}, s_1_p{};
+  float *bqkv_p = nullptr, *b1_p = nullptr;
+  // ... and of EPI_FOLD_*GLU: the interleaved FFN-up matrix scaled by the LayerNorm gain in front of it, its column
+  // sums and folded bias (what s_1_f, cs_1, c_1 are to the stacked matrix)
+  SplitWeight s_1_fp{};
+  float *cs_1_p = nullptr, *c_1_p = nullptr;
 };
 
 struct Encoder {
@@ -58,6 +70,12 @@ struct Encoder {
   float* xs = nullptr;  // f16x3 / f16 mode: the hidden state as GEMM input ((hi, lo) or plain f16 rows)
   float* lnstat = nullptr;  // f16 mode: two arrays of per-row (mean, 1/sigma), see forward_chunk
   float* lnpart = nullptr;  // f16 mode: per (row, 64 columns) partial (sum, sum of squares) of the folded LayerNorms
+  float* glu = nullptr;     // gated FFN: the [T, 2I] pre-activation (gate | up) of glu_kernel, f32 or plain f16 rows
+  // rotary positions: (cos, sin) of position p for the pair q = head * d_h/2 + i of a head-major [H/2] row (the d_h/2
+  // frequencies repeated for every head, so that an epilogue finds its entry from the column alone), max_pos rows
+  float2* rope = nullptr;
+  float* posidx = nullptr;  // rotary: int32 position of every token inside its own sequence (positions_kernel)
+  bool fuse = true;         // rotate / gate inside the skinny epilogues; VR_ENCODE_FUSE=0 at load time: separate passes
   DevArray<int32_t> ids, cu, seg;
   DevArray<float> out;
   // a cross-encoder (the reranker slot): pooler dense [H,H] + bias, classifier [1,H] + bias; the pooled [CLS] rows
@@ -263,19 +281,20 @@ __device__ __forceinline__ void row_layernorm(float2 (&v)[kMaxPairs], int pairs,
 }
 
 // one wave per token: x[t] = LayerNorm(word[id] + pos[p] + type[0]); SEG (a cross-encoder's pairs): type[1] for the
-// positions p >= seg_b[sequence], the segment-B tokens
-template <bool SEG>
-__global__ __launch_bounds__(256) void embed_ln_kernel(const int32_t* __restrict__ ids,
-                                                       const int32_t* __restrict__ cu, int n_seq,
-                                                       int tok_base, int T, int H, int vocab,
-                                                       const float* __restrict__ word,
-                                                       const float* __restrict__ pos,
-                                                       const float* __restrict__ type,
-                                                       const float* __restrict__ g,
-                                                       const float* __restrict__ b, float eps,
-                                                       float* __restrict__ x, half_t* __restrict__ x_hi,
-                                                       half_t* __restrict__ x_lo, float* __restrict__ pre,
-                                                       float2* __restrict__ stat, const int32_t* __restrict__ seg_b) {
+// positions p >= seg_b[sequence], the segment-B tokens. POS = false (a rotary model): word + type only, no table is read.
+// (The body of embed_ln_kernel and embed_ln_rotary_kernel: two kernels, so that the former keeps its signature.)
+template <bool SEG, bool POS>
+__device__ __forceinline__ void embed_ln_body(const int32_t* __restrict__ ids,
+                                              const int32_t* __restrict__ cu, int n_seq,
+                                              int tok_base, int T, int H, int vocab,
+                                              const float* __restrict__ word,
+                                              const float* __restrict__ pos,
+                                              const float* __restrict__ type,
+                                              const float* __restrict__ g,
+                                              const float* __restrict__ b, float eps,
+                                              float* __restrict__ x, half_t* __restrict__ x_hi,
+                                              half_t* __restrict__ x_lo, float* __restrict__ pre,
+                                              float2* __restrict__ stat, const int32_t* __restrict__ seg_b) {
   const int lane = threadIdx.x & 63;
   const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (t >= T) return;
@@ -297,15 +316,50 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const int32_t* __restrict
     if (i < pairs) {
       int e = (i * 64 + lane) * 2;
       float2 w = *reinterpret_cast<const float2*>(word + static_cast<int64_t>(id) * H + e);
-      float2 pp = *reinterpret_cast<const float2*>(pos + static_cast<int64_t>(p) * H + e);
       float2 tt = *reinterpret_cast<const float2*>(type + e);
-      v[i].x = w.x + pp.x + tt.x;
-      v[i].y = w.y + pp.y + tt.y;
+      if constexpr (POS) {
+        float2 pp = *reinterpret_cast<const float2*>(pos + static_cast<int64_t>(p) * H + e);
+        v[i].x = w.x + pp.x + tt.x;
+        v[i].y = w.y + pp.y + tt.y;
+      } else {
+        v[i].x = w.x + tt.x;
+        v[i].y = w.y + tt.y;
+      }
       if (pre) *reinterpret_cast<float2*>(pre + static_cast<int64_t>(t) * H + e) = v[i];  // the pre-LN row
     }
   const int64_t o = static_cast<int64_t>(t) * H;
   row_layernorm(v, pairs, H, g, b, eps, lane, x ? x + o : nullptr, x_hi ? x_hi + (x_lo ? 2 : 1) * o : nullptr,
                 x_lo ? x_lo + 2 * o : nullptr, stat ? stat + t : nullptr);
+}
+
+template <bool SEG>
+__global__ __launch_bounds__(256) void embed_ln_kernel(const int32_t* __restrict__ ids,
+                                                       const int32_t* __restrict__ cu, int n_seq,
+                                                       int tok_base, int T, int H, int vocab,
+                                                       const float* __restrict__ word,
+                                                       const float* __restrict__ pos,
+                                                       const float* __restrict__ type,
+                                                       const float* __restrict__ g,
+                                                       const float* __restrict__ b, float eps,
+                                                       float* __restrict__ x, half_t* __restrict__ x_hi,
+                                                       half_t* __restrict__ x_lo, float* __restrict__ pre,
+                                                       float2* __restrict__ stat, const int32_t* __restrict__ seg_b) {
+  embed_ln_body<SEG, true>(ids, cu, n_seq, tok_base, T, H, vocab, word, pos, type, g, b, eps, x, x_hi, x_lo, pre, stat, seg_b);
+}
+
+// a rotary model: no position table (and no segment B: cross-encoders are not rotary)
+__global__ __launch_bounds__(256) void embed_ln_rotary_kernel(const int32_t* __restrict__ ids,
+                                                              const int32_t* __restrict__ cu, int n_seq,
+                                                              int tok_base, int T, int H, int vocab,
+                                                              const float* __restrict__ word,
+                                                              const float* __restrict__ type,
+                                                              const float* __restrict__ g,
+                                                              const float* __restrict__ b, float eps,
+                                                              float* __restrict__ x, half_t* __restrict__ x_hi,
+                                                              half_t* __restrict__ x_lo, float* __restrict__ pre,
+                                                              float2* __restrict__ stat) {
+  embed_ln_body<false, false>(ids, cu, n_seq, tok_base, T, H, vocab, word, nullptr, type, g, b, eps, x, x_hi, x_lo, pre, stat,
+                              nullptr);
 }
 
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ in, int T, int H,
@@ -511,6 +565,146 @@ __global__ __launch_bounds__(256) void gather_first_rows_ln16_kernel(const half_
         ln_apply(static_cast<float>(pre[static_cast<int64_t>(t) * H + c]), st.x, st.y, g[c], b[c]);
 }
 
+// ---- rotary positions and the gated FFN, as passes of their own ------------------------------------
+
+// eight consecutive values of a row (16-byte aligned: every caller's column is a multiple of 8) as floats, and back
+__device__ __forceinline__ void load8(const float* p, float (&v)[8]) {
+  const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
+  v[0] = a.x, v[1] = a.y, v[2] = a.z, v[3] = a.w, v[4] = b.x, v[5] = b.y, v[6] = b.z, v[7] = b.w;
+}
+__device__ __forceinline__ void load8(const half_t* p, float (&v)[8]) {
+  const f16x8 h = *reinterpret_cast<const f16x8*>(p);
+#pragma unroll
+  for (int k = 0; k < 8; ++k) v[k] = static_cast<float>(h[k]);
+}
+__device__ __forceinline__ void store8(float* p, const float (&v)[8]) {
+  *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+  *reinterpret_cast<float4*>(p + 4) = make_float4(v[4], v[5], v[6], v[7]);
+}
+__device__ __forceinline__ void store8(half_t* p, const float (&v)[8]) {
+  f16x8 h;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) h[k] = static_cast<half_t>(fminf(fmaxf(v[k], -65504.0f), 65504.0f));
+  *reinterpret_cast<f16x8*>(p) = h;
+}
+
+// One wave per token, in place on the Q and K thirds of its [3H] row (T = float: the f32 / f16x3 modes, half_t: the
+// f16 mode, whose rotated values are rounded to f16 a second time). Feature j < d_h/2 of a head pairs with j + d_h/2:
+//   x[j] <- x[j] cos - x[j + d_h/2] sin,  x[j + d_h/2] <- x[j + d_h/2] cos + x[j] sin   (HF rotate_half)
+// with (cos, sin) of (the token's position inside its own sequence, frequency j). The arithmetic is f32.
+template <typename T>
+__global__ __launch_bounds__(256) void rope_kernel(T* __restrict__ qkv, const int32_t* __restrict__ pos, int Tn, int H,
+                                                   int dh, const float2* __restrict__ table) {
+  const int lane = threadIdx.x & 63;
+  const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (t >= Tn) return;
+  const int half = dh >> 1;          // 16 or 32
+  const int groups = half >> 3;      // groups of 8 pairs per head
+  const int per_third = (H / dh) * groups;
+  T* row = qkv + static_cast<int64_t>(t) * 3 * H;
+  const float2* cs_row = table + static_cast<int64_t>(pos[t]) * (H >> 1);  // (the first head's entries serve every head)
+  for (int c = lane; c < 2 * per_third; c += 64) {  // a lane takes 8 pairs of one head of the query or the key
+    const int third = c >= per_third ? 1 : 0;
+    const int w = c - third * per_third;
+    const int head = w / groups, i8 = (w - head * groups) << 3;
+    T* at = row + third * H + head * dh + i8;
+    float a[8], b[8], cs0[8], cs1[8];  // cs0 / cs1: (cos, sin) of pairs 0..3 / 4..7
+    load8(at, a);
+    load8(at + half, b);
+    load8(reinterpret_cast<const float*>(cs_row + i8), cs0);
+    load8(reinterpret_cast<const float*>(cs_row + i8 + 4), cs1);
+    float ra[8], rb[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const float co = k < 4 ? cs0[2 * k] : cs1[2 * k - 8], si = k < 4 ? cs0[2 * k + 1] : cs1[2 * k - 7];
+      ra[k] = a[k] * co - b[k] * si;
+      rb[k] = b[k] * co + a[k] * si;
+    }
+    store8(at, ra);
+    store8(at + half, rb);
+  }
+}
+
+// pos[t] = index of token t inside its own sequence (binary search of the offsets), once per forward pass: the
+// rotation of every layer reads it. Lengths are checked against max_pos before any launch, so pos < max_pos.
+__global__ __launch_bounds__(256) void positions_kernel(const int32_t* __restrict__ cu, int n_seq, int tok_base, int Tn,
+                                                        int32_t* __restrict__ pos) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= Tn) return;
+  int lo = 0, hi = n_seq;
+  const int tg = t + tok_base;
+  while (hi - lo > 1) {
+    int mid = (lo + hi) >> 1;
+    if (cu[mid] <= tg) lo = mid; else hi = mid;
+  }
+  pos[t] = tg - cu[lo];
+}
+
+// dst row r = src row map(r), rows of K floats (K = 1: a bias). mode 0 (query / key / value stacked, H rows each):
+// inside every head of the first two thirds, row 2i <- row i, row 2i + 1 <- row i + d_h/2; mode 1 ([gate; up], n rows
+// each): row 2j <- gate row j, row 2j + 1 <- up row j.
+__global__ void reorder_rows_kernel(const float* __restrict__ src, int64_t total, int K, int mode, int n, int dh,
+                                    float* __restrict__ dst) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const int r = static_cast<int>(i / K), k = static_cast<int>(i - static_cast<int64_t>(r) * K);
+  int from = r;
+  if (mode == 0) {
+    if (r < 2 * n) {
+      const int local = r % dh, base = r - local;
+      from = base + (local >> 1) + ((local & 1) ? (dh >> 1) : 0);
+    }
+  } else {
+    from = (r >> 1) + ((r & 1) ? n : 0);
+  }
+  dst[i] = src[static_cast<int64_t>(from) * K + k];
+}
+
+// SiLU as x / (1 + 2^(-x log2 e)) on the hardware exp2 and reciprocal (1 ulp each: f32-class, as gelu_fast); the
+// exact-erf GELU through erff where the result stays f32, through gelu_fast (|erf error| <= 1.5e-7) where it is
+// rounded to f16 or split into (hi, lo) — the choices the plain FFN's epilogues make
+template <bool F32OUT>
+__device__ __forceinline__ float glu_act(float g, int ffn) {
+  if (ffn == VR_FFN_SWIGLU) return g * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * g));
+  if (F32OUT) return 0.5f * g * (1.0f + erff(g * 0.70710678118654752440f));
+  return gelu_fast(g);
+}
+
+// out[t][j] = act(pre[t][j]) * pre[t][I + j] for 8 consecutive j per thread. TIN: the pre-activation's type.
+// OUT 0: f32 rows; 1: interleaved (hi, lo) f16 rows (split_at); 2: plain f16 rows.
+template <typename TIN, int OUT>
+__global__ __launch_bounds__(256) void glu_kernel(const TIN* __restrict__ pre, int64_t n8, int I, int ffn,
+                                                  float* __restrict__ out, half_t* __restrict__ out_h) {
+  const int64_t i8 = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i8 >= n8) return;
+  const int per_row = I >> 3;
+  const int64_t t = i8 / per_row;
+  const int j = static_cast<int>(i8 - t * per_row) << 3;
+  const TIN* gp = pre + t * 2 * I + j;
+  float g[8], u[8], v[8];
+  load8(gp, g);
+  load8(gp + I, u);
+#pragma unroll
+  for (int k = 0; k < 8; ++k) v[k] = glu_act<OUT == 0>(g[k], ffn) * u[k];
+  if constexpr (OUT == 0) {
+    store8(out + t * I + j, v);
+  } else if constexpr (OUT == 2) {
+    store8(out_h + t * I + j, v);
+  } else {
+    f16x8 h, l;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      half_t hk, lk;
+      split_f16(v[k], hk, lk);
+      h[k] = hk;
+      l[k] = lk;
+    }
+    half_t* o = out_h + t * 2 * I + split_at(j);
+    *reinterpret_cast<f16x8*>(o) = h;
+    *reinterpret_cast<f16x8*>(o + 8) = l;
+  }
+}
+
 // ---- GEMM: C[M,N] = A[M,K] W[N,K]^T + bias (+ GELU | + R) ---------------------------------------
 
 constexpr int BM = 128, BN = 128, BK = 32;
@@ -531,7 +725,15 @@ enum { EPI_BIAS = 0, EPI_BIAS_GELU = 1, EPI_BIAS_RESIDUAL = 2, EPI_BIAS_F16 = 3,
        // rounding). R32_O16: residual rows still f32 (layer 0: the embedding sum), f16 out; R16_O16: f16 in and
        // out, IN PLACE (every element is read and written by the same lane); R16_O32: f16 in, f32 + f16 out
        // (the last layer of a mean-pooled model: the final LayerNorm and the pooling read f32 rows).
-       EPI_RLS_R32_O16 = 8, EPI_RLS_R16_O16 = 9, EPI_RLS_R16_O32 = 10 };
+       EPI_RLS_R32_O16 = 8, EPI_RLS_R16_O16 = 9, EPI_RLS_R16_O32 = 10,
+       // the skinny kernels only (at most 256 rows; skinny_apply), over the re-ordered matrices of LayerWeights:
+       // ROPE_F16: bias, then the (x, y) column pairs of the query and key thirds rotated by the row's position
+       // (ln_stat = the cos/sin table, ln_g = the int32 positions), f16 out; *GLU_F16: bias, act(gate) * up of the
+       // (gate, up) column pairs, N/2 f16 columns out
+       EPI_ROPE_F16 = 11, EPI_SWIGLU_F16 = 12, EPI_GEGLU_F16 = 13,
+       // the direct_epilogue kernels (mid, ping-pong) on the large-batch path: FOLD_F16's folded LayerNorm over the
+       // gain-scaled INTERLEAVED matrix, then act(gate) * up of the lane's four (gate, up) column pairs, N/2 f16 columns out
+       EPI_FOLD_SWIGLU = 14, EPI_FOLD_GEGLU = 15 };
 
 // Linear tile id -> (row panel, column panel), row panels taken kGroupM at a time with the column
 // index slow inside a group. The ~32 blocks an XCD runs together then cover ~8 row panels x ~4
@@ -1288,7 +1490,8 @@ __device__ __forceinline__ void direct_epilogue(f32x4 (&acc)[8][4], int row0, in
       if (grow2 < M && c2 < N) out_store(reinterpret_cast<f16x8*>(Ch + static_cast<int64_t>(grow2) * N + c2), xh);
     }
   };
-  constexpr bool kFold = EPI == EPI_FOLD_F16 || EPI == EPI_FOLD_GELU;
+  constexpr bool kGlu = EPI == EPI_FOLD_SWIGLU || EPI == EPI_FOLD_GEGLU;
+  constexpr bool kFold = EPI == EPI_FOLD_F16 || EPI == EPI_FOLD_GELU || kGlu;
   constexpr bool kStats = EPI == EPI_BIAS_RESIDUAL_LN_STATS || EPI == EPI_RLS_R32_O16 || EPI == EPI_RLS_R16_O16 ||
                           EPI == EPI_RLS_R16_O32;
   constexpr bool kR16 = EPI == EPI_RLS_R16_O16 || EPI == EPI_RLS_R16_O32;   // residual rows are f16
@@ -1308,7 +1511,7 @@ __device__ __forceinline__ void direct_epilogue(f32x4 (&acc)[8][4], int row0, in
   // trow0 / tcol0 = this wave's first row / column inside the tile
   const bool in_lds = FULL && tile_const != nullptr;
   const float2* lds_stat = reinterpret_cast<const float2*>(tile_const + 768) + trow0;
-  constexpr bool kStatUpfront = (EPI == EPI_FOLD_F16 || EPI == EPI_FOLD_GELU);
+  constexpr bool kStatUpfront = kFold;
   float2 st8[kStatUpfront ? 8 : 1] = {};
   if (kStatUpfront && !in_lds) {
 #pragma unroll
@@ -1420,6 +1623,23 @@ __device__ __forceinline__ void direct_epilogue(f32x4 (&acc)[8][4], int row0, in
         for (int q = 0; q < 2; ++q)
           v[q][0] = g[2 * q].x, v[q][1] = g[2 * q].y, v[q][2] = g[2 * q + 1].x, v[q][3] = g[2 * q + 1].y;
       }
+      if (kGlu && !VR_DIAG(64)) {
+        // the lane's eight columns are four (gate, up) pairs of the interleaved matrix: four f16 outputs at column c0 / 2
+        // of a row of N / 2, one 8-byte store (the four lanes of a token write 32 contiguous bytes)
+        constexpr int kFfn = EPI == EPI_FOLD_SWIGLU ? VR_FFN_SWIGLU : VR_FFN_GEGLU;
+        half_t h4[4];
+#pragma unroll
+        for (int q = 0; q < 2; ++q)
+#pragma unroll
+          for (int r = 0; r < 2; ++r)
+            h4[2 * q + r] = static_cast<half_t>(fminf(fmaxf(glu_act<false>(v[q][2 * r], kFfn) * v[q][2 * r + 1], -65504.0f), 65504.0f));
+        const int n2 = N >> 1;
+        if (FULL)
+          *reinterpret_cast<uint2*>((Ch + (static_cast<int64_t>(row0 + 16 * pc) * n2 + ((col0 + 32 * p2) >> 1))) +
+                                    static_cast<uint32_t>(tok * n2 + 4 * fg)) = *reinterpret_cast<const uint2*>(h4);
+        else if (ok)
+          *reinterpret_cast<uint2*>(Ch + static_cast<int64_t>(grow) * n2 + (c0 >> 1)) = *reinterpret_cast<const uint2*>(h4);
+      }
       if (kHalfOut || kStats) {  // f16 row: 8 consecutive features, one 16-byte store
         f16x8 h;
 #pragma unroll
@@ -1442,7 +1662,8 @@ __device__ __forceinline__ void direct_epilogue(f32x4 (&acc)[8][4], int row0, in
         else if (ok)
           out_store(reinterpret_cast<f16x8*>(Ch + static_cast<int64_t>(grow) * N + c0), h);
       }
-      if (!kHalfOut && FULL) {  // f32 row
+      if (kGlu) {
+      } else if (!kHalfOut && FULL) {  // f32 row
         *reinterpret_cast<float4*>(upiece(C, pc, col0 + 32 * p2) + loff) = make_float4(v[0][0], v[0][1], v[0][2], v[0][3]);
         *reinterpret_cast<float4*>(upiece(C, pc, col0 + 32 * p2 + 4) + loff) = make_float4(v[1][0], v[1][1], v[1][2], v[1][3]);
       } else if (!kHalfOut && ok) {
@@ -1807,10 +2028,12 @@ __global__ __launch_bounds__(512) void gemm_f16_pp_kernel(
   // the tile's epilogue constants (direct_epilogue: tile_const), fetched by waves 0-4 at the start of the tile's K loop —
   // one direct-to-LDS load each — so that the epilogue starts on LDS reads instead of three rounds of global-load latency
   half_t* tile_const_h = lds + 2 * kStageHalfs + 8 * kWaveStatHalfs;
-  constexpr bool kUsesGain = EPI == EPI_FOLD_F16 || EPI == EPI_FOLD_GELU || EPI == EPI_BIAS_RESIDUAL_LN ||
+  constexpr bool kUsesGain = EPI == EPI_FOLD_F16 || EPI == EPI_FOLD_GELU || EPI == EPI_FOLD_SWIGLU || EPI == EPI_FOLD_GEGLU ||
+                             EPI == EPI_BIAS_RESIDUAL_LN ||
                              EPI == EPI_BIAS_RESIDUAL_LN_STATS || EPI == EPI_RLS_R32_O16 || EPI == EPI_RLS_R16_O16 ||
                              EPI == EPI_RLS_R16_O32;
-  constexpr bool kUsesShift = kUsesGain && EPI != EPI_FOLD_F16 && EPI != EPI_FOLD_GELU;
+  constexpr bool kUsesShift = kUsesGain && EPI != EPI_FOLD_F16 && EPI != EPI_FOLD_GELU && EPI != EPI_FOLD_SWIGLU &&
+                              EPI != EPI_FOLD_GEGLU;
   // (the branch-free form of the epilogues that also read residual rows needs ~30 registers more than this kernel
   // has left beside its staging state; those keep the predicated form and their global loads)
   constexpr bool kBranchFree = EPI != EPI_BIAS_RESIDUAL_LN && EPI != EPI_BIAS_RESIDUAL_LN_STATS && EPI != EPI_RLS_R32_O16 &&
@@ -2343,7 +2566,28 @@ __device__ __forceinline__ void skinny_apply(float4 v, int m, int n, int N, floa
     const f32x2 g01 = gelu_poly2(f32x2{v.x, v.y}), g23 = gelu_poly2(f32x2{v.z, v.w});  // f16 mode only
     v = make_float4(g01.x, g01.y, g23.x, g23.y);
   }
-  if (EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_F16) {
+  if (EPI == EPI_SWIGLU_F16 || EPI == EPI_GEGLU_F16) {  // columns n .. n + 3 = gate_j, up_j, gate_j+1, up_j+1, j = n / 2
+    constexpr int kFfn = EPI == EPI_SWIGLU_F16 ? VR_FFN_SWIGLU : VR_FFN_GEGLU;
+    const float o0 = glu_act<false>(v.x, kFfn) * v.y, o1 = glu_act<false>(v.z, kFfn) * v.w;
+    half_t h[2] = {static_cast<half_t>(fminf(fmaxf(o0, -65504.0f), 65504.0f)),
+                   static_cast<half_t>(fminf(fmaxf(o1, -65504.0f), 65504.0f))};
+    *reinterpret_cast<uint32_t*>(Ch + static_cast<int64_t>(m) * (N >> 1) + (n >> 1)) = *reinterpret_cast<const uint32_t*>(h);
+    return;
+  }
+  if (EPI == EPI_ROPE_F16) {  // N = 3H; (v.x, v.y) and (v.z, v.w) are rotation partners in the query and key thirds
+    const int H = N / 3;
+    if (n < 2 * H) {
+      const int c = n >= H ? n - H : n;
+      const int p = reinterpret_cast<const int32_t*>(ln_g)[m];
+      const float4 cs = *reinterpret_cast<const float4*>(ln_stat + static_cast<int64_t>(p) * (H >> 1) + (c >> 1));
+      const float x0 = v.x, y0 = v.y, x1 = v.z, y1 = v.w;
+      v.x = x0 * cs.x - y0 * cs.y;
+      v.y = y0 * cs.x + x0 * cs.y;
+      v.z = x1 * cs.z - y1 * cs.w;
+      v.w = y1 * cs.z + x1 * cs.w;
+    }
+  }
+  if (EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_F16 || EPI == EPI_ROPE_F16) {
     half_t h[4] = {static_cast<half_t>(fminf(fmaxf(v.x, -65504.0f), 65504.0f)),
                    static_cast<half_t>(fminf(fmaxf(v.y, -65504.0f), 65504.0f)),
                    static_cast<half_t>(fminf(fmaxf(v.z, -65504.0f), 65504.0f)),
@@ -2568,6 +2812,8 @@ static void launch_d2(int epi, hipStream_t s, const half_t* Ah, const half_t* Wh
     case EPI_BIAS_RESIDUAL_LN: VR_LAUNCH_D2(EPI_BIAS_RESIDUAL_LN); break;
     case EPI_FOLD_F16: VR_LAUNCH_D2(EPI_FOLD_F16); break;
     case EPI_FOLD_GELU: VR_LAUNCH_D2(EPI_FOLD_GELU); break;
+    case EPI_FOLD_SWIGLU: VR_LAUNCH_D2(EPI_FOLD_SWIGLU); break;
+    case EPI_FOLD_GEGLU: VR_LAUNCH_D2(EPI_FOLD_GEGLU); break;
     case EPI_BIAS_RESIDUAL_LN_STATS: VR_LAUNCH_D2(EPI_BIAS_RESIDUAL_LN_STATS); break;
     case EPI_RLS_R32_O16: VR_LAUNCH_D2(EPI_RLS_R32_O16); break;
     case EPI_RLS_R16_O16: VR_LAUNCH_D2(EPI_RLS_R16_O16); break;
@@ -2605,6 +2851,8 @@ static void launch_pp(int epi, int grid, hipStream_t s, const half_t* Ah, const 
     case EPI_BIAS_RESIDUAL_LN: VR_LAUNCH_PP(EPI_BIAS_RESIDUAL_LN); break;
     case EPI_FOLD_F16: VR_LAUNCH_PP(EPI_FOLD_F16); break;
     case EPI_FOLD_GELU: VR_LAUNCH_PP(EPI_FOLD_GELU); break;
+    case EPI_FOLD_SWIGLU: VR_LAUNCH_PP(EPI_FOLD_SWIGLU); break;
+    case EPI_FOLD_GEGLU: VR_LAUNCH_PP(EPI_FOLD_GEGLU); break;
     case EPI_BIAS_RESIDUAL_LN_STATS: VR_LAUNCH_PP(EPI_BIAS_RESIDUAL_LN_STATS); break;
     case EPI_RLS_R32_O16: VR_LAUNCH_PP(EPI_RLS_R32_O16); break;
     case EPI_RLS_R16_O16: VR_LAUNCH_PP(EPI_RLS_R16_O16); break;
@@ -2637,11 +2885,13 @@ static void launch_pp(int epi, int grid, hipStream_t s, const half_t* Ah, const 
 // stores the statistics, which the residual epilogue of the NEXT projection needs (ln_apply re-derives
 // the LayerNorm output from the pre-LN row). K = hidden size: each wave holds STEPS * 8 values per row.
 // Two launches fewer per layer for a single query (7 -> 5): its forward pass is launch latency, not work.
+// (gemm_f16_skinny_ln_body: shared by the kernel below and its rotary twin, which has two arguments more)
 template <int EPI, int STEPS, int NW>
-__global__ __launch_bounds__(NW * 64) void gemm_f16_skinny_ln_kernel(
+__device__ __forceinline__ void gemm_f16_skinny_ln_body(
     const float* __restrict__ pre, const float* __restrict__ ln_g, const float* __restrict__ ln_b, float eps,
     float2* __restrict__ stat_out, const half_t* __restrict__ W, int M, int N, int K, float unscale,
-    const float* __restrict__ bias, half_t* __restrict__ Ch) {
+    const float* __restrict__ bias, half_t* __restrict__ Ch, const float2* __restrict__ rope_tab,
+    const int32_t* __restrict__ rope_pos) {
   __shared__ float red[NW][16][17];  // [wave][output column][activation row (+1 pad)]
   __shared__ float part[2][NW][16];  // row sums per wave: [pass][wave][row]
   const int lane = threadIdx.x & 63;
@@ -2719,8 +2969,26 @@ __global__ __launch_bounds__(NW * 64) void gemm_f16_skinny_ln_kernel(
     for (int w = 1; w < NW; ++w) t += red[w][n4 + j][m];  // fixed order
     v[j] = t;
   }
-  skinny_apply<EPI>(make_float4(v[0], v[1], v[2], v[3]), m, n0 + n4, N, unscale, bias, nullptr, nullptr, nullptr, nullptr,
-                    nullptr, Ch);
+  skinny_apply<EPI>(make_float4(v[0], v[1], v[2], v[3]), m, n0 + n4, N, unscale, bias, nullptr, rope_tab,
+                    reinterpret_cast<const float*>(rope_pos), nullptr, nullptr, Ch);
+}
+
+template <int EPI, int STEPS, int NW>
+__global__ __launch_bounds__(NW * 64) void gemm_f16_skinny_ln_kernel(
+    const float* __restrict__ pre, const float* __restrict__ ln_g, const float* __restrict__ ln_b, float eps,
+    float2* __restrict__ stat_out, const half_t* __restrict__ W, int M, int N, int K, float unscale,
+    const float* __restrict__ bias, half_t* __restrict__ Ch) {
+  gemm_f16_skinny_ln_body<EPI, STEPS, NW>(pre, ln_g, ln_b, eps, stat_out, W, M, N, K, unscale, bias, Ch, nullptr, nullptr);
+}
+
+// EPI_ROPE_F16: the Q/K/V projection of a rotary model, with the cos/sin table and the rows' positions
+template <int STEPS, int NW>
+__global__ __launch_bounds__(NW * 64) void gemm_f16_skinny_ln_rope_kernel(
+    const float* __restrict__ pre, const float* __restrict__ ln_g, const float* __restrict__ ln_b, float eps,
+    float2* __restrict__ stat_out, const half_t* __restrict__ W, int M, int N, int K, float unscale,
+    const float* __restrict__ bias, half_t* __restrict__ Ch, const float2* __restrict__ rope_tab,
+    const int32_t* __restrict__ rope_pos) {
+  gemm_f16_skinny_ln_body<EPI_ROPE_F16, STEPS, NW>(pre, ln_g, ln_b, eps, stat_out, W, M, N, K, unscale, bias, Ch, rope_tab, rope_pos);
 }
 
 // K = hidden size H: 8 waves x 3 steps (768), 8 x 4 (1024), 4 x 3 (384); anything else keeps the LayerNorm launch
@@ -2728,22 +2996,35 @@ static bool skinny_ln_supported(int M, int N, int K) { return M <= 16 && N % 16 
 
 static int launch_skinny_ln(vr_engine* e, int epi, const float* pre, const float* ln_g, const float* ln_b, float eps,
                             float2* stat_out, const half_t* W, float unscale, const float* bias, half_t* Ch, int M,
-                            int N, int K) {
+                            int N, int K, const float2* rope_tab = nullptr, const int32_t* rope_pos = nullptr) {
   hipStream_t s = e->stream;
   prof_begin(e, VR_PROF_GEMM, 2.0 * M * static_cast<double>(N) * K);
   const dim3 grid(static_cast<unsigned>(N / 16));
 #define VR_SKINNY_LN(E, ST, NWV)                                                                                   \
   hipLaunchKernelGGL((gemm_f16_skinny_ln_kernel<E, ST, NWV>), grid, dim3(NWV * 64), 0, s, pre, ln_g, ln_b, eps,    \
                      stat_out, W, M, N, K, unscale, bias, Ch)
-  if (epi == EPI_BIAS_GELU) {
-    if (K == 768) VR_SKINNY_LN(EPI_BIAS_GELU, 3, 8);
-    else if (K == 1024) VR_SKINNY_LN(EPI_BIAS_GELU, 4, 8);
-    else VR_SKINNY_LN(EPI_BIAS_GELU, 3, 4);
-  } else {
-    if (K == 768) VR_SKINNY_LN(EPI_BIAS_F16, 3, 8);
-    else if (K == 1024) VR_SKINNY_LN(EPI_BIAS_F16, 4, 8);
-    else VR_SKINNY_LN(EPI_BIAS_F16, 3, 4);
+#define VR_SKINNY_LN_ROPE(ST, NWV)                                                                                 \
+  hipLaunchKernelGGL((gemm_f16_skinny_ln_rope_kernel<ST, NWV>), grid, dim3(NWV * 64), 0, s, pre, ln_g, ln_b, eps,  \
+                     stat_out, W, M, N, K, unscale, bias, Ch, rope_tab, rope_pos)
+#define VR_SKINNY_LN_K(E)                      \
+  do {                                         \
+    if (K == 768) VR_SKINNY_LN(E, 3, 8);       \
+    else if (K == 1024) VR_SKINNY_LN(E, 4, 8); \
+    else VR_SKINNY_LN(E, 3, 4);                \
+  } while (0)
+  switch (epi) {
+    case EPI_BIAS_GELU: VR_SKINNY_LN_K(EPI_BIAS_GELU); break;
+    case EPI_ROPE_F16:
+      if (K == 768) VR_SKINNY_LN_ROPE(3, 8);
+      else if (K == 1024) VR_SKINNY_LN_ROPE(4, 8);
+      else VR_SKINNY_LN_ROPE(3, 4);
+      break;
+    case EPI_SWIGLU_F16: VR_SKINNY_LN_K(EPI_SWIGLU_F16); break;
+    case EPI_GEGLU_F16: VR_SKINNY_LN_K(EPI_GEGLU_F16); break;
+    default: VR_SKINNY_LN_K(EPI_BIAS_F16); break;
   }
+#undef VR_SKINNY_LN_K
+#undef VR_SKINNY_LN_ROPE
 #undef VR_SKINNY_LN
   prof_end(e);
   VR_HIP(hipGetLastError());
@@ -2753,6 +3034,14 @@ static int launch_skinny_ln(vr_engine* e, int epi, const float* pre, const float
 // passes = 3: operands are interleaved (hi, lo) rows (Al = Ah + 8, Wl = Wh + 8); passes = 1: plain f16
 // rows, Al / Wl / Cl unused.
 // enc: the model whose forward pass this is (its split-K scratch and graph cache)
+// whether launch_gemm_f16x3 sends an f16-mode product of this shape to one of the skinny kernels (its two tests below)
+static bool skinny_routed(int M, int N, int K) {
+  const int sk_waves = K % 256 == 0 ? 8 : K % 128 == 0 ? 4 : 0;
+  const int sk_steps = sk_waves ? K / (32 * sk_waves) : 0;
+  const bool one_launch = sk_steps > 0 && (sk_steps % 6 == 0 || sk_steps % 4 == 0 || sk_steps % 3 == 0) && N % 16 == 0;
+  return M <= 4 * kSkinnyM && (one_launch || (skinny_slice(K) > 0 && N % 64 == 0));
+}
+
 static int launch_gemm_f16x3(vr_engine* e, Encoder* enc, int epi, const half_t* Ah, const half_t* Al, const half_t* Wh,
                              const half_t* Wl, float unscale, const float* bias, const float* R, float* C,
                              half_t* Ch, half_t* Cl, int M, int N, int K, int passes = 3,
@@ -2788,6 +3077,9 @@ static int launch_gemm_f16x3(vr_engine* e, Encoder* enc, int epi, const half_t* 
       case EPI_BIAS: VR_SKINNY1(EPI_BIAS); break;
       case EPI_BIAS_GELU: VR_SKINNY1(EPI_BIAS_GELU); break;
       case EPI_BIAS_F16: VR_SKINNY1(EPI_BIAS_F16); break;
+      case EPI_ROPE_F16: VR_SKINNY1(EPI_ROPE_F16); break;
+      case EPI_SWIGLU_F16: VR_SKINNY1(EPI_SWIGLU_F16); break;
+      case EPI_GEGLU_F16: VR_SKINNY1(EPI_GEGLU_F16); break;
       case EPI_BIAS_RESIDUAL_LN: VR_SKINNY1(EPI_BIAS_RESIDUAL_LN); break;
       default: VR_SKINNY1(EPI_BIAS_RESIDUAL); break;
     }
@@ -2814,6 +3106,9 @@ static int launch_gemm_f16x3(vr_engine* e, Encoder* enc, int epi, const half_t* 
       case EPI_BIAS: VR_SKINNY_EPI(EPI_BIAS); break;
       case EPI_BIAS_GELU: VR_SKINNY_EPI(EPI_BIAS_GELU); break;
       case EPI_BIAS_F16: VR_SKINNY_EPI(EPI_BIAS_F16); break;
+      case EPI_ROPE_F16: VR_SKINNY_EPI(EPI_ROPE_F16); break;
+      case EPI_SWIGLU_F16: VR_SKINNY_EPI(EPI_SWIGLU_F16); break;
+      case EPI_GEGLU_F16: VR_SKINNY_EPI(EPI_GEGLU_F16); break;
       case EPI_BIAS_RESIDUAL_LN: VR_SKINNY_EPI(EPI_BIAS_RESIDUAL_LN); break;
       default: VR_SKINNY_EPI(EPI_BIAS_RESIDUAL); break;
     }
@@ -2822,6 +3117,8 @@ static int launch_gemm_f16x3(vr_engine* e, Encoder* enc, int epi, const half_t* 
     VR_HIP(hipGetLastError());
     return 0;
   }
+  VR_CHECK(epi < EPI_ROPE_F16 || ((epi == EPI_FOLD_SWIGLU || epi == EPI_FOLD_GEGLU) && passes == 1 && pp_usable(N, K)),
+           "epilogue %d does not exist for the kernel of this product (M=%d N=%d K=%d)", epi, M, N, K);
   if (passes == 1 || (N % GBN == 0 && K % GBK == 0 && M >= GBM && force_tile != 128)) {
     static int n_cu = 0;  // persistent grid: one block per CU (the kernel uses 128 KiB of the CU's LDS)
     if (n_cu == 0) {
@@ -3451,55 +3748,140 @@ int encoder_hidden(vr_engine* e) {
   return enc ? enc->d.hidden : 0;
 }
 
-// a model from its 5 + 16 L tensors (vr_encoder_load's order) into *slot, replacing what is there
-static int build_encoder(vr_engine* e, void** slot, const vr_bert_desc* d, const void* const* t, int n_tensors, int mem) {
-  VR_CHECK(d->struct_size == static_cast<int32_t>(sizeof(vr_bert_desc)), "vr_bert_desc size mismatch");
+// The caller's description, zero-extended: a caller compiled against the header that ended at `precision` passes that
+// shorter struct_size, and gets what it always got (learned positions, the plain GELU FFN).
+static int read_desc(const vr_bert_desc* src, vr_bert_desc* out) {
+  const int32_t short_size = static_cast<int32_t>(offsetof(vr_bert_desc, position));
+  VR_CHECK(src->struct_size == static_cast<int32_t>(sizeof(vr_bert_desc)) || src->struct_size == short_size,
+           "vr_bert_desc size mismatch");
+  *out = vr_bert_desc{};
+  memcpy(out, src, static_cast<size_t>(src->struct_size));
+  out->struct_size = static_cast<int32_t>(sizeof(vr_bert_desc));
+  return 0;
+}
+
+// device array of n floats from src, or of zeros when src is null (an absent bias)
+static int dev_alloc_copy_or_zero(vr_engine* e, Encoder* enc, const void* src, size_t n_floats, int mem, float** out) {
+  VR_TRY(dev_alloc_copy(e, enc, src, n_floats, mem, out));
+  if (!src) VR_HIP(hipMemsetAsync(*out, 0, n_floats * sizeof(float), e->stream));
+  return 0;
+}
+
+// a model from its 5 + 16 L (gated FFN: 5 + 18 L) tensors (vr_encoder_load's order) into *slot, replacing what is there
+static int build_encoder(vr_engine* e, void** slot, const vr_bert_desc* d_in, const void* const* t, int n_tensors, int mem) {
+  vr_bert_desc desc;
+  VR_TRY(read_desc(d_in, &desc));
+  const vr_bert_desc* d = &desc;
   const int H = d->hidden, I = d->intermediate, L = d->layers;
+  VR_CHECK(d->position == VR_POS_LEARNED || d->position == VR_POS_ROTARY, "unknown position scheme %d", d->position);
+  VR_CHECK(d->ffn == VR_FFN_GELU || d->ffn == VR_FFN_SWIGLU || d->ffn == VR_FFN_GEGLU, "unknown ffn kind %d", d->ffn);
+  const bool rotary = d->position == VR_POS_ROTARY, gated = d->ffn != VR_FFN_GELU;
+  const int per_layer = gated ? 18 : 16;
+  VR_CHECK(!rotary || (std::isfinite(d->rope_theta) && d->rope_theta > 0.0f), "rope_theta %g must be positive",
+           static_cast<double>(d->rope_theta));
+  VR_CHECK(d->max_pos >= 1, "max_pos %d must be positive", d->max_pos);
   VR_CHECK(L >= 1 && H >= 128 && H % 128 == 0 && H <= 1024, "hidden %d must be a multiple of 128 in 128..1024", H);
   VR_CHECK(I % 128 == 0 && I % BK == 0, "intermediate %d must be a multiple of 128", I);
   VR_CHECK(d->heads >= 1 && H % d->heads == 0 && (H / d->heads == 32 || H / d->heads == 64),
            "head size %d unsupported (32 or 64)", d->heads ? H / d->heads : 0);
-  VR_CHECK(n_tensors == 5 + 16 * L, "expected %d tensors, got %d", 5 + 16 * L, n_tensors);
+  VR_CHECK(n_tensors == 5 + per_layer * L, "expected %d tensors, got %d", 5 + per_layer * L, n_tensors);
   VR_CHECK(d->pooling == 0 || d->pooling == 1, "pooling must be 0 (mean) or 1 (cls)");
   VR_CHECK(d->precision == VR_PRECISION_F32 || d->precision == VR_PRECISION_F16X3 || d->precision == VR_PRECISION_F16,
            "unknown precision %d", d->precision);
-  for (int i = 0; i < n_tensors; ++i) VR_CHECK(t[i] != nullptr, "tensor %d is null", i);
+  for (int i = 0; i < n_tensors; ++i) {
+    const int in_layer = i < 5 ? -1 : (i - 5) % per_layer;  // null is allowed for a projection's bias, and for the
+    const bool bias = in_layer == 1 || in_layer == 3 || in_layer == 5 || in_layer == 7 || in_layer == 11 ||  // unused table
+                      in_layer == 13 || in_layer == 17;
+    VR_CHECK(t[i] != nullptr || bias || (i == 1 && rotary), "tensor %d is null", i);
+  }
   free_encoder(slot);
   Encoder* enc = new Encoder();
   *slot = enc;
   enc->d = *d;
+  enc->fuse = !(getenv("VR_ENCODE_FUSE") && atoi(getenv("VR_ENCODE_FUSE")) == 0);
   const size_t HH = static_cast<size_t>(H) * H;
   VR_TRY(dev_alloc_copy(e, enc, t[0], static_cast<size_t>(d->vocab) * H, mem, &enc->word));
-  VR_TRY(dev_alloc_copy(e, enc, t[1], static_cast<size_t>(d->max_pos) * H, mem, &enc->pos));
+  if (!rotary) VR_TRY(dev_alloc_copy(e, enc, t[1], static_cast<size_t>(d->max_pos) * H, mem, &enc->pos));
+  std::vector<float2> rope_host;  // (lives until the synchronisation at the end: it is the source of an async copy)
+  if (rotary) {  // (cos, sin)(p * theta^(-2i/d_h)) in f64, stored as f32
+    const int half = H / d->heads / 2, row = H / 2;  // a row repeats the d_h/2 frequencies for every head
+    rope_host.resize(static_cast<size_t>(d->max_pos) * row);
+    for (int i = 0; i < half; ++i) {
+      const double inv_freq = std::pow(static_cast<double>(d->rope_theta), -2.0 * i / (2.0 * half));
+      for (int p = 0; p < d->max_pos; ++p) {
+        const double a = p * inv_freq;
+        const float2 cs = make_float2(static_cast<float>(std::cos(a)), static_cast<float>(std::sin(a)));
+        for (int h = 0; h < d->heads; ++h) rope_host[static_cast<size_t>(p) * row + h * half + i] = cs;
+      }
+    }
+    float* table = nullptr;
+    VR_TRY(dev_alloc_copy(e, enc, rope_host.data(), rope_host.size() * 2, VR_MEM_HOST, &table));
+    enc->rope = reinterpret_cast<float2*>(table);
+  }
   VR_TRY(dev_alloc_copy(e, enc, t[2], static_cast<size_t>(d->type_vocab) * H, mem, &enc->type));
   VR_TRY(dev_alloc_copy(e, enc, t[3], H, mem, &enc->lng));
   VR_TRY(dev_alloc_copy(e, enc, t[4], H, mem, &enc->lnb));
   const hipMemcpyKind kind = mem == VR_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
   for (int l = 0; l < L; ++l) {
-    const void* const* w = t + 5 + 16 * l;  // q_w q_b k_w k_b v_w v_b o_w o_b ln1_g ln1_b i_w i_b f_w f_b ln2_g ln2_b
+    // q_w q_b k_w k_b v_w v_b o_w o_b ln1_g ln1_b i_w i_b f_w f_b ln2_g ln2_b (gated: + gate_w gate_b, i_* = up)
+    const void* const* w = t + 5 + per_layer * l;
+    const int N1 = gated ? 2 * I : I;  // rows of the FFN-up matrix: gated = the gate's I rows, then the up projection's
     LayerWeights lw{};
     VR_TRY(dev_alloc_copy(e, enc, nullptr, 3 * HH, mem, &lw.wqkv));
     VR_TRY(dev_alloc_copy(e, enc, nullptr, 3 * static_cast<size_t>(H), mem, &lw.bqkv));
     for (int p = 0; p < 3; ++p) {  // fused QKV projection: rows [0,H) = query, [H,2H) = key, [2H,3H) = value
       VR_HIP(hipMemcpyAsync(lw.wqkv + p * HH, w[2 * p], HH * sizeof(float), kind, e->stream));
-      VR_HIP(hipMemcpyAsync(lw.bqkv + p * H, w[2 * p + 1], H * sizeof(float), kind, e->stream));
+      if (w[2 * p + 1]) VR_HIP(hipMemcpyAsync(lw.bqkv + p * H, w[2 * p + 1], H * sizeof(float), kind, e->stream));
+      else VR_HIP(hipMemsetAsync(lw.bqkv + p * H, 0, H * sizeof(float), e->stream));
     }
     VR_TRY(dev_alloc_copy(e, enc, w[6], HH, mem, &lw.wo));
-    VR_TRY(dev_alloc_copy(e, enc, w[7], H, mem, &lw.bo));
+    VR_TRY(dev_alloc_copy_or_zero(e, enc, w[7], H, mem, &lw.bo));
     VR_TRY(dev_alloc_copy(e, enc, w[8], H, mem, &lw.ln1g));
     VR_TRY(dev_alloc_copy(e, enc, w[9], H, mem, &lw.ln1b));
-    VR_TRY(dev_alloc_copy(e, enc, w[10], static_cast<size_t>(I) * H, mem, &lw.w1));
-    VR_TRY(dev_alloc_copy(e, enc, w[11], I, mem, &lw.b1));
+    if (gated) {
+      const size_t IH = static_cast<size_t>(I) * H;
+      VR_TRY(dev_alloc_copy(e, enc, nullptr, 2 * IH, mem, &lw.w1));
+      VR_TRY(dev_alloc_copy(e, enc, nullptr, 2 * static_cast<size_t>(I), mem, &lw.b1));
+      for (int p = 0; p < 2; ++p) {  // p = 0: gate (slots 16, 17), 1: up (slots 10, 11)
+        const void* pw = p == 0 ? w[16] : w[10];
+        const void* pb = p == 0 ? w[17] : w[11];
+        VR_HIP(hipMemcpyAsync(lw.w1 + p * IH, pw, IH * sizeof(float), kind, e->stream));
+        if (pb) VR_HIP(hipMemcpyAsync(lw.b1 + p * I, pb, I * sizeof(float), kind, e->stream));
+        else VR_HIP(hipMemsetAsync(lw.b1 + p * I, 0, I * sizeof(float), e->stream));
+      }
+    } else {
+      VR_TRY(dev_alloc_copy(e, enc, w[10], static_cast<size_t>(I) * H, mem, &lw.w1));
+      VR_TRY(dev_alloc_copy_or_zero(e, enc, w[11], I, mem, &lw.b1));
+    }
     VR_TRY(dev_alloc_copy(e, enc, w[12], static_cast<size_t>(I) * H, mem, &lw.w2));
-    VR_TRY(dev_alloc_copy(e, enc, w[13], H, mem, &lw.b2));
+    VR_TRY(dev_alloc_copy_or_zero(e, enc, w[13], H, mem, &lw.b2));
     VR_TRY(dev_alloc_copy(e, enc, w[14], H, mem, &lw.ln2g));
     VR_TRY(dev_alloc_copy(e, enc, w[15], H, mem, &lw.ln2b));
     if (d->precision != VR_PRECISION_F32) {
       const bool plain = d->precision == VR_PRECISION_F16;
       VR_TRY(make_split(e, enc, lw.wqkv, 3 * HH, H, plain, &lw.s_qkv));
       VR_TRY(make_split(e, enc, lw.wo, HH, H, plain, &lw.s_o));
-      VR_TRY(make_split(e, enc, lw.w1, static_cast<size_t>(I) * H, H, plain, &lw.s_1));
+      VR_TRY(make_split(e, enc, lw.w1, static_cast<size_t>(N1) * H, H, plain, &lw.s_1));
       VR_TRY(make_split(e, enc, lw.w2, static_cast<size_t>(I) * H, I, plain, &lw.s_2));
+      if (plain && (rotary || gated) && enc->fuse) {  // the re-ordered matrices and biases of the fused epilogues
+        auto reordered = [&](const float* w_dev, const float* b_dev, int rows, int mode, int n, SplitWeight* sw, float** bias) -> int {
+          const size_t cnt = static_cast<size_t>(rows) * H;
+          float* tmp = nullptr;
+          VR_HIP(hipMalloc(reinterpret_cast<void**>(&tmp), cnt * sizeof(float)));
+          hipLaunchKernelGGL(reorder_rows_kernel, dim3(static_cast<unsigned>((cnt + 255) / 256)), dim3(256), 0, e->stream, w_dev,
+                             static_cast<int64_t>(cnt), H, mode, n, H / d->heads, tmp);
+          int rc = make_split(e, enc, tmp, cnt, H, true, sw);
+          if (rc == 0) rc = dev_alloc_copy(e, enc, nullptr, rows, 0, bias);
+          if (rc == 0)
+            hipLaunchKernelGGL(reorder_rows_kernel, dim3(static_cast<unsigned>((rows + 255) / 256)), dim3(256), 0, e->stream, b_dev,
+                               static_cast<int64_t>(rows), 1, mode, n, H / d->heads, *bias);
+          (void)hipStreamSynchronize(e->stream);
+          (void)hipFree(tmp);
+          return rc;
+        };
+        if (rotary) VR_TRY(reordered(lw.wqkv, lw.bqkv, 3 * H, 0, H, &lw.s_qkv_p, &lw.bqkv_p));
+        if (gated) VR_TRY(reordered(lw.w1, lw.b1, 2 * I, 1, I, &lw.s_1_p, &lw.b1_p));
+      }
       if (plain && H % 64 == 0) {  // operands of the folded-LayerNorm GEMMs
         auto fold = [&](const float* w_dev, int N, const float* g, const float* b, const float* bias, SplitWeight* sw,
                         float** colsum, float** c) -> int {
@@ -3518,7 +3900,17 @@ static int build_encoder(vr_engine* e, void** slot, const vr_bert_desc* d, const
           (void)hipFree(scaled);
           return rc;
         };
-        VR_TRY(fold(lw.w1, I, lw.ln1g, lw.ln1b, lw.b1, &lw.s_1_f, &lw.cs_1, &lw.c_1));
+        VR_TRY(fold(lw.w1, N1, lw.ln1g, lw.ln1b, lw.b1, &lw.s_1_f, &lw.cs_1, &lw.c_1));
+        if (gated && lw.b1_p) {  // the same from the interleaved matrix (EPI_FOLD_*GLU)
+          const size_t cnt = static_cast<size_t>(N1) * H;
+          float* inter = nullptr;
+          VR_HIP(hipMalloc(reinterpret_cast<void**>(&inter), cnt * sizeof(float)));
+          hipLaunchKernelGGL(reorder_rows_kernel, dim3(static_cast<unsigned>((cnt + 255) / 256)), dim3(256), 0, e->stream, lw.w1,
+                             static_cast<int64_t>(cnt), H, 1, I, H / d->heads, inter);
+          const int rc = fold(inter, N1, lw.ln1g, lw.ln1b, lw.b1_p, &lw.s_1_fp, &lw.cs_1_p, &lw.c_1_p);  // (drains the stream)
+          (void)hipFree(inter);
+          VR_TRY(rc);
+        }
         if (!enc->layers.empty()) {
           const LayerWeights& prev = enc->layers.back();
           VR_TRY(fold(lw.wqkv, 3 * H, prev.ln2g, prev.ln2b, lw.bqkv, &lw.s_qkv_f, &lw.cs_qkv, &lw.c_qkv));
@@ -3535,8 +3927,13 @@ int encoder_load(vr_engine* e, const vr_bert_desc* d, const void* const* t, int 
   return build_encoder(e, &e->encoder, d, t, n_tensors, mem);
 }
 
-int reranker_load(vr_engine* e, const vr_bert_desc* d, const void* const* t, int n_tensors, int mem) {
-  VR_CHECK(d->struct_size == static_cast<int32_t>(sizeof(vr_bert_desc)), "vr_bert_desc size mismatch");
+int reranker_load(vr_engine* e, const vr_bert_desc* d_in, const void* const* t, int n_tensors, int mem) {
+  vr_bert_desc desc;
+  VR_TRY(read_desc(d_in, &desc));
+  const vr_bert_desc* d = &desc;
+  VR_CHECK(d->position == VR_POS_LEARNED && d->ffn == VR_FFN_GELU,
+           "a reranker with rotary positions or a gated FFN is not supported (position %d, ffn %d): cross-encoders are "
+           "BERT or XLM-RoBERTa models", d->position, d->ffn);
   VR_CHECK(d->pooling == VR_POOL_CLS && d->normalize == 0, "a reranker pools the [CLS] row (pooling 1) without normalising");
   // two token types (BERT: segment B reads type row 1), or one (XLM-R: every token reads row 0, seg_b is not used)
   VR_CHECK(d->type_vocab >= 1, "a reranker needs a token type (type_vocab %d)", d->type_vocab);
@@ -3569,7 +3966,7 @@ static int ensure_workspace(vr_engine* e, Encoder* enc, int64_t tokens) {
   if (tokens > 4096) tokens = (tokens + tokens / 16 + 4095) / 4096 * 4096;
   VR_HIP(hipStreamSynchronize(e->stream));
   invalidate_graphs(enc);
-  for (float** p : {&enc->x, &enc->qkv, &enc->ctx, &enc->tmp, &enc->ffn, &enc->xs, &enc->lnstat, &enc->lnpart}) {
+  for (float** p : {&enc->x, &enc->qkv, &enc->ctx, &enc->tmp, &enc->ffn, &enc->xs, &enc->lnstat, &enc->lnpart, &enc->glu, &enc->posidx}) {
     if (*p) {
       enc->owned.erase(std::remove(enc->owned.begin(), enc->owned.end(), *p), enc->owned.end());
       (void)hipFree(*p);
@@ -3586,6 +3983,8 @@ static int ensure_workspace(vr_engine* e, Encoder* enc, int64_t tokens) {
   if (enc->d.precision != VR_PRECISION_F32) VR_TRY(dev_alloc_copy(e, enc, nullptr, T * H, 0, &enc->xs));
   if (enc->d.precision == VR_PRECISION_F16) VR_TRY(dev_alloc_copy(e, enc, nullptr, T * 4, 0, &enc->lnstat));
   if (enc->d.precision == VR_PRECISION_F16) VR_TRY(dev_alloc_copy(e, enc, nullptr, T * ((H + 63) / 64) * 2, 0, &enc->lnpart));
+  if (enc->d.position == VR_POS_ROTARY) VR_TRY(dev_alloc_copy(e, enc, nullptr, T, 0, &enc->posidx));
+  // (enc->glu, the gated FFN's pre-activation, is allocated by forward_chunk when a pass is about to store one)
   enc->ws_tokens = tokens;
   return 0;
 }
@@ -3645,16 +4044,57 @@ static int forward_chunk(vr_engine* e, Encoder* enc, const int32_t* ids_dev, con
   const int segs = H / 64;
   const unsigned fin_blocks = static_cast<unsigned>((T + 255) / 256);
   if (seg_dev)
-    hipLaunchKernelGGL(embed_ln_kernel<true>, dim3(row_blocks), dim3(256), 0, s, ids_dev, cu_dev, n_seq_total,
+    hipLaunchKernelGGL((embed_ln_kernel<true>), dim3(row_blocks), dim3(256), 0, s, ids_dev, cu_dev, n_seq_total,
                        tok_base, T, H, d.vocab, enc->word, enc->pos, enc->type, enc->lng, enc->lnb, d.eps,
                        lnfuse ? nullptr : enc->x, xh, xl, lnfuse ? enc->x : nullptr, lnfuse ? stat_b : nullptr, seg_dev);
+  else if (d.position == VR_POS_ROTARY)
+    hipLaunchKernelGGL(embed_ln_rotary_kernel, dim3(row_blocks), dim3(256), 0, s, ids_dev, cu_dev, n_seq_total,
+                       tok_base, T, H, d.vocab, enc->word, enc->type, enc->lng, enc->lnb, d.eps, lnfuse ? nullptr : enc->x, xh, xl,
+                       lnfuse ? enc->x : nullptr, lnfuse ? stat_b : nullptr);
   else
-    hipLaunchKernelGGL(embed_ln_kernel<false>, dim3(row_blocks), dim3(256), 0, s, ids_dev, cu_dev, n_seq_total,
+    hipLaunchKernelGGL((embed_ln_kernel<false>), dim3(row_blocks), dim3(256), 0, s, ids_dev, cu_dev, n_seq_total,
                        tok_base, T, H, d.vocab, enc->word, enc->pos, enc->type, enc->lng, enc->lnb, d.eps,
                        lnfuse ? nullptr : enc->x, xh, xl, lnfuse ? enc->x : nullptr, lnfuse ? stat_b : nullptr,
                        static_cast<const int32_t*>(nullptr));
   const int qblocks = (max_len + 63) / 64;
   const float scale = 1.0f / sqrtf(static_cast<float>(dh));
+  // Rotary positions and the gated FFN. UNFUSED: passes of their own behind the projections' existing epilogues —
+  // rope_kernel in place on the Q and K thirds of the qkv rows, and the FFN-up projection (N = 2I, bias only) into
+  // enc->glu followed by glu_kernel, which writes the rows the FFN-down projection reads. FUSED (f16 mode, products that
+  // launch_gemm_f16x3 / launch_skinny_ln send to a skinny kernel, i.e. at most 256 rows — a question, a few chunks):
+  // the projection runs over the re-ordered matrix and its epilogue rotates / gates (EPI_ROPE_F16, EPI_*GLU_F16), no
+  // further launch and no second f16 rounding. VR_ENCODE_FUSE=0 when the model is loaded keeps the unfused form
+  // everywhere for that model (A/B runs in one process, tests); its cached graphs then hold that form too.
+  const bool rotary = d.position == VR_POS_ROTARY, gated = d.ffn != VR_FFN_GELU;
+  const int N1 = gated ? 2 * I : I;
+  half_t* gluh = reinterpret_cast<half_t*>(enc->glu);
+  const bool fuse_enabled = enc->fuse;
+  const bool fuse_rope = rotary && plain && fuse_enabled && skinny_routed(T, 3 * H, H);
+  auto fuse_glu = [&](int M) { return gated && plain && fuse_enabled && skinny_routed(M, N1, H); };
+  const int glu_epi = d.ffn == VR_FFN_SWIGLU ? EPI_SWIGLU_F16 : EPI_GEGLU_F16;
+  // large batches: the gate in the epilogue of the folded-LayerNorm projection (mid / ping-pong kernel, EPI_FOLD_*GLU)
+  const bool fuse_glu_big = gated && fuse_enabled && !fuse_glu(T) && fold_big && pp_usable(N1, H) &&
+                            enc->layers[0].cs_1_p != nullptr;
+  const int32_t* posidx = reinterpret_cast<const int32_t*>(enc->posidx);
+  if (rotary)
+    hipLaunchKernelGGL(positions_kernel, dim3(static_cast<unsigned>((T + 255) / 256)), dim3(256), 0, s, cu_dev, n_seq_total,
+                       tok_base, T, reinterpret_cast<int32_t*>(enc->posidx));
+  auto rope = [&]() {
+    if (!rotary || fuse_rope) return;
+    if (plain)
+      hipLaunchKernelGGL(rope_kernel<half_t>, dim3(row_blocks), dim3(256), 0, s, reinterpret_cast<half_t*>(enc->qkv), posidx, T,
+                         H, dh, enc->rope);
+    else
+      hipLaunchKernelGGL(rope_kernel<float>, dim3(row_blocks), dim3(256), 0, s, enc->qkv, posidx, T, H, dh, enc->rope);
+  };
+  // M rows of enc->glu -> the FFN-down input: f16 mode plain f16 rows at out_h, f16x3 (hi, lo) rows at out_h, f32 at out
+  auto glu = [&](int M, float* out, half_t* out_h) {
+    const int64_t n8 = static_cast<int64_t>(M) * (I / 8);
+    const dim3 grid(static_cast<unsigned>((n8 + 255) / 256));
+    if (plain) hipLaunchKernelGGL((glu_kernel<half_t, 2>), grid, dim3(256), 0, s, gluh, n8, I, d.ffn, static_cast<float*>(nullptr), out_h);
+    else if (split) hipLaunchKernelGGL((glu_kernel<float, 1>), grid, dim3(256), 0, s, enc->glu, n8, I, d.ffn, static_cast<float*>(nullptr), out_h);
+    else hipLaunchKernelGGL((glu_kernel<float, 0>), grid, dim3(256), 0, s, enc->glu, n8, I, d.ffn, out, static_cast<half_t*>(nullptr));
+  };
   // CLS pooling reads one row per sequence, so everything after the LAST layer's attention is needed
   // for those rows only: their context rows (and residual rows) are gathered into compact [n_seq, *]
   // matrices carved out of the qkv buffer (free once attention has run), and the output projection,
@@ -3665,6 +4105,14 @@ static int forward_chunk(vr_engine* e, Encoder* enc, const int32_t* ids_dev, con
   const int n_seq = seq1 - seq0;
   const bool cls_tail = d.pooling == VR_POOL_CLS && !enc->layers.empty() &&
                         static_cast<int64_t>(n_seq) * (4 * H + I) <= static_cast<int64_t>(T) * 3 * H;
+  // The [rows, 2I] pre-activation workspace exists only once a pass really stores one: an unfused FFN-up over the T
+  // rows, or over the CLS tail's n_seq rows. (Never during a graph capture: a shape runs eagerly first, and a
+  // reallocation of the workspace drops both this buffer and the graphs.)
+  if (gated && !enc->glu && ((!fuse_glu(T) && !fuse_glu_big) || (cls_tail && !fuse_glu(n_seq)))) {
+    const size_t rows = static_cast<size_t>(enc->ws_tokens);
+    VR_TRY(dev_alloc_copy(e, enc, nullptr, plain ? rows * I : rows * 2 * I, 0, &enc->glu));
+    gluh = reinterpret_cast<half_t*>(enc->glu);
+  }
   float* xc = enc->qkv;                                       // [n_seq, H] hidden state of the [CLS] rows
   float* tmpc = xc + static_cast<int64_t>(n_seq) * H;         // [n_seq, H]
   float* xsc = tmpc + static_cast<int64_t>(n_seq) * H;        // [n_seq, 2H] halfs (split) = n_seq*H floats
@@ -3673,13 +4121,20 @@ static int forward_chunk(vr_engine* e, Encoder* enc, const int32_t* ids_dev, con
   for (size_t li = 0; li < enc->layers.size(); ++li) {
     const LayerWeights& w = enc->layers[li];
     const bool tail = cls_tail && li + 1 == enc->layers.size();
-    if (plain && fold_ln && li > 0)  // the previous layer's closing LayerNorm runs inside this projection
+    if (plain && fold_ln && li > 0 && fuse_rope)  // ... and the rotation in its epilogue
+      VR_TRY(launch_skinny_ln(e, EPI_ROPE_F16, cur.pre, cur.g, cur.b, d.eps, const_cast<float2*>(cur.stat), w.s_qkv_p.hi,
+                              w.s_qkv_p.unscale, w.bqkv_p, reinterpret_cast<half_t*>(enc->qkv), T, 3 * H, H, enc->rope, posidx));
+    else if (plain && fold_ln && li > 0)  // the previous layer's closing LayerNorm runs inside this projection
       VR_TRY(launch_skinny_ln(e, EPI_BIAS_F16, cur.pre, cur.g, cur.b, d.eps, const_cast<float2*>(cur.stat), w.s_qkv.hi,
                               w.s_qkv.unscale, w.bqkv, reinterpret_cast<half_t*>(enc->qkv), T, 3 * H, H));
     else if (plain && fold_big && li > 0)  // xh holds the f16 PRE-LN rows the previous FFN-down epilogue stored
       VR_TRY(launch_gemm_f16x3(e, enc, EPI_FOLD_F16, xh, nullptr, w.s_qkv_f.hi, nullptr, w.s_qkv_f.unscale, w.c_qkv, nullptr,
                                nullptr, reinterpret_cast<half_t*>(enc->qkv), nullptr, T, 3 * H, H, 1, cur.stat, w.cs_qkv,
                                nullptr));
+    else if (plain && fuse_rope)  // (ln_stat / ln_g carry the table and the positions, see EPI_ROPE_F16)
+      VR_TRY(launch_gemm_f16x3(e, enc, EPI_ROPE_F16, xh, nullptr, w.s_qkv_p.hi, nullptr, w.s_qkv_p.unscale, w.bqkv_p, nullptr,
+                               nullptr, reinterpret_cast<half_t*>(enc->qkv), nullptr, T, 3 * H, H, 1, enc->rope,
+                               reinterpret_cast<const float*>(posidx)));
     else if (plain)  // Q, K, V as plain f16 rows for attention_f16_kernel
       VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_F16, xh, xl, w.s_qkv.hi, w.s_qkv.lo, w.s_qkv.unscale, w.bqkv, nullptr,
                                nullptr, reinterpret_cast<half_t*>(enc->qkv), nullptr, T, 3 * H, H, passes));
@@ -3688,6 +4143,7 @@ static int forward_chunk(vr_engine* e, Encoder* enc, const int32_t* ids_dev, con
                                enc->qkv, nullptr, nullptr, T, 3 * H, H, passes));
     else
       VR_TRY(launch_gemm(e, EPI_BIAS, enc->x, w.wqkv, w.bqkv, nullptr, enc->qkv, T, 3 * H, H));
+    rope();
     const int qb = tail ? 1 : qblocks;  // tail: only the query block that holds token 0 of every sequence
     dim3 agrid(static_cast<unsigned>(n_seq * qb), static_cast<unsigned>(nh));
     prof_begin(e, VR_PROF_ATTENTION, tail ? attn_flop / qblocks : attn_flop);
@@ -3759,13 +4215,29 @@ static int forward_chunk(vr_engine* e, Encoder* enc, const int32_t* ids_dev, con
         VR_TRY(launch_gemm(e, EPI_BIAS_RESIDUAL, ctxc, w.wo, w.bo, xc, tmpc, n_seq, H, H));
       hipLaunchKernelGGL(layernorm_kernel, dim3(cblocks), dim3(256), 0, s, tmpc, n_seq, H, w.ln1g, w.ln1b, d.eps, xc,
                          split ? xch : nullptr, split && !plain ? xch + 8 : nullptr, static_cast<float2*>(nullptr));
-      if (split) {
+      if (gated && fuse_glu(n_seq)) {
+        VR_TRY(launch_gemm_f16x3(e, enc, glu_epi, xch, nullptr, w.s_1_p.hi, nullptr, w.s_1_p.unscale, w.b1_p, nullptr, nullptr, fch,
+                                 nullptr, n_seq, N1, H, 1));
+      } else if (gated) {
+        if (plain)
+          VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_F16, xch, nullptr, w.s_1.hi, nullptr, w.s_1.unscale, w.b1, nullptr, nullptr, gluh,
+                                   nullptr, n_seq, N1, H, 1));
+        else if (split)
+          VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS, xch, xch + 8, w.s_1.hi, w.s_1.lo, w.s_1.unscale, w.b1, nullptr, enc->glu,
+                                   nullptr, nullptr, n_seq, N1, H, passes));
+        else
+          VR_TRY(launch_gemm(e, EPI_BIAS, xc, w.w1, w.b1, nullptr, enc->glu, n_seq, N1, H));
+        glu(n_seq, ffnc, fch);
+      } else if (split) {
         VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_GELU, xch, plain ? nullptr : xch + 8, w.s_1.hi, w.s_1.lo, w.s_1.unscale, w.b1, nullptr, nullptr,
                                  fch, plain ? nullptr : fch + 8, n_seq, I, H, passes));
+      } else {
+        VR_TRY(launch_gemm(e, EPI_BIAS_GELU, xc, w.w1, w.b1, nullptr, ffnc, n_seq, I, H));
+      }
+      if (split) {
         VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_RESIDUAL, fch, plain ? nullptr : fch + 8, w.s_2.hi, w.s_2.lo, w.s_2.unscale, w.b2, xc, tmpc,
                                  nullptr, nullptr, n_seq, H, I, passes));
       } else {
-        VR_TRY(launch_gemm(e, EPI_BIAS_GELU, xc, w.w1, w.b1, nullptr, ffnc, n_seq, I, H));
         VR_TRY(launch_gemm(e, EPI_BIAS_RESIDUAL, ffnc, w.w2, w.b2, xc, tmpc, n_seq, H, I));
       }
       hipLaunchKernelGGL(layernorm_kernel, dim3(cblocks), dim3(256), 0, s, tmpc, n_seq, H, w.ln2g, w.ln2b, d.eps, xc,
@@ -3805,14 +4277,27 @@ static int forward_chunk(vr_engine* e, Encoder* enc, const int32_t* ids_dev, con
       const Hidden mid{t1, s1, w.ln1g, w.ln1b};
       float* t2 = const_cast<float*>(cur.pre);  // its last reader (the epilogue above) is done
       float2* s2 = const_cast<float2*>(cur.stat);
-      if (fold_ln)
-        VR_TRY(launch_skinny_ln(e, EPI_BIAS_GELU, t1, w.ln1g, w.ln1b, d.eps, s1, w.s_1.hi, w.s_1.unscale, w.b1, fh, T, I, H));
+      half_t* up_out = gated ? gluh : fh;  // gated: the same projections with the bias-only f16 epilogues, then glu_kernel
+      const bool fg = fuse_glu(T);      // ... or, fused, the gate in the projection's epilogue over the re-ordered matrix
+      const bool fgb = fuse_glu_big;
+      if (fg && fold_ln)
+        VR_TRY(launch_skinny_ln(e, glu_epi, t1, w.ln1g, w.ln1b, d.eps, s1, w.s_1_p.hi, w.s_1_p.unscale, w.b1_p, fh, T, N1, H));
+      else if (fg)
+        VR_TRY(launch_gemm_f16x3(e, enc, glu_epi, xh, nullptr, w.s_1_p.hi, nullptr, w.s_1_p.unscale, w.b1_p, nullptr, nullptr, fh,
+                                 nullptr, T, N1, H, 1));
+      else if (fgb)
+        VR_TRY(launch_gemm_f16x3(e, enc, d.ffn == VR_FFN_SWIGLU ? EPI_FOLD_SWIGLU : EPI_FOLD_GEGLU, xh, nullptr, w.s_1_fp.hi, nullptr,
+                                 w.s_1_fp.unscale, w.c_1_p, nullptr, nullptr, fh, nullptr, T, N1, H, 1, s1, w.cs_1_p, nullptr));
+      else if (fold_ln)
+        VR_TRY(launch_skinny_ln(e, gated ? EPI_BIAS_F16 : EPI_BIAS_GELU, t1, w.ln1g, w.ln1b, d.eps, s1, w.s_1.hi, w.s_1.unscale,
+                                w.b1, up_out, T, N1, H));
       else if (fold_big)
-        VR_TRY(launch_gemm_f16x3(e, enc, EPI_FOLD_GELU, xh, nullptr, w.s_1_f.hi, nullptr, w.s_1_f.unscale, w.c_1, nullptr, nullptr,
-                                 fh, nullptr, T, I, H, 1, s1, w.cs_1, nullptr));
+        VR_TRY(launch_gemm_f16x3(e, enc, gated ? EPI_FOLD_F16 : EPI_FOLD_GELU, xh, nullptr, w.s_1_f.hi, nullptr, w.s_1_f.unscale,
+                                 w.c_1, nullptr, nullptr, up_out, nullptr, T, N1, H, 1, s1, w.cs_1, nullptr));
       else
-      VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_GELU, xh, nullptr, w.s_1.hi, nullptr, w.s_1.unscale, w.b1, nullptr, nullptr, fh,
-                               nullptr, T, I, H, 1));
+      VR_TRY(launch_gemm_f16x3(e, enc, gated ? EPI_BIAS_F16 : EPI_BIAS_GELU, xh, nullptr, w.s_1.hi, nullptr, w.s_1.unscale, w.b1,
+                               nullptr, nullptr, up_out, nullptr, T, N1, H, 1));
+      if (gated && !fg && !fgb) glu(T, nullptr, fh);
       if (res16)  // (the last layer of a mean-pooled model also writes f32 rows: the final LayerNorm reads them)
         VR_TRY(launch_gemm_f16x3(e, enc, last ? EPI_RLS_R16_O32 : EPI_RLS_R16_O16, fh, nullptr, w.s_2.hi, nullptr, w.s_2.unscale,
                                  w.b2, reinterpret_cast<const float*>(xh), last ? t2 : nullptr, xh,
@@ -3846,13 +4331,25 @@ static int forward_chunk(vr_engine* e, Encoder* enc, const int32_t* ids_dev, con
       VR_TRY(launch_gemm(e, EPI_BIAS_RESIDUAL, enc->ctx, w.wo, w.bo, enc->x, enc->tmp, T, H, H));
     hipLaunchKernelGGL(layernorm_kernel, dim3(row_blocks), dim3(256), 0, s, enc->tmp, T, H, w.ln1g, w.ln1b,
                        d.eps, enc->x, xh, xl, static_cast<float2*>(nullptr));
+    if (gated) {
+      if (split)
+        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS, xh, xl, w.s_1.hi, w.s_1.lo, w.s_1.unscale, w.b1, nullptr, enc->glu, nullptr,
+                                 nullptr, T, N1, H, passes));
+      else
+        VR_TRY(launch_gemm(e, EPI_BIAS, enc->x, w.w1, w.b1, nullptr, enc->glu, T, N1, H));
+      glu(T, enc->ffn, fh);
+    }
     if (split) {
-      VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_GELU, xh, xl, w.s_1.hi, w.s_1.lo, w.s_1.unscale, w.b1, nullptr,
-                               nullptr, fh, fl, T, I, H, passes));
+      if (!gated) {
+        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_GELU, xh, xl, w.s_1.hi, w.s_1.lo, w.s_1.unscale, w.b1, nullptr,
+                                 nullptr, fh, fl, T, I, H, passes));
+      }
       VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_RESIDUAL, fh, fl, w.s_2.hi, w.s_2.lo, w.s_2.unscale, w.b2, enc->x,
                                enc->tmp, nullptr, nullptr, T, H, I, passes));
     } else {
-      VR_TRY(launch_gemm(e, EPI_BIAS_GELU, enc->x, w.w1, w.b1, nullptr, enc->ffn, T, I, H));
+      if (!gated) {
+        VR_TRY(launch_gemm(e, EPI_BIAS_GELU, enc->x, w.w1, w.b1, nullptr, enc->ffn, T, I, H));
+      }
       VR_TRY(launch_gemm(e, EPI_BIAS_RESIDUAL, enc->ffn, w.w2, w.b2, enc->x, enc->tmp, T, H, I));
     }
     hipLaunchKernelGGL(layernorm_kernel, dim3(row_blocks), dim3(256), 0, s, enc->tmp, T, H, w.ln2g, w.ln2b,

@@ -42,13 +42,34 @@ def read_encoder_config(path: str) -> dict:
     pad_token_id - 1); one token type; max_seq = min(max_seq_length, max_pos), refused above 512."""
     cfg = json.load(open(os.path.join(path, "config.json")))
     kind = cfg.get("model_type", "bert")
+    if kind == "nomic_bert":
+        return _read_rope_config(path, cfg)
     if kind not in ("bert", "xlm-roberta"):
-        raise ValueError(f"unsupported model_type {kind}: BERT and XLM-RoBERTa encoders only")
+        raise ValueError(f"unsupported model_type {kind}: BERT, XLM-RoBERTa and nomic_bert encoders only")
     if cfg.get("hidden_act", "gelu") != "gelu" or cfg.get("position_embedding_type", "absolute") != "absolute":
         raise ValueError("only exact-erf GELU and absolute position embeddings are implemented")
     pos_start = int(cfg.get("pad_token_id", 1)) + 1 if kind == "xlm-roberta" else 0
     max_pos = int(cfg["max_position_embeddings"]) - pos_start
-    pooling, normalize, max_seq = "mean", False, max_pos
+    pooling, normalize, max_seq = _read_modules(path, max_pos)
+    max_seq = min(max_seq, max_pos)
+    if kind == "xlm-roberta" and max_seq > MAX_SEQ:
+        raise ValueError(f"{path} uses sequences of up to {max_seq} tokens; the engine runs at most {MAX_SEQ}: set "
+                         f"max_seq_length <= {MAX_SEQ} in its sentence_bert_config.json")
+    desc = _enc.BertDesc(layers=cfg["num_hidden_layers"], hidden=cfg["hidden_size"],
+                         heads=cfg["num_attention_heads"], intermediate=cfg["intermediate_size"],
+                         vocab=cfg["vocab_size"], max_pos=max_pos,
+                         type_vocab=cfg.get("type_vocab_size", 2), pooling=pooling, normalize=normalize,
+                         eps=cfg.get("layer_norm_eps", 1e-12),
+                         # f16 (default): f16 MFMA operands, f32 accumulate, |1 - cos| < 1e-6 vs f64
+                         # (north_star allows 1e-4); f16x3: (hi, lo) f16 operands, three passes,
+                         # |1 - cos| ~5e-8, 1.8x slower; f32: the f32-input MFMA, 5x slower
+                         precision=os.environ.get("VOITTA_ENCODER_PRECISION", "f16"))
+    return {"desc": desc, "max_seq": max_seq, "pos_start": pos_start, "config": cfg}
+
+
+def _read_modules(path: str, max_seq: int):
+    """modules.json / sentence_bert_config.json of a sentence-transformers directory -> (pooling, normalize, max_seq)."""
+    pooling, normalize = "mean", False
     mod_path = os.path.join(path, "modules.json")
     if os.path.exists(mod_path):
         for m in json.load(open(mod_path)):
@@ -64,20 +85,47 @@ def read_encoder_config(path: str) -> dict:
     sb = os.path.join(path, "sentence_bert_config.json")
     if os.path.exists(sb):
         max_seq = int(json.load(open(sb)).get("max_seq_length", max_seq))
-    max_seq = min(max_seq, max_pos)
-    if kind == "xlm-roberta" and max_seq > MAX_SEQ:
-        raise ValueError(f"{path} uses sequences of up to {max_seq} tokens; the engine runs at most {MAX_SEQ}: set "
-                         f"max_seq_length <= {MAX_SEQ} in its sentence_bert_config.json")
-    desc = _enc.BertDesc(layers=cfg["num_hidden_layers"], hidden=cfg["hidden_size"],
-                         heads=cfg["num_attention_heads"], intermediate=cfg["intermediate_size"],
-                         vocab=cfg["vocab_size"], max_pos=max_pos,
+    return pooling, normalize, max_seq
+
+
+def _read_rope_config(path: str, cfg: dict) -> dict:
+    """model_type nomic_bert in the native transformers layout (NomicBertConfig's keys): a post-LayerNorm BERT with
+    rotary positions over the whole head (rotate-half pairing) and a gated FFN without biases. Sequences are capped at
+    MAX_SEQ (these checkpoints declare 2048-8192): truncation is well defined without a learned table."""
+    if "hidden_size" not in cfg:
+        raise ValueError(f"{path}: model_type nomic_bert without 'hidden_size' — the hub checkpoint's older config "
+                         "spelling (n_embd, n_head, rotary_emb_base, ...) is not read; re-save the config in the "
+                         "native transformers layout (NomicBertConfig)")
+    H, heads = int(cfg["hidden_size"]), int(cfg["num_attention_heads"])
+    rp = cfg.get("rope_parameters") or {}
+    rope_type = rp.get("rope_type", rp.get("type", "default"))
+    if rope_type != "default":
+        raise ValueError(f"rope_type {rope_type!r}: only the default rotary embedding is implemented (no scaling)")
+    if float(rp.get("partial_rotary_factor", cfg.get("rotary_emb_fraction", 1.0))) != 1.0:
+        raise ValueError("partial rotary embeddings are not implemented: the whole head must be rotated")
+    if cfg.get("rotary_emb_interleaved", False):
+        raise ValueError("interleaved rotary embeddings are not implemented (rotate-half pairing only)")
+    if cfg.get("head_dim") not in (None, H // heads):
+        raise ValueError(f"head_dim {cfg['head_dim']} differs from hidden_size / num_attention_heads = {H // heads}")
+    if cfg.get("prenorm", False):
+        raise ValueError("pre-norm encoders are not implemented (post-LayerNorm residual blocks only)")
+    act = cfg.get("hidden_act", "silu")
+    if act not in ("silu", "gelu"):
+        raise ValueError(f"hidden_act {act!r}: the gated FFN runs SiLU (SwiGLU) or exact-erf GELU (GeGLU)")
+    declared = int(cfg.get("max_position_embeddings", 2048))
+    pooling, normalize, max_seq = _read_modules(path, declared)
+    max_seq = min(max_seq, declared)
+    if max_seq > MAX_SEQ:
+        logger.warning("%s declares sequences of up to %d tokens; the engine runs at most %d: longer texts are "
+                       "truncated to %d tokens", path, max_seq, MAX_SEQ, MAX_SEQ)
+        max_seq = MAX_SEQ
+    desc = _enc.BertDesc(layers=cfg["num_hidden_layers"], hidden=H, heads=heads, intermediate=cfg["intermediate_size"],
+                         vocab=cfg["vocab_size"], max_pos=max_seq,  # rotary: the length of the cos/sin table
                          type_vocab=cfg.get("type_vocab_size", 2), pooling=pooling, normalize=normalize,
                          eps=cfg.get("layer_norm_eps", 1e-12),
-                         # f16 (default): f16 MFMA operands, f32 accumulate, |1 - cos| < 1e-6 vs f64
-                         # (north_star allows 1e-4); f16x3: (hi, lo) f16 operands, three passes,
-                         # |1 - cos| ~5e-8, 1.8x slower; f32: the f32-input MFMA, 5x slower
-                         precision=os.environ.get("VOITTA_ENCODER_PRECISION", "f16"))
-    return {"desc": desc, "max_seq": max_seq, "pos_start": pos_start, "config": cfg}
+                         precision=os.environ.get("VOITTA_ENCODER_PRECISION", "f16"), position="rotary",
+                         rope_theta=float(rp.get("rope_theta", 1000.0)), ffn="swiglu" if act == "silu" else "geglu")
+    return {"desc": desc, "max_seq": max_seq, "pos_start": 0, "config": cfg}
 
 
 def slice_positions(state: dict, pos_start: int) -> dict:
@@ -235,16 +283,29 @@ class EmbeddingService:
             logger.info("Model loaded successfully on the MI355X engine")
         return self._model
 
-    def embed_text(self, text: str) -> list[float]:
-        if "e5" in self.model_name.lower():  # embedding.py:50-51
+    # Task prefixes. The reference knows the e5 rule only (model name contains "e5"); models that expect other
+    # prefixes (nomic: "search_document: " / "search_query: ") are served by the opt-in VOITTA_EMBED_PASSAGE_PREFIX /
+    # VOITTA_EMBED_QUERY_PREFIX, applied in front of the (possibly e5-prefixed) text. Empty by default: nothing changes.
+    def _passage(self, text: str) -> str:
+        if "e5" in self.model_name.lower():  # embedding.py:50-51, 65-66
             text = f"passage: {text}"
+        prefix = get_settings().embed_passage_prefix
+        return prefix + text if prefix else text
+
+    def _query(self, text: str) -> str:
+        if "e5" in self.model_name.lower():  # embedding.py:82-83
+            text = f"query: {text}"
+        prefix = get_settings().embed_query_prefix
+        return prefix + text if prefix else text
+
+    def embed_text(self, text: str) -> list[float]:
+        text = self._passage(text)
         return self.model.encode(text, convert_to_numpy=True).tolist()
 
     def embed_texts(self, texts: list[str], batch_size: int = 32) -> list[list[float]]:
         if not texts:
             return []
-        if "e5" in self.model_name.lower():  # embedding.py:65-66
-            texts = [f"passage: {text}" for text in texts]
+        texts = [self._passage(text) for text in texts]
         if _deferred.enabled():
             # tokenised now, encoded when somebody looks at a number — or, when the list goes to store_chunks
             # untouched, together with thousands of other chunks inside the engine (voitta_rag_amd/deferred.py)
@@ -255,8 +316,7 @@ class EmbeddingService:
 
     def embed_query(self, query: str) -> list[float]:
         question = query
-        if "e5" in self.model_name.lower():  # embedding.py:82-83
-            query = f"query: {query}"
+        query = self._query(query)
         model = self.model
         if _deferred.enabled() and native_tokenizer(model.tokenizer):
             out = _deferred.QueryRef(model, query)  # encoded when looked at — or inside the search call it goes to
@@ -266,10 +326,9 @@ class EmbeddingService:
         return out
 
     def query_texts(self, queries: list[str]) -> list[str]:
-        """The questions as the encoder sees them: with the e5 ``query: `` prefix, as embed_query applies it."""
-        if "e5" in self.model_name.lower():  # embedding.py:82-83
-            return [f"query: {q}" for q in queries]
-        return list(queries)
+        """The questions as the encoder sees them: with the e5 ``query: `` prefix (and the opt-in query prefix), as
+        embed_query applies them."""
+        return [self._query(q) for q in queries]
 
     def embed_queries(self, queries: list[str]) -> list[list[float]]:
         """embed_query for many questions in ONE forward pass (the packed batch of vr_encode)."""

@@ -32,6 +32,27 @@ LAYER_SUFFIXES = [
     "output.LayerNorm.weight", "output.LayerNorm.bias",
 ]
 
+# A rotary, gated-FFN encoder (model_type nomic_bert) in the slot order of vr_encoder_load, named as the native
+# transformers NomicBertModel names them. None = a slot the checkpoint has no tensor for (these models carry no
+# biases in their projections and no position table): it crosses the ABI as NULL.
+ROPE_EMB_SUFFIXES = [
+    "embeddings.word_embeddings.weight", None, "embeddings.token_type_embeddings.weight",
+    "embeddings.LayerNorm.weight", "embeddings.LayerNorm.bias",
+]
+ROPE_LAYER_SUFFIXES = [
+    "self_attn.q_proj.weight", None, "self_attn.k_proj.weight", None, "self_attn.v_proj.weight", None,
+    "self_attn.o_proj.weight", None,
+    "post_attention_layernorm.weight", "post_attention_layernorm.bias",
+    "mlp.up_proj.weight", None, "mlp.down_proj.weight", None,
+    "post_mlp_layernorm.weight", "post_mlp_layernorm.bias",
+    "mlp.gate_proj.weight", None,
+]
+# the hub checkpoint's names -> the native ones (transformers' conversion mapping for nomic_bert); attn.Wqkv is the
+# q, k, v matrices stacked along dim 0
+HUB_RENAMES = [("encoder.layers.", "layers."), ("emb_ln.", "embeddings.LayerNorm."), ("attn.out_proj.", "self_attn.o_proj."),
+               ("mlp.fc11.", "mlp.up_proj."), ("mlp.fc12.", "mlp.gate_proj."), ("mlp.fc2.", "mlp.down_proj."),
+               ("norm1.", "post_attention_layernorm."), ("norm2.", "post_mlp_layernorm.")]
+
 
 @dataclass
 class BertDesc:
@@ -46,6 +67,17 @@ class BertDesc:
     normalize: bool = True
     eps: float = 1e-12
     precision: str = "f32"  # "f32" (exact f32 MFMA) | "f16x3" (split-precision f16 MFMA, f32-class accuracy)
+    position: str = "learned"  # "learned" (a position table) | "rotary" (max_pos = length of the cos/sin table)
+    rope_theta: float = 0.0
+    ffn: str = "gelu"  # "gelu" | "swiglu" | "geglu" (down(act(gate(x)) * up(x)), act = SiLU / exact GELU)
+
+    @property
+    def rotary(self) -> bool:
+        return self.position == "rotary"
+
+    @property
+    def gated(self) -> bool:
+        return self.ffn != "gelu"
 
     def to_c(self) -> _lib.VrBertDesc:
         d = _lib.VrBertDesc()
@@ -59,6 +91,13 @@ class BertDesc:
         if self.precision not in codes:
             raise ValueError(f"unknown encoder precision {self.precision!r}")
         d.precision = codes[self.precision]
+        positions = {"learned": _lib.VR_POS_LEARNED, "rotary": _lib.VR_POS_ROTARY}
+        ffns = {"gelu": _lib.VR_FFN_GELU, "swiglu": _lib.VR_FFN_SWIGLU, "geglu": _lib.VR_FFN_GEGLU}
+        if self.position not in positions:
+            raise ValueError(f"unknown position scheme {self.position!r}")
+        if self.ffn not in ffns:
+            raise ValueError(f"unknown ffn kind {self.ffn!r}")
+        d.position, d.rope_theta, d.ffn = positions[self.position], float(self.rope_theta), ffns[self.ffn]
         return d
 
 
@@ -67,6 +106,40 @@ def tensor_names(layers: int) -> list[str]:
     for i in range(layers):
         names += [f"encoder.layer.{i}.{s}" for s in LAYER_SUFFIXES]
     return names
+
+
+def rope_tensor_names(layers: int) -> list:
+    """The slots of a rotary, gated model (5 + 18 per layer) by native name; None = no tensor (NULL)."""
+    names = list(ROPE_EMB_SUFFIXES)
+    for i in range(layers):
+        names += [None if s is None else f"layers.{i}.{s}" for s in ROPE_LAYER_SUFFIXES]
+    return names
+
+
+def names_for(desc: "BertDesc") -> list:
+    """Tensor names by family: BERT / XLM-RoBERTa state-dict names, or the rotary gated family's."""
+    if desc.rotary != desc.gated:
+        raise ValueError("checkpoints are read for BERT-style (learned positions, GELU) and nomic-style (rotary, gated "
+                         f"FFN) encoders; got position={desc.position!r} with ffn={desc.ffn!r}")
+    return rope_tensor_names(desc.layers) if desc.rotary else tensor_names(desc.layers)
+
+
+def native_rope_state(state: dict) -> dict:
+    """A nomic-style state dict under its native names: hub-named entries (encoder.layers.N.attn.Wqkv, mlp.fc11, norm1,
+    emb_ln, ...) are renamed and the fused Wqkv split in thirds along dim 0; native entries pass through."""
+    out = {}
+    for k, v in state.items():
+        for old, new in HUB_RENAMES:
+            k = k.replace(old, new)
+        if ".attn.Wqkv." in k:
+            if v.shape[0] % 3:
+                raise ValueError(f"weight '{k}' has {v.shape[0]} rows, not three equal parts")
+            n = v.shape[0] // 3
+            for j, part in enumerate(("q_proj", "k_proj", "v_proj")):
+                out[k.replace(".attn.Wqkv.", f".self_attn.{part}.")] = v[j * n:(j + 1) * n]
+        else:
+            out[k] = v
+    return out
 
 
 # a BertForSequenceClassification's head, after the encoder's tensors (vr_reranker_load)
@@ -81,10 +154,12 @@ def expected_shape(desc: BertDesc, name: str) -> tuple:
     if name.endswith("word_embeddings.weight"): return (desc.vocab, H)
     if name.endswith("position_embeddings.weight"): return (desc.max_pos, H)
     if name.endswith("token_type_embeddings.weight"): return (desc.type_vocab, H)
+    if name.endswith("mlp.up_proj.weight") or name.endswith("mlp.gate_proj.weight"): return (inter, H)
+    if name.endswith("mlp.down_proj.weight"): return (H, inter)
     if name.endswith("intermediate.dense.weight"): return (inter, H)
     if name.endswith("intermediate.dense.bias"): return (inter,)
     if name.endswith("output.dense.weight") and "attention" not in name: return (H, inter)
-    if name.endswith(".weight") and "LayerNorm" not in name: return (H, H)
+    if name.endswith(".weight") and "layernorm" not in name.lower(): return (H, H)
     return (H,)
 
 
@@ -100,7 +175,9 @@ def _find(state: dict, suffix: str):
 def load_encoder(engine, desc: BertDesc, state: dict) -> None:
     """state: HF BertModel state dict (any key prefix), values NumPy arrays or torch tensors.
     Tensors on the engine's GPU are passed as device pointers, everything else as host memory."""
-    _load(engine, desc, state, tensor_names(desc.layers), engine._lib.vr_encoder_load)
+    if desc.rotary or desc.gated:
+        state = native_rope_state(state)
+    _load(engine, desc, state, names_for(desc), engine._lib.vr_encoder_load)
     engine.encoder_desc = desc
 
 
@@ -114,6 +191,7 @@ def load_reranker(engine, desc: BertDesc, state: dict) -> None:
 
 
 def _load(engine, desc: BertDesc, state: dict, names: list[str], load_fn) -> None:
+    names, all_names = [n for n in names if n is not None], names
     tensors = [_find(state, n) for n in names]
     # raw pointers cross the C-ABI next: a checkpoint whose config.json disagrees with its weights (padded or
     # resized vocabulary, another max_position_embeddings, ...) must fail HERE, not read past a buffer there
@@ -137,6 +215,8 @@ def _load(engine, desc: BertDesc, state: dict, names: list[str], load_fn) -> Non
         keep.append(t)
     if on_device:
         engine._follow(keep[0])
+    it = iter(ptrs)
+    ptrs = [None if n is None else next(it) for n in all_names]  # NULL where the family has no tensor for a slot
     arr = (C.c_void_p * len(ptrs))(*ptrs)
     cdesc = desc.to_c()
     check(load_fn(engine.handle, C.byref(cdesc), arr, len(ptrs), VR_MEM_DEVICE if on_device else VR_MEM_HOST))
