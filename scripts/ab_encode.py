@@ -2,7 +2,7 @@
 differ only in environment variables (the engine reads its switches once per process); every child
 saves its embeddings and prints its timings, the parent compares the outputs bit for bit.
 
-  python scripts/ab_encode.py [model] [n_seq] VAR=a,b [VAR2=c,d ...]     e.g.  VR_GEMM_PP=0,1
+  python scripts/ab_encode.py [model] [n_seq] VAR=a,b [VAR2=c,d ...]     e.g.  VR_GEMM_MID=0,1
 
 Children run one after the other (one process on the GPU at a time), interleaved `rounds` times so that
 clock drift shows up as spread, not as a difference."""

@@ -208,6 +208,29 @@ def test_positions_restart_per_sequence(gpu, path_refs, precision):
     e.close()
 
 
+def test_sequences_past_the_staged_attention_limit(gpu):
+    """f16 attention stages a whole sequence's keys and values in LDS (attention_seq_kernel) while the longest sequence of
+    the call fits a workgroup's LDS: 640 keys at head size 64. 656 tokens, the first multiple of 16 past that, go to the
+    streaming kernel (attention_f16_kernel), and so does everything that shares the call; 640 tokens alone still stage.
+    Each against the f64 oracle, and each sequence the same alone and in the batch, within TOL["f16"] (the two kernels
+    accumulate in different orders: no equal bits across them)."""
+    from voitta_rag_amd import encoder as enc
+
+    shape = ro.RopeShape(1, 128, 2, 256, vocab=300, max_pos=1024, act="silu")
+    w = ro.random_weights(shape, 31)
+    rng = np.random.default_rng(32)
+    seqs = [rng.integers(0, shape.vocab, size=n).astype(np.int32) for n in (656, 9, 640)]
+    want = ro.sentence_embeddings(w, shape, seqs, "mean")
+    e = _engine(shape, "mean", "f16", w)
+    together = enc.encode(e, *_pack(seqs)).astype(np.float64)
+    _check(together, want, "f16", "656 + 9 + 640 tokens in one call")
+    for i in (0, 2):
+        alone = enc.encode(e, *_pack([seqs[i]])).astype(np.float64)
+        _check(alone, want[i:i + 1], "f16", f"{len(seqs[i])} tokens alone")
+        _check(alone, together[i:i + 1], "f16", f"{len(seqs[i])} tokens alone vs in the batch")
+    e.close()
+
+
 def test_missing_biases_are_zeros_and_the_old_description_size_loads(gpu):
     """A plain BERT whose projection biases are absent (NULL slots) equals the same BERT with zero biases, bit for bit;
     and a description that ends at `precision` (the size before the rotary / gated fields) still loads."""

@@ -735,6 +735,14 @@ enum { EPI_BIAS = 0, EPI_BIAS_GELU = 1, EPI_BIAS_RESIDUAL = 2, EPI_BIAS_F16 = 3,
        // gain-scaled INTERLEAVED matrix, then act(gate) * up of the lane's four (gate, up) column pairs, N/2 f16 columns out
        EPI_FOLD_SWIGLU = 14, EPI_FOLD_GEGLU = 15 };
 
+// Run-time epilogue id -> template argument: f(std::integral_constant<int, E>{}) for the E of the list that equals
+// `epi`. Every launcher names the epilogues its kernel is instantiated for once, in its call of this; an id outside
+// that list launches nothing and returns false, which the launcher reports as an error.
+template <int... E, class F>
+static bool with_epi(int epi, F&& f) {
+  return ((epi == E && (f(std::integral_constant<int, E>{}), true)) || ...);
+}
+
 // Linear tile id -> (row panel, column panel), row panels taken kGroupM at a time with the column
 // index slow inside a group. The ~32 blocks an XCD runs together then cover ~8 row panels x ~4
 // column panels, so both operands' working set (~4 MB per sweep of K) fits the XCD's 4-MiB L2;
@@ -886,18 +894,11 @@ static int launch_gemm(vr_engine* e, int epi, const float* A, const float* W, co
   hipStream_t s = e->stream;
   const int grid = ((M + BM - 1) / BM) * (N / BN);
   prof_begin(e, VR_PROF_GEMM, 2.0 * M * static_cast<double>(N) * K);
-  switch (epi) {
-    case EPI_BIAS:
-      hipLaunchKernelGGL((gemm_f32_kernel<EPI_BIAS>), dim3(grid), dim3(256), 0, s, A, W, bias, R, C, M, N, K);
-      break;
-    case EPI_BIAS_GELU:
-      hipLaunchKernelGGL((gemm_f32_kernel<EPI_BIAS_GELU>), dim3(grid), dim3(256), 0, s, A, W, bias, R, C, M, N, K);
-      break;
-    default:
-      hipLaunchKernelGGL((gemm_f32_kernel<EPI_BIAS_RESIDUAL>), dim3(grid), dim3(256), 0, s, A, W, bias, R, C, M, N, K);
-      break;
-  }
+  const bool known = with_epi<EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESIDUAL>(epi, [&](auto E) {
+    hipLaunchKernelGGL((gemm_f32_kernel<decltype(E)::value>), dim3(grid), dim3(256), 0, s, A, W, bias, R, C, M, N, K);
+  });
   prof_end(e);
+  VR_CHECK(known, "epilogue %d does not exist for the f32 GEMM (M=%d N=%d K=%d)", epi, M, N, K);
   VR_HIP(hipGetLastError());
   return 0;
 }
@@ -1385,7 +1386,7 @@ __global__ __launch_bounds__(512) void gemm_f16x3_256_kernel(
 }
 
 // The epilogue of the f16 kernels whose MFMAs take the WEIGHT fragment as their A operand (gemm_f16_pp_kernel,
-// gemm_f16_d2_kernel), straight from the accumulators of a wave's 128-token x 64-feature tile at token row
+// gemm_f16_mid_kernel), straight from the accumulators of a wave's 128-token x 64-feature tile at token row
 // `row0`, feature `col0`: acc[i][j][r] of lane (t = lane & 15, g = lane >> 4) is token row 16 i + t, feature 4 g + r of
 // weight fragment j — four CONSECUTIVE features of one token — and the W image was staged with its rows permuted so
 // that fragments 2p and 2p + 1 hold features 32 p + 8 g + {0..3} and {4..7}: a lane owns 8 consecutive features per
@@ -1397,55 +1398,17 @@ __global__ __launch_bounds__(512) void gemm_f16x3_256_kernel(
 // (bias, residual rows) are then merged over both paths into vmcnt(0) — and on gfx950 vmcnt counts STORES too, so every
 // store waited for the one before it: one 1 KiB store in flight per wave, the epilogue latency-bound. In straight-line
 // code the counts are exact and the stores stay in flight.
-// Diagnostic build only (make diag -> libvoitta_engine_diag.so, selected with VOITTA_ENGINE_LIB): VR_GEMM_DIAG in the
-// environment switches parts of gemm_f16_pp_kernel off at run time, so that one box can time the kernel without
-// its loads (1), its epilogue (2), its MFMAs (4), its fragment reads (8), its barriers (16), the epilogue's
-// stores (32: arithmetic only) or the epilogue's arithmetic (64: stores of the raw accumulators only). Results are then
-// wrong by construction; only the timings mean anything. The shipped library compiles none of this.
-#ifdef VR_GEMM_DIAG_BUILD
-__device__ int g_gemm_diag = 0;
-#define VR_DIAG(bit) ((diag_bits & (bit)) != 0)
-#else
-#define VR_DIAG(bit) false
-#endif
-// Stamp build (make stamps -> libvoitta_engine_stamps.so; the diag build has them too): the shipped code path plus
-// s_memtime stamps — the middle block of the grid, waves 0 and 4, six points of each of its first 16 tiles;
-// VR_GEMM_STAMPS=n in the environment prints them for the first n launches (launch_pp; scripts/pp_stamps.sh).
-#if defined(VR_GEMM_DIAG_BUILD) || defined(VR_GEMM_STAMP_BUILD)
-#define VR_GEMM_HAS_STAMPS 1
-__device__ long long g_pp_stamps[2][16][8];
-#define VR_PP_STAMP(slot)                                                                  \
-  do {                                                                                     \
-    if (stamp_on && tile_seq < 16 && (wave & 3) == 0 && lane == 0)                         \
-      g_pp_stamps[wave >> 2][tile_seq][slot] = __builtin_amdgcn_s_memtime();                \
-  } while (0)
-#else
-#define VR_PP_STAMP(slot) \
-  do {                    \
-  } while (0)
-#endif
 
 constexpr int kWaveStatHalfs = 128 * 4;  // 128 float2 per wave (direct_epilogue's row statistics), in halfs
 constexpr int kTileConstHalfs = (3 * 256 * 4 + 256 * 8) / 2;  // a tile's bias / gain / shift vectors and row statistics
 
 // Output rows are written once and read by the NEXT kernel, long after they have left the caches: non-temporal stores
 // (they do not push the weight panels and activation rows the other tiles still need out of L2). Measured +2.7 % on the
-// GEMMs and +2 % on the attention kernel that runs between them (profiles/r02_gemm_experiments.md §5);
-// -DVR_GEMM_PLAIN_STORES builds the comparison.
+// GEMMs and +2 % on the attention kernel that runs between them (profiles/r02_gemm_experiments.md §5).
 template <typename T>
 __device__ __forceinline__ void out_store(T* p, const T& v) {
-#ifdef VR_GEMM_PLAIN_STORES
-  *p = v;
-#else
   __builtin_nontemporal_store(v, p);
-#endif
 }
-
-#ifdef VR_GEMM_NO_XPOSE  // (make noxpose: the A/B twin that stores straight from the accumulators, as round 2 did)
-constexpr bool kXposeStores = false;
-#else
-constexpr bool kXposeStores = true;
-#endif
 
 template <int EPI, bool FULL, bool XPOSE = false>
 __device__ __forceinline__ void direct_epilogue(f32x4 (&acc)[8][4], int row0, int col0, int lane,
@@ -1457,9 +1420,6 @@ __device__ __forceinline__ void direct_epilogue(f32x4 (&acc)[8][4], int row0, in
                                                 int tcol0 = 0, half_t* xpose = nullptr) {
   asm volatile("" : "+v"(lane));  // (lane-derived offsets are made per tile, not carried through the K loop)
   const int tok = lane & 15, fg = lane >> 4;
-#ifdef VR_GEMM_DIAG_BUILD
-  const int diag_bits = __builtin_amdgcn_readfirstlane(g_gemm_diag);
-#endif
   const int fbase = col0 + 8 * fg;  // + 32 p (+ 4 q): this lane's features
   // FULL tiles address everything as (wave-uniform pointer) + (one 32-bit lane offset): the uniform part — row
   // 16 pc of the tile, column col0 + 32 p2 — lives in scalar registers, where per-lane 64-bit addresses of eight pieces
@@ -1603,10 +1563,6 @@ __device__ __forceinline__ void direct_epilogue(f32x4 (&acc)[8][4], int row0, in
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           float x = acc[pc][2 * p2 + q][r];
-          if (VR_DIAG(64)) {
-            v[q][r] = x;
-            continue;
-          }
           if (kFold)  // inv (acc unscale - mean colsum) + c
             x = fmaf(fmaf(x, unscale, -(st.x * gg[r])), st.y, bb[r]);
           else
@@ -1616,14 +1572,14 @@ __device__ __forceinline__ void direct_epilogue(f32x4 (&acc)[8][4], int row0, in
           v[q][r] = x;
         }
       }
-      if (kGelu && !VR_DIAG(64)) {
+      if (kGelu) {
         f32x2 g[4] = {f32x2{v[0][0], v[0][1]}, f32x2{v[0][2], v[0][3]}, f32x2{v[1][0], v[1][1]}, f32x2{v[1][2], v[1][3]}};
         gelu_poly2x4(g);
 #pragma unroll
         for (int q = 0; q < 2; ++q)
           v[q][0] = g[2 * q].x, v[q][1] = g[2 * q].y, v[q][2] = g[2 * q + 1].x, v[q][3] = g[2 * q + 1].y;
       }
-      if (kGlu && !VR_DIAG(64)) {
+      if (kGlu) {
         // the lane's eight columns are four (gate, up) pairs of the interleaved matrix: four f16 outputs at column c0 / 2
         // of a row of N / 2, one 8-byte store (the four lanes of a token write 32 contiguous bytes)
         constexpr int kFfn = EPI == EPI_FOLD_SWIGLU ? VR_FFN_SWIGLU : VR_FFN_GEGLU;
@@ -1647,9 +1603,7 @@ __device__ __forceinline__ void direct_epilogue(f32x4 (&acc)[8][4], int row0, in
           h[r] = static_cast<half_t>(fminf(fmaxf(v[0][r], -65504.0f), 65504.0f));
           h[4 + r] = static_cast<half_t>(fminf(fmaxf(v[1][r], -65504.0f), 65504.0f));
         }
-        if (VR_DIAG(32)) {
-          if (h[0] == static_cast<half_t>(123.0f) && h[7] == static_cast<half_t>(77.0f)) Ch[0] = h[3];  // (keeps the arithmetic alive)
-        } else if (XPOSE) {
+        if (XPOSE) {
           half_t* slot = xpose + ((8 * p2 + pc) & 3) * 512;
           *reinterpret_cast<f16x8*>(slot + xw) = h;
           asm volatile("" ::: "memory");
@@ -1714,7 +1668,7 @@ __device__ __forceinline__ void direct_epilogue(f32x4 (&acc)[8][4], int row0, in
 
 // Whole tiles of the f16-output projections without residual rows (QKV, FFN-up: four fifths of the bytes the GEMMs write),
 // gemm_f16_pp_kernel only. Same arithmetic per element as direct_epilogue (same bits); what differs is the ORDER of things.
-// In-kernel stamps (make diag, VR_GEMM_DIAG=128, scripts/pp_stamps.sh) showed direct_epilogue's whole-tile path at 9-10k
+// In-kernel time stamps (profiles/r03_experiments.md) showed direct_epilogue's whole-tile path at 9-10k
 // cycles per tile for the QKV variant with its arithmetic switched off as well as on, against 5.4k for the arithmetic
 // alone: every 16-token piece ended in an LDS round trip (lane exchange in front of the store, see direct_epilogue) and
 // began with one (row statistics) that nothing covered — one basic block per piece, lgkmcnt(0) at every block entry.
@@ -2038,7 +1992,7 @@ __global__ __launch_bounds__(512) void gemm_f16_pp_kernel(
   // has left beside its staging state; those keep the predicated form and their global loads)
   constexpr bool kBranchFree = EPI != EPI_BIAS_RESIDUAL_LN && EPI != EPI_BIAS_RESIDUAL_LN_STATS && EPI != EPI_RLS_R32_O16 &&
                                EPI != EPI_RLS_R16_O16 && EPI != EPI_RLS_R16_O32;
-  constexpr bool kRlsTile = kXposeStores && EPI == EPI_RLS_R16_O16;  // whole tiles: rls16_tile_epilogue
+  constexpr bool kRlsTile = EPI == EPI_RLS_R16_O16;  // whole tiles: rls16_tile_epilogue
   auto issue_tile_consts = [&](int bm_, int bn_) {
     // edge tiles read them from global memory (predicated epilogue) — except a last column tile that ends on a 64-column
     // boundary (N = 384, 1152: the waves behind the edge have nothing to store, the others run the whole-tile epilogue)
@@ -2109,24 +2063,11 @@ __global__ __launch_bounds__(512) void gemm_f16_pp_kernel(
   f32x4 acc[8][4];
 
   const int nk = K / 64;  // even
-#ifdef VR_GEMM_DIAG_BUILD
-  const int diag_bits = __builtin_amdgcn_readfirstlane(g_gemm_diag);
-#endif
-#ifdef VR_GEMM_HAS_STAMPS
-  const bool stamp_on = static_cast<int>(blockIdx.x) == G / 2;
-  int tile_seq = 0;
-#endif
-#define VR_PP_BARRIER()                                      \
-  do {                                                       \
-    __builtin_amdgcn_sched_barrier(0);                       \
-    if (!VR_DIAG(16)) __builtin_amdgcn_s_barrier();          \
-    __builtin_amdgcn_sched_barrier(0);                       \
-  } while (0)
-#define VR_PP_HARD_BARRIER()                 \
-  do {                                       \
-    __builtin_amdgcn_sched_barrier(0);       \
-    __builtin_amdgcn_s_barrier();            \
-    __builtin_amdgcn_sched_barrier(0);       \
+#define VR_PP_BARRIER()                 \
+  do {                                  \
+    __builtin_amdgcn_sched_barrier(0);  \
+    __builtin_amdgcn_s_barrier();       \
+    __builtin_amdgcn_sched_barrier(0);  \
   } while (0)
 #define VR_PP_VMCNT4() asm volatile("s_waitcnt vmcnt(4)" ::: "memory")
   // Epilogues that issue a known number of stores and no global loads (whole tiles of the branch-free f16-output variants:
@@ -2134,8 +2075,8 @@ __global__ __launch_bounds__(512) void gemm_f16_pp_kernel(
   // in the last two phases of the K loop) are NOT waited for before the epilogue — their latency runs under its arithmetic —
   // but by counted waits in the first two phases of the next K loop that let exactly the younger operations (A hi where
   // it applies, the kEpiStores stores, the phase's own loads) stay in flight. Every other epilogue drains vmcnt first.
-  constexpr bool kTileEpilogue = kXposeStores && (EPI == EPI_FOLD_F16 || EPI == EPI_FOLD_GELU || EPI == EPI_BIAS_F16 || EPI == EPI_BIAS_GELU);
-  constexpr int kEpiStores = (kXposeStores && (EPI == EPI_FOLD_F16 || EPI == EPI_FOLD_GELU || EPI == EPI_BIAS_F16 || EPI == EPI_BIAS_GELU)) ? 16 : -1;
+  constexpr bool kTileEpilogue = EPI == EPI_FOLD_F16 || EPI == EPI_FOLD_GELU || EPI == EPI_BIAS_F16 || EPI == EPI_BIAS_GELU;
+  constexpr int kEpiStores = kTileEpilogue ? 16 : -1;
   bool counted_tail = false;  // block-uniform: the previous tile's epilogue left W hi / A hi to the counted waits
 #define VR_PP_VMCNT_TAIL() asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kEpiStores > 0 ? kEpiStores + 4 : 0) : "memory")
 
@@ -2156,7 +2097,6 @@ __global__ __launch_bounds__(512) void gemm_f16_pp_kernel(
     const int next = tile + G;
     const bool has_next = next < total;
     int nbm = bm, nbn = bn;
-    VR_PP_STAMP(0);
 
     // one K-tile out of stage buffer B; the next K-tile (or K-tile 0 of the next tile, or — at the very
     // end — a harmless re-load) goes into buffer B ^ 1
@@ -2172,23 +2112,19 @@ __global__ __launch_bounds__(512) void gemm_f16_pp_kernel(
       if (lastk && has_next) set_ptrs(nbm, nbn);
       const int koff = lastk ? 0 : (kt + 1) * 64;
       f16x8 af[4][2], bf[2][2];
-#ifdef VR_GEMM_DIAG_BUILD
-      for (int i = 0; i < 4; ++i) af[i][0] = af[i][1] = f16x8{1, 1, 1, 1, 1, 1, 1, 1};
-      for (int j = 0; j < 2; ++j) bf[j][0] = bf[j][1] = f16x8{1, 1, 1, 1, 1, 1, 1, 1};
-#endif
       // ---- phase 0: quadrant rows 0-63 x columns 0-31 ------------------------------------------------
       if (kt == 0) issue_tile_consts(bm, bn);  // (older than every load the counted waits below reason about)
-      if (!VR_DIAG(1)) glds16(g_a0 + koff, nd + da0);
-      if (!VR_DIAG(1)) glds16(g_a1 + koff, nd + da1);
+      glds16(g_a0 + koff, nd + da0);
+      glds16(g_a1 + koff, nd + da1);
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
-        if (!VR_DIAG(8)) bf[j][0] = *reinterpret_cast<const f16x8*>(st + pw + j * 16 * 64 + fk0);
-        if (!VR_DIAG(8)) bf[j][1] = *reinterpret_cast<const f16x8*>(st + pw + j * 16 * 64 + fk1);
+        bf[j][0] = *reinterpret_cast<const f16x8*>(st + pw + j * 16 * 64 + fk0);
+        bf[j][1] = *reinterpret_cast<const f16x8*>(st + pw + j * 16 * 64 + fk1);
       }
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        if (!VR_DIAG(8)) af[i][0] = *reinterpret_cast<const f16x8*>(st + pa + i * 16 * 64 + fk0);
-        if (!VR_DIAG(8)) af[i][1] = *reinterpret_cast<const f16x8*>(st + pa + i * 16 * 64 + fk1);
+        af[i][0] = *reinterpret_cast<const f16x8*>(st + pa + i * 16 * 64 + fk0);
+        af[i][1] = *reinterpret_cast<const f16x8*>(st + pa + i * 16 * 64 + fk1);
       }
       if (kt != 0) VR_PP_VMCNT4();  // W hi of this K-tile has landed (K-tile 0: waited for whole, or by the counted tail)
       else if (kEpiStores > 0 && counted_tail) VR_PP_VMCNT_TAIL();  // younger: A hi, the stores, this phase's two loads
@@ -2200,16 +2136,16 @@ __global__ __launch_bounds__(512) void gemm_f16_pp_kernel(
         for (int i = 0; i < 4; ++i)
 #pragma unroll
           for (int j = 0; j < 2; ++j)
-            if (!VR_DIAG(4)) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bf[j][kk], af[i][kk], (FIRST && kk == 0) ? zero4 : acc[i][j], 0, 0, 0);
+            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bf[j][kk], af[i][kk], (FIRST && kk == 0) ? zero4 : acc[i][j], 0, 0, 0);
       __builtin_amdgcn_s_setprio(0);
       VR_PP_BARRIER();
       // ---- phase 1: rows 0-63 x columns 32-63 ---------------------------------------------------------
-      if (!VR_DIAG(1)) glds16(g_w0 + koff, nd + dw0);
-      if (!VR_DIAG(1)) glds16(g_w1 + koff, nd + dw1);
+      glds16(g_w0 + koff, nd + dw0);
+      glds16(g_w1 + koff, nd + dw1);
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
-        if (!VR_DIAG(8)) bf[j][0] = *reinterpret_cast<const f16x8*>(st + pw + (2 + j) * 16 * 64 + fk0);
-        if (!VR_DIAG(8)) bf[j][1] = *reinterpret_cast<const f16x8*>(st + pw + (2 + j) * 16 * 64 + fk1);
+        bf[j][0] = *reinterpret_cast<const f16x8*>(st + pw + (2 + j) * 16 * 64 + fk0);
+        bf[j][1] = *reinterpret_cast<const f16x8*>(st + pw + (2 + j) * 16 * 64 + fk1);
       }
       if (kt != 0) VR_PP_VMCNT4();  // A hi of this K-tile has landed
       else if (kEpiStores > 0 && counted_tail) VR_PP_VMCNT_TAIL();  // younger: the stores, the loads of phases 0 and 1
@@ -2221,16 +2157,16 @@ __global__ __launch_bounds__(512) void gemm_f16_pp_kernel(
         for (int i = 0; i < 4; ++i)
 #pragma unroll
           for (int j = 0; j < 2; ++j)
-            if (!VR_DIAG(4)) acc[i][2 + j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bf[j][kk], af[i][kk], (FIRST && kk == 0) ? zero4 : acc[i][2 + j], 0, 0, 0);
+            acc[i][2 + j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bf[j][kk], af[i][kk], (FIRST && kk == 0) ? zero4 : acc[i][2 + j], 0, 0, 0);
       __builtin_amdgcn_s_setprio(0);
       VR_PP_BARRIER();
       // ---- phase 2: rows 64-127 x columns 32-63 -------------------------------------------------------
-      if (!VR_DIAG(1)) glds16(g_w2 + koff, nd + dw2);
-      if (!VR_DIAG(1)) glds16(g_w3 + koff, nd + dw3);
+      glds16(g_w2 + koff, nd + dw2);
+      glds16(g_w3 + koff, nd + dw3);
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        if (!VR_DIAG(8)) af[i][0] = *reinterpret_cast<const f16x8*>(st + pa + (4 + i) * 16 * 64 + fk0);
-        if (!VR_DIAG(8)) af[i][1] = *reinterpret_cast<const f16x8*>(st + pa + (4 + i) * 16 * 64 + fk1);
+        af[i][0] = *reinterpret_cast<const f16x8*>(st + pa + (4 + i) * 16 * 64 + fk0);
+        af[i][1] = *reinterpret_cast<const f16x8*>(st + pa + (4 + i) * 16 * 64 + fk1);
       }
       VR_PP_BARRIER();
       __builtin_amdgcn_s_setprio(1);
@@ -2240,21 +2176,19 @@ __global__ __launch_bounds__(512) void gemm_f16_pp_kernel(
         for (int i = 0; i < 4; ++i)
 #pragma unroll
           for (int j = 0; j < 2; ++j)
-            if (!VR_DIAG(4)) acc[4 + i][2 + j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bf[j][kk], af[i][kk], (FIRST && kk == 0) ? zero4 : acc[4 + i][2 + j], 0, 0, 0);
+            acc[4 + i][2 + j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bf[j][kk], af[i][kk], (FIRST && kk == 0) ? zero4 : acc[4 + i][2 + j], 0, 0, 0);
       __builtin_amdgcn_s_setprio(0);
       VR_PP_BARRIER();
       // ---- phase 3: rows 64-127 x columns 0-31 (W fragments read again: holding them costs 16 VGPRs) ----
-      if (!VR_DIAG(1)) glds16(g_a2 + koff, nd + da2);
-      if (!VR_DIAG(1)) glds16(g_a3 + koff, nd + da3);
+      glds16(g_a2 + koff, nd + da2);
+      glds16(g_a3 + koff, nd + da3);
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
-        if (!VR_DIAG(8)) bf[j][0] = *reinterpret_cast<const f16x8*>(st + pw + j * 16 * 64 + fk0);
-        if (!VR_DIAG(8)) bf[j][1] = *reinterpret_cast<const f16x8*>(st + pw + j * 16 * 64 + fk1);
+        bf[j][0] = *reinterpret_cast<const f16x8*>(st + pw + j * 16 * 64 + fk0);
+        bf[j][1] = *reinterpret_cast<const f16x8*>(st + pw + j * 16 * 64 + fk1);
       }
       VR_PP_VMCNT4();  // A lo and W lo of the next K-tile have landed; W hi and A hi stay in flight
       VR_PP_BARRIER();
-      if (kt == 0) VR_PP_STAMP(1);
-      if (kt == 1) VR_PP_STAMP(6);
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int kk = 0; kk < 2; ++kk)
@@ -2262,7 +2196,7 @@ __global__ __launch_bounds__(512) void gemm_f16_pp_kernel(
         for (int i = 0; i < 4; ++i)
 #pragma unroll
           for (int j = 0; j < 2; ++j)
-            if (!VR_DIAG(4)) acc[4 + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bf[j][kk], af[i][kk], (FIRST && kk == 0) ? zero4 : acc[4 + i][j], 0, 0, 0);
+            acc[4 + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bf[j][kk], af[i][kk], (FIRST && kk == 0) ? zero4 : acc[4 + i][j], 0, 0, 0);
       __builtin_amdgcn_s_setprio(0);
       VR_PP_BARRIER();
     };
@@ -2280,7 +2214,6 @@ __global__ __launch_bounds__(512) void gemm_f16_pp_kernel(
     // waves 0-3 are a segment ahead: they wait here for waves 4-7's last MFMA segment, so that all eight waves
     // run the epilogue TOGETHER (one half after the other costs 13 %: each wave's epilogue is bound by the latency of
     // its own loads, and the two waves of a SIMD hide each other's — profiles/r02_gemm_experiments.md §4)
-    VR_PP_STAMP(2);
     if (wm == 0) VR_PP_BARRIER();
     // Epilogue, straight from the accumulators (direct_epilogue).
     // W hi / A hi of the next tile's K-tile 0 may still be in flight: waited for HERE, before this wave's
@@ -2289,34 +2222,22 @@ __global__ __launch_bounds__(512) void gemm_f16_pp_kernel(
     // whole tile, or a last column tile that ends on a 64-column boundary: every wave's 64 columns are in or out as a whole
     const bool whole_tile = bm + GBM <= M && (bn + GBN <= N || N % 64 == 0);  // block-uniform
     const bool no_columns = bn + wn * 64 >= N;                                // wave-uniform: nothing to store
-    counted_tail = kEpiStores > 0 && whole_tile && !VR_DIAG(2) && !VR_DIAG(32);
+    counted_tail = kEpiStores > 0 && whole_tile;
     if (!counted_tail) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    VR_PP_STAMP(3);
-    if (!VR_DIAG(2)) {
     if (whole_tile && no_columns)
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the counted waits of the next K loop assume this wave's stores)
-    else if (kTileEpilogue && whole_tile && !VR_DIAG(32) && !VR_DIAG(64))
+    else if (kTileEpilogue && whole_tile)
       f16_tile_epilogue<EPI>(acc, bm + wm * 128, bn + wn * 64, lane, Ch, M, N, unscale, reinterpret_cast<const float*>(tile_const_h),
                              wm * 128, wn * 64, xpose);
-    else if (kRlsTile && whole_tile && !VR_DIAG(32) && !VR_DIAG(64))
+    else if (kRlsTile && whole_tile)
       rls16_tile_epilogue(acc, bm + wm * 128, bn + wn * 64, lane, reinterpret_cast<const half_t*>(R), Ch, Cl, M, N, unscale,
                           reinterpret_cast<const float*>(tile_const_h), wm * 128, wn * 64, xpose, xspare);
     else if (kBranchFree && whole_tile)
-      direct_epilogue<EPI, true, kXposeStores>(acc, bm + wm * 128, bn + wn * 64, lane, bias, R, C, Ch, Cl, M, N, unscale, ln_stat, ln_g, ln_b, wave_stat,
+      direct_epilogue<EPI, true, true>(acc, bm + wm * 128, bn + wn * 64, lane, bias, R, C, Ch, Cl, M, N, unscale, ln_stat, ln_g, ln_b, wave_stat,
                                  reinterpret_cast<const float*>(tile_const_h), wm * 128, wn * 64, xpose);
     else
-      direct_epilogue<EPI, false, kXposeStores && !kRlsTile>(acc, bm + wm * 128, bn + wn * 64, lane, bias, R, C, Ch, Cl, M, N, unscale, ln_stat, ln_g, ln_b, wave_stat,
+      direct_epilogue<EPI, false, !kRlsTile>(acc, bm + wm * 128, bn + wn * 64, lane, bias, R, C, Ch, Cl, M, N, unscale, ln_stat, ln_g, ln_b, wave_stat,
                                   nullptr, 0, 0, xpose);
-    } else if (acc[0][0][0] == 12345.678f && acc[7][3][3] == 1.0f) {  // (diagnostic) keep the accumulators alive
-      float t = 0.0f;
-      for (int i = 0; i < 8; ++i)
-        for (int j = 0; j < 4; ++j) t += acc[i][j][0] + acc[i][j][1] + acc[i][j][2] + acc[i][j][3];
-      C[0] = t;
-    }
-    VR_PP_STAMP(4);
-#ifdef VR_GEMM_HAS_STAMPS
-    ++tile_seq;
-#endif
     if (!has_next) break;
     tile = next;
     bm = nbm;
@@ -2338,50 +2259,42 @@ __global__ __launch_bounds__(512) void gemm_f16_pp_kernel(
 #undef VR_PP_VMCNT_TAIL
 }
 
-// ---- the f16 product as TWO INDEPENDENT 256x128 tiles per CU ----------------------------------------------
+// ---- the f16 product for mid-size M: 128x128 tiles, three blocks per CU ------------------------------------
 //
-// gemm_f16_pp_kernel owns a CU alone (128 KiB of LDS, 8 waves): while its eight waves run the epilogue — at
-// K = 768 the 128 KiB an output tile writes are a third of the tile's time, bound by the CU's store path —
-// the matrix pipes idle, and while they multiply the store path idles. Here a block is FOUR waves (one per
-// SIMD) on a 256-token x 128-feature tile with 72 KiB of LDS, so two blocks share a CU: they are dispatched
-// independently and drift apart, and while one stores its tile the other has the matrix pipes to itself.
-// Inside the K loop the two blocks' waves of a SIMD interleave the way the ping-pong halves do: one reads
-// fragments or waits at its block's barrier while the other multiplies.
-//   * K advances in steps of 32 through a ring of THREE stage buffers (A 256 x 32 + W 128 x 32 halfs = 24 KiB):
+// gemm_f16_pp_kernel owns a CU alone (128 KiB of LDS, 8 waves) and walks 256x256 tiles: at 1.6k tokens and N = 768
+// those number 7 x 3 = 21 for 256 CUs. Here (256 < M, a batch of questions or one file's chunks: mid_usable) a block
+// is TWO waves on a 128-token x 128-feature tile with 48 KiB of stages, three blocks per CU: 13 x 6 = 78 tiles.
+//   * K advances in steps of 32 through a ring of THREE stage buffers (A 128 x 32 + W 128 x 32 halfs = 16 KiB):
 //     step s multiplies out of stage s % 3 while the loads of steps s + 1 and s + 2 are in flight — one
-//     counted vmcnt(6) and one barrier per step (every wave issues 6 direct-to-LDS loads per step);
+//     counted vmcnt(8) and one barrier per step (every wave issues 4 + 4 direct-to-LDS loads per step);
 //   * rows are 64 bytes in LDS; 16-byte chunk c of row r sits at chunk c ^ ((r >> 1) & 3) (source-side swizzle of
 //     the direct-to-LDS loads), which makes the ds_read_b128 fragment reads conflict-free;
 //   * same wave tile (128 x 64), fragment roles, W row permutation and accumulation order (k ascending) as
 //     gemm_f16_pp_kernel: the result is bit-identical to it, and the epilogue is the same code (direct_epilogue).
 // One tile per block, no persistence: consecutive blocks of an XCD (blockIdx % 8) take the column tiles of one
-// 256-row panel one after the other, so a panel of A is read from HBM once and then from that XCD's L2.
-//
-// The MID-SIZE instantiation (WM = 1, gemm_f16_mid: 256 < M, a batch of questions or one file's chunks) is the same
-// kernel on a 128-token x 128-feature tile: TWO waves (one row of wave tiles), 48 KiB of stages, three blocks per CU.
-// At 1.6k tokens and N = 768 the 256x256 ping-pong tiles number 7 x 3 = 21 for 256 CUs; these number 13 x 6 = 78. Every
-// wave tile, fragment, K order and epilogue is the one above, so its bits are gemm_f16_pp_kernel's too.
-constexpr int D2N = 128, D2K = 32;  // (stages: 24 KiB; WM = 1: 16 KiB)
-template <int WM> constexpr int d2_rows() { return 128 * WM; }
-template <int WM> constexpr int d2_stage_halfs() { return (d2_rows<WM>() + D2N) * D2K; }
+// 128-row panel one after the other, so a panel of A is read from HBM once and then from that XCD's L2.
+// (The same loop on 256x128 tiles, four waves and two blocks per CU, was tried as a replacement for the ping-pong
+// kernel and lost, 750 against 930 TFLOP/s: profiles/r02_gemm_experiments.md)
+constexpr int kMidM = 128, kMidN = 128, kMidK = 32;
+constexpr int kMidStageHalfs = (kMidM + kMidN) * kMidK;
 
-template <int EPI, int WM = 2>
-__global__ __launch_bounds__(128 * WM, 2) void gemm_f16_d2_kernel(
+template <int EPI>
+__global__ __launch_bounds__(128, 2) void gemm_f16_mid_kernel(
     const half_t* __restrict__ Ah, const half_t* __restrict__ Wh, const float* __restrict__ bias,
     const float* __restrict__ R, float* __restrict__ C, half_t* __restrict__ Ch, half_t* __restrict__ Cl, int M,
     int N, int K, float unscale, const float2* __restrict__ ln_stat, const float* __restrict__ ln_g,
     const float* __restrict__ ln_b) {
-  constexpr int NW = 2 * WM;                       // waves: WM rows x 2 columns of 128 x 64 wave tiles
-  constexpr int TM = d2_rows<WM>();                // token rows of the block tile
-  constexpr int kStage = d2_stage_halfs<WM>();
+  constexpr int NW = 2;                            // waves: one row of two 128 x 64 wave tiles
+  constexpr int TM = kMidM;                        // token rows of the block tile
+  constexpr int kStage = kMidStageHalfs;
   constexpr int kLoadsW = 8 / NW;                  // W image loads per wave and step (A: always 4)
   __shared__ half_t lds[3 * kStage + NW * kWaveStatHalfs];  // the only LDS object (see gemm_f16x3_256_kernel)
-  const int tiles_n = (N + D2N - 1) / D2N;
+  const int tiles_n = (N + kMidN - 1) / kMidN;
   const int tiles_m = (M + TM - 1) / TM;
   const int xcd = static_cast<int>(blockIdx.x) & 7, seq = static_cast<int>(blockIdx.x) >> 3;
   const int panel = (seq / tiles_n) * 8 + xcd;
   if (panel >= tiles_m) return;  // block-uniform (the grid is padded to a multiple of 8 panels)
-  const int bm = panel * TM, bn = (seq % tiles_n) * D2N;
+  const int bm = panel * TM, bn = (seq % tiles_n) * kMidN;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -2405,8 +2318,8 @@ __global__ __launch_bounds__(128 * WM, 2) void gemm_f16_d2_kernel(
     const int wrow = (img & ~31) + 8 * (srow >> 2) + 4 * ((img >> 4) & 1) + (srow & 3);
     g_w[t] = Wh + static_cast<int64_t>(min(bn + wrow, N - 1)) * K + schunk;
   }
-  const int da = wave * 16 * D2K;               // + NW t * 16 * D2K
-  const int dw = TM * D2K + wave * 16 * D2K;    // + NW t * 16 * D2K
+  const int da = wave * 16 * kMidK;               // + NW t * 16 * kMidK
+  const int dw = TM * kMidK + wave * 16 * kMidK;    // + NW t * 16 * kMidK
 
   f32x4 acc[8][4];
 #pragma unroll
@@ -2416,14 +2329,11 @@ __global__ __launch_bounds__(128 * WM, 2) void gemm_f16_d2_kernel(
   // fragments (v_mfma_f32_16x16x32_f16): lane l supplies row (l & 15), k = 8 (l >> 4) + j of the 32-deep step
   const int frow = lane & 15;
   const int fk = ((lane >> 4) ^ ((frow >> 1) & 3)) * 8;
-  const int pa = (wm * 128 + frow) * D2K + fk;
-  const int pw = TM * D2K + (wn * 64 + frow) * D2K + fk;
-  const int nk = K / D2K;
-#ifdef VR_GEMM_DIAG_BUILD
-  const int diag_bits = __builtin_amdgcn_readfirstlane(g_gemm_diag);
-#endif
+  const int pa = (wm * 128 + frow) * kMidK + fk;
+  const int pw = TM * kMidK + (wn * 64 + frow) * kMidK + fk;
+  const int nk = K / kMidK;
 
-#define VR_D2_BARRIER()                   \
+#define VR_MID_BARRIER()                   \
   do {                                    \
     __builtin_amdgcn_sched_barrier(0);    \
     __builtin_amdgcn_s_barrier();         \
@@ -2431,12 +2341,12 @@ __global__ __launch_bounds__(128 * WM, 2) void gemm_f16_d2_kernel(
   } while (0)
   auto issue = [&](half_t* stage, int k0) {
 #pragma unroll
-    for (int t = 0; t < 4; ++t) glds16(g_a[t] + k0, stage + da + t * NW * 16 * D2K);
+    for (int t = 0; t < 4; ++t) glds16(g_a[t] + k0, stage + da + t * NW * 16 * kMidK);
 #pragma unroll
-    for (int t = 0; t < kLoadsW; ++t) glds16(g_w[t] + k0, stage + dw + t * NW * 16 * D2K);
+    for (int t = 0; t < kLoadsW; ++t) glds16(g_w[t] + k0, stage + dw + t * NW * 16 * kMidK);
   };
   issue(lds, 0);
-  if (nk > 1) issue(lds + kStage, D2K);
+  if (nk > 1) issue(lds + kStage, kMidK);
 
   auto step = [&](auto bsel, int s) {
     constexpr int B = decltype(bsel)::value;
@@ -2444,32 +2354,26 @@ __global__ __launch_bounds__(128 * WM, 2) void gemm_f16_d2_kernel(
     half_t* nd = lds + ((B + 2) % 3) * kStage;
     // the loads of step s have landed (those of step s + 1, if any, stay in flight) ...
     if (s + 1 < nk) {
-      if constexpr (kLoadsW == 2)
-        asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-      else
-        asm volatile("s_waitcnt vmcnt(8)" ::: "memory");  // (WM = 1: 4 + 4 loads per wave and step)
+      asm volatile("s_waitcnt vmcnt(8)" ::: "memory");  // (4 + 4 loads per wave and step)
     } else
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    VR_D2_BARRIER();  // ... every wave's; and every wave has finished with stage (s - 1) % 3 = (s + 2) % 3
-    if (s + 2 < nk && !VR_DIAG(1)) issue(nd, (s + 2) * D2K);
+    VR_MID_BARRIER();  // ... every wave's; and every wave has finished with stage (s - 1) % 3 = (s + 2) % 3
+    if (s + 2 < nk) issue(nd, (s + 2) * kMidK);
     f16x8 af[4], bf[4];  // token rows in two halves of 64: holding all eight fragments did not fit beside acc
-#ifdef VR_GEMM_DIAG_BUILD
-    for (int i = 0; i < 4; ++i) af[i] = bf[i] = f16x8{1, 1, 1, 1, 1, 1, 1, 1};
-#endif
 #pragma unroll
     for (int j = 0; j < 4; ++j)
-      if (!VR_DIAG(8)) bf[j] = *reinterpret_cast<const f16x8*>(st + pw + j * 16 * D2K);
+      bf[j] = *reinterpret_cast<const f16x8*>(st + pw + j * 16 * kMidK);
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
 #pragma unroll
       for (int i = 0; i < 4; ++i)
-        if (!VR_DIAG(8)) af[i] = *reinterpret_cast<const f16x8*>(st + pa + (4 * h + i) * 16 * D2K);
+        af[i] = *reinterpret_cast<const f16x8*>(st + pa + (4 * h + i) * 16 * kMidK);
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-          if (!VR_DIAG(4)) acc[4 * h + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bf[j], af[i], acc[4 * h + i][j], 0, 0, 0);
+          acc[4 * h + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bf[j], af[i], acc[4 * h + i][j], 0, 0, 0);
       __builtin_amdgcn_s_setprio(0);
     }
   };
@@ -2482,13 +2386,9 @@ __global__ __launch_bounds__(128 * WM, 2) void gemm_f16_d2_kernel(
   }
   if (s < nk) step(std::integral_constant<int, 0>{}, s);
   if (s + 1 < nk) step(std::integral_constant<int, 1>{}, s + 1);
-#undef VR_D2_BARRIER
-  if (VR_DIAG(2)) {
-    if (acc[0][0][0] == 12345.678f && acc[7][3][3] == 1.0f) C[0] = acc[3][1][2];  // (diagnostic) keep the accumulators alive
-    return;
-  }
+#undef VR_MID_BARRIER
   // (EPI_RLS_R32_O16 — layer 0 only — holds two pieces of f32 residual rows: four registers too many without branches)
-  if (EPI != EPI_RLS_R32_O16 && bm + TM <= M && bn + D2N <= N)  // block-uniform
+  if (EPI != EPI_RLS_R32_O16 && bm + TM <= M && bn + kMidN <= N)  // block-uniform
     direct_epilogue<EPI, true>(acc, bm + wm * 128, bn + wn * 64, lane, bias, R, C, Ch, Cl, M, N, unscale, ln_stat, ln_g, ln_b, wave_stat);
   else
     direct_epilogue<EPI, false>(acc, bm + wm * 128, bn + wn * 64, lane, bias, R, C, Ch, Cl, M, N, unscale, ln_stat, ln_g, ln_b, wave_stat);
@@ -2736,146 +2636,76 @@ __global__ void split_weights_kernel(const float* __restrict__ w, int64_t n, int
   }
 }
 
+// One product C = A W^T * unscale + bias (+ epilogue) as launch_gemm_f16x3 and the launchers behind it take it: a call
+// site names the fields its epilogue uses, the rest stay null.
+struct GemmArgs {
+  const half_t *A = nullptr, *A_lo = nullptr;  // activation rows; passes = 3: interleaved (hi, lo) rows, A_lo = A + 8
+  SplitWeight W{};                             // [N][K] weights (lo: passes = 3 only) and their 2^-s
+  const float* bias = nullptr;
+  const float* R = nullptr;                    // residual rows (EPI_RLS_R16_*: f16 rows behind this pointer)
+  float* C = nullptr;                          // f32 output rows
+  half_t *Ch = nullptr, *Cl = nullptr;         // f16 output rows (hi, lo); *_STATS / EPI_RLS_*: Cl = the rows' partial sums
+  int M = 0, N = 0, K = 0;
+  int passes = 3;                              // 3: (hi, lo) operands, three MFMA passes; 1: plain f16 rows
+  const float2* ln_stat = nullptr;             // per row (mean, 1/sigma) of the LayerNorm an epilogue applies,
+  const float *ln_g = nullptr, *ln_b = nullptr;  // its gain (EPI_FOLD_*: the column sums) and shift
+  const float2* rope_tab = nullptr;            // EPI_ROPE_F16: the cos/sin table and the rows' positions
+  const int32_t* rope_pos = nullptr;
+};
+
+// the kernels whose epilogue is direct_epilogue (gemm_f16_mid_kernel, gemm_f16_pp_kernel) exist for these
+#define VR_DIRECT_EPIS                                                                                          \
+  EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESIDUAL, EPI_BIAS_F16, EPI_BIAS_RESIDUAL_LN, EPI_FOLD_F16, EPI_FOLD_GELU,  \
+      EPI_FOLD_SWIGLU, EPI_FOLD_GEGLU, EPI_BIAS_RESIDUAL_LN_STATS, EPI_RLS_R32_O16, EPI_RLS_R16_O16, EPI_RLS_R16_O32
+
+// (the launch_* below return false for an epilogue their kernel does not exist for: launch_gemm_f16x3 reports it)
 template <int PASSES>
-static void launch_256(int epi, int grid, hipStream_t s, const half_t* Ah, const half_t* Al, const half_t* Wh,
-                       const half_t* Wl, const float* bias, const float* R, float* C, half_t* Ch, half_t* Cl, int M,
-                       int N, int K, float unscale, const float2* ln_stat, const float* ln_g, const float* ln_b) {
-#define VR_LAUNCH_256(E)                                                                                         \
-  hipLaunchKernelGGL((gemm_f16x3_256_kernel<E, PASSES>), dim3(grid), dim3(512), 0, s, Ah, Al, Wh, Wl, bias, R, C, \
-                     Ch, Cl, M, N, K, unscale, ln_stat, ln_g, ln_b)
-  switch (epi) {
-    case EPI_BIAS: VR_LAUNCH_256(EPI_BIAS); break;
-    case EPI_BIAS_GELU: VR_LAUNCH_256(EPI_BIAS_GELU); break;
-    case EPI_BIAS_F16: VR_LAUNCH_256(EPI_BIAS_F16); break;
-    case EPI_BIAS_RESIDUAL_LN: VR_LAUNCH_256(EPI_BIAS_RESIDUAL_LN); break;
-    case EPI_FOLD_F16: if constexpr (PASSES == 1) VR_LAUNCH_256(EPI_FOLD_F16); break;
-    case EPI_FOLD_GELU: if constexpr (PASSES == 1) VR_LAUNCH_256(EPI_FOLD_GELU); break;
-    case EPI_BIAS_RESIDUAL_LN_STATS: if constexpr (PASSES == 1) VR_LAUNCH_256(EPI_BIAS_RESIDUAL_LN_STATS); break;
-    default: VR_LAUNCH_256(EPI_BIAS_RESIDUAL); break;
-  }
-#undef VR_LAUNCH_256
+static bool launch_256(int epi, int grid, hipStream_t s, const GemmArgs& g) {
+  auto launch = [&](auto E) {
+    hipLaunchKernelGGL((gemm_f16x3_256_kernel<decltype(E)::value, PASSES>), dim3(grid), dim3(512), 0, s, g.A, g.A_lo, g.W.hi,
+                       g.W.lo, g.bias, g.R, g.C, g.Ch, g.Cl, g.M, g.N, g.K, g.W.unscale, g.ln_stat, g.ln_g, g.ln_b);
+  };
+  if constexpr (PASSES == 1)  // the EPI_FOLD_* / *_STATS variants exist for plain f16 operands only
+    return with_epi<EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESIDUAL, EPI_BIAS_F16, EPI_BIAS_RESIDUAL_LN, EPI_FOLD_F16,
+                    EPI_FOLD_GELU, EPI_BIAS_RESIDUAL_LN_STATS>(epi, launch);
+  else
+    return with_epi<EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESIDUAL, EPI_BIAS_F16, EPI_BIAS_RESIDUAL_LN>(epi, launch);
 }
 
 // the ping-pong kernel serves the f16 mode when K is whole pairs of 64-deep K-tiles and a lane's 8 features are in
-// or out of N together; VR_GEMM_PP=0 keeps the one-barrier-per-K-tile loop (A/B runs)
-static bool pp_usable(int N, int K) {
-  static const bool pp_on = !(getenv("VR_GEMM_PP") && atoi(getenv("VR_GEMM_PP")) == 0);
-  return pp_on && K % 128 == 0 && N % 8 == 0;
-}
+// or out of N together
+static bool pp_usable(int N, int K) { return K % 128 == 0 && N % 8 == 0; }
 
-// gemm_f16_d2_kernel: any K that is a multiple of 32 (the ping-pong kernel needs 128). OFF unless VR_GEMM_D2=1:
-// measured on bge-base, 2200 chunks (profiles/r02_gemm_experiments.md) it runs at 750 TFLOP/s against the ping-pong
-// kernel's 930 — its epilogues do overlap the other block's main loop, but 32-deep stages of a 256x128 tile pull
-// 1.5x the bytes through L2 -> LDS in 64-byte row segments, and that path (14.5 TB/s here) is what bounds it.
-static bool d2_usable(int N, int K) {
-  // VR_GEMM_D2=1: every projection; 2: only those whose width leaves the 256-wide kernel half a column tile (N % 256 != 0)
-  static const int d2_mode = getenv("VR_GEMM_D2") ? atoi(getenv("VR_GEMM_D2")) : 0;
-  const bool on = d2_mode == 1 || (d2_mode == 2 && N % 256 != 0);
-  return on && K % D2K == 0 && N % 8 == 0;
-}
-
-// gemm_f16_mid (gemm_f16_d2_kernel<EPI, 1>, 128x128 tiles) in place of the ping-pong kernel for 256 < M while the
-// 256x256 tiles would fill at most a quarter of the CUs. Measured on an MI355X: at 21-48 ping-pong tiles
-// (1k tokens, N = 768 / 2304 / 3072) it is 15-40 % faster; at 189 (16k tokens, N = 768) up to 35 % slower; the shapes
-// between were not measured and stay with the ping-pong kernel. VR_GEMM_MID=0 turns it off (A/B runs; the bit-identity test).
+// gemm_f16_mid_kernel (128x128 tiles) in place of the ping-pong kernel for 256 < M while the 256x256 tiles would fill
+// at most a quarter of the CUs. Measured on an MI355X: at 21-48 ping-pong tiles (1k tokens,
+// N = 768 / 2304 / 3072) it is 15-40 % faster; at 189 (16k tokens, N = 768) up to 35 % slower; the shapes between were
+// not measured and stay with the ping-pong kernel. VR_GEMM_MID=0 turns it off (the bit-identity test's reference).
 static bool mid_usable(int M, int N, int K, int n_cu) {
   static const bool mid_on = !(getenv("VR_GEMM_MID") && atoi(getenv("VR_GEMM_MID")) == 0);
-  if (!mid_on || K % D2K != 0 || N % 8 != 0 || M <= 256) return false;
+  if (!mid_on || K % kMidK != 0 || N % 8 != 0 || M <= 256) return false;
   const int tiles_pp = ((M + GBM - 1) / GBM) * ((N + GBN - 1) / GBN);
   return 4 * tiles_pp <= n_cu;
 }
 
 // the kernels whose epilogue is direct_epilogue (all EPI_* variants, f16 residual stream included)
-static bool direct_usable(int N, int K) { return d2_usable(N, K) || pp_usable(N, K); }
+static bool direct_usable(int N, int K) { return pp_usable(N, K); }
 
-template <int WM>
-static void launch_d2(int epi, hipStream_t s, const half_t* Ah, const half_t* Wh, const float* bias, const float* R,
-                      float* C, half_t* Ch, half_t* Cl, int M, int N, int K, float unscale, const float2* ln_stat,
-                      const float* ln_g, const float* ln_b) {
-  const int tiles_m = (M + d2_rows<WM>() - 1) / d2_rows<WM>(), tiles_n = (N + D2N - 1) / D2N;
+static bool launch_mid(int epi, hipStream_t s, const GemmArgs& g) {
+  const int tiles_m = (g.M + kMidM - 1) / kMidM, tiles_n = (g.N + kMidN - 1) / kMidN;
   const int grid = (tiles_m + 7) / 8 * 8 * tiles_n;
-#ifdef VR_GEMM_DIAG_BUILD
-  static bool diag_set = false;
-  if (!diag_set) {
-    const int v = getenv("VR_GEMM_DIAG") ? atoi(getenv("VR_GEMM_DIAG")) : 0;
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_gemm_diag), &v, sizeof(int));
-    diag_set = true;
-  }
-#endif
-#define VR_LAUNCH_D2(E)                                                                                       \
-  hipLaunchKernelGGL((gemm_f16_d2_kernel<E, WM>), dim3(grid), dim3(128 * WM), 0, s, Ah, Wh, bias, R, C, Ch, Cl, M, N, \
-                     K, unscale, ln_stat, ln_g, ln_b)
-  switch (epi) {
-    case EPI_BIAS: VR_LAUNCH_D2(EPI_BIAS); break;
-    case EPI_BIAS_GELU: VR_LAUNCH_D2(EPI_BIAS_GELU); break;
-    case EPI_BIAS_F16: VR_LAUNCH_D2(EPI_BIAS_F16); break;
-    case EPI_BIAS_RESIDUAL_LN: VR_LAUNCH_D2(EPI_BIAS_RESIDUAL_LN); break;
-    case EPI_FOLD_F16: VR_LAUNCH_D2(EPI_FOLD_F16); break;
-    case EPI_FOLD_GELU: VR_LAUNCH_D2(EPI_FOLD_GELU); break;
-    case EPI_FOLD_SWIGLU: VR_LAUNCH_D2(EPI_FOLD_SWIGLU); break;
-    case EPI_FOLD_GEGLU: VR_LAUNCH_D2(EPI_FOLD_GEGLU); break;
-    case EPI_BIAS_RESIDUAL_LN_STATS: VR_LAUNCH_D2(EPI_BIAS_RESIDUAL_LN_STATS); break;
-    case EPI_RLS_R32_O16: VR_LAUNCH_D2(EPI_RLS_R32_O16); break;
-    case EPI_RLS_R16_O16: VR_LAUNCH_D2(EPI_RLS_R16_O16); break;
-    case EPI_RLS_R16_O32: VR_LAUNCH_D2(EPI_RLS_R16_O32); break;
-    default: VR_LAUNCH_D2(EPI_BIAS_RESIDUAL); break;
-  }
-#undef VR_LAUNCH_D2
+  return with_epi<VR_DIRECT_EPIS>(epi, [&](auto E) {
+    hipLaunchKernelGGL((gemm_f16_mid_kernel<decltype(E)::value>), dim3(grid), dim3(128), 0, s, g.A, g.W.hi, g.bias, g.R, g.C,
+                       g.Ch, g.Cl, g.M, g.N, g.K, g.W.unscale, g.ln_stat, g.ln_g, g.ln_b);
+  });
 }
 
-static void launch_pp(int epi, int grid, hipStream_t s, const half_t* Ah, const half_t* Wh, const float* bias,
-                      const float* R, float* C, half_t* Ch, half_t* Cl, int M, int N, int K, float unscale,
-                      const float2* ln_stat, const float* ln_g, const float* ln_b) {
-  // start-time spread of the persistent blocks, as a fraction of one tile's time (estimated: ~2400 cycles per
-  // K-tile + ~12000 of epilogue, in units of 64 cycles); only when a block walks several tiles
-  static const float stagger_frac = getenv("VR_GEMM_STAGGER") ? static_cast<float>(atof(getenv("VR_GEMM_STAGGER"))) : 0.0f;
-  // row panels per group of the tile walk (column index slow inside a group): experiment switch VR_GEMM_GROUPM
-  static const int group_m = getenv("VR_GEMM_GROUPM") ? std::max(1, atoi(getenv("VR_GEMM_GROUPM"))) : kGroupM256;
-  const int tiles_total = ((M + GBM - 1) / GBM) * ((N + GBN - 1) / GBN);
-  const int stagger = tiles_total >= 3 * grid ? static_cast<int>(stagger_frac * ((K / 64) * 2400.0f + 12000.0f) / 64.0f) : 0;
-#ifdef VR_GEMM_DIAG_BUILD
-  static bool diag_set = false;
-  if (!diag_set) {
-    const int v = getenv("VR_GEMM_DIAG") ? atoi(getenv("VR_GEMM_DIAG")) : 0;
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_gemm_diag), &v, sizeof(int));
-    diag_set = true;
-  }
-#endif
-#define VR_LAUNCH_PP(E)                                                                                        \
-  hipLaunchKernelGGL((gemm_f16_pp_kernel<E>), dim3(grid), dim3(512), 0, s, Ah, Wh, bias, R, C, Ch, Cl, M, N, K, \
-                     unscale, ln_stat, ln_g, ln_b, stagger, group_m)
-  switch (epi) {
-    case EPI_BIAS: VR_LAUNCH_PP(EPI_BIAS); break;
-    case EPI_BIAS_GELU: VR_LAUNCH_PP(EPI_BIAS_GELU); break;
-    case EPI_BIAS_F16: VR_LAUNCH_PP(EPI_BIAS_F16); break;
-    case EPI_BIAS_RESIDUAL_LN: VR_LAUNCH_PP(EPI_BIAS_RESIDUAL_LN); break;
-    case EPI_FOLD_F16: VR_LAUNCH_PP(EPI_FOLD_F16); break;
-    case EPI_FOLD_GELU: VR_LAUNCH_PP(EPI_FOLD_GELU); break;
-    case EPI_FOLD_SWIGLU: VR_LAUNCH_PP(EPI_FOLD_SWIGLU); break;
-    case EPI_FOLD_GEGLU: VR_LAUNCH_PP(EPI_FOLD_GEGLU); break;
-    case EPI_BIAS_RESIDUAL_LN_STATS: VR_LAUNCH_PP(EPI_BIAS_RESIDUAL_LN_STATS); break;
-    case EPI_RLS_R32_O16: VR_LAUNCH_PP(EPI_RLS_R32_O16); break;
-    case EPI_RLS_R16_O16: VR_LAUNCH_PP(EPI_RLS_R16_O16); break;
-    case EPI_RLS_R16_O32: VR_LAUNCH_PP(EPI_RLS_R16_O32); break;
-    default: VR_LAUNCH_PP(EPI_BIAS_RESIDUAL); break;
-  }
-#undef VR_LAUNCH_PP
-#ifdef VR_GEMM_HAS_STAMPS
-  static int stamps_left = getenv("VR_GEMM_STAMPS") ? atoi(getenv("VR_GEMM_STAMPS")) : 0;
-  if (stamps_left > 0) {
-    --stamps_left;
-    (void)hipStreamSynchronize(s);
-    static long long h[2][16][8];
-    (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_pp_stamps), sizeof(h));
-    fprintf(stderr, "[pp stamps] epi %d M %d N %d K %d: per tile, cycles: main loop (to first new-load wait, to second) | align+wait | epilogue | to next tile\n",
-            epi, M, N, K);
-    for (int w = 0; w < 2; ++w)
-      for (int t = 0; t + 1 < 12; ++t)
-        fprintf(stderr, "  wave %d tile %2d: main %6lld (first %5lld, second %5lld) | %5lld | %6lld | %5lld\n", 4 * w, t, h[w][t][2] - h[w][t][0],
-                h[w][t][1] - h[w][t][0], h[w][t][6] - h[w][t][0], h[w][t][3] - h[w][t][2], h[w][t][4] - h[w][t][3], h[w][t + 1][0] - h[w][t][4]);
-  }
-#endif
+static bool launch_pp(int epi, int grid, hipStream_t s, const GemmArgs& g) {
+  return with_epi<VR_DIRECT_EPIS>(epi, [&](auto E) {  // (no start-time stagger; tile walk in groups of kGroupM256 row panels)
+    hipLaunchKernelGGL((gemm_f16_pp_kernel<decltype(E)::value>), dim3(grid), dim3(512), 0, s, g.A, g.W.hi, g.bias, g.R, g.C,
+                       g.Ch, g.Cl, g.M, g.N, g.K, g.W.unscale, g.ln_stat, g.ln_g, g.ln_b, 0, kGroupM256);
+  });
 }
+#undef VR_DIRECT_EPIS
 
 // The skinny GEMM of a handful of tokens (M <= 16) with the LayerNorm IN FRONT of it folded in: the
 // activation operand is built from the pre-LayerNorm f32 rows instead of being read as f16 rows that a
@@ -2994,46 +2824,33 @@ __global__ __launch_bounds__(NW * 64) void gemm_f16_skinny_ln_rope_kernel(
 // K = hidden size H: 8 waves x 3 steps (768), 8 x 4 (1024), 4 x 3 (384); anything else keeps the LayerNorm launch
 static bool skinny_ln_supported(int M, int N, int K) { return M <= 16 && N % 16 == 0 && (K == 768 || K == 1024 || K == 384); }
 
-static int launch_skinny_ln(vr_engine* e, int epi, const float* pre, const float* ln_g, const float* ln_b, float eps,
-                            float2* stat_out, const half_t* W, float unscale, const float* bias, half_t* Ch, int M,
-                            int N, int K, const float2* rope_tab = nullptr, const int32_t* rope_pos = nullptr) {
+// `pre`: the pre-LayerNorm f32 rows, `stat_out`: where block 0 stores their statistics; of `g`: W, bias, Ch, M, N, K,
+// ln_g / ln_b (the folded LayerNorm's gain and shift) and, for EPI_ROPE_F16, rope_tab / rope_pos
+static int launch_skinny_ln(vr_engine* e, int epi, const float* pre, float eps, float2* stat_out, const GemmArgs& g) {
   hipStream_t s = e->stream;
-  prof_begin(e, VR_PROF_GEMM, 2.0 * M * static_cast<double>(N) * K);
-  const dim3 grid(static_cast<unsigned>(N / 16));
-#define VR_SKINNY_LN(E, ST, NWV)                                                                                   \
-  hipLaunchKernelGGL((gemm_f16_skinny_ln_kernel<E, ST, NWV>), grid, dim3(NWV * 64), 0, s, pre, ln_g, ln_b, eps,    \
-                     stat_out, W, M, N, K, unscale, bias, Ch)
-#define VR_SKINNY_LN_ROPE(ST, NWV)                                                                                 \
-  hipLaunchKernelGGL((gemm_f16_skinny_ln_rope_kernel<ST, NWV>), grid, dim3(NWV * 64), 0, s, pre, ln_g, ln_b, eps,  \
-                     stat_out, W, M, N, K, unscale, bias, Ch, rope_tab, rope_pos)
-#define VR_SKINNY_LN_K(E)                      \
-  do {                                         \
-    if (K == 768) VR_SKINNY_LN(E, 3, 8);       \
-    else if (K == 1024) VR_SKINNY_LN(E, 4, 8); \
-    else VR_SKINNY_LN(E, 3, 4);                \
-  } while (0)
-  switch (epi) {
-    case EPI_BIAS_GELU: VR_SKINNY_LN_K(EPI_BIAS_GELU); break;
-    case EPI_ROPE_F16:
-      if (K == 768) VR_SKINNY_LN_ROPE(3, 8);
-      else if (K == 1024) VR_SKINNY_LN_ROPE(4, 8);
-      else VR_SKINNY_LN_ROPE(3, 4);
-      break;
-    case EPI_SWIGLU_F16: VR_SKINNY_LN_K(EPI_SWIGLU_F16); break;
-    case EPI_GEGLU_F16: VR_SKINNY_LN_K(EPI_GEGLU_F16); break;
-    default: VR_SKINNY_LN_K(EPI_BIAS_F16); break;
-  }
-#undef VR_SKINNY_LN_K
-#undef VR_SKINNY_LN_ROPE
-#undef VR_SKINNY_LN
+  prof_begin(e, VR_PROF_GEMM, 2.0 * g.M * static_cast<double>(g.N) * g.K);
+  const dim3 grid(static_cast<unsigned>(g.N / 16));
+  const bool known = with_epi<EPI_BIAS_F16, EPI_BIAS_GELU, EPI_ROPE_F16, EPI_SWIGLU_F16, EPI_GEGLU_F16>(epi, [&](auto E) {
+    auto launch = [&](auto ST, auto NWV) {
+      constexpr int kE = decltype(E)::value, kSteps = decltype(ST)::value, kWaves = decltype(NWV)::value;
+      if constexpr (kE == EPI_ROPE_F16)  // (a kernel of its own: two arguments more)
+        hipLaunchKernelGGL((gemm_f16_skinny_ln_rope_kernel<kSteps, kWaves>), grid, dim3(kWaves * 64), 0, s, pre, g.ln_g, g.ln_b,
+                           eps, stat_out, g.W.hi, g.M, g.N, g.K, g.W.unscale, g.bias, g.Ch, g.rope_tab, g.rope_pos);
+      else
+        hipLaunchKernelGGL((gemm_f16_skinny_ln_kernel<kE, kSteps, kWaves>), grid, dim3(kWaves * 64), 0, s, pre, g.ln_g, g.ln_b,
+                           eps, stat_out, g.W.hi, g.M, g.N, g.K, g.W.unscale, g.bias, g.Ch);
+    };
+    if (g.K == 768) launch(std::integral_constant<int, 3>{}, std::integral_constant<int, 8>{});
+    else if (g.K == 1024) launch(std::integral_constant<int, 4>{}, std::integral_constant<int, 8>{});
+    else launch(std::integral_constant<int, 3>{}, std::integral_constant<int, 4>{});
+  });
   prof_end(e);
+  VR_CHECK(known, "epilogue %d does not exist for the skinny GEMM with a folded LayerNorm (M=%d N=%d K=%d)", epi, g.M, g.N,
+           g.K);
   VR_HIP(hipGetLastError());
   return 0;
 }
 
-// passes = 3: operands are interleaved (hi, lo) rows (Al = Ah + 8, Wl = Wh + 8); passes = 1: plain f16
-// rows, Al / Wl / Cl unused.
-// enc: the model whose forward pass this is (its split-K scratch and graph cache)
 // whether launch_gemm_f16x3 sends an f16-mode product of this shape to one of the skinny kernels (its two tests below)
 static bool skinny_routed(int M, int N, int K) {
   const int sk_waves = K % 256 == 0 ? 8 : K % 128 == 0 ? 4 : 0;
@@ -3042,14 +2859,22 @@ static bool skinny_routed(int M, int N, int K) {
   return M <= 4 * kSkinnyM && (one_launch || (skinny_slice(K) > 0 && N % 64 == 0));
 }
 
-static int launch_gemm_f16x3(vr_engine* e, Encoder* enc, int epi, const half_t* Ah, const half_t* Al, const half_t* Wh,
-                             const half_t* Wl, float unscale, const float* bias, const float* R, float* C,
-                             half_t* Ch, half_t* Cl, int M, int N, int K, int passes = 3,
-                             const float2* ln_stat = nullptr, const float* ln_g = nullptr, const float* ln_b = nullptr) {
+// the skinny kernels (skinny_apply) exist for these
+#define VR_SKINNY_EPIS \
+  EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESIDUAL, EPI_BIAS_F16, EPI_BIAS_RESIDUAL_LN, EPI_ROPE_F16, EPI_SWIGLU_F16, EPI_GEGLU_F16
+
+// g.passes = 3: operands are interleaved (hi, lo) rows (A_lo = A + 8, W.lo = W.hi + 8); 1: plain f16 rows, A_lo / W.lo
+// unused. enc: the model whose forward pass this is (its split-K scratch and graph cache)
+static int launch_gemm_f16x3(vr_engine* e, Encoder* enc, int epi, const GemmArgs& g) {
+  const int M = g.M, N = g.N, K = g.K, passes = g.passes;
   VR_CHECK(N % 4 == 0 && K % HBK_ == 0, "GEMM shape N=%d K=%d: N must be a multiple of 4, K of %d", N, K, HBK_);
   if (M <= 0) return 0;
   hipStream_t s = e->stream;
-  static const int force_tile = getenv("VR_GEMM_TILE") ? atoi(getenv("VR_GEMM_TILE")) : 0;  // 128: A/B runs
+  // EPI_ROPE_F16 (skinny kernels only): their ln_stat / ln_g parameters carry the cos/sin table and the int32 positions
+  // (skinny_apply casts the positions back) — the one place where the two meet
+  const float2* k_stat = epi == EPI_ROPE_F16 ? g.rope_tab : g.ln_stat;
+  const float* k_g = epi == EPI_ROPE_F16 ? reinterpret_cast<const float*>(g.rope_pos) : g.ln_g;
+  bool known = false;  // whether the kernel this product goes to exists for `epi`
   prof_begin(e, VR_PROF_GEMM, 2.0 * M * static_cast<double>(N) * K);
   // one-launch skinny kernel: 8 waves per block when an eighth of K is whole 32-deep MFMA steps, else 4;
   // UNR = steps whose loads are issued together (the largest of 6, 4, 3 dividing the wave's step count)
@@ -3058,38 +2883,21 @@ static int launch_gemm_f16x3(vr_engine* e, Encoder* enc, int epi, const half_t* 
   const int sk_unr = sk_steps == 0 ? 0 : sk_steps % 6 == 0 ? 6 : sk_steps % 4 == 0 ? 4 : sk_steps % 3 == 0 ? 3 : 0;
   if (passes == 1 && M <= 4 * kSkinnyM && sk_unr > 0 && N % 16 == 0) {
     const dim3 sg(static_cast<unsigned>(N / 16), static_cast<unsigned>((M + kSkinnyM - 1) / kSkinnyM));
-#define VR_SKINNY1_LAUNCH(E, U, W)                                                                                    \
-  hipLaunchKernelGGL((gemm_f16_skinny1_kernel<E, U, W>), sg, dim3(W * 64), 0, s, Ah, Wh, M, N, K, unscale, bias, R,  \
-                     ln_stat, ln_g, ln_b, C, Ch)
-#define VR_SKINNY1(E)                                                  \
-  do {                                                                 \
-    if (sk_waves == 8) {                                               \
-      if (sk_unr == 6) VR_SKINNY1_LAUNCH(E, 6, 8);                     \
-      else if (sk_unr == 4) VR_SKINNY1_LAUNCH(E, 4, 8);                \
-      else VR_SKINNY1_LAUNCH(E, 3, 8);                                 \
-    } else {                                                           \
-      if (sk_unr == 6) VR_SKINNY1_LAUNCH(E, 6, 4);                     \
-      else if (sk_unr == 4) VR_SKINNY1_LAUNCH(E, 4, 4);                \
-      else VR_SKINNY1_LAUNCH(E, 3, 4);                                 \
-    }                                                                  \
-  } while (0)
-    switch (epi) {
-      case EPI_BIAS: VR_SKINNY1(EPI_BIAS); break;
-      case EPI_BIAS_GELU: VR_SKINNY1(EPI_BIAS_GELU); break;
-      case EPI_BIAS_F16: VR_SKINNY1(EPI_BIAS_F16); break;
-      case EPI_ROPE_F16: VR_SKINNY1(EPI_ROPE_F16); break;
-      case EPI_SWIGLU_F16: VR_SKINNY1(EPI_SWIGLU_F16); break;
-      case EPI_GEGLU_F16: VR_SKINNY1(EPI_GEGLU_F16); break;
-      case EPI_BIAS_RESIDUAL_LN: VR_SKINNY1(EPI_BIAS_RESIDUAL_LN); break;
-      default: VR_SKINNY1(EPI_BIAS_RESIDUAL); break;
-    }
-#undef VR_SKINNY1
-#undef VR_SKINNY1_LAUNCH
-    prof_end(e);
-    VR_HIP(hipGetLastError());
-    return 0;
-  }
-  if (passes == 1 && M <= 4 * kSkinnyM && skinny_slice(K) > 0 && N % 64 == 0) {  // K % 128 != 0: split-K, two launches
+    known = with_epi<VR_SKINNY_EPIS>(epi, [&](auto E) {
+      auto launch = [&](auto U, auto W) {
+        constexpr int kWaves = decltype(W)::value;
+        hipLaunchKernelGGL((gemm_f16_skinny1_kernel<decltype(E)::value, decltype(U)::value, kWaves>), sg, dim3(kWaves * 64), 0, s,
+                           g.A, g.W.hi, M, N, K, g.W.unscale, g.bias, g.R, k_stat, k_g, g.ln_b, g.C, g.Ch);
+      };
+      auto by_unr = [&](auto W) {
+        if (sk_unr == 6) launch(std::integral_constant<int, 6>{}, W);
+        else if (sk_unr == 4) launch(std::integral_constant<int, 4>{}, W);
+        else launch(std::integral_constant<int, 3>{}, W);
+      };
+      if (sk_waves == 8) by_unr(std::integral_constant<int, 8>{});
+      else by_unr(std::integral_constant<int, 4>{});
+    });
+  } else if (passes == 1 && M <= 4 * kSkinnyM && skinny_slice(K) > 0 && N % 64 == 0) {  // K % 128 != 0: split-K, two launches
     const int kslice = skinny_slice(K), slices = K / kslice;
     {
       const float* before = enc->skinny_ws.p;
@@ -3097,29 +2905,13 @@ static int launch_gemm_f16x3(vr_engine* e, Encoder* enc, int epi, const half_t* 
       if (enc->skinny_ws.p != before) invalidate_graphs(enc);  // (never during a capture: a shape runs eagerly first)
     }
     hipLaunchKernelGGL(gemm_f16_skinny_kernel, dim3(static_cast<unsigned>(N / 64), static_cast<unsigned>(slices), static_cast<unsigned>((M + kSkinnyM - 1) / kSkinnyM)),
-                       dim3(256), 0, s, Ah, Wh, enc->skinny_ws.p, M, N, K, kslice);
+                       dim3(256), 0, s, g.A, g.W.hi, enc->skinny_ws.p, M, N, K, kslice);
     const unsigned eb = static_cast<unsigned>((static_cast<int64_t>(M) * N / 4 + 255) / 256);
-#define VR_SKINNY_EPI(E)                                                                                          \
-  hipLaunchKernelGGL((skinny_epilogue_kernel<E>), dim3(eb), dim3(256), 0, s, enc->skinny_ws.p, slices, M, N, unscale, \
-                     bias, R, ln_stat, ln_g, ln_b, C, Ch)
-    switch (epi) {
-      case EPI_BIAS: VR_SKINNY_EPI(EPI_BIAS); break;
-      case EPI_BIAS_GELU: VR_SKINNY_EPI(EPI_BIAS_GELU); break;
-      case EPI_BIAS_F16: VR_SKINNY_EPI(EPI_BIAS_F16); break;
-      case EPI_ROPE_F16: VR_SKINNY_EPI(EPI_ROPE_F16); break;
-      case EPI_SWIGLU_F16: VR_SKINNY_EPI(EPI_SWIGLU_F16); break;
-      case EPI_GEGLU_F16: VR_SKINNY_EPI(EPI_GEGLU_F16); break;
-      case EPI_BIAS_RESIDUAL_LN: VR_SKINNY_EPI(EPI_BIAS_RESIDUAL_LN); break;
-      default: VR_SKINNY_EPI(EPI_BIAS_RESIDUAL); break;
-    }
-#undef VR_SKINNY_EPI
-    prof_end(e);
-    VR_HIP(hipGetLastError());
-    return 0;
-  }
-  VR_CHECK(epi < EPI_ROPE_F16 || ((epi == EPI_FOLD_SWIGLU || epi == EPI_FOLD_GEGLU) && passes == 1 && pp_usable(N, K)),
-           "epilogue %d does not exist for the kernel of this product (M=%d N=%d K=%d)", epi, M, N, K);
-  if (passes == 1 || (N % GBN == 0 && K % GBK == 0 && M >= GBM && force_tile != 128)) {
+    known = with_epi<VR_SKINNY_EPIS>(epi, [&](auto E) {
+      hipLaunchKernelGGL((skinny_epilogue_kernel<decltype(E)::value>), dim3(eb), dim3(256), 0, s, enc->skinny_ws.p, slices, M, N,
+                         g.W.unscale, g.bias, g.R, k_stat, k_g, g.ln_b, g.C, g.Ch);
+    });
+  } else if (passes == 1 || (N % GBN == 0 && K % GBK == 0 && M >= GBM)) {
     static int n_cu = 0;  // persistent grid: one block per CU (the kernel uses 128 KiB of the CU's LDS)
     if (n_cu == 0) {
       hipDeviceProp_t prop;
@@ -3129,40 +2921,28 @@ static int launch_gemm_f16x3(vr_engine* e, Encoder* enc, int epi, const half_t* 
     }
     const int tiles = ((M + GBM - 1) / GBM) * ((N + GBN - 1) / GBN);
     const int grid256 = std::min(tiles, n_cu);
-    if (passes == 1 && d2_usable(N, K))  // f16 mode: two independent half-width tiles per CU (gemm_f16_d2_kernel)
-      launch_d2<2>(epi, s, Ah, Wh, bias, R, C, Ch, Cl, M, N, K, unscale, ln_stat, ln_g, ln_b);
-    else if (passes == 1 && mid_usable(M, N, K, n_cu))  // mid-size M: 128x128 tiles (gemm_f16_mid)
-      launch_d2<1>(epi, s, Ah, Wh, bias, R, C, Ch, Cl, M, N, K, unscale, ln_stat, ln_g, ln_b);
+    if (passes == 1 && mid_usable(M, N, K, n_cu))  // mid-size M: 128x128 tiles (gemm_f16_mid_kernel)
+      known = launch_mid(epi, s, g);
     else if (passes == 1 && pp_usable(N, K))  // the ping-pong main loop (gemm_f16_pp_kernel)
-      launch_pp(epi, grid256, s, Ah, Wh, bias, R, C, Ch, Cl, M, N, K, unscale, ln_stat, ln_g, ln_b);
+      known = launch_pp(epi, grid256, s, g);
     else if (passes == 1)
-      launch_256<1>(epi, grid256, s, Ah, Al, Wh, Wl, bias, R, C, Ch, Cl, M, N, K, unscale, ln_stat, ln_g, ln_b);
+      known = launch_256<1>(epi, grid256, s, g);
     else
-      launch_256<3>(epi, grid256, s, Ah, Al, Wh, Wl, bias, R, C, Ch, Cl, M, N, K, unscale, ln_stat, ln_g, ln_b);
-    prof_end(e);
-    VR_HIP(hipGetLastError());
-    return 0;
-  }
-  VR_CHECK(N % HBN_ == 0, "GEMM shape N=%d must be a multiple of %d", N, HBN_);
-  const int grid = ((M + HBM_ - 1) / HBM_) * (N / HBN_);
-  switch (epi) {
-    case EPI_BIAS:
-      hipLaunchKernelGGL((gemm_f16x3_kernel<EPI_BIAS>), dim3(grid), dim3(256), 0, s, Ah, Al, Wh, Wl, bias, R, C, Ch,
-                         Cl, M, N, K, unscale);
-      break;
-    case EPI_BIAS_GELU:
-      hipLaunchKernelGGL((gemm_f16x3_kernel<EPI_BIAS_GELU>), dim3(grid), dim3(256), 0, s, Ah, Al, Wh, Wl, bias, R,
-                         C, Ch, Cl, M, N, K, unscale);
-      break;
-    default:
-      hipLaunchKernelGGL((gemm_f16x3_kernel<EPI_BIAS_RESIDUAL>), dim3(grid), dim3(256), 0, s, Ah, Al, Wh, Wl, bias,
-                         R, C, Ch, Cl, M, N, K, unscale);
-      break;
+      known = launch_256<3>(epi, grid256, s, g);
+  } else {
+    VR_CHECK(N % HBN_ == 0, "GEMM shape N=%d must be a multiple of %d", N, HBN_);
+    const int grid = ((M + HBM_ - 1) / HBM_) * (N / HBN_);
+    known = with_epi<EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESIDUAL>(epi, [&](auto E) {
+      hipLaunchKernelGGL((gemm_f16x3_kernel<decltype(E)::value>), dim3(grid), dim3(256), 0, s, g.A, g.A_lo, g.W.hi, g.W.lo, g.bias,
+                         g.R, g.C, g.Ch, g.Cl, M, N, K, g.W.unscale);
+    });
   }
   prof_end(e);
+  VR_CHECK(known, "epilogue %d does not exist for the kernel of this product (M=%d N=%d K=%d passes=%d)", epi, M, N, K, passes);
   VR_HIP(hipGetLastError());
   return 0;
 }
+#undef VR_SKINNY_EPIS
 
 // ---- attention -----------------------------------------------------------------------------------
 
@@ -4028,18 +3808,15 @@ static int forward_chunk(vr_engine* e, Encoder* enc, const int32_t* ids_dev, con
   const float* final_x = enc->x;  // the f32 rows pooling reads
   const bool lnfuse = plain && !enc->layers.empty();  // (a model without layers pools the embedding LayerNorm's output)
   // a handful of tokens (one query): the two LayerNorm launches of a layer are folded into the projections
-  // that consume them (gemm_f16_skinny_ln_kernel); VR_ENCODE_FOLD_LN=0 keeps them apart
-  static const bool fold_ln_enabled = !(getenv("VR_ENCODE_FOLD_LN") && atoi(getenv("VR_ENCODE_FOLD_LN")) == 0);
-  const bool fold_ln = lnfuse && fold_ln_enabled && skinny_ln_supported(T, 3 * H, H) && I % 16 == 0;
+  // that consume them (gemm_f16_skinny_ln_kernel)
+  const bool fold_ln = lnfuse && skinny_ln_supported(T, 3 * H, H) && I % 16 == 0;
   // large batches (the 256-tile GEMM): the LayerNorm passes disappear into the GEMMs on both sides of them —
   // the producing epilogue also stores f16 pre-LN rows and per-(row, 64 columns) partial sums, a tiny
   // kernel turns those into (mean, 1/sigma), and the consuming GEMM multiplies the pre-LN rows by the
-  // gain-scaled weights and applies the statistics in its epilogue (EPI_FOLD_*). VR_ENCODE_FOLD_GEMM=0: off.
-  static const bool fold_big_enabled = !(getenv("VR_ENCODE_FOLD_GEMM") && atoi(getenv("VR_ENCODE_FOLD_GEMM")) == 0);
-  const bool fold_big = lnfuse && fold_big_enabled && T > 4 * kSkinnyM && H % 64 == 0 && enc->layers[0].cs_1 != nullptr;
-  // ... and with an f16 residual stream (EPI_RLS_*): the pre-LayerNorm rows live in xh only. VR_ENCODE_RES16=0: f32 rows
-  static const bool res16_enabled = !(getenv("VR_ENCODE_RES16") && atoi(getenv("VR_ENCODE_RES16")) == 0);
-  const bool res16 = fold_big && res16_enabled && direct_usable(H, H) && direct_usable(H, I);
+  // gain-scaled weights and applies the statistics in its epilogue (EPI_FOLD_*).
+  const bool fold_big = lnfuse && T > 4 * kSkinnyM && H % 64 == 0 && enc->layers[0].cs_1 != nullptr;
+  // ... and with an f16 residual stream (EPI_RLS_*): the pre-LayerNorm rows live in xh only
+  const bool res16 = fold_big && direct_usable(H, H) && direct_usable(H, I);
   float2* part = reinterpret_cast<float2*>(enc->lnpart);
   const int segs = H / 64;
   const unsigned fin_blocks = static_cast<unsigned>((T + 255) / 256);
@@ -4076,6 +3853,8 @@ static int forward_chunk(vr_engine* e, Encoder* enc, const int32_t* ids_dev, con
   const bool fuse_glu_big = gated && fuse_enabled && !fuse_glu(T) && fold_big && pp_usable(N1, H) &&
                             enc->layers[0].cs_1_p != nullptr;
   const int32_t* posidx = reinterpret_cast<const int32_t*>(enc->posidx);
+  half_t* qkvh = reinterpret_cast<half_t*>(enc->qkv);  // f16 mode: the Q/K/V rows
+  half_t* parth = reinterpret_cast<half_t*>(part);     // the folded LayerNorms' partial sums, in an epilogue's Cl slot
   if (rotary)
     hipLaunchKernelGGL(positions_kernel, dim3(static_cast<unsigned>((T + 255) / 256)), dim3(256), 0, s, cu_dev, n_seq_total,
                        tok_base, T, reinterpret_cast<int32_t*>(enc->posidx));
@@ -4122,35 +3901,42 @@ static int forward_chunk(vr_engine* e, Encoder* enc, const int32_t* ids_dev, con
     const LayerWeights& w = enc->layers[li];
     const bool tail = cls_tail && li + 1 == enc->layers.size();
     if (plain && fold_ln && li > 0 && fuse_rope)  // ... and the rotation in its epilogue
-      VR_TRY(launch_skinny_ln(e, EPI_ROPE_F16, cur.pre, cur.g, cur.b, d.eps, const_cast<float2*>(cur.stat), w.s_qkv_p.hi,
-                              w.s_qkv_p.unscale, w.bqkv_p, reinterpret_cast<half_t*>(enc->qkv), T, 3 * H, H, enc->rope, posidx));
+      VR_TRY(launch_skinny_ln(e, EPI_ROPE_F16, cur.pre, d.eps, const_cast<float2*>(cur.stat),
+                              {.W = w.s_qkv_p, .bias = w.bqkv_p, .Ch = qkvh, .M = T, .N = 3 * H, .K = H, .ln_g = cur.g,
+                               .ln_b = cur.b, .rope_tab = enc->rope, .rope_pos = posidx}));
     else if (plain && fold_ln && li > 0)  // the previous layer's closing LayerNorm runs inside this projection
-      VR_TRY(launch_skinny_ln(e, EPI_BIAS_F16, cur.pre, cur.g, cur.b, d.eps, const_cast<float2*>(cur.stat), w.s_qkv.hi,
-                              w.s_qkv.unscale, w.bqkv, reinterpret_cast<half_t*>(enc->qkv), T, 3 * H, H));
+      VR_TRY(launch_skinny_ln(e, EPI_BIAS_F16, cur.pre, d.eps, const_cast<float2*>(cur.stat),
+                              {.W = w.s_qkv, .bias = w.bqkv, .Ch = qkvh, .M = T, .N = 3 * H, .K = H, .ln_g = cur.g, .ln_b = cur.b}));
     else if (plain && fold_big && li > 0)  // xh holds the f16 PRE-LN rows the previous FFN-down epilogue stored
-      VR_TRY(launch_gemm_f16x3(e, enc, EPI_FOLD_F16, xh, nullptr, w.s_qkv_f.hi, nullptr, w.s_qkv_f.unscale, w.c_qkv, nullptr,
-                               nullptr, reinterpret_cast<half_t*>(enc->qkv), nullptr, T, 3 * H, H, 1, cur.stat, w.cs_qkv,
-                               nullptr));
-    else if (plain && fuse_rope)  // (ln_stat / ln_g carry the table and the positions, see EPI_ROPE_F16)
-      VR_TRY(launch_gemm_f16x3(e, enc, EPI_ROPE_F16, xh, nullptr, w.s_qkv_p.hi, nullptr, w.s_qkv_p.unscale, w.bqkv_p, nullptr,
-                               nullptr, reinterpret_cast<half_t*>(enc->qkv), nullptr, T, 3 * H, H, 1, enc->rope,
-                               reinterpret_cast<const float*>(posidx)));
+      VR_TRY(launch_gemm_f16x3(e, enc, EPI_FOLD_F16, {.A = xh, .W = w.s_qkv_f, .bias = w.c_qkv, .Ch = qkvh, .M = T, .N = 3 * H,
+                                                      .K = H, .passes = 1, .ln_stat = cur.stat, .ln_g = w.cs_qkv}));
+    else if (plain && fuse_rope)
+      VR_TRY(launch_gemm_f16x3(e, enc, EPI_ROPE_F16, {.A = xh, .W = w.s_qkv_p, .bias = w.bqkv_p, .Ch = qkvh, .M = T, .N = 3 * H,
+                                                      .K = H, .passes = 1, .rope_tab = enc->rope, .rope_pos = posidx}));
     else if (plain)  // Q, K, V as plain f16 rows for attention_f16_kernel
-      VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_F16, xh, xl, w.s_qkv.hi, w.s_qkv.lo, w.s_qkv.unscale, w.bqkv, nullptr,
-                               nullptr, reinterpret_cast<half_t*>(enc->qkv), nullptr, T, 3 * H, H, passes));
+      VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_F16, {.A = xh, .A_lo = xl, .W = w.s_qkv, .bias = w.bqkv, .Ch = qkvh, .M = T,
+                                                      .N = 3 * H, .K = H, .passes = passes}));
     else if (split)
-      VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS, xh, xl, w.s_qkv.hi, w.s_qkv.lo, w.s_qkv.unscale, w.bqkv, nullptr,
-                               enc->qkv, nullptr, nullptr, T, 3 * H, H, passes));
+      VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS, {.A = xh, .A_lo = xl, .W = w.s_qkv, .bias = w.bqkv, .C = enc->qkv, .M = T,
+                                                  .N = 3 * H, .K = H, .passes = passes}));
     else
       VR_TRY(launch_gemm(e, EPI_BIAS, enc->x, w.wqkv, w.bqkv, nullptr, enc->qkv, T, 3 * H, H));
     rope();
     const int qb = tail ? 1 : qblocks;  // tail: only the query block that holds token 0 of every sequence
     dim3 agrid(static_cast<unsigned>(n_seq * qb), static_cast<unsigned>(nh));
     prof_begin(e, VR_PROF_ATTENTION, tail ? attn_flop / qblocks : attn_flop);
-    static const bool attn_seq = !(getenv("VR_ATTN_SEQ") && atoi(getenv("VR_ATTN_SEQ")) == 0);
-    if (plain && attn_seq && (dh == 64 || dh == 32)) {  // one block per (sequence, head): K/V staged once
-      const int lds_keys = (max_len + 15) & ~15;
-      const size_t lds_bytes = static_cast<size_t>(2) * lds_keys * dh * sizeof(half_t);
+    // f16 mode: one block per (sequence, head) with the sequence's K/V staged once in dynamic LDS (attention_seq_kernel)
+    // while the longest sequence's rows fit what a workgroup may have on this device; beyond that (rotary models admit
+    // such lengths through max_pos) attention_f16_kernel, which streams the keys in 64-row tiles through static LDS
+    const int lds_keys = (max_len + 15) & ~15;
+    const size_t lds_bytes = static_cast<size_t>(2) * lds_keys * dh * sizeof(half_t);
+    static size_t lds_limit = 0;
+    if (plain && lds_limit == 0) {
+      hipDeviceProp_t prop;
+      VR_HIP(hipGetDeviceProperties(&prop, e->device));
+      lds_limit = std::max(prop.sharedMemPerBlock, prop.sharedMemPerBlockOptin);
+    }
+    if (plain && lds_bytes <= lds_limit) {
       static size_t lds_allowed[2] = {0, 0};  // per instantiation: raised above the 64 KiB default when a sequence needs it
       const int which = dh == 64 ? 0 : 1;
       if (lds_bytes > 65536 && lds_bytes > lds_allowed[which]) {
@@ -4163,21 +3949,13 @@ static int forward_chunk(vr_engine* e, Encoder* enc, const int32_t* ids_dev, con
         lds_allowed[which] = lds_bytes;
       }
       const dim3 sgrid(static_cast<unsigned>(n_seq) * static_cast<unsigned>(nh));
-#ifdef VR_GEMM_DIAG_BUILD  // (timing experiment: VR_ATTN_QLIMIT=16 leaves the staging and one query tile per block)
-      static const int q_limit_env = getenv("VR_ATTN_QLIMIT") ? atoi(getenv("VR_ATTN_QLIMIT")) : 0;
-      const int q_limit = tail ? 16 : (q_limit_env > 0 ? q_limit_env : max_len);
-#else
       const int q_limit = tail ? 16 : max_len;
-#endif
-      static const int attn_waves = getenv("VR_ATTN_WAVES") ? atoi(getenv("VR_ATTN_WAVES")) : 4;  // (experiment switch: 4 or 8)
-#define VR_ATTN_SEQ(DHV, NWV)                                                                                                   \
-  hipLaunchKernelGGL((attention_seq_kernel<DHV, NWV>), sgrid, dim3(NWV * 64), lds_bytes, s, reinterpret_cast<const half_t*>(enc->qkv), \
-                     cu_dev, seq0, tok_base, H, scale, q_limit, lds_keys, ch)
-      if (dh == 64 && attn_waves == 8) VR_ATTN_SEQ(64, 8);
-      else if (dh == 64) VR_ATTN_SEQ(64, 4);
-      else if (attn_waves == 8) VR_ATTN_SEQ(32, 8);
-      else VR_ATTN_SEQ(32, 4);
-#undef VR_ATTN_SEQ
+      if (dh == 64)
+        hipLaunchKernelGGL((attention_seq_kernel<64, 4>), sgrid, dim3(256), lds_bytes, s, reinterpret_cast<const half_t*>(enc->qkv),
+                           cu_dev, seq0, tok_base, H, scale, q_limit, lds_keys, ch);
+      else
+        hipLaunchKernelGGL((attention_seq_kernel<32, 4>), sgrid, dim3(256), lds_bytes, s, reinterpret_cast<const half_t*>(enc->qkv),
+                           cu_dev, seq0, tok_base, H, scale, q_limit, lds_keys, ch);
     } else if (plain && dh == 64)  // (8 waves = 128 queries per block stage K/V once per 128-token sequence, and measured 30 % slower)
       hipLaunchKernelGGL((attention_f16_kernel<64, 4>), agrid, dim3(256), 0, s, reinterpret_cast<const half_t*>(enc->qkv),
                          cu_dev, seq0, tok_base, H, qb, scale, ch);
@@ -4209,34 +3987,34 @@ static int forward_chunk(vr_engine* e, Encoder* enc, const int32_t* ids_dev, con
       half_t* cch = reinterpret_cast<half_t*>(ctxc);
       half_t* fch = reinterpret_cast<half_t*>(ffnc);
       if (split)
-        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_RESIDUAL, cch, plain ? nullptr : cch + 8, w.s_o.hi, w.s_o.lo, w.s_o.unscale, w.bo, xc, tmpc,
-                                 nullptr, nullptr, n_seq, H, H, passes));
+        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_RESIDUAL, {.A = cch, .A_lo = plain ? nullptr : cch + 8, .W = w.s_o, .bias = w.bo,
+                                                             .R = xc, .C = tmpc, .M = n_seq, .N = H, .K = H, .passes = passes}));
       else
         VR_TRY(launch_gemm(e, EPI_BIAS_RESIDUAL, ctxc, w.wo, w.bo, xc, tmpc, n_seq, H, H));
       hipLaunchKernelGGL(layernorm_kernel, dim3(cblocks), dim3(256), 0, s, tmpc, n_seq, H, w.ln1g, w.ln1b, d.eps, xc,
                          split ? xch : nullptr, split && !plain ? xch + 8 : nullptr, static_cast<float2*>(nullptr));
       if (gated && fuse_glu(n_seq)) {
-        VR_TRY(launch_gemm_f16x3(e, enc, glu_epi, xch, nullptr, w.s_1_p.hi, nullptr, w.s_1_p.unscale, w.b1_p, nullptr, nullptr, fch,
-                                 nullptr, n_seq, N1, H, 1));
+        VR_TRY(launch_gemm_f16x3(e, enc, glu_epi, {.A = xch, .W = w.s_1_p, .bias = w.b1_p, .Ch = fch, .M = n_seq, .N = N1, .K = H,
+                                                   .passes = 1}));
       } else if (gated) {
         if (plain)
-          VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_F16, xch, nullptr, w.s_1.hi, nullptr, w.s_1.unscale, w.b1, nullptr, nullptr, gluh,
-                                   nullptr, n_seq, N1, H, 1));
+          VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_F16, {.A = xch, .W = w.s_1, .bias = w.b1, .Ch = gluh, .M = n_seq, .N = N1, .K = H,
+                                                          .passes = 1}));
         else if (split)
-          VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS, xch, xch + 8, w.s_1.hi, w.s_1.lo, w.s_1.unscale, w.b1, nullptr, enc->glu,
-                                   nullptr, nullptr, n_seq, N1, H, passes));
+          VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS, {.A = xch, .A_lo = xch + 8, .W = w.s_1, .bias = w.b1, .C = enc->glu, .M = n_seq,
+                                                      .N = N1, .K = H, .passes = passes}));
         else
           VR_TRY(launch_gemm(e, EPI_BIAS, xc, w.w1, w.b1, nullptr, enc->glu, n_seq, N1, H));
         glu(n_seq, ffnc, fch);
       } else if (split) {
-        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_GELU, xch, plain ? nullptr : xch + 8, w.s_1.hi, w.s_1.lo, w.s_1.unscale, w.b1, nullptr, nullptr,
-                                 fch, plain ? nullptr : fch + 8, n_seq, I, H, passes));
+        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_GELU, {.A = xch, .A_lo = plain ? nullptr : xch + 8, .W = w.s_1, .bias = w.b1, .Ch = fch,
+                                                         .Cl = plain ? nullptr : fch + 8, .M = n_seq, .N = I, .K = H, .passes = passes}));
       } else {
         VR_TRY(launch_gemm(e, EPI_BIAS_GELU, xc, w.w1, w.b1, nullptr, ffnc, n_seq, I, H));
       }
       if (split) {
-        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_RESIDUAL, fch, plain ? nullptr : fch + 8, w.s_2.hi, w.s_2.lo, w.s_2.unscale, w.b2, xc, tmpc,
-                                 nullptr, nullptr, n_seq, H, I, passes));
+        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_RESIDUAL, {.A = fch, .A_lo = plain ? nullptr : fch + 8, .W = w.s_2, .bias = w.b2,
+                                                             .R = xc, .C = tmpc, .M = n_seq, .N = H, .K = I, .passes = passes}));
       } else {
         VR_TRY(launch_gemm(e, EPI_BIAS_RESIDUAL, ffnc, w.w2, w.b2, xc, tmpc, n_seq, H, I));
       }
@@ -4255,17 +4033,19 @@ static int forward_chunk(vr_engine* e, Encoder* enc, const int32_t* ids_dev, con
       if (res16) {
         // f16 residual stream: residual rows are f32 only in layer 0 (the embedding sum), the pre-LN rows go out
         // as f16 into xh, in place where the residual came from there
-        VR_TRY(launch_gemm_f16x3(e, enc, cur16 ? EPI_RLS_R16_O16 : EPI_RLS_R32_O16, ch, nullptr, w.s_o.hi, nullptr,
-                                 w.s_o.unscale, w.bo, cur16 ? reinterpret_cast<const float*>(xh) : cur.pre, nullptr, xh,
-                                 reinterpret_cast<half_t*>(part), T, H, H, 1, cur.stat, cur.g, cur.b));
+        VR_TRY(launch_gemm_f16x3(e, enc, cur16 ? EPI_RLS_R16_O16 : EPI_RLS_R32_O16,
+                                 {.A = ch, .W = w.s_o, .bias = w.bo, .R = cur16 ? reinterpret_cast<const float*>(xh) : cur.pre, .Ch = xh,
+                                  .Cl = parth, .M = T, .N = H, .K = H, .passes = 1, .ln_stat = cur.stat, .ln_g = cur.g, .ln_b = cur.b}));
         hipLaunchKernelGGL(ln_finalize_kernel, dim3(fin_blocks), dim3(256), 0, s, part, T, segs, H, d.eps, s1);
       } else if (fold_big) {
-        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_RESIDUAL_LN_STATS, ch, nullptr, w.s_o.hi, nullptr, w.s_o.unscale, w.bo, cur.pre,
-                                 t1, xh, reinterpret_cast<half_t*>(part), T, H, H, 1, cur.stat, cur.g, cur.b));
+        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_RESIDUAL_LN_STATS,
+                                 {.A = ch, .W = w.s_o, .bias = w.bo, .R = cur.pre, .C = t1, .Ch = xh, .Cl = parth, .M = T, .N = H, .K = H,
+                                  .passes = 1, .ln_stat = cur.stat, .ln_g = cur.g, .ln_b = cur.b}));
         hipLaunchKernelGGL(ln_finalize_kernel, dim3(fin_blocks), dim3(256), 0, s, part, T, segs, H, d.eps, s1);
       } else
-      VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_RESIDUAL_LN, ch, nullptr, w.s_o.hi, nullptr, w.s_o.unscale, w.bo, cur.pre, t1,
-                               nullptr, nullptr, T, H, H, 1, cur.stat, cur.g, cur.b));
+        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_RESIDUAL_LN,
+                                 {.A = ch, .W = w.s_o, .bias = w.bo, .R = cur.pre, .C = t1, .M = T, .N = H, .K = H, .passes = 1,
+                                  .ln_stat = cur.stat, .ln_g = cur.g, .ln_b = cur.b}));
       if (fold_ln || fold_big)
         ;  // the attention-output LayerNorm runs inside the FFN-up projection below
       else if (H % 256 == 0)
@@ -4281,33 +4061,38 @@ static int forward_chunk(vr_engine* e, Encoder* enc, const int32_t* ids_dev, con
       const bool fg = fuse_glu(T);      // ... or, fused, the gate in the projection's epilogue over the re-ordered matrix
       const bool fgb = fuse_glu_big;
       if (fg && fold_ln)
-        VR_TRY(launch_skinny_ln(e, glu_epi, t1, w.ln1g, w.ln1b, d.eps, s1, w.s_1_p.hi, w.s_1_p.unscale, w.b1_p, fh, T, N1, H));
+        VR_TRY(launch_skinny_ln(e, glu_epi, t1, d.eps, s1,
+                                {.W = w.s_1_p, .bias = w.b1_p, .Ch = fh, .M = T, .N = N1, .K = H, .ln_g = w.ln1g, .ln_b = w.ln1b}));
       else if (fg)
-        VR_TRY(launch_gemm_f16x3(e, enc, glu_epi, xh, nullptr, w.s_1_p.hi, nullptr, w.s_1_p.unscale, w.b1_p, nullptr, nullptr, fh,
-                                 nullptr, T, N1, H, 1));
+        VR_TRY(launch_gemm_f16x3(e, enc, glu_epi, {.A = xh, .W = w.s_1_p, .bias = w.b1_p, .Ch = fh, .M = T, .N = N1, .K = H, .passes = 1}));
       else if (fgb)
-        VR_TRY(launch_gemm_f16x3(e, enc, d.ffn == VR_FFN_SWIGLU ? EPI_FOLD_SWIGLU : EPI_FOLD_GEGLU, xh, nullptr, w.s_1_fp.hi, nullptr,
-                                 w.s_1_fp.unscale, w.c_1_p, nullptr, nullptr, fh, nullptr, T, N1, H, 1, s1, w.cs_1_p, nullptr));
+        VR_TRY(launch_gemm_f16x3(e, enc, d.ffn == VR_FFN_SWIGLU ? EPI_FOLD_SWIGLU : EPI_FOLD_GEGLU,
+                                 {.A = xh, .W = w.s_1_fp, .bias = w.c_1_p, .Ch = fh, .M = T, .N = N1, .K = H, .passes = 1, .ln_stat = s1,
+                                  .ln_g = w.cs_1_p}));
       else if (fold_ln)
-        VR_TRY(launch_skinny_ln(e, gated ? EPI_BIAS_F16 : EPI_BIAS_GELU, t1, w.ln1g, w.ln1b, d.eps, s1, w.s_1.hi, w.s_1.unscale,
-                                w.b1, up_out, T, N1, H));
+        VR_TRY(launch_skinny_ln(e, gated ? EPI_BIAS_F16 : EPI_BIAS_GELU, t1, d.eps, s1,
+                                {.W = w.s_1, .bias = w.b1, .Ch = up_out, .M = T, .N = N1, .K = H, .ln_g = w.ln1g, .ln_b = w.ln1b}));
       else if (fold_big)
-        VR_TRY(launch_gemm_f16x3(e, enc, gated ? EPI_FOLD_F16 : EPI_FOLD_GELU, xh, nullptr, w.s_1_f.hi, nullptr, w.s_1_f.unscale,
-                                 w.c_1, nullptr, nullptr, up_out, nullptr, T, N1, H, 1, s1, w.cs_1, nullptr));
+        VR_TRY(launch_gemm_f16x3(e, enc, gated ? EPI_FOLD_F16 : EPI_FOLD_GELU,
+                                 {.A = xh, .W = w.s_1_f, .bias = w.c_1, .Ch = up_out, .M = T, .N = N1, .K = H, .passes = 1, .ln_stat = s1,
+                                  .ln_g = w.cs_1}));
       else
-      VR_TRY(launch_gemm_f16x3(e, enc, gated ? EPI_BIAS_F16 : EPI_BIAS_GELU, xh, nullptr, w.s_1.hi, nullptr, w.s_1.unscale, w.b1,
-                               nullptr, nullptr, up_out, nullptr, T, N1, H, 1));
+        VR_TRY(launch_gemm_f16x3(e, enc, gated ? EPI_BIAS_F16 : EPI_BIAS_GELU,
+                                 {.A = xh, .W = w.s_1, .bias = w.b1, .Ch = up_out, .M = T, .N = N1, .K = H, .passes = 1}));
       if (gated && !fg && !fgb) glu(T, nullptr, fh);
       if (res16)  // (the last layer of a mean-pooled model also writes f32 rows: the final LayerNorm reads them)
-        VR_TRY(launch_gemm_f16x3(e, enc, last ? EPI_RLS_R16_O32 : EPI_RLS_R16_O16, fh, nullptr, w.s_2.hi, nullptr, w.s_2.unscale,
-                                 w.b2, reinterpret_cast<const float*>(xh), last ? t2 : nullptr, xh,
-                                 reinterpret_cast<half_t*>(part), T, H, I, 1, mid.stat, mid.g, mid.b));
+        VR_TRY(launch_gemm_f16x3(e, enc, last ? EPI_RLS_R16_O32 : EPI_RLS_R16_O16,
+                                 {.A = fh, .W = w.s_2, .bias = w.b2, .R = reinterpret_cast<const float*>(xh), .C = last ? t2 : nullptr,
+                                  .Ch = xh, .Cl = parth, .M = T, .N = H, .K = I, .passes = 1, .ln_stat = mid.stat, .ln_g = mid.g,
+                                  .ln_b = mid.b}));
       else if (fold_big)
-        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_RESIDUAL_LN_STATS, fh, nullptr, w.s_2.hi, nullptr, w.s_2.unscale, w.b2, mid.pre,
-                                 t2, xh, reinterpret_cast<half_t*>(part), T, H, I, 1, mid.stat, mid.g, mid.b));
+        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_RESIDUAL_LN_STATS,
+                                 {.A = fh, .W = w.s_2, .bias = w.b2, .R = mid.pre, .C = t2, .Ch = xh, .Cl = parth, .M = T, .N = H, .K = I,
+                                  .passes = 1, .ln_stat = mid.stat, .ln_g = mid.g, .ln_b = mid.b}));
       else
-      VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_RESIDUAL_LN, fh, nullptr, w.s_2.hi, nullptr, w.s_2.unscale, w.b2, mid.pre, t2,
-                               nullptr, nullptr, T, H, I, 1, mid.stat, mid.g, mid.b));
+        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_RESIDUAL_LN,
+                                 {.A = fh, .W = w.s_2, .bias = w.b2, .R = mid.pre, .C = t2, .M = T, .N = H, .K = I, .passes = 1,
+                                  .ln_stat = mid.stat, .ln_g = mid.g, .ln_b = mid.b}));
       // the last LayerNorm of the network also stores its f32 rows (into the free buffer): pooling reads them
       if (fold_ln && !last)
         ;  // this layer's closing LayerNorm runs inside the next layer's Q/K/V projection
@@ -4325,27 +4110,27 @@ static int forward_chunk(vr_engine* e, Encoder* enc, const int32_t* ids_dev, con
       continue;
     }
     if (split)
-      VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_RESIDUAL, ch, cl, w.s_o.hi, w.s_o.lo, w.s_o.unscale, w.bo, enc->x,
-                               enc->tmp, nullptr, nullptr, T, H, H, passes));
+      VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_RESIDUAL, {.A = ch, .A_lo = cl, .W = w.s_o, .bias = w.bo, .R = enc->x, .C = enc->tmp,
+                                                           .M = T, .N = H, .K = H, .passes = passes}));
     else
       VR_TRY(launch_gemm(e, EPI_BIAS_RESIDUAL, enc->ctx, w.wo, w.bo, enc->x, enc->tmp, T, H, H));
     hipLaunchKernelGGL(layernorm_kernel, dim3(row_blocks), dim3(256), 0, s, enc->tmp, T, H, w.ln1g, w.ln1b,
                        d.eps, enc->x, xh, xl, static_cast<float2*>(nullptr));
     if (gated) {
       if (split)
-        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS, xh, xl, w.s_1.hi, w.s_1.lo, w.s_1.unscale, w.b1, nullptr, enc->glu, nullptr,
-                                 nullptr, T, N1, H, passes));
+        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS, {.A = xh, .A_lo = xl, .W = w.s_1, .bias = w.b1, .C = enc->glu, .M = T, .N = N1,
+                                                    .K = H, .passes = passes}));
       else
         VR_TRY(launch_gemm(e, EPI_BIAS, enc->x, w.w1, w.b1, nullptr, enc->glu, T, N1, H));
       glu(T, enc->ffn, fh);
     }
     if (split) {
       if (!gated) {
-        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_GELU, xh, xl, w.s_1.hi, w.s_1.lo, w.s_1.unscale, w.b1, nullptr,
-                                 nullptr, fh, fl, T, I, H, passes));
+        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_GELU, {.A = xh, .A_lo = xl, .W = w.s_1, .bias = w.b1, .Ch = fh, .Cl = fl, .M = T,
+                                                         .N = I, .K = H, .passes = passes}));
       }
-      VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_RESIDUAL, fh, fl, w.s_2.hi, w.s_2.lo, w.s_2.unscale, w.b2, enc->x,
-                               enc->tmp, nullptr, nullptr, T, H, I, passes));
+      VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_RESIDUAL, {.A = fh, .A_lo = fl, .W = w.s_2, .bias = w.b2, .R = enc->x, .C = enc->tmp,
+                                                           .M = T, .N = H, .K = I, .passes = passes}));
     } else {
       if (!gated) {
         VR_TRY(launch_gemm(e, EPI_BIAS_GELU, enc->x, w.w1, w.b1, nullptr, enc->ffn, T, I, H));
