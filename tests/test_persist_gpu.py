@@ -174,3 +174,118 @@ def test_compact_drops_tombstones_and_keeps_every_answer(gpu, dim, n):
     assert e.compact().shape[0] == e2.count()[0] and e.count()[0] == e.count()[1]
     e.close()
     e2.close()
+
+
+# ---- what a search lane and a compaction must carry from one state of the index to the next ---------------------------
+# 1,300 rows in an engine of 1,024: the second batch moves every per-row table, brings a folder id no filter table has
+# seen (7) and 263 x 2,048 new terms — more than half of the 2^20 slots the document-frequency table starts with, so it
+# re-hashes — and ends with 37 rows that carry no sparse vector. 1,300 is no multiple of 64 (SELL slice) or 16 (tile).
+_N0, _N_SPARSE, _N_PLAIN, _NEW_TERMS, _NEW_FOLDER = 1000, 263, 37, 2048, 7
+_FLT_FOLDERS = [1, _NEW_FOLDER]
+
+
+def _grown(e, between=lambda: None):
+    """Store the 1,300 rows in stages (1,000; `between()`; 263 with sparse vectors; 37 without); returns them."""
+    rng = np.random.default_rng(1300)
+    x0, (off0, idx0, val0), folder0, modified0 = _fill(e, rng, _N0, 64)
+    between()
+    n1 = _N_SPARSE + _N_PLAIN
+    x1 = rng.standard_normal((n1, 64)).astype(np.float32)
+    old = [np.sort(rng.choice(5000, size=10, replace=False)) for _ in range(_N_SPARSE)]   # terms the queries ask for
+    idx1 = np.concatenate([np.concatenate([o, 10_000 + r * _NEW_TERMS + np.arange(_NEW_TERMS)])
+                           for r, o in enumerate(old)]).astype(np.int32)
+    off1 = np.arange(_N_SPARSE + 1, dtype=np.int64) * (10 + _NEW_TERMS)
+    val1 = (rng.random(off1[-1]) + 0.25).astype(np.float32)
+    folder1 = np.full(n1, _NEW_FOLDER, np.int32)
+    modified1 = rng.integers(1_600_000_000, 1_700_000_000, size=n1).astype(np.int64)
+    e.upsert(x1[:_N_SPARSE], sparse=(off1, idx1, val1), folder_ids=folder1[:_N_SPARSE], modified=modified1[:_N_SPARSE])
+    e.upsert(x1[_N_SPARSE:], folder_ids=folder1[_N_SPARSE:], modified=modified1[_N_SPARSE:])
+    return dict(x=np.concatenate([x0, x1]), off=np.concatenate([off0, off0[-1] + off1[1:]]), idx=np.concatenate([idx0, idx1]),
+                val=np.concatenate([val0, val1]), folder=np.concatenate([folder0, folder1]),
+                modified=np.concatenate([modified0, modified1]))
+
+
+def _answers(e, flt):
+    """_queries (dense, batched dense, sparse and hybrid, filtered) and the batched sparse and hybrid searches."""
+    rng = np.random.default_rng(8)
+    q = rng.standard_normal((40, 64)).astype(np.float32)
+    sq = [(np.sort(rng.choice(5000, size=5, replace=False)).astype(np.int32), np.ones(5, np.float32)) for _ in range(40)]
+    return (_queries(e, np.random.default_rng(7), 64, flt), e.search_dense(q, 10, flt), e.search_sparse_batch(sq, 10),
+            e.search_sparse_batch(sq, 10, flt), e.search_hybrid_batch(q, sq, 10, 0.1, flt=flt))
+
+
+def _renumbered(res, remap):
+    if isinstance(res, tuple) and len(res) and isinstance(res[0], np.ndarray) and res[0].dtype == np.int64:
+        return (remap[res[0]],) + tuple(res[1:])
+    if isinstance(res, (tuple, list)):
+        return type(res)(_renumbered(r, remap) for r in res)
+    return res
+
+
+def _term_sample(d):
+    """20 term ids: 10 that the first batch brought, 10 that only the second did."""
+    return np.concatenate([d["idx"][:10], d["idx"][-10:]]).astype(np.int32)
+
+
+def test_a_reused_lane_sees_every_table_after_a_regrowth(gpu, monkeypatch):
+    """One search lane, used before and after an upsert that crosses the engine's capacity: its view of the index must
+    follow every table that moved (corpus, shadow, payload columns, SELL tables, inverted twin, the re-hashed document
+    frequencies, the folder maximum). The answers equal, bit for bit, those of an engine that never grew. (The rows
+    without a sparse vector need an upsert of their own, so the second engine takes 1,263 rows in one call and 37 in another.)"""
+    from voitta_rag_amd import Engine, SearchFilter
+
+    monkeypatch.setenv("VR_SEARCH_LANES", "1")
+    flt = SearchFilter(include_folders=_FLT_FOLDERS)
+    e = Engine(64, initial_rows=1024)
+    d = _grown(e, between=lambda: _answers(e, flt))
+    assert e.count() == (1300, 1300)
+    ids = _term_sample(d)
+    want_df = np.asarray([(d["idx"] == t).sum() for t in ids], np.int32)   # no row lists a term twice
+    df, points = e.sparse_stats(ids)
+    assert np.array_equal(df, want_df) and points == _N0 + _N_SPARSE
+    e2 = Engine(64, initial_rows=4096)
+    n = _N0 + _N_SPARSE
+    e2.upsert(d["x"][:n], sparse=(d["off"], d["idx"], d["val"]), folder_ids=d["folder"][:n], modified=d["modified"][:n])
+    e2.upsert(d["x"][n:], folder_ids=d["folder"][n:], modified=d["modified"][n:])
+    _same(_answers(e, flt), _answers(e2, flt))
+    _same(e.sparse_stats(ids), e2.sparse_stats(ids))
+    e.close()
+    e2.close()
+
+
+def test_what_a_compaction_carries_over(gpu, tmp_path):
+    """vr_compact replaces the index tables and leaves the totals alone: document frequencies, the sparse point count and
+    every (renumbered) answer are unchanged, the generation rises by one, and the compacted engine saves, loads and
+    keeps growing like any other."""
+    from voitta_rag_amd import Engine, SearchFilter
+
+    flt = SearchFilter(include_folders=_FLT_FOLDERS)
+    e = Engine(64, initial_rows=1024)
+    d = _grown(e)
+    rng = np.random.default_rng(31)
+    dead = np.union1d(rng.choice(1300, size=300, replace=False),          # about a third in all, with
+                      np.concatenate([np.arange(128, 256),                # two whole 64-row slices
+                                      np.arange(1270, 1290)]))            # and rows without a sparse vector
+    e.delete_rows(dead)
+    ids = _term_sample(d)
+    stats, counts, before, generation = e.sparse_stats(ids), e.count(), _answers(e, flt), e.generation()
+    assert counts == (1300, 1300 - dead.size)
+    remap = e.compact()
+    assert (remap[dead] == -1).all() and e.count() == (counts[1], counts[1])
+    assert e.generation() == generation + 1
+    _same(stats, e.sparse_stats(ids))
+    after = _answers(e, flt)
+    _same(_renumbered(before, remap), after)
+    path = str(tmp_path / "compacted.vrindex")
+    e.save(path)
+    e2 = Engine(64)
+    e2.load(path)
+    assert e2.count() == e.count()
+    _same(stats, e2.sparse_stats(ids))
+    _same(after, _answers(e2, flt))
+    for eng in (e, e2):
+        _fill(eng, np.random.default_rng(99), 100, 64)
+    _same(_answers(e, flt), _answers(e2, flt))
+    assert e.count() == e2.count()
+    e.close()
+    e2.close()

@@ -132,121 +132,10 @@ static int search_sparse_block(vr_engine* e, const int32_t* q_idx, const float* 
 
 // ---- search lanes and the writer protocol (see vr_engine::rw) -----------------------------------------------
 
-static void release_scratch(vr_engine* e) {
-  e->upper.release();
-  e->cand_rows.release();
-  e->cand_keys.release();
-  e->stage_dense.release();
-  e->stage_len.release();
-  e->stage_off.release();
-  e->stage_idx.release();
-  e->stage_val.release();
-  e->stage_i32a.release();
-  e->stage_i32b.release();
-  e->stage_i64a.release();
-  e->stage_i64b.release();
-  e->stage_f64.release();
-  e->bm_marks.release();
-  e->bm_cnt.release();
-  e->bm_idx.release();
-  e->bm_val.release();
-  e->enc_out.release();
-  e->q_tiled.release();
-  e->scores.release();
-  e->sp_scores.release();
-  e->mask.release();
-  e->pass_folder.release();
-  e->pass_ifolder.release();
-  e->cand_a.release();
-  e->cand_b.release();
-  e->sp_cand.release();
-  e->q_ids.release();
-  e->q_w.release();
-  e->bq_hat.release();
-  e->bq_params.release();
-  e->bq_best.release();
-  e->bq_thr.release();
-  e->bq_img.release();
-  e->bq_cand.release();
-  e->bq_cnt.release();
-  e->bq_keys.release();
-  e->bq_tile_ub.release();
-  e->bq_pairs.release();
-  e->bq_stage.release();
-  e->qt_emb.release();
-  e->qt_pick.release();
-  e->qt_gather.release();
-  e->cls_planes.release();
-  e->cls_of_q.release();
-  e->cls_pass.release();
-  e->cls_desc.release();
-  e->sq_off.release();
-  e->sq_ids.release();
-  e->sq_val.release();
-  e->sq_w.release();
-  e->sq_keys.release();
-  e->mg_in.release();
-  e->mg_gid.release();
-  e->mg_score.release();
-  e->mg_cnt.release();
-  e->mmr_ws.release();
-  e->mmr_gram.release();
-  e->mmr_rows.release();
-  e->mmr_rel.release();
-  e->mmr_lists.release();
-  e->mmr_tiles.release();
-  e->mmr_pairs.release();
-  e->mmr_out.release();
-  if (e->pinned) (void)hipHostFree(e->pinned);
-  e->pinned = nullptr;
-  if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
-  if (e->ev_join) (void)hipEventDestroy(e->ev_join);
-  if (e->ev_input) (void)hipEventDestroy(e->ev_input);
-  if (e->aux_stream) (void)hipStreamDestroy(e->aux_stream);
-  if (e->own_stream) (void)hipStreamDestroy(e->own_stream);
-  e->ev_fork = e->ev_join = e->ev_input = nullptr;
-  e->aux_stream = e->own_stream = nullptr;
-}
-
 // the index as the master holds it right now: pointers and counts only (call with rw held)
 static void lane_view(vr_engine* L, const vr_engine* m) {
-  L->n_rows = m->n_rows;
-  L->n_live = m->n_live;
-  L->cap_rows = m->cap_rows;
-  L->corpus = m->corpus;
-  L->corpus16 = m->corpus16;
-  L->row_scale = m->row_scale;
-  L->row_err = m->row_err;
-  L->centre = m->centre;
-  L->centre_norm = m->centre_norm;
-  L->centre_rows = m->centre_rows;
-  L->centre_checked_rows = m->centre_checked_rows;
-  L->live = m->live;
-  L->folder = m->folder;
-  L->index_folder = m->index_folder;
-  L->created = m->created;
-  L->modified = m->modified;
-  L->row_slice = m->row_slice;
-  L->max_folder_id = m->max_folder_id;
-  L->max_index_folder_id = m->max_index_folder_id;
-  L->slices = m->slices;
-  L->n_slices_dev = m->n_slices_dev;
-  L->sp_idx = m->sp_idx;
-  L->sp_val = m->sp_val;
-  L->sp_used = m->sp_used;
-  L->n_sparse_points = m->n_sparse_points;
-  L->inv_key = m->inv_key;
-  L->inv_val = m->inv_val;
-  L->inv_seg = m->inv_seg;
-  L->inv_used = m->inv_used;
-  L->n_inv_seg = m->n_inv_seg;
-  L->inv_slices = m->inv_slices;
-  L->sp_has_dups = m->sp_has_dups;
-  L->df_keys = m->df_keys;
-  L->df_cnt = m->df_cnt;
-  L->df_cap = m->df_cap;
-  L->df_bound = m->df_bound;
-  L->df_distinct = m->df_distinct;
+  static_cast<IndexTables&>(*L) = *m;
+  static_cast<IndexTotals&>(*L) = *m;
   L->profiler = m->profiler;
 }
 
@@ -274,7 +163,7 @@ static vr_engine* lane_create(vr_engine* m) {
             hipHostGetDevicePointer(&L->pinned_dev, L->pinned, 0) == hipSuccess;
   if (!ok) {
     set_error("creating a search lane failed");
-    release_scratch(L);
+    L->LaneResources::release();
     delete L;
     return nullptr;
   }
@@ -318,16 +207,7 @@ struct SearchLane {
   }
   ~SearchLane() {
     if (!L) return;
-    m->stat_two_stage += L->stat_two_stage.exchange(0);
-    m->stat_fallback += L->stat_fallback.exchange(0);
-    m->stat_batched += L->stat_batched.exchange(0);
-    m->stat_batch_fallback += L->stat_batch_fallback.exchange(0);
-    m->stat_batch_cands += L->stat_batch_cands.exchange(0);
-    m->stat_sparse_grouped += L->stat_sparse_grouped.exchange(0);
-    m->stat_sparse_group_redo += L->stat_sparse_group_redo.exchange(0);
-    m->stat_sparse_group_cands += L->stat_sparse_group_cands.exchange(0);
-    const int64_t lc = L->stat_last_candidates.exchange(-1);
-    if (lc >= 0) m->stat_last_candidates.store(lc);
+    L->drain_into(*m);
     if (lock.owns_lock()) lock.unlock();
     {
       std::lock_guard<std::mutex> g(m->lane_mu);
@@ -415,33 +295,17 @@ void vr_engine_destroy(vr_engine* e) {
   if (e->stream) (void)hipStreamSynchronize(e->stream);
   encoder_release(e);
   prof_release(e);
-  e->corpus.release();
-  e->corpus16.release();
-  e->row_err.release();
-  e->row_scale.release();
-  e->centre.release();
-  e->centre_sum.release();
-  for (vr_engine* L : e->lanes_all) {
+  for (vr_engine* L : e->lanes_all) {  // (a lane holds views of the index, its own resources and scratch)
     if (L->own_stream) (void)hipStreamSynchronize(L->own_stream);
-    release_scratch(L);
+    L->LaneResources::release();
     delete L;
   }
   e->lanes_all.clear();
   e->lanes_free.clear();
-  e->live.release();
-  e->folder.release();
-  e->index_folder.release();
-  e->created.release();
-  e->modified.release();
-  e->row_slice.release();
-  e->slices.release();
-  e->sp_idx.release();
-  e->sp_val.release();
-  inv_release(e);
-  e->df_keys.release();
-  e->df_cnt.release();
-  if (e->df_distinct) (void)hipFree(e->df_distinct);
-  release_scratch(e);
+  e->IndexTables::release();
+  e->IndexTotals::release();
+  for (float* p : e->query_rows_free) (void)hipFree(p);
+  e->LaneResources::release();
   delete e;
 }
 
@@ -1875,23 +1739,13 @@ int vr_df_apply(vr_engine* e, const int32_t* ids, int64_t n_ids, int mem, int64_
 
 namespace {
 
-// a few device rows for query embeddings in flight (one per concurrent vr_query_text)
-struct QueryRows {
-  std::mutex mu;
-  std::vector<float*> free_rows;
-  ~QueryRows() {
-    for (float* p : free_rows) (void)hipFree(p);
-  }
-};
-QueryRows g_query_rows[16];  // per device (indexed by ordinal % 16; rows are kMaxDim floats, any engine fits)
-
-float* take_query_row(int device) {
-  QueryRows& q = g_query_rows[device & 15];
+// a device row for a query embedding in flight: from the engine's free list (released by vr_engine_destroy), or a new one
+float* take_query_row(vr_engine* e) {
   {
-    std::lock_guard<std::mutex> g(q.mu);
-    if (!q.free_rows.empty()) {
-      float* p = q.free_rows.back();
-      q.free_rows.pop_back();
+    std::lock_guard<std::mutex> g(e->query_rows_mu);
+    if (!e->query_rows_free.empty()) {
+      float* p = e->query_rows_free.back();
+      e->query_rows_free.pop_back();
       return p;
     }
   }
@@ -1900,10 +1754,9 @@ float* take_query_row(int device) {
   return p;
 }
 
-void give_query_row(int device, float* p) {
-  QueryRows& q = g_query_rows[device & 15];
-  std::lock_guard<std::mutex> g(q.mu);
-  q.free_rows.push_back(p);
+void give_query_row(vr_engine* e, float* p) {
+  std::lock_guard<std::mutex> g(e->query_rows_mu);
+  e->query_rows_free.push_back(p);
 }
 
 // token ids of n (prefixed) questions, packed: ids and n + 1 offsets as vr_encode takes them (host threads)
@@ -2003,13 +1856,13 @@ int query_text(vr_engine* e, const Tokenizer* tokenizer, const char* dense_text,
   }
   // 2. the embedding, left in device memory (the encoder is shared with the writers: one forward pass at a time)
   VR_CHECK(encoder_hidden(e) == e->dim, "encoder width %d != store dimension %d", encoder_hidden(e), e->dim);
-  float* q_dev = take_query_row(e->device);
+  float* q_dev = take_query_row(e);
   VR_CHECK(q_dev != nullptr, "no device memory for the query embedding");
   struct Giver {
-    int device;
+    vr_engine* e;
     float* p;
-    ~Giver() { give_query_row(device, p); }
-  } giver{e->device, q_dev};
+    ~Giver() { give_query_row(e, p); }
+  } giver{e, q_dev};
   const bool hybrid = !stems.empty();
   if (out_hybrid) *out_hybrid = hybrid ? 1 : 0;
   // (VR_QUERY_TEXT_LANE_FIRST=0: the forward pass, then vr_search_hybrid as a caller would — the round's earlier form, for A/B timings)

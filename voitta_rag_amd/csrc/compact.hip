@@ -116,65 +116,32 @@ int engine_compact(vr_engine* e, int64_t* new_row_of_old, int64_t* n_rows_after)
   if (n_new == n_old) return 0;  // nothing to reclaim
   hipStream_t s = e->stream;
 
-  vr_engine t;  // the shadow
+  vr_engine t;  // the shadow (its scratch goes with it)
   t.device = e->device;
   t.dim = e->dim;
   t.kblocks = e->kblocks;
   t.prefilter = e->prefilter;
   t.prefilter8 = e->prefilter8;
   t.stream = s;  // (the master's stream: searches run on their lanes' streams)
-  // temporaries of the rebuild (released by fail() on every path out)
-  DevArray<int32_t> map, cnt, tmp_idx;
-  DevArray<float> tmp_val;
-  DevArray<int64_t> begin;
-  DevArray<uint8_t> has_sparse;
-  auto fail = [&](int rc) {
-    (void)hipStreamSynchronize(s);
-    map.release();
-    cnt.release();
-    tmp_idx.release();
-    tmp_val.release();
-    begin.release();
-    has_sparse.release();
-    t.corpus.release();
-    t.corpus16.release();
-    t.row_err.release();
-    t.row_scale.release();
-    t.centre.release();
-    t.centre_sum.release();
-    t.live.release();
-    t.folder.release();
-    t.index_folder.release();
-    t.created.release();
-    t.modified.release();
-    t.row_slice.release();
-    t.slices.release();
-    t.sp_idx.release();
-    t.sp_val.release();
-    inv_release(&t);
-    t.stage_i32a.release();
-    t.stage_i32b.release();
-    return rc;
-  };
-#define VR_CTRY(expr)                  \
-  do {                                 \
-    const int rc_ = (expr);            \
-    if (rc_ != 0) return fail(rc_);    \
-  } while (0)
-  // HIP calls behind this point fail through fail() as well: a plain VR_HIP return would leak the shadow — a full-size copy
-  // of the index (and the temporaries below, which own their memory and are released by their destructors or here)
-#define VR_CHIP(call)                                                                                       \
-  do {                                                                                                      \
-    hipError_t err_ = (call);                                                                               \
-    if (err_ != hipSuccess) {                                                                               \
-      ::vr::set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(err_), __FILE__, __LINE__);         \
-      return fail(-1);                                                                                      \
-    }                                                                                                       \
-  } while (0)
-  VR_CTRY(ensure_rows(&t, std::max<int64_t>(e->cap_rows, 1024)));  // same capacity: later appends find the room they had
+  // temporaries of the rebuild
+  OwnedArray<int32_t> map, cnt, tmp_idx;
+  OwnedArray<float> tmp_val;
+  OwnedArray<int64_t> begin;
+  OwnedArray<uint8_t> has_sparse;
+  // On every path out, and before the temporaries and the shadow's scratch are freed (it is declared after them): wait for
+  // the kernels that use them, then release the index the shadow holds — half built after a failure (a full-size copy),
+  // the old one after the swap (no search can still be reading it).
+  struct ShadowGuard {
+    vr_engine& t;
+    ~ShadowGuard() {
+      (void)hipStreamSynchronize(t.stream);
+      t.IndexTables::release();
+    }
+  } guard{t};
+  VR_TRY(ensure_rows(&t, std::max<int64_t>(e->cap_rows, 1024)));  // same capacity: later appends find the room they had
 
-  VR_CTRY(map.grow(std::max<int64_t>(n_new, 1), 0, s));
-  if (n_new) VR_CHIP(hipMemcpyAsync(map.p, old_of_new.data(), sizeof(int32_t) * static_cast<size_t>(n_new), hipMemcpyHostToDevice, s));
+  VR_TRY(map.grow(std::max<int64_t>(n_new, 1), 0, s));
+  if (n_new) VR_HIP(hipMemcpyAsync(map.p, old_of_new.data(), sizeof(int32_t) * static_cast<size_t>(n_new), hipMemcpyHostToDevice, s));
 
   // ---- sparse rows out of the old slices, into a temporary CSR
   std::vector<int32_t> cnt_host(static_cast<size_t>(n_new));
@@ -182,18 +149,18 @@ int engine_compact(vr_engine* e, int64_t* new_row_of_old, int64_t* n_rows_after)
   const bool any_sparse = !e->slices_host.empty() && n_new > 0;
   if (any_sparse) {
     const unsigned blocks = static_cast<unsigned>((n_new + 255) / 256);
-    VR_CTRY(cnt.grow(n_new, 0, s));
+    VR_TRY(cnt.grow(n_new, 0, s));
     hipLaunchKernelGGL(count_entries_kernel, dim3(blocks), dim3(256), 0, s, map.p, n_new, e->row_slice.p, e->slices.p,
                        e->sp_idx.p, cnt.p);
-    VR_CHIP(hipMemcpyAsync(cnt_host.data(), cnt.p, sizeof(int32_t) * static_cast<size_t>(n_new), hipMemcpyDeviceToHost, s));
-    VR_CHIP(hipStreamSynchronize(s));
+    VR_HIP(hipMemcpyAsync(cnt_host.data(), cnt.p, sizeof(int32_t) * static_cast<size_t>(n_new), hipMemcpyDeviceToHost, s));
+    VR_HIP(hipStreamSynchronize(s));
     for (int64_t i = 0; i < n_new; ++i) begin_host[static_cast<size_t>(i) + 1] = begin_host[static_cast<size_t>(i)] + cnt_host[static_cast<size_t>(i)];
     const int64_t nnz = begin_host.back();
-    VR_CTRY(begin.grow(n_new + 1, 0, s));
-    VR_CTRY(tmp_idx.grow(std::max<int64_t>(nnz, 1), 0, s));
-    VR_CTRY(tmp_val.grow(std::max<int64_t>(nnz, 1), 0, s));
-    VR_CTRY(has_sparse.grow(n_new, 0, s));
-    VR_CHIP(hipMemcpyAsync(begin.p, begin_host.data(), sizeof(int64_t) * (static_cast<size_t>(n_new) + 1), hipMemcpyHostToDevice, s));
+    VR_TRY(begin.grow(n_new + 1, 0, s));
+    VR_TRY(tmp_idx.grow(std::max<int64_t>(nnz, 1), 0, s));
+    VR_TRY(tmp_val.grow(std::max<int64_t>(nnz, 1), 0, s));
+    VR_TRY(has_sparse.grow(n_new, 0, s));
+    VR_HIP(hipMemcpyAsync(begin.p, begin_host.data(), sizeof(int64_t) * (static_cast<size_t>(n_new) + 1), hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(extract_entries_kernel, dim3(blocks), dim3(256), 0, s, map.p, n_new, e->row_slice.p, e->slices.p,
                        e->sp_idx.p, e->sp_val.p, begin.p, tmp_idx.p, tmp_val.p, has_sparse.p);
   }
@@ -202,63 +169,32 @@ int engine_compact(vr_engine* e, int64_t* new_row_of_old, int64_t* n_rows_after)
   if (n_new)
     hipLaunchKernelGGL(gather_dense_kernel, dim3(static_cast<unsigned>((n_new + 3) / 4)), dim3(256), 0, s, e->corpus.p, map.p,
                        n_new, e->dim, e->kblocks, t.corpus.p);
-  VR_CTRY(gather_column(s, e->folder, t.folder, map.p, n_new));
-  VR_CTRY(gather_column(s, e->index_folder, t.index_folder, map.p, n_new));
-  VR_CTRY(gather_column(s, e->created, t.created, map.p, n_new));
-  VR_CTRY(gather_column(s, e->modified, t.modified, map.p, n_new));
-  VR_CHIP(hipMemsetAsync(t.live.p, 1, static_cast<size_t>(n_new), s));  // (ensure_rows zeroed the rest)
-  VR_CHIP(hipMemsetAsync(t.row_slice.p, 0xFF, sizeof(int32_t) * static_cast<size_t>(t.cap_rows), s));  // -1
+  VR_TRY(gather_column(s, e->folder, t.folder, map.p, n_new));
+  VR_TRY(gather_column(s, e->index_folder, t.index_folder, map.p, n_new));
+  VR_TRY(gather_column(s, e->created, t.created, map.p, n_new));
+  VR_TRY(gather_column(s, e->modified, t.modified, map.p, n_new));
+  VR_HIP(hipMemsetAsync(t.live.p, 1, static_cast<size_t>(n_new), s));  // (ensure_rows zeroed the rest)
+  VR_HIP(hipMemsetAsync(t.row_slice.p, 0xFF, sizeof(int32_t) * static_cast<size_t>(t.cap_rows), s));  // -1
 
   // ---- sparse index re-packed in the new row order; the df table and the point count carry over as they are
   t.n_rows = n_new;
   t.n_live = n_new;
   if (any_sparse) {
-    VR_CTRY(sparse_append(&t, n_new, 0, cnt_host.data(), begin.p, nullptr, tmp_idx.p, tmp_val.p, /*account=*/false));
+    VR_TRY(sparse_append(&t, n_new, 0, cnt_host.data(), begin.p, nullptr, tmp_idx.p, tmp_val.p, /*account=*/false));
     hipLaunchKernelGGL(restore_no_sparse_kernel, dim3(static_cast<unsigned>((n_new + 255) / 256)), dim3(256), 0, s,
                        has_sparse.p, n_new, t.row_slice.p);
   }
-  VR_CTRY(prefilter_recentre(&t));  // the shadow of the compacted rows, around THEIR column mean
-  VR_CHIP(hipStreamSynchronize(s));
-  VR_CHIP(hipGetLastError());
-#undef VR_CTRY
-#undef VR_CHIP
+  VR_TRY(prefilter_recentre(&t));  // the shadow of the compacted rows, around THEIR column mean
+  VR_HIP(hipStreamSynchronize(s));
+  VR_HIP(hipGetLastError());
 
   {  // ---- the swap: the only moment searches wait for
     PublishLock publish(e);
-    std::swap(e->corpus, t.corpus);
-    std::swap(e->corpus16, t.corpus16);
-    std::swap(e->row_err, t.row_err);
-    std::swap(e->row_scale, t.row_scale);
-    std::swap(e->centre, t.centre);
-    std::swap(e->centre_norm, t.centre_norm);
-    std::swap(e->centre_rows, t.centre_rows);
-    std::swap(e->centre_checked_rows, t.centre_checked_rows);
-    std::swap(e->live, t.live);
-    std::swap(e->folder, t.folder);
-    std::swap(e->index_folder, t.index_folder);
-    std::swap(e->created, t.created);
-    std::swap(e->modified, t.modified);
-    std::swap(e->row_slice, t.row_slice);
-    std::swap(e->slices, t.slices);
-    std::swap(e->sp_idx, t.sp_idx);
-    std::swap(e->sp_val, t.sp_val);
+    std::swap(static_cast<IndexTables&>(*e), static_cast<IndexTables&>(t));  // (the totals stay the master's own)
     e->slices_host.swap(t.slices_host);
-    std::swap(e->inv_key, t.inv_key);
-    std::swap(e->inv_val, t.inv_val);
-    std::swap(e->inv_seg, t.inv_seg);
-    std::swap(e->inv_used, t.inv_used);
-    std::swap(e->n_inv_seg, t.n_inv_seg);
-    std::swap(e->inv_slices, t.inv_slices);
-    std::swap(e->inv_rows, t.inv_rows);
-    e->n_slices_dev = t.n_slices_dev;
-    e->sp_used = t.sp_used;
-    e->cap_rows = t.cap_rows;
-    e->n_rows = n_new;
-    e->n_live = n_new;
     e->generation.fetch_add(1);
   }
-  fail(0);  // what the shadow holds now is the old index: release it and the temporaries (no search can still be reading it)
-  return 0;
+  return 0;  // (the guard releases the old index, now the lock is dropped)
 }
 
 }  // namespace vr

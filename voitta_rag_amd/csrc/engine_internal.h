@@ -13,6 +13,8 @@
 #include <mutex>
 #include <shared_mutex>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "voitta_engine.h"
@@ -97,6 +99,19 @@ struct DevArray {
     p = nullptr;
     cap = 0;
   }
+};
+
+// A DevArray that owns its memory: freed with the object, move-only. Scratch and temporaries are of this type; the index
+// tables stay plain DevArray handles, because views copy them and a compaction swaps them.
+template <class T>
+struct OwnedArray : DevArray<T> {
+  OwnedArray() = default;
+  OwnedArray(OwnedArray&& o) noexcept : DevArray<T>(o) { static_cast<DevArray<T>&>(o) = {}; }
+  OwnedArray& operator=(OwnedArray&& o) noexcept {
+    std::swap(static_cast<DevArray<T>&>(*this), static_cast<DevArray<T>&>(o));
+    return *this;
+  }
+  ~OwnedArray() { this->release(); }
 };
 
 // One SELL-64 slice of the sparse index: 64 consecutive rows, entries stored in chunks of 4
@@ -197,25 +212,251 @@ struct ClassPlanes {
   const int32_t* q_cls;
 };
 
-}  // namespace vr
 
-struct vr_engine {
-  int device = 0;
-  int dim = 0;
-  int kblocks = 0;  // dim / 16
+// ---- the engine's state, grouped by lifetime. vr_engine derives from every group, so members are reached as e->corpus,
+// e->n_rows and so on. A new member goes into the group whose lifetime it shares; nothing else has to be edited.
+
+// What a compaction replaces wholesale (engine_compact swaps this group) and a search lane views.
+struct IndexTables {
+  int64_t n_rows = 0;
+  int64_t n_live = 0;
+  int64_t cap_rows = 0;  // multiple of 64
+
+  // dense corpus, MFMA-tiled: [row/16][k/16][tile_pos(k%4, row%16)][c = (k%16)/4]
+  DevArray<float> corpus;
+  // f16 shadow of the corpus for the two-stage exact search (prefilter.hip), present when vr_engine::prefilter:
+  // [row/16][k/32][lane = (k%32)/8*16 + row%16][8 halfs], plus the exact rounding residual |x - f16(x)|_2 of every row.
+  // int8 form (vr_engine::prefilter8): corpus16 then holds [row/16][k/64][lane = (k%64)/16*16 + row%16][16 int8] with one
+  // scale per row (row_scale), and row_err the exact residual |x - scale * int8(x)|_2. Half the bytes of the f16 shadow again.
+  DevArray<uint16_t> corpus16;
+  DevArray<float> row_scale;
+  DevArray<float> row_err;
+  // Centre of the int8 shadow (prefilter.hip "centred shadow"): the shadow holds the quantised RESIDUALS x - centre.
+  // Any fixed vector is valid (a shift of every score by centre.q cancels out of the candidate test); the column
+  // mean of the stored rows makes the residuals of a real embedding collection — rows that share a common direction —
+  // several times smaller than the rows, and the bound with them. Recomputed (and the whole shadow rebuilt, ~1 ms per
+  // million rows) whenever the collection has doubled since the last time, after a compaction and after a load.
+  DevArray<float> centre;          // [dim], zeros until the collection holds kCentreMinRows rows
+  float centre_norm = 0.0f;        // |centre|_2, rounded up
+  int64_t centre_rows = 0;         // rows the collection held when the centre was last recomputed
+  int64_t centre_checked_rows = 0; // rows it held when a re-centring was last ATTEMPTED (centring switched off, or a non-finite
+                                   // centre, leaves centre_rows at 0: without this every upsert would rebuild the whole shadow)
+  // payload columns
+  DevArray<uint8_t> live;
+  DevArray<int32_t> folder;
+  DevArray<int32_t> index_folder;
+  DevArray<int64_t> created;
+  DevArray<int64_t> modified;
+  DevArray<int32_t> row_slice;  // slice index of the row's sparse vector, -1 = none
+
+  // sparse index (SELL-64, see SliceDesc); the host copy of the descriptors is vr_engine::slices_host
+  DevArray<SliceDesc> slices;
+  int64_t n_slices_dev = 0;
+  DevArray<int32_t> sp_idx;
+  DevArray<float> sp_val;
+  int64_t sp_used = 0;
+
+  // inverted twin of the SELL index (invert.hip), derived data: rebuilt by vr_load and vr_compact
+  DevArray<uint64_t> inv_key;
+  DevArray<float> inv_val;
+  DevArray<InvSeg> inv_seg;
+  int64_t inv_used = 0;      // postings
+  int64_t n_inv_seg = 0;
+  int64_t inv_slices = 0;    // slices the inverted index covers (== n_slices_dev when usable)
+  int64_t inv_rows = 0;      // rows its segments span
+
+  void release() {  // by the owner (the master, or the shadow of a compaction), never through a lane's view
+    corpus.release();
+    corpus16.release();
+    row_scale.release();
+    row_err.release();
+    centre.release();
+    live.release();
+    folder.release();
+    index_folder.release();
+    created.release();
+    modified.release();
+    row_slice.release();
+    slices.release();
+    sp_idx.release();
+    sp_val.release();
+    inv_key.release();
+    inv_val.release();
+    inv_seg.release();
+    *this = IndexTables{};
+  }
+};
+
+// What a compaction carries over untouched and a search lane views as well.
+struct IndexTotals {
+  // document-frequency table: open addressing, key -1 = empty
+  DevArray<int32_t> df_keys;
+  DevArray<int32_t> df_cnt;
+  int64_t df_cap = 0;          // power of two
+  int64_t df_bound = 0;        // upper bound of distinct keys (exact count + nnz since last read)
+  int32_t* df_distinct = nullptr;  // device counter
+  int64_t n_sparse_points = 0;
+  int32_t max_folder_id = -1;
+  int32_t max_index_folder_id = -1;
+  bool sp_has_dups = false;  // some row lists a term twice: queries stay on the forward scan
+
+  void release() {  // by the master only
+    df_keys.release();
+    df_cnt.release();
+    if (df_distinct) (void)hipFree(df_distinct);
+    *this = IndexTotals{};
+  }
+};
+static_assert(std::is_trivially_copyable_v<IndexTables>, "a lane view and the compaction swap copy it as a whole");
+static_assert(std::is_trivially_copyable_v<IndexTotals>, "a lane view copies it as a whole");
+
+// Working memory of whoever runs kernels on this engine object (the master's writer, a search lane, the shadow of a
+// compaction): never shared, freed with the object.
+struct Scratch {
+  OwnedArray<float> centre_sum;     // [dim] column sums of a re-centring
+  OwnedArray<unsigned long long> inv_counter;  // [0] postings emitted by the current inverted build, [1] duplicates seen
+  OwnedArray<float> upper;          // [cap_rows] upper bounds of the last prefilter pass
+  OwnedArray<int32_t> cand_rows;    // candidate rows (+ counter at the end)
+  OwnedArray<uint64_t> cand_keys;
+  OwnedArray<float> stage_dense;    // host->device staging of upsert / query rows
+  OwnedArray<float> stage_len;      // per-row length
+  OwnedArray<int64_t> stage_off;
+  OwnedArray<int32_t> stage_idx;
+  OwnedArray<float> stage_val;
+  OwnedArray<int32_t> stage_i32a;
+  OwnedArray<int32_t> stage_i32b;
+  OwnedArray<int64_t> stage_i64a;
+  OwnedArray<int64_t> stage_i64b;
+  OwnedArray<double> stage_f64;
+  OwnedArray<int32_t> bm_marks;     // bm25_tf_kernel scratch for documents longer than its LDS
+  OwnedArray<int32_t> bm_cnt;       // vr_index_batch: per-document distinct terms
+  OwnedArray<int32_t> bm_idx;       //                 padded term ids
+  OwnedArray<float> bm_val;         //                 padded tf weights (f32, as stored)
+  OwnedArray<float> enc_out;        //                 encoder output rows
+  OwnedArray<float> q_tiled;       // 16-query image, kblocks KiB
+  OwnedArray<float> scores;         // [16][cap_rows]
+  OwnedArray<float> sp_scores;      // [cap_rows]
+  OwnedArray<uint8_t> mask;         // [cap_rows]
+  OwnedArray<uint8_t> pass_folder;  // per folder id
+  OwnedArray<uint8_t> pass_ifolder;
+  OwnedArray<uint64_t> cand_a;
+  OwnedArray<uint64_t> cand_b;
+  OwnedArray<uint64_t> sp_cand;  // per-block lists of the fused sparse scan
+  OwnedArray<int32_t> q_ids;
+  OwnedArray<float> q_w;
+  // batched dense search (batch.hip): preprocessed queries, their int8 images and constants, per-slab bounds,
+  // thresholds, candidate rows / counts (+ overflow flags), exact keys (+ results)
+  OwnedArray<float> bq_hat, bq_params, bq_best, bq_thr;
+  OwnedArray<int32_t> bq_img, bq_cand, bq_cnt;
+  OwnedArray<uint64_t> bq_keys;
+  OwnedArray<uint16_t> bq_tile_ub;  // f16 bits: per (16-row tile, query) the largest upper bound (rounded up)
+  OwnedArray<int32_t> bq_pairs;     // per query: the tiles whose bound reaches its threshold ([nq][kBatchCand]), then the counts [nq]
+  OwnedArray<float> bq_stage;  // host queries staged on the device
+  // vr_query_text_batch: the questions' embeddings (n x dim), and them gathered hybrid-first by the picks
+  OwnedArray<float> qt_emb;
+  OwnedArray<int32_t> qt_pick;
+  OwnedArray<float> qt_gather;
+  // filtered batches (vr_search_*_multi): one bit plane per class of filter ([class][plane words], bit r % 32 of word
+  // r / 32 = row r passes), the class of every query of the batch, and the classes' pass tables and descriptors
+  OwnedArray<uint32_t> cls_planes;
+  OwnedArray<int32_t> cls_of_q;
+  OwnedArray<uint8_t> cls_pass;
+  OwnedArray<ClassDesc> cls_desc;
+  // batched sparse search (invert.hip): the queries' terms as CSR (offsets, ascending distinct ids, raw values,
+  // weights q_t * idf_t) and the nq x k result keys
+  OwnedArray<int32_t> sq_off, sq_ids;
+  OwnedArray<float> sq_val, sq_w;
+  OwnedArray<uint64_t> sq_keys;
+  // ... grouped form (sparse_inv_group_kernel): the group tables, per query a candidate buffer and its fill count
+  OwnedArray<int32_t> sq_grp, sq_cnt;
+  const int32_t* sq_overflow_q = nullptr;  // (into sq_cnt) per query of the last grouped batch: 1 = its candidates overflowed
+  OwnedArray<uint64_t> sq_cand;   // (+ the groups' threshold keys behind the buffers)
+  OwnedArray<int32_t> sq_bounds;  // int2 run bounds per (segment, distinct term), then per (segment, group, union term)
+  OwnedArray<float> sq_entw;      // weights per (group, union term, query of the group)
+  std::vector<int32_t> sq_grp_host;
+  // vr_merge_keys: the parts' keys staged on the device, merged global ids / scores / counts
+  OwnedArray<uint64_t> mg_in;
+  OwnedArray<int64_t> mg_gid;
+  OwnedArray<float> mg_score;
+  OwnedArray<int32_t> mg_cnt;
+  // vr_mmr_select (mmr.hip): the gathered candidate rows (MFMA-tiled, 16-row tiles per list), the lists' Gram matrices,
+  // the slice's rows / relevance / list descriptors / tile -> list map / (list, tile column) pairs, and the picks
+  OwnedArray<float> mmr_ws;
+  OwnedArray<float> mmr_gram;
+  OwnedArray<int64_t> mmr_rows;
+  OwnedArray<double> mmr_rel;
+  OwnedArray<MmrList> mmr_lists;
+  OwnedArray<int32_t> mmr_tiles;
+  OwnedArray<int2> mmr_pairs;
+  OwnedArray<int32_t> mmr_out;
+};
+
+// Streams, events and the pinned block of the master and of every lane.
+struct LaneResources {
   hipStream_t stream = nullptr;      // stream every kernel of a call is queued on
   hipStream_t own_stream = nullptr;  // created by the engine; `stream` points here unless rebound
   // hybrid search runs its sparse leg here, concurrently with the dense leg (fork/join by events)
   hipStream_t aux_stream = nullptr;
   hipEvent_t ev_fork = nullptr;
   hipEvent_t ev_join = nullptr;
+  hipEvent_t ev_input = nullptr;  // lane: orders its stream behind the master's bound stream (device inputs)
+  // Pinned, device-mapped host scratch (1 MiB). Query inputs are written here by the host and
+  // read by the kernels straight over PCIe, results are written here by the last kernel of a
+  // search: the latency path of a query has no hipMemcpy at all.
+  void* pinned = nullptr;      // host address
+  void* pinned_dev = nullptr;  // the same memory as the device sees it
+  size_t pinned_bytes = 0;
+
+  void release() {
+    if (pinned) (void)hipHostFree(pinned);
+    for (hipEvent_t ev : {ev_fork, ev_join, ev_input})
+      if (ev) (void)hipEventDestroy(ev);
+    if (aux_stream) (void)hipStreamDestroy(aux_stream);
+    if (own_stream) (void)hipStreamDestroy(own_stream);
+    *this = LaneResources{};
+  }
+};
+
+// A lane counts for itself; its counts are added to the master's when it is handed back.
+struct LaneCounters {
+  std::atomic<int64_t> stat_two_stage{0};       // single-query dense searches served by the two-stage path
+  std::atomic<int64_t> stat_fallback{0};        // ... of which overflowed the re-score budget and were redone one-stage
+  std::atomic<int64_t> stat_batched{0};         // queries served by the batched search (batch.hip)
+  std::atomic<int64_t> stat_batch_cands{0};     // ... and the rows they re-scored exactly, in total
+  std::atomic<int64_t> stat_batch_fallback{0};  // ... of which overflowed their candidate budget and were redone alone
+  std::atomic<int64_t> stat_last_candidates{0}; // rows re-scored by the last two-stage search (lane: -1 = none ran)
+  std::atomic<int64_t> stat_sparse_grouped{0};    // sparse queries served by the grouped batch scan (invert.hip)
+  std::atomic<int64_t> stat_sparse_group_cands{0}; // candidate keys its selection ranked (read when the next batch starts)
+  std::atomic<int64_t> stat_sparse_group_redo{0}; // queries it gave up (a candidate region overflowed) and the per-query kernels redid
+  void drain_into(LaneCounters& m) {
+    m.stat_two_stage += stat_two_stage.exchange(0);
+    m.stat_fallback += stat_fallback.exchange(0);
+    m.stat_batched += stat_batched.exchange(0);
+    m.stat_batch_cands += stat_batch_cands.exchange(0);
+    m.stat_batch_fallback += stat_batch_fallback.exchange(0);
+    m.stat_sparse_grouped += stat_sparse_grouped.exchange(0);
+    m.stat_sparse_group_cands += stat_sparse_group_cands.exchange(0);
+    m.stat_sparse_group_redo += stat_sparse_group_redo.exchange(0);
+    const int64_t lc = stat_last_candidates.exchange(-1);  // stored, not added; -1: no two-stage search ran on the lane
+    if (lc >= 0) m.stat_last_candidates.store(lc);
+  }
+};
+
+}  // namespace vr
+
+struct vr_engine : vr::IndexTables, vr::IndexTotals, vr::Scratch, vr::LaneResources, vr::LaneCounters {
+  int device = 0;
+  int dim = 0;
+  int kblocks = 0;  // dim / 16
+  bool prefilter = false;   // two-stage exact search with a shadow corpus (dim % 32 == 0 and not disabled)
+  bool prefilter8 = false;  // ... whose shadow is int8 (dim % 64 == 0, unless VR_PREFILTER=f16)
   // Concurrency (callers: MCP worker threads search while the indexing thread, the watcher
   // and the event loop mutate — watcher.py:149-171, indexing.py:281-288, api/routes/folders.py:137-143):
   //   rw       searches hold it SHARED for their whole duration; a mutation holds it EXCLUSIVELY only while it
   //            publishes (appends rows, sets tombstones, swaps in a compacted index)
   //   wmu      one writer (or encoder call) at a time; they share the master's stream and scratch
-  //   lanes    a search runs on a LANE: a private vr_engine that owns its stream, pinned staging area and scratch
-  //            arrays and holds a VIEW (pointers + counts, refreshed under the shared lock) of the master's index —
+  //   lanes    a search runs on a LANE: a private vr_engine that owns its LaneResources and Scratch and holds a VIEW
+  //            (IndexTables and IndexTotals copied under the shared lock) of the master's index —
   //            so several searches run at once, each on its own HIP stream, over the same HBM-resident tables.
   std::shared_mutex rw;
   std::mutex wmu;
@@ -226,164 +467,12 @@ struct vr_engine {
   std::vector<vr_engine*> lanes_all;
   int lanes_max = 4;
   vr_engine* master = nullptr;  // set in a lane
-  hipEvent_t ev_input = nullptr;  // lane: orders its stream behind the master's bound stream (device inputs)
-
-  int64_t n_rows = 0;
-  int64_t n_live = 0;
-  int64_t cap_rows = 0;  // multiple of 64
-
-  // dense corpus, MFMA-tiled: [row/16][k/16][tile_pos(k%4, row%16)][c = (k%16)/4]
-  vr::DevArray<float> corpus;
-  // f16 shadow of the corpus for the two-stage exact search (prefilter.hip), present when dim % 32 == 0
-  // and not disabled: [row/16][k/32][lane = (k%32)/8*16 + row%16][8 halfs], plus the exact
-  // rounding residual |x - f16(x)|_2 of every row.
-  bool prefilter = false;
-  // int8 form of the shadow (dim % 64 == 0, unless VR_PREFILTER=f16): corpus16 then holds
-  // [row/16][k/64][lane = (k%64)/16*16 + row%16][16 int8] with one scale per row (row_scale), and
-  // row_err the exact residual |x - scale * int8(x)|_2. Half the bytes of the f16 shadow again.
-  bool prefilter8 = false;
-  vr::DevArray<float> row_scale;
-  // Centre of the int8 shadow (prefilter.hip "centred shadow"): the shadow holds the quantised RESIDUALS x - centre.
-  // Any fixed vector is valid (a shift of every score by centre.q cancels out of the candidate test); the column
-  // mean of the stored rows makes the residuals of a real embedding collection — rows that share a common direction —
-  // several times smaller than the rows, and the bound with them. Recomputed (and the whole shadow rebuilt, ~1 ms per
-  // million rows) whenever the collection has doubled since the last time, after a compaction and after a load.
-  vr::DevArray<float> centre;      // [dim], zeros until the collection holds kCentreMinRows rows
-  vr::DevArray<float> centre_sum;  // [dim] scratch of the column sums
-  float centre_norm = 0.0f;        // |centre|_2, rounded up
-  int64_t centre_rows = 0;         // rows the collection held when the centre was last recomputed
-  int64_t centre_checked_rows = 0; // rows it held when a re-centring was last ATTEMPTED (centring switched off, or a non-finite
-                                   // centre, leaves centre_rows at 0: without this every upsert would rebuild the whole shadow)
-  // (a lane counts for itself; its counts are added to the master's when it is handed back)
-  std::atomic<int64_t> stat_two_stage{0};       // single-query dense searches served by the two-stage path
-  std::atomic<int64_t> stat_fallback{0};        // ... of which overflowed the re-score budget and were redone one-stage
-  std::atomic<int64_t> stat_batched{0};         // queries served by the batched search (batch.hip)
-  std::atomic<int64_t> stat_batch_cands{0};     // ... and the rows they re-scored exactly, in total
-  std::atomic<int64_t> stat_batch_fallback{0};  // ... of which overflowed their candidate budget and were redone alone
-  std::atomic<int64_t> stat_last_candidates{0}; // rows re-scored by the last two-stage search
-  std::atomic<int64_t> stat_sparse_grouped{0};    // sparse queries served by the grouped batch scan (invert.hip)
-  std::atomic<int64_t> stat_sparse_group_cands{0}; // candidate keys its selection ranked (read when the next batch starts)
-  std::atomic<int64_t> stat_sparse_group_redo{0}; // queries it gave up (a candidate region overflowed) and the per-query kernels redid
-  std::atomic<int64_t> generation{0};           // bumped whenever row numbers change (vr_compact's swap, vr_load)
-  vr::DevArray<uint16_t> corpus16;
-  vr::DevArray<float> row_err;
-  vr::DevArray<float> upper;       // [cap_rows] upper bounds of the last prefilter pass
-  vr::DevArray<int32_t> cand_rows; // candidate rows (+ counter at the end)
-  vr::DevArray<uint64_t> cand_keys;
-  vr::DevArray<uint8_t> live;
-  vr::DevArray<int32_t> folder;
-  vr::DevArray<int32_t> index_folder;
-  vr::DevArray<int64_t> created;
-  vr::DevArray<int64_t> modified;
-  vr::DevArray<int32_t> row_slice;  // slice index of the row's sparse vector, -1 = none
-  int32_t max_folder_id = -1;
-  int32_t max_index_folder_id = -1;
-
-  // sparse index (SELL-64, see SliceDesc)
+  std::atomic<int64_t> generation{0};  // bumped whenever row numbers change (vr_compact's swap, vr_load)
+  // host copy of IndexTables::slices, swapped with it; the master's only (a lane must not copy a vector on the query path)
   std::vector<vr::SliceDesc> slices_host;
-  vr::DevArray<vr::SliceDesc> slices;
-  int64_t n_slices_dev = 0;
-  vr::DevArray<int32_t> sp_idx;
-  vr::DevArray<float> sp_val;
-  int64_t sp_used = 0;
-  int64_t n_sparse_points = 0;
-
-  // inverted twin of the SELL index (invert.hip), derived data: rebuilt by vr_load and vr_compact
-  vr::DevArray<uint64_t> inv_key;
-  vr::DevArray<float> inv_val;
-  vr::DevArray<vr::InvSeg> inv_seg;
-  int64_t inv_used = 0;      // postings
-  int64_t n_inv_seg = 0;
-  int64_t inv_slices = 0;    // slices the inverted index covers (== n_slices_dev when usable)
-  int64_t inv_rows = 0;      // rows its segments span
-  unsigned long long* inv_counter = nullptr;  // [0] postings emitted by the current build, [1] duplicates seen
-  bool sp_has_dups = false;  // some row lists a term twice: queries stay on the forward scan
-
-  // document-frequency table: open addressing, key -1 = empty
-  vr::DevArray<int32_t> df_keys;
-  vr::DevArray<int32_t> df_cnt;
-  int64_t df_cap = 0;          // power of two
-  int64_t df_bound = 0;        // upper bound of distinct keys (exact count + nnz since last read)
-  int32_t* df_distinct = nullptr;  // device counter
-
-  // scratch
-  vr::DevArray<float> stage_dense;    // host->device staging of upsert / query rows
-  vr::DevArray<float> stage_len;      // per-row length
-  vr::DevArray<int64_t> stage_off;
-  vr::DevArray<int32_t> stage_idx;
-  vr::DevArray<float> stage_val;
-  vr::DevArray<int32_t> stage_i32a;
-  vr::DevArray<int32_t> stage_i32b;
-  vr::DevArray<int64_t> stage_i64a;
-  vr::DevArray<int64_t> stage_i64b;
-  vr::DevArray<double> stage_f64;
-  vr::DevArray<int32_t> bm_marks;     // bm25_tf_kernel scratch for documents longer than its LDS
-  vr::DevArray<int32_t> bm_cnt;       // vr_index_batch: per-document distinct terms
-  vr::DevArray<int32_t> bm_idx;       //                 padded term ids
-  vr::DevArray<float> bm_val;         //                 padded tf weights (f32, as stored)
-  vr::DevArray<float> enc_out;        //                 encoder output rows
-  vr::DevArray<float> q_tiled;       // 16-query image, kblocks KiB
-  vr::DevArray<float> scores;         // [16][cap_rows]
-  vr::DevArray<float> sp_scores;      // [cap_rows]
-  vr::DevArray<uint8_t> mask;         // [cap_rows]
-  vr::DevArray<uint8_t> pass_folder;  // per folder id
-  vr::DevArray<uint8_t> pass_ifolder;
-  vr::DevArray<uint64_t> cand_a;
-  vr::DevArray<uint64_t> cand_b;
-  vr::DevArray<uint64_t> sp_cand;  // per-block lists of the fused sparse scan
-  vr::DevArray<int32_t> q_ids;
-  vr::DevArray<float> q_w;
-  // batched dense search (batch.hip): preprocessed queries, their int8 images and constants, per-slab bounds,
-  // thresholds, candidate rows / counts (+ overflow flags), exact keys (+ results)
-  vr::DevArray<float> bq_hat, bq_params, bq_best, bq_thr;
-  vr::DevArray<int32_t> bq_img, bq_cand, bq_cnt;
-  vr::DevArray<uint64_t> bq_keys;
-  vr::DevArray<uint16_t> bq_tile_ub;  // f16 bits: per (16-row tile, query) the largest upper bound (rounded up)
-  vr::DevArray<int32_t> bq_pairs;     // per query: the tiles whose bound reaches its threshold ([nq][kBatchCand]), then the counts [nq]
-  vr::DevArray<float> bq_stage;  // host queries staged on the device
-  // vr_query_text_batch: the questions' embeddings (n x dim), and them gathered hybrid-first by the picks
-  vr::DevArray<float> qt_emb;
-  vr::DevArray<int32_t> qt_pick;
-  vr::DevArray<float> qt_gather;
-  // filtered batches (vr_search_*_multi): one bit plane per class of filter ([class][plane words], bit r % 32 of word
-  // r / 32 = row r passes), the class of every query of the batch, and the classes' pass tables and descriptors
-  vr::DevArray<uint32_t> cls_planes;
-  vr::DevArray<int32_t> cls_of_q;
-  vr::DevArray<uint8_t> cls_pass;
-  vr::DevArray<vr::ClassDesc> cls_desc;
-  // batched sparse search (invert.hip): the queries' terms as CSR (offsets, ascending distinct ids, raw values,
-  // weights q_t * idf_t) and the nq x k result keys
-  vr::DevArray<int32_t> sq_off, sq_ids;
-  vr::DevArray<float> sq_val, sq_w;
-  vr::DevArray<uint64_t> sq_keys;
-  // ... grouped form (sparse_inv_group_kernel): the group tables, per query a candidate buffer and its fill count
-  vr::DevArray<int32_t> sq_grp, sq_cnt;
-  const int32_t* sq_overflow_q = nullptr;  // (into sq_cnt) per query of the last grouped batch: 1 = its candidates overflowed
-  vr::DevArray<uint64_t> sq_cand;   // (+ the groups' threshold keys behind the buffers)
-  vr::DevArray<int32_t> sq_bounds;  // int2 run bounds per (segment, distinct term), then per (segment, group, union term)
-  vr::DevArray<float> sq_entw;      // weights per (group, union term, query of the group)
-  std::vector<int32_t> sq_grp_host;
-  // vr_merge_keys: the parts' keys staged on the device, merged global ids / scores / counts
-  vr::DevArray<uint64_t> mg_in;
-  vr::DevArray<int64_t> mg_gid;
-  vr::DevArray<float> mg_score;
-  vr::DevArray<int32_t> mg_cnt;
-  // vr_mmr_select (mmr.hip): the gathered candidate rows (MFMA-tiled, 16-row tiles per list), the lists' Gram matrices,
-  // the slice's rows / relevance / list descriptors / tile -> list map / (list, tile column) pairs, and the picks
-  vr::DevArray<float> mmr_ws;
-  vr::DevArray<float> mmr_gram;
-  vr::DevArray<int64_t> mmr_rows;
-  vr::DevArray<double> mmr_rel;
-  vr::DevArray<vr::MmrList> mmr_lists;
-  vr::DevArray<int32_t> mmr_tiles;
-  vr::DevArray<int2> mmr_pairs;
-  vr::DevArray<int32_t> mmr_out;
-  // Pinned, device-mapped host scratch (1 MiB). Query inputs are written here by the host and
-  // read by the kernels straight over PCIe, results are written here by the last kernel of a
-  // search: the latency path of a query has no hipMemcpy at all.
-  void* pinned = nullptr;      // host address
-  void* pinned_dev = nullptr;  // the same memory as the device sees it
-  size_t pinned_bytes = 0;
+  // device rows (kMaxDim floats) for query embeddings in flight, one per concurrent vr_query_text; the master's only
+  std::mutex query_rows_mu;
+  std::vector<float*> query_rows_free;
 
   void* encoder = nullptr;   // vr::Encoder (encoder.hip)
   void* reranker = nullptr;  // vr::Encoder of a cross-encoder (vr_reranker_load), beside the embedder
@@ -483,7 +572,6 @@ int inv_rebuild(vr_engine* e);
 // once the stream has been synchronised
 int inv_note_csr_dups(vr_engine* e, const int64_t* off_dev, const int32_t* idx_dev, int64_t n,
                       unsigned long long* out_host);
-void inv_release(vr_engine* e);
 bool inv_usable(const vr_engine* e, int nnz);
 int inv_scan_topk(vr_engine* e, const int32_t* q_idx_host, const float* q_val_host, int nnz, bool weights_given,
                   float n_points, const uint8_t* mask_dev, int k, uint64_t* out_keys_dev);

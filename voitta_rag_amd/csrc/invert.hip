@@ -289,9 +289,9 @@ __global__ void inv_csr_dups_kernel(const int64_t* __restrict__ off, const int32
 }
 
 static int inv_counters(vr_engine* e) {
-  if (!e->inv_counter) {
-    VR_HIP(hipMalloc(reinterpret_cast<void**>(&e->inv_counter), 2 * sizeof(unsigned long long)));
-    VR_HIP(hipMemsetAsync(e->inv_counter, 0, 2 * sizeof(unsigned long long), e->stream));
+  if (!e->inv_counter.p) {
+    VR_TRY(e->inv_counter.grow(2, 0, e->stream));
+    VR_HIP(hipMemsetAsync(e->inv_counter.p, 0, 2 * sizeof(unsigned long long), e->stream));
   }
   return 0;
 }
@@ -301,22 +301,10 @@ int inv_note_csr_dups(vr_engine* e, const int64_t* off_dev, const int32_t* idx_d
   VR_TRY(inv_counters(e));
   if (n > 0)
     hipLaunchKernelGGL(inv_csr_dups_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, e->stream,
-                       off_dev, idx_dev, n, e->inv_counter);
+                       off_dev, idx_dev, n, e->inv_counter.p);
   VR_HIP(hipGetLastError());
-  VR_HIP(hipMemcpyAsync(out_host, e->inv_counter + 1, sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
+  VR_HIP(hipMemcpyAsync(out_host, e->inv_counter.p + 1, sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
   return 0;  // the caller synchronises the stream before it reads *out_host
-}
-
-void inv_release(vr_engine* e) {
-  e->inv_key.release();
-  e->inv_val.release();
-  e->inv_seg.release();
-  if (e->inv_counter) (void)hipFree(e->inv_counter);
-  e->inv_counter = nullptr;
-  e->inv_used = 0;
-  e->n_inv_seg = 0;
-  e->inv_slices = 0;
-  e->inv_rows = 0;
 }
 
 int inv_append(vr_engine* e, int64_t slice0, int64_t n_new, int64_t first_row, int64_t n_rows, int64_t nnz) {
@@ -333,7 +321,7 @@ int inv_append(vr_engine* e, int64_t slice0, int64_t n_new, int64_t first_row, i
   int64_t n_pad = kSortTile;
   while (n_pad < room) n_pad <<= 1;
   VR_TRY(inv_counters(e));
-  VR_HIP(hipMemsetAsync(e->inv_counter, 0, sizeof(unsigned long long), e->stream));
+  VR_HIP(hipMemsetAsync(e->inv_counter.p, 0, sizeof(unsigned long long), e->stream));
   // emitted and sorted in place, behind the postings already there (the padding of the sort is overwritten by the
   // next batch)
   VR_TRY(e->inv_key.grow(e->inv_used + n_pad, e->inv_used, e->stream));
@@ -342,11 +330,11 @@ int inv_append(vr_engine* e, int64_t slice0, int64_t n_new, int64_t first_row, i
   uint64_t* keys = e->inv_key.p + e->inv_used;
   float* vals = e->inv_val.p + e->inv_used;
   hipLaunchKernelGGL(inv_emit_kernel, dim3(static_cast<unsigned>(n_new)), dim3(64), 0, e->stream, e->slices.p,
-                     slice0, first_row, seg_rows, e->sp_idx.p, e->sp_val.p, keys, vals, e->inv_counter);
+                     slice0, first_row, seg_rows, e->sp_idx.p, e->sp_val.p, keys, vals, e->inv_counter.p);
   VR_HIP(hipGetLastError());
   if (rebuilding) {
     unsigned long long c = 0;
-    VR_HIP(hipMemcpyAsync(&c, e->inv_counter, sizeof(c), hipMemcpyDeviceToHost, e->stream));
+    VR_HIP(hipMemcpyAsync(&c, e->inv_counter.p, sizeof(c), hipMemcpyDeviceToHost, e->stream));
     VR_HIP(hipStreamSynchronize(e->stream));
     nnz = static_cast<int64_t>(c);
     VR_CHECK(nnz <= room, "inverted-index rebuild: %lld entries in %lld slots", static_cast<long long>(nnz),
@@ -361,7 +349,7 @@ int inv_append(vr_engine* e, int64_t slice0, int64_t n_new, int64_t first_row, i
     VR_TRY(inv_sort(e, keys, vals, n_pad));
     if (rebuilding)
       hipLaunchKernelGGL(inv_count_dups_kernel, dim3(static_cast<unsigned>((nnz + 255) / 256)), dim3(256), 0,
-                         e->stream, keys, nnz, e->inv_counter);
+                         e->stream, keys, nnz, e->inv_counter.p);
   }
   hipLaunchKernelGGL(inv_segments_kernel, dim3(static_cast<unsigned>((n_sub + 255) / 256)), dim3(256), 0, e->stream,
                      keys, nnz, e->inv_used, first_row, n_rows, seg_rows, static_cast<int>(n_sub),
@@ -400,7 +388,7 @@ int inv_rebuild(vr_engine* e) {
   }
   VR_TRY(inv_append(e, 0, n, first, end - first, -1));
   unsigned long long dups = 0;
-  VR_HIP(hipMemcpyAsync(&dups, e->inv_counter + 1, sizeof(dups), hipMemcpyDeviceToHost, e->stream));
+  VR_HIP(hipMemcpyAsync(&dups, e->inv_counter.p + 1, sizeof(dups), hipMemcpyDeviceToHost, e->stream));
   VR_HIP(hipStreamSynchronize(e->stream));
   if (dups) e->sp_has_dups = true;
   return 0;
