@@ -109,10 +109,10 @@ def test_sparse_batch_pruning_keeps_the_exact_answer(small, monkeypatch):
 
 
 def test_grouped_sparse_batch_keeps_the_exact_answer(small, monkeypatch):
-    """Batches of 16 queries or more take the GROUPED scan (csrc/invert.hip, sparse_inv_group_kernel): groups of up to 8
+    """Batches of 16 queries or more take the GROUPED scan (csrc/invert.hip, sparse_inv_group_kernel): pairs of
     queries share a block per segment, a term's postings are read once per group and added to every member's
     accumulators — in ascending term order per query, so the bits stay the forward scan's. Queries from a Zipfian
-    vocabulary (shared common terms, the case it is built for), groups of 8 and of 4, a filter, k from 1 to 64; held
+    vocabulary (shared common terms, the case it is built for), a filter, k from 1 to 64; held
     against the oracle and against the per-query kernels (VR_SPARSE_GROUPED=0). Candidates that do not fit
     their (query, segment) region spill into the query's spill area (VR_SPARSE_GROUP_CAP); a spill area that overflows
     (VR_SPARSE_GROUP_SPILL) makes the engine redo THAT query on the per-query kernels: same answer, counted."""
@@ -130,23 +130,20 @@ def test_grouped_sparse_batch_keeps_the_exact_answer(small, monkeypatch):
         qs.append((ids, rng.uniform(0.5, 1.5, size=m).astype(np.float32)))
     qs[7] = (np.zeros(0, np.int32), np.zeros(0, np.float32))            # no terms
     qs[11] = (np.array([5], np.int32), np.ones(1, np.float32))         # a term no row carries
-    for group in ("2", "3", "4", "8"):
-        monkeypatch.setenv("VR_SPARSE_GROUP", group)
-        for flt, mask in ((None, live.astype(bool)), (SearchFilter(include_folders=[0, 2, 5]), live.astype(bool) & np.isin(folder, [0, 2, 5]))):
-            for k in (1, 10, 30, 64):
-                before = e.stats()
-                got = e.search_sparse_batch(qs, k, flt)
-                after = e.stats()
-                assert after["sparse_grouped"] - before["sparse_grouped"] == len(qs)
-                assert after["sparse_group_redo"] == before["sparse_group_redo"]
-                for i, (qi, qv) in enumerate(qs):
-                    if len(qi) == 0:
-                        assert len(got[i][0]) == 0
-                        continue
-                    wr, ws = ocore.topk(sp.scores(qi, qv), k, mask.astype(np.uint8))
-                    assert np.array_equal(got[i][0], wr), (group, k, i)
-                    assert np.array_equal(got[i][1].view(np.uint32), ws.view(np.uint32)), (group, k, i)
-    monkeypatch.delenv("VR_SPARSE_GROUP")
+    for flt, mask in ((None, live.astype(bool)), (SearchFilter(include_folders=[0, 2, 5]), live.astype(bool) & np.isin(folder, [0, 2, 5]))):
+        for k in (1, 10, 30, 64):
+            before = e.stats()
+            got = e.search_sparse_batch(qs, k, flt)
+            after = e.stats()
+            assert after["sparse_grouped"] - before["sparse_grouped"] == len(qs)
+            assert after["sparse_group_redo"] == before["sparse_group_redo"]
+            for i, (qi, qv) in enumerate(qs):
+                if len(qi) == 0:
+                    assert len(got[i][0]) == 0
+                    continue
+                wr, ws = ocore.topk(sp.scores(qi, qv), k, mask.astype(np.uint8))
+                assert np.array_equal(got[i][0], wr), (k, i)
+                assert np.array_equal(got[i][1].view(np.uint32), ws.view(np.uint32)), (k, i)
     # long queries: 24-32 terms each, so a group's union of terms passes the 64 the scan block holds and the host has to
     # close groups early (down to one query per group); weights with both signs (sums that cancel, negative scores)
     long_qs = []

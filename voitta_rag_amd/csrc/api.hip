@@ -736,36 +736,17 @@ int vr_sparse_stats(vr_engine* e, const int32_t* ids, int32_t n, int32_t* out_df
 // drained. The two legs share nothing but the mask: the (small, latency-bound) sparse leg is forked onto the auxiliary
 // stream and runs under the dense scan. The k > kFusedMaxK sparse path borrows the dense leg's selection buffers and
 // stays on the main stream.
-// The sparse leg of a hybrid query queued on the lane's auxiliary stream right away (behind the mask on the main
-// stream): what vr_query_text can do BEFORE the question's forward pass (VR_QUERY_TEXT_AHEAD=1; measured slower than
-// running it beside the dense scan, see there). hybrid_one_query(..., sparse_in_flight = true) joins it.
-static int hybrid_sparse_ahead(vr_engine* e, const int32_t* q_idx, const float* q_val, int nnz, int k, const uint8_t* mask,
-                               bool weights_given) {
-  VR_CHECK(q_idx && q_val && nnz > 0 && k <= kFusedMaxK && e->n_slices_dev > 0, "no sparse leg to start ahead");
-  VR_HIP(hipEventRecord(e->ev_fork, e->stream));  // after the mask
-  VR_HIP(hipStreamWaitEvent(e->aux_stream, e->ev_fork, 0));
-  hipStream_t main_stream = e->stream;
-  e->stream = e->aux_stream;
-  const int rc = search_sparse_block(e, q_idx, q_val, nnz, k, mask, weights_given);
-  e->stream = main_stream;
-  if (rc != 0) return rc;
-  VR_HIP(hipEventRecord(e->ev_join, e->aux_stream));
-  return 0;
-}
-
 static int hybrid_one_query(vr_engine* e, const float* q, int mem, const int32_t* q_idx, const float* q_val, int nnz, int k,
-                            bool weights_given, const uint8_t* mask, bool* have_sparse_out, bool sparse_in_flight = false) {
+                            bool weights_given, const uint8_t* mask, bool* have_sparse_out) {
   const float* q_dev = stage_query(e, q, 1, mem);
   bool two_stage = false;
   const bool have_sparse = nnz > 0 && e->n_slices_dev > 0;
   *have_sparse_out = have_sparse;
-  const bool fork = have_sparse && k <= kFusedMaxK && !sparse_in_flight;
+  const bool fork = have_sparse && k <= kFusedMaxK;
   if (have_sparse) VR_CHECK(q_idx && q_val, "null sparse query");
   if (fork) VR_HIP(hipEventRecord(e->ev_fork, e->stream));  // after the mask, before the dense leg
   VR_TRY(search_dense_block(e, q_dev, 1, k, mask, true, &two_stage));
-  if (sparse_in_flight) {
-    VR_HIP(hipStreamWaitEvent(e->stream, e->ev_join, 0));
-  } else if (fork) {
+  if (fork) {
     // queued after the dense leg (whose scan is already running by now), executed beside it
     VR_HIP(hipStreamWaitEvent(e->aux_stream, e->ev_fork, 0));
     hipStream_t main_stream = e->stream;
@@ -1865,9 +1846,7 @@ int query_text(vr_engine* e, const Tokenizer* tokenizer, const char* dense_text,
   } giver{e, q_dev};
   const bool hybrid = !stems.empty();
   if (out_hybrid) *out_hybrid = hybrid ? 1 : 0;
-  // (VR_QUERY_TEXT_LANE_FIRST=0: the forward pass, then vr_search_hybrid as a caller would — the round's earlier form, for A/B timings)
-  const bool lane_first = !(getenv("VR_QUERY_TEXT_LANE_FIRST") && atoi(getenv("VR_QUERY_TEXT_LANE_FIRST")) == 0);
-  if (hybrid && lane_first) {
+  if (hybrid) {
     // 3a. hybrid: the lane is taken and the filter mask built BEFORE the forward pass (both used to follow it, in a
     //     second engine call; worth a hundredth of a millisecond), then the forward pass, then both legs on the lane. Lock order as
     //     everywhere: the writers' mutex (the encoder), then the shared lock of the lane — a writer takes the same mutex
@@ -1882,16 +1861,10 @@ int query_text(vr_engine* e, const Tokenizer* tokenizer, const char* dense_text,
     const uint8_t* mask = nullptr;
     VR_TRY(filter_build_mask(L, filter, &mask));
     const int nnz = static_cast<int>(stems.size());
-    // VR_QUERY_TEXT_AHEAD=1: the sparse leg is queued on the auxiliary stream BEFORE the forward pass (it needs the words,
-    // not the embedding) instead of beside the dense scan. Measured on bench.py's from-text section and NOT the default:
-    // 0.90-0.92 ms against 0.82-0.84 — the forward pass of one question is 63 small latency-bound kernels, and a sparse kernel that
-    // holds every CU beside them slows each of them (profiles/r03_experiments.md §13).
-    const bool ahead = L->n_slices_dev > 0 && k <= kFusedMaxK && getenv("VR_QUERY_TEXT_AHEAD") && atoi(getenv("VR_QUERY_TEXT_AHEAD")) != 0;
-    if (ahead) VR_TRY(hybrid_sparse_ahead(L, stems.data(), ones.data(), nnz, k, mask, false));
     VR_TRY(encoder_encode(e, wp.data(), off32.data(), 1, VR_MEM_HOST, q_dev, VR_MEM_DEVICE));  // (returns with the stream drained)
     writer.unlock();
     bool have_sparse = false;
-    VR_TRY(hybrid_one_query(L, q_dev, VR_MEM_DEVICE, stems.data(), ones.data(), nnz, k, false, mask, &have_sparse, ahead));
+    VR_TRY(hybrid_one_query(L, q_dev, VR_MEM_DEVICE, stems.data(), ones.data(), nnz, k, false, mask, &have_sparse));
     int64_t d_rows[kMaxK], s_rows[kMaxK];
     float d_scores[kMaxK], s_scores[kMaxK];
     const int nd = static_cast<int>(decode_keys(pin_host<uint64_t>(L, kPinDenseKeys), k, d_rows, d_scores));
@@ -1904,11 +1877,6 @@ int query_text(vr_engine* e, const Tokenizer* tokenizer, const char* dense_text,
   {
     std::lock_guard<std::mutex> writer(e->wmu);
     VR_TRY(encoder_encode(e, wp.data(), off32.data(), 1, VR_MEM_HOST, q_dev, VR_MEM_DEVICE));  // (returns with the stream drained)
-  }
-  if (hybrid) {
-    std::vector<float> ones(stems.size(), 1.0f);
-    return vr_search_hybrid(e, q_dev, VR_MEM_DEVICE, stems.data(), ones.data(), static_cast<int32_t>(stems.size()), limit, sparse_weight,
-                            fusion, filter, out_rows, out_scores, out_from_dense, out_count);
   }
   // no term survived the stop-word filter: the dense-only branch of VectorStoreService.search (vector_store.py:612-617)
   std::vector<float> sc(static_cast<size_t>(limit));

@@ -24,9 +24,9 @@
 //   revisit  rows with A + E >= T_q are the candidates of query q (a superset of its top k), and they can only sit in
 //            tiles whose stored bound reaches T_q: batch_flag_kernel lists those (tile, query) pairs — about as many as
 //            candidates, tens per query — and batch_pairs_kernel recomputes their 16 rows' bounds (v_dot4_i32_i8, the
-//            same bound function). Until r02j the GEMM simply ran a second time for this (VR_BATCH_TWO_PASS=1 still
-//            does): the revisit costs 0.25 ms where the second pass cost 2.4 (1k queries, a million rows). Storing all
-//            N x Q bounds instead would be 4 GB per 1k queries at 1M rows; one f16 per tile and query is 131 MB.
+//            same bound function). Until r02j the GEMM simply ran a second time for this: the revisit costs 0.25 ms
+//            where the second pass cost 2.4 (1k queries, a million rows). Storing all N x Q bounds instead would be
+//            4 GB per 1k queries at 1M rows; one f16 per tile and query is 131 MB.
 //   rescore  every (query, candidate row) pair is scored with the exact k-ordered f32 fma chain (one lane per
 //            pair; the MFMA chain of dense.hip is bit for bit this chain) and ranked by the usual 64-bit keys.
 // A query whose candidates overflow its budget (a corpus of near-duplicates) is flagged; the host redoes
@@ -179,25 +179,18 @@ __device__ __forceinline__ void glds16b(const void* src, void* lds_dst) {
 // K-step of the current one, like any other next step, so only a block's very first item pays a prologue, and the stores
 // of an item's epilogue drain under the next item's main loop (one-item blocks: 4k cycles of prologue and 2-3k of drain per
 // 39k-cycle item, phase stamps of round 3 — profiles/r03_batch_scan_stamps.txt).
-// PASS 1: best[q][128-row slab] = max lower bound (slab = row block x wave row). PASS 2: rows with upper bound >= thr[q] -> cand[q][...].
+// Leaves best[q][128-row slab] = max lower bound (slab = row block x wave row) and tile_ub[16-row tile][q] = max upper bound.
 // MULTI (a filtered batch, vr_search_*_multi): query q passes the rows of its class's bit plane, planes + q_cls[q] * plane_words,
 // instead of the shared mask. A wave's 128 rows start on a multiple of 128, so they are four words of that plane: one
 // 16-byte load per query fragment and item, where the shared mask costs a four-byte load per tile.
-template <int PASS, bool MULTI>
+template <bool MULTI>
 __global__ __launch_bounds__(512) void batch_scan_kernel(
     const uint4* __restrict__ corpus8, const uint4* __restrict__ img_a, const uint4* __restrict__ img_b,
     const float* __restrict__ params, const float* __restrict__ row_err, const float* __restrict__ row_scale,
-    const uint8_t* __restrict__ mask, int64_t n_tiles, int n_rb, int rb_stride, int n_qc, int nq, int kb8n,
-    float* __restrict__ best, const float* __restrict__ thr, int32_t* __restrict__ cand, int32_t* __restrict__ cand_cnt,
-    __half* __restrict__ tile_ub, unsigned long long* __restrict__ stamps, int n_ids, const uint32_t* __restrict__ planes,
+    const uint8_t* __restrict__ mask, int64_t n_tiles, int n_rb, int n_qc, int nq, int kb8n,
+    float* __restrict__ best, __half* __restrict__ tile_ub, int n_ids, const uint32_t* __restrict__ planes,
     const int32_t* __restrict__ q_cls, int64_t plane_words) {
   __shared__ uint4 lds[2 * kBStage / 16];  // the only LDS object (direct-to-LDS loads in flight beside fragment reads)
-  // diagnostics (VR_BATCH_STAMPS=1): every 61st block's thread 0 writes the shader clock at the phase boundaries of its FIRST item
-  bool stamping = stamps != nullptr && blockIdx.x % 61 == 0 && threadIdx.x == 0;
-  unsigned long long* my_stamps = stamps + (blockIdx.x / 61) * 16;
-  int stamp_at = 0;
-#define VR_STAMP() do { if (stamping) my_stamps[stamp_at++] = __builtin_readcyclecounter(); } while (0)
-  VR_STAMP();
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int wm = wave >> 2, wn = wave & 3;
@@ -205,8 +198,7 @@ __global__ __launch_bounds__(512) void batch_scan_kernel(
   const int nk = kb8n / 2;  // 128-deep K-tiles (kb8n is even: dim % 128 == 0)
   const int64_t last_tile = n_tiles - 1;
   const int nq_pad = n_qc * kBQ;
-  // ids b and b + 8 share an XCD: the n_qc query chunks of a row block get ids 8 apart. n_rb row blocks take part:
-  // every rb_stride-th of the corpus (a sampled pass 1)
+  // ids b and b + 8 share an XCD: the n_qc query chunks of a row block get ids 8 apart
   auto decode = [&](int id, int& rbi_, int& qc_) {
     const int lane8 = id & 7, rest = id >> 3;
     qc_ = rest % n_qc;
@@ -229,7 +221,7 @@ __global__ __launch_bounds__(512) void batch_scan_kernel(
   // LDS image of a stage, in 1-KiB blocks: rows  [tile 0..15][kb 0..1] = block 2 t + c;
   //                                        query [qfrag 0..7][part a, b][kb 0..1] = block 32 + 4 f + 2 p + c
   auto stage = [&](int buf, int rbi_, int qc_, int kt) {
-    const int64_t t0 = static_cast<int64_t>(rbi_) * rb_stride * 16;
+    const int64_t t0 = static_cast<int64_t>(rbi_) * 16;
     const uint4* gA0 = corpus8 + std::min<int64_t>(t0 + wave, last_tile) * kb8n * 64 + lane;
     const uint4* gA1 = corpus8 + std::min<int64_t>(t0 + wave + 8, last_tile) * kb8n * 64 + lane;
     const int64_t qf = static_cast<int64_t>(qc_) * 8 + wave;  // (images are padded to whole chunks of 128 queries)
@@ -255,22 +247,20 @@ __global__ __launch_bounds__(512) void batch_scan_kernel(
   stage(0, rbi, qc, rbi % nk);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  VR_STAMP();
   while (true) {
     const int rot = rbi % nk;
-    const int64_t tile0 = static_cast<int64_t>(rbi) * rb_stride * 16;
+    const int64_t tile0 = static_cast<int64_t>(rbi) * 16;
     const int next_id = next_item(id);
     int nrbi = 0, nqc = 0;
     if (next_id < n_ids) decode(next_id, nrbi, nqc);
     // the constants of this lane's two queries (needed by the epilogue only; requested now, so that they are there)
-    float pa[2], pb[2], p1[2], p2[2], pthr[2];
+    float pa[2], pb[2], p1[2], p2[2];
     int qidx[2];
     const uint32_t* qplane[2];
 #pragma unroll
     for (int f = 0; f < 2; ++f) {
       qidx[f] = qc * kBQ + (2 * wn + f) * 16 + (lane & 15);
       batch_query_consts(params + static_cast<int64_t>(std::min(qidx[f], nq - 1)) * kQParams, pa[f], pb[f], p1[f], p2[f]);
-      pthr[f] = PASS == 2 ? thr[std::min(qidx[f], nq - 1)] : 0.0f;
       if constexpr (MULTI) qplane[f] = planes + static_cast<int64_t>(q_cls[std::min(qidx[f], nq - 1)]) * plane_words;
     }
     i32x4 acc[8][2][2];  // [row tile of the wave][qfrag of the wave][part a, b]
@@ -304,7 +294,6 @@ __global__ __launch_bounds__(512) void batch_scan_kernel(
       }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
-      VR_STAMP();
     }
     // the stage buffer of the item's LAST K-step is free now (every wave is past the barrier); the other one may already
     // hold the next item's first K-step. The fold of the tile bounds below uses the free one.
@@ -333,104 +322,56 @@ __global__ __launch_bounds__(512) void batch_scan_kernel(
       const uint32_t w = (i >> 1) == 0 ? w4[f].x : (i >> 1) == 1 ? w4[f].y : (i >> 1) == 2 ? w4[f].z : w4[f].w;
       return w >> (16 * (i & 1) + 4 * g);
     };
-    float run[2] = {-__builtin_inff(), -__builtin_inff()};
-    if constexpr (MULTI) {
-      if (stamping && (w4[1].w | 1)) VR_STAMP();
-    } else {
-      if (stamping && (m8[7].x | 1)) VR_STAMP();  // (after the per-row words have arrived)
-    }
-    if (PASS == 1) {
-      // two elements per instruction on the packed-f32 VALU: the lane's two query fragments side by side. A masked row (or
-      // one behind the corpus's end) gets a bias of -inf into its score, so both of its bounds are -inf and no select is needed.
-      using f32x2 = __attribute__((ext_vector_type(2))) float;
-      const f32x2 PA = {pa[0], pa[1]}, PB = {pb[0], pb[1]}, P1 = {p1[0], p1[1]}, P2 = {p2[0], p2[1]};
-      f32x2 run2 = {-__builtin_inff(), -__builtin_inff()};
+    // two elements per instruction on the packed-f32 VALU: the lane's two query fragments side by side. A masked row (or
+    // one behind the corpus's end) gets a bias of -inf into its score, so both of its bounds are -inf and no select is needed.
+    using f32x2 = __attribute__((ext_vector_type(2))) float;
+    const f32x2 PA = {pa[0], pa[1]}, PB = {pb[0], pb[1]}, P1 = {p1[0], p1[1]}, P2 = {p2[0], p2[1]};
+    f32x2 run2 = {-__builtin_inff(), -__builtin_inff()};
 #pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const bool real = static_cast<int>(tile0) + 8 * wm + i <= static_cast<int>(last_tile);  // wave-uniform (tiles < 2^28)
-        unsigned char mm[4];
-        if constexpr (!MULTI) {
-          mm[0] = m8[i].x;
-          mm[1] = m8[i].y;
-          mm[2] = m8[i].z;
-          mm[3] = m8[i].w;
-        }
-        uint32_t qb[2];
-        if constexpr (MULTI) {
-          qb[0] = bits4(0, i);
-          qb[1] = bits4(1, i);
-        }
-        const float ee[4] = {e8[i].x, e8[i].y, e8[i].z, e8[i].w};
-        const float ss[4] = {s8[i].x, s8[i].y, s8[i].z, s8[i].w};
-        f32x2 top2 = {-__builtin_inff(), -__builtin_inff()};
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          f32x2 bias2;
-          if constexpr (MULTI) {
-            bias2 = f32x2{(real && ((qb[0] >> r) & 1u)) ? 0.0f : -__builtin_inff(), (real && ((qb[1] >> r) & 1u)) ? 0.0f : -__builtin_inff()};
-          } else {
-            const float bias = (real && mm[r]) ? 0.0f : -__builtin_inff();
-            bias2 = f32x2{bias, bias};
-          }
-          const f32x2 da = {static_cast<float>(acc[i][0][0][r]), static_cast<float>(acc[i][1][0][r])};
-          const f32x2 db = {static_cast<float>(acc[i][0][1][r]), static_cast<float>(acc[i][1][1][r])};
-          const f32x2 t = __builtin_elementwise_fma(PB, db, PA * da);
-          const f32x2 score = __builtin_elementwise_fma(f32x2{ss[r], ss[r]}, t, bias2);
-          const f32x2 err = __builtin_elementwise_fma(f32x2{ee[r], ee[r]}, P1, P2);
-          const f32x2 lo = score - err, up = score + err;
-          run2 = __builtin_elementwise_max(run2, lo);
-          top2 = __builtin_elementwise_max(top2, up);
-        }
-        // the tile's 16 rows are spread over the four lane groups: each leaves its four-row maximum in LDS as
-        // [group][16 tiles][128 queries] f16 rounded up; they are folded on the way out (cross-lane maxima here — two
-        // swizzles per tile and fragment — cost pass 1 a sixth of its time, and so did writing the bounds as 2-byte
-        // stores from 16 lanes)
-        if (tile_ub) {
-          __half* dst = reinterpret_cast<__half*>(fold) + ((g * 16 + 8 * wm + i) * kBQ) + (2 * wn) * 16 + (lane & 15);
-          dst[0] = __float2half_ru(top2.x);
-          dst[16] = __float2half_ru(top2.y);
-        }
+    for (int i = 0; i < 8; ++i) {
+      const bool real = static_cast<int>(tile0) + 8 * wm + i <= static_cast<int>(last_tile);  // wave-uniform (tiles < 2^28)
+      unsigned char mm[4];
+      if constexpr (!MULTI) {
+        mm[0] = m8[i].x;
+        mm[1] = m8[i].y;
+        mm[2] = m8[i].z;
+        mm[3] = m8[i].w;
       }
-      run[0] = run2.x;
-      run[1] = run2.y;
-    } else {
+      uint32_t qb[2];
+      if constexpr (MULTI) {
+        qb[0] = bits4(0, i);
+        qb[1] = bits4(1, i);
+      }
+      const float ee[4] = {e8[i].x, e8[i].y, e8[i].z, e8[i].w};
+      const float ss[4] = {s8[i].x, s8[i].y, s8[i].z, s8[i].w};
+      f32x2 top2 = {-__builtin_inff(), -__builtin_inff()};
 #pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int64_t tile = tile0 + 8 * wm + i;
-        const bool real = tile <= last_tile;  // wave-uniform
-        const int64_t row0 = tile * kTileRows + 4 * g;
-        const float ee[4] = {e8[i].x, e8[i].y, e8[i].z, e8[i].w};
-        const float ss[4] = {s8[i].x, s8[i].y, s8[i].z, s8[i].w};
+      for (int r = 0; r < 4; ++r) {
+        f32x2 bias2;
         if constexpr (MULTI) {
-#pragma unroll
-          for (int f = 0; f < 2; ++f)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              float score, err;
-              batch_bound(pa[f], pb[f], p1[f], p2[f], ss[r], ee[r], acc[i][f][0][r], acc[i][f][1][r], score, err);
-              if (real && ((bits4(f, i) >> r) & 1u) && score + err >= pthr[f] && qidx[f] < nq) {
-                const int slot = atomicAdd(cand_cnt + qidx[f], 1);
-                if (slot < kBatchCand) cand[static_cast<int64_t>(qidx[f]) * kBatchCand + slot] = static_cast<int32_t>(row0 + r);
-              }
-            }
+          bias2 = f32x2{(real && ((qb[0] >> r) & 1u)) ? 0.0f : -__builtin_inff(), (real && ((qb[1] >> r) & 1u)) ? 0.0f : -__builtin_inff()};
         } else {
-          const unsigned char mm[4] = {m8[i].x, m8[i].y, m8[i].z, m8[i].w};
-#pragma unroll
-          for (int f = 0; f < 2; ++f)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              float score, err;
-              batch_bound(pa[f], pb[f], p1[f], p2[f], ss[r], ee[r], acc[i][f][0][r], acc[i][f][1][r], score, err);
-              if (real && mm[r] && score + err >= pthr[f] && qidx[f] < nq) {
-                const int slot = atomicAdd(cand_cnt + qidx[f], 1);
-                if (slot < kBatchCand) cand[static_cast<int64_t>(qidx[f]) * kBatchCand + slot] = static_cast<int32_t>(row0 + r);
-              }
-            }
+          const float bias = (real && mm[r]) ? 0.0f : -__builtin_inff();
+          bias2 = f32x2{bias, bias};
         }
+        const f32x2 da = {static_cast<float>(acc[i][0][0][r]), static_cast<float>(acc[i][1][0][r])};
+        const f32x2 db = {static_cast<float>(acc[i][0][1][r]), static_cast<float>(acc[i][1][1][r])};
+        const f32x2 t = __builtin_elementwise_fma(PB, db, PA * da);
+        const f32x2 score = __builtin_elementwise_fma(f32x2{ss[r], ss[r]}, t, bias2);
+        const f32x2 err = __builtin_elementwise_fma(f32x2{ee[r], ee[r]}, P1, P2);
+        const f32x2 lo = score - err, up = score + err;
+        run2 = __builtin_elementwise_max(run2, lo);
+        top2 = __builtin_elementwise_max(top2, up);
       }
+      // the tile's 16 rows are spread over the four lane groups: each leaves its four-row maximum in LDS as
+      // [group][16 tiles][128 queries] f16 rounded up; they are folded on the way out (cross-lane maxima here — two
+      // swizzles per tile and fragment — cost pass 1 a sixth of its time, and so did writing the bounds as 2-byte
+      // stores from 16 lanes)
+      __half* dst = reinterpret_cast<__half*>(fold) + ((g * 16 + 8 * wm + i) * kBQ) + (2 * wn) * 16 + (lane & 15);
+      dst[0] = __float2half_ru(top2.x);
+      dst[16] = __float2half_ru(top2.y);
     }
-    VR_STAMP();
-    if (PASS == 1 && tile_ub) {
+    {
       __syncthreads();
       const int row = threadIdx.x >> 5, part = threadIdx.x & 31;  // 16 tiles x 32 pieces of four queries (8 bytes)
       using h4 = __attribute__((ext_vector_type(4))) _Float16;
@@ -443,26 +384,21 @@ __global__ __launch_bounds__(512) void batch_scan_kernel(
       }
       *reinterpret_cast<h4*>(tile_ub + (tile0 + row) * nq_pad + qc * kBQ + part * 4) = best4;
     }
-    if (PASS == 1) {
-      // this wave's 128 rows -> one value per query (the four lane groups hold different rows of the same queries)
+    // this wave's 128 rows -> one value per query (the four lane groups hold different rows of the same queries)
 #pragma unroll
-      for (int f = 0; f < 2; ++f) {
-        float v = run[f];
-        v = fmaxf(v, __shfl_xor(v, 16));
-        v = fmaxf(v, __shfl_xor(v, 32));
-        if (g == 0 && qidx[f] < nq) best[static_cast<int64_t>(qidx[f]) * (2 * n_rb) + 2 * rbi + wm] = v;
-      }
+    for (int f = 0; f < 2; ++f) {
+      float v = run2[f];
+      v = fmaxf(v, __shfl_xor(v, 16));
+      v = fmaxf(v, __shfl_xor(v, 32));
+      if (g == 0 && qidx[f] < nq) best[static_cast<int64_t>(qidx[f]) * (2 * n_rb) + 2 * rbi + wm] = v;
     }
-    VR_STAMP();
-    stamping = false;  // (the first item only)
     if (next_id >= n_ids) break;  // block-uniform
     // the next item's first K-step stages its second one into the buffer the fold above was read from
-    if (PASS == 1 && tile_ub) __syncthreads();
+    __syncthreads();
     id = next_id;
     rbi = nrbi;
     qc = nqc;
   }
-#undef VR_STAMP
 }
 
 // ---- instead of a second pass: revisit the few (tile, query) pairs that can hold a candidate ------------------
@@ -475,7 +411,7 @@ __global__ __launch_bounds__(512) void batch_scan_kernel(
 //   batch_pairs_kernel  a wave per pair: the 16 rows' exact int32 dot products with the query's two int8 parts on
 //                       v_dot4_i32_i8 (lane = (row, 16-byte k segment), the shadow tile and the query image are read
 //                       in the layout the MFMAs read them), then batch_bound() — the same bits as pass 1 — and the
-//                       rows whose upper bound reaches T_q go to the query's candidate list, as pass 2 put them.
+//                       rows whose upper bound reaches T_q go to the query's candidate list.
 
 __global__ __launch_bounds__(256) void batch_flag_kernel(const __half* __restrict__ tile_ub, const float* __restrict__ thr,
                                                          int64_t n_cells, int nq, int nq_pad, int32_t* __restrict__ pairs,
@@ -692,8 +628,7 @@ bool batch_usable(vr_engine* e, int nq, int k) {
 int batch_search(vr_engine* e, const float* q_dev, int nq, int k, const uint8_t* mask_dev, const uint64_t** out_keys_dev,
                  const int32_t** overflow_dev, const uint32_t* planes, const int32_t* q_cls_dev, int64_t plane_words) {
   const bool multi = planes != nullptr;
-  auto* scan1 = multi ? batch_scan_kernel<1, true> : batch_scan_kernel<1, false>;
-  auto* scan2 = multi ? batch_scan_kernel<2, true> : batch_scan_kernel<2, false>;
+  auto* scan = multi ? batch_scan_kernel<true> : batch_scan_kernel<false>;
   auto* pairs_k = multi ? batch_pairs_kernel<true> : batch_pairs_kernel<false>;
   hipStream_t s = e->stream;
   const int dim = e->dim, kb8n = dim / 64;
@@ -717,92 +652,37 @@ int batch_search(vr_engine* e, const float* q_dev, int nq, int k, const uint8_t*
                      s, q_dev, nq, dim, kb8n, e->bq_hat.p, img_a, img_b, e->bq_params.p,
                      e->centre_rows > 0 ? e->centre_norm : 0.0f);
   const unsigned grid = static_cast<unsigned>(((n_rb + 7) / 8) * n_qc * 8);
-  // Pass 1 only has to produce SOME k rows' lower bounds per query, so it could run on every stride-th row block
-  // (VR_BATCH_SAMPLE=stride; at least 8 k slabs, and 64, stay in the sample). Measured and NOT the default: the
-  // threshold of a sample is lower, and the candidate count is steep in it — bench corpus, 1000 queries: 69
-  // candidates per query with the full pass, 239 at stride 4 (scan 5.3 -> 3.5 ms, call 6.9 -> 6.7 ms: the exact
-  // re-score eats the gain), 800 at stride 16 with a fifth of the queries over budget; an anisotropic corpus
-  // overflows at stride 4 already (profiles/r02_gemm_experiments.md §11).
-  static const int want_stride = getenv("VR_BATCH_SAMPLE") ? std::max(1, atoi(getenv("VR_BATCH_SAMPLE"))) : 1;
-  const int stride = std::max(1, std::min(want_stride, 2 * n_rb / std::max(8 * k, 64)));
-  const int n_rb1 = (n_rb + stride - 1) / stride;
-  const unsigned grid1 = static_cast<unsigned>(((n_rb1 + 7) / 8) * n_qc * 8);
   // algorithmic work of the batched scan: 2 N D Q operations (the second query part is overhead); timed: the GEMM
-  // pass, the threshold selection, and the flag + pairs kernels (or the second pass)
+  // pass, the threshold selection, and the flag + pairs kernels
   prof_begin(e, VR_PROF_BATCH_SCAN, 2.0 * static_cast<double>(e->n_rows) * dim * nq);
-  // VR_BATCH_TWO_PASS=1 (and a sampled pass 1) keeps the second integer GEMM; the default revisits flagged pairs
-  static const bool two_pass_env = getenv("VR_BATCH_TWO_PASS") && atoi(getenv("VR_BATCH_TWO_PASS")) != 0;
-  const bool two_pass = two_pass_env || stride != 1;
   const int64_t n_cells = static_cast<int64_t>(n_rb) * 16 * nq_pad;  // (tile, query) cells, padded to whole blocks
   const int64_t pair_cap = static_cast<int64_t>(nq) * kBatchCand;  // tiles listed per query, then the counts
-  __half* tile_ub = nullptr;
-  if (!two_pass) {
-    VR_TRY(e->bq_tile_ub.grow(n_cells, 0, s));
-    VR_TRY(e->bq_pairs.grow(pair_cap + nq, 0, s));
-    VR_HIP(hipMemsetAsync(e->bq_pairs.p + pair_cap, 0, sizeof(int32_t) * static_cast<size_t>(nq), s));
-    tile_ub = reinterpret_cast<__half*>(e->bq_tile_ub.p);
-  }
-  // VR_BATCH_STAMPS=1 (diagnostics): phase time stamps of a sample of blocks, printed after the call
-  static const bool stamps_on = getenv("VR_BATCH_STAMPS") && atoi(getenv("VR_BATCH_STAMPS")) != 0;
-  unsigned long long* stamps = nullptr;
-  const size_t n_stamp_blocks = grid1 / 61 + 1;  // (room for the one-item-per-block grid)
-  if (stamps_on) {
-    VR_HIP(hipMalloc(reinterpret_cast<void**>(&stamps), n_stamp_blocks * 16 * sizeof(unsigned long long)));
-    VR_HIP(hipMemsetAsync(stamps, 0, n_stamp_blocks * 16 * sizeof(unsigned long long), s));
-  }
+  VR_TRY(e->bq_tile_ub.grow(n_cells, 0, s));
+  VR_TRY(e->bq_pairs.grow(pair_cap + nq, 0, s));
+  VR_HIP(hipMemsetAsync(e->bq_pairs.p + pair_cap, 0, sizeof(int32_t) * static_cast<size_t>(nq), s));
+  __half* tile_ub = reinterpret_cast<__half*>(e->bq_tile_ub.p);
   // persistent blocks: one per CU (128 KiB of LDS each), ids dealt round-robin — a multiple of 8 blocks keeps an id's XCD
   static const int n_cus = [] {
     int dev = 0, n = 256;
     if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
     return std::max(8, n / 8 * 8);
   }();
-  static const bool persistent = !(getenv("VR_BATCH_PERSISTENT") && atoi(getenv("VR_BATCH_PERSISTENT")) == 0);
-  const unsigned blocks1 = persistent ? std::min<unsigned>(grid1, static_cast<unsigned>(n_cus)) : grid1;
-  hipLaunchKernelGGL(scan1, dim3(blocks1), dim3(512), 0, s,
+  hipLaunchKernelGGL(scan, dim3(std::min<unsigned>(grid, static_cast<unsigned>(n_cus))), dim3(512), 0, s,
                      reinterpret_cast<const uint4*>(e->corpus16.p),
                      reinterpret_cast<const uint4*>(img_a), reinterpret_cast<const uint4*>(img_b), e->bq_params.p,
-                     e->row_err.p, e->row_scale.p, mask_dev, n_tiles, n_rb1, stride, n_qc, nq, kb8n, e->bq_best.p,
-                     static_cast<const float*>(nullptr), static_cast<int32_t*>(nullptr), static_cast<int32_t*>(nullptr),
-                     tile_ub, stamps, static_cast<int>(grid1), planes, q_cls_dev, plane_words);
-  if (stamps_on) {
-    std::vector<unsigned long long> h(n_stamp_blocks * 16);
-    VR_HIP(hipMemcpyAsync(h.data(), stamps, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    VR_HIP(hipStreamSynchronize(s));
-    (void)hipFree(stamps);
-    double sum[16] = {0};
-    int n = 0;
-    const int nk = kb8n / 2;  // K-steps of the kernel (<= 8: stamps fit in 16 slots)
-    for (size_t b = 0; b < n_stamp_blocks; ++b) {
-      const unsigned long long* t = h.data() + b * 16;
-      if (!t[0] || !t[nk + 4]) continue;
-      for (int i = 1; i <= nk + 4; ++i) sum[i] += static_cast<double>(t[i] - t[i - 1]);
-      ++n;
-    }
-    fprintf(stderr, "[batch_scan stamps] %d blocks, cycles per phase: prologue %.0f |", n, n ? sum[1] / n : 0.0);
-    for (int i = 2; i <= nk + 1; ++i) fprintf(stderr, " k%d %.0f", i - 2, n ? sum[i] / n : 0.0);
-    fprintf(stderr, " | row words %.0f | bounds %.0f | fold+store %.0f\n", n ? sum[nk + 2] / n : 0.0, n ? sum[nk + 3] / n : 0.0,
-            n ? sum[nk + 4] / n : 0.0);
-  }
+                     e->row_err.p, e->row_scale.p, mask_dev, n_tiles, n_rb, n_qc, nq, kb8n, e->bq_best.p, tile_ub,
+                     static_cast<int>(grid), planes, q_cls_dev, plane_words);
   const uint64_t* kth = nullptr;
-  VR_TRY(topk_select(e, e->bq_best.p, 2 * n_rb1, 2 * n_rb1, nq, k, &kth));
+  VR_TRY(topk_select(e, e->bq_best.p, 2 * n_rb, 2 * n_rb, nq, k, &kth));
   hipLaunchKernelGGL(batch_threshold_kernel, dim3(static_cast<unsigned>((nq + 255) / 256)), dim3(256), 0, s, kth, nq, k,
                      e->bq_thr.p);
-  if (two_pass) {
-    hipLaunchKernelGGL(scan2, dim3(grid), dim3(512), 0, s,
-                       reinterpret_cast<const uint4*>(e->corpus16.p),
-                       reinterpret_cast<const uint4*>(img_a), reinterpret_cast<const uint4*>(img_b), e->bq_params.p,
-                       e->row_err.p, e->row_scale.p, mask_dev, n_tiles, n_rb, 1, n_qc, nq, kb8n, static_cast<float*>(nullptr),
-                       e->bq_thr.p, e->bq_cand.p, e->bq_cnt.p, static_cast<__half*>(nullptr),
-                       static_cast<unsigned long long*>(nullptr), static_cast<int>(grid), planes, q_cls_dev, plane_words);
-  } else {
-    hipLaunchKernelGGL(batch_flag_kernel, dim3(static_cast<unsigned>((n_cells / 8 + 255) / 256)), dim3(256), 0, s, tile_ub,
-                       e->bq_thr.p, n_cells, nq, static_cast<int>(nq_pad), e->bq_pairs.p, e->bq_pairs.p + pair_cap);
-    hipLaunchKernelGGL(pairs_k, dim3(2048), dim3(256), 0, s,
-                       reinterpret_cast<const uint4*>(e->corpus16.p),
-                       reinterpret_cast<const uint4*>(img_a), reinterpret_cast<const uint4*>(img_b), e->bq_params.p,
-                       e->row_err.p, e->row_scale.p, mask_dev, e->n_rows, kb8n, e->bq_thr.p, nq, e->bq_pairs.p,
-                       e->bq_pairs.p + pair_cap, e->bq_cand.p, e->bq_cnt.p, planes, q_cls_dev, plane_words);
-  }
+  hipLaunchKernelGGL(batch_flag_kernel, dim3(static_cast<unsigned>((n_cells / 8 + 255) / 256)), dim3(256), 0, s, tile_ub,
+                     e->bq_thr.p, n_cells, nq, static_cast<int>(nq_pad), e->bq_pairs.p, e->bq_pairs.p + pair_cap);
+  hipLaunchKernelGGL(pairs_k, dim3(2048), dim3(256), 0, s,
+                     reinterpret_cast<const uint4*>(e->corpus16.p),
+                     reinterpret_cast<const uint4*>(img_a), reinterpret_cast<const uint4*>(img_b), e->bq_params.p,
+                     e->row_err.p, e->row_scale.p, mask_dev, e->n_rows, kb8n, e->bq_thr.p, nq, e->bq_pairs.p,
+                     e->bq_pairs.p + pair_cap, e->bq_cand.p, e->bq_cnt.p, planes, q_cls_dev, plane_words);
   prof_end(e);
   uint64_t* keys = e->bq_keys.p;
   uint64_t* out = keys + static_cast<int64_t>(nq) * kBatchCand;
@@ -811,7 +691,7 @@ int batch_search(vr_engine* e, const float* q_dev, int nq, int k, const uint8_t*
                      e->bq_cnt.p, nq, dim,
                      e->kblocks, keys);
   hipLaunchKernelGGL(batch_final_kernel, dim3(static_cast<unsigned>(nq)), dim3(256), 0, s, keys, e->bq_cnt.p,
-                     two_pass ? static_cast<const int32_t*>(nullptr) : e->bq_pairs.p + pair_cap, k, out, e->bq_cnt.p + nq);
+                     e->bq_pairs.p + pair_cap, k, out, e->bq_cnt.p + nq);
   VR_HIP(hipGetLastError());
   *out_keys_dev = out;
   *overflow_dev = e->bq_cnt.p + nq;

@@ -880,8 +880,7 @@ __global__ __launch_bounds__(kInvWaves * 64) void sparse_inv_pruned_kernel(
     const InvSeg* __restrict__ segs, int n_seg, const uint64_t* __restrict__ keys, const float* __restrict__ vals,
     const int32_t* __restrict__ q_off, const int32_t* __restrict__ q_ids, const float* __restrict__ q_w,
     const float* __restrict__ q_frac, const uint8_t* __restrict__ mask, int k, uint64_t* __restrict__ cand_out,
-    const InvForward fw, float n_points, const uint64_t* __restrict__ seed_keys, int32_t* __restrict__ need_full,
-    unsigned long long* __restrict__ dbg) {
+    const InvForward fw, float n_points, const uint64_t* __restrict__ seed_keys, int32_t* __restrict__ need_full) {
   __shared__ InvPrunedShared sh;
   const int qy = blockIdx.y;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -953,7 +952,6 @@ __global__ __launch_bounds__(kInvWaves * 64) void sparse_inv_pruned_kernel(
       // any set of real rows gives a valid bound, a smaller set a weaker one)
     } else {
       const uint64_t theta_key = seed_keys[static_cast<int64_t>(qy) * k + (k - 1)];
-      if (dbg && theta_key == 0ull) atomicAdd(dbg + 1, 1ull);  // diagnostics (VR_SPARSE_DEBUG=1): no seed
       if (theta_key != 0ull) {
         const float theta = inv_key_score(theta_key);
         const float vmax = __int_as_float(sh.vmax_bits);
@@ -969,7 +967,6 @@ __global__ __launch_bounds__(kInvWaves * 64) void sparse_inv_pruned_kernel(
         // one by one. Worth it while those postings are a minor part of all of them)
         // ... and the rows they name fit a wave's table: ~600 of a segment's 4096)
         if (n > 0 && ess * 3.0f < all && ess < 0.15f) ne = n;
-        if (dbg) atomicAdd(dbg + (ne >= 0 ? 0 : n == 0 ? 2 : 3), 1ull);  // pruned / every term essential / too many rows to mark
         sh.theta = theta;
       }
     }
@@ -1100,7 +1097,6 @@ __global__ __launch_bounds__(kInvWaves * 64) void sparse_inv_pruned_kernel(
     }
   }
   flush();
-  if (dbg && lane == 0) atomicAdd(dbg + (SEED ? 5 : 4), static_cast<unsigned long long>(scored));  // rows scored one by one
   block_merge_lists(sh.lists, kListLen, kInvWaves, wave, lane);
   if (threadIdx.x < kListLen) cand_out[slot * kListLen + threadIdx.x] = sh.lists[threadIdx.x];
 }
@@ -1131,10 +1127,7 @@ __global__ __launch_bounds__(kInvWaves * 64) void sparse_inv_pruned_kernel(
 // segment run together, blockIdx.x = group), against 12 B per posting, query and term before.
 constexpr int kGrpThreads = 512;
 constexpr int kGrpMaxU = 64;     // union terms of a group (the host closes a group before it exceeds this): one per lane
-#ifndef VR_GRP_SLICES
-#define VR_GRP_SLICES 4
-#endif
-constexpr int kGrpSlices = VR_GRP_SLICES;  // postings per thread and batch (two batches in flight). 4, not 8: 56 registers
+constexpr int kGrpSlices = 4;    // postings per thread and batch (two batches in flight). 4, not 8: 56 registers
                                            // instead of 79 let four blocks of a two-query group share a CU
 constexpr int kGrpPer = 2;       // ... of which a thread adds up this many together
 constexpr int kGrpHdr = 4 + 8;   // ints per group: union size, class (filtered batches), 2 spare, the (<= 8) queries' numbers (-1: none)
@@ -1259,7 +1252,7 @@ __global__ __launch_bounds__(kGrpThreads) void sparse_inv_group_kernel(
     const InvSeg* __restrict__ segs, const uint64_t* __restrict__ keys, const float* __restrict__ vals,
     const int32_t* __restrict__ grp_hdr, const int32_t* __restrict__ grp_ent, const float* __restrict__ ent_w,
     const int2* __restrict__ bounds, int stride_u, const uint8_t* __restrict__ mask, const uint64_t* __restrict__ theta,
-    uint64_t* __restrict__ cand, int32_t* __restrict__ cnt, int cap, int dbg_mode, int seg_stride,
+    uint64_t* __restrict__ cand, int32_t* __restrict__ cnt, int cap, int seg_stride,
     uint64_t* __restrict__ spill, int32_t* __restrict__ spill_cnt, int spill_cap, int sample_tail, int n_seg_all,
     const uint32_t* __restrict__ planes, int64_t plane_words) {
   static_assert(G >= 1 && G <= 8, "group size");
@@ -1347,7 +1340,7 @@ __global__ __launch_bounds__(kGrpThreads) void sparse_inv_group_kernel(
   __syncthreads();
   const int n_c = s_nc;
   const int total = s_pre[n_c];
-  if (total == 0 || (dbg_mode & 4)) return;  // block-uniform: no term of the group occurs in this segment
+  if (total == 0) return;  // block-uniform: no term of the group occurs in this segment
   const uint64_t* kp = keys + seg.off;
   const float* vp = vals + seg.off;
   // the run table once more, in registers: lane c of every wave holds run c (block-uniform reads are v_readlane then,
@@ -1401,10 +1394,8 @@ __global__ __launch_bounds__(kGrpThreads) void sparse_inv_group_kernel(
         const int i = s0 + v * kGrpThreads + tid;
         r[v] = static_cast<int>(bk[set][j0 + v] & (kInvSegRows - 1));
         val[v] = bv[set][j0 + v];
-        mine[v] = (i < total && !(dbg_mode & 1)) ? bc[set][j0 + v] : -1;
-        if ((dbg_mode & 9) && bk[set][j0 + v] == 0xFFFFFFFFu && val[v] == 1.25f) acc[0] = val[v];  // (diagnostics: keeps the loads alive)
+        mine[v] = i < total ? bc[set][j0 + v] : -1;
       }
-      if (dbg_mode & 8) continue;
       // every plane's sum of these rows, requested together (a read the posting may not need costs nothing but LDS
       // bandwidth; the writes below are conditional — another term's thread may own the planes this term does not touch)
 #pragma unroll
@@ -1451,7 +1442,6 @@ __global__ __launch_bounds__(kGrpThreads) void sparse_inv_group_kernel(
     add_up(1, base + kBatch);
   }
   __syncthreads();
-  if (dbg_mode & 2) return;
 
   // The rows that reach their query's threshold key (the seed's k-th: k real rows are at or above it) go to the
   // (query, segment) region of the candidate array — this block's own, so a slot costs an LDS atomic and the block ends
@@ -1658,23 +1648,25 @@ int inv_scan_topk(vr_engine* e, const int32_t* q_idx_host, const float* q_val_ho
   return topk_merge_lists(e, e->sp_cand.p, blocks, 1, k, out_keys_dev);
 }
 
+// keys per (query, segment) region of the grouped scan: 32 at a million rows (250 segments), more while the segments are
+// few (a region may then hold most of a query's k best), <= 8192 per query in all
+static int64_t inv_region_cap(int64_t n_seg) {
+  return std::max<int64_t>(kGrpCandCap, std::min<int64_t>(512, 8192 / std::max<int64_t>(n_seg, 1)));
+}
+
 // The grouped scan of a batch (see sparse_inv_group_kernel). out_keys_dev: in — the seed lists (sampled == false), out — the
 // nq x k result keys. *done = false: no query of the batch has terms (nothing was launched). Closes the profiler slot.
 static int inv_scan_grouped(vr_engine* e, const float* q_w_dev, int nq, const uint8_t* mask_dev, int k, uint64_t* out_keys_dev,
                             const int32_t* q_off_host, const int32_t* q_ids_host, bool sampled, bool* done,
                             const ClassPlanes* classes) {
-  // (2: 34 KB of LDS and 56 registers — four blocks = 32 waves per CU, the most a CU holds; measured best: the block is a
+  // (pairs: 34 KB of LDS and 56 registers — four blocks = 32 waves per CU, the most a CU holds; measured best: the block is a
   // chain of dependent phases and other blocks are what hides them — 2.5 ms of kernels per 1000 queries against 3.0 for
   // groups of 4 at two blocks per CU, although those read fewer postings)
-  const int want_group = std::getenv("VR_SPARSE_GROUP") ? atoi(std::getenv("VR_SPARSE_GROUP")) : 2;
-  const int group_size = !classes && (want_group == 3 || want_group == 4 || want_group == 8) ? want_group : 2;  // (planes: pairs)
-  const int dbg_mode = std::getenv("VR_SPARSE_GROUP_DBG") ? atoi(std::getenv("VR_SPARSE_GROUP_DBG")) : 0;  // timing experiments
+  constexpr int kGroup = 2;
   const int64_t n_seg = e->n_inv_seg;
-  // keys per (query, segment) region: 32 at a million rows (250 segments), more while the segments are few (a region may
-  // then hold most of a query's k best), <= 8192 per query in all
-  const int fit_cap = static_cast<int>(std::max<int64_t>(kGrpCandCap, std::min<int64_t>(512, 8192 / std::max<int64_t>(n_seg, 1))));
+  const int fit_cap = static_cast<int>(inv_region_cap(n_seg));
   const int cand_cap = std::getenv("VR_SPARSE_GROUP_CAP") ? std::min(fit_cap, std::max(1, atoi(std::getenv("VR_SPARSE_GROUP_CAP")))) : fit_cap;
-  const GroupLayout lay = inv_group_queries(q_off_host, q_ids_host, nq, group_size, &e->sq_grp_host, classes ? classes->q_cls : nullptr);
+  const GroupLayout lay = inv_group_queries(q_off_host, q_ids_host, nq, kGroup, &e->sq_grp_host, classes ? classes->q_cls : nullptr);
   *done = lay.n_groups > 0;
   if (!*done) return 0;
   const int64_t n_gu = static_cast<int64_t>(lay.n_groups) * lay.stride_u;
@@ -1719,89 +1711,61 @@ static int inv_scan_grouped(vr_engine* e, const float* q_w_dev, int nq, const ui
   auto launch = [&](auto kernel, int64_t rows_y, uint64_t* cand, int32_t* cnt, int cap, int stride) {
     hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(lay.n_groups), static_cast<unsigned>(rows_y)), dim3(kGrpThreads), 0, e->stream,
                        e->inv_seg.p, e->inv_key.p, e->inv_val.p, hdr, ent, e->sq_entw.p, grp_bounds, lay.stride_u, mask_dev, theta, cand,
-                       cnt, cap, dbg_mode, stride, spill, spill_cnt, kSpillCap, kSampleTail, static_cast<int>(n_seg), planes,
-                       plane_words);
+                       cnt, cap, stride, spill, spill_cnt, kSpillCap, kSampleTail, static_cast<int>(n_seg), planes, plane_words);
   };
   if (sampled) {
     // thresholds: the sampled segments scanned in full, the best key of every 512 rows kept; the k-th best of a query's
     // sample (real rows, real scores) is a lower bound of its final k-th best key
-    if (planes) launch(sparse_inv_group_kernel<2, true, true>, n_samp, samp_cand, samp_cnt, kSampCap, seg_stride);
-    else if (group_size == 2) launch(sparse_inv_group_kernel<2, true, false>, n_samp, samp_cand, samp_cnt, kSampCap, seg_stride);
-    else if (group_size == 3) launch(sparse_inv_group_kernel<3, true, false>, n_samp, samp_cand, samp_cnt, kSampCap, seg_stride);
-    else if (group_size == 4) launch(sparse_inv_group_kernel<4, true, false>, n_samp, samp_cand, samp_cnt, kSampCap, seg_stride);
-    else launch(sparse_inv_group_kernel<8, true, false>, n_samp, samp_cand, samp_cnt, kSampCap, seg_stride);
+    if (planes) launch(sparse_inv_group_kernel<kGroup, true, true>, n_samp, samp_cand, samp_cnt, kSampCap, seg_stride);
+    else launch(sparse_inv_group_kernel<kGroup, true, false>, n_samp, samp_cand, samp_cnt, kSampCap, seg_stride);
     VR_TRY(topk_select_regions(e, samp_cand, static_cast<int>(n_samp), kSampCap, samp_cnt, nullptr, 0, nullptr, nq, k, out_keys_dev,
                                pin_dev<int32_t>(e, kPinSparseOverflow), nullptr, nullptr));
   }
   hipLaunchKernelGGL(sparse_inv_theta_kernel, dim3(static_cast<unsigned>((lay.n_groups * 8 + 255) / 256)), dim3(256), 0, e->stream, hdr,
                      lay.n_groups, out_keys_dev, k, theta);
-  if (planes) launch(sparse_inv_group_kernel<2, false, true>, n_seg, e->sq_cand.p, e->sq_cnt.p, cand_cap, 1);
-  else if (group_size == 2) launch(sparse_inv_group_kernel<2, false, false>, n_seg, e->sq_cand.p, e->sq_cnt.p, cand_cap, 1);
-  else if (group_size == 3) launch(sparse_inv_group_kernel<3, false, false>, n_seg, e->sq_cand.p, e->sq_cnt.p, cand_cap, 1);
-  else if (group_size == 4) launch(sparse_inv_group_kernel<4, false, false>, n_seg, e->sq_cand.p, e->sq_cnt.p, cand_cap, 1);
-  else launch(sparse_inv_group_kernel<8, false, false>, n_seg, e->sq_cand.p, e->sq_cnt.p, cand_cap, 1);
+  if (planes) launch(sparse_inv_group_kernel<kGroup, false, true>, n_seg, e->sq_cand.p, e->sq_cnt.p, cand_cap, 1);
+  else launch(sparse_inv_group_kernel<kGroup, false, false>, n_seg, e->sq_cand.p, e->sq_cnt.p, cand_cap, 1);
   prof_end(e);
   VR_HIP(hipGetLastError());
   e->stat_sparse_grouped += nq;
   e->sq_overflow_q = overflow_q;
   VR_TRY(topk_select_regions(e, e->sq_cand.p, static_cast<int>(n_seg), cand_cap, e->sq_cnt.p, spill, kSpillCap, spill_cnt, nq, k,
                              out_keys_dev, pin_dev<int32_t>(e, kPinSparseOverflow), ranked, overflow_q));
-  if (std::getenv("VR_SPARSE_GROUP_DEBUG") && atoi(std::getenv("VR_SPARSE_GROUP_DEBUG")) != 0) {  // diagnostics: what filled the regions
-    std::vector<int32_t> h(static_cast<size_t>(cnt_main));
-    std::vector<uint64_t> th(static_cast<size_t>(lay.n_groups) * 8);
-    VR_HIP(hipMemcpyAsync(h.data(), e->sq_cnt.p, sizeof(int32_t) * h.size(), hipMemcpyDeviceToHost, e->stream));
-    VR_HIP(hipMemcpyAsync(th.data(), theta, sizeof(uint64_t) * th.size(), hipMemcpyDeviceToHost, e->stream));
-    VR_HIP(hipStreamSynchronize(e->stream));
-    int64_t over_regions = 0, max_region = 0, max_total = 0, over_q = 0, no_theta = 0, n_members = 0, max_spill = 0;
-    int worst_q = -1, worst_seg = -1;
-    for (int q = 0; q < nq; ++q) {
-      int64_t tot = 0;
-      for (int64_t s2 = 0; s2 < n_seg; ++s2) {
-        const int32_t c = h[static_cast<size_t>(q * n_seg + s2)];
-        tot += c;
-        over_regions += c > cand_cap;
-        if (c > max_region) max_region = c, worst_q = q, worst_seg = static_cast<int>(s2);
-      }
-      max_total = std::max(max_total, tot);
-      over_q += h[static_cast<size_t>(nq) * n_seg + 1 + q];
-      max_spill = std::max<int64_t>(max_spill, h[static_cast<size_t>(nq) * n_seg + 1 + nq + q]);
-    }
-    for (size_t i = 0; i < th.size(); ++i)
-      if (th[i] != ~0ull) {
-        ++n_members;
-        no_theta += th[i] == 0ull;
-      }
-    fprintf(stderr, "[sparse grouped] %d queries (%lld in groups, %lld without a threshold), %lld segments, region cap %d: largest region %lld "
-            "(query %d, segment %d), %lld regions over the cap, largest query total %lld, largest spill %lld, %lld queries overflowed\n", nq,
-            static_cast<long long>(n_members), static_cast<long long>(no_theta), static_cast<long long>(n_seg), cand_cap,
-            static_cast<long long>(max_region), worst_q, worst_seg, static_cast<long long>(over_regions),
-            static_cast<long long>(max_total), static_cast<long long>(max_spill), static_cast<long long>(over_q));
-  }
   VR_HIP(hipMemcpyAsync(pin_host<int32_t>(e, kPinSparseCands), ranked, sizeof(int32_t), hipMemcpyDeviceToHost, e->stream));
   return 0;
 }
 
-static bool inv_seeding() {
-  static const bool on = !(std::getenv("VR_SPARSE_SEED") && atoi(std::getenv("VR_SPARSE_SEED")) == 0);
-  return on;
-}
-static bool inv_debug() {
-  static const bool on = std::getenv("VR_SPARSE_DEBUG") && atoi(std::getenv("VR_SPARSE_DEBUG")) != 0;
-  return on;
-}
 // the grouped scan can take nq queries: enough of them, and candidate regions (nq x segments x >= 16 keys) under 2 GB
 static bool inv_grouped_fits(const vr_engine* e, int nq) {
   return nq >= 16 && e->n_inv_seg <= 65535 &&
-         static_cast<int64_t>(nq) * e->n_inv_seg * std::max<int64_t>(kGrpCandCap, std::min<int64_t>(512, 8192 / std::max<int64_t>(e->n_inv_seg, 1))) <= (int64_t{1} << 28) &&
-         !(std::getenv("VR_SPARSE_GROUPED") && atoi(std::getenv("VR_SPARSE_GROUPED")) == 0);
+         static_cast<int64_t>(nq) * e->n_inv_seg * inv_region_cap(e->n_inv_seg) <= (int64_t{1} << 28);
 }
-// ... with its thresholds from a sample of the segments, once there are enough of them
-static bool inv_sample_fits(const vr_engine* e) {
-  return e->n_inv_seg >= 128 && !(std::getenv("VR_SPARSE_GROUP_SAMPLE") && atoi(std::getenv("VR_SPARSE_GROUP_SAMPLE")) == 0);
+
+// How a batch of sparse queries is scanned.
+enum class SparseRoute {
+  kFull,            // every term's postings of every share (given weights: the engine does not know the terms' frequencies)
+  kSeedPruned,      // per query: seed lists, the pruned scan, the full scan of the shares that one flags
+  kGroupedSeed,     // seed lists, then the grouped scan with their k-th keys as thresholds (few segments)
+  kGroupedSampled,  // the grouped scan of a sample of the segments gives the thresholds of the grouped scan of all of them
+};
+
+// The one place where the route is chosen. The switches are read per call (tests compare the paths, and force an
+// overflow, in one process), VR_SPARSE_SEED once per process.
+static SparseRoute inv_pick_route(const vr_engine* e, int nq, bool weights_given, bool allow_grouped, bool host_csr) {
+  static const bool seeding = !(std::getenv("VR_SPARSE_SEED") && atoi(std::getenv("VR_SPARSE_SEED")) == 0);
+  if (!seeding || weights_given) return SparseRoute::kFull;
+  // many queries: groups of queries share a block per segment and every run of the group's terms is read once
+  // (batches whose candidate regions would pass 2 GB stay on the per-query kernels, as do the queries a grouped scan gave up)
+  const bool grouped = allow_grouped && host_csr && inv_grouped_fits(e, nq) &&
+                       !(std::getenv("VR_SPARSE_GROUPED") && atoi(std::getenv("VR_SPARSE_GROUPED")) == 0);
+  if (!grouped) return SparseRoute::kSeedPruned;
+  // ... with the thresholds from a sample of the segments scanned the same way, once there are enough of them
+  const bool sampled = e->n_inv_seg >= 128 && !(std::getenv("VR_SPARSE_GROUP_SAMPLE") && atoi(std::getenv("VR_SPARSE_GROUP_SAMPLE")) == 0);
+  return sampled ? SparseRoute::kGroupedSampled : SparseRoute::kGroupedSeed;
 }
 
 bool inv_class_grouped_usable(const vr_engine* e, int nq) {
-  return inv_usable(e, 1) && inv_seeding() && !inv_debug() && inv_grouped_fits(e, nq) && inv_sample_fits(e);
+  return inv_usable(e, 1) && inv_pick_route(e, nq, false, true, true) == SparseRoute::kGroupedSampled;
 }
 
 // nq queries in device memory (CSR as sparse_inv_batch_kernel takes it, raw values in q_val_dev) -> nq x k keys in
@@ -1828,62 +1792,55 @@ int inv_scan_topk_batch(vr_engine* e, const int32_t* q_off_dev, const int32_t* q
   gx = std::min(gx, kScanBlocks);
   const InvForward fw{e->row_slice.p, e->slices.p, e->sp_idx.p, e->sp_val.p};
   const dim3 block(kInvWaves * 64);
-  const bool pruned = inv_seeding() && !weights_given;  // (given weights: the engine does not know the terms' frequencies)
   const int gs = std::min(gx, 16);  // blocks per query of the seed pass (a few rows per segment: latency, not work)
   VR_TRY(e->sp_cand.grow(static_cast<int64_t>(nq) * std::max(gx, gs) * kListLen, 0, e->stream));
   prof_begin(e, VR_PROF_SPARSE_SCAN, 0.0);
+  const SparseRoute route = inv_pick_route(e, nq, weights_given, allow_grouped, q_off_host && q_ids_host);
+  // (a filtered batch's classes: only the sampled grouped scan reads planes — the caller asks inv_class_grouped_usable)
+  VR_CHECK(!classes || route == SparseRoute::kGroupedSampled, "the grouped sparse scan cannot take this filtered batch");
   const uint64_t* seed_keys = nullptr;
   const int32_t* need_full = nullptr;
-  const bool debug = inv_debug();
-  unsigned long long* dbg = nullptr;
-  if (pruned && debug) {
-    VR_HIP(hipMalloc(reinterpret_cast<void**>(&dbg), 8 * sizeof(unsigned long long)));
-    VR_HIP(hipMemsetAsync(dbg, 0, 8 * sizeof(unsigned long long), e->stream));
-  }
-  // many queries: groups of queries share a block per segment and every run of the group's terms is read once
-  // (inv_scan_grouped; VR_SPARSE_GROUPED=0 keeps the per-query kernels. The switches are read per call: tests compare the
-  // paths, and force an overflow, in one process)
-  // (its candidate regions are nq x segments x >= 16 keys: batches whose regions would pass 2 GB stay on the per-query kernels)
-  const bool grouped = pruned && !dbg && allow_grouped && q_off_host && q_ids_host && inv_grouped_fits(e, nq);
-  // ... with the thresholds from a sample of the segments scanned the same way, once there are enough of them
-  const bool sampled = grouped && inv_sample_fits(e);
-  // (a filtered batch's classes: only the sampled grouped scan reads planes — the caller asks inv_class_grouped_usable)
-  VR_CHECK(!classes || sampled, "the grouped sparse scan cannot take this filtered batch");
-  if (pruned && !sampled) {
-    // 1. seed: per query the k best rows among those that carry its rarest terms, scored exactly -> out_keys_dev; the
-    //    k-th of them is a lower bound of the final k-th best score (real rows, real scores)
+  // seed: per query the k best rows among those that carry its rarest terms, scored exactly -> out_keys_dev; the k-th of
+  // them is a lower bound of the final k-th best score (real rows, real scores)
+  auto seed = [&]() -> int {
     hipLaunchKernelGGL((sparse_inv_pruned_kernel<true>), dim3(static_cast<unsigned>(gs), static_cast<unsigned>(nq)), block, 0,
                        e->stream, e->inv_seg.p, static_cast<int>(e->n_inv_seg), e->inv_key.p, e->inv_val.p, q_off_dev, q_ids_dev, q_w_dev,
                        q_w_dev + n_terms, mask_dev, k, e->sp_cand.p, fw, n_points, static_cast<const uint64_t*>(nullptr),
-                       static_cast<int32_t*>(nullptr), dbg);
+                       static_cast<int32_t*>(nullptr));
     VR_TRY(topk_merge_lists(e, e->sp_cand.p, gs, nq, k, out_keys_dev));
     seed_keys = out_keys_dev;
-  }
-  if (grouped) {
-    bool done = false;
-    VR_TRY(inv_scan_grouped(e, q_w_dev, nq, mask_dev, k, out_keys_dev, q_off_host, q_ids_host, sampled, &done, classes));
-    if (done) return 0;
-    VR_CHECK(!sampled, "the grouped scan found no query with terms");  // (n_terms > 0 here: cannot happen)
-  }
-  if (pruned) {
-    // 2. the pruned scan: only the essential terms' postings, from the first segment on; blocks that cannot prune flag
-    //    their share
+    return 0;
+  };
+  // the pruned scan: only the essential terms' postings, from the first segment on; blocks that cannot prune flag their share
+  auto pruned = [&]() -> int {
     VR_TRY(e->stage_i32b.grow(static_cast<int64_t>(nq) * gx, 0, e->stream));
     hipLaunchKernelGGL((sparse_inv_pruned_kernel<false>), dim3(static_cast<unsigned>(gx), static_cast<unsigned>(nq)), block,
                        static_cast<size_t>(kInvWaves) * kPrunedHash * 8,
                        e->stream, e->inv_seg.p, static_cast<int>(e->n_inv_seg), e->inv_key.p, e->inv_val.p, q_off_dev, q_ids_dev, q_w_dev,
-                       q_w_dev + n_terms, mask_dev, k, e->sp_cand.p, fw, n_points, seed_keys, e->stage_i32b.p, dbg);
+                       q_w_dev + n_terms, mask_dev, k, e->sp_cand.p, fw, n_points, seed_keys, e->stage_i32b.p);
     need_full = e->stage_i32b.p;
-    if (dbg) {
-      unsigned long long h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      VR_HIP(hipMemcpyAsync(h, dbg, sizeof(h), hipMemcpyDeviceToHost, e->stream));
-      VR_HIP(hipStreamSynchronize(e->stream));
-      (void)hipFree(dbg);
-      fprintf(stderr, "[sparse batch] %d queries x %d shares: pruned %llu, no seed %llu, every term essential %llu, too many rows %llu; "
-              "rows scored one by one: %llu by the scan, %llu by the seed pass\n", nq, gx, h[0], h[1], h[2], h[3], h[4], h[5]);
-    }
+    return 0;
+  };
+  bool done = false;
+  switch (route) {
+    case SparseRoute::kGroupedSampled:
+      VR_TRY(inv_scan_grouped(e, q_w_dev, nq, mask_dev, k, out_keys_dev, q_off_host, q_ids_host, true, &done, classes));
+      VR_CHECK(done, "the grouped scan found no query with terms");  // (n_terms > 0 here: cannot happen)
+      return 0;
+    case SparseRoute::kGroupedSeed:
+      VR_TRY(seed());
+      VR_TRY(inv_scan_grouped(e, q_w_dev, nq, mask_dev, k, out_keys_dev, q_off_host, q_ids_host, false, &done, classes));
+      if (done) return 0;
+      VR_TRY(pruned());
+      break;
+    case SparseRoute::kSeedPruned:
+      VR_TRY(seed());
+      VR_TRY(pruned());
+      break;
+    case SparseRoute::kFull:
+      break;
   }
-  // 3. the full scan (every term's postings added up per segment) of the shares that are left — all of them without a seed
+  // the full scan (every term's postings added up per segment) of the shares that are left — all of them without a seed
   hipLaunchKernelGGL(sparse_inv_batch_kernel, dim3(static_cast<unsigned>(gx), static_cast<unsigned>(nq)), block, 0, e->stream,
                      e->inv_seg.p, static_cast<int>(e->n_inv_seg), e->inv_key.p, e->inv_val.p, q_off_dev, q_ids_dev, q_w_dev,
                      q_w_dev + n_terms, mask_dev, k, e->sp_cand.p, fw, seed_keys, need_full);
