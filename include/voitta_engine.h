@@ -126,7 +126,8 @@ typedef struct vr_bert_desc {
   int32_t intermediate;  /* multiple of 128 */
   int32_t vocab;
   int32_t max_pos;       /* max_position_embeddings; also the longest accepted sequence. VR_POS_ROTARY: the length of
-                          * the cos/sin table the engine builds, which is again the longest accepted sequence */
+                          * the cos/sin table the engine builds, which is again the longest accepted sequence.
+                          * 1 .. 8192 */
   int32_t type_vocab;
   int32_t pooling;       /* VR_POOL_MEAN | VR_POOL_CLS (sentence-transformers Pooling module) */
   int32_t normalize;     /* 1 = L2-normalise (sentence-transformers Normalize module) */

@@ -8,6 +8,10 @@ import os
 from functools import lru_cache
 
 
+DEFAULT_MAX_SEQ_LENGTH = 512
+MAX_SEQ_LENGTH_LIMIT = 8192  # the longest sequence the engine loads a model for (vr_encoder_load / vr_reranker_load)
+
+
 class Settings:
     def __init__(self):
         self.qdrant_collection: str = os.getenv("QDRANT_COLLECTION", "voitta_documents")  # config.py:30
@@ -37,6 +41,12 @@ class Settings:
         # that expect them and that the reference's e5 rule does not know (nomic: "search_document: " / "search_query: ")
         self.embed_passage_prefix: str = os.getenv("VOITTA_EMBED_PASSAGE_PREFIX", "")
         self.embed_query_prefix: str = os.getenv("VOITTA_EMBED_QUERY_PREFIX", "")
+        # the longest sequence, in tokens, that an embedder or reranker may run (opt-in above 512): a rotary checkpoint
+        # that declares more is truncated to it, an XLM-R one is refused; past 640 tokens attention streams its keys
+        self.max_seq_length: int = int(os.getenv("VOITTA_MAX_SEQ_LENGTH", str(DEFAULT_MAX_SEQ_LENGTH)))
+        if not 1 <= self.max_seq_length <= MAX_SEQ_LENGTH_LIMIT:
+            raise ValueError(f"VOITTA_MAX_SEQ_LENGTH={self.max_seq_length}: accepted values are 1 ... "
+                             f"{MAX_SEQ_LENGTH_LIMIT} (default {DEFAULT_MAX_SEQ_LENGTH})")
 
 
 @lru_cache

@@ -373,7 +373,7 @@ static int rerank_text(vr_engine* e, const vr::Tokenizer* tokenizer, int32_t n_q
                        const int64_t* query_lens, const int64_t* cand_off, const char* const* passages,
                        const int64_t* passage_lens, int32_t max_len, float* out_logits) {
   VR_CHECK(n_queries >= 0 && (n_queries == 0 || (tokenizer && queries && query_lens && cand_off)), "bad arguments");
-  VR_CHECK(max_len >= 3 && max_len <= 4096, "max_len %d", max_len);
+  VR_CHECK(max_len >= 3 && max_len <= 8192, "max_len %d", max_len);
   if (n_queries == 0) return check_engine(e);
   VR_CHECK(cand_off[0] == 0, "cand_off[0] = %lld, must be 0", static_cast<long long>(cand_off[0]));
   for (int q = 0; q < n_queries; ++q) {
@@ -400,10 +400,22 @@ static int rerank_text(vr_engine* e, const vr::Tokenizer* tokenizer, int32_t n_q
       a_len[static_cast<size_t>(i)] = query_lens[q];
     }
   std::vector<int64_t> off(static_cast<size_t>(n) + 1);
-  std::vector<int32_t> seg(static_cast<size_t>(n)), ids(static_cast<size_t>(n) * max_len);
+  // room for the ids: a piece consumes at least a byte of text (n * max_len ids would be megabytes of zeros to write
+  // at max_len = 8192); a normaliser that expands its input can need more, and then the tokenizer says how many
+  size_t room = 0;
+  for (int64_t i = 0; i < n; ++i)
+    room += static_cast<size_t>(std::min<int64_t>(a_len[static_cast<size_t>(i)] + passage_lens[i] + 4, max_len));
+  std::vector<int32_t> seg(static_cast<size_t>(n)), ids(room);
   int64_t needed = 0;
-  VR_TRY(tokenizer->encode_pairs(a.data(), a_len.data(), passages, passage_lens, n, max_len, off.data(), ids.data(),
-                                 seg.data(), static_cast<int64_t>(ids.size()), &needed));
+  int rc = tokenizer->encode_pairs(a.data(), a_len.data(), passages, passage_lens, n, max_len, off.data(), ids.data(),
+                                   seg.data(), static_cast<int64_t>(ids.size()), &needed);
+  if (rc == -2) {
+    ids.resize(static_cast<size_t>(needed));
+    rc = tokenizer->encode_pairs(a.data(), a_len.data(), passages, passage_lens, n, max_len, off.data(), ids.data(),
+                                 seg.data(), static_cast<int64_t>(ids.size()), &needed);
+    if (rc == 0) vr::set_error("%s", "");  // (the first attempt's "buffer holds ..." is not this call's error)
+  }
+  VR_TRY(rc);
   VR_CHECK(needed <= INT32_MAX, "%lld tokens", static_cast<long long>(needed));
   std::vector<int32_t> off32(static_cast<size_t>(n) + 1);
   for (int64_t i = 0; i <= n; ++i) off32[static_cast<size_t>(i)] = static_cast<int32_t>(off[static_cast<size_t>(i)]);
@@ -1744,9 +1756,19 @@ void give_query_row(vr_engine* e, float* p) {
 int question_wordpieces(const Tokenizer* tokenizer, const char* const* texts, const int64_t* lens, int n, int max_len,
                         std::vector<int32_t>* ids, std::vector<int32_t>* off32) {
   std::vector<int64_t> off(static_cast<size_t>(n) + 1, 0);
-  ids->resize(static_cast<size_t>(n) * max_len);
+  // room for the ids: a piece consumes at least a byte of text (n * max_len ids would be megabytes of zeros to write
+  // at max_len = 8192); a normaliser that expands its input can need more, and then the tokenizer says how many
+  size_t room = 0;
+  for (int i = 0; i < n; ++i) room += static_cast<size_t>(std::min<int64_t>(std::max<int64_t>(lens[i], 0) + 2, max_len));
+  ids->resize(room);
   int64_t needed = 0;
-  VR_TRY(tokenizer->encode(texts, lens, n, max_len, off.data(), ids->data(), static_cast<int64_t>(ids->size()), &needed));
+  int rc = tokenizer->encode(texts, lens, n, max_len, off.data(), ids->data(), static_cast<int64_t>(ids->size()), &needed);
+  if (rc == -2) {
+    ids->resize(static_cast<size_t>(needed));
+    rc = tokenizer->encode(texts, lens, n, max_len, off.data(), ids->data(), static_cast<int64_t>(ids->size()), &needed);
+    if (rc == 0) vr::set_error("%s", "");  // (the first attempt's "buffer holds ..." is not this call's error)
+  }
+  VR_TRY(rc);
   VR_CHECK(needed <= INT32_MAX, "%lld tokens", static_cast<long long>(needed));
   ids->resize(static_cast<size_t>(needed));
   off32->resize(static_cast<size_t>(n) + 1);

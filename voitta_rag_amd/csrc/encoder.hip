@@ -3085,154 +3085,20 @@ __global__ __launch_bounds__(256) void attention_kernel(const float* __restrict_
 // v_mfma_f32_16x16x32_f16 has the C layout of the 16x16x4 instruction, so the structure above
 // carries over: S^T = K Q^T leaves lane (q, g) with the logits of keys 16t + 4g + r — and the B
 // operand of O^T += V^T P^T wants 8 k-slots per lane, so a 32-key step takes its slots in the order
-// (g, tile parity, r): slot 8g + 4b + r = key 32u + 16b + 4g + r. V is staged TRANSPOSED in that
-// order (sVt[d][slot]), so its A fragments are plain 16-byte reads. 16 MFMAs of 16 cycles per 64
-// keys against 128 of 32 cycles in the f32 kernel: the kernel is bound by the softmax's VALU work.
-// NW waves = 16 * NW queries per block.
-template <int DH, int NW>
-__global__ __launch_bounds__(NW * 64) void attention_f16_kernel(const half_t* __restrict__ qkv,
-                                                            const int32_t* __restrict__ cu, int seq0,
-                                                            int tok_base, int H, int qblocks, float scale,
-                                                            half_t* __restrict__ ctx_h) {
-  constexpr int LDK = DH + 8;   // halfs per staged K row
-  constexpr int LDV = 64 + 8;   // halfs per staged V^T row (64 key slots)
-  constexpr int NS = DH / 16;   // 16-wide d blocks of the output
-  constexpr int NKB = DH / 32;  // 32-deep MFMA steps over d
-  __shared__ half_t sK[64 * LDK];
-  __shared__ half_t sVt[DH * LDV];
-  __shared__ half_t sV[64 * LDK];  // V rows as loaded; transposed into sVt by the wave that wrote them
-  const int seq = seq0 + blockIdx.x / qblocks;
-  const int qb = blockIdx.x % qblocks;
-  const int head = blockIdx.y;
-  const int t0 = cu[seq] - tok_base;
-  const int len = cu[seq + 1] - cu[seq];
-  if (qb * (NW * 16) >= len) return;
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
-  const int qi = lane & 15, g = lane >> 4;
-  const int q_tok = qb * (NW * 16) + wave * 16 + qi;
-  const bool q_valid = q_tok < len;
-  const int64_t row3 = 3 * static_cast<int64_t>(H);
-
-  f16x8 qf[NKB];
-  {
-    const half_t* qp = qkv + (t0 + (q_valid ? q_tok : len - 1)) * row3 + head * DH + 8 * g;
-#pragma unroll
-    for (int u = 0; u < NKB; ++u) qf[u] = *reinterpret_cast<const f16x8*>(qp + 32 * u);
-  }
-  const float scale2 = scale * 1.4426950408889634f;  // logits in the log2 domain: the softmax uses v_exp_f32 directly
-  f32x4 o[NS];
-#pragma unroll
-  for (int s = 0; s < NS; ++s) o[s] = f32x4{0.f, 0.f, 0.f, 0.f};
-  float m = -__builtin_inff();
-  float l = 0.0f;
-
-  for (int kt = 0; kt < len; kt += 64) {
-    __syncthreads();
-    // K: 16-byte rows. V: transposed on the way in, in two conflict-free steps — the wave writes its 8
-    // (DH = 64) or 16 (DH = 32) key rows to sV as loaded, then lane d reads column d of 8 of those rows
-    // (64 lanes = 128 contiguous bytes per row) and writes them as two 8-byte pieces of sVt[d]. (Scattering
-    // the eight halfs of a loaded row straight into eight sVt rows put the lanes of a store 8 rows apart on
-    // two banks: 70 % of the kernel's LDS cycles were bank conflicts.)
-    for (int idx = tid; idx < 64 * (DH / 8); idx += NW * 64) {
-      const int key = idx / (DH / 8), c8 = idx % (DH / 8);
-      uint4 kv = make_uint4(0, 0, 0, 0), vv = kv;
-      if (kt + key < len) {
-        const half_t* p = qkv + (t0 + kt + key) * row3 + H + head * DH + c8 * 8;
-        kv = *reinterpret_cast<const uint4*>(p);
-        vv = *reinterpret_cast<const uint4*>(p + H);
-      }
-      *reinterpret_cast<uint4*>(sK + key * LDK + c8 * 8) = kv;
-      *reinterpret_cast<uint4*>(sV + key * LDK + c8 * 8) = vv;
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-      __builtin_amdgcn_wave_barrier();
-      // the wave's keys this iteration: kb .. kb + 512 / DH - 1; lane -> (d, group of 8 keys)
-      const int kb = (idx - lane) / (DH / 8);
-      const int d = lane % DH, k8 = kb + 8 * (lane / DH);
-      half_t h[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) h[j] = sV[(k8 + j) * LDK + d];
-      // keys k8 .. k8 + 3 -> slots sa .. sa + 3, keys k8 + 4 .. k8 + 7 -> slots sa + 8 .. sa + 11
-      // (key = 32u + 16b + 4g' + r  ->  slot 32u + 8g' + 4b + r, and k8 is a multiple of 8)
-      const int sa = (k8 & 32) + ((k8 >> 2) & 3) * 8 + ((k8 >> 4) & 1) * 4;
-      *reinterpret_cast<uint2*>(sVt + d * LDV + sa) = *reinterpret_cast<const uint2*>(h);
-      *reinterpret_cast<uint2*>(sVt + d * LDV + sa + 8) = *reinterpret_cast<const uint2*>(h + 4);
-    }
-    __syncthreads();
-
-    f32x4 st[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      st[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int u = 0; u < NKB; ++u) {
-        const f16x8 kf = *reinterpret_cast<const f16x8*>(sK + (t * 16 + qi) * LDK + 32 * u + 8 * g);
-        st[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf, qf[u], st[t], 0, 0, 0);
-      }
-    }
-    float mx = -__builtin_inff();
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int key = kt + t * 16 + 4 * g + r;
-        const float v = key < len ? st[t][r] * scale2 : -__builtin_inff();
-        st[t][r] = v;
-        mx = fmaxf(mx, v);
-      }
-    mx = fmaxf(mx, __shfl_xor(mx, 16));
-    mx = fmaxf(mx, __shfl_xor(mx, 32));
-    const float m_new = fmaxf(m, mx);  // finite: key kt < len is always valid
-    const float alpha = __builtin_amdgcn_exp2f(m - m_new);
-    float psum = 0.0f;
-    f16x8 pb[2];
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float p = __builtin_amdgcn_exp2f(st[t][r] - m_new);
-        psum += p;
-        pb[t >> 1][(t & 1) * 4 + r] = static_cast<half_t>(p);
-      }
-    l = l * alpha + psum;
-    m = m_new;
-#pragma unroll
-    for (int s = 0; s < NS; ++s) o[s] *= alpha;
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-      for (int s = 0; s < NS; ++s) {
-        const f16x8 vf = *reinterpret_cast<const f16x8*>(sVt + (16 * s + qi) * LDV + 32 * u + 8 * g);
-        o[s] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf, pb[u], o[s], 0, 0, 0);
-      }
-  }
-  l += __shfl_xor(l, 16);
-  l += __shfl_xor(l, 32);
-  if (q_valid) {
-    const float inv = 1.0f / l;
-    const int64_t off = static_cast<int64_t>(t0 + q_tok) * H + head * DH + 4 * g;
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-      half_t h[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) h[r] = static_cast<half_t>(fminf(fmaxf(o[s][r] * inv, -65504.0f), 65504.0f));
-      *reinterpret_cast<uint2*>(ctx_h + off + 16 * s) = *reinterpret_cast<const uint2*>(h);
-    }
-  }
-}
+// (g, tile parity, r): slot 8g + 4b + r = key 32u + 16b + 4g + r. 16 MFMAs of 16 cycles per 64 keys and
+// 16-query tile against 128 of 32 cycles in the f32 kernel: the softmax's VALU work is what bounds it.
+// Two kernels: attention_seq_kernel while a sequence's K and V fit a workgroup's LDS, attention_stream_kernel beyond.
 
 // ---- attention, one block per (sequence, head) -------------------------------------------------------------
 //
-// attention_f16_kernel above stages 64 keys at a time, once per 64-query block: for the ~118-token chunks of the
-// indexing path that is four staging phases per (sequence, head), each with its global-load latency exposed and its
-// V tile transposed through LDS by hand — the kernel runs at half of what its 1.6 GB per launch cost at the HBM rate.
+// A kernel that stages 64 keys at a time, once per 64-query block, pays four staging phases per (sequence, head) on the
+// ~118-token chunks of the indexing path, each with its global-load latency exposed (the first f16 kernel did, and
+// transposed its V tile through LDS by hand: it ran at half of what its 1.6 GB per launch cost at the HBM rate).
 // Here the block stages the sequence's K and V rows ONCE, all loads of up to 128 keys in flight together, V stays
 // row-major in LDS and its transposed MFMA operand comes out of ds_read_b64_tr_b16 (lane 4q + p of a 16-lane group
 // addresses row q, columns 4p..4p+3 of a 4 x 16 block; lane i receives column i); the four waves then walk the
-// sequence's 16-query tiles (wave w: tiles w, w + 4, ...) against keys already in LDS. Same arithmetic as
-// attention_f16_kernel (logits on the f16 MFMA, online softmax in the log2 domain over 64-key tiles, P as f16).
+// sequence's 16-query tiles (wave w: tiles w, w + 4, ...) against keys already in LDS. Logits on the f16 MFMA, online
+// softmax in the log2 domain over 64-key tiles, P as f16.
 // `q_limit`: only queries below it are computed (the last layer of a CLS-pooled model needs token 0 only).
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 
@@ -3412,6 +3278,203 @@ __global__ __launch_bounds__(NW * 64) void attention_seq_kernel(const half_t* __
   }
 }
 
+// ---- attention, keys streamed through LDS: sequences too long to stage whole ---------------------------------
+//
+// attention_seq_kernel holds a sequence's K and V in LDS: 640 keys at d_h = 64. Past that the keys stream: one block =
+// 128 queries of one (sequence, head), and the sequence's keys pass through LDS in 64-key tiles, K and V row-major with
+// the swizzles of attention_seq_kernel (the same ds_read_b128 / ds_read_b64_tr_b16 fragments, a tile's rows taking the
+// place of the sequence's). Each wave owns 32 queries as two 16-query tiles held in registers, so every K fragment and
+// every transposed V fragment read from LDS feeds two MFMAs. The tiles are double-buffered: tile j + 1's rows are
+// requested into registers before tile j's products (CH / NW 16-byte loads of K and of V per thread, all in flight
+// together), written to the other buffer behind those products, and one barrier per tile hands it over. Rows behind
+// the sequence's end are staged as zeros, their logits masked to -inf before the running maximum. Same arithmetic as
+// attention_seq_kernel. Grid: heads fastest, then the 128-query blocks of a sequence (`qblocks` of them per sequence);
+// `q_limit` as in attention_seq_kernel — the host launches query block 0 alone for it, and a wave whose queries all
+// lie at or behind it stages and takes every barrier but skips the products.
+template <int DH, int NW>
+__global__ __launch_bounds__(NW * 64) void attention_stream_kernel(const half_t* __restrict__ qkv, const int32_t* __restrict__ cu,
+                                                               int seq0, int tok_base, int H, int qblocks, float scale,
+                                                               int q_limit, half_t* __restrict__ ctx_h) {
+  static_assert(NW == 4 && (DH == 64 || DH == 32), "one 16-byte piece of a 64-key tile per thread and CH / NW rounds");
+  constexpr int LDK = DH;       // halfs per staged row: unpadded, 16-byte chunks XOR-swizzled by the row
+  constexpr int CH = DH / 8;    // 16-byte chunks per row
+  constexpr int NS = DH / 16;   // 16-wide d blocks of the output
+  constexpr int NKB = DH / 32;  // 32-deep MFMA steps over d
+  constexpr int NT = NW * 64;
+  constexpr int NLD = 64 * CH / NT;  // 16-byte loads of K and of V per thread and tile
+  constexpr int TILE = 64 * LDK;     // halfs of one K or V tile
+  auto kswz = [](int r) { return DH == 64 ? (r >> 1) & 7 : (r >> 1) & 3; };
+  auto vswz = [](int r) { return DH == 64 ? ((r >> 1) & 3) << 1 : ((r >> 2) & 1) << 1; };
+  __shared__ __attribute__((aligned(16))) half_t att_tiles[4 * TILE];  // buffer b: K at 2 b TILE, V at (2 b + 1) TILE
+  const int n_heads = H / DH;
+  const int head = static_cast<int>(blockIdx.x) % n_heads;
+  const int sq = static_cast<int>(blockIdx.x) / n_heads;
+  const int seq = seq0 + sq / qblocks;
+  const int q0 = (sq % qblocks) * (NW * 32);
+  const int t0 = cu[seq] - tok_base;
+  const int len = cu[seq + 1] - cu[seq];
+  if (q0 >= len) return;  // block-uniform, ahead of every barrier
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int qi = lane & 15, g = lane >> 4;
+  const int64_t row3 = 3 * static_cast<int64_t>(H);
+  const int q_end = min(len, q_limit);
+  const int qw = q0 + wave * 32;   // the wave's first query
+  const bool active = qw < q_end;  // wave-uniform: EXEC stays full inside (the transposed reads need it)
+  const bool two = qw + 16 < q_end;  // ... and so is this: the wave's second tile holds a query (not so in the CLS tail)
+
+  f16x8 qf[2][NKB];
+  if (active) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const half_t* qp = qkv + (t0 + min(qw + 16 * i + qi, len - 1)) * row3 + head * DH + 8 * g;
+#pragma unroll
+      for (int u = 0; u < NKB; ++u) qf[i][u] = *reinterpret_cast<const f16x8*>(qp + 32 * u);
+    }
+  }
+  // a tile's rows: requested from a row inside the sequence whatever the key (no branch around a load), zeroed behind
+  // the sequence's end when they are written. The registers of a request belong to one iteration of the key loop (a
+  // pair carried around the loop is copied, and the copy waits for the loads ahead of the products).
+  const half_t* kv_base = qkv + static_cast<int64_t>(t0) * row3 + H + head * DH;
+  auto request = [&](int kt, uint4 (&kr)[NLD], uint4 (&vr)[NLD]) {
+#pragma unroll
+    for (int i = 0; i < NLD; ++i) {
+      const int idx = i * NT + tid;
+      const half_t* p = kv_base + min(kt + idx / CH, len - 1) * row3 + (idx % CH) * 8;
+      kr[i] = *reinterpret_cast<const uint4*>(p);
+      vr[i] = *reinterpret_cast<const uint4*>(p + H);
+    }
+  };
+  auto write = [&](int kt, const uint4 (&kr)[NLD], const uint4 (&vr)[NLD], half_t* sK, half_t* sV) {
+#pragma unroll
+    for (int i = 0; i < NLD; ++i) {
+      const int idx = i * NT + tid;
+      const int key = idx / CH, c8 = idx % CH;
+      const bool behind = kt + key >= len;
+      *reinterpret_cast<uint4*>(sK + key * LDK + (c8 ^ kswz(key)) * 8) = behind ? make_uint4(0, 0, 0, 0) : kr[i];
+      *reinterpret_cast<uint4*>(sV + key * LDK + (c8 ^ vswz(key)) * 8) = behind ? make_uint4(0, 0, 0, 0) : vr[i];
+    }
+  };
+  {
+    uint4 kr[NLD], vr[NLD];
+    request(0, kr, vr);
+    write(0, kr, vr, att_tiles, att_tiles + TILE);
+  }
+  __syncthreads();
+
+  const float scale2 = scale * 1.4426950408889634f;  // logits in the log2 domain: the softmax uses v_exp_f32 directly
+  // transposed V reads: lane 4q + p of its 16-lane group -> row (key) q, columns 4p .. 4p + 3 of the block
+  const int tr_q = (lane & 15) >> 2, tr_p = lane & 3;
+  const int tr_row = tr_q * LDK, tr_sw = vswz(4 * g + tr_q), tr_in = 4 * (tr_p & 1);
+  const int k_sw = kswz(qi);  // rows 16 t + qi of the tile
+  f32x4 o[2][NS];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int s = 0; s < NS; ++s) o[i][s] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float m[2] = {-__builtin_inff(), -__builtin_inff()};
+  float l[2] = {0.0f, 0.0f};
+  int buf = 0;
+  for (int kt = 0; kt < len; kt += 64, buf ^= 1) {
+    const bool more = kt + 64 < len;  // block-uniform
+    uint4 kr[NLD], vr[NLD];
+    if (more) request(kt + 64, kr, vr);
+    if (active) {
+      const half_t* sK = att_tiles + 2 * buf * TILE;
+      const half_t* sV = sK + TILE;
+      f32x4 st[2][4];
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        st[0][t] = st[1][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int u = 0; u < NKB; ++u) {
+          const f16x8 kf = *reinterpret_cast<const f16x8*>(sK + (t * 16 + qi) * LDK + ((4 * u + g) ^ k_sw) * 8);
+          st[0][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf, qf[0][u], st[0][t], 0, 0, 0);
+          if (two) st[1][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf, qf[1][u], st[1][t], 0, 0, 0);
+        }
+      }
+      f16x8 pb[2][2];  // pb[i][u][j]: key kt + 32 u + 16 (j >> 2) + 4 g + (j & 3)
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        if (i == 1 && !two) break;
+        float mx = -__builtin_inff();
+        if (kt + 64 <= len) {  // every key of the tile exists: no masks
+#pragma unroll
+          for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              st[i][t][r] *= scale2;
+              mx = fmaxf(mx, st[i][t][r]);
+            }
+        } else {
+#pragma unroll
+          for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int key = kt + t * 16 + 4 * g + r;
+              const float v = key < len ? st[i][t][r] * scale2 : -__builtin_inff();
+              st[i][t][r] = v;
+              mx = fmaxf(mx, v);
+            }
+        }
+        mx = fmaxf(mx, __shfl_xor(mx, 16));
+        mx = fmaxf(mx, __shfl_xor(mx, 32));
+        const float m_new = fmaxf(m[i], mx);  // finite: key kt < len is always valid
+        const float alpha = __builtin_amdgcn_exp2f(m[i] - m_new);
+        float psum = 0.0f;
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float p = __builtin_amdgcn_exp2f(st[i][t][r] - m_new);
+            psum += p;
+            pb[i][t >> 1][(t & 1) * 4 + r] = static_cast<half_t>(p);
+          }
+        l[i] = l[i] * alpha + psum;
+        m[i] = m_new;
+#pragma unroll
+        for (int s = 0; s < NS; ++s) o[i][s] *= alpha;
+      }
+#pragma unroll
+      for (int u = 0; u < 2; ++u)
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+          // V^T fragment: d = 16 s + qi, k index 8 g + j <-> the key of pb[.][u][j]: two 4-key blocks, 16 keys apart
+          const half_t* vb = sV + (32 * u + 4 * g) * LDK + tr_row + ((2 * s + (tr_p >> 1)) ^ tr_sw) * 8 + tr_in;
+          const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(vb));
+          const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(vb + 16 * LDK));
+          f16x8 vf;
+          *reinterpret_cast<s16x4*>(&vf) = lo;
+          *(reinterpret_cast<s16x4*>(&vf) + 1) = hi;
+          o[0][s] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf, pb[0][u], o[0][s], 0, 0, 0);
+          if (two) o[1][s] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf, pb[1][u], o[1][s], 0, 0, 0);
+        }
+    }
+    if (more) write(kt + 64, kr, vr, att_tiles + 2 * (buf ^ 1) * TILE, att_tiles + (2 * (buf ^ 1) + 1) * TILE);
+    __syncthreads();  // tile kt + 64 is in place, and nobody reads tile kt any more
+  }
+  if (!active) return;
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    float li = l[i];
+    li += __shfl_xor(li, 16);
+    li += __shfl_xor(li, 32);
+    const int q_tok = qw + 16 * i + qi;
+    if (q_tok < len && (i == 0 || two)) {
+      const float inv = 1.0f / li;
+      const int64_t off = static_cast<int64_t>(t0 + q_tok) * H + head * DH + 4 * g;
+#pragma unroll
+      for (int s = 0; s < NS; ++s) {
+        half_t h[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) h[r] = static_cast<half_t>(fminf(fmaxf(o[i][s][r] * inv, -65504.0f), 65504.0f));
+        *reinterpret_cast<uint2*>(ctx_h + off + 16 * s) = *reinterpret_cast<const uint2*>(h);
+      }
+    }
+  }
+}
+
 // ---- host side -----------------------------------------------------------------------------------
 
 static int dev_alloc_copy(vr_engine* e, Encoder* enc, const void* src, size_t n_floats, int mem, float** out) {
@@ -3559,7 +3622,8 @@ static int build_encoder(vr_engine* e, void** slot, const vr_bert_desc* d_in, co
   const int per_layer = gated ? 18 : 16;
   VR_CHECK(!rotary || (std::isfinite(d->rope_theta) && d->rope_theta > 0.0f), "rope_theta %g must be positive",
            static_cast<double>(d->rope_theta));
-  VR_CHECK(d->max_pos >= 1, "max_pos %d must be positive", d->max_pos);
+  VR_CHECK(d->max_pos >= 1 && d->max_pos <= 8192, "max_pos %d must lie in 1..8192 (the longest sequence the engine runs)",
+           d->max_pos);
   VR_CHECK(L >= 1 && H >= 128 && H % 128 == 0 && H <= 1024, "hidden %d must be a multiple of 128 in 128..1024", H);
   VR_CHECK(I % 128 == 0 && I % BK == 0, "intermediate %d must be a multiple of 128", I);
   VR_CHECK(d->heads >= 1 && H % d->heads == 0 && (H / d->heads == 32 || H / d->heads == 64),
@@ -3913,7 +3977,7 @@ static int forward_chunk(vr_engine* e, Encoder* enc, const int32_t* ids_dev, con
     else if (plain && fuse_rope)
       VR_TRY(launch_gemm_f16x3(e, enc, EPI_ROPE_F16, {.A = xh, .W = w.s_qkv_p, .bias = w.bqkv_p, .Ch = qkvh, .M = T, .N = 3 * H,
                                                       .K = H, .passes = 1, .rope_tab = enc->rope, .rope_pos = posidx}));
-    else if (plain)  // Q, K, V as plain f16 rows for attention_f16_kernel
+    else if (plain)  // Q, K, V as plain f16 rows for the f16 attention kernels
       VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_F16, {.A = xh, .A_lo = xl, .W = w.s_qkv, .bias = w.bqkv, .Ch = qkvh, .M = T,
                                                       .N = 3 * H, .K = H, .passes = passes}));
     else if (split)
@@ -3926,8 +3990,8 @@ static int forward_chunk(vr_engine* e, Encoder* enc, const int32_t* ids_dev, con
     dim3 agrid(static_cast<unsigned>(n_seq * qb), static_cast<unsigned>(nh));
     prof_begin(e, VR_PROF_ATTENTION, tail ? attn_flop / qblocks : attn_flop);
     // f16 mode: one block per (sequence, head) with the sequence's K/V staged once in dynamic LDS (attention_seq_kernel)
-    // while the longest sequence's rows fit what a workgroup may have on this device; beyond that (rotary models admit
-    // such lengths through max_pos) attention_f16_kernel, which streams the keys in 64-row tiles through static LDS
+    // while the longest sequence's rows fit what a workgroup may have on this device; beyond that (max_pos admits up
+    // to 8192 tokens) attention_stream_kernel, which streams the keys in 64-row tiles through static LDS
     const int lds_keys = (max_len + 15) & ~15;
     const size_t lds_bytes = static_cast<size_t>(2) * lds_keys * dh * sizeof(half_t);
     static size_t lds_limit = 0;
@@ -3956,12 +4020,17 @@ static int forward_chunk(vr_engine* e, Encoder* enc, const int32_t* ids_dev, con
       else
         hipLaunchKernelGGL((attention_seq_kernel<32, 4>), sgrid, dim3(256), lds_bytes, s, reinterpret_cast<const half_t*>(enc->qkv),
                            cu_dev, seq0, tok_base, H, scale, q_limit, lds_keys, ch);
-    } else if (plain && dh == 64)  // (8 waves = 128 queries per block stage K/V once per 128-token sequence, and measured 30 % slower)
-      hipLaunchKernelGGL((attention_f16_kernel<64, 4>), agrid, dim3(256), 0, s, reinterpret_cast<const half_t*>(enc->qkv),
-                         cu_dev, seq0, tok_base, H, qb, scale, ch);
-    else if (plain)
-      hipLaunchKernelGGL((attention_f16_kernel<32, 4>), agrid, dim3(256), 0, s, reinterpret_cast<const half_t*>(enc->qkv),
-                         cu_dev, seq0, tok_base, H, qb, scale, ch);
+    } else if (plain) {  // 128 queries per block
+      const int qb128 = tail ? 1 : (max_len + 127) / 128;
+      const dim3 sgrid(static_cast<unsigned>(n_seq) * static_cast<unsigned>(qb128) * static_cast<unsigned>(nh));
+      const int q_limit = tail ? 16 : max_len;
+      if (dh == 64)
+        hipLaunchKernelGGL((attention_stream_kernel<64, 4>), sgrid, dim3(256), 0, s, reinterpret_cast<const half_t*>(enc->qkv),
+                           cu_dev, seq0, tok_base, H, qb128, scale, q_limit, ch);
+      else
+        hipLaunchKernelGGL((attention_stream_kernel<32, 4>), sgrid, dim3(256), 0, s, reinterpret_cast<const half_t*>(enc->qkv),
+                           cu_dev, seq0, tok_base, H, qb128, scale, q_limit, ch);
+    }
     else if (dh == 64)
       hipLaunchKernelGGL((attention_kernel<64>), agrid, dim3(256), 0, s, enc->qkv, cu_dev, seq0, tok_base, H,
                          qb, scale, enc->ctx, ch, cl);

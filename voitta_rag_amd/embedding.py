@@ -17,15 +17,31 @@ import numpy as np
 
 from . import deferred as _deferred
 from . import encoder as _enc
-from .config import get_settings
+from .config import MAX_SEQ_LENGTH_LIMIT, get_settings
 from .store_registry import get_engine
 from .unigram import UnigramTokenizer, is_unigram_pipeline
 from .wordpiece import WordPieceTokenizer
 
 logger = logging.getLogger(__name__)
 
-# the longest sequence the attention kernels have run (a checkpoint that declares more is refused at load)
+# the default cap on a sequence's tokens; VOITTA_MAX_SEQ_LENGTH (1 ... 8192) sets another one, see seq_cap()
 MAX_SEQ = 512
+SEQ_CAP_VARIABLE = "VOITTA_MAX_SEQ_LENGTH"
+
+
+def seq_cap() -> int:
+    """The longest sequence a model may run: the VOITTA_MAX_SEQ_LENGTH setting, MAX_SEQ when it is unset."""
+    return get_settings().max_seq_length
+
+
+# vr_query_text(_batch) take a max_len of at most this (a question is not a document)
+TEXT_PATH_MAX_LEN = 4096
+
+
+def one_call_text_paths(model) -> bool:
+    """Whether questions for `model` go through vr_query_text(_batch): a tokenizer of the engine, and a sequence cap those
+    calls accept. Otherwise they are tokenised, encoded and searched in calls of their own, with the same result."""
+    return native_tokenizer(model.tokenizer) and model.max_seq_length <= TEXT_PATH_MAX_LEN
 
 
 def native_tokenizer(tok) -> bool:
@@ -39,7 +55,7 @@ def read_encoder_config(path: str) -> dict:
     description and how to load it: {"desc": BertDesc, "max_seq": int, "pos_start": first position-table row}.
     BERT: max_seq = min(max_seq_length, max_position_embeddings). XLM-RoBERTa (multilingual-e5 and the like): position
     p reads row pad_token_id + 1 + p, so the table is used from that row on (max_pos = max_position_embeddings -
-    pad_token_id - 1); one token type; max_seq = min(max_seq_length, max_pos), refused above 512."""
+    pad_token_id - 1); one token type; max_seq = min(max_seq_length, max_pos), refused above seq_cap()."""
     cfg = json.load(open(os.path.join(path, "config.json")))
     kind = cfg.get("model_type", "bert")
     if kind == "nomic_bert":
@@ -52,9 +68,11 @@ def read_encoder_config(path: str) -> dict:
     max_pos = int(cfg["max_position_embeddings"]) - pos_start
     pooling, normalize, max_seq = _read_modules(path, max_pos)
     max_seq = min(max_seq, max_pos)
-    if kind == "xlm-roberta" and max_seq > MAX_SEQ:
-        raise ValueError(f"{path} uses sequences of up to {max_seq} tokens; the engine runs at most {MAX_SEQ}: set "
-                         f"max_seq_length <= {MAX_SEQ} in its sentence_bert_config.json")
+    cap = seq_cap()
+    if kind == "xlm-roberta" and max_seq > cap:
+        raise ValueError(f"{path} uses sequences of up to {max_seq} tokens; the engine runs at most {cap}: set "
+                         f"max_seq_length <= {cap} in its sentence_bert_config.json, or raise {SEQ_CAP_VARIABLE} "
+                         f"(up to {MAX_SEQ_LENGTH_LIMIT})")
     desc = _enc.BertDesc(layers=cfg["num_hidden_layers"], hidden=cfg["hidden_size"],
                          heads=cfg["num_attention_heads"], intermediate=cfg["intermediate_size"],
                          vocab=cfg["vocab_size"], max_pos=max_pos,
@@ -91,7 +109,7 @@ def _read_modules(path: str, max_seq: int):
 def _read_rope_config(path: str, cfg: dict) -> dict:
     """model_type nomic_bert in the native transformers layout (NomicBertConfig's keys): a post-LayerNorm BERT with
     rotary positions over the whole head (rotate-half pairing) and a gated FFN without biases. Sequences are capped at
-    MAX_SEQ (these checkpoints declare 2048-8192): truncation is well defined without a learned table."""
+    seq_cap() (these checkpoints declare 2048-8192): truncation is well defined without a learned table."""
     if "hidden_size" not in cfg:
         raise ValueError(f"{path}: model_type nomic_bert without 'hidden_size' — the hub checkpoint's older config "
                          "spelling (n_embd, n_head, rotary_emb_base, ...) is not read; re-save the config in the "
@@ -115,10 +133,12 @@ def _read_rope_config(path: str, cfg: dict) -> dict:
     declared = int(cfg.get("max_position_embeddings", 2048))
     pooling, normalize, max_seq = _read_modules(path, declared)
     max_seq = min(max_seq, declared)
-    if max_seq > MAX_SEQ:
+    cap = seq_cap()
+    if max_seq > cap:
         logger.warning("%s declares sequences of up to %d tokens; the engine runs at most %d: longer texts are "
-                       "truncated to %d tokens", path, max_seq, MAX_SEQ, MAX_SEQ)
-        max_seq = MAX_SEQ
+                       "truncated to %d tokens (%s raises the cap, up to %d)", path, max_seq, cap, cap, SEQ_CAP_VARIABLE,
+                       MAX_SEQ_LENGTH_LIMIT)
+        max_seq = cap
     desc = _enc.BertDesc(layers=cfg["num_hidden_layers"], hidden=H, heads=heads, intermediate=cfg["intermediate_size"],
                          vocab=cfg["vocab_size"], max_pos=max_seq,  # rotary: the length of the cos/sin table
                          type_vocab=cfg.get("type_vocab_size", 2), pooling=pooling, normalize=normalize,
@@ -318,7 +338,7 @@ class EmbeddingService:
         question = query
         query = self._query(query)
         model = self.model
-        if _deferred.enabled() and native_tokenizer(model.tokenizer):
+        if _deferred.enabled() and one_call_text_paths(model):
             out = _deferred.QueryRef(model, query)  # encoded when looked at — or inside the search call it goes to
         else:
             out = _deferred.QueryEmbedding(model.encode(query, convert_to_numpy=True))

@@ -15,7 +15,8 @@ import threading
 import numpy as np
 
 from . import encoder as _enc
-from .embedding import MAX_SEQ, NativeSentenceEncoder, slice_positions
+from .config import MAX_SEQ_LENGTH_LIMIT
+from .embedding import SEQ_CAP_VARIABLE, NativeSentenceEncoder, seq_cap, slice_positions
 from .store_registry import get_engine
 from .unigram import UnigramTokenizer
 from .wordpiece import WordPieceTokenizer
@@ -90,9 +91,11 @@ class NativeCrossEncoder:
                 ml = json.load(open(tc)).get("model_max_length")
                 if isinstance(ml, int) and ml > 0:
                     max_length = min(max_length, ml)
-        if xlmr and min(int(max_length), max_pos) > MAX_SEQ:
+        cap = seq_cap()
+        if xlmr and min(int(max_length), max_pos) > cap:
             raise ValueError(f"reranker {path} reads pairs of up to {min(int(max_length), max_pos)} tokens; the engine "
-                             f"runs at most {MAX_SEQ}: pass max_length <= {MAX_SEQ}")
+                             f"runs at most {cap}: pass max_length <= {cap}, or raise {SEQ_CAP_VARIABLE} (up to "
+                             f"{MAX_SEQ_LENGTH_LIMIT})")
         state = NativeSentenceEncoder._load_weights(path)
         if not xlmr:
             return cls(engine or get_engine(), desc, state, WordPieceTokenizer.from_pretrained(path, max_length),

@@ -1204,7 +1204,7 @@ class VectorStoreService:
         return self._search_questions_first_stage(requests)
 
     def _search_questions_first_stage(self, requests: list[dict]) -> list[list[StoredChunk]]:
-        from .embedding import get_embedding_service, native_tokenizer
+        from .embedding import get_embedding_service, one_call_text_paths
 
         n = len(requests)
         out: list[list[StoredChunk]] = [[] for _ in range(n)]
@@ -1214,7 +1214,7 @@ class VectorStoreService:
         emb = get_embedding_service()
         model = emb.model
         queries = [requests[i]["query"] for i in live]
-        if not (native_tokenizer(model.tokenizer) and model.engine is self._engine
+        if not (one_call_text_paths(model) and model.engine is self._engine
                 and int(model.desc.hidden) == self.dimension):
             # (an encoder outside this engine: the two services, then search_requests — the definition of the answer)
             from .sparse_embedding import _query_vector
