@@ -236,6 +236,49 @@ def test_class_slices_give_the_same_answer(small, tmp_path, n_cls):
     assert np.array_equal(z["dr"], dr) and np.array_equal(z["ds"], ds) and np.array_equal(z["dc"], dc)
 
 
+def test_filtered_batch_overflow_is_redone_by_class(gpu):
+    """A query of a FILTERED batch over its dense candidate budget: the batched scan gives it up and the class loop
+    redoes it on the byte mask of its class. The corpus of test_batched_search_overflow_falls_back_per_query (6,000
+    near-duplicates of row 0) with folder = row % 3: each folder holds 2,000 of them, so a query on the cluster exceeds
+    the budget of 1,024 under every filter here, whether or not the scan counts the rows its filter removes."""
+    from voitta_rag_amd import Engine, SearchFilter
+    from voitta_rag_amd.engine import VR_FUSION_MINMAX
+
+    dim, n, nq, k = 256, 20000, 42, 10
+    rng = np.random.default_rng(77)
+    x = rng.standard_normal((n, dim)).astype(np.float32)
+    x[:6000] = x[0] + 2e-4 * rng.standard_normal((6000, dim)).astype(np.float32)
+    folder = (np.arange(n) % 3).astype(np.int32)
+    filters = [None, SearchFilter(include_folders=[0, 1]), SearchFilter(exclude_folders=[0])]
+    masks = [np.ones(n, np.uint8), (folder != 2).astype(np.uint8), (folder != 0).astype(np.uint8)]
+    q = rng.standard_normal((nq, dim)).astype(np.float32)
+    q[3:6] = x[0]
+    q[6:9] = x[17] + 0.01 * rng.standard_normal((3, dim)).astype(np.float32)
+    flt = [filters[i % 3] for i in range(nq)]
+    want = ocore.dense_scores(ocore.cosine_preprocess(q), ocore.cosine_preprocess(x))
+    e = Engine(dim, initial_rows=n)
+    try:
+        e.upsert(x, folder_ids=folder)
+        before = e.stats()
+        got = e.search_dense_multi(q, k, flt)
+        after = e.stats()
+        print("batch_fallback:", after["batch_fallback"] - before["batch_fallback"])
+        assert after["batched"] - before["batched"] == nq
+        assert after["batch_fallback"] - before["batch_fallback"] >= 1
+        for i in range(nq):
+            wr, ws = ocore.topk(want[i], k, masks[i % 3])
+            assert np.array_equal(got[i][0], wr) and np.array_equal(got[i][1].view(np.uint32), ws.view(np.uint32)), i
+            r1, s1 = e.search_dense(q[i:i + 1], k, flt[i])[0]
+            assert np.array_equal(got[i][0], r1) and np.array_equal(got[i][1].view(np.uint32), s1.view(np.uint32)), i
+        # the same batch as hybrid queries without sparse terms: limits 3, so k = 9 per leg
+        none = (np.zeros(0, np.int32), np.zeros(0, np.float32))
+        fused = e.search_hybrid_batch_multi(q, [none] * nq, [3] * nq, [0.1] * nq, flt, fusion=VR_FUSION_MINMAX)
+        for i in range(nq):
+            assert _same(fused[i], e.search_hybrid(q[i], none[0], none[1], 3, 0.1, fusion=VR_FUSION_MINMAX, flt=flt[i])), i
+    finally:
+        e.close()
+
+
 def test_search_requests_equals_search_per_request(monkeypatch, gpu):
     """VectorStoreService with string folders and dates: result i of search_requests is search(**requests[i])."""
     from voitta_rag_amd import config, store_registry, vector_store

@@ -503,7 +503,7 @@ inline T* pin_dev(vr_engine* e, size_t off) {
   return reinterpret_cast<T*>(static_cast<char*>(e->pinned_dev) + off);
 }
 
-// ---- api.hip
+// ---- api.hip (what search.hip shares — check_engine, SearchLane, decode_keys, the argument checks — is in search.h)
 int ensure_rows(vr_engine* e, int64_t need);  // grow every per-row table to hold `need` rows
 
 // ---- persist.hip: on-disk image of the index (vr_save / vr_load)
