@@ -24,7 +24,7 @@
  *   - thread-safety: one engine may be called from any number of threads. Searches run CONCURRENTLY, each on
  *     its own HIP stream with its own staging area ("lanes", VR_SEARCH_LANES of them, default 4; further
  *     searches wait for a free one), and hold a shared lock on the index for their duration. Mutations
- *     (vr_upsert, vr_index_batch, vr_delete_rows, vr_compact, vr_load) and vr_encode are serialised among
+ *     (vr_upsert, vr_index_batch(_spans), vr_delete_rows, vr_compact, vr_load) and vr_encode(_spans) are serialised among
  *     themselves and take the exclusive lock only to PUBLISH: the append of a batch, the tombstones of a
  *     delete, the pointer swap of a compaction (which builds its result beside the live index). A search
  *     therefore sees the state before or after a mutation, never a mixture, and waits for no encode and
@@ -184,6 +184,21 @@ int vr_encoder_load(vr_engine* e, const vr_bert_desc* desc, const void* const* t
 int vr_encode(vr_engine* e, const int32_t* ids, const int32_t* offsets, int32_t n_seq, int mem,
               float* out, int out_mem);
 
+/* vr_encode with one output row per token SPAN instead of per sequence (late chunking: a document goes through the
+ * encoder once and each of its chunks is pooled from its own tokens' final hidden states).
+ *   span_off  n_seq + 1 int32, starts at 0, never decreases: sequence i owns spans span_off[i] .. span_off[i+1]
+ *             (possibly none: such a sequence only provides context)
+ *   span_tok  2 int32 per span, (begin, end): token positions inside the span's own sequence,
+ *             0 <= begin < end <= len. Spans of a sequence may overlap, repeat and come in any order.
+ * ids / offsets / span_off / span_tok in `mem`. out: span_off[n_seq] x H f32 in `out_mem`; row s is the mean over
+ * t in [begin, end) of the final hidden state of token t, summed in token order, then (desc.normalize) divided by
+ * max(|x|, 1e-12). desc.pooling is ignored: the forward pass runs as a mean-pooled model's does, so one span [0, len)
+ * on a mean-pooled model gives vr_encode's row bit for bit. Host arrays are checked before any work is queued;
+ * vr_last_error names the offending sequence and span. No spans, or n_seq <= 0: returns 0 and writes nothing. */
+int vr_encode_spans(vr_engine* e, const int32_t* ids, const int32_t* offsets, int32_t n_seq,
+                    const int32_t* span_off, const int32_t* span_tok, int mem,
+                    float* out, int out_mem);
+
 /* Host-only WordPiece tokenizer (no engine, no GPU): the tokenise step of SentenceTransformer.encode
  * (embedding.py:40,68-73 -> [EXT] HF tokenizers: BertNormalizer, BertPreTokenizer, WordPiece,
  * "[CLS] $A [SEP]", right truncation — SURVEY.md §8 a4 step 2), producing the ids / offsets vr_encode
@@ -312,6 +327,18 @@ int vr_index_batch(vr_engine* e, int64_t n, int mem,
                    const int32_t* folder_id, const int32_t* index_folder_id,
                    const int64_t* created, const int64_t* modified,
                    int64_t* out_first_row);
+
+/* vr_index_batch for rows that are spans (vr_encode_spans) of n_seq sequences: n must equal span_off[n_seq]; row r gets
+ * the dense vector of span r, the BM25 vector of bm_ids / bm_off entry r (n entries, per chunk as above) and payload
+ * entry r. */
+int vr_index_batch_spans(vr_engine* e, int64_t n, int mem,
+                         const int32_t* wp_ids, const int32_t* wp_off, int32_t n_seq,
+                         const int32_t* span_off, const int32_t* span_tok,
+                         const int32_t* bm_ids, const int64_t* bm_off,
+                         double k, double b, double avg_len,
+                         const int32_t* folder_id, const int32_t* index_folder_id,
+                         const int64_t* created, const int64_t* modified,
+                         int64_t* out_first_row);
 
 /* ---- index: replaces VectorStoreService.store_chunks' client.upsert (vector_store.py:291-313)
  * and the Qdrant-side cosine normalisation on insert (SURVEY.md a10 [EXT]). ------------------- */

@@ -98,6 +98,7 @@ SIGNATURES = {
     "vr_set_stream": (C.c_int, [_vp, _vp]),
     "vr_encoder_load": (C.c_int, [_vp, C.POINTER(VrBertDesc), C.POINTER(_vp), C.c_int32, C.c_int]),
     "vr_encode": (C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_int, _vp, C.c_int]),
+    "vr_encode_spans": (C.c_int, [_vp, _vp, _vp, C.c_int32, _vp, _vp, C.c_int, _vp, C.c_int]),
     "vr_wordpiece_create": (C.c_int, [C.POINTER(C.c_char_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                      C.POINTER(_vp)]),
     "vr_wordpiece_destroy": (None, [_vp]),
@@ -123,6 +124,8 @@ SIGNATURES = {
     "vr_porter2_stem": (C.c_int, [C.c_char_p, C.c_int64, C.c_char_p, C.c_int64]),
     "vr_index_batch": (C.c_int, [_vp, C.c_int64, C.c_int, _vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_double,
                                  _i32p, _i32p, _i64p, _i64p, _i64p]),
+    "vr_index_batch_spans": (C.c_int, [_vp, C.c_int64, C.c_int, _vp, _vp, C.c_int32, _vp, _vp, _vp, _vp, C.c_double,
+                                       C.c_double, C.c_double, _i32p, _i32p, _i64p, _i64p, _i64p]),
     "vr_upsert": (C.c_int, [_vp, C.c_int64, C.c_int, _vp, _vp, _vp, _vp, _i32p, _i32p, _i64p, _i64p, _i64p]),
     "vr_delete_rows": (C.c_int, [_vp, _i64p, C.c_int64]),
     "vr_stats": (C.c_int, [_vp, C.c_int32, _i64p]),

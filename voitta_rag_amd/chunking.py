@@ -3,7 +3,8 @@ in front of the indexing path (services/indexing.py:380,515; SURVEY.md §8 row f
 ``Chunk`` fields, same constructor defaults (``x or settings.x``, so 0 falls back to the setting just
 as it does there). The splitting runs in the native library (vr_chunk_texts, csrc/chunking.cpp), one
 document per host thread; ``chunk_texts`` is the batched form the indexer uses to cut a whole folder
-at once. Parity unpinned: see csrc/chunking.cpp."""
+at once. Parity unpinned: see csrc/chunking.cpp. With VOITTA_LATE_CHUNKING=1 the chunk texts are
+``LateChunkText``: plain strings that also carry their document, which is how ``embed_texts`` finds it."""
 from __future__ import annotations
 
 import ctypes as C
@@ -11,6 +12,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
+from . import late_chunking as _late
 from ._lib import check, load_library
 from .config import get_settings
 
@@ -69,9 +71,12 @@ class ChunkingService:
         else:
             texts_out = [data[offs[i]:offs[i + 1]].decode("utf-8", "surrogatepass") for i in range(m)]
         out: list[list[Chunk]] = []
+        # late chunking (VOITTA_LATE_CHUNKING=1): a chunk text also knows its document, for embed_texts
+        late = get_settings().late_chunking
         for d in range(n):
             lo, hi = int(docs[d]), int(docs[d + 1])
-            out.append([Chunk(texts_out[i], i - lo, spans[2 * i], spans[2 * i + 1]) for i in range(lo, hi)])
+            own = _late.wrap_chunks(texts[d] or "", texts_out[lo:hi]) if late else texts_out[lo:hi]
+            out.append([Chunk(own[i - lo], i - lo, spans[2 * i], spans[2 * i + 1]) for i in range(lo, hi)])
         return out
 
 

@@ -10,6 +10,7 @@ from functools import lru_cache
 
 DEFAULT_MAX_SEQ_LENGTH = 512
 MAX_SEQ_LENGTH_LIMIT = 8192  # the longest sequence the engine loads a model for (vr_encoder_load / vr_reranker_load)
+DEFAULT_LATE_CHUNKING_CONTEXT = 256
 
 
 class Settings:
@@ -47,6 +48,19 @@ class Settings:
         if not 1 <= self.max_seq_length <= MAX_SEQ_LENGTH_LIMIT:
             raise ValueError(f"VOITTA_MAX_SEQ_LENGTH={self.max_seq_length}: accepted values are 1 ... "
                              f"{MAX_SEQ_LENGTH_LIMIT} (default {DEFAULT_MAX_SEQ_LENGTH})")
+        # late chunking (opt-in): a document goes through the encoder once, in windows of the model's max_seq_length,
+        # and each stored chunk's dense vector is the mean of its own tokens' final hidden states. A follow-on window
+        # of a document longer than the window starts this many tokens before its first chunk (left context)
+        late = os.getenv("VOITTA_LATE_CHUNKING", "0").strip() or "0"
+        if late not in ("0", "1"):
+            raise ValueError(f"VOITTA_LATE_CHUNKING={late}: accepted values are 0 and 1 (default 0)")
+        self.late_chunking: bool = late == "1"
+        self.late_chunking_context: int = int(os.getenv("VOITTA_LATE_CHUNKING_CONTEXT",
+                                                        str(min(DEFAULT_LATE_CHUNKING_CONTEXT, self.max_seq_length // 2))))
+        if not 0 <= self.late_chunking_context <= self.max_seq_length // 2:
+            raise ValueError(f"VOITTA_LATE_CHUNKING_CONTEXT={self.late_chunking_context}: accepted values are 0 ... "
+                             f"{self.max_seq_length // 2} (half of VOITTA_MAX_SEQ_LENGTH={self.max_seq_length}; default "
+                             f"{DEFAULT_LATE_CHUNKING_CONTEXT})")
 
 
 @lru_cache

@@ -184,6 +184,19 @@ int vr_encode(vr_engine* e, const int32_t* ids, const int32_t* offsets, int32_t 
   return encoder_encode(e, ids, offsets, n_seq, mem, out, out_mem);
 }
 
+int vr_encode_spans(vr_engine* e, const int32_t* ids, const int32_t* offsets, int32_t n_seq, const int32_t* span_off,
+                    const int32_t* span_tok, int mem, float* out, int out_mem) {
+  VR_TRY(check_engine(e));
+  if (n_seq <= 0) return 0;
+  VR_CHECK(ids && offsets && span_off, "bad arguments");
+  VR_CHECK((mem == VR_MEM_HOST || mem == VR_MEM_DEVICE) && (out_mem == VR_MEM_HOST || out_mem == VR_MEM_DEVICE),
+           "bad mem");
+  if (mem == VR_MEM_HOST) VR_CHECK(span_off[n_seq] <= 0 || (span_tok && out), "bad arguments");
+  else VR_CHECK(span_tok && out, "bad arguments");
+  std::lock_guard<std::mutex> writer(e->wmu);
+  return encoder_encode_spans(e, ids, offsets, n_seq, span_off, span_tok, mem, -1, out, out_mem);
+}
+
 int vr_reranker_load(vr_engine* e, const vr_bert_desc* desc, const void* const* tensors, int32_t n_tensors, int mem) {
   VR_TRY(check_engine(e));
   VR_CHECK(desc && tensors, "null argument");
@@ -282,7 +295,7 @@ int vr_rerank_text_unigram(vr_engine* e, const vr_unigram* tokenizer, int32_t n_
 
 }  // extern "C"
 
-// Body of vr_upsert, also the last stage of vr_index_batch. Caller holds e->wmu and the exclusive lock.
+// Body of vr_upsert, also the last stage of index_batch. Caller holds e->wmu and the exclusive lock.
 // sp_cnt_dev (device memory, mem == VR_MEM_DEVICE only): when given, the sparse rows are in the
 // padded layout bm25_tf_kernel writes — row r = idx/val[sp_off[r] .. sp_off[r] + sp_cnt_dev[r]).
 static int upsert_locked(vr_engine* e, int64_t n, int mem, const float* dense, const int64_t* sp_off,
@@ -431,27 +444,12 @@ static int upsert_locked(vr_engine* e, int64_t n, int mem, const float* dense, c
   return 0;
 }
 
-extern "C" {
-
-int vr_upsert(vr_engine* e, int64_t n, int mem, const float* dense, const int64_t* sp_off,
-              const int32_t* sp_idx, const float* sp_val, const int32_t* folder_id,
-              const int32_t* index_folder_id, const int64_t* created, const int64_t* modified,
-              int64_t* out_first_row) {
-  VR_TRY(check_engine(e));
-  VR_CHECK(n >= 0, "negative row count");
-  VR_TRY(check_mem(mem));
-  std::lock_guard<std::mutex> writer(e->wmu);
-  PublishLock publish(e);  // (the append itself: a fraction of a millisecond per thousand rows)
-  return upsert_locked(e, n, mem, dense, sp_off, sp_idx, sp_val, nullptr, folder_id, index_folder_id,
-                       created, modified, out_first_row);
-}
-
-int vr_index_batch(vr_engine* e, int64_t n, int mem, const int32_t* wp_ids, const int32_t* wp_off,
-                   const int32_t* bm_ids, const int64_t* bm_off, double k, double b, double avg_len,
-                   const int32_t* folder_id, const int32_t* index_folder_id, const int64_t* created,
-                   const int64_t* modified, int64_t* out_first_row) {
-  VR_TRY(check_engine(e));
-  VR_CHECK(n >= 0 && (n == 0 || (wp_ids && wp_off)), "bad arguments");
+// Body of vr_index_batch and vr_index_batch_spans: BM25 tf of the n rows, the forward pass of n_seq sequences into n
+// engine-owned dense rows — one per sequence (span_off null, n_seq == n) or one per span — and the append.
+static int index_batch(vr_engine* e, int64_t n, int mem, const int32_t* wp_ids, const int32_t* wp_off, int32_t n_seq,
+                       const int32_t* span_off, const int32_t* span_tok, const int32_t* bm_ids, const int64_t* bm_off,
+                       double k, double b, double avg_len, const int32_t* folder_id, const int32_t* index_folder_id,
+                       const int64_t* created, const int64_t* modified, int64_t* out_first_row) {
   VR_TRY(check_mem(mem));
   VR_CHECK((bm_ids == nullptr) == (bm_off == nullptr), "bm_ids and bm_off go together");
   std::lock_guard<std::mutex> writer(e->wmu);
@@ -492,12 +490,52 @@ int vr_index_batch(vr_engine* e, int64_t n, int mem, const int32_t* wp_ids, cons
   // 2. dense encode into engine-owned rows
   VR_CHECK(encoder_hidden(e) == e->dim, "encoder width %d != store dimension %d", encoder_hidden(e), e->dim);
   VR_TRY(e->enc_out.grow(n * e->dim, 0, e->stream));
-  VR_TRY(encoder_encode(e, wp_ids, wp_off, static_cast<int>(n), mem, e->enc_out.p, VR_MEM_DEVICE));
+  if (span_off)
+    VR_TRY(encoder_encode_spans(e, wp_ids, wp_off, n_seq, span_off, span_tok, mem, n, e->enc_out.p, VR_MEM_DEVICE));
+  else
+    VR_TRY(encoder_encode(e, wp_ids, wp_off, n_seq, mem, e->enc_out.p, VR_MEM_DEVICE));
   // 3. store: the only part searches wait for (they ran beside the encode)
   PublishLock publish(e);
   return upsert_locked(e, n, VR_MEM_DEVICE, e->enc_out.p, bm_off_dev, bm_off ? e->bm_idx.p : nullptr,
                        bm_off ? e->bm_val.p : nullptr, bm_off ? e->bm_cnt.p : nullptr, folder_id,
                        index_folder_id, created, modified, out_first_row);
+}
+
+extern "C" {
+
+int vr_upsert(vr_engine* e, int64_t n, int mem, const float* dense, const int64_t* sp_off,
+              const int32_t* sp_idx, const float* sp_val, const int32_t* folder_id,
+              const int32_t* index_folder_id, const int64_t* created, const int64_t* modified,
+              int64_t* out_first_row) {
+  VR_TRY(check_engine(e));
+  VR_CHECK(n >= 0, "negative row count");
+  VR_TRY(check_mem(mem));
+  std::lock_guard<std::mutex> writer(e->wmu);
+  PublishLock publish(e);  // (the append itself: a fraction of a millisecond per thousand rows)
+  return upsert_locked(e, n, mem, dense, sp_off, sp_idx, sp_val, nullptr, folder_id, index_folder_id,
+                       created, modified, out_first_row);
+}
+
+int vr_index_batch(vr_engine* e, int64_t n, int mem, const int32_t* wp_ids, const int32_t* wp_off,
+                   const int32_t* bm_ids, const int64_t* bm_off, double k, double b, double avg_len,
+                   const int32_t* folder_id, const int32_t* index_folder_id, const int64_t* created,
+                   const int64_t* modified, int64_t* out_first_row) {
+  VR_TRY(check_engine(e));
+  VR_CHECK(n >= 0 && n <= INT32_MAX && (n == 0 || (wp_ids && wp_off)), "bad arguments");
+  return index_batch(e, n, mem, wp_ids, wp_off, static_cast<int32_t>(n), nullptr, nullptr, bm_ids, bm_off, k, b, avg_len,
+                     folder_id, index_folder_id, created, modified, out_first_row);
+}
+
+int vr_index_batch_spans(vr_engine* e, int64_t n, int mem, const int32_t* wp_ids, const int32_t* wp_off, int32_t n_seq,
+                         const int32_t* span_off, const int32_t* span_tok, const int32_t* bm_ids, const int64_t* bm_off,
+                         double k, double b, double avg_len, const int32_t* folder_id, const int32_t* index_folder_id,
+                         const int64_t* created, const int64_t* modified, int64_t* out_first_row) {
+  VR_TRY(check_engine(e));
+  VR_CHECK(n >= 0 && n_seq >= 0 && span_off && (n == 0 || (n_seq > 0 && wp_ids && wp_off && span_tok)), "bad arguments");
+  if (mem == VR_MEM_HOST)  // (device arrays: checked with the other span conditions, after the copy)
+    VR_CHECK(span_off[n_seq] == n, "%lld rows announced, span_off holds %d spans", static_cast<long long>(n), span_off[n_seq]);
+  return index_batch(e, n, mem, wp_ids, wp_off, n_seq, span_off, span_tok, bm_ids, bm_off, k, b, avg_len, folder_id,
+                     index_folder_id, created, modified, out_first_row);
 }
 
 int vr_delete_rows(vr_engine* e, const int64_t* rows, int64_t n) {

@@ -77,6 +77,10 @@ struct Encoder {
   float* posidx = nullptr;  // rotary: int32 position of every token inside its own sequence (positions_kernel)
   bool fuse = true;         // rotate / gate inside the skinny epilogues; VR_ENCODE_FUSE=0 at load time: separate passes
   DevArray<int32_t> ids, cu, seg;
+  // a span call (encoder_encode_spans): the caller's (begin, end) pairs when they come from the host, and every span's
+  // sequence index (built on the host from span_off; its host copy lives here until the upload has run)
+  DevArray<int32_t> span_tok, span_seq;
+  std::vector<int32_t> span_seq_host;
   DevArray<float> out;
   // a cross-encoder (the reranker slot): pooler dense [H,H] + bias, classifier [1,H] + bias; the pooled [CLS] rows
   float *pool_w = nullptr, *pool_b = nullptr, *cls_w = nullptr, *cls_b = nullptr;
@@ -84,11 +88,16 @@ struct Encoder {
   DevArray<float> skinny_ws;  // K-slice partial sums of gemm_f16_skinny_kernel
   // hipGraphs of small forward passes (a query, a handful of sequences): ~135 launches of a few
   // microseconds of work each are launch-bound; replayed as one graph they are not
+  // (a span call: its span buffers and span count as well — a whole-sequence call has null and 0 there. The span
+  // VALUES are not part of the key: they are copied into the buffers before every launch, as the ids are.)
   struct GraphKey {
     int T, n_seq, max_len;
     const void *ids, *cu, *seg, *out;
+    const void *span_tok = nullptr, *span_seq = nullptr;
+    int n_spans = 0;
     bool operator<(const GraphKey& o) const {
-      return std::tie(T, n_seq, max_len, ids, cu, seg, out) < std::tie(o.T, o.n_seq, o.max_len, o.ids, o.cu, o.seg, o.out);
+      return std::tie(T, n_seq, max_len, ids, cu, seg, out, span_tok, span_seq, n_spans) <
+             std::tie(o.T, o.n_seq, o.max_len, o.ids, o.cu, o.seg, o.out, o.span_tok, o.span_seq, o.n_spans);
     }
   };
   struct GraphEntry {
@@ -469,6 +478,44 @@ __global__ __launch_bounds__(256) void pool_kernel(const float* __restrict__ x,
   for (int j = 0; j < 4; ++j) {
     int c = threadIdx.x + 256 * j;
     if (c < H) out[static_cast<int64_t>(seq) * H + c] = vals[j] / den;
+  }
+}
+
+// one block per span: the mean of the final hidden rows [begin, end) of the span's own sequence, summed in token order,
+// then x / max(|x|, 1e-12) — pool_kernel's mean arithmetic over a token range, so a span [0, len) gives pool_kernel's
+// bits. Block b serves span span0 + b; span_seq holds each span's sequence (no search here), span_tok its (begin, end).
+__global__ __launch_bounds__(256) void span_pool_kernel(const float* __restrict__ x, const int32_t* __restrict__ cu,
+                                                        const int32_t* __restrict__ span_tok,
+                                                        const int32_t* __restrict__ span_seq, int span0, int tok_base,
+                                                        int H, int normalize, float* __restrict__ out) {
+  __shared__ float red[4];
+  const int sp = span0 + blockIdx.x;
+  const int begin = span_tok[2 * sp];
+  const int len = span_tok[2 * sp + 1] - begin;
+  const int t0 = cu[span_seq[sp]] - tok_base + begin;
+  float vals[4];
+  float ss = 0.0f;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    int c = threadIdx.x + 256 * j;
+    float v = 0.0f;
+    if (c < H && len > 0) {
+      float acc = 0.0f;
+      for (int t = 0; t < len; ++t) acc += x[static_cast<int64_t>(t0 + t) * H + c];
+      v = acc / fmaxf(static_cast<float>(len), 1e-9f);
+    }
+    vals[j] = v;
+    ss += v * v;
+  }
+  ss = wave_sum(ss);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ss;
+  __syncthreads();
+  const float norm = sqrtf(red[0] + red[1] + red[2] + red[3]);
+  const float den = normalize ? fmaxf(norm, 1e-12f) : 1.0f;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    int c = threadIdx.x + 256 * j;
+    if (c < H) out[static_cast<int64_t>(sp) * H + c] = vals[j] / den;
   }
 }
 
@@ -3573,6 +3620,8 @@ static void free_encoder(void** slot) {
   enc->ids.release();
   enc->cu.release();
   enc->seg.release();
+  enc->span_tok.release();
+  enc->span_seq.release();
   enc->skinny_ws.release();
   invalidate_graphs(enc);
   enc->out.release();
@@ -3833,10 +3882,20 @@ static int ensure_workspace(vr_engine* e, Encoder* enc, int64_t tokens) {
   return 0;
 }
 
-// forward of sequences [seq0, seq1) whose tokens are ids_dev[tok_base .. tok_base + T)
+// The checked spans of a span call: span_off on the host (forward_all cuts the span range of a forward chunk from it),
+// the (begin, end) pairs and the sequence index of every span on the device.
+struct Spans {
+  std::vector<int32_t> off;
+  const int32_t* tok_dev = nullptr;
+  const int32_t* seq_dev = nullptr;
+};
+
+// forward of sequences [seq0, seq1) whose tokens are ids_dev[tok_base .. tok_base + T). sp (or null): pool the spans
+// of these sequences, one row each at out_dev[span], instead of one row per sequence — the pass then runs as a
+// mean-pooled model's does, whatever the description's pooling says.
 static int forward_chunk(vr_engine* e, Encoder* enc, const int32_t* ids_dev, const int32_t* cu_dev,
                          const int32_t* seg_dev, int n_seq_total, int seq0, int seq1, int tok_base, int T, int max_len,
-                         double attn_flop, float* out_dev) {
+                         double attn_flop, float* out_dev, const Spans* sp = nullptr) {
   const vr_bert_desc& d = enc->d;
   const int H = d.hidden, I = d.intermediate, nh = d.heads, dh = H / nh;
   hipStream_t s = e->stream;
@@ -3946,7 +4005,7 @@ static int forward_chunk(vr_engine* e, Encoder* enc, const int32_t* ids_dev, con
   // bge-base this removes 10/12 of the last layer's GEMM work. The Q projection of the other
   // tokens is still computed (it is one GEMM with K and V).
   const int n_seq = seq1 - seq0;
-  const bool cls_tail = d.pooling == VR_POOL_CLS && !enc->layers.empty() &&
+  const bool cls_tail = !sp && d.pooling == VR_POOL_CLS && !enc->layers.empty() &&
                         static_cast<int64_t>(n_seq) * (4 * H + I) <= static_cast<int64_t>(T) * 3 * H;
   // The [rows, 2I] pre-activation workspace exists only once a pass really stores one: an unfused FFN-up over the T
   // rows, or over the CLS tail's n_seq rows. (Never during a graph capture: a shape runs eagerly first, and a
@@ -4209,8 +4268,15 @@ static int forward_chunk(vr_engine* e, Encoder* enc, const int32_t* ids_dev, con
     hipLaunchKernelGGL(layernorm_kernel, dim3(row_blocks), dim3(256), 0, s, enc->tmp, T, H, w.ln2g, w.ln2b,
                        d.eps, enc->x, xh, xl, static_cast<float2*>(nullptr));
   }
-  hipLaunchKernelGGL(pool_kernel, dim3(static_cast<unsigned>(seq1 - seq0)), dim3(256), 0, s, final_x, cu_dev,
-                     seq0, tok_base, H, d.pooling, d.normalize, 0, out_dev);
+  if (sp) {
+    const int span0 = sp->off[static_cast<size_t>(seq0)], n_spans = sp->off[static_cast<size_t>(seq1)] - span0;
+    if (n_spans > 0)
+      hipLaunchKernelGGL(span_pool_kernel, dim3(static_cast<unsigned>(n_spans)), dim3(256), 0, s, final_x, cu_dev,
+                         sp->tok_dev, sp->seq_dev, span0, tok_base, H, d.normalize, out_dev);
+  } else {
+    hipLaunchKernelGGL(pool_kernel, dim3(static_cast<unsigned>(seq1 - seq0)), dim3(256), 0, s, final_x, cu_dev,
+                       seq0, tok_base, H, d.pooling, d.normalize, 0, out_dev);
+  }
   VR_HIP(hipGetLastError());
   return 0;
 }
@@ -4222,17 +4288,24 @@ static int forward_chunk(vr_engine* e, Encoder* enc, const int32_t* ids_dev, con
 static const int64_t kMaxChunkTokens = getenv("VR_CHUNK_TOKENS") ? atoll(getenv("VR_CHUNK_TOKENS")) : 262144;
 
 // The host copy of the offsets (needed to cut chunks), every length and segment start checked: before any work
-// is queued when the arguments are in host memory
+// is queued when the arguments are in host memory. span_off (or null, n_seq + 1 entries in `mem`) is copied with them
+// into *span_off_host; read_spans checks it.
 static int read_offsets(vr_engine* e, Encoder* enc, const int32_t* offsets, const int32_t* seg_b, int n_seq, int mem,
-                        std::vector<int32_t>* cu_host) {
+                        std::vector<int32_t>* cu_host, const int32_t* span_off = nullptr,
+                        std::vector<int32_t>* span_off_host = nullptr) {
   cu_host->resize(static_cast<size_t>(n_seq) + 1);
   std::vector<int32_t> seg_host(seg_b ? static_cast<size_t>(n_seq) : 0);
+  if (span_off) span_off_host->resize(cu_host->size());
   if (mem == VR_MEM_HOST) {
     memcpy(cu_host->data(), offsets, sizeof(int32_t) * cu_host->size());
     if (seg_b) memcpy(seg_host.data(), seg_b, sizeof(int32_t) * seg_host.size());
+    if (span_off) memcpy(span_off_host->data(), span_off, sizeof(int32_t) * cu_host->size());
   } else {
     VR_HIP(hipMemcpyAsync(cu_host->data(), offsets, sizeof(int32_t) * cu_host->size(), hipMemcpyDeviceToHost,
                           e->stream));
+    if (span_off)
+      VR_HIP(hipMemcpyAsync(span_off_host->data(), span_off, sizeof(int32_t) * cu_host->size(), hipMemcpyDeviceToHost,
+                            e->stream));
     if (seg_b)
       VR_HIP(hipMemcpyAsync(seg_host.data(), seg_b, sizeof(int32_t) * seg_host.size(), hipMemcpyDeviceToHost, e->stream));
     VR_HIP(hipStreamSynchronize(e->stream));
@@ -4249,9 +4322,10 @@ static int read_offsets(vr_engine* e, Encoder* enc, const int32_t* offsets, cons
 }
 
 // The forward pass of n_seq checked sequences (cu_host: their offsets), one pooled row each into out_dev (device).
-// seg_b (or null): each sequence's first segment-B position.
+// seg_b (or null): each sequence's first segment-B position. sp (or null): one row per span instead, see forward_chunk.
 static int forward_all(vr_engine* e, Encoder* enc, const int32_t* ids, const int32_t* offsets, const int32_t* seg_b,
-                       int n_seq, int mem, const std::vector<int32_t>& cu_host, float* out_dev) {
+                       int n_seq, int mem, const std::vector<int32_t>& cu_host, float* out_dev,
+                       const Spans* sp = nullptr) {
   const int H = enc->d.hidden;
   const int64_t T_all = cu_host[static_cast<size_t>(n_seq)];
   const int32_t* ids_dev = ids;
@@ -4298,11 +4372,13 @@ static int forward_all(vr_engine* e, Encoder* enc, const int32_t* ids, const int
     if (graphable) {
       if (enc->graphs.size() > 256) invalidate_graphs(enc);  // (shapes are few in practice; start over rather than track recency)
       Encoder::GraphEntry& g =
-          enc->graphs[Encoder::GraphKey{static_cast<int>(T), n_seq, max_len, ids_dev, cu_dev, seg_dev, out_dev}];
+          enc->graphs[Encoder::GraphKey{static_cast<int>(T), n_seq, max_len, ids_dev, cu_dev, seg_dev, out_dev,
+                                        sp ? sp->tok_dev : nullptr, sp ? sp->seq_dev : nullptr,
+                                        sp ? sp->off[static_cast<size_t>(n_seq)] : 0}];
       if (!g.exec && !g.bad && g.seen >= 1) {
         if (hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
           const int rc = forward_chunk(e, enc, ids_dev, cu_dev, seg_dev, n_seq, seq0, seq1, 0, static_cast<int>(T),
-                                       max_len, 4.0 * H * len2, out_dev);
+                                       max_len, 4.0 * H * len2, out_dev, sp);
           hipGraph_t graph = nullptr;
           const hipError_t end = hipStreamEndCapture(e->stream, &graph);
           if (rc != 0 || end != hipSuccess || !graph ||
@@ -4325,7 +4401,7 @@ static int forward_all(vr_engine* e, Encoder* enc, const int32_t* ids, const int
     }
     if (!done)
       VR_TRY(forward_chunk(e, enc, ids_dev, cu_dev, seg_dev, n_seq, seq0, seq1, cu_host[static_cast<size_t>(seq0)],
-                           static_cast<int>(T), max_len, 4.0 * H * len2, out_dev));
+                           static_cast<int>(T), max_len, 4.0 * H * len2, out_dev, sp));
     seq0 = seq1;
   }
   return 0;
@@ -4358,6 +4434,77 @@ int encoder_encode(vr_engine* e, const int32_t* ids, const int32_t* offsets, int
   }
   VR_TRY(forward_all(e, enc, ids, offsets, nullptr, n_seq, mem, cu_host, out_dev));
   return finish(e, out, out_dev, static_cast<int64_t>(n_seq) * H, mem, out_mem);
+}
+
+// The spans of a span call, checked against the sequences (cu_host) — span_off monotone from 0 (sp->off holds its host
+// copy already), every span non-empty and inside its sequence — and made ready for span_pool_kernel: sp->tok_dev is
+// the caller's array or its staged copy, sp->seq_dev the sequence index of every span. n_expected >= 0: the span count
+// the caller announced. Nothing is queued before the checks when the arrays are in host memory.
+static int read_spans(vr_engine* e, Encoder* enc, const int32_t* span_tok, int n_seq, int mem,
+                      const std::vector<int32_t>& cu_host, int64_t n_expected, Spans* sp) {
+  VR_CHECK(sp->off[0] == 0, "span_off must start at 0");
+  for (int i = 0; i < n_seq; ++i)
+    VR_CHECK(sp->off[static_cast<size_t>(i) + 1] >= sp->off[static_cast<size_t>(i)],
+             "span_off decreases at sequence %d (%d spans before it, %d after)", i, sp->off[static_cast<size_t>(i)],
+             sp->off[static_cast<size_t>(i) + 1]);
+  const int64_t n_spans = sp->off[static_cast<size_t>(n_seq)];
+  VR_CHECK(n_expected < 0 || n_spans == n_expected, "%lld rows announced, span_off holds %lld spans",
+           static_cast<long long>(n_expected), static_cast<long long>(n_spans));
+  if (n_spans == 0) return 0;
+  VR_CHECK(span_tok != nullptr, "null span_tok");
+  std::vector<int32_t> tok_copy;
+  const int32_t* tok = span_tok;
+  if (mem != VR_MEM_HOST) {
+    tok_copy.resize(static_cast<size_t>(2 * n_spans));
+    VR_HIP(hipMemcpyAsync(tok_copy.data(), span_tok, sizeof(int32_t) * tok_copy.size(), hipMemcpyDeviceToHost, e->stream));
+    VR_HIP(hipStreamSynchronize(e->stream));
+    tok = tok_copy.data();
+  }
+  enc->span_seq_host.resize(static_cast<size_t>(n_spans));
+  for (int i = 0; i < n_seq; ++i) {
+    const int len = cu_host[static_cast<size_t>(i) + 1] - cu_host[static_cast<size_t>(i)];
+    for (int r = sp->off[static_cast<size_t>(i)]; r < sp->off[static_cast<size_t>(i) + 1]; ++r) {
+      const int begin = tok[2 * static_cast<size_t>(r)], end = tok[2 * static_cast<size_t>(r) + 1];
+      VR_CHECK(begin >= 0 && begin < end && end <= len, "sequence %d span %d: [%d, %d) is empty or outside its %d tokens", i,
+               r, begin, end, len);
+      enc->span_seq_host[static_cast<size_t>(r)] = i;
+    }
+  }
+  VR_TRY(enc->span_seq.grow(n_spans, 0, e->stream));
+  VR_HIP(hipMemcpyAsync(enc->span_seq.p, enc->span_seq_host.data(), sizeof(int32_t) * static_cast<size_t>(n_spans),
+                        hipMemcpyHostToDevice, e->stream));
+  sp->seq_dev = enc->span_seq.p;
+  sp->tok_dev = span_tok;
+  if (mem == VR_MEM_HOST) {
+    VR_TRY(enc->span_tok.grow(2 * n_spans, 0, e->stream));
+    VR_HIP(hipMemcpyAsync(enc->span_tok.p, span_tok, sizeof(int32_t) * static_cast<size_t>(2 * n_spans),
+                          hipMemcpyHostToDevice, e->stream));
+    sp->tok_dev = enc->span_tok.p;
+  }
+  return 0;
+}
+
+int encoder_encode_spans(vr_engine* e, const int32_t* ids, const int32_t* offsets, int n_seq, const int32_t* span_off,
+                         const int32_t* span_tok, int mem, int64_t n_expected, float* out, int out_mem) {
+  Encoder* enc = static_cast<Encoder*>(e->encoder);
+  VR_CHECK(enc != nullptr, "no encoder loaded (vr_encoder_load)");
+  if (n_seq <= 0) return 0;
+  const int H = enc->d.hidden;
+  std::vector<int32_t> cu_host;
+  Spans sp;
+  VR_TRY(read_offsets(e, enc, offsets, nullptr, n_seq, mem, &cu_host, span_off, &sp.off));
+  VR_TRY(read_spans(e, enc, span_tok, n_seq, mem, cu_host, n_expected, &sp));
+  const int64_t n_spans = sp.off[static_cast<size_t>(n_seq)];
+  if (n_spans == 0) return 0;
+  float* out_dev = out;
+  if (out_mem == VR_MEM_HOST) {
+    VR_TRY(enc->out.grow(n_spans * H, 0, e->stream));
+    out_dev = enc->out.p;
+  }
+  VR_TRY(forward_all(e, enc, ids, offsets, nullptr, n_seq, mem, cu_host, out_dev, &sp));
+  // (device arrays in and out: drain here, enc->span_seq_host must outlive its upload)
+  if (mem != VR_MEM_HOST && out_mem != VR_MEM_HOST) VR_HIP(hipStreamSynchronize(e->stream));
+  return finish(e, out, out_dev, n_spans * H, mem, out_mem);
 }
 
 int encoder_rerank(vr_engine* e, const int32_t* ids, const int32_t* offsets, const int32_t* seg_b, int n_seq, int mem,

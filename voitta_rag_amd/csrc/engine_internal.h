@@ -608,6 +608,9 @@ int sparse_lookup_df(vr_engine* e, const int32_t* ids_host, int n, int32_t* out_
 int encoder_load(vr_engine* e, const vr_bert_desc* d, const void* const* tensors, int n_tensors, int mem);
 int encoder_encode(vr_engine* e, const int32_t* ids, const int32_t* offsets, int n_seq, int mem,
                    float* out, int out_mem);
+// one row per token span instead of per sequence (vr_encode_spans); n_expected >= 0: the span count the caller announced
+int encoder_encode_spans(vr_engine* e, const int32_t* ids, const int32_t* offsets, int n_seq, const int32_t* span_off,
+                         const int32_t* span_tok, int mem, int64_t n_expected, float* out, int out_mem);
 void encoder_release(vr_engine* e);  // the embedder and the reranker
 int reranker_load(vr_engine* e, const vr_bert_desc* d, const void* const* tensors, int n_tensors, int mem);
 bool reranker_loaded(vr_engine* e);

@@ -17,6 +17,7 @@ import numpy as np
 
 from . import deferred as _deferred
 from . import encoder as _enc
+from . import late_chunking as _late
 from .config import MAX_SEQ_LENGTH_LIMIT, get_settings
 from .store_registry import get_engine
 from .unigram import UnigramTokenizer, is_unigram_pipeline
@@ -175,6 +176,9 @@ class NativeSentenceEncoder:
             self.tokenizer.no_padding()
             self.tokenizer.enable_truncation(max_length=self.max_seq_length)
         _enc.load_encoder(engine, desc, state)
+        if get_settings().late_chunking and desc.pooling == "cls":
+            logger.warning("VOITTA_LATE_CHUNKING=1 with a checkpoint that pools [CLS]: late-chunked vectors are means "
+                           "over a chunk's tokens, which this model was not trained to produce; it runs all the same")
 
     # ---- loading ---------------------------------------------------------------------------------
     @classmethod
@@ -264,6 +268,28 @@ class NativeSentenceEncoder:
         out = _enc.encode(self.engine, ids, off)
         return out[0] if single else out
 
+    # ---- late chunking -----------------------------------------------------------------------------
+    def plan_documents(self, documents, prefix: str = "") -> _late.Plan:
+        """The late-chunking plan (late_chunking.plan_many) of [(document, chunk_texts), ...] for this model: windows of
+        max_seq_length tokens, VOITTA_LATE_CHUNKING_CONTEXT tokens of left context, ``prefix`` (the passage prefix) as
+        ids in front of every window. A document that cannot be late-chunked goes the plain way inside the plan."""
+        return _late.plan_many(documents, self.tokenize, self.max_seq_length, get_settings().late_chunking_context,
+                               _late.prefix_ids_of(prefix, self.tokenize), plain_text=lambda t: prefix + t,
+                               pooling=self.desc.pooling)
+
+    def encode_documents(self, documents, prefix: str = ""):
+        """[(document, chunk_texts), ...] -> (total chunks, D): every chunk embedded in the context of its document,
+        ONE engine call (vr_encode_spans) for all of them."""
+        plan = self.plan_documents(documents, prefix)
+        if plan.n_chunks == 0:
+            return np.zeros((0, self.desc.hidden), np.float32)
+        return _enc.encode_spans(self.engine, plan.ids, plan.offsets, plan.span_off, plan.span_tok)
+
+    def encode_document(self, document: str, chunk_texts, prefix: str = ""):
+        """(n, D): the vectors of one document's chunks, each the mean of its own tokens' final hidden states after
+        the whole document (or its window of it) went through the encoder."""
+        return self.encode_documents([(document, chunk_texts)], prefix)
+
 
 def build_wordpiece_tokenizer(vocab: list[str], lowercase: bool = True):
     """BertTokenizerFast equivalent from a vocab.txt: BertNormalizer + BertPreTokenizer + WordPiece
@@ -322,9 +348,23 @@ class EmbeddingService:
         text = self._passage(text)
         return self.model.encode(text, convert_to_numpy=True).tolist()
 
+    def embed_document(self, document: str, chunk_texts: list[str]) -> list[list[float]]:
+        """The vectors of one document's chunks, late-chunked: see NativeSentenceEncoder.encode_document."""
+        return self.embed_documents([(document, chunk_texts)])
+
+    def embed_documents(self, documents) -> list[list[float]]:
+        """embed_document for [(document, chunk_texts), ...] in one engine call; the rows in chunk order."""
+        return self.model.encode_documents(documents, self._passage("")).tolist()
+
     def embed_texts(self, texts: list[str], batch_size: int = 32) -> list[list[float]]:
         if not texts:
             return []
+        if get_settings().late_chunking:
+            # chunk texts that ChunkingService cut (LateChunkText), whole documents of them in order: embedded in the
+            # context of their documents, plain floats at once (no deferred references in this mode)
+            documents = _late.group_documents(texts)
+            if documents is not None:
+                return self.embed_documents(documents)
         texts = [self._passage(text) for text in texts]
         if _deferred.enabled():
             # tokenised now, encoded when somebody looks at a number — or, when the list goes to store_chunks

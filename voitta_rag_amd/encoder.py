@@ -246,3 +246,38 @@ def encode(engine, ids, offsets, out=None):
     res = np.empty((n, desc.hidden), np.float32)
     check(engine._lib.vr_encode(engine.handle, ip, op_, n, mem, C.c_void_p(res.ctypes.data), VR_MEM_HOST))
     return res
+
+
+def encode_spans(engine, ids, offsets, span_off, span_tok, out=None):
+    """``encode`` with one row per token span (late chunking): span_off (n_seq + 1) gives each sequence's range of
+    spans, span_tok (n_spans, 2) their (begin, end) token positions inside that sequence. All four arrays NumPy int32
+    (host) or torch int32 tensors on the GPU. Returns an (n_spans, H) f32 NumPy array — the mean of each span's final
+    hidden states, normalised as the description says — or fills/returns ``out`` when a device tensor is given."""
+    desc = engine.encoder_desc
+    dev_in = hasattr(ids, "is_cuda") and ids.is_cuda
+    if dev_in:
+        engine._follow(ids)
+        arrays = [ids, offsets, span_off, span_tok.contiguous()]
+        ptrs = [C.c_void_p(a.data_ptr()) for a in arrays]
+        n_spans = int(span_off[-1].item()) if int(span_off.shape[0]) else 0
+        mem = VR_MEM_DEVICE
+    else:
+        arrays = [np.ascontiguousarray(a, dtype=np.int32) for a in (ids, offsets, span_off, span_tok)]
+        ptrs = [C.c_void_p(a.ctypes.data) for a in arrays]
+        n_spans = int(arrays[2][-1]) if arrays[2].shape[0] else 0
+        mem = VR_MEM_HOST
+    n = int(arrays[1].shape[0]) - 1
+    if int(arrays[2].shape[0]) != n + 1:
+        raise ValueError(f"span_off has {int(arrays[2].shape[0])} entries for {n} sequences ({n + 1} expected)")
+    if int(arrays[3].numel() if dev_in else arrays[3].size) < 2 * max(n_spans, 0):
+        raise ValueError(f"span_tok holds fewer than the {n_spans} (begin, end) pairs span_off announces")
+    ip, op_, sop, stp = ptrs
+    if out is not None and hasattr(out, "is_cuda") and out.is_cuda:
+        assert out.is_contiguous() and tuple(out.shape) == (max(n_spans, 0), desc.hidden)
+        engine._follow(out)
+        check(engine._lib.vr_encode_spans(engine.handle, ip, op_, n, sop, stp, mem, C.c_void_p(out.data_ptr()),
+                                          VR_MEM_DEVICE))
+        return out
+    res = np.empty((max(n_spans, 0), desc.hidden), np.float32)
+    check(engine._lib.vr_encode_spans(engine.handle, ip, op_, n, sop, stp, mem, C.c_void_p(res.ctypes.data), VR_MEM_HOST))
+    return res

@@ -232,20 +232,52 @@ class Engine:
                     created=None, modified=None, k: float = BM25_K, b: float = BM25_B,
                     avg_len: float = BM25_AVG_LEN) -> int:
         """encode -> BM25 tf -> store, all on the GPU. Token arrays are NumPy (host) or device tensors."""
+        return self._index_batch(wp_ids, wp_off, None, bm_ids, bm_off, folder_ids, index_folder_ids, created, modified,
+                                 k, b, avg_len)
+
+    def index_batch_spans(self, wp_ids, wp_off, span_off, span_tok, bm_ids=None, bm_off=None, folder_ids=None,
+                          index_folder_ids=None, created=None, modified=None, k: float = BM25_K, b: float = BM25_B,
+                          avg_len: float = BM25_AVG_LEN) -> int:
+        """index_batch for rows that are token spans of the sequences (encode_spans): row r gets the dense vector of
+        span r, and entry r of the BM25 arrays and of the payload columns."""
+        return self._index_batch(wp_ids, wp_off, (span_off, span_tok), bm_ids, bm_off, folder_ids, index_folder_ids,
+                                 created, modified, k, b, avg_len)
+
+    def encode_spans(self, ids, offsets, span_off, span_tok, out=None):
+        from . import encoder
+
+        return encoder.encode_spans(self, ids, offsets, span_off, span_tok, out)
+
+    def _index_batch(self, wp_ids, wp_off, spans, bm_ids, bm_off, folder_ids, index_folder_ids, created, modified,
+                     k, b, avg_len) -> int:
         dev = _is_device_tensor(wp_ids)
+        span_off, span_tok = spans if spans is not None else (None, None)
         if dev:
             self._follow(wp_ids)
-            n = int(wp_off.shape[0]) - 1
-            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(None)  # noqa: E731
-            keep = [wp_ids, wp_off, bm_ids, bm_off]
-            args = [ptr(wp_ids), ptr(wp_off), ptr(bm_ids), ptr(bm_off)]
+            if spans is not None:
+                span_tok = span_tok.contiguous()
+            keep = [wp_ids, wp_off, span_off, span_tok, bm_ids, bm_off]
+            args = [C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(None) for t in keep]
+            n_last = int(span_off[-1].item()) if spans is not None else 0
         else:
             wp_ids, wp_off = _np(wp_ids, np.int32), _np(wp_off, np.int32)
-            n = wp_off.shape[0] - 1
+            if spans is not None:
+                span_off, span_tok = _np(span_off, np.int32), _np(span_tok, np.int32)
             if bm_ids is not None:
                 bm_ids, bm_off = _np(bm_ids, np.int32), _np(bm_off, np.int64)
-            keep = [wp_ids, wp_off, bm_ids, bm_off]
+            keep = [wp_ids, wp_off, span_off, span_tok, bm_ids, bm_off]
             args = [C.c_void_p(a.ctypes.data) if a is not None else C.c_void_p(None) for a in keep]
+            n_last = int(span_off[-1]) if spans is not None else 0
+        n_seq = int(wp_off.shape[0]) - 1
+        n = n_seq
+        if spans is not None:
+            if int(span_off.shape[0]) != n_seq + 1:
+                raise ValueError(f"span_off has {int(span_off.shape[0])} entries for {n_seq} sequences")
+            # one row per chunk: the BM25 offsets, else a payload column, else span_off itself say how many
+            given = [len(c) for c in (folder_ids, index_folder_ids, created, modified) if c is not None]
+            n = int(bm_off.shape[0]) - 1 if bm_off is not None else given[0] if given else n_last
+            if int(span_tok.numel() if dev else span_tok.size) < 2 * max(n_last, 0):
+                raise ValueError(f"span_tok holds fewer than the {n_last} (begin, end) pairs span_off announces")
 
         def col(a, dtype, ctype):
             if a is None:
@@ -256,10 +288,13 @@ class Engine:
             return _ptr(a, ctype)
 
         first = C.c_int64(-1)
-        check(self._lib.vr_index_batch(self._h, n, VR_MEM_DEVICE if dev else VR_MEM_HOST, *args, k, b, avg_len,
-                                       col(folder_ids, np.int32, C.c_int32), col(index_folder_ids, np.int32, C.c_int32),
-                                       col(created, np.int64, C.c_int64), col(modified, np.int64, C.c_int64),
-                                       C.byref(first)))
+        mem = VR_MEM_DEVICE if dev else VR_MEM_HOST
+        tail = (k, b, avg_len, col(folder_ids, np.int32, C.c_int32), col(index_folder_ids, np.int32, C.c_int32),
+                col(created, np.int64, C.c_int64), col(modified, np.int64, C.c_int64), C.byref(first))
+        if spans is None:
+            check(self._lib.vr_index_batch(self._h, n, mem, args[0], args[1], args[4], args[5], *tail))
+        else:
+            check(self._lib.vr_index_batch_spans(self._h, n, mem, args[0], args[1], n_seq, *args[2:], *tail))
         return int(first.value)
 
     def delete_rows(self, rows) -> None:

@@ -7,7 +7,9 @@ before and N×D Python floats passing between them. ``BulkIndexer`` runs the sam
 stream of files with the same stored result (same chunks, payload fields, vectors and scores), but
 
 * cut into batches of ``batch_chunks`` chunks regardless of file boundaries (a 3-chunk file does not
-  pay a GPU launch sequence of its own),
+  pay a GPU launch sequence of its own) — with VOITTA_LATE_CHUNKING=1, into batches of whole files until
+  ``batch_chunks`` is reached: a file's chunks are token spans of the file's own sequences
+  (late_chunking.plan_many, vr_index_batch_spans), so a batch never holds half a file,
 * the host stages — chunking (vr_chunk_texts), WordPiece (vr_wordpiece_encode) and the BM25 tokeniser
   (vr_bm25_tokenize), all on every host thread — run on a producer thread for batch i+1 while
 * point ids and payload dicts of batch i+1 are made there too (VectorStoreService.prepare_rows), and
@@ -25,6 +27,7 @@ from datetime import datetime, timezone
 from typing import Iterable, Iterator
 
 from . import bm25 as _bm25
+from .config import get_settings
 from .chunking import ChunkingService, get_chunking_service
 from .embedding import EmbeddingService, get_embedding_service
 from .vector_store import ChunkMetadata, VectorStoreService, get_vector_store
@@ -55,6 +58,7 @@ class _Batch:
     bm_off: object
     counts: dict[str, int]
     rows: tuple | None = None  # (point ids, payload dicts) made on the producer thread
+    spans: tuple | None = None  # late chunking: (n_seq, span_off, span_tok), wp_ids / wp_off are document windows
 
 
 class BulkIndexer:
@@ -67,32 +71,43 @@ class BulkIndexer:
         self.sparse = sparse
         self.batch_chunks = int(batch_chunks)
         self.files_per_cut = int(files_per_cut)
+        # late chunking (VOITTA_LATE_CHUNKING=1): a batch is whole files, their contents kept beside the chunks
+        self.late = get_settings().late_chunking
 
     # ---- host stages (producer thread) -------------------------------------------------------------
-    def _tokenise(self, texts: list[str], metadatas: list[ChunkMetadata], counts: dict[str, int]) -> _Batch:
+    def _tokenise(self, texts: list[str], metadatas: list[ChunkMetadata], counts: dict[str, int],
+                  documents: list | None = None) -> _Batch:
         model = self.embedder.model
-        encoder_texts = texts
-        if "e5" in self.embedder.model_name.lower():  # embedding.py:65-66
-            encoder_texts = [f"passage: {t}" for t in texts]
-        wp_ids, wp_off = model.tokenize(encoder_texts)
+        spans = None
+        if documents is not None:  # [(content, its chunk texts)]: the texts of this batch, file by file
+            plan = model.plan_documents(documents, self.embedder._passage(""))
+            wp_ids, wp_off, spans = plan.ids, plan.offsets, plan.spans()
+        else:
+            encoder_texts = texts
+            if "e5" in self.embedder.model_name.lower():  # embedding.py:65-66
+                encoder_texts = [f"passage: {t}" for t in texts]
+            wp_ids, wp_off = model.tokenize(encoder_texts)
         bm_ids = bm_off = None
         if self.sparse:
             bm_off, bm_ids = _bm25.hashed_stems(texts)  # BM25 sees the chunk text itself (indexing.py:529-530)
         rows = self.vector_store.prepare_rows(texts, metadatas) if hasattr(self.vector_store, "prepare_rows") else None
-        return _Batch(texts, metadatas, wp_ids, wp_off, bm_ids, bm_off, counts, rows)
+        return _Batch(texts, metadatas, wp_ids, wp_off, bm_ids, bm_off, counts, rows, spans)
 
     def _batches(self, files: Iterable[ParsedFile]) -> Iterator[_Batch]:
         texts: list[str] = []
         metadatas: list[ChunkMetadata] = []
         counts: dict[str, int] = {}
         pending: list[ParsedFile] = []
+        documents: list = []  # late chunking: (content, chunk texts) of every file with chunks, in the order of `texts`
 
         def cut(group: list[ParsedFile]):
             indexed_at = datetime.now(timezone.utc).isoformat()  # indexing.py:538
             for f, chunks in zip(group, self.chunker.chunk_texts([f.content for f in group])):
                 counts[f.file_path] = len(chunks)  # 0: empty content / no chunks (indexing.py:509-522)
+                if self.late and chunks:
+                    documents.append((f.content, [str(c.text) for c in chunks]))
                 for c in chunks:
-                    texts.append(c.text)
+                    texts.append(str(c.text) if self.late else c.text)
                     metadatas.append(ChunkMetadata(
                         file_path=f.file_path, folder_path=f.folder_path, index_folder=f.index_folder,
                         file_name=f.file_name, chunk_index=c.index, total_chunks=len(chunks),
@@ -101,11 +116,18 @@ class BulkIndexer:
                         allowed_users=f.allowed_users, source_url=f.source_url))
 
         def drain(everything: bool):
-            nonlocal texts, metadatas, counts
+            nonlocal texts, metadatas, counts, documents
             while len(texts) >= self.batch_chunks or (everything and texts):
                 take = min(len(texts), self.batch_chunks)
+                docs = None
+                if self.late:  # files until batch_chunks is reached, never half a file: its chunks share its sequences
+                    n_docs = take = 0
+                    while n_docs < len(documents) and take < self.batch_chunks:
+                        take += len(documents[n_docs][1])
+                        n_docs += 1
+                    docs, documents = documents[:n_docs], documents[n_docs:]
                 last = take == len(texts)
-                yield self._tokenise(texts[:take], metadatas[:take], counts if last else {})
+                yield self._tokenise(texts[:take], metadatas[:take], counts if last else {}, docs)
                 texts, metadatas = texts[take:], metadatas[take:]
                 if last:
                     counts = {}
@@ -149,7 +171,11 @@ class BulkIndexer:
                 if batch is None:
                     break
                 if batch.texts:
-                    if batch.rows is not None:
+                    if batch.spans is not None:
+                        extra = {"rows": batch.rows} if batch.rows is not None else {}
+                        self.vector_store.index_chunks(batch.texts, batch.metadatas, batch.wp_ids, batch.wp_off,
+                                                       batch.bm_ids, batch.bm_off, spans=batch.spans, **extra)
+                    elif batch.rows is not None:
                         self.vector_store.index_chunks(batch.texts, batch.metadatas, batch.wp_ids, batch.wp_off,
                                                        batch.bm_ids, batch.bm_off, rows=batch.rows)
                     else:

@@ -389,7 +389,7 @@ class VectorStoreService:
     @staticmethod
     def _payload_of(text: str, metadata: ChunkMetadata) -> dict:
         payload = {  # vector_store.py:259-288
-            "text": text,
+            "text": text if type(text) is str else str(text),  # (a LateChunkText is stored as its characters alone)
             "file_path": metadata.file_path,
             "folder_path": metadata.folder_path,
             "index_folder": metadata.index_folder,
@@ -710,7 +710,8 @@ class VectorStoreService:
         return ids, [cls._payload_of(text, metadata) for text, metadata in zip(texts, metadatas)]
 
     def index_chunks(self, texts: list[str], metadatas: list[ChunkMetadata], wp_ids, wp_off,
-                     bm_ids=None, bm_off=None, rows: tuple[list[str], list[dict]] | None = None) -> list[str]:
+                     bm_ids=None, bm_off=None, rows: tuple[list[str], list[dict]] | None = None,
+                     spans: tuple | None = None) -> list[str]:
         """The fused form of the three calls of IndexingService._index_file_standard —
         ``embedder.embed_texts`` + ``sparse_embedder.embed_texts`` + ``store_chunks``
         (indexing.py:527-530,560) — for a caller that hands over token ids instead of vectors: WordPiece
@@ -718,7 +719,9 @@ class VectorStoreService:
         ``bm_off``, or None for a dense-only store). Encode, tf weighting and the append run in ONE engine
         call (vr_index_batch) and nothing leaves HBM; the stored rows, payloads and scores are those the
         three calls would have produced. Needs the encoder loaded into this store's engine.
-        ``rows``: the result of ``prepare_rows`` for this batch, when the caller made it ahead of time."""
+        ``rows``: the result of ``prepare_rows`` for this batch, when the caller made it ahead of time.
+        ``spans``: (n_seq, span_off, span_tok) of a late-chunking plan — ``wp_ids`` / ``wp_off`` then hold n_seq
+        document windows, chunk r is token span r of them, and the call is vr_index_batch_spans."""
         n = len(texts)
         if n == 0:
             return []
@@ -737,8 +740,15 @@ class VectorStoreService:
                 folder = np.array([col.folder_id(m.folder_path, True) for m in metadatas], np.int32)
                 ifolder = np.array([col.index_folder_id(m.index_folder, True) for m in metadatas], np.int32)
             try:
-                got = self._engine.index_batch(wp_ids, wp_off, bm_ids, bm_off, folder_ids=folder, index_folder_ids=ifolder,
-                                              created=created, modified=modified)
+                if spans is not None:
+                    n_seq, span_off, span_tok = spans
+                    assert len(wp_off) == n_seq + 1 and len(span_off) == n_seq + 1 and int(span_off[-1]) == n
+                    got = self._engine.index_batch_spans(wp_ids, wp_off, span_off, span_tok, bm_ids, bm_off,
+                                                         folder_ids=folder, index_folder_ids=ifolder, created=created,
+                                                         modified=modified)
+                else:
+                    got = self._engine.index_batch(wp_ids, wp_off, bm_ids, bm_off, folder_ids=folder,
+                                                   index_folder_ids=ifolder, created=created, modified=modified)
                 assert got == first, "host table and engine rows diverged"
             except BaseException:
                 self._drop_host_rows(col, first, ids, payloads)
