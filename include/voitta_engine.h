@@ -138,6 +138,13 @@ typedef struct vr_bert_desc {
   int32_t position;      /* VR_POS_LEARNED | VR_POS_ROTARY */
   float   rope_theta;    /* VR_POS_ROTARY: base of the rotary frequencies, inv_freq_i = theta^(-2i/d_h); > 0 */
   int32_t ffn;           /* VR_FFN_GELU | VR_FFN_SWIGLU | VR_FFN_GEGLU */
+  /* Added with the pre-norm family (ModernBERT): again zero in every field is the behaviour of a description that
+   * ends at `ffn`, and struct_size may be that shorter size. */
+  int32_t norm;          /* VR_NORM_POST | VR_NORM_PRE */
+  int32_t window;        /* sliding-window attention: the half-width w, 0 .. 4096. 0: every layer attends globally.
+                          * Otherwise query i of a windowed layer sees key j of its own sequence iff |i - j| <= w */
+  int32_t global_every;  /* window > 0: layer l attends globally iff l % global_every == 0 (>= 1), the rest are windowed */
+  float   rope_theta_local; /* the rotary base of the windowed layers; 0 = rope_theta */
 } vr_bert_desc;
 
 /* position: LEARNED adds a row of the position table to every token's embedding; ROTARY has no table — the query and
@@ -150,6 +157,11 @@ typedef struct vr_bert_desc {
 #define VR_FFN_GELU   0
 #define VR_FFN_SWIGLU 1
 #define VR_FFN_GEGLU  2
+/* norm: POST is BERT's x = LN(x + f(x)). PRE is x = x + attn(LN(x)), x = x + mlp(LN(x)) with one final LayerNorm; the
+ * embedding LayerNorm stays in the stream and layer 0 has no attention norm. PRE needs VR_POS_ROTARY and a gated ffn;
+ * a window needs VR_NORM_PRE (and so rotary positions). A reranker takes neither. */
+#define VR_NORM_POST 0
+#define VR_NORM_PRE  1
 
 /* arithmetic of the encoder's matrix products:
  *   F32    every product on the f32-input MFMA (exact f32 fma chains) — 157 TFLOP/s peak
@@ -171,6 +183,11 @@ typedef struct vr_bert_desc {
  *   intermediate.dense.{weight,bias}, output.dense.{weight,bias}, output.LayerNorm.{weight,bias}.
  * A gated ffn (VR_FFN_SWIGLU / VR_FFN_GEGLU) has 18 slots per layer (5 + 18*layers tensors): the 16 above, where
  * intermediate.dense.{weight,bias} is the UP projection [I,H], followed by the GATE projection's {weight [I,H], bias}.
+ * VR_NORM_PRE: the LayerNorm slots keep their places in the dataflow — each holds the norm that FOLLOWS the residual
+ * add it sits behind, and the residual stream bypasses it: embeddings.LayerNorm = the embedding norm (in the stream);
+ * layer l's attention.output.LayerNorm = the norm in front of layer l's FFN (ModernBERT: layers.l.mlp_norm); layer l's
+ * output.LayerNorm = the norm in front of layer l + 1's attention (layers.l+1.attn_norm), and for the last layer the
+ * final norm (final_norm). Layer 0's attention reads the embedding norm's output as it is.
  * NULL slots: any bias (read as zeros), and position_embeddings when position is VR_POS_ROTARY (ignored then).
  * Every other slot must be non-NULL.
  * The engine copies (and re-packs) them; the caller's tensors may be freed afterwards.

@@ -61,6 +61,10 @@ class VrBertDesc(C.Structure):
         ("position", C.c_int32),
         ("rope_theta", C.c_float),
         ("ffn", C.c_int32),
+        ("norm", C.c_int32),
+        ("window", C.c_int32),
+        ("global_every", C.c_int32),
+        ("rope_theta_local", C.c_float),
     ]
 
 
@@ -72,6 +76,8 @@ VR_POS_ROTARY = 1
 VR_FFN_GELU = 0
 VR_FFN_SWIGLU = 1
 VR_FFN_GEGLU = 2
+VR_NORM_POST = 0
+VR_NORM_PRE = 1
 VR_POOL_MEAN = 0
 VR_POOL_CLS = 1
 VR_MEM_HOST = 0

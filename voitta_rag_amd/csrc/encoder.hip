@@ -74,6 +74,8 @@ struct Encoder {
   // rotary positions: (cos, sin) of position p for the pair q = head * d_h/2 + i of a head-major [H/2] row (the d_h/2
   // frequencies repeated for every head, so that an epilogue finds its entry from the column alone), max_pos rows
   float2* rope = nullptr;
+  float2* rope_local = nullptr;  // ... of the windowed layers' base (vr_bert_desc.rope_theta_local); null: they use `rope`
+  int window_stream_from = 0;    // windowed layers: sequences from this length on take attention_stream_kernel (build_encoder)
   float* posidx = nullptr;  // rotary: int32 position of every token inside its own sequence (positions_kernel)
   bool fuse = true;         // rotate / gate inside the skinny epilogues; VR_ENCODE_FUSE=0 at load time: separate passes
   DevArray<int32_t> ids, cu, seg;
@@ -2993,16 +2995,41 @@ static int launch_gemm_f16x3(vr_engine* e, Encoder* enc, int epi, const GemmArgs
 
 // ---- attention -----------------------------------------------------------------------------------
 
+// Sliding-window attention (vr_bert_desc.window = w > 0 on a windowed layer): query i sees key j of its own sequence iff
+// |i - j| <= w. The three kernels below take `window` (0: none) and mask the logits outside it to -inf exactly as they
+// mask keys behind the sequence's end. WIN, a template flag the host sets to window > 0, makes the argument a
+// compile-time 0 for every other launch: those instantiate the code they ran before there was a window (with the
+// bounds and the guard below as run-time values the staged kernel, 11 % of an indexing step, ran about 4 % slower in
+// one A/B of the contract benchmark; those lines were not kept).
+// One unsigned compare per logit: key - (q - w) <= 2w; without a window the bound is UINT_MAX and every key passes.
+struct WindowMask {
+  int lo;
+  unsigned span;
+  __device__ __forceinline__ WindowMask(int q, int window)
+      : lo(window > 0 ? q - window : 0), span(window > 0 ? 2u * static_cast<unsigned>(window) : 0xffffffffu) {}
+  __device__ __forceinline__ bool sees(int key) const { return static_cast<unsigned>(key - lo) <= span; }
+};
+// With a window a query can meet a 64-key tile none of whose keys it sees — and that can be the FIRST tile it meets (the
+// last queries of a block against the block's first key tile; query tiles are skipped per wave where the whole tile lies
+// outside, but inside a tile that some query of the wave sees, others may see nothing). Its running maximum is then
+// still -inf, and exp(s - m) = exp(-inf + inf) is NaN. The value the exponentials SUBTRACT is therefore 0 while the
+// maximum is -inf: every p is exp(-inf) = 0, the rescale factor exp(-inf - 0) = 0 multiplies sums that are 0 anyway.
+// Only the subtrahend is guarded: the running maximum a kernel keeps stays -inf (m = m_raw), so the first tile with a
+// visible key rescales by exp(-inf - finite) = 0 and subtracts that tile's own maximum — a 0 stored back as the maximum
+// would floor every later base at 0, and logits far below 0 (P rounds to f16 zero below about -17) would lose the row.
+__device__ __forceinline__ float softmax_base(float m_raw) { return m_raw == -__builtin_inff() ? 0.0f : m_raw; }
+
 // One block = 64 queries of one (sequence, head); wave w owns queries 16w..16w+15.
 // S^T = K Q^T is computed with keys on the MFMA rows, so a lane (q = lane & 15, g = lane >> 4)
 // ends up holding the logits of query q against keys 4g..4g+3 of each 16-key tile: exactly the B
 // operand layout of the following O^T += V^T P^T product — no transpose, no LDS round trip for P.
-template <int DH>
+template <int DH, bool WIN>
 __global__ __launch_bounds__(256) void attention_kernel(const float* __restrict__ qkv,
                                                         const int32_t* __restrict__ cu, int seq0,
                                                         int tok_base, int H, int qblocks, float scale,
                                                         float* __restrict__ ctx, half_t* __restrict__ ctx_hi,
-                                                        half_t* __restrict__ ctx_lo) {
+                                                        half_t* __restrict__ ctx_lo, int window_arg) {
+  const int window = WIN ? window_arg : 0;
   constexpr int LDK = DH + 4;
   constexpr int NS = DH / 16;  // 16-wide d blocks
   __shared__ float sK[64 * LDK];
@@ -3033,6 +3060,7 @@ __global__ __launch_bounds__(256) void attention_kernel(const float* __restrict_
   for (int s = 0; s < NS; ++s) o[s] = f32x4{0.f, 0.f, 0.f, 0.f};
   float m = -__builtin_inff();
   float l = 0.0f;
+  const WindowMask wm(q_tok, window);
 
   for (int kt = 0; kt < len; kt += 64) {
     __syncthreads();
@@ -3068,13 +3096,14 @@ __global__ __launch_bounds__(256) void attention_kernel(const float* __restrict_
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int key = kt + t * 16 + 4 * g + r;
-        const float v = key < len ? st[t][r] * scale : -__builtin_inff();
+        const float v = key < len && wm.sees(key) ? st[t][r] * scale : -__builtin_inff();
         st[t][r] = v;
         mx = fmaxf(mx, v);
       }
     mx = fmaxf(mx, __shfl_xor(mx, 16));
     mx = fmaxf(mx, __shfl_xor(mx, 32));
-    const float m_new = fmaxf(m, mx);  // finite: key kt < len is always valid
+    const float m_raw = fmaxf(m, mx);  // (no window: finite, key kt < len is always valid)
+    const float m_new = WIN ? softmax_base(m_raw) : m_raw;  // what the exponentials subtract; the maximum kept is m_raw
     const float alpha = expf(m - m_new);
     float psum = 0.0f;
 #pragma unroll
@@ -3086,7 +3115,7 @@ __global__ __launch_bounds__(256) void attention_kernel(const float* __restrict_
         psum += p;
       }
     l = l * alpha + psum;
-    m = m_new;
+    m = m_raw;
 #pragma unroll
     for (int s = 0; s < NS; ++s) o[s] *= alpha;
 #pragma unroll
@@ -3149,10 +3178,11 @@ __global__ __launch_bounds__(256) void attention_kernel(const float* __restrict_
 // `q_limit`: only queries below it are computed (the last layer of a CLS-pooled model needs token 0 only).
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 
-template <int DH, int NW>
+template <int DH, int NW, bool WIN>
 __global__ __launch_bounds__(NW * 64) void attention_seq_kernel(const half_t* __restrict__ qkv, const int32_t* __restrict__ cu,
                                                             int seq0, int tok_base, int H, float scale, int q_limit,
-                                                            int lds_keys, half_t* __restrict__ ctx_h) {
+                                                            int lds_keys, half_t* __restrict__ ctx_h, int window_arg) {
+  const int window = WIN ? window_arg : 0;
   constexpr int LDK = DH;       // halfs per staged row: unpadded, 16-byte chunks XOR-swizzled by the row instead
   constexpr int CH = DH / 8;    // 16-byte chunks per row
   // chunk c of K row r sits at c ^ kswz(r): the 16 rows x one chunk of a ds_read_b128 fragment read then cover all 64
@@ -3236,7 +3266,11 @@ __global__ __launch_bounds__(NW * 64) void attention_seq_kernel(const half_t* __
     for (int s = 0; s < NS; ++s) o[s] = f32x4{0.f, 0.f, 0.f, 0.f};
     float m = -__builtin_inff();
     float l = 0.0f;
-    for (int kt = 0; kt < keys_pad; kt += 64) {
+    // a window: only the 64-key tiles that hold a key some query of this tile sees (wave-uniform bounds)
+    const int kt0 = window > 0 ? max(0, qt * 16 - window) & ~63 : 0;
+    const int kt1 = window > 0 ? min(keys_pad, qt * 16 + 16 + window) : keys_pad;
+    const WindowMask wm(q_tok, window);
+    for (int kt = kt0; kt < kt1; kt += 64) {
       const int nt = min(4, (keys_pad - kt) >> 4);  // 16-key groups in this tile (block-uniform)
       f32x4 st[4];
 #pragma unroll
@@ -3251,7 +3285,8 @@ __global__ __launch_bounds__(NW * 64) void attention_seq_kernel(const half_t* __
         }
       }
       float mx = -__builtin_inff();
-      if (kt + 64 <= len) {  // every key of the tile exists: no masks
+      // every key of the tile exists and every query of the tile sees all of them: no masks
+      if (kt + 64 <= len && (window <= 0 || (kt + 63 - qt * 16 <= window && qt * 16 + 15 - kt <= window))) {
 #pragma unroll
         for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -3265,14 +3300,15 @@ __global__ __launch_bounds__(NW * 64) void attention_seq_kernel(const half_t* __
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const int key = kt + t * 16 + 4 * g + r;
-            const float v = key < len ? st[t][r] * scale2 : -__builtin_inff();
+            const float v = key < len && wm.sees(key) ? st[t][r] * scale2 : -__builtin_inff();
             st[t][r] = v;
             mx = fmaxf(mx, v);
           }
       }
       mx = fmaxf(mx, __shfl_xor(mx, 16));
       mx = fmaxf(mx, __shfl_xor(mx, 32));
-      const float m_new = fmaxf(m, mx);  // finite: key kt < len is always valid
+      const float m_raw = fmaxf(m, mx);  // (no window: finite, key kt < len is always valid)
+      const float m_new = WIN ? softmax_base(m_raw) : m_raw;  // what the exponentials subtract; the maximum kept is m_raw
       const float alpha = __builtin_amdgcn_exp2f(m - m_new);
       float psum = 0.0f;
       f16x8 pb[2];  // pb[u][j]: key kt + 32 u + 16 (j >> 2) + 4 g + (j & 3)
@@ -3285,7 +3321,7 @@ __global__ __launch_bounds__(NW * 64) void attention_seq_kernel(const half_t* __
           pb[t >> 1][(t & 1) * 4 + r] = static_cast<half_t>(p);
         }
       l = l * alpha + psum;
-      m = m_new;
+      m = m_raw;
 #pragma unroll
       for (int s = 0; s < NS; ++s) o[s] *= alpha;
 #pragma unroll
@@ -3338,10 +3374,11 @@ __global__ __launch_bounds__(NW * 64) void attention_seq_kernel(const half_t* __
 // attention_seq_kernel. Grid: heads fastest, then the 128-query blocks of a sequence (`qblocks` of them per sequence);
 // `q_limit` as in attention_seq_kernel — the host launches query block 0 alone for it, and a wave whose queries all
 // lie at or behind it stages and takes every barrier but skips the products.
-template <int DH, int NW>
+template <int DH, int NW, bool WIN>
 __global__ __launch_bounds__(NW * 64) void attention_stream_kernel(const half_t* __restrict__ qkv, const int32_t* __restrict__ cu,
                                                                int seq0, int tok_base, int H, int qblocks, float scale,
-                                                               int q_limit, half_t* __restrict__ ctx_h) {
+                                                               int q_limit, half_t* __restrict__ ctx_h, int window_arg) {
+  const int window = WIN ? window_arg : 0;
   static_assert(NW == 4 && (DH == 64 || DH == 32), "one 16-byte piece of a 64-key tile per thread and CH / NW rounds");
   constexpr int LDK = DH;       // halfs per staged row: unpadded, 16-byte chunks XOR-swizzled by the row
   constexpr int CH = DH / 8;    // 16-byte chunks per row
@@ -3403,10 +3440,14 @@ __global__ __launch_bounds__(NW * 64) void attention_stream_kernel(const half_t*
       *reinterpret_cast<uint4*>(sV + key * LDK + (c8 ^ vswz(key)) * 8) = behind ? make_uint4(0, 0, 0, 0) : vr[i];
     }
   };
+  // a window: the block's 128 queries see keys q0 - w .. q0 + 127 + w only, so the key loop runs over the tiles that
+  // hold those — 128 + 2 w keys and a tile's rounding, whatever the sequence's length (block-uniform bounds)
+  const int kt0 = window > 0 ? max(0, q0 - window) & ~63 : 0;
+  const int kt1 = window > 0 ? min(len, q0 + NW * 32 + window) : len;
   {
     uint4 kr[NLD], vr[NLD];
-    request(0, kr, vr);
-    write(0, kr, vr, att_tiles, att_tiles + TILE);
+    request(kt0, kr, vr);
+    write(kt0, kr, vr, att_tiles, att_tiles + TILE);
   }
   __syncthreads();
 
@@ -3422,12 +3463,14 @@ __global__ __launch_bounds__(NW * 64) void attention_stream_kernel(const half_t*
     for (int s = 0; s < NS; ++s) o[i][s] = f32x4{0.f, 0.f, 0.f, 0.f};
   float m[2] = {-__builtin_inff(), -__builtin_inff()};
   float l[2] = {0.0f, 0.0f};
+  const WindowMask wm[2] = {WindowMask(qw + qi, window), WindowMask(qw + 16 + qi, window)};
   int buf = 0;
-  for (int kt = 0; kt < len; kt += 64, buf ^= 1) {
-    const bool more = kt + 64 < len;  // block-uniform
+  for (int kt = kt0; kt < kt1; kt += 64, buf ^= 1) {
+    const bool more = kt + 64 < kt1;  // block-uniform
     uint4 kr[NLD], vr[NLD];
     if (more) request(kt + 64, kr, vr);
-    if (active) {
+    // a tile none of the wave's 32 queries sees is skipped (wave-uniform; the wave still stages and takes the barrier)
+    if (active && (window <= 0 || (kt <= qw + 31 + window && kt + 63 >= qw - window))) {
       const half_t* sK = att_tiles + 2 * buf * TILE;
       const half_t* sV = sK + TILE;
       f32x4 st[2][4];
@@ -3446,7 +3489,9 @@ __global__ __launch_bounds__(NW * 64) void attention_stream_kernel(const half_t*
       for (int i = 0; i < 2; ++i) {
         if (i == 1 && !two) break;
         float mx = -__builtin_inff();
-        if (kt + 64 <= len) {  // every key of the tile exists: no masks
+        const int qt0 = qw + 16 * i;  // the tile's first query
+        // every key of the tile exists and every query of the tile sees all of them: no masks
+        if (kt + 64 <= len && (window <= 0 || (kt + 63 - qt0 <= window && qt0 + 15 - kt <= window))) {
 #pragma unroll
           for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -3460,14 +3505,15 @@ __global__ __launch_bounds__(NW * 64) void attention_stream_kernel(const half_t*
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
               const int key = kt + t * 16 + 4 * g + r;
-              const float v = key < len ? st[i][t][r] * scale2 : -__builtin_inff();
+              const float v = key < len && wm[i].sees(key) ? st[i][t][r] * scale2 : -__builtin_inff();
               st[i][t][r] = v;
               mx = fmaxf(mx, v);
             }
         }
         mx = fmaxf(mx, __shfl_xor(mx, 16));
         mx = fmaxf(mx, __shfl_xor(mx, 32));
-        const float m_new = fmaxf(m[i], mx);  // finite: key kt < len is always valid
+        const float m_raw = fmaxf(m[i], mx);  // (no window: finite, key kt < len is always valid)
+        const float m_new = WIN ? softmax_base(m_raw) : m_raw;  // what the exponentials subtract; the maximum kept is m_raw
         const float alpha = __builtin_amdgcn_exp2f(m[i] - m_new);
         float psum = 0.0f;
 #pragma unroll
@@ -3479,7 +3525,7 @@ __global__ __launch_bounds__(NW * 64) void attention_stream_kernel(const half_t*
             pb[i][t >> 1][(t & 1) * 4 + r] = static_cast<half_t>(p);
           }
         l[i] = l[i] * alpha + psum;
-        m[i] = m_new;
+        m[i] = m_raw;
 #pragma unroll
         for (int s = 0; s < NS; ++s) o[i][s] *= alpha;
       }
@@ -3644,7 +3690,9 @@ int encoder_hidden(vr_engine* e) {
 // shorter struct_size, and gets what it always got (learned positions, the plain GELU FFN).
 static int read_desc(const vr_bert_desc* src, vr_bert_desc* out) {
   const int32_t short_size = static_cast<int32_t>(offsetof(vr_bert_desc, position));
-  VR_CHECK(src->struct_size == static_cast<int32_t>(sizeof(vr_bert_desc)) || src->struct_size == short_size,
+  const int32_t post_size = static_cast<int32_t>(offsetof(vr_bert_desc, norm));  // ... or at `ffn`: post-norm, no window
+  VR_CHECK(src->struct_size == static_cast<int32_t>(sizeof(vr_bert_desc)) || src->struct_size == short_size ||
+               src->struct_size == post_size,
            "vr_bert_desc size mismatch");
   *out = vr_bert_desc{};
   memcpy(out, src, static_cast<size_t>(src->struct_size));
@@ -3659,6 +3707,10 @@ static int dev_alloc_copy_or_zero(vr_engine* e, Encoder* enc, const void* src, s
   return 0;
 }
 
+// windowed layers take attention_stream_kernel from this many tokens on (the longest sequence of the pass), the staged
+// kernel below: the measured crossover, see DESIGN.md §19
+static const int kWindowStreamFrom = 384;
+
 // a model from its 5 + 16 L (gated FFN: 5 + 18 L) tensors (vr_encoder_load's order) into *slot, replacing what is there
 static int build_encoder(vr_engine* e, void** slot, const vr_bert_desc* d_in, const void* const* t, int n_tensors, int mem) {
   vr_bert_desc desc;
@@ -3671,6 +3723,20 @@ static int build_encoder(vr_engine* e, void** slot, const vr_bert_desc* d_in, co
   const int per_layer = gated ? 18 : 16;
   VR_CHECK(!rotary || (std::isfinite(d->rope_theta) && d->rope_theta > 0.0f), "rope_theta %g must be positive",
            static_cast<double>(d->rope_theta));
+  VR_CHECK(d->norm == VR_NORM_POST || d->norm == VR_NORM_PRE, "unknown norm placement %d", d->norm);
+  const bool prenorm = d->norm == VR_NORM_PRE;
+  VR_CHECK(!prenorm || rotary, "norm VR_NORM_PRE needs position VR_POS_ROTARY (position %d): pre-norm encoders with a "
+           "position table are not implemented", d->position);
+  VR_CHECK(!prenorm || gated, "norm VR_NORM_PRE needs a gated ffn (ffn %d): pre-norm encoders with the plain GELU "
+           "feed-forward block are not implemented", d->ffn);
+  VR_CHECK(d->window >= 0 && d->window <= 4096, "window %d must lie in 0..4096", d->window);
+  VR_CHECK(d->window == 0 || rotary, "window %d needs position VR_POS_ROTARY (position %d)", d->window, d->position);
+  VR_CHECK(d->window == 0 || prenorm, "window %d needs norm VR_NORM_PRE (norm %d): sliding-window attention in a "
+           "post-norm encoder is not implemented", d->window, d->norm);
+  VR_CHECK(d->window == 0 || d->global_every >= 1, "global_every %d must be >= 1 when window is set", d->global_every);
+  VR_CHECK(d->rope_theta_local == 0.0f || (rotary && std::isfinite(d->rope_theta_local) && d->rope_theta_local > 0.0f),
+           "rope_theta_local %g must be positive (or 0: rope_theta) and needs position VR_POS_ROTARY",
+           static_cast<double>(d->rope_theta_local));
   VR_CHECK(d->max_pos >= 1 && d->max_pos <= 8192, "max_pos %d must lie in 1..8192 (the longest sequence the engine runs)",
            d->max_pos);
   VR_CHECK(L >= 1 && H >= 128 && H % 128 == 0 && H <= 1024, "hidden %d must be a multiple of 128 in 128..1024", H);
@@ -3687,6 +3753,14 @@ static int build_encoder(vr_engine* e, void** slot, const vr_bert_desc* d_in, co
                       in_layer == 13 || in_layer == 17;
     VR_CHECK(t[i] != nullptr || bias || (i == 1 && rotary), "tensor %d is null", i);
   }
+  int window_stream_from = kWindowStreamFrom;  // (checked here: nothing is replaced when it is refused)
+  if (const char* from = getenv("VR_WINDOW_STREAM_FROM")) {
+    char* end = nullptr;
+    const long v = strtol(from, &end, 10);
+    VR_CHECK(end != from && *end == '\0' && v >= 1 && v <= INT32_MAX, "VR_WINDOW_STREAM_FROM='%s' must be a whole number >= 1",
+             from);
+    window_stream_from = static_cast<int>(v);
+  }
   free_encoder(slot);
   Encoder* enc = new Encoder();
   *slot = enc;
@@ -3695,22 +3769,33 @@ static int build_encoder(vr_engine* e, void** slot, const vr_bert_desc* d_in, co
   const size_t HH = static_cast<size_t>(H) * H;
   VR_TRY(dev_alloc_copy(e, enc, t[0], static_cast<size_t>(d->vocab) * H, mem, &enc->word));
   if (!rotary) VR_TRY(dev_alloc_copy(e, enc, t[1], static_cast<size_t>(d->max_pos) * H, mem, &enc->pos));
-  std::vector<float2> rope_host;  // (lives until the synchronisation at the end: it is the source of an async copy)
-  if (rotary) {  // (cos, sin)(p * theta^(-2i/d_h)) in f64, stored as f32
+  std::vector<float2> rope_host[2];  // (live until the synchronisation at the end: they are sources of async copies)
+  auto rope_table = [&](float theta, std::vector<float2>& host, float2** out) -> int {
+    // (cos, sin)(p * theta^(-2i/d_h)) in f64, stored as f32
     const int half = H / d->heads / 2, row = H / 2;  // a row repeats the d_h/2 frequencies for every head
-    rope_host.resize(static_cast<size_t>(d->max_pos) * row);
+    host.resize(static_cast<size_t>(d->max_pos) * row);
     for (int i = 0; i < half; ++i) {
-      const double inv_freq = std::pow(static_cast<double>(d->rope_theta), -2.0 * i / (2.0 * half));
+      const double inv_freq = std::pow(static_cast<double>(theta), -2.0 * i / (2.0 * half));
       for (int p = 0; p < d->max_pos; ++p) {
         const double a = p * inv_freq;
         const float2 cs = make_float2(static_cast<float>(std::cos(a)), static_cast<float>(std::sin(a)));
-        for (int h = 0; h < d->heads; ++h) rope_host[static_cast<size_t>(p) * row + h * half + i] = cs;
+        for (int h = 0; h < d->heads; ++h) host[static_cast<size_t>(p) * row + h * half + i] = cs;
       }
     }
     float* table = nullptr;
-    VR_TRY(dev_alloc_copy(e, enc, rope_host.data(), rope_host.size() * 2, VR_MEM_HOST, &table));
-    enc->rope = reinterpret_cast<float2*>(table);
-  }
+    VR_TRY(dev_alloc_copy(e, enc, host.data(), host.size() * 2, VR_MEM_HOST, &table));
+    *out = reinterpret_cast<float2*>(table);
+    return 0;
+  };
+  if (rotary) VR_TRY(rope_table(d->rope_theta, rope_host[0], &enc->rope));
+  // the windowed layers' table: only where a layer is windowed and its base differs (bit for bit the same table else)
+  if (rotary && d->window > 0 && d->rope_theta_local != 0.0f && d->rope_theta_local != d->rope_theta)
+    VR_TRY(rope_table(d->rope_theta_local, rope_host[1], &enc->rope_local));
+  // Windowed layers of sequences short enough to stage whole: the staged kernel visits 128 + 2 w keys per 128 queries
+  // as well (it skips the key tiles outside a query tile's window) but runs one block per (sequence, head), the
+  // streamed kernel one per 128 queries. Which is faster was measured at 512 tokens;
+  // VR_WINDOW_STREAM_FROM, read when the model is loaded, moves the length from which the streamed kernel runs.
+  enc->window_stream_from = window_stream_from;
   VR_TRY(dev_alloc_copy(e, enc, t[2], static_cast<size_t>(d->type_vocab) * H, mem, &enc->type));
   VR_TRY(dev_alloc_copy(e, enc, t[3], H, mem, &enc->lng));
   VR_TRY(dev_alloc_copy(e, enc, t[4], H, mem, &enc->lnb));
@@ -3775,7 +3860,7 @@ static int build_encoder(vr_engine* e, void** slot, const vr_bert_desc* d_in, co
         if (rotary) VR_TRY(reordered(lw.wqkv, lw.bqkv, 3 * H, 0, H, &lw.s_qkv_p, &lw.bqkv_p));
         if (gated) VR_TRY(reordered(lw.w1, lw.b1, 2 * I, 1, I, &lw.s_1_p, &lw.b1_p));
       }
-      if (plain && H % 64 == 0) {  // operands of the folded-LayerNorm GEMMs
+      if (plain && H % 64 == 0 && !prenorm) {  // operands of the folded-LayerNorm GEMMs (the post-norm loop's)
         auto fold = [&](const float* w_dev, int N, const float* g, const float* b, const float* bias, SplitWeight* sw,
                         float** colsum, float** c) -> int {
           const size_t n = static_cast<size_t>(N) * H;
@@ -3827,6 +3912,9 @@ int reranker_load(vr_engine* e, const vr_bert_desc* d_in, const void* const* t, 
   VR_CHECK(d->position == VR_POS_LEARNED && d->ffn == VR_FFN_GELU,
            "a reranker with rotary positions or a gated FFN is not supported (position %d, ffn %d): cross-encoders are "
            "BERT or XLM-RoBERTa models", d->position, d->ffn);
+  VR_CHECK(d->norm == VR_NORM_POST && d->window == 0,
+           "a reranker with norm %d or window %d is not supported: pre-norm and sliding-window cross-encoders are not "
+           "implemented", d->norm, d->window);
   VR_CHECK(d->pooling == VR_POOL_CLS && d->normalize == 0, "a reranker pools the [CLS] row (pooling 1) without normalising");
   // two token types (BERT: segment B reads type row 1), or one (XLM-R: every token reads row 0, seg_b is not used)
   VR_CHECK(d->type_vocab >= 1, "a reranker needs a token type (type_vocab %d)", d->type_vocab);
@@ -3882,6 +3970,92 @@ static int ensure_workspace(vr_engine* e, Encoder* enc, int64_t tokens) {
   return 0;
 }
 
+// One layer's attention over the Q/K/V rows in enc->qkv into enc->ctx, for sequences [seq0, seq0 + n_seq). tail: only the
+// query block that holds token 0 of every sequence (the CLS tail of forward_chunk). window: 0, or the half-width of a
+// windowed layer.
+static int launch_attention(vr_engine* e, Encoder* enc, const int32_t* cu_dev, int seq0, int n_seq, int tok_base,
+                            int max_len, bool tail, int window, double attn_flop) {
+  const vr_bert_desc& d = enc->d;
+  const int H = d.hidden, nh = d.heads, dh = H / nh;
+  hipStream_t s = e->stream;
+  const bool split = d.precision != VR_PRECISION_F32;
+  const bool plain = d.precision == VR_PRECISION_F16;
+  half_t* ch = split ? reinterpret_cast<half_t*>(enc->ctx) : nullptr;
+  half_t* cl = split && !plain ? ch + 8 : nullptr;
+  const int qblocks = (max_len + 63) / 64;
+  const float scale = 1.0f / sqrtf(static_cast<float>(dh));
+  // the kernels' WIN flag: a launch without a window instantiates the code that never knew one
+  auto windowed = [&](auto launch) {
+    if (window > 0) launch(std::true_type{});
+    else launch(std::false_type{});
+  };
+  const int qb = tail ? 1 : qblocks;  // tail: only the query block that holds token 0 of every sequence
+  dim3 agrid(static_cast<unsigned>(n_seq * qb), static_cast<unsigned>(nh));
+  prof_begin(e, VR_PROF_ATTENTION, tail ? attn_flop / qblocks : attn_flop);
+  // f16 mode: one block per (sequence, head) with the sequence's K/V staged once in dynamic LDS (attention_seq_kernel)
+  // while the longest sequence's rows fit what a workgroup may have on this device; beyond that (max_pos admits up
+  // to 8192 tokens) attention_stream_kernel, which streams the keys in 64-row tiles through static LDS
+  const int lds_keys = (max_len + 15) & ~15;
+  const size_t lds_bytes = static_cast<size_t>(2) * lds_keys * dh * sizeof(half_t);
+  static size_t lds_limit = 0;
+  if (plain && lds_limit == 0) {
+    hipDeviceProp_t prop;
+    VR_HIP(hipGetDeviceProperties(&prop, e->device));
+    lds_limit = std::max(prop.sharedMemPerBlock, prop.sharedMemPerBlockOptin);
+  }
+  // (a windowed layer: the streamed kernel from enc->window_stream_from tokens on, see build_encoder)
+  if (plain && lds_bytes <= lds_limit && !(window > 0 && max_len >= enc->window_stream_from)) {
+    static size_t lds_allowed[2] = {0, 0};  // per instantiation: raised above the 64 KiB default when a sequence needs it
+    const int which = dh == 64 ? 0 : 1;
+    if (lds_bytes > 65536 && lds_bytes > lds_allowed[which]) {
+      for (const void* f : {reinterpret_cast<const void*>(&attention_seq_kernel<64, 4, false>),
+                            reinterpret_cast<const void*>(&attention_seq_kernel<64, 4, true>)})
+        if (dh == 64) VR_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_bytes)));
+      for (const void* f : {reinterpret_cast<const void*>(&attention_seq_kernel<32, 4, false>),
+                            reinterpret_cast<const void*>(&attention_seq_kernel<32, 4, true>)})
+        if (dh != 64) VR_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_bytes)));
+      lds_allowed[which] = lds_bytes;
+    }
+    const dim3 sgrid(static_cast<unsigned>(n_seq) * static_cast<unsigned>(nh));
+    const int q_limit = tail ? 16 : max_len;
+    windowed([&](auto W) {
+      constexpr bool kWin = decltype(W)::value;
+      if (dh == 64)
+        hipLaunchKernelGGL((attention_seq_kernel<64, 4, kWin>), sgrid, dim3(256), lds_bytes, s, reinterpret_cast<const half_t*>(enc->qkv),
+                           cu_dev, seq0, tok_base, H, scale, q_limit, lds_keys, ch, window);
+      else
+        hipLaunchKernelGGL((attention_seq_kernel<32, 4, kWin>), sgrid, dim3(256), lds_bytes, s, reinterpret_cast<const half_t*>(enc->qkv),
+                           cu_dev, seq0, tok_base, H, scale, q_limit, lds_keys, ch, window);
+    });
+  } else if (plain) {  // 128 queries per block
+    const int qb128 = tail ? 1 : (max_len + 127) / 128;
+    const dim3 sgrid(static_cast<unsigned>(n_seq) * static_cast<unsigned>(qb128) * static_cast<unsigned>(nh));
+    const int q_limit = tail ? 16 : max_len;
+    windowed([&](auto W) {
+      constexpr bool kWin = decltype(W)::value;
+      if (dh == 64)
+        hipLaunchKernelGGL((attention_stream_kernel<64, 4, kWin>), sgrid, dim3(256), 0, s, reinterpret_cast<const half_t*>(enc->qkv),
+                           cu_dev, seq0, tok_base, H, qb128, scale, q_limit, ch, window);
+      else
+        hipLaunchKernelGGL((attention_stream_kernel<32, 4, kWin>), sgrid, dim3(256), 0, s, reinterpret_cast<const half_t*>(enc->qkv),
+                           cu_dev, seq0, tok_base, H, qb128, scale, q_limit, ch, window);
+    });
+  } else {
+    windowed([&](auto W) {
+      constexpr bool kWin = decltype(W)::value;
+      if (dh == 64)
+        hipLaunchKernelGGL((attention_kernel<64, kWin>), agrid, dim3(256), 0, s, enc->qkv, cu_dev, seq0, tok_base, H, qb, scale,
+                           enc->ctx, ch, cl, window);
+      else
+        hipLaunchKernelGGL((attention_kernel<32, kWin>), agrid, dim3(256), 0, s, enc->qkv, cu_dev, seq0, tok_base, H, qb, scale,
+                           enc->ctx, ch, cl, window);
+    });
+  }
+  prof_end(e);
+  VR_HIP(hipGetLastError());
+  return 0;
+}
+
 // The checked spans of a span call: span_off on the host (forward_all cuts the span range of a forward chunk from it),
 // the (begin, end) pairs and the sequence index of every span on the device.
 struct Spans {
@@ -3890,6 +4064,166 @@ struct Spans {
   const int32_t* seq_dev = nullptr;
 };
 
+// The forward pass of a pre-norm model (VR_NORM_PRE: rotary positions, a gated FFN, optionally alternating global and
+// windowed attention — the ModernBERT family), forward_chunk's arguments:
+//   h = LN_emb(word[id]);  per layer  h += W_o attn(N_a(h)),  h += W_down(act(gate(N_m(h))) * up(N_m(h)));  out = N_f(h)
+// with N_a of layer 0 the identity, N_a of layer l > 0 in layer l - 1's output.LayerNorm slot, N_m in the layer's
+// attention.output.LayerNorm slot and N_f in the last layer's output.LayerNorm slot (include/voitta_engine.h). The
+// residual stream h is f32 and alternates between enc->x and enc->tmp: each projection back into it adds its residual
+// in the epilogue (EPI_BIAS_RESIDUAL) and writes the other buffer. Every projection's input is a LayerNorm of h,
+// written by a LayerNorm launch as the f16 / (hi, lo) / f32 rows the product reads — or, for a question (<= 16 rows in
+// f16 mode), computed inside the projection from h itself (launch_skinny_ln: a folded LayerNorm IS a pre-norm
+// projection), which keeps a question at the launch count of a post-norm rotary model. Rotation and gate run in the
+// skinny epilogues where forward_chunk runs them there (VR_ENCODE_FUSE=0: passes of their own). None of the post-norm
+// loop's LayerNorm folds apply: they exist to re-derive a LayerNorm output for the RESIDUAL, which here is h itself.
+static int forward_chunk_prenorm(vr_engine* e, Encoder* enc, const int32_t* ids_dev, const int32_t* cu_dev, int n_seq_total,
+                                 int seq0, int seq1, int tok_base, int T, int max_len, double attn_flop, float* out_dev,
+                                 const Spans* sp) {
+  const vr_bert_desc& d = enc->d;
+  const int H = d.hidden, I = d.intermediate, dh = H / d.heads, N1 = 2 * I;
+  hipStream_t s = e->stream;
+  const unsigned row_blocks = static_cast<unsigned>((T + 3) / 4);
+  const bool split = d.precision != VR_PRECISION_F32;
+  const bool plain = d.precision == VR_PRECISION_F16;
+  const int passes = plain ? 1 : 3;
+  // GEMM inputs, as in forward_chunk: the normalised rows in xs (f32 mode: in ctx, free until attention writes it and
+  // again behind the output projection), the context in ctx, the gated activation in ffn
+  half_t* xh = split ? reinterpret_cast<half_t*>(enc->xs) : nullptr;
+  half_t* xl = split && !plain ? xh + 8 : nullptr;
+  half_t* ch = split ? reinterpret_cast<half_t*>(enc->ctx) : nullptr;
+  half_t* cl = split && !plain ? ch + 8 : nullptr;
+  half_t* fh = split ? reinterpret_cast<half_t*>(enc->ffn) : nullptr;
+  half_t* fl = split && !plain ? fh + 8 : nullptr;
+  half_t* qkvh = reinterpret_cast<half_t*>(enc->qkv);
+  const int32_t* posidx = reinterpret_cast<const int32_t*>(enc->posidx);
+  float2* stat = reinterpret_cast<float2*>(enc->lnstat);  // (launch_skinny_ln stores the rows' statistics; nobody reads them)
+  const bool fuse = plain && enc->fuse;
+  const bool fold_ln = plain && skinny_ln_supported(T, 3 * H, H) && I % 16 == 0;
+  const bool fuse_rope = fuse && skinny_routed(T, 3 * H, H);
+  const bool fuse_glu = fuse && skinny_routed(T, N1, H);
+  const int glu_epi = d.ffn == VR_FFN_SWIGLU ? EPI_SWIGLU_F16 : EPI_GEGLU_F16;
+  // the [T, 2I] pre-activation of the unfused gate (never allocated during a graph capture: a shape runs eagerly first)
+  if (!fuse_glu && !enc->glu) {
+    const size_t rows = static_cast<size_t>(enc->ws_tokens);
+    VR_TRY(dev_alloc_copy(e, enc, nullptr, plain ? rows * I : rows * 2 * I, 0, &enc->glu));
+  }
+  half_t* gluh = reinterpret_cast<half_t*>(enc->glu);
+  // rows of h normalised by (g, b) -> the next product's input
+  auto norm_rows = [&](const float* h, const float* g, const float* b) {
+    if (plain && H % 256 == 0)
+      hipLaunchKernelGGL(layernorm_f16_kernel, dim3(row_blocks), dim3(256), 0, s, h, T, H, g, b, d.eps, static_cast<float*>(nullptr),
+                         xh, static_cast<float2*>(nullptr));
+    else
+      hipLaunchKernelGGL(layernorm_kernel, dim3(row_blocks), dim3(256), 0, s, h, T, H, g, b, d.eps, split ? nullptr : enc->ctx, xh,
+                         xl, static_cast<float2*>(nullptr));
+  };
+  hipLaunchKernelGGL(embed_ln_rotary_kernel, dim3(row_blocks), dim3(256), 0, s, ids_dev, cu_dev, n_seq_total, tok_base, T, H,
+                     d.vocab, enc->word, enc->type, enc->lng, enc->lnb, d.eps, enc->x, xh, xl, static_cast<float*>(nullptr),
+                     static_cast<float2*>(nullptr));
+  hipLaunchKernelGGL(positions_kernel, dim3(static_cast<unsigned>((T + 255) / 256)), dim3(256), 0, s, cu_dev, n_seq_total,
+                     tok_base, T, reinterpret_cast<int32_t*>(enc->posidx));
+  float* h = enc->x;      // the residual stream
+  float* other = enc->tmp;
+  const int n_seq = seq1 - seq0;
+  for (size_t li = 0; li < enc->layers.size(); ++li) {
+    const LayerWeights& w = enc->layers[li];
+    const bool global = d.window == 0 || li % static_cast<size_t>(d.global_every) == 0;
+    const float2* table = !global && enc->rope_local ? enc->rope_local : enc->rope;
+    // Q, K, V of N_a(h); layer 0 reads the embedding LayerNorm's rows as they are
+    const float* a32 = li == 0 ? h : enc->ctx;  // f32 mode: the product's input rows
+    const bool fold_a = fold_ln && li > 0;
+    if (fold_a) {
+      const LayerWeights& prev = enc->layers[li - 1];
+      if (fuse_rope)
+        VR_TRY(launch_skinny_ln(e, EPI_ROPE_F16, h, d.eps, stat,
+                                {.W = w.s_qkv_p, .bias = w.bqkv_p, .Ch = qkvh, .M = T, .N = 3 * H, .K = H, .ln_g = prev.ln2g,
+                                 .ln_b = prev.ln2b, .rope_tab = table, .rope_pos = posidx}));
+      else
+        VR_TRY(launch_skinny_ln(e, EPI_BIAS_F16, h, d.eps, stat,
+                                {.W = w.s_qkv, .bias = w.bqkv, .Ch = qkvh, .M = T, .N = 3 * H, .K = H, .ln_g = prev.ln2g,
+                                 .ln_b = prev.ln2b}));
+    } else {
+      if (li > 0) norm_rows(h, enc->layers[li - 1].ln2g, enc->layers[li - 1].ln2b);
+      if (fuse_rope)
+        VR_TRY(launch_gemm_f16x3(e, enc, EPI_ROPE_F16, {.A = xh, .W = w.s_qkv_p, .bias = w.bqkv_p, .Ch = qkvh, .M = T, .N = 3 * H,
+                                                        .K = H, .passes = 1, .rope_tab = table, .rope_pos = posidx}));
+      else if (plain)
+        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_F16, {.A = xh, .W = w.s_qkv, .bias = w.bqkv, .Ch = qkvh, .M = T, .N = 3 * H,
+                                                        .K = H, .passes = 1}));
+      else if (split)
+        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS, {.A = xh, .A_lo = xl, .W = w.s_qkv, .bias = w.bqkv, .C = enc->qkv, .M = T,
+                                                    .N = 3 * H, .K = H, .passes = passes}));
+      else
+        VR_TRY(launch_gemm(e, EPI_BIAS, a32, w.wqkv, w.bqkv, nullptr, enc->qkv, T, 3 * H, H));
+    }
+    if (!fuse_rope) {  // the rotation as a pass of its own, with the table of the layer's kind
+      if (plain)
+        hipLaunchKernelGGL(rope_kernel<half_t>, dim3(row_blocks), dim3(256), 0, s, qkvh, posidx, T, H, dh, table);
+      else
+        hipLaunchKernelGGL(rope_kernel<float>, dim3(row_blocks), dim3(256), 0, s, enc->qkv, posidx, T, H, dh, table);
+    }
+    // (the profiler's flop count of a windowed layer: at most 2 w + 1 keys per query, instead of the sequence's length)
+    const double layer_flop = global ? attn_flop : std::min(attn_flop, 4.0 * H * T * (2.0 * d.window + 1.0));
+    VR_TRY(launch_attention(e, enc, cu_dev, seq0, n_seq, tok_base, max_len, false, global ? 0 : d.window, layer_flop));
+    // h' = h + W_o ctx
+    if (split)
+      VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_RESIDUAL, {.A = ch, .A_lo = cl, .W = w.s_o, .bias = w.bo, .R = h, .C = other, .M = T,
+                                                           .N = H, .K = H, .passes = passes}));
+    else
+      VR_TRY(launch_gemm(e, EPI_BIAS_RESIDUAL, enc->ctx, w.wo, w.bo, h, other, T, H, H));
+    std::swap(h, other);
+    // the gated FFN of N_m(h)
+    if (fold_ln && fuse_glu) {
+      VR_TRY(launch_skinny_ln(e, glu_epi, h, d.eps, stat,
+                              {.W = w.s_1_p, .bias = w.b1_p, .Ch = fh, .M = T, .N = N1, .K = H, .ln_g = w.ln1g, .ln_b = w.ln1b}));
+    } else if (fold_ln) {
+      VR_TRY(launch_skinny_ln(e, EPI_BIAS_F16, h, d.eps, stat,
+                              {.W = w.s_1, .bias = w.b1, .Ch = gluh, .M = T, .N = N1, .K = H, .ln_g = w.ln1g, .ln_b = w.ln1b}));
+    } else {
+      norm_rows(h, w.ln1g, w.ln1b);
+      if (fuse_glu)
+        VR_TRY(launch_gemm_f16x3(e, enc, glu_epi, {.A = xh, .W = w.s_1_p, .bias = w.b1_p, .Ch = fh, .M = T, .N = N1, .K = H, .passes = 1}));
+      else if (plain)
+        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_F16, {.A = xh, .W = w.s_1, .bias = w.b1, .Ch = gluh, .M = T, .N = N1, .K = H,
+                                                        .passes = 1}));
+      else if (split)
+        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS, {.A = xh, .A_lo = xl, .W = w.s_1, .bias = w.b1, .C = enc->glu, .M = T, .N = N1,
+                                                    .K = H, .passes = passes}));
+      else
+        VR_TRY(launch_gemm(e, EPI_BIAS, enc->ctx, w.w1, w.b1, nullptr, enc->glu, T, N1, H));
+    }
+    if (!fuse_glu) {
+      const int64_t n8 = static_cast<int64_t>(T) * (I / 8);
+      const dim3 grid(static_cast<unsigned>((n8 + 255) / 256));
+      if (plain) hipLaunchKernelGGL((glu_kernel<half_t, 2>), grid, dim3(256), 0, s, gluh, n8, I, d.ffn, static_cast<float*>(nullptr), fh);
+      else if (split) hipLaunchKernelGGL((glu_kernel<float, 1>), grid, dim3(256), 0, s, enc->glu, n8, I, d.ffn, static_cast<float*>(nullptr), fh);
+      else hipLaunchKernelGGL((glu_kernel<float, 0>), grid, dim3(256), 0, s, enc->glu, n8, I, d.ffn, enc->ffn, static_cast<half_t*>(nullptr));
+    }
+    // h' = h + W_down act
+    if (split)
+      VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_RESIDUAL, {.A = fh, .A_lo = fl, .W = w.s_2, .bias = w.b2, .R = h, .C = other, .M = T,
+                                                           .N = H, .K = I, .passes = passes}));
+    else
+      VR_TRY(launch_gemm(e, EPI_BIAS_RESIDUAL, enc->ffn, w.w2, w.b2, h, other, T, H, I));
+    std::swap(h, other);
+  }
+  // the final norm writes the f32 rows pooling reads, into the buffer the stream is not in
+  const LayerWeights& last = enc->layers.back();
+  hipLaunchKernelGGL(layernorm_kernel, dim3(row_blocks), dim3(256), 0, s, h, T, H, last.ln2g, last.ln2b, d.eps, other,
+                     static_cast<half_t*>(nullptr), static_cast<half_t*>(nullptr), static_cast<float2*>(nullptr));
+  if (sp) {
+    const int span0 = sp->off[static_cast<size_t>(seq0)], n_spans = sp->off[static_cast<size_t>(seq1)] - span0;
+    if (n_spans > 0)
+      hipLaunchKernelGGL(span_pool_kernel, dim3(static_cast<unsigned>(n_spans)), dim3(256), 0, s, other, cu_dev, sp->tok_dev,
+                         sp->seq_dev, span0, tok_base, H, d.normalize, out_dev);
+  } else {
+    hipLaunchKernelGGL(pool_kernel, dim3(static_cast<unsigned>(n_seq)), dim3(256), 0, s, other, cu_dev, seq0, tok_base, H,
+                       d.pooling, d.normalize, 0, out_dev);
+  }
+  VR_HIP(hipGetLastError());
+  return 0;
+}
+
 // forward of sequences [seq0, seq1) whose tokens are ids_dev[tok_base .. tok_base + T). sp (or null): pool the spans
 // of these sequences, one row each at out_dev[span], instead of one row per sequence — the pass then runs as a
 // mean-pooled model's does, whatever the description's pooling says.
@@ -3897,6 +4231,8 @@ static int forward_chunk(vr_engine* e, Encoder* enc, const int32_t* ids_dev, con
                          const int32_t* seg_dev, int n_seq_total, int seq0, int seq1, int tok_base, int T, int max_len,
                          double attn_flop, float* out_dev, const Spans* sp = nullptr) {
   const vr_bert_desc& d = enc->d;
+  if (d.norm == VR_NORM_PRE)  // a routine of its own: none of the LayerNorm folds below applies to it
+    return forward_chunk_prenorm(e, enc, ids_dev, cu_dev, n_seq_total, seq0, seq1, tok_base, T, max_len, attn_flop, out_dev, sp);
   const int H = d.hidden, I = d.intermediate, nh = d.heads, dh = H / nh;
   hipStream_t s = e->stream;
   const unsigned row_blocks = static_cast<unsigned>((T + 3) / 4);
@@ -3956,8 +4292,6 @@ static int forward_chunk(vr_engine* e, Encoder* enc, const int32_t* ids_dev, con
                        tok_base, T, H, d.vocab, enc->word, enc->pos, enc->type, enc->lng, enc->lnb, d.eps,
                        lnfuse ? nullptr : enc->x, xh, xl, lnfuse ? enc->x : nullptr, lnfuse ? stat_b : nullptr,
                        static_cast<const int32_t*>(nullptr));
-  const int qblocks = (max_len + 63) / 64;
-  const float scale = 1.0f / sqrtf(static_cast<float>(dh));
   // Rotary positions and the gated FFN. UNFUSED: passes of their own behind the projections' existing epilogues —
   // rope_kernel in place on the Q and K thirds of the qkv rows, and the FFN-up projection (N = 2I, bias only) into
   // enc->glu followed by glu_kernel, which writes the rows the FFN-down projection reads. FUSED (f16 mode, products that
@@ -4045,58 +4379,7 @@ static int forward_chunk(vr_engine* e, Encoder* enc, const int32_t* ids_dev, con
     else
       VR_TRY(launch_gemm(e, EPI_BIAS, enc->x, w.wqkv, w.bqkv, nullptr, enc->qkv, T, 3 * H, H));
     rope();
-    const int qb = tail ? 1 : qblocks;  // tail: only the query block that holds token 0 of every sequence
-    dim3 agrid(static_cast<unsigned>(n_seq * qb), static_cast<unsigned>(nh));
-    prof_begin(e, VR_PROF_ATTENTION, tail ? attn_flop / qblocks : attn_flop);
-    // f16 mode: one block per (sequence, head) with the sequence's K/V staged once in dynamic LDS (attention_seq_kernel)
-    // while the longest sequence's rows fit what a workgroup may have on this device; beyond that (max_pos admits up
-    // to 8192 tokens) attention_stream_kernel, which streams the keys in 64-row tiles through static LDS
-    const int lds_keys = (max_len + 15) & ~15;
-    const size_t lds_bytes = static_cast<size_t>(2) * lds_keys * dh * sizeof(half_t);
-    static size_t lds_limit = 0;
-    if (plain && lds_limit == 0) {
-      hipDeviceProp_t prop;
-      VR_HIP(hipGetDeviceProperties(&prop, e->device));
-      lds_limit = std::max(prop.sharedMemPerBlock, prop.sharedMemPerBlockOptin);
-    }
-    if (plain && lds_bytes <= lds_limit) {
-      static size_t lds_allowed[2] = {0, 0};  // per instantiation: raised above the 64 KiB default when a sequence needs it
-      const int which = dh == 64 ? 0 : 1;
-      if (lds_bytes > 65536 && lds_bytes > lds_allowed[which]) {
-        if (dh == 64)
-          VR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_seq_kernel<64, 4>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_bytes)));
-        else
-          VR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&attention_seq_kernel<32, 4>),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_bytes)));
-        lds_allowed[which] = lds_bytes;
-      }
-      const dim3 sgrid(static_cast<unsigned>(n_seq) * static_cast<unsigned>(nh));
-      const int q_limit = tail ? 16 : max_len;
-      if (dh == 64)
-        hipLaunchKernelGGL((attention_seq_kernel<64, 4>), sgrid, dim3(256), lds_bytes, s, reinterpret_cast<const half_t*>(enc->qkv),
-                           cu_dev, seq0, tok_base, H, scale, q_limit, lds_keys, ch);
-      else
-        hipLaunchKernelGGL((attention_seq_kernel<32, 4>), sgrid, dim3(256), lds_bytes, s, reinterpret_cast<const half_t*>(enc->qkv),
-                           cu_dev, seq0, tok_base, H, scale, q_limit, lds_keys, ch);
-    } else if (plain) {  // 128 queries per block
-      const int qb128 = tail ? 1 : (max_len + 127) / 128;
-      const dim3 sgrid(static_cast<unsigned>(n_seq) * static_cast<unsigned>(qb128) * static_cast<unsigned>(nh));
-      const int q_limit = tail ? 16 : max_len;
-      if (dh == 64)
-        hipLaunchKernelGGL((attention_stream_kernel<64, 4>), sgrid, dim3(256), 0, s, reinterpret_cast<const half_t*>(enc->qkv),
-                           cu_dev, seq0, tok_base, H, qb128, scale, q_limit, ch);
-      else
-        hipLaunchKernelGGL((attention_stream_kernel<32, 4>), sgrid, dim3(256), 0, s, reinterpret_cast<const half_t*>(enc->qkv),
-                           cu_dev, seq0, tok_base, H, qb128, scale, q_limit, ch);
-    }
-    else if (dh == 64)
-      hipLaunchKernelGGL((attention_kernel<64>), agrid, dim3(256), 0, s, enc->qkv, cu_dev, seq0, tok_base, H,
-                         qb, scale, enc->ctx, ch, cl);
-    else
-      hipLaunchKernelGGL((attention_kernel<32>), agrid, dim3(256), 0, s, enc->qkv, cu_dev, seq0, tok_base, H,
-                         qb, scale, enc->ctx, ch, cl);
-    prof_end(e);
+    VR_TRY(launch_attention(e, enc, cu_dev, seq0, n_seq, tok_base, max_len, tail, 0, attn_flop));
     if (tail) {
       const unsigned gblocks = static_cast<unsigned>((n_seq + 3) / 4);
       const unsigned cblocks = gblocks;

@@ -61,8 +61,10 @@ def read_encoder_config(path: str) -> dict:
     kind = cfg.get("model_type", "bert")
     if kind == "nomic_bert":
         return _read_rope_config(path, cfg)
+    if kind == "modernbert":
+        return _read_modernbert_config(path, cfg)
     if kind not in ("bert", "xlm-roberta"):
-        raise ValueError(f"unsupported model_type {kind}: BERT, XLM-RoBERTa and nomic_bert encoders only")
+        raise ValueError(f"unsupported model_type {kind}: BERT, XLM-RoBERTa, nomic_bert and modernbert encoders only")
     if cfg.get("hidden_act", "gelu") != "gelu" or cfg.get("position_embedding_type", "absolute") != "absolute":
         raise ValueError("only exact-erf GELU and absolute position embeddings are implemented")
     pos_start = int(cfg.get("pad_token_id", 1)) + 1 if kind == "xlm-roberta" else 0
@@ -146,6 +148,63 @@ def _read_rope_config(path: str, cfg: dict) -> dict:
                          eps=cfg.get("layer_norm_eps", 1e-12),
                          precision=os.environ.get("VOITTA_ENCODER_PRECISION", "f16"), position="rotary",
                          rope_theta=float(rp.get("rope_theta", 1000.0)), ffn="swiglu" if act == "silu" else "geglu")
+    return {"desc": desc, "max_seq": max_seq, "pos_start": 0, "config": cfg}
+
+
+def _read_modernbert_config(path: str, cfg: dict) -> dict:
+    """model_type modernbert (transformers' ModernBertConfig, in the spelling of transformers 5 — rope_parameters per
+    attention kind, layer_types — or the older one — global_rope_theta / local_rope_theta): a pre-norm encoder with
+    rotary positions, GeGLU, and sliding-window attention in every layer that is not a multiple of
+    global_attn_every_n_layers. Query i of a windowed layer sees key j iff |i - j| <= local_attention // 2. Sequences
+    are capped at seq_cap() as for nomic_bert."""
+    H, heads, L = int(cfg["hidden_size"]), int(cfg["num_attention_heads"]), int(cfg["num_hidden_layers"])
+    act = cfg.get("hidden_activation", "gelu")
+    if act != "gelu":
+        raise ValueError(f"hidden_activation {act!r} is not implemented: a modernbert gate is the exact-erf GELU (GeGLU)")
+    if cfg.get("head_dim") not in (None, H // heads):
+        raise ValueError(f"head_dim {cfg['head_dim']} differs from hidden_size / num_attention_heads = {H // heads}: "
+                         "not implemented")
+    rp = cfg.get("rope_parameters") or {}
+    kinds = {"full_attention": ("global_rope_theta", 160000.0), "sliding_attention": ("local_rope_theta", 10000.0)}
+    theta = {}
+    for name, (old_key, default) in kinds.items():
+        part = rp.get(name) or {}
+        rope_type = part.get("rope_type", part.get("type", "default"))
+        if rope_type != "default" or cfg.get("rope_scaling"):
+            raise ValueError(f"rope type {rope_type!r} ({name}) is not implemented: only the default rotary embedding "
+                             "(no rope scaling)")
+        value = part.get("rope_theta", cfg.get(old_key, default))
+        theta[name] = None if value is None else float(value)
+    if theta["full_attention"] is None:
+        raise ValueError("global_rope_theta null is not implemented: the global layers need a rotary base")
+    if theta["sliding_attention"] is None:  # transformers: a null local_rope_theta means the global layers' base
+        theta["sliding_attention"] = theta["full_attention"]
+    every = int(cfg.get("global_attn_every_n_layers", 3))
+    if every < 1:
+        raise ValueError(f"global_attn_every_n_layers {every} must be >= 1")
+    pattern = ["full_attention" if i % every == 0 else "sliding_attention" for i in range(L)]
+    if cfg.get("layer_types") is not None and list(cfg["layer_types"]) != pattern:
+        raise ValueError("layer_types that are not 'every global_attn_every_n_layers-th layer is full_attention' are "
+                         f"not implemented (got {list(cfg['layer_types'])}, global_attn_every_n_layers = {every})")
+    window = int(cfg.get("local_attention", 128)) // 2
+    if not 0 <= window <= 4096:
+        raise ValueError(f"local_attention {cfg.get('local_attention')}: the engine's window half-width is 0..4096")
+    windowed = window > 0 and "sliding_attention" in pattern
+    declared = int(cfg.get("max_position_embeddings", 8192))
+    pooling, normalize, max_seq = _read_modules(path, declared)
+    max_seq = min(max_seq, declared)
+    cap = seq_cap()
+    if max_seq > cap:
+        logger.warning("%s declares sequences of up to %d tokens; the engine runs at most %d: longer texts are "
+                       "truncated to %d tokens (%s raises the cap, up to %d)", path, max_seq, cap, cap, SEQ_CAP_VARIABLE,
+                       MAX_SEQ_LENGTH_LIMIT)
+        max_seq = cap
+    desc = _enc.BertDesc(layers=L, hidden=H, heads=heads, intermediate=int(cfg["intermediate_size"]),
+                         vocab=int(cfg["vocab_size"]), max_pos=max_seq, type_vocab=1, pooling=pooling, normalize=normalize,
+                         eps=float(cfg.get("norm_eps", 1e-5)), precision=os.environ.get("VOITTA_ENCODER_PRECISION", "f16"),
+                         position="rotary", rope_theta=theta["full_attention"], ffn="geglu", norm="pre",
+                         window=window if windowed else 0, global_every=every if windowed else 0,
+                         rope_theta_local=theta["sliding_attention"] if windowed else 0.0)
     return {"desc": desc, "max_seq": max_seq, "pos_start": 0, "config": cfg}
 
 

@@ -70,6 +70,10 @@ class BertDesc:
     position: str = "learned"  # "learned" (a position table) | "rotary" (max_pos = length of the cos/sin table)
     rope_theta: float = 0.0
     ffn: str = "gelu"  # "gelu" | "swiglu" | "geglu" (down(act(gate(x)) * up(x)), act = SiLU / exact GELU)
+    norm: str = "post"  # "post" (x = LN(x + f(x))) | "pre" (x = x + f(LN(x)), a final LayerNorm: the ModernBERT family)
+    window: int = 0  # sliding-window attention: query i of a windowed layer sees key j iff |i - j| <= window; 0 = none
+    global_every: int = 0  # window > 0: layer l attends globally iff l % global_every == 0
+    rope_theta_local: float = 0.0  # the rotary base of the windowed layers; 0 = rope_theta
 
     @property
     def rotary(self) -> bool:
@@ -78,6 +82,10 @@ class BertDesc:
     @property
     def gated(self) -> bool:
         return self.ffn != "gelu"
+
+    @property
+    def prenorm(self) -> bool:
+        return self.norm == "pre"
 
     def to_c(self) -> _lib.VrBertDesc:
         d = _lib.VrBertDesc()
@@ -98,6 +106,11 @@ class BertDesc:
         if self.ffn not in ffns:
             raise ValueError(f"unknown ffn kind {self.ffn!r}")
         d.position, d.rope_theta, d.ffn = positions[self.position], float(self.rope_theta), ffns[self.ffn]
+        norms = {"post": _lib.VR_NORM_POST, "pre": _lib.VR_NORM_PRE}
+        if self.norm not in norms:
+            raise ValueError(f"unknown norm placement {self.norm!r}")
+        d.norm, d.window, d.global_every = norms[self.norm], int(self.window), int(self.global_every)
+        d.rope_theta_local = float(self.rope_theta_local)
         return d
 
 
@@ -117,7 +130,8 @@ def rope_tensor_names(layers: int) -> list:
 
 
 def names_for(desc: "BertDesc") -> list:
-    """Tensor names by family: BERT / XLM-RoBERTa state-dict names, or the rotary gated family's."""
+    """Tensor names by family: BERT / XLM-RoBERTa state-dict names, or the rotary gated family's (a pre-norm model's
+    state is brought to those by modernbert_slots, which also knows which biases it has)."""
     if desc.rotary != desc.gated:
         raise ValueError("checkpoints are read for BERT-style (learned positions, GELU) and nomic-style (rotary, gated "
                          f"FFN) encoders; got position={desc.position!r} with ffn={desc.ffn!r}")
@@ -142,6 +156,76 @@ def native_rope_state(state: dict) -> dict:
     return out
 
 
+# A pre-norm encoder (model_type modernbert) in the slot order of vr_encoder_load. Every slot is named here — these
+# checkpoints may carry biases (attention_bias, mlp_bias, norm_bias) — under the rotary family's native names, which
+# modernbert_slots maps a ModernBertModel state dict to.
+PRENORM_LAYER_SUFFIXES = [
+    "self_attn.q_proj.weight", "self_attn.q_proj.bias", "self_attn.k_proj.weight", "self_attn.k_proj.bias",
+    "self_attn.v_proj.weight", "self_attn.v_proj.bias", "self_attn.o_proj.weight", "self_attn.o_proj.bias",
+    "post_attention_layernorm.weight", "post_attention_layernorm.bias",
+    "mlp.up_proj.weight", "mlp.up_proj.bias", "mlp.down_proj.weight", "mlp.down_proj.bias",
+    "post_mlp_layernorm.weight", "post_mlp_layernorm.bias",
+    "mlp.gate_proj.weight", "mlp.gate_proj.bias",
+]
+
+
+def modernbert_slots(state: dict, desc: "BertDesc"):
+    """A transformers ModernBertModel state dict (any key prefix) -> (slot names, state under those names).
+    Under VR_NORM_PRE a LayerNorm slot holds the norm that follows the residual add it sits behind: layer l's
+    post_attention_layernorm is layers.l.mlp_norm, its post_mlp_layernorm is layers.l+1.attn_norm — final_norm for the
+    last layer — and layers.0 has no attn_norm (the embedding norm's rows go straight into its attention). attn.Wqkv is
+    split in thirds (query, key, value); mlp.Wi in halves: rows [0, I) are what the activation is applied to (the GATE),
+    rows [I, 2I) the UP projection. What these checkpoints lack is filled in here: zeros for an absent LayerNorm shift,
+    a [1, H] zero table for the token types; an absent projection bias stays an empty (NULL) slot."""
+    H, inter, L = desc.hidden, desc.intermediate, desc.layers
+
+    def get(name, optional=False):
+        hits = [k for k in state if k == name or k.endswith("." + name)]
+        if not hits and optional:
+            return None
+        if len(hits) != 1:
+            raise KeyError(f"weight '{name}' not found (or ambiguous) in state dict: {hits[:3]}")
+        return state[hits[0]]
+
+    def rows(t, name, parts):
+        if t.shape[0] % parts:
+            raise ValueError(f"weight '{name}' has {t.shape[0]} rows, not {parts} equal parts")
+        n = t.shape[0] // parts
+        return [t[j * n:(j + 1) * n] for j in range(parts)]
+
+    zeros_h = np.zeros(H, np.float32)
+    out = {"embeddings.word_embeddings.weight": get("embeddings.tok_embeddings.weight"),
+           "embeddings.token_type_embeddings.weight": np.zeros((1, H), np.float32)}
+
+    def norm(dst, src):
+        out[dst + ".weight"] = get(src + ".weight")
+        b = get(src + ".bias", optional=True)
+        out[dst + ".bias"] = zeros_h if b is None else b
+
+    norm("embeddings.LayerNorm", "embeddings.norm")
+    for i in range(L):
+        p = f"layers.{i}."
+        for kind in ("weight", "bias"):
+            t = get(p + "attn.Wqkv." + kind, optional=kind == "bias")
+            if t is not None:
+                for part, name in zip(rows(t, p + "attn.Wqkv." + kind, 3), ("q_proj", "k_proj", "v_proj")):
+                    out[p + "self_attn." + name + "." + kind] = part
+            t = get(p + "mlp.Wi." + kind, optional=kind == "bias")
+            if t is not None:
+                out[p + "mlp.gate_proj." + kind], out[p + "mlp.up_proj." + kind] = rows(t, p + "mlp.Wi." + kind, 2)
+            for dst, src in (("self_attn.o_proj", "attn.Wo"), ("mlp.down_proj", "mlp.Wo")):
+                t = get(p + src + "." + kind, optional=kind == "bias")
+                if t is not None:
+                    out[p + dst + "." + kind] = t
+        norm(p + "post_attention_layernorm", p + "mlp_norm")
+        norm(p + "post_mlp_layernorm", f"layers.{i + 1}.attn_norm" if i + 1 < L else "final_norm")
+    names = ["embeddings.word_embeddings.weight", None, "embeddings.token_type_embeddings.weight",
+             "embeddings.LayerNorm.weight", "embeddings.LayerNorm.bias"]
+    for i in range(L):
+        names += [n if n in out else None for n in (f"layers.{i}.{s}" for s in PRENORM_LAYER_SUFFIXES)]
+    return names, out
+
+
 # a BertForSequenceClassification's head, after the encoder's tensors (vr_reranker_load)
 HEAD_NAMES = ["pooler.dense.weight", "pooler.dense.bias", "classifier.weight", "classifier.bias"]
 
@@ -155,6 +239,7 @@ def expected_shape(desc: BertDesc, name: str) -> tuple:
     if name.endswith("position_embeddings.weight"): return (desc.max_pos, H)
     if name.endswith("token_type_embeddings.weight"): return (desc.type_vocab, H)
     if name.endswith("mlp.up_proj.weight") or name.endswith("mlp.gate_proj.weight"): return (inter, H)
+    if name.endswith("mlp.up_proj.bias") or name.endswith("mlp.gate_proj.bias"): return (inter,)
     if name.endswith("mlp.down_proj.weight"): return (H, inter)
     if name.endswith("intermediate.dense.weight"): return (inter, H)
     if name.endswith("intermediate.dense.bias"): return (inter,)
@@ -175,9 +260,13 @@ def _find(state: dict, suffix: str):
 def load_encoder(engine, desc: BertDesc, state: dict) -> None:
     """state: HF BertModel state dict (any key prefix), values NumPy arrays or torch tensors.
     Tensors on the engine's GPU are passed as device pointers, everything else as host memory."""
-    if desc.rotary or desc.gated:
-        state = native_rope_state(state)
-    _load(engine, desc, state, names_for(desc), engine._lib.vr_encoder_load)
+    if desc.prenorm:
+        names, state = modernbert_slots(state, desc)
+    else:
+        if desc.rotary or desc.gated:
+            state = native_rope_state(state)
+        names = names_for(desc)
+    _load(engine, desc, state, names, engine._lib.vr_encoder_load)
     engine.encoder_desc = desc
 
 
