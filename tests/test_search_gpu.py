@@ -53,12 +53,18 @@ def test_store_and_dense_search_bit_exact(gpu, dim, n):
     q = rng.standard_normal((21, dim)).astype(np.float32)
     q[3] = x[17]  # exact duplicate of a stored row
     want_scores = ocore.dense_scores(ocore.cosine_preprocess(q), want_x)
-    for k in (1, 10, 30, 64, 70):  # <= 64: fused scan+select; above: score array + select kernels
+    # 21 queries run as blocks of 16 and 5: more than 4 queries take the score array + select kernels at every k.
+    # The first three alone take the fused scan + select for k <= 64 (the score array + select kernels above).
+    for k in (1, 10, 30, 64, 70):
         got = e.search_dense(q, k)
+        few = e.search_dense(q[:3], k)
         for i in range(q.shape[0]):
             wr, ws = ocore.topk(want_scores[i], k)
             assert np.array_equal(got[i][0], wr), (dim, n, k, i)
             assert np.array_equal(got[i][1].view(np.uint32), ws.view(np.uint32))
+            if i < 3:
+                assert np.array_equal(few[i][0], wr), (dim, n, k, i)
+                assert np.array_equal(few[i][1].view(np.uint32), ws.view(np.uint32))
     e.close()
 
 
