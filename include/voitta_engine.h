@@ -159,7 +159,8 @@ typedef struct vr_bert_desc {
 #define VR_FFN_GEGLU  2
 /* norm: POST is BERT's x = LN(x + f(x)). PRE is x = x + attn(LN(x)), x = x + mlp(LN(x)) with one final LayerNorm; the
  * embedding LayerNorm stays in the stream and layer 0 has no attention norm. PRE needs VR_POS_ROTARY and a gated ffn;
- * a window needs VR_NORM_PRE (and so rotary positions). A reranker takes neither. */
+ * a window needs VR_NORM_PRE (and so rotary positions). A reranker takes them together (a ModernBERT cross-encoder, see
+ * vr_reranker_load) or not at all. */
 #define VR_NORM_POST 0
 #define VR_NORM_PRE  1
 
@@ -283,6 +284,35 @@ int vr_unigram_encode_pairs(const vr_unigram* t, const char* const* a_texts, con
                             const char* const* b_texts, const int64_t* b_lens, int64_t n, int32_t max_len,
                             int64_t* out_offsets, int32_t* out_ids, int32_t* out_seg_b, int64_t capacity,
                             int64_t* needed);
+
+/* Host-only byte-level BPE tokenizer (ModernBERT: gte-modernbert-base, modernbert-embed-base, gte-reranker-modernbert),
+ * matching HF tokenizers as such a tokenizer.json configures it, in its order:
+ *   1. added tokens WITHOUT VR_ADDED_NORMALIZED (the specials) matched in the raw text, leftmost-longest, flags as above;
+ *   2. the normalizer: NFC (nfc != 0: canonical decomposition, reordering, composition incl. Hangul, the composition
+ *      exclusions honoured; tables of the Unicode version named in csrc/bpe_tables.inc) or none;
+ *   3. added tokens WITH VR_ADDED_NORMALIZED matched in the normalised text (runs of spaces in ModernBERT's vocabulary);
+ *   4. ByteLevel(add_prefix_space=false, use_regex=true): the GPT-2 split
+ *      's|'t|'re|'ve|'m|'ll|'d| ?\p{L}+| ?\p{N}+| ?[^\s\p{L}\p{N}]+|\s+(?!\S)|\s+  (case-sensitive), then every byte of
+ *      a piece as its code point of the 256-entry byte alphabet;
+ *   5. BPE per piece: the lowest-rank merge first, the leftmost among equals; a symbol absent from the vocabulary
+ *      becomes unk_id, or is dropped when unk_id is -1;
+ *   6. cls ids sep / cls A sep B sep.
+ * vocab[n_vocab]: NUL-terminated UTF-8 tokens, the index is the id. merges: n_merges (left, right) token pairs in rank
+ * order, merge_left[i] + merge_right[i] must be in the vocabulary. Read-only after creation and thread-safe. */
+typedef struct vr_bpe vr_bpe;
+#define VR_ADDED_NORMALIZED 8
+int vr_bpe_create(const char* const* vocab, int32_t n_vocab, const char* const* merge_left, const char* const* merge_right,
+                  int32_t n_merges, int32_t unk_id, int32_t cls_id, int32_t sep_id, int32_t nfc, const char* const* added,
+                  const int32_t* added_ids, const int32_t* added_flags, int32_t n_added, vr_bpe** out);
+void vr_bpe_destroy(vr_bpe* t);
+/* As vr_wordpiece_encode: cls ids... sep, the ids truncated on the right to max_len - 2; max_len >= 2. */
+int vr_bpe_encode(const vr_bpe* t, const char* const* texts, const int64_t* text_lens, int64_t n_texts, int32_t max_len,
+                  int64_t* out_offsets, int32_t* out_ids, int64_t capacity, int64_t* needed);
+/* As vr_wordpiece_encode_pairs: cls A sep B sep, truncated LongestFirst to max_len - 3 ids of A and B together;
+ * out_seg_b[i] is the index of the first id of B; max_len >= 3. */
+int vr_bpe_encode_pairs(const vr_bpe* t, const char* const* a_texts, const int64_t* a_lens, const char* const* b_texts,
+                        const int64_t* b_lens, int64_t n, int32_t max_len, int64_t* out_offsets, int32_t* out_ids,
+                        int32_t* out_seg_b, int64_t capacity, int64_t* needed);
 
 /* ---- BM25 document side: replaces SparseTextEmbedding("Qdrant/bm25").embed's token-count / TF
  * weighting (sparse_embedding.py:25,49; scripts/build_sparse_vectors.py:124,170) -- */
@@ -591,7 +621,20 @@ int vr_query_text_unigram(vr_engine* e, const vr_unigram* tokenizer, const char*
                           double sparse_weight, int32_t fusion, const vr_filter* filter,
                           int64_t* out_rows, double* out_scores, int32_t* out_from_dense, int32_t* out_count,
                           int32_t* out_hybrid);
+/* ... and with a byte-level BPE tokenizer (vr_bpe_encode). */
+int vr_query_text_bpe(vr_engine* e, const vr_bpe* tokenizer, const char* dense_text, int64_t dense_len,
+                          const char* sparse_text, int64_t sparse_len, int32_t max_len, int32_t limit,
+                          double sparse_weight, int32_t fusion, const vr_filter* filter,
+                          int64_t* out_rows, double* out_scores, int32_t* out_from_dense, int32_t* out_count,
+                          int32_t* out_hybrid);
 int vr_query_text_batch_unigram(vr_engine* e, const vr_unigram* tokenizer, int32_t n, const char* const* dense_texts,
+                                const int64_t* dense_lens, const char* const* sparse_texts, const int64_t* sparse_lens,
+                                int32_t max_len, const int32_t* limits, const double* sparse_weights, int32_t fusion,
+                                const vr_filter* filters, int32_t n_filters, const int32_t* filter_of_query,
+                                int32_t out_stride, int64_t* out_rows, double* out_scores, int32_t* out_from_dense,
+                                int32_t* out_counts, int32_t* out_hybrid, float* out_embeddings);
+/* ... and with a byte-level BPE tokenizer (vr_bpe_encode). */
+int vr_query_text_batch_bpe(vr_engine* e, const vr_bpe* tokenizer, int32_t n, const char* const* dense_texts,
                                 const int64_t* dense_lens, const char* const* sparse_texts, const int64_t* sparse_lens,
                                 int32_t max_len, const int32_t* limits, const double* sparse_weights, int32_t fusion,
                                 const vr_filter* filters, int32_t n_filters, const int32_t* filter_of_query,
@@ -608,11 +651,19 @@ int vr_query_text_batch_unigram(vr_engine* e, const vr_unigram* tokenizer, int32
  * classifier.dense / classifier.out_proj as the four head tensors, type_vocab 1, and its position table from row
  * pad_token_id + 1 on (max_pos = max_position_embeddings - pad_token_id - 1). The model gets
  * its own weights, workspace and graph cache, is replaced by the next load and freed with the engine; loading it never
- * touches the embedder. */
+ * touches the embedder.
+ * A ModernBERT cross-encoder (ModernBertForSequenceClassification with one label: gte-reranker-modernbert-base): a
+ * description with norm VR_NORM_PRE, position VR_POS_ROTARY and a gated ffn, with window / global_every / both thetas as
+ * vr_encoder_load takes them, type_vocab 1, normalize 0, pooling VR_POOL_CLS or VR_POOL_MEAN (config.json's
+ * classifier_pooling) over the final norm's rows. Its tensors are vr_encoder_load's 5 + 18 L followed by 6: head.dense.weight
+ * [H,H], head.dense.bias [H], head.norm.weight [H], head.norm.bias [H], classifier.weight [1,H], classifier.bias [1]
+ * (zeros where the checkpoint has no head.dense.bias or no head.norm.bias; none may be NULL). Its logit is
+ * wc . LN(gelu(Wd p + bd)) + bc: p the pooled row, gelu the exact-erf one, LN with the description's eps. Any other
+ * mix of norm, window, position and ffn is refused. */
 int vr_reranker_load(vr_engine* e, const vr_bert_desc* desc, const void* const* tensors, int32_t n_tensors, int mem);
 
 /* One logit per (question, passage) pair: logit = wc . tanh(Wp h_CLS + bp) + bc, h_CLS the last hidden state of the
- * pair's [CLS] token. ids / offsets as vr_encode (pair sequences, e.g. from vr_wordpiece_encode_pairs); seg_b[n_seq]
+ * pair's [CLS] token (a ModernBERT cross-encoder: its own head, see vr_reranker_load). ids / offsets as vr_encode (pair sequences, e.g. from vr_wordpiece_encode_pairs); seg_b[n_seq]
  * int32: tokens at positions >= seg_b[i] of sequence i are segment B (token type 1), 1 <= seg_b[i] <= its length. A
  * model with one token type (type_vocab 1, XLM-R) has no segment B: seg_b may be NULL and is ignored. All three in
  * `mem`; out_logits: n_seq f32 in `out_mem`. The head runs in f32 whatever the precision, in a fixed order:
@@ -631,6 +682,10 @@ int vr_rerank_text(vr_engine* e, const vr_wordpiece* tokenizer, int32_t n_querie
 int vr_rerank_text_unigram(vr_engine* e, const vr_unigram* tokenizer, int32_t n_queries, const char* const* queries,
                            const int64_t* query_lens, const int64_t* cand_off, const char* const* passages,
                            const int64_t* passage_lens, int32_t max_len, float* out_logits);
+/* The same with a byte-level BPE tokenizer (vr_bpe_encode_pairs, max_len >= 3). */
+int vr_rerank_text_bpe(vr_engine* e, const vr_bpe* tokenizer, int32_t n_queries, const char* const* queries,
+                       const int64_t* query_lens, const int64_t* cand_off, const char* const* passages,
+                       const int64_t* passage_lens, int32_t max_len, float* out_logits);
 
 /* Persistence. The reference's index survives a restart in Qdrant's volume
  * (docker-compose.yml:8-9; VectorStoreService._ensure_collection re-attaches, vector_store.py:75-115).

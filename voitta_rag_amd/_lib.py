@@ -120,6 +120,13 @@ SIGNATURES = {
                                    _i64p]),
     "vr_unigram_encode_pairs": (C.c_int, [_vp, C.POINTER(C.c_char_p), _i64p, C.POINTER(C.c_char_p), _i64p, C.c_int64,
                                          C.c_int32, _i64p, _i32p, _i32p, C.c_int64, _i64p]),
+    "vr_bpe_create": (C.c_int, [C.POINTER(C.c_char_p), C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_int32,
+                               C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_char_p), _i32p, _i32p, C.c_int32,
+                               C.POINTER(_vp)]),
+    "vr_bpe_destroy": (None, [_vp]),
+    "vr_bpe_encode": (C.c_int, [_vp, C.POINTER(C.c_char_p), _i64p, C.c_int64, C.c_int32, _i64p, _i32p, C.c_int64, _i64p]),
+    "vr_bpe_encode_pairs": (C.c_int, [_vp, C.POINTER(C.c_char_p), _i64p, C.POINTER(C.c_char_p), _i64p, C.c_int64,
+                                     C.c_int32, _i64p, _i32p, _i32p, C.c_int64, _i64p]),
     "vr_chunk_texts": (C.c_int, [C.POINTER(C.c_char_p), _i64p, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
                                 C.POINTER(_vp)]),
     "vr_chunks_view": (C.c_int, [_vp, _i64p, C.POINTER(_i64p), C.POINTER(_i64p), C.POINTER(_i64p),
@@ -176,15 +183,22 @@ SIGNATURES = {
                                       _i64p, _dp, _i32p, _i32p, _i32p, _fp]),
     "vr_query_text_unigram": (C.c_int, [_vp, _vp, C.c_char_p, C.c_int64, C.c_char_p, C.c_int64, C.c_int32, C.c_int32,
                                         C.c_double, C.c_int32, C.POINTER(VrFilter), _i64p, _dp, _i32p, _i32p, _i32p]),
+    "vr_query_text_bpe": (C.c_int, [_vp, _vp, C.c_char_p, C.c_int64, C.c_char_p, C.c_int64, C.c_int32, C.c_int32,
+                                    C.c_double, C.c_int32, C.POINTER(VrFilter), _i64p, _dp, _i32p, _i32p, _i32p]),
     "vr_query_text_batch_unigram": (C.c_int, [_vp, _vp, C.c_int32, C.POINTER(C.c_char_p), _i64p, C.POINTER(C.c_char_p),
                                               _i64p, C.c_int32, _i32p, _dp, C.c_int32, C.POINTER(VrFilter), C.c_int32,
                                               _i32p, C.c_int32, _i64p, _dp, _i32p, _i32p, _i32p, _fp]),
+    "vr_query_text_batch_bpe": (C.c_int, [_vp, _vp, C.c_int32, C.POINTER(C.c_char_p), _i64p, C.POINTER(C.c_char_p),
+                                          _i64p, C.c_int32, _i32p, _dp, C.c_int32, C.POINTER(VrFilter), C.c_int32,
+                                          _i32p, C.c_int32, _i64p, _dp, _i32p, _i32p, _i32p, _fp]),
     "vr_reranker_load": (C.c_int, [_vp, C.POINTER(VrBertDesc), C.POINTER(_vp), C.c_int32, C.c_int]),
     "vr_rerank": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, C.c_int, _vp, C.c_int]),
     "vr_rerank_text": (C.c_int, [_vp, _vp, C.c_int32, C.POINTER(C.c_char_p), _i64p, _i64p, C.POINTER(C.c_char_p), _i64p,
                                  C.c_int32, _fp]),
     "vr_rerank_text_unigram": (C.c_int, [_vp, _vp, C.c_int32, C.POINTER(C.c_char_p), _i64p, _i64p, C.POINTER(C.c_char_p),
                                          _i64p, C.c_int32, _fp]),
+    "vr_rerank_text_bpe": (C.c_int, [_vp, _vp, C.c_int32, C.POINTER(C.c_char_p), _i64p, _i64p, C.POINTER(C.c_char_p),
+                                     _i64p, C.c_int32, _fp]),
 }
 
 

@@ -293,6 +293,14 @@ int vr_rerank_text_unigram(vr_engine* e, const vr_unigram* tokenizer, int32_t n_
                      max_len, out_logits);
 }
 
+int vr_rerank_text_bpe(vr_engine* e, const vr_bpe* tokenizer, int32_t n_queries, const char* const* queries,
+                           const int64_t* query_lens, const int64_t* cand_off, const char* const* passages,
+                           const int64_t* passage_lens, int32_t max_len, float* out_logits) {
+  VR_CHECK(max_len >= 3, "max_len %d cannot hold the three special tokens of a pair", max_len);
+  return rerank_text(e, vr::as_tokenizer(tokenizer), n_queries, queries, query_lens, cand_off, passages, passage_lens,
+                     max_len, out_logits);
+}
+
 }  // extern "C"
 
 // Body of vr_upsert, also the last stage of index_batch. Caller holds e->wmu and the exclusive lock.

@@ -16,6 +16,7 @@
 //   layernorm_kernel  LayerNorm over H                               HBM bound
 //   pool_kernel       mean / CLS pooling + L2 normalise              HBM bound
 //   rerank_head_kernel cross-encoder head on the pooled [CLS] rows   one f32 logit per pair (encoder_rerank)
+//   rerank_head_ln_kernel the head of a pre-norm cross-encoder: dense, GELU, LayerNorm, classifier (encoder_rerank)
 //   rope_kernel       rotary positions, in place on Q and K            HBM bound (VR_POS_ROTARY models only)
 //   glu_kernel        act(gate) * up of a gated FFN                    HBM bound (VR_FFN_SWIGLU / VR_FFN_GEGLU only)
 // Algorithmic FLOP per token = L * (24 H^2 + 4 S H), of which the GEMMs are
@@ -85,7 +86,10 @@ struct Encoder {
   std::vector<int32_t> span_seq_host;
   DevArray<float> out;
   // a cross-encoder (the reranker slot): pooler dense [H,H] + bias, classifier [1,H] + bias; the pooled [CLS] rows
+  // (a pre-norm one, ModernBertForSequenceClassification: pool_w / pool_b are its head.dense, head_ln_g / head_ln_b its
+  // head.norm, and the pooled rows are CLS or mean rows of the final norm; null head_ln_g: the tanh pooler head)
   float *pool_w = nullptr, *pool_b = nullptr, *cls_w = nullptr, *cls_b = nullptr;
+  float *head_ln_g = nullptr, *head_ln_b = nullptr;
   DevArray<float> rows;
   DevArray<float> skinny_ws;  // K-slice partial sums of gemm_f16_skinny_kernel
   // hipGraphs of small forward passes (a query, a handful of sequences): ~135 launches of a few
@@ -563,6 +567,106 @@ __global__ __launch_bounds__(256) void rerank_head_kernel(const float* __restric
   __syncthreads();
   const int t = threadIdx.x;
   if (t < 16 && p0 + t < n) out[p0 + t] = bc[0] + red[0][t] + red[1][t] + red[2][t] + red[3][t];
+}
+
+constexpr int kHeadTiles = 16;  // 16-unit tiles of the head's dense layer per wave: H / 64, H <= 1024
+
+// The head of a pre-norm cross-encoder (ModernBertForSequenceClassification) on n pooled rows [n, H]:
+// out[i] = wc . LN(gelu(Wd p_i + bd)) + bc, gelu the exact-erf one, LN over all H units with gain g, shift b and eps,
+// all f32. The dense layer runs as rerank_head_kernel's does: one block of 4 waves per 16 rows, wave w takes the
+// 16-unit tiles w, w + 4, ... on v_mfma_f32_16x16x4_f32, Wd read once per 16 rows. A row's H activations then sit in
+// registers, 4 rows x H/64 tiles per lane, and three sums over them follow, each in the same fixed order — per lane over
+// its tiles, a xor butterfly across the 16 lanes of a row group, then the four waves in order through LDS: the mean,
+// the centred sum of squares (two passes: no cancellation), and the dot of the normalised units with wc. No atomics;
+// a row's arithmetic never meets another row's, so its bits depend neither on n nor on its place among the 16.
+__global__ __launch_bounds__(256) void rerank_head_ln_kernel(const float* __restrict__ rows, int n, int H,
+                                                             const float* __restrict__ wd, const float* __restrict__ bd,
+                                                             const float* __restrict__ g, const float* __restrict__ b,
+                                                             float eps, const float* __restrict__ wc,
+                                                             const float* __restrict__ bc, float* __restrict__ out) {
+  __shared__ float red[3][4][16];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int r = lane & 15, q = lane >> 4;
+  const int p0 = blockIdx.x * 16;
+  const bool live = p0 + r < n;
+  const float* a_row = rows + static_cast<int64_t>(live ? p0 + r : p0) * H;
+  const int tiles = H / 16;
+  float act[kHeadTiles][4];
+#pragma unroll
+  for (int t = 0; t < kHeadTiles; ++t) {
+    const int jt = wave + 4 * t;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) act[t][i] = 0.0f;
+    if (jt < tiles) {
+      const float* w_row = wd + static_cast<int64_t>(jt * 16 + r) * H;
+      f32x4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
+      for (int k0 = 0; k0 < H; k0 += 16) {
+        const float4 a = live ? *reinterpret_cast<const float4*>(a_row + k0 + 4 * q) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        const float4 w = *reinterpret_cast<const float4*>(w_row + k0 + 4 * q);
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, w.x, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, w.y, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, w.z, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, w.w, acc, 0, 0, 0);
+      }
+      const float bj = bd[jt * 16 + r];  // D: column (unit) lane & 15, row (pair) 4 q + i
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const float v = acc[i] + bj;
+        act[t][i] = 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
+      }
+    }
+  }
+  // the sum of part[i] over all H units of row 4 q + i, the same bits in every lane of the block that holds the row
+  auto row_sums = [&](float (&part)[4], int slot) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int off = 1; off < 16; off <<= 1) part[i] += __shfl_xor(part[i], off);
+    if (r == 0)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) red[slot][wave][4 * q + i] = part[i];
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      part[i] = red[slot][0][4 * q + i] + red[slot][1][4 * q + i] + red[slot][2][4 * q + i] + red[slot][3][4 * q + i];
+  };
+  const float inv_h = 1.0f / static_cast<float>(H);
+  float mean[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+  for (int t = 0; t < kHeadTiles; ++t)  // (tiles past H / 16 hold zeros)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) mean[i] += act[t][i];
+  row_sums(mean, 0);
+  float inv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) mean[i] *= inv_h;
+#pragma unroll
+  for (int t = 0; t < kHeadTiles; ++t)
+    if (wave + 4 * t < tiles)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        act[t][i] -= mean[i];
+        inv[i] += act[t][i] * act[t][i];
+      }
+  row_sums(inv, 1);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) inv[i] = 1.0f / sqrtf(inv[i] * inv_h + eps);
+  float part[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+  for (int t = 0; t < kHeadTiles; ++t) {
+    const int jt = wave + 4 * t;
+    if (jt < tiles) {
+      const int j = jt * 16 + r;
+      const float gj = g[j], sj = b[j], cj = wc[j];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) part[i] += (act[t][i] * inv[i] * gj + sj) * cj;
+    }
+  }
+  row_sums(part, 2);
+  if (wave == 0 && r == 0)
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      if (p0 + 4 * q + i < n) out[p0 + 4 * q + i] = bc[0] + part[i];
 }
 
 // dst[i] = src[first token of sequence seq0 + i]; rows of `row_f4` float4s (an f32 row of H floats and
@@ -3909,27 +4013,40 @@ int reranker_load(vr_engine* e, const vr_bert_desc* d_in, const void* const* t, 
   vr_bert_desc desc;
   VR_TRY(read_desc(d_in, &desc));
   const vr_bert_desc* d = &desc;
-  VR_CHECK(d->position == VR_POS_LEARNED && d->ffn == VR_FFN_GELU,
-           "a reranker with rotary positions or a gated FFN is not supported (position %d, ffn %d): cross-encoders are "
-           "BERT or XLM-RoBERTa models", d->position, d->ffn);
-  VR_CHECK(d->norm == VR_NORM_POST && d->window == 0,
-           "a reranker with norm %d or window %d is not supported: pre-norm and sliding-window cross-encoders are not "
-           "implemented", d->norm, d->window);
-  VR_CHECK(d->pooling == VR_POOL_CLS && d->normalize == 0, "a reranker pools the [CLS] row (pooling 1) without normalising");
+  // a pre-norm, rotary, gated description is a ModernBERT cross-encoder: its own head (6 tensors), CLS or mean pooling
+  const bool modern = d->norm == VR_NORM_PRE && d->position == VR_POS_ROTARY && d->ffn != VR_FFN_GELU;
+  if (!modern) {
+    VR_CHECK(d->position == VR_POS_LEARNED && d->ffn == VR_FFN_GELU,
+             "a reranker with rotary positions or a gated FFN is not supported (position %d, ffn %d): cross-encoders are "
+             "BERT, XLM-RoBERTa or (pre-norm) ModernBERT models", d->position, d->ffn);
+    VR_CHECK(d->norm == VR_NORM_POST && d->window == 0,
+             "a reranker with norm %d or window %d is not supported: pre-norm and sliding-window cross-encoders need "
+             "rotary positions and a gated FFN", d->norm, d->window);
+    VR_CHECK(d->pooling == VR_POOL_CLS && d->normalize == 0, "a reranker pools the [CLS] row (pooling 1) without normalising");
+  } else {
+    VR_CHECK(d->normalize == 0, "a reranker pools without normalising (normalize %d)", d->normalize);
+    VR_CHECK(d->type_vocab == 1, "a pre-norm reranker has one token type (type_vocab %d)", d->type_vocab);
+  }
   // two token types (BERT: segment B reads type row 1), or one (XLM-R: every token reads row 0, seg_b is not used)
   VR_CHECK(d->type_vocab >= 1, "a reranker needs a token type (type_vocab %d)", d->type_vocab);
-  VR_CHECK(d->layers >= 1 && n_tensors == 5 + 16 * d->layers + 4, "expected %d tensors, got %d", 5 + 16 * d->layers + 4,
-           n_tensors);
-  for (int i = 0; i < 4; ++i) VR_CHECK(t[n_tensors - 4 + i] != nullptr, "tensor %d is null", n_tensors - 4 + i);
-  VR_TRY(build_encoder(e, &e->reranker, d, t, n_tensors - 4, mem));
+  const int n_head = modern ? 6 : 4, per_layer = modern ? 18 : 16;
+  VR_CHECK(d->layers >= 1 && n_tensors == 5 + per_layer * d->layers + n_head, "expected %d tensors, got %d",
+           5 + per_layer * d->layers + n_head, n_tensors);
+  for (int i = 0; i < n_head; ++i) VR_CHECK(t[n_tensors - n_head + i] != nullptr, "tensor %d is null", n_tensors - n_head + i);
+  VR_TRY(build_encoder(e, &e->reranker, d, t, n_tensors - n_head, mem));
   Encoder* enc = static_cast<Encoder*>(e->reranker);
   const int H = d->hidden;
-  const void* const* h = t + n_tensors - 4;
+  const void* const* h = t + n_tensors - n_head;
   const int rc = [&]() -> int {
+    // post-norm: pooler.dense w, b, classifier w, b. Pre-norm: head.dense w, b, head.norm w, b, classifier w, b
     VR_TRY(dev_alloc_copy(e, enc, h[0], static_cast<size_t>(H) * H, mem, &enc->pool_w));
     VR_TRY(dev_alloc_copy(e, enc, h[1], H, mem, &enc->pool_b));
-    VR_TRY(dev_alloc_copy(e, enc, h[2], H, mem, &enc->cls_w));
-    VR_TRY(dev_alloc_copy(e, enc, h[3], 1, mem, &enc->cls_b));
+    if (modern) {
+      VR_TRY(dev_alloc_copy(e, enc, h[2], H, mem, &enc->head_ln_g));
+      VR_TRY(dev_alloc_copy(e, enc, h[3], H, mem, &enc->head_ln_b));
+    }
+    VR_TRY(dev_alloc_copy(e, enc, h[n_head - 2], H, mem, &enc->cls_w));
+    VR_TRY(dev_alloc_copy(e, enc, h[n_head - 1], 1, mem, &enc->cls_b));
     VR_HIP(hipStreamSynchronize(e->stream));
     return 0;
   }();
@@ -4807,8 +4924,13 @@ int encoder_rerank(vr_engine* e, const int32_t* ids, const int32_t* offsets, con
     out_dev = enc->out.p;
   }
   VR_TRY(forward_all(e, enc, ids, offsets, seg_b, n_seq, mem, cu_host, enc->rows.p));
-  hipLaunchKernelGGL(rerank_head_kernel, dim3(static_cast<unsigned>((n_seq + 15) / 16)), dim3(256), 0, e->stream,
-                     enc->rows.p, n_seq, H, enc->pool_w, enc->pool_b, enc->cls_w, enc->cls_b, out_dev);
+  const dim3 head_grid(static_cast<unsigned>((n_seq + 15) / 16));
+  if (enc->head_ln_g)
+    hipLaunchKernelGGL(rerank_head_ln_kernel, head_grid, dim3(256), 0, e->stream, enc->rows.p, n_seq, H, enc->pool_w,
+                       enc->pool_b, enc->head_ln_g, enc->head_ln_b, enc->d.eps, enc->cls_w, enc->cls_b, out_dev);
+  else
+    hipLaunchKernelGGL(rerank_head_kernel, head_grid, dim3(256), 0, e->stream, enc->rows.p, n_seq, H, enc->pool_w,
+                       enc->pool_b, enc->cls_w, enc->cls_b, out_dev);
   VR_HIP(hipGetLastError());
   return finish(e, out, out_dev, n_seq, mem, out_mem);
 }

@@ -49,7 +49,8 @@ void set_error(const char* fmt, ...);
 
 // What the engine's text calls (vr_query_text, vr_query_text_batch, vr_rerank_text) need of a tokenizer: the packed
 // single-text and pair encodings of the C-ABI, with its output conventions (offsets, ids, -2 with *needed, seg_b).
-// vr_wordpiece (wordpiece.cpp) and vr_unigram (unigram.cpp) implement it; both are read-only after creation.
+// vr_wordpiece (wordpiece.cpp), vr_unigram (unigram.cpp) and vr_bpe (bpe.cpp) implement it; all are read-only after
+// creation.
 struct Tokenizer {
   virtual ~Tokenizer() = default;
   virtual int encode(const char* const* texts, const int64_t* text_lens, int64_t n_texts, int32_t max_len,
@@ -60,6 +61,7 @@ struct Tokenizer {
 };
 const Tokenizer* as_tokenizer(const vr_wordpiece* t);  // (nullptr for nullptr)
 const Tokenizer* as_tokenizer(const vr_unigram* t);
+const Tokenizer* as_tokenizer(const vr_bpe* t);
 
 // Host text helpers shared by the tokenizers (wordpiece.cpp)
 // UTF-8 -> code points; a malformed byte becomes U+FFFD
@@ -70,6 +72,11 @@ inline bool is_white_space(uint32_t c) {
   return (c >= 9 && c <= 13) || c == 0x20 || c == 0x85 || c == 0xA0 || c == 0x1680 || (c >= 0x2000 && c <= 0x200A) ||
          c == 0x2028 || c == 0x2029 || c == 0x202F || c == 0x205F || c == 0x3000;
 }
+// NFD of a text and a code point's canonical combining class (wordpiece.cpp's tables); Unicode \w as the added tokens'
+// single_word flag reads it (unigram.cpp)
+void nfd_text(const std::u32string& in, std::u32string* out);
+uint32_t combining_class(uint32_t c);
+bool is_word_character(uint32_t c);
 // HF tokenizers' LongestFirst truncation of a pair's id counts to m together (the specials already taken off max_len)
 void longest_first(size_t* na, size_t* nb, size_t m);
 

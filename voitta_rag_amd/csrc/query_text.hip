@@ -332,6 +332,14 @@ int vr_query_text_unigram(vr_engine* e, const vr_unigram* tokenizer, const char*
                     sparse_weight, fusion, filter, out_rows, out_scores, out_from_dense, out_count, out_hybrid);
 }
 
+int vr_query_text_bpe(vr_engine* e, const vr_bpe* tokenizer, const char* dense_text, int64_t dense_len,
+                          const char* sparse_text, int64_t sparse_len, int32_t max_len, int32_t limit,
+                          double sparse_weight, int32_t fusion, const vr_filter* filter, int64_t* out_rows,
+                          double* out_scores, int32_t* out_from_dense, int32_t* out_count, int32_t* out_hybrid) {
+  return query_text(e, as_tokenizer(tokenizer), dense_text, dense_len, sparse_text, sparse_len, max_len, limit,
+                    sparse_weight, fusion, filter, out_rows, out_scores, out_from_dense, out_count, out_hybrid);
+}
+
 int vr_query_text_batch(vr_engine* e, const vr_wordpiece* tokenizer, int32_t n, const char* const* dense_texts,
                         const int64_t* dense_lens, const char* const* sparse_texts, const int64_t* sparse_lens,
                         int32_t max_len, const int32_t* limits, const double* sparse_weights, int32_t fusion,
@@ -344,6 +352,17 @@ int vr_query_text_batch(vr_engine* e, const vr_wordpiece* tokenizer, int32_t n, 
 }
 
 int vr_query_text_batch_unigram(vr_engine* e, const vr_unigram* tokenizer, int32_t n, const char* const* dense_texts,
+                                const int64_t* dense_lens, const char* const* sparse_texts, const int64_t* sparse_lens,
+                                int32_t max_len, const int32_t* limits, const double* sparse_weights, int32_t fusion,
+                                const vr_filter* filters, int32_t n_filters, const int32_t* filter_of_query,
+                                int32_t out_stride, int64_t* out_rows, double* out_scores, int32_t* out_from_dense,
+                                int32_t* out_counts, int32_t* out_hybrid, float* out_embeddings) {
+  return query_text_batch(e, as_tokenizer(tokenizer), n, dense_texts, dense_lens, sparse_texts, sparse_lens, max_len,
+                          limits, sparse_weights, fusion, filters, n_filters, filter_of_query, out_stride, out_rows,
+                          out_scores, out_from_dense, out_counts, out_hybrid, out_embeddings);
+}
+
+int vr_query_text_batch_bpe(vr_engine* e, const vr_bpe* tokenizer, int32_t n, const char* const* dense_texts,
                                 const int64_t* dense_lens, const char* const* sparse_texts, const int64_t* sparse_lens,
                                 int32_t max_len, const int32_t* limits, const double* sparse_weights, int32_t fusion,
                                 const vr_filter* filters, int32_t n_filters, const int32_t* filter_of_query,

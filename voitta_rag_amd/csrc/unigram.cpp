@@ -389,6 +389,7 @@ void encode_one(const vr_unigram& t, const char* s, size_t n, int32_t max_len, s
 
 namespace vr {
 const Tokenizer* as_tokenizer(const vr_unigram* t) { return t; }
+bool is_word_character(uint32_t c) { return is_word_char(c); }
 }  // namespace vr
 
 extern "C" {

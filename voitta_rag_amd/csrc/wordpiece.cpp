@@ -308,6 +308,10 @@ void append_utf8(uint32_t cp, std::string* out) {
   }
 }
 
+// NFD and the canonical combining class for the other tokenizers (bpe.cpp builds NFC on them)
+void nfd_text(const std::u32string& in, std::u32string* out) { nfd(in, out); }
+uint32_t combining_class(uint32_t c) { return ccc_of(c); }
+
 // HF tokenizers' LongestFirst truncation of a pair to m ids (the specials already taken off max_len): the shorter side
 // keeps min(n_short, m/2) or all of itself, the longer side the rest; when both exceed m/2 the longer one gets the odd id
 void longest_first(size_t* na, size_t* nb, size_t m) {

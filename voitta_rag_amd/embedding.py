@@ -18,6 +18,7 @@ import numpy as np
 from . import deferred as _deferred
 from . import encoder as _enc
 from . import late_chunking as _late
+from .bpe import BpeTokenizer
 from .config import MAX_SEQ_LENGTH_LIMIT, get_settings
 from .store_registry import get_engine
 from .unigram import UnigramTokenizer, is_unigram_pipeline
@@ -46,9 +47,9 @@ def one_call_text_paths(model) -> bool:
 
 
 def native_tokenizer(tok) -> bool:
-    """A tokenizer of the engine itself (WordPiece or Unigram): the one-call text paths (vr_query_text(_batch), the
+    """A tokenizer of the engine itself (WordPiece, Unigram or byte-level BPE): the one-call text paths (vr_query_text(_batch), the
     deferred write-behind) take models with one; a tokenizers-library object goes through several calls instead."""
-    return isinstance(tok, (WordPieceTokenizer, UnigramTokenizer))
+    return isinstance(tok, (WordPieceTokenizer, UnigramTokenizer, BpeTokenizer))
 
 
 def read_encoder_config(path: str) -> dict:
@@ -267,8 +268,9 @@ class NativeSentenceEncoder:
     @staticmethod
     def _load_tokenizer(path: str, cfg: dict):
         """The native WordPiece (csrc/wordpiece.cpp) for plain BERT tokenizers, the native Unigram (csrc/unigram.cpp)
-        for the XLM-R pipeline of an XLM-R model; anything else that a tokenizer.json may describe (a BERT model with
-        a Unigram tokenizer.json among them, as before) goes through the HF `tokenizers` library."""
+        for the XLM-R pipeline of an XLM-R model, the native byte-level BPE (csrc/bpe.cpp) for a ModernBERT model's
+        pipeline; anything else that a tokenizer.json may describe (a BERT model with a Unigram tokenizer.json among
+        them, as before) goes through the HF `tokenizers` library."""
         tj = os.path.join(path, "tokenizer.json")
         if os.path.exists(tj) and cfg.get("model_type") == "xlm-roberta":
             spec = json.load(open(tj, encoding="utf-8"))
@@ -276,6 +278,13 @@ class NativeSentenceEncoder:
                 if is_unigram_pipeline(spec):
                     return UnigramTokenizer.from_tokenizer_json(spec)
                 logger.info("native Unigram not applicable; using the tokenizers library")
+        if os.path.exists(tj) and cfg.get("model_type") == "modernbert":
+            spec = json.load(open(tj, encoding="utf-8"))
+            if (spec.get("model") or {}).get("type") == "BPE":
+                try:
+                    return BpeTokenizer.from_tokenizer_json(spec)
+                except (ValueError, KeyError, TypeError) as e:
+                    logger.info("native byte-level BPE not applicable (%s); using the tokenizers library", e)
         if os.path.exists(os.path.join(path, "vocab.txt")) or os.path.exists(tj):
             try:
                 if os.path.exists(tj):

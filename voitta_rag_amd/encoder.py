@@ -228,6 +228,27 @@ def modernbert_slots(state: dict, desc: "BertDesc"):
 
 # a BertForSequenceClassification's head, after the encoder's tensors (vr_reranker_load)
 HEAD_NAMES = ["pooler.dense.weight", "pooler.dense.bias", "classifier.weight", "classifier.bias"]
+# a ModernBertForSequenceClassification's: classifier(norm(gelu(dense(pooled row)))), six tensors
+PRENORM_HEAD_NAMES = ["head.dense.weight", "head.dense.bias", "head.norm.weight", "head.norm.bias", "classifier.weight",
+                      "classifier.bias"]
+
+
+def modernbert_head(state: dict, desc: "BertDesc") -> dict:
+    """The six head tensors of a ModernBertForSequenceClassification state dict (any key prefix) under
+    PRENORM_HEAD_NAMES; zeros for an absent head.dense.bias (classifier_bias false) or head.norm.bias (norm_bias
+    false), as modernbert_slots fills in an absent LayerNorm shift."""
+    out = {}
+    for name in PRENORM_HEAD_NAMES:
+        hits = [k for k in state if k == name or k.endswith("." + name)]
+        if len(hits) > 1:
+            raise KeyError(f"weight '{name}' is ambiguous in state dict: {hits[:3]}")
+        if hits:
+            out[name] = state[hits[0]]
+        elif name in ("head.dense.bias", "head.norm.bias"):
+            out[name] = np.zeros(desc.hidden, np.float32)
+        else:
+            raise KeyError(f"weight '{name}' not found in state dict")
+    return out
 
 
 def expected_shape(desc: BertDesc, name: str) -> tuple:
@@ -235,6 +256,7 @@ def expected_shape(desc: BertDesc, name: str) -> tuple:
     H, inter = desc.hidden, desc.intermediate
     if name == "classifier.weight": return (1, H)
     if name == "classifier.bias": return (1,)
+    if name.startswith("head.norm."): return (H,)
     if name.endswith("word_embeddings.weight"): return (desc.vocab, H)
     if name.endswith("position_embeddings.weight"): return (desc.max_pos, H)
     if name.endswith("token_type_embeddings.weight"): return (desc.type_vocab, H)
@@ -272,7 +294,18 @@ def load_encoder(engine, desc: BertDesc, state: dict) -> None:
 
 def load_reranker(engine, desc: BertDesc, state: dict) -> None:
     """state: a one-label HF BertForSequenceClassification state dict (any key prefix), the encoder's tensors plus the
-    pooler and the classifier. desc: CLS pooling, no normalisation."""
+    pooler and the classifier. desc: CLS pooling, no normalisation. A pre-norm, rotary, gated description: a one-label
+    ModernBertForSequenceClassification state dict (modernbert_slots' body, modernbert_head's head), pooling "cls" or
+    "mean" (config.json's classifier_pooling), no normalisation."""
+    if desc.prenorm and desc.rotary and desc.gated:
+        if desc.normalize:
+            raise ValueError("a reranker pools without normalising")
+        names, body = modernbert_slots({k: v for k, v in state.items() if ".head." not in "." + k
+                                        and not k.endswith(("classifier.weight", "classifier.bias"))}, desc)
+        body.update(modernbert_head(state, desc))
+        _load(engine, desc, body, names + PRENORM_HEAD_NAMES, engine._lib.vr_reranker_load)
+        engine.reranker_desc = desc
+        return
     if desc.pooling != "cls" or desc.normalize:
         raise ValueError("a reranker pools the [CLS] row without normalising it")
     _load(engine, desc, state, tensor_names(desc.layers) + HEAD_NAMES, engine._lib.vr_reranker_load)

@@ -475,12 +475,15 @@ class Engine:
         return rows[:n].copy(), scores[:n].copy(), fd[:n].copy()
 
     def _text_fn(self, name: str, tokenizer):
-        """The C-ABI text call for `tokenizer` and its handle: vr_<name>_unigram for a UnigramTokenizer, vr_<name> for
-        a WordPieceTokenizer or a raw vr_wordpiece handle."""
+        """The C-ABI text call for `tokenizer` and its handle: vr_<name>_unigram for a UnigramTokenizer, vr_<name>_bpe for
+        a BpeTokenizer, vr_<name> for a WordPieceTokenizer or a raw vr_wordpiece handle."""
+        from .bpe import BpeTokenizer
         from .unigram import UnigramTokenizer
 
         if isinstance(tokenizer, UnigramTokenizer):
             return getattr(self._lib, f"vr_{name}_unigram"), tokenizer._h
+        if isinstance(tokenizer, BpeTokenizer):
+            return getattr(self._lib, f"vr_{name}_bpe"), tokenizer._h
         return getattr(self._lib, f"vr_{name}"), getattr(tokenizer, "_h", tokenizer)
 
     def query_text(self, tokenizer_handle, dense_text: str, sparse_text: str | None, max_len: int, limit: int,

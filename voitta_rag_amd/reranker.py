@@ -1,25 +1,34 @@
 """Second-stage reranking: a BERT cross-encoder (``BertForSequenceClassification`` with one label, such as
-cross-encoder/ms-marco-MiniLM-L-6-v2) or an XLM-R one (``XLMRobertaForSequenceClassification``: BAAI/bge-reranker-base,
--large) that reads a question and a passage together and scores the pair. It lives in
+cross-encoder/ms-marco-MiniLM-L-6-v2), an XLM-R one (``XLMRobertaForSequenceClassification``: BAAI/bge-reranker-base,
+-large) or a ModernBERT one (``ModernBertForSequenceClassification``: Alibaba-NLP/gte-reranker-modernbert-base) that
+reads a question and a passage together and scores the pair. It lives in
 the engine beside the embedder (vr_reranker_load) and runs on the GPU: pair tokenisation on the host threads
 (vr_wordpiece_encode_pairs / vr_unigram_encode_pairs), one forward pass and the classification head (vr_rerank / vr_rerank_text).
+A ModernBERT checkpoint's byte-level BPE runs natively (vr_bpe_encode_pairs, vr_rerank_text_bpe); a tokenizer.json
+outside that pipeline is tokenised by the HF `tokenizers` library (``LibraryPairTokenizer``) and scored by vr_rerank,
+the same forward pass and head.
 
 ``NativeCrossEncoder`` answers what sentence-transformers' ``CrossEncoder`` does for one label: ``predict`` applies a
 sigmoid (on the host, in f64) unless ``activation=False``; ``rank`` sorts the documents of one question."""
 from __future__ import annotations
 
+import dataclasses
 import json
+import logging
 import os
 import threading
 
 import numpy as np
 
 from . import encoder as _enc
+from .bpe import BpeTokenizer
 from .config import MAX_SEQ_LENGTH_LIMIT
-from .embedding import SEQ_CAP_VARIABLE, NativeSentenceEncoder, seq_cap, slice_positions
+from .embedding import SEQ_CAP_VARIABLE, NativeSentenceEncoder, _read_modernbert_config, seq_cap, slice_positions
 from .store_registry import get_engine
 from .unigram import UnigramTokenizer
 from .wordpiece import WordPieceTokenizer
+
+logger = logging.getLogger(__name__)
 
 # XLMRobertaClassificationHead -> the head tensors of vr_reranker_load (encoder.HEAD_NAMES order): out_proj(tanh(dense
 # h_<s>)) is what the BERT pooler + classifier compute
@@ -42,8 +51,22 @@ def read_config(path: str) -> dict:
 
 
 def read_cross_encoder_config(path: str) -> dict:
-    """config.json of a one-label BERT (read_config) or XLM-R (XLMRobertaForSequenceClassification) cross-encoder."""
+    """config.json of a one-label BERT (read_config), XLM-R (XLMRobertaForSequenceClassification) or ModernBERT
+    (ModernBertForSequenceClassification) cross-encoder."""
     cfg = json.load(open(os.path.join(path, "config.json")))
+    if cfg.get("model_type", "bert") == "modernbert":
+        archs = cfg.get("architectures") or ["ModernBertForSequenceClassification"]
+        if archs != ["ModernBertForSequenceClassification"]:
+            raise ValueError(f"unsupported reranker modernbert / {archs}: ModernBertForSequenceClassification only")
+        labels = cfg.get("num_labels", len(cfg.get("id2label") or {0: "LABEL_0"}))
+        if labels != 1:
+            raise ValueError(f"the reranker has {labels} labels: only one-label (relevance score) heads are implemented")
+        if cfg.get("classifier_activation", "gelu") != "gelu":
+            raise ValueError(f"classifier_activation {cfg.get('classifier_activation')!r} is not implemented: the head's "
+                             "activation is the exact-erf GELU")
+        if cfg.get("classifier_pooling", "cls") not in ("cls", "mean"):
+            raise ValueError(f"classifier_pooling {cfg.get('classifier_pooling')!r} is not implemented: cls or mean")
+        return cfg
     if cfg.get("model_type", "bert") != "xlm-roberta":
         return read_config(path)
     archs = cfg.get("architectures") or ["XLMRobertaForSequenceClassification"]
@@ -61,6 +84,44 @@ def _check_head(cfg: dict) -> dict:
     return cfg
 
 
+class LibraryPairTokenizer:
+    """Pair tokenisation by the HF `tokenizers` library, for a tokenizer.json the engine has no tokenizer for (a
+    byte-level BPE outside bpe.parse_tokenizer_json's pipeline): encode_pairs as the native tokenizers answer it,
+    LongestFirst truncation to max_length."""
+
+    def __init__(self, tok, max_length: int):
+        self._tok = tok
+        self._tok.no_padding()
+        self.max_length = int(max_length)
+
+    @property
+    def max_length(self) -> int:
+        return self._max_length
+
+    @max_length.setter
+    def max_length(self, value: int) -> None:
+        self._max_length = int(value)
+        self._tok.enable_truncation(max_length=self._max_length, strategy="longest_first")
+
+    @classmethod
+    def from_pretrained(cls, path: str, max_length: int) -> "LibraryPairTokenizer":
+        from tokenizers import Tokenizer
+
+        tj = os.path.join(path, "tokenizer.json")
+        if not os.path.exists(tj):
+            raise FileNotFoundError(f"no tokenizer.json under {path}")
+        return cls(Tokenizer.from_file(tj), max_length)
+
+    def encode_pairs(self, a: list[str], b: list[str]):
+        """-> (ids int32, offsets int64, seg_b int32): the packed pair sequences and the index of each B's first id."""
+        encs = self._tok.encode_batch(list(zip(a, b)))
+        off = np.zeros(len(encs) + 1, np.int64)
+        off[1:] = np.cumsum([len(e.ids) for e in encs])
+        ids = np.fromiter((t for e in encs for t in e.ids), dtype=np.int32, count=int(off[-1]))
+        seg = np.array([next((i for i, s in enumerate(e.sequence_ids) if s == 1), len(e.ids) - 1) for e in encs], np.int32)
+        return ids, off, seg
+
+
 class NativeCrossEncoder:
     def __init__(self, engine, desc: _enc.BertDesc, state: dict, tokenizer, max_length: int):
         self.engine = engine
@@ -75,6 +136,8 @@ class NativeCrossEncoder:
         if not os.path.isdir(path):
             raise FileNotFoundError(f"reranker '{path}' is not a local checkpoint directory")
         cfg = read_cross_encoder_config(path)
+        if cfg.get("model_type", "bert") == "modernbert":
+            return cls._modernbert(path, cfg, engine, max_length)
         xlmr = cfg.get("model_type", "bert") == "xlm-roberta"
         pos_start = int(cfg.get("pad_token_id", 1)) + 1 if xlmr else 0  # XLM-R: position p reads row pad + 1 + p
         max_pos = int(cfg["max_position_embeddings"]) - pos_start
@@ -105,8 +168,41 @@ class NativeCrossEncoder:
             state[head] = state.pop(name)
         return cls(engine or get_engine(), desc, state, UnigramTokenizer.from_pretrained(path, max_length), max_length)
 
+    @classmethod
+    def _modernbert(cls, path: str, cfg: dict, engine, max_length: int | None) -> "NativeCrossEncoder":
+        """A ModernBertForSequenceClassification directory: the body as the embedder reads it (_read_modernbert_config,
+        sequences capped at seq_cap()), pooled as classifier_pooling says, not normalised."""
+        rc = _read_modernbert_config(path, cfg)
+        if max_length is None:
+            max_length = rc["max_seq"]
+            tc = os.path.join(path, "tokenizer_config.json")
+            if os.path.exists(tc):
+                ml = json.load(open(tc)).get("model_max_length")
+                if isinstance(ml, int) and ml > 0:
+                    max_length = min(max_length, ml)
+        desc = dataclasses.replace(rc["desc"], pooling=cfg.get("classifier_pooling", "cls"), normalize=False,
+                                   precision=os.environ.get("VOITTA_RERANK_PRECISION", "f16"))
+        state = NativeSentenceEncoder._load_weights(path)
+        max_length = min(int(max_length), desc.max_pos)
+        try:
+            tokenizer = BpeTokenizer.from_pretrained(path, max_length)
+        except (ValueError, KeyError, TypeError) as e:
+            logger.info("native byte-level BPE not applicable (%s); using the tokenizers library", e)
+            tokenizer = LibraryPairTokenizer.from_pretrained(path, max_length)
+        return cls(engine or get_engine(), desc, state, tokenizer, max_length)
+
     def logits(self, queries: list[str], candidates: list[list[str]]) -> list[np.ndarray]:
-        """Raw logits of every (queries[q], candidates[q][j]) pair, one f32 array per question, in ONE engine call."""
+        """Raw logits of every (queries[q], candidates[q][j]) pair, one f32 array per question, in ONE engine call
+        (a LibraryPairTokenizer: one tokenizers-library call, then one vr_rerank)."""
+        if isinstance(self.tokenizer, LibraryPairTokenizer):
+            a = [q for q, c in zip(queries, candidates) for _ in c]
+            cand_off = np.zeros(len(queries) + 1, np.int64)
+            cand_off[1:] = np.cumsum([len(c) for c in candidates])
+            if not a:
+                return [np.zeros(0, np.float32) for _ in queries]
+            ids, off, _ = self.tokenizer.encode_pairs(a, [p for c in candidates for p in c])
+            out = self.engine.rerank(ids, off.astype(np.int32), None)
+            return [out[cand_off[i]:cand_off[i + 1]].copy() for i in range(len(queries))]
         return self.engine.rerank_text(self.tokenizer, queries, candidates, self.max_length)
 
     def predict(self, pairs, activation: bool = True) -> np.ndarray:
