@@ -81,10 +81,14 @@ def test_sparse_batch_against_the_oracle_and_the_single_search(small):
 
 
 def test_sparse_batch_pruning_keeps_the_exact_answer(small, monkeypatch):
-    """One block per query walks ALL segments (VR_SPARSE_BATCH_BLOCKS=1): after the first segment its lists are full and
-    the others are scanned with dynamic pruning (csrc/invert.hip: only the essential terms' postings, candidates scored
-    from the forward index). Rows, scores and order must still be the oracle's, bit for bit — common terms (every row
-    has them: pure non-essential ballast), rare terms, a filter, and k from 1 to 64."""
+    """The per-query kernels with dynamic pruning (csrc/invert.hip: seed lists, then sparse_inv_pruned_kernel — only the
+    essential terms' postings, candidates scored from the forward index — then the full scan, inv_scan_segments, of the
+    shares that one flags). A batch of 80 queries reaches them only with VR_SPARSE_GROUPED=0: by default 16 queries or more
+    take the grouped scan (7 segments: seed thresholds), which never reads VR_SPARSE_BATCH_BLOCKS. So every case runs twice:
+    on the per-query kernels, where one block per query walks ALL segments (VR_SPARSE_BATCH_BLOCKS=1; 2: every second) and
+    `sparse_grouped` must not move, and on the default route beside it. Rows, scores and order must be the oracle's, bit for
+    bit — common terms (every row has them: pure non-essential ballast), rare terms, a filter, and k from 1 to 64.
+    (test_sparse_layouts_cpu.py proves the route of both passes from the router's conditions.)"""
     from voitta_rag_amd import SearchFilter
 
     e, rng, x, sp, folder, live, vocab = small
@@ -97,15 +101,22 @@ def test_sparse_batch_pruning_keeps_the_exact_answer(small, monkeypatch):
         if not terms:
             terms = [common[0]]
         qs.append((np.array(terms, np.int32), rng.uniform(0.5, 1.5, size=len(terms)).astype(np.float32)))
-    for blocks in ("1", "2"):
-        monkeypatch.setenv("VR_SPARSE_BATCH_BLOCKS", blocks)
-        for flt, mask in ((None, live.astype(bool)), (SearchFilter(exclude_folders=[3]), live.astype(bool) & (folder != 3))):
-            for k in (1, 10, 30, 64):
-                got = e.search_sparse_batch(qs, k, flt)
-                for i, (qi, qv) in enumerate(qs):
-                    wr, ws = ocore.topk(sp.scores(qi, qv), k, mask.astype(np.uint8))
-                    assert np.array_equal(got[i][0], wr), (blocks, k, i)
-                    assert np.array_equal(got[i][1].view(np.uint32), ws.view(np.uint32)), (blocks, k, i)
+    for grouped in ("0", None):
+        if grouped is None:
+            monkeypatch.delenv("VR_SPARSE_GROUPED")
+        else:
+            monkeypatch.setenv("VR_SPARSE_GROUPED", grouped)
+        for blocks in ("1", "2"):
+            monkeypatch.setenv("VR_SPARSE_BATCH_BLOCKS", blocks)
+            for flt, mask in ((None, live.astype(bool)), (SearchFilter(exclude_folders=[3]), live.astype(bool) & (folder != 3))):
+                for k in (1, 10, 30, 64):
+                    before = e.stats()["sparse_grouped"]
+                    got = e.search_sparse_batch(qs, k, flt)
+                    assert e.stats()["sparse_grouped"] - before == (0 if grouped == "0" else len(qs)), (grouped, blocks, k)
+                    for i, (qi, qv) in enumerate(qs):
+                        wr, ws = ocore.topk(sp.scores(qi, qv), k, mask.astype(np.uint8))
+                        assert np.array_equal(got[i][0], wr), (grouped, blocks, k, i)
+                        assert np.array_equal(got[i][1].view(np.uint32), ws.view(np.uint32)), (grouped, blocks, k, i)
 
 
 def test_grouped_sparse_batch_keeps_the_exact_answer(small, monkeypatch):
