@@ -196,6 +196,15 @@ typedef struct vr_bert_desc {
 int vr_encoder_load(vr_engine* e, const vr_bert_desc* desc, const void* const* tensors,
                     int32_t n_tensors, int mem);
 
+/* Additive attention bias of the loaded ENCODER, by relative offset: every layer's logit of query i against key j of
+ * head h becomes q.k/sqrt(d_h) + table[h][clamp(j - i, -radius, radius) + radius]. table: heads x (2*radius + 1) f32
+ * in `mem`, copied. 1 <= radius <= 512; heads must equal the loaded description's. Needs VR_POS_LEARNED and
+ * VR_NORM_POST (refused otherwise, the encoder stays as it was). NULL table removes the bias. vr_encoder_load
+ * resets it. The reranker never has one.
+ * (MPNet: one T5-style bucketed table shared by all layers; its buckets depend on j - i alone and are constant from
+ * |j - i| = 128 on, so radius 128 reproduces the model at any length.) */
+int vr_encoder_set_attention_bias(vr_engine* e, const float* table, int32_t heads, int32_t radius, int mem);
+
 /* ids: concatenated WordPiece ids of n_seq sequences ([CLS] ... [SEP] already added, truncated
  * to max_pos by the tokenizer); offsets: n_seq+1 int32, offsets[0] = 0. Both in `mem`.
  * out: n_seq x H f32 sentence embeddings in `out_mem`. */
@@ -232,6 +241,13 @@ int vr_encode_spans(vr_engine* e, const int32_t* ids, const int32_t* offsets, in
 typedef struct vr_wordpiece vr_wordpiece;
 int vr_wordpiece_create(const char* const* vocab_tokens, int32_t n_vocab, int32_t lowercase, int32_t strip_accents,
                         int32_t handle_chinese_chars, int32_t clean_text, vr_wordpiece** out);
+/* The same tokenizer with the three specials by name (MPNet's WordPiece wraps a sequence in <s> ... </s> and keeps
+ * [UNK] as the model's unknown token): cls_token A sep_token, unknown words become unk_token; all three must be in the
+ * vocabulary. vr_wordpiece_create is this with "[CLS]", "[SEP]", "[UNK]". With other names than [CLS] / [SEP]
+ * vr_wordpiece_encode_pairs is refused: such models pair with another template. */
+int vr_wordpiece_create_specials(const char* const* vocab_tokens, int32_t n_vocab, int32_t lowercase, int32_t strip_accents,
+                                 int32_t handle_chinese_chars, int32_t clean_text,
+                                 const char* cls_token, const char* sep_token, const char* unk_token, vr_wordpiece** out);
 void vr_wordpiece_destroy(vr_wordpiece* t);
 int vr_wordpiece_encode(const vr_wordpiece* t, const char* const* texts, const int64_t* text_lens, int64_t n_texts,
                         int32_t max_len, int64_t* out_offsets, int32_t* out_ids, int64_t capacity, int64_t* needed);

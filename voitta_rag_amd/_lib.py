@@ -103,10 +103,13 @@ SIGNATURES = {
     "vr_stream": (_vp, [_vp]),
     "vr_set_stream": (C.c_int, [_vp, _vp]),
     "vr_encoder_load": (C.c_int, [_vp, C.POINTER(VrBertDesc), C.POINTER(_vp), C.c_int32, C.c_int]),
+    "vr_encoder_set_attention_bias": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int]),
     "vr_encode": (C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_int, _vp, C.c_int]),
     "vr_encode_spans": (C.c_int, [_vp, _vp, _vp, C.c_int32, _vp, _vp, C.c_int, _vp, C.c_int]),
     "vr_wordpiece_create": (C.c_int, [C.POINTER(C.c_char_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                      C.POINTER(_vp)]),
+    "vr_wordpiece_create_specials": (C.c_int, [C.POINTER(C.c_char_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                              C.c_char_p, C.c_char_p, C.c_char_p, C.POINTER(_vp)]),
     "vr_wordpiece_destroy": (None, [_vp]),
     "vr_wordpiece_encode": (C.c_int, [_vp, C.POINTER(C.c_char_p), _i64p, C.c_int64, C.c_int32, _i64p, _i32p, C.c_int64,
                                      _i64p]),

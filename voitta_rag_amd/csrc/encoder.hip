@@ -76,6 +76,9 @@ struct Encoder {
   // frequencies repeated for every head, so that an epilogue finds its entry from the column alone), max_pos rows
   float2* rope = nullptr;
   float2* rope_local = nullptr;  // ... of the windowed layers' base (vr_bert_desc.rope_theta_local); null: they use `rope`
+  // vr_encoder_set_attention_bias: [heads, 2 bias_radius + 1] f32, logit += bias[h][clamp(key - query) + bias_radius]
+  float* bias = nullptr;
+  int bias_radius = 0;
   int window_stream_from = 0;    // windowed layers: sequences from this length on take attention_stream_kernel (build_encoder)
   float* posidx = nullptr;  // rotary: int32 position of every token inside its own sequence (positions_kernel)
   bool fuse = true;         // rotate / gate inside the skinny epilogues; VR_ENCODE_FUSE=0 at load time: separate passes
@@ -3123,16 +3126,60 @@ struct WindowMask {
 // would floor every later base at 0, and logits far below 0 (P rounds to f16 zero below about -17) would lose the row.
 __device__ __forceinline__ float softmax_base(float m_raw) { return m_raw == -__builtin_inff() ? 0.0f : m_raw; }
 
+// An additive bias by relative offset (vr_encoder_set_attention_bias): the logit of query i against key j of head h
+// gains table[h][clamp(j - i, -radius, radius) + radius]. BIAS, a template flag the host sets like WIN, keeps every
+// launch without a table on the code it ran before; a bias and a window never meet (a window needs pre-norm, the bias
+// post-norm), so <WIN = false, BIAS = true> is the one new instantiation of each kernel. A block works on one head: it
+// stages that head's 2 radius + 1 floats in LDS once, ahead of a barrier it takes anyway (`mul`: log2(e) in the two f16
+// kernels, whose softmax runs in the log2 domain, so that no logit pays a multiply for it). A lane then holds, per
+// query, the row's origin radius - q and reads entry clamp(origin + key, 0, 2 radius): an add, a clamp and an LDS read
+// per logit, in f32, ahead of the key-validity mask and the running maximum. Queries and keys behind the sequence's
+// end index inside the row like any other (the clamp), and their logits are masked or never stored.
+constexpr int kMaxBiasRadius = 512;
+__device__ __forceinline__ void stage_bias(float* sB, const float* __restrict__ table, int head, int radius, float mul,
+                                           int tid, int n_threads) {
+  const int n = 2 * radius + 1;
+  for (int i = tid; i < n; i += n_threads) sB[i] = table[static_cast<int64_t>(head) * n + i] * mul;
+}
+struct BiasRow {
+  const float* row;
+  int origin, last;
+  __device__ __forceinline__ BiasRow(const float* sB, int q, int radius) : row(sB), origin(radius - q), last(2 * radius) {}
+  __device__ __forceinline__ float at(int key) const { return row[min(max(origin + key, 0), last)]; }
+};
+// The two f16 kernels: a 64-key tile's logits of the 16-query tile at qt0 into the log2 domain, with their bias (lane
+// (q, g) holds keys kt + 16 t + 4 g + r). A tile that lies `radius` keys or more to one side of every query of the
+// tile — most tiles of a long sequence — has one bias for all its logits: one LDS read instead of sixteen
+// (wave-uniform: qt0, kt and the radius are).
+__device__ __forceinline__ void bias_tile(f32x4 (&st)[4], float scale2, const BiasRow& br, int kt, int g, int qt0) {
+  const int radius = br.last >> 1;
+  const bool after = kt - (qt0 + 15) >= radius, before = qt0 - (kt + 63) >= radius;
+  if (after || before) {
+    const float far = br.row[after ? br.last : 0];
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) st[t][r] = fmaf(st[t][r], scale2, far);
+  } else {
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) st[t][r] = fmaf(st[t][r], scale2, br.at(kt + t * 16 + 4 * g + r));
+  }
+}
+
 // One block = 64 queries of one (sequence, head); wave w owns queries 16w..16w+15.
 // S^T = K Q^T is computed with keys on the MFMA rows, so a lane (q = lane & 15, g = lane >> 4)
 // ends up holding the logits of query q against keys 4g..4g+3 of each 16-key tile: exactly the B
 // operand layout of the following O^T += V^T P^T product — no transpose, no LDS round trip for P.
-template <int DH, bool WIN>
+template <int DH, bool WIN, bool BIAS>
 __global__ __launch_bounds__(256) void attention_kernel(const float* __restrict__ qkv,
                                                         const int32_t* __restrict__ cu, int seq0,
                                                         int tok_base, int H, int qblocks, float scale,
                                                         float* __restrict__ ctx, half_t* __restrict__ ctx_hi,
-                                                        half_t* __restrict__ ctx_lo, int window_arg) {
+                                                        half_t* __restrict__ ctx_lo, int window_arg,
+                                                        const float* __restrict__ bias_table, int bias_radius) {
+  static_assert(!(WIN && BIAS), "a window needs pre-norm, a bias post-norm");
   const int window = WIN ? window_arg : 0;
   constexpr int LDK = DH + 4;
   constexpr int NS = DH / 16;  // 16-wide d blocks
@@ -3150,6 +3197,13 @@ __global__ __launch_bounds__(256) void attention_kernel(const float* __restrict_
   const int wave = tid >> 6;
   const int qi = lane & 15, g = lane >> 4;
   const int q_tok = qb * 64 + wave * 16 + qi;
+  float* sB = nullptr;
+  if constexpr (BIAS) {
+    __shared__ float bias_lds[2 * kMaxBiasRadius + 1];
+    sB = bias_lds;
+    stage_bias(sB, bias_table, head, bias_radius, 1.0f, tid, 256);  // (read behind the key loop's first barriers)
+  }
+  const BiasRow br(sB, q_tok, BIAS ? bias_radius : 0);
   const bool q_valid = q_tok < len;
   const int64_t row3 = 3 * static_cast<int64_t>(H);
 
@@ -3200,7 +3254,7 @@ __global__ __launch_bounds__(256) void attention_kernel(const float* __restrict_
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int key = kt + t * 16 + 4 * g + r;
-        const float v = key < len && wm.sees(key) ? st[t][r] * scale : -__builtin_inff();
+        const float v = key < len && wm.sees(key) ? (BIAS ? st[t][r] * scale + br.at(key) : st[t][r] * scale) : -__builtin_inff();
         st[t][r] = v;
         mx = fmaxf(mx, v);
       }
@@ -3282,10 +3336,12 @@ __global__ __launch_bounds__(256) void attention_kernel(const float* __restrict_
 // `q_limit`: only queries below it are computed (the last layer of a CLS-pooled model needs token 0 only).
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 
-template <int DH, int NW, bool WIN>
+template <int DH, int NW, bool WIN, bool BIAS>
 __global__ __launch_bounds__(NW * 64) void attention_seq_kernel(const half_t* __restrict__ qkv, const int32_t* __restrict__ cu,
                                                             int seq0, int tok_base, int H, float scale, int q_limit,
-                                                            int lds_keys, half_t* __restrict__ ctx_h, int window_arg) {
+                                                            int lds_keys, half_t* __restrict__ ctx_h, int window_arg,
+                                                            const float* __restrict__ bias_table, int bias_radius) {
+  static_assert(!(WIN && BIAS), "a window needs pre-norm, a bias post-norm");
   const int window = WIN ? window_arg : 0;
   constexpr int LDK = DH;       // halfs per staged row: unpadded, 16-byte chunks XOR-swizzled by the row instead
   constexpr int CH = DH / 8;    // 16-byte chunks per row
@@ -3298,6 +3354,8 @@ __global__ __launch_bounds__(NW * 64) void attention_seq_kernel(const half_t* __
   extern __shared__ __attribute__((aligned(16))) half_t att_lds[];
   half_t* sK = att_lds;
   half_t* sV = att_lds + static_cast<size_t>(lds_keys) * LDK;
+  // BIAS: the head's table behind V (the host adds its bytes to the launch's LDS; 4 lds_keys DH bytes in, 16-aligned)
+  float* sB = BIAS ? reinterpret_cast<float*>(att_lds + static_cast<size_t>(2) * lds_keys * LDK) : nullptr;
   // heads fastest: the twelve 128-byte slices of a token's Q/K/V row are then fetched by blocks that run side by side —
   // one DRAM page opened once — instead of 2200 blocks apart (sequence-fastest order: 3.2 TB/s of 128-byte reads)
   const int n_heads = H / DH;
@@ -3351,6 +3409,7 @@ __global__ __launch_bounds__(NW * 64) void attention_seq_kernel(const half_t* __
       }
     }
   }
+  if constexpr (BIAS) stage_bias(sB, bias_table, head, bias_radius, 1.4426950408889634f, tid, NT);
   __syncthreads();
 
   const float scale2 = scale * 1.4426950408889634f;  // logits in the log2 domain: the softmax uses v_exp_f32 directly
@@ -3374,6 +3433,7 @@ __global__ __launch_bounds__(NW * 64) void attention_seq_kernel(const half_t* __
     const int kt0 = window > 0 ? max(0, qt * 16 - window) & ~63 : 0;
     const int kt1 = window > 0 ? min(keys_pad, qt * 16 + 16 + window) : keys_pad;
     const WindowMask wm(q_tok, window);
+    const BiasRow br(sB, q_tok, BIAS ? bias_radius : 0);
     for (int kt = kt0; kt < kt1; kt += 64) {
       const int nt = min(4, (keys_pad - kt) >> 4);  // 16-key groups in this tile (block-uniform)
       f32x4 st[4];
@@ -3389,13 +3449,16 @@ __global__ __launch_bounds__(NW * 64) void attention_seq_kernel(const half_t* __
         }
       }
       float mx = -__builtin_inff();
+      // BIAS: scaled and biased ahead of both branches, which then take the logits as they are (a factor of 1)
+      if constexpr (BIAS) bias_tile(st, scale2, br, kt, g, qt * 16);
+      const float sc = BIAS ? 1.0f : scale2;
       // every key of the tile exists and every query of the tile sees all of them: no masks
       if (kt + 64 <= len && (window <= 0 || (kt + 63 - qt * 16 <= window && qt * 16 + 15 - kt <= window))) {
 #pragma unroll
         for (int t = 0; t < 4; ++t)
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            st[t][r] *= scale2;
+            st[t][r] *= sc;
             mx = fmaxf(mx, st[t][r]);
           }
       } else {
@@ -3404,7 +3467,7 @@ __global__ __launch_bounds__(NW * 64) void attention_seq_kernel(const half_t* __
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const int key = kt + t * 16 + 4 * g + r;
-            const float v = key < len && wm.sees(key) ? st[t][r] * scale2 : -__builtin_inff();
+            const float v = key < len && wm.sees(key) ? st[t][r] * sc : -__builtin_inff();
             st[t][r] = v;
             mx = fmaxf(mx, v);
           }
@@ -3478,10 +3541,12 @@ __global__ __launch_bounds__(NW * 64) void attention_seq_kernel(const half_t* __
 // attention_seq_kernel. Grid: heads fastest, then the 128-query blocks of a sequence (`qblocks` of them per sequence);
 // `q_limit` as in attention_seq_kernel — the host launches query block 0 alone for it, and a wave whose queries all
 // lie at or behind it stages and takes every barrier but skips the products.
-template <int DH, int NW, bool WIN>
+template <int DH, int NW, bool WIN, bool BIAS>
 __global__ __launch_bounds__(NW * 64) void attention_stream_kernel(const half_t* __restrict__ qkv, const int32_t* __restrict__ cu,
                                                                int seq0, int tok_base, int H, int qblocks, float scale,
-                                                               int q_limit, half_t* __restrict__ ctx_h, int window_arg) {
+                                                               int q_limit, half_t* __restrict__ ctx_h, int window_arg,
+                                                               const float* __restrict__ bias_table, int bias_radius) {
+  static_assert(!(WIN && BIAS), "a window needs pre-norm, a bias post-norm");
   const int window = WIN ? window_arg : 0;
   static_assert(NW == 4 && (DH == 64 || DH == 32), "one 16-byte piece of a 64-key tile per thread and CH / NW rounds");
   constexpr int LDK = DH;       // halfs per staged row: unpadded, 16-byte chunks XOR-swizzled by the row
@@ -3553,6 +3618,12 @@ __global__ __launch_bounds__(NW * 64) void attention_stream_kernel(const half_t*
     request(kt0, kr, vr);
     write(kt0, kr, vr, att_tiles, att_tiles + TILE);
   }
+  float* sB = nullptr;
+  if constexpr (BIAS) {
+    __shared__ float bias_lds[2 * kMaxBiasRadius + 1];
+    sB = bias_lds;
+    stage_bias(sB, bias_table, head, bias_radius, 1.4426950408889634f, tid, NT);
+  }
   __syncthreads();
 
   const float scale2 = scale * 1.4426950408889634f;  // logits in the log2 domain: the softmax uses v_exp_f32 directly
@@ -3568,6 +3639,7 @@ __global__ __launch_bounds__(NW * 64) void attention_stream_kernel(const half_t*
   float m[2] = {-__builtin_inff(), -__builtin_inff()};
   float l[2] = {0.0f, 0.0f};
   const WindowMask wm[2] = {WindowMask(qw + qi, window), WindowMask(qw + 16 + qi, window)};
+  const BiasRow br[2] = {BiasRow(sB, qw + qi, BIAS ? bias_radius : 0), BiasRow(sB, qw + 16 + qi, BIAS ? bias_radius : 0)};
   int buf = 0;
   for (int kt = kt0; kt < kt1; kt += 64, buf ^= 1) {
     const bool more = kt + 64 < kt1;  // block-uniform
@@ -3594,13 +3666,15 @@ __global__ __launch_bounds__(NW * 64) void attention_stream_kernel(const half_t*
         if (i == 1 && !two) break;
         float mx = -__builtin_inff();
         const int qt0 = qw + 16 * i;  // the tile's first query
+        if constexpr (BIAS) bias_tile(st[i], scale2, br[i], kt, g, qt0);  // (as in attention_seq_kernel)
+        const float sc = BIAS ? 1.0f : scale2;
         // every key of the tile exists and every query of the tile sees all of them: no masks
         if (kt + 64 <= len && (window <= 0 || (kt + 63 - qt0 <= window && qt0 + 15 - kt <= window))) {
 #pragma unroll
           for (int t = 0; t < 4; ++t)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-              st[i][t][r] *= scale2;
+              st[i][t][r] *= sc;
               mx = fmaxf(mx, st[i][t][r]);
             }
         } else {
@@ -3609,7 +3683,7 @@ __global__ __launch_bounds__(NW * 64) void attention_stream_kernel(const half_t*
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
               const int key = kt + t * 16 + 4 * g + r;
-              const float v = key < len && wm[i].sees(key) ? st[i][t][r] * scale2 : -__builtin_inff();
+              const float v = key < len && wm[i].sees(key) ? st[i][t][r] * sc : -__builtin_inff();
               st[i][t][r] = v;
               mx = fmaxf(mx, v);
             }
@@ -4009,6 +4083,41 @@ int encoder_load(vr_engine* e, const vr_bert_desc* d, const void* const* t, int 
   return build_encoder(e, &e->encoder, d, t, n_tensors, mem);
 }
 
+// The embedder's attention bias (vr_encoder_set_attention_bias). Every check runs before anything changes; the captured
+// graphs hold the table's pointer and the kernels' instantiation, so they go as they do when the workspace moves.
+int encoder_set_attention_bias(vr_engine* e, const float* table, int heads, int radius, int mem) {
+  Encoder* enc = static_cast<Encoder*>(e->encoder);
+  VR_CHECK(enc, "no encoder loaded");
+  float* fresh = nullptr;
+  if (table) {
+    VR_CHECK(enc->d.position == VR_POS_LEARNED && enc->d.norm == VR_NORM_POST,
+             "an attention bias needs position VR_POS_LEARNED and norm VR_NORM_POST (position %d, norm %d)", enc->d.position,
+             enc->d.norm);
+    VR_CHECK(heads == enc->d.heads, "bias table of %d heads for an encoder of %d", heads, enc->d.heads);
+    VR_CHECK(radius >= 1 && radius <= kMaxBiasRadius, "radius %d must lie in 1..%d", radius, kMaxBiasRadius);
+    const size_t n = static_cast<size_t>(heads) * (2 * static_cast<size_t>(radius) + 1);
+    VR_HIP(hipMalloc(reinterpret_cast<void**>(&fresh), n * sizeof(float)));
+    hipError_t err = hipMemcpyAsync(fresh, table, n * sizeof(float),
+                                    mem == VR_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, e->stream);
+    if (err == hipSuccess) err = hipStreamSynchronize(e->stream);  // (the source may go; passes that read the old table are over)
+    if (err != hipSuccess) {
+      (void)hipFree(fresh);
+      VR_HIP(err);
+    }
+  } else {
+    VR_HIP(hipStreamSynchronize(e->stream));
+  }
+  invalidate_graphs(enc);
+  if (enc->bias) {
+    enc->owned.erase(std::remove(enc->owned.begin(), enc->owned.end(), enc->bias), enc->owned.end());
+    (void)hipFree(enc->bias);
+  }
+  enc->bias = fresh;
+  enc->bias_radius = fresh ? radius : 0;
+  if (fresh) enc->owned.push_back(fresh);
+  return 0;
+}
+
 int reranker_load(vr_engine* e, const vr_bert_desc* d_in, const void* const* t, int n_tensors, int mem) {
   vr_bert_desc desc;
   VR_TRY(read_desc(d_in, &desc));
@@ -4101,10 +4210,15 @@ static int launch_attention(vr_engine* e, Encoder* enc, const int32_t* cu_dev, i
   half_t* cl = split && !plain ? ch + 8 : nullptr;
   const int qblocks = (max_len + 63) / 64;
   const float scale = 1.0f / sqrtf(static_cast<float>(dh));
-  // the kernels' WIN flag: a launch without a window instantiates the code that never knew one
+  // the kernels' WIN and BIAS flags: a launch without a window or a bias instantiates the code that never knew one
+  // (never both: vr_encoder_set_attention_bias refuses the pre-norm descriptions, and only those have a window)
+  const float* bias = enc->bias;
+  const int radius = enc->bias_radius;
+  VR_CHECK(!(bias && window > 0), "an attention bias and a window %d cannot meet", window);
   auto windowed = [&](auto launch) {
-    if (window > 0) launch(std::true_type{});
-    else launch(std::false_type{});
+    if (bias) launch(std::false_type{}, std::true_type{});
+    else if (window > 0) launch(std::true_type{}, std::false_type{});
+    else launch(std::false_type{}, std::false_type{});
   };
   const int qb = tail ? 1 : qblocks;  // tail: only the query block that holds token 0 of every sequence
   dim3 agrid(static_cast<unsigned>(n_seq * qb), static_cast<unsigned>(nh));
@@ -4113,7 +4227,8 @@ static int launch_attention(vr_engine* e, Encoder* enc, const int32_t* cu_dev, i
   // while the longest sequence's rows fit what a workgroup may have on this device; beyond that (max_pos admits up
   // to 8192 tokens) attention_stream_kernel, which streams the keys in 64-row tiles through static LDS
   const int lds_keys = (max_len + 15) & ~15;
-  const size_t lds_bytes = static_cast<size_t>(2) * lds_keys * dh * sizeof(half_t);
+  // (a bias: the head's table behind the staged rows — the staged-or-streamed decision counts it)
+  const size_t lds_bytes = static_cast<size_t>(2) * lds_keys * dh * sizeof(half_t) + (bias ? (2 * radius + 1) * sizeof(float) : 0);
   static size_t lds_limit = 0;
   if (plain && lds_limit == 0) {
     hipDeviceProp_t prop;
@@ -4125,47 +4240,49 @@ static int launch_attention(vr_engine* e, Encoder* enc, const int32_t* cu_dev, i
     static size_t lds_allowed[2] = {0, 0};  // per instantiation: raised above the 64 KiB default when a sequence needs it
     const int which = dh == 64 ? 0 : 1;
     if (lds_bytes > 65536 && lds_bytes > lds_allowed[which]) {
-      for (const void* f : {reinterpret_cast<const void*>(&attention_seq_kernel<64, 4, false>),
-                            reinterpret_cast<const void*>(&attention_seq_kernel<64, 4, true>)})
+      for (const void* f : {reinterpret_cast<const void*>(&attention_seq_kernel<64, 4, false, false>),
+                            reinterpret_cast<const void*>(&attention_seq_kernel<64, 4, true, false>),
+                            reinterpret_cast<const void*>(&attention_seq_kernel<64, 4, false, true>)})
         if (dh == 64) VR_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_bytes)));
-      for (const void* f : {reinterpret_cast<const void*>(&attention_seq_kernel<32, 4, false>),
-                            reinterpret_cast<const void*>(&attention_seq_kernel<32, 4, true>)})
+      for (const void* f : {reinterpret_cast<const void*>(&attention_seq_kernel<32, 4, false, false>),
+                            reinterpret_cast<const void*>(&attention_seq_kernel<32, 4, true, false>),
+                            reinterpret_cast<const void*>(&attention_seq_kernel<32, 4, false, true>)})
         if (dh != 64) VR_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_bytes)));
       lds_allowed[which] = lds_bytes;
     }
     const dim3 sgrid(static_cast<unsigned>(n_seq) * static_cast<unsigned>(nh));
     const int q_limit = tail ? 16 : max_len;
-    windowed([&](auto W) {
-      constexpr bool kWin = decltype(W)::value;
+    windowed([&](auto W, auto B) {
+      constexpr bool kWin = decltype(W)::value, kBias = decltype(B)::value;
       if (dh == 64)
-        hipLaunchKernelGGL((attention_seq_kernel<64, 4, kWin>), sgrid, dim3(256), lds_bytes, s, reinterpret_cast<const half_t*>(enc->qkv),
-                           cu_dev, seq0, tok_base, H, scale, q_limit, lds_keys, ch, window);
+        hipLaunchKernelGGL((attention_seq_kernel<64, 4, kWin, kBias>), sgrid, dim3(256), lds_bytes, s, reinterpret_cast<const half_t*>(enc->qkv),
+                           cu_dev, seq0, tok_base, H, scale, q_limit, lds_keys, ch, window, bias, radius);
       else
-        hipLaunchKernelGGL((attention_seq_kernel<32, 4, kWin>), sgrid, dim3(256), lds_bytes, s, reinterpret_cast<const half_t*>(enc->qkv),
-                           cu_dev, seq0, tok_base, H, scale, q_limit, lds_keys, ch, window);
+        hipLaunchKernelGGL((attention_seq_kernel<32, 4, kWin, kBias>), sgrid, dim3(256), lds_bytes, s, reinterpret_cast<const half_t*>(enc->qkv),
+                           cu_dev, seq0, tok_base, H, scale, q_limit, lds_keys, ch, window, bias, radius);
     });
   } else if (plain) {  // 128 queries per block
     const int qb128 = tail ? 1 : (max_len + 127) / 128;
     const dim3 sgrid(static_cast<unsigned>(n_seq) * static_cast<unsigned>(qb128) * static_cast<unsigned>(nh));
     const int q_limit = tail ? 16 : max_len;
-    windowed([&](auto W) {
-      constexpr bool kWin = decltype(W)::value;
+    windowed([&](auto W, auto B) {
+      constexpr bool kWin = decltype(W)::value, kBias = decltype(B)::value;
       if (dh == 64)
-        hipLaunchKernelGGL((attention_stream_kernel<64, 4, kWin>), sgrid, dim3(256), 0, s, reinterpret_cast<const half_t*>(enc->qkv),
-                           cu_dev, seq0, tok_base, H, qb128, scale, q_limit, ch, window);
+        hipLaunchKernelGGL((attention_stream_kernel<64, 4, kWin, kBias>), sgrid, dim3(256), 0, s, reinterpret_cast<const half_t*>(enc->qkv),
+                           cu_dev, seq0, tok_base, H, qb128, scale, q_limit, ch, window, bias, radius);
       else
-        hipLaunchKernelGGL((attention_stream_kernel<32, 4, kWin>), sgrid, dim3(256), 0, s, reinterpret_cast<const half_t*>(enc->qkv),
-                           cu_dev, seq0, tok_base, H, qb128, scale, q_limit, ch, window);
+        hipLaunchKernelGGL((attention_stream_kernel<32, 4, kWin, kBias>), sgrid, dim3(256), 0, s, reinterpret_cast<const half_t*>(enc->qkv),
+                           cu_dev, seq0, tok_base, H, qb128, scale, q_limit, ch, window, bias, radius);
     });
   } else {
-    windowed([&](auto W) {
-      constexpr bool kWin = decltype(W)::value;
+    windowed([&](auto W, auto B) {
+      constexpr bool kWin = decltype(W)::value, kBias = decltype(B)::value;
       if (dh == 64)
-        hipLaunchKernelGGL((attention_kernel<64, kWin>), agrid, dim3(256), 0, s, enc->qkv, cu_dev, seq0, tok_base, H, qb, scale,
-                           enc->ctx, ch, cl, window);
+        hipLaunchKernelGGL((attention_kernel<64, kWin, kBias>), agrid, dim3(256), 0, s, enc->qkv, cu_dev, seq0, tok_base, H, qb, scale,
+                           enc->ctx, ch, cl, window, bias, radius);
       else
-        hipLaunchKernelGGL((attention_kernel<32, kWin>), agrid, dim3(256), 0, s, enc->qkv, cu_dev, seq0, tok_base, H, qb, scale,
-                           enc->ctx, ch, cl, window);
+        hipLaunchKernelGGL((attention_kernel<32, kWin, kBias>), agrid, dim3(256), 0, s, enc->qkv, cu_dev, seq0, tok_base, H, qb, scale,
+                           enc->ctx, ch, cl, window, bias, radius);
     });
   }
   prof_end(e);

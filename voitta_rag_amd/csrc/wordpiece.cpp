@@ -36,6 +36,7 @@
 struct vr_wordpiece final : vr::Tokenizer {
   std::unordered_map<std::string, int32_t> vocab;
   int32_t unk = -1, cls = -1, sep = -1;
+  bool pair_template = true;  // [CLS] A [SEP] B [SEP] is this tokenizer's pair form (not so with named specials)
   bool lowercase = true, strip_accents = true, chinese = true, clean = true;
 
   int encode(const char* const* texts, const int64_t* text_lens, int64_t n_texts, int32_t max_len, int64_t* out_offsets,
@@ -335,7 +336,14 @@ extern "C" {
 
 int vr_wordpiece_create(const char* const* vocab_tokens, int32_t n_vocab, int32_t lowercase, int32_t strip_accents,
                         int32_t handle_chinese_chars, int32_t clean_text, vr_wordpiece** out) {
-  VR_CHECK(vocab_tokens && out && n_vocab > 0, "bad arguments");
+  return vr_wordpiece_create_specials(vocab_tokens, n_vocab, lowercase, strip_accents, handle_chinese_chars, clean_text,
+                                      "[CLS]", "[SEP]", "[UNK]", out);
+}
+
+int vr_wordpiece_create_specials(const char* const* vocab_tokens, int32_t n_vocab, int32_t lowercase, int32_t strip_accents,
+                                 int32_t handle_chinese_chars, int32_t clean_text, const char* cls_token,
+                                 const char* sep_token, const char* unk_token, vr_wordpiece** out) {
+  VR_CHECK(vocab_tokens && out && n_vocab > 0 && cls_token && sep_token && unk_token, "bad arguments");
   vr_wordpiece* t = new vr_wordpiece();
   t->vocab.reserve(static_cast<size_t>(n_vocab) * 2);
   // HF's WordPiece::read_file builds {token: line}: a later duplicate line overwrites an earlier one
@@ -345,14 +353,16 @@ int vr_wordpiece_create(const char* const* vocab_tokens, int32_t n_vocab, int32_
     auto it = t->vocab.find(name);
     return it == t->vocab.end() ? -1 : it->second;
   };
-  t->unk = special("[UNK]");
-  t->cls = special("[CLS]");
-  t->sep = special("[SEP]");
+  t->unk = special(unk_token);
+  t->cls = special(cls_token);
+  t->sep = special(sep_token);
   if (t->unk < 0 || t->cls < 0 || t->sep < 0) {
     delete t;
-    vr::set_error("vocabulary lacks [UNK], [CLS] or [SEP]");
+    vr::set_error("vocabulary lacks %s, %s or %s", unk_token, cls_token, sep_token);
     return -1;
   }
+  // other names wrap a single sequence the same way, but such models (MPNet: <s> A </s></s> B </s>) pair differently
+  t->pair_template = strcmp(cls_token, "[CLS]") == 0 && strcmp(sep_token, "[SEP]") == 0;
   t->lowercase = lowercase != 0;
   t->strip_accents = strip_accents < 0 ? t->lowercase : strip_accents != 0;
   t->chinese = handle_chinese_chars != 0;
@@ -397,6 +407,8 @@ int vr_wordpiece_encode_pairs(const vr_wordpiece* t, const char* const* a_texts,
                               int64_t* needed) {
   VR_CHECK(t && n >= 0 && (n == 0 || (a_texts && a_lens && b_texts && b_lens)) && out_offsets && needed, "bad arguments");
   VR_CHECK(max_len >= 3, "max_len %d cannot hold [CLS] and two [SEP]", max_len);
+  VR_CHECK(t->pair_template, "this tokenizer was created with named specials (vr_wordpiece_create_specials): its model's "
+           "pair template is not [CLS] A [SEP] B [SEP], and pairs are not implemented for it");
   for (int64_t i = 0; i < n; ++i)
     VR_CHECK(a_texts[i] && b_texts[i] && a_lens[i] >= 0 && b_lens[i] >= 0, "pair %lld: null text or negative length",
              static_cast<long long>(i));

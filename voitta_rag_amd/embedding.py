@@ -64,8 +64,10 @@ def read_encoder_config(path: str) -> dict:
         return _read_rope_config(path, cfg)
     if kind == "modernbert":
         return _read_modernbert_config(path, cfg)
+    if kind == "mpnet":
+        return _read_mpnet_config(path, cfg)
     if kind not in ("bert", "xlm-roberta"):
-        raise ValueError(f"unsupported model_type {kind}: BERT, XLM-RoBERTa, nomic_bert and modernbert encoders only")
+        raise ValueError(f"unsupported model_type {kind}: BERT, XLM-RoBERTa, MPNet, nomic_bert and modernbert encoders only")
     if cfg.get("hidden_act", "gelu") != "gelu" or cfg.get("position_embedding_type", "absolute") != "absolute":
         raise ValueError("only exact-erf GELU and absolute position embeddings are implemented")
     pos_start = int(cfg.get("pad_token_id", 1)) + 1 if kind == "xlm-roberta" else 0
@@ -108,6 +110,36 @@ def _read_modules(path: str, max_seq: int):
     if os.path.exists(sb):
         max_seq = int(json.load(open(sb)).get("max_seq_length", max_seq))
     return pooling, normalize, max_seq
+
+
+def _read_mpnet_config(path: str, cfg: dict) -> dict:
+    """model_type mpnet (all-mpnet-base-v2, multi-qa-mpnet-*, paraphrase-mpnet-*): a post-LayerNorm BERT with exact-erf
+    GELU, no token types, learned positions from row padding_idx + 1 = 2 on (as XLM-R's), and one relative-position
+    attention bias shared by all layers — encoder.mpnet_slots turns its bucket table into the engine's offset table."""
+    act = cfg.get("hidden_act", "gelu")
+    if act != "gelu":
+        raise ValueError(f"hidden_act {act!r} is not implemented: an mpnet FFN runs the exact-erf GELU")
+    buckets = int(cfg.get("relative_attention_num_buckets", 32))
+    if buckets % 2:
+        raise ValueError(f"relative_attention_num_buckets {buckets} is not implemented: the buckets are split in two "
+                         "halves by the sign of the offset")
+    if buckets != 32:
+        raise ValueError(f"relative_attention_num_buckets {buckets} is not implemented: transformers' MPNetEncoder computes "
+                         "its buckets for 32 whatever this says, and so would not use such a table as it was trained")
+    pos_start = 2  # MPNetEmbeddings.padding_idx + 1, fixed in the model's code
+    max_pos = int(cfg["max_position_embeddings"]) - pos_start
+    pooling, normalize, max_seq = _read_modules(path, max_pos)
+    max_seq = min(max_seq, max_pos)
+    cap = seq_cap()
+    if max_seq > cap:
+        raise ValueError(f"{path} uses sequences of up to {max_seq} tokens; the engine runs at most {cap}: set "
+                         f"max_seq_length <= {cap} in its sentence_bert_config.json, or raise {SEQ_CAP_VARIABLE} "
+                         f"(up to {MAX_SEQ_LENGTH_LIMIT})")
+    desc = _enc.BertDesc(layers=cfg["num_hidden_layers"], hidden=cfg["hidden_size"], heads=cfg["num_attention_heads"],
+                         intermediate=cfg["intermediate_size"], vocab=cfg["vocab_size"], max_pos=max_pos, type_vocab=1,
+                         pooling=pooling, normalize=normalize, eps=cfg.get("layer_norm_eps", 1e-5),
+                         precision=os.environ.get("VOITTA_ENCODER_PRECISION", "f16"))
+    return {"desc": desc, "max_seq": max_seq, "pos_start": pos_start, "config": cfg}
 
 
 def _read_rope_config(path: str, cfg: dict) -> dict:
@@ -248,7 +280,10 @@ class NativeSentenceEncoder:
                 f"EMBEDDING_MODEL='{path}' is not a local checkpoint directory (hub names cannot be "
                 "downloaded here: there is no network). Point it at a sentence-transformers / HF BERT directory.")
         rc = read_encoder_config(path)
-        state = slice_positions(cls._load_weights(path), rc["pos_start"])
+        if rc["config"].get("model_type") == "mpnet":
+            state, rc["desc"].attention_bias = _enc.mpnet_slots(cls._load_weights(path), rc["desc"], rc["pos_start"])
+        else:
+            state = slice_positions(cls._load_weights(path), rc["pos_start"])
         return cls(engine or get_engine(), rc["desc"], state, cls._load_tokenizer(path, rc["config"]), rc["max_seq"])
 
     @staticmethod
@@ -267,7 +302,9 @@ class NativeSentenceEncoder:
 
     @staticmethod
     def _load_tokenizer(path: str, cfg: dict):
-        """The native WordPiece (csrc/wordpiece.cpp) for plain BERT tokenizers, the native Unigram (csrc/unigram.cpp)
+        """The native WordPiece (csrc/wordpiece.cpp) for plain BERT tokenizers (an MPNet model's among them: the same
+        pipeline wrapped in <s> ... </s>, the names read from tokenizer.json's post_processor), the native Unigram
+        (csrc/unigram.cpp)
         for the XLM-R pipeline of an XLM-R model, the native byte-level BPE (csrc/bpe.cpp) for a ModernBERT model's
         pipeline; anything else that a tokenizer.json may describe (a BERT model with a Unigram tokenizer.json among
         them, as before) goes through the HF `tokenizers` library."""
@@ -296,6 +333,13 @@ class NativeSentenceEncoder:
                              and spec["model"].get("max_input_chars_per_word", 100) == 100)
                     if not plain:
                         raise ValueError("not a plain BERT WordPiece pipeline")
+                    # the wrapper is part of the pipeline: WordPieceTokenizer reads the specials' names from the
+                    # post_processor and refuses one that is not <cls> $A <sep>. An MPNet model needs them found
+                    # (<s> ... </s>): without a post_processor there the [CLS] ... [SEP] default would be wrong ids
+                    if cfg.get("model_type") == "mpnet" and spec.get("post_processor") is None:
+                        raise ValueError("an MPNet tokenizer.json without a post_processor names no specials")
+                elif cfg.get("model_type") == "mpnet":
+                    raise ValueError("an MPNet vocab.txt alone names no specials")
                 return WordPieceTokenizer.from_pretrained(path)
             except (ValueError, KeyError) as e:
                 logger.info("native WordPiece not applicable (%s); using the tokenizers library", e)

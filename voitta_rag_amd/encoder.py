@@ -7,7 +7,7 @@ Replaces the ``SentenceTransformer(model_name, device)`` object the reference la
 from __future__ import annotations
 
 import ctypes as C
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 
 import numpy as np
 
@@ -74,6 +74,9 @@ class BertDesc:
     window: int = 0  # sliding-window attention: query i of a windowed layer sees key j iff |i - j| <= window; 0 = none
     global_every: int = 0  # window > 0: layer l attends globally iff l % global_every == 0
     rope_theta_local: float = 0.0  # the rotary base of the windowed layers; 0 = rope_theta
+    # additive attention bias by relative offset, f32 [heads, 2 * radius + 1] (MPNet: mpnet_bias_table); not a field of
+    # vr_bert_desc: load_encoder hands it to vr_encoder_set_attention_bias once the model is loaded
+    attention_bias: object = field(default=None, compare=False, repr=False)
 
     @property
     def rotary(self) -> bool:
@@ -226,6 +229,74 @@ def modernbert_slots(state: dict, desc: "BertDesc"):
     return names, out
 
 
+def mpnet_relative_position_bucket(relative_position, num_buckets: int = 32, max_distance: int = 128):
+    """transformers' MPNetEncoder.relative_position_bucket, operation for operation (torch's f32 log decides the bucket
+    at the logarithmic edges, so it is torch here too): relative_position = key - query, int64 tensor -> bucket."""
+    import math
+
+    import torch
+
+    ret = 0
+    n = -relative_position
+    num_buckets //= 2
+    ret += (n < 0).to(torch.long) * num_buckets
+    n = torch.abs(n)
+    max_exact = num_buckets // 2
+    is_small = n < max_exact
+    val_if_large = max_exact + (
+        torch.log(n.float() / max_exact) / math.log(max_distance / max_exact) * (num_buckets - max_exact)
+    ).to(torch.long)
+    val_if_large = torch.min(val_if_large, torch.full_like(val_if_large, num_buckets - 1))
+    ret += torch.where(is_small, n, val_if_large)
+    return ret
+
+
+def mpnet_bias_table(weight, radius: int = 128) -> np.ndarray:
+    """encoder.relative_attention_bias.weight [buckets, heads] -> float32 [heads, 2 * radius + 1], the table
+    vr_encoder_set_attention_bias takes: entry [h, d + radius] is the bias of key - query = d. The buckets depend on
+    key - query alone and saturate at |d| = 128, so radius 128 reproduces compute_position_bias at every length."""
+    import torch
+
+    if hasattr(weight, "detach"):
+        weight = weight.detach().cpu().numpy()
+    w = torch.from_numpy(np.array(weight, dtype=np.float32))
+    if w.ndim != 2 or w.shape[0] % 2:
+        raise ValueError(f"relative_attention_bias.weight of shape {tuple(w.shape)}: expected [an even bucket count, heads]")
+    if radius < 128:
+        raise ValueError(f"radius {radius}: the buckets saturate at a distance of 128 only")
+    rel = torch.arange(-radius, radius + 1, dtype=torch.long)
+    bucket = mpnet_relative_position_bucket(rel, num_buckets=int(w.shape[0]))
+    return np.ascontiguousarray(w[bucket].T.numpy(), dtype=np.float32)
+
+
+def mpnet_slots(state: dict, desc: "BertDesc", pos_start: int = 2):
+    """A transformers MPNetModel state dict (with or without the `mpnet.` prefix) -> (state under the BERT names of
+    tensor_names(), bias table). MPNet is a post-LayerNorm BERT without token types whose positions start at row
+    padding_idx + 1 = 2: the token-type slot is a zero [1, H] row and the position table is taken from row pos_start.
+    encoder.relative_attention_bias.weight, shared by all layers, becomes the offset table of mpnet_bias_table."""
+
+    def get(name):
+        hits = [k for k in state if k == name or k.endswith("." + name)]
+        if len(hits) != 1:
+            raise KeyError(f"weight '{name}' not found (or ambiguous) in state dict: {hits[:3]}")
+        return state[hits[0]]
+
+    out = {"embeddings.word_embeddings.weight": get("embeddings.word_embeddings.weight"),
+           "embeddings.position_embeddings.weight": get("embeddings.position_embeddings.weight")[pos_start:],
+           "embeddings.token_type_embeddings.weight": np.zeros((1, desc.hidden), np.float32),
+           "embeddings.LayerNorm.weight": get("embeddings.LayerNorm.weight"),
+           "embeddings.LayerNorm.bias": get("embeddings.LayerNorm.bias")}
+    renames = [("attention.self.query", "attention.attn.q"), ("attention.self.key", "attention.attn.k"),
+               ("attention.self.value", "attention.attn.v"), ("attention.output.dense", "attention.attn.o"),
+               ("attention.output.LayerNorm", "attention.LayerNorm"), ("intermediate.dense", "intermediate.dense"),
+               ("output.dense", "output.dense"), ("output.LayerNorm", "output.LayerNorm")]
+    for i in range(desc.layers):
+        for dst, src in renames:
+            for kind in ("weight", "bias"):
+                out[f"encoder.layer.{i}.{dst}.{kind}"] = get(f"encoder.layer.{i}.{src}.{kind}")
+    return out, mpnet_bias_table(get("encoder.relative_attention_bias.weight"))
+
+
 # a BertForSequenceClassification's head, after the encoder's tensors (vr_reranker_load)
 HEAD_NAMES = ["pooler.dense.weight", "pooler.dense.bias", "classifier.weight", "classifier.bias"]
 # a ModernBertForSequenceClassification's: classifier(norm(gelu(dense(pooled row)))), six tensors
@@ -281,7 +352,8 @@ def _find(state: dict, suffix: str):
 
 def load_encoder(engine, desc: BertDesc, state: dict) -> None:
     """state: HF BertModel state dict (any key prefix), values NumPy arrays or torch tensors.
-    Tensors on the engine's GPU are passed as device pointers, everything else as host memory."""
+    Tensors on the engine's GPU are passed as device pointers, everything else as host memory.
+    A description that carries an attention_bias table (MPNet, see mpnet_slots) sets it once the model is loaded."""
     if desc.prenorm:
         names, state = modernbert_slots(state, desc)
     else:
@@ -290,6 +362,8 @@ def load_encoder(engine, desc: BertDesc, state: dict) -> None:
         names = names_for(desc)
     _load(engine, desc, state, names, engine._lib.vr_encoder_load)
     engine.encoder_desc = desc
+    if desc.attention_bias is not None:
+        engine.set_attention_bias(desc.attention_bias)
 
 
 def load_reranker(engine, desc: BertDesc, state: dict) -> None:

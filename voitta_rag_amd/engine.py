@@ -248,6 +248,21 @@ class Engine:
 
         return encoder.encode_spans(self, ids, offsets, span_off, span_tok, out)
 
+    def set_attention_bias(self, table) -> None:
+        """The loaded encoder's additive attention bias by relative offset (vr_encoder_set_attention_bias):
+        table[heads, 2 * radius + 1], f32; the logit of query i against key j of head h gains
+        table[h, clamp(j - i, -radius, radius) + radius] in every layer. None removes it. Loading an encoder resets it."""
+        if table is None:
+            check(self._lib.vr_encoder_set_attention_bias(self._h, None, 0, 0, VR_MEM_HOST))
+            return
+        if hasattr(table, "detach"):
+            table = table.detach().cpu().numpy()
+        table = np.ascontiguousarray(table, dtype=np.float32)
+        if table.ndim != 2 or table.shape[1] % 2 != 1:
+            raise ValueError(f"attention bias table of shape {table.shape}: expected [heads, 2 * radius + 1]")
+        check(self._lib.vr_encoder_set_attention_bias(self._h, C.c_void_p(table.ctypes.data), table.shape[0],
+                                                      (table.shape[1] - 1) // 2, VR_MEM_HOST))
+
     def _index_batch(self, wp_ids, wp_off, spans, bm_ids, bm_off, folder_ids, index_folder_ids, created, modified,
                      k, b, avg_len) -> int:
         dev = _is_device_tensor(wp_ids)
