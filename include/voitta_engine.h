@@ -127,7 +127,7 @@ typedef struct vr_bert_desc {
   int32_t vocab;
   int32_t max_pos;       /* max_position_embeddings; also the longest accepted sequence. VR_POS_ROTARY: the length of
                           * the cos/sin table the engine builds, which is again the longest accepted sequence.
-                          * 1 .. 8192 */
+                          * VR_POS_NONE: there is no table, the longest accepted sequence alone. 1 .. 8192 */
   int32_t type_vocab;
   int32_t pooling;       /* VR_POOL_MEAN | VR_POOL_CLS (sentence-transformers Pooling module) */
   int32_t normalize;     /* 1 = L2-normalise (sentence-transformers Normalize module) */
@@ -135,7 +135,7 @@ typedef struct vr_bert_desc {
   int32_t precision;     /* VR_PRECISION_F32 | VR_PRECISION_F16X3 | VR_PRECISION_F16 */
   /* Added after the first release: zero in every field below is the behaviour of a description that ends at
    * `precision` (struct_size may still be that shorter size; the missing fields are then read as zero). */
-  int32_t position;      /* VR_POS_LEARNED | VR_POS_ROTARY */
+  int32_t position;      /* VR_POS_LEARNED | VR_POS_ROTARY | VR_POS_NONE */
   float   rope_theta;    /* VR_POS_ROTARY: base of the rotary frequencies, inv_freq_i = theta^(-2i/d_h); > 0 */
   int32_t ffn;           /* VR_FFN_GELU | VR_FFN_SWIGLU | VR_FFN_GEGLU */
   /* Added with the pre-norm family (ModernBERT): again zero in every field is the behaviour of a description that
@@ -149,9 +149,12 @@ typedef struct vr_bert_desc {
 
 /* position: LEARNED adds a row of the position table to every token's embedding; ROTARY has no table — the query and
  * key of every head are rotated by the token's position inside its own sequence (rotate-half pairing: feature j with
- * j + d_h/2, as in HF apply_rotary_pos_emb; the full head is rotated). */
+ * j + d_h/2, as in HF apply_rotary_pos_emb; the full head is rotated). NONE has no table and no rotation: the
+ * embeddings are word + token type, and the model sees order through vr_encoder_set_attention_slopes alone (ALiBi:
+ * jina-embeddings-v2). NONE needs VR_NORM_POST and no window. */
 #define VR_POS_LEARNED 0
 #define VR_POS_ROTARY  1
+#define VR_POS_NONE    2
 /* ffn: GELU is down(gelu(up(x))); the gated forms are down(act(gate(x)) * up(x)) with act = SiLU (SWIGLU) or the
  * exact-erf GELU (GEGLU). */
 #define VR_FFN_GELU   0
@@ -189,7 +192,8 @@ typedef struct vr_bert_desc {
  * layer l's attention.output.LayerNorm = the norm in front of layer l's FFN (ModernBERT: layers.l.mlp_norm); layer l's
  * output.LayerNorm = the norm in front of layer l + 1's attention (layers.l+1.attn_norm), and for the last layer the
  * final norm (final_norm). Layer 0's attention reads the embedding norm's output as it is.
- * NULL slots: any bias (read as zeros), and position_embeddings when position is VR_POS_ROTARY (ignored then).
+ * NULL slots: any bias (read as zeros), and position_embeddings when position is VR_POS_ROTARY or VR_POS_NONE (ignored
+ * then).
  * Every other slot must be non-NULL.
  * The engine copies (and re-packs) them; the caller's tensors may be freed afterwards.
  * Replaces EmbeddingService.model's lazy SentenceTransformer(...) load (embedding.py:23-42). */
@@ -199,11 +203,19 @@ int vr_encoder_load(vr_engine* e, const vr_bert_desc* desc, const void* const* t
 /* Additive attention bias of the loaded ENCODER, by relative offset: every layer's logit of query i against key j of
  * head h becomes q.k/sqrt(d_h) + table[h][clamp(j - i, -radius, radius) + radius]. table: heads x (2*radius + 1) f32
  * in `mem`, copied. 1 <= radius <= 512; heads must equal the loaded description's. Needs VR_POS_LEARNED and
- * VR_NORM_POST (refused otherwise, the encoder stays as it was). NULL table removes the bias. vr_encoder_load
- * resets it. The reranker never has one.
+ * VR_NORM_POST (refused otherwise, and while vr_encoder_set_attention_slopes' slopes are set; the encoder stays as it
+ * was). NULL table removes the bias. vr_encoder_load resets it. The reranker never has one.
  * (MPNet: one T5-style bucketed table shared by all layers; its buckets depend on j - i alone and are constant from
  * |j - i| = 128 on, so radius 128 reproduces the model at any length.) */
 int vr_encoder_set_attention_bias(vr_engine* e, const float* table, int32_t heads, int32_t radius, int mem);
+
+/* Linear attention bias of the loaded ENCODER (ALiBi): every layer's logit of query i against key j of head h becomes
+ * q.k/sqrt(d_h) - slopes[h] * |j - i|, at any distance (nothing saturates, no key is skipped). slopes: `heads` f32 in
+ * `mem`, copied; each finite, 0 <= slope <= 1e30 (beyond that the bias of a far key would leave f32's range); heads
+ * must equal the loaded description's. Needs VR_NORM_POST and VR_POS_LEARNED or VR_POS_NONE. Slopes and a table
+ * (vr_encoder_set_attention_bias) never coexist: setting one while the other is set is refused. A refused call leaves
+ * the encoder as it was. NULL slopes removes them. vr_encoder_load resets them. The reranker never has any. */
+int vr_encoder_set_attention_slopes(vr_engine* e, const float* slopes, int32_t heads, int mem);
 
 /* ids: concatenated WordPiece ids of n_seq sequences ([CLS] ... [SEP] already added, truncated
  * to max_pos by the tokenizer); offsets: n_seq+1 int32, offsets[0] = 0. Both in `mem`.

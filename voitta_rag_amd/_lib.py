@@ -73,6 +73,7 @@ VR_PRECISION_F16X3 = 1
 VR_PRECISION_F16 = 2
 VR_POS_LEARNED = 0
 VR_POS_ROTARY = 1
+VR_POS_NONE = 2
 VR_FFN_GELU = 0
 VR_FFN_SWIGLU = 1
 VR_FFN_GEGLU = 2
@@ -104,6 +105,7 @@ SIGNATURES = {
     "vr_set_stream": (C.c_int, [_vp, _vp]),
     "vr_encoder_load": (C.c_int, [_vp, C.POINTER(VrBertDesc), C.POINTER(_vp), C.c_int32, C.c_int]),
     "vr_encoder_set_attention_bias": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int]),
+    "vr_encoder_set_attention_slopes": (C.c_int, [_vp, _vp, C.c_int32, C.c_int]),
     "vr_encode": (C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_int, _vp, C.c_int]),
     "vr_encode_spans": (C.c_int, [_vp, _vp, _vp, C.c_int32, _vp, _vp, C.c_int, _vp, C.c_int]),
     "vr_wordpiece_create": (C.c_int, [C.POINTER(C.c_char_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,

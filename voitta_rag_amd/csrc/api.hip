@@ -181,6 +181,13 @@ int vr_encoder_set_attention_bias(vr_engine* e, const float* table, int32_t head
   return encoder_set_attention_bias(e, table, heads, radius, mem);
 }
 
+int vr_encoder_set_attention_slopes(vr_engine* e, const float* slopes, int32_t heads, int mem) {
+  VR_TRY(check_engine(e));
+  if (slopes) VR_TRY(check_mem(mem));
+  std::lock_guard<std::mutex> writer(e->wmu);
+  return encoder_set_attention_slopes(e, slopes, heads, mem);
+}
+
 int vr_encode(vr_engine* e, const int32_t* ids, const int32_t* offsets, int32_t n_seq, int mem,
               float* out, int out_mem) {
   VR_TRY(check_engine(e));

@@ -79,6 +79,8 @@ struct Encoder {
   // vr_encoder_set_attention_bias: [heads, 2 bias_radius + 1] f32, logit += bias[h][clamp(key - query) + bias_radius]
   float* bias = nullptr;
   int bias_radius = 0;
+  // vr_encoder_set_attention_slopes: [heads] f32, logit -= slopes[h] |key - query|; never set together with `bias`
+  float* slopes = nullptr;
   int window_stream_from = 0;    // windowed layers: sequences from this length on take attention_stream_kernel (build_encoder)
   float* posidx = nullptr;  // rotary: int32 position of every token inside its own sequence (positions_kernel)
   bool fuse = true;         // rotate / gate inside the skinny epilogues; VR_ENCODE_FUSE=0 at load time: separate passes
@@ -365,7 +367,7 @@ __global__ __launch_bounds__(256) void embed_ln_kernel(const int32_t* __restrict
   embed_ln_body<SEG, true>(ids, cu, n_seq, tok_base, T, H, vocab, word, pos, type, g, b, eps, x, x_hi, x_lo, pre, stat, seg_b);
 }
 
-// a rotary model: no position table (and no segment B: cross-encoders are not rotary)
+// a rotary model, or one without positions (VR_POS_NONE): no position table (and no segment B: cross-encoders are neither)
 __global__ __launch_bounds__(256) void embed_ln_rotary_kernel(const int32_t* __restrict__ ids,
                                                               const int32_t* __restrict__ cu, int n_seq,
                                                               int tok_base, int T, int H, int vocab,
@@ -3129,7 +3131,7 @@ __device__ __forceinline__ float softmax_base(float m_raw) { return m_raw == -__
 // An additive bias by relative offset (vr_encoder_set_attention_bias): the logit of query i against key j of head h
 // gains table[h][clamp(j - i, -radius, radius) + radius]. BIAS, a template flag the host sets like WIN, keeps every
 // launch without a table on the code it ran before; a bias and a window never meet (a window needs pre-norm, the bias
-// post-norm), so <WIN = false, BIAS = true> is the one new instantiation of each kernel. A block works on one head: it
+// post-norm), so <WIN = false, BIAS = kBiasTable> is the one new instantiation of each kernel. A block works on one head: it
 // stages that head's 2 radius + 1 floats in LDS once, ahead of a barrier it takes anyway (`mul`: log2(e) in the two f16
 // kernels, whose softmax runs in the log2 domain, so that no logit pays a multiply for it). A lane then holds, per
 // query, the row's origin radius - q and reads entry clamp(origin + key, 0, 2 radius): an add, a clamp and an LDS read
@@ -3168,18 +3170,47 @@ __device__ __forceinline__ void bias_tile(f32x4 (&st)[4], float scale2, const Bi
   }
 }
 
+// A linear bias (vr_encoder_set_attention_slopes, ALiBi): the logit of query i against key j of head h loses
+// slope[h] |j - i|, at any distance. The third state of BIAS; like the table it never meets a window, so
+// <WIN = false, BIAS = kBiasSlopes> is one more instantiation of each kernel and the other two states compile to what
+// they did. The kernels take the slopes where they take the table (`bias_table`: [heads] f32 then, `bias_radius`
+// unused). Nothing is staged: a block works on one head, so the slope is one block-uniform value, and the bias is
+// arithmetic on the key index. A lane's keys inside a 64-key tile are kt + 16 t + 4 g + r, so the tile costs one
+// int -> float conversion, of kt + 4 g - q, and every logit a constant add on top of it.
+// The f32 kernel keeps the distance exact (whole numbers below 2^24) and rounds once, in fmaf(|d|, -slope, s scale).
+// The two f16 kernels, whose softmax VALU work bounds them, spend an add and an fma per logit (both packed, two logits
+// an instruction) and the modulus where an unbiased tile spends one multiply: they carry the distance pre-multiplied
+// by the slope (in the log2 domain, as the table is),
+// d' = slope2 (kt + 4 g - q) + slope2 16 t + slope2 r with the six products block-uniform loop invariants (six
+// registers; the sixteen of slope2 (16 t + r) took the streamed kernel from three waves per SIMD to two), and the
+// logit is fmaf(s, scale2, -|d'|) (slope >= 0, so slope |d| = |slope d|; the sign is a source modifier of the packed
+// fma, the modulus is not: one v_and_b32 per logit). Against the exact form that is three roundings more, each
+// 2^-24 of a bias whose logit weighs 2^-bias: far below what the f16 rounding of P leaves. Applied ahead of the
+// key-validity mask and the running maximum, for padded queries and in the CLS tail alike, exactly where the table is.
+constexpr int kBiasNone = 0, kBiasTable = 1, kBiasSlopes = 2;
+__device__ __forceinline__ void slope_tile(f32x4 (&st)[4], float scale2, float slope2, int kt, int g, int q) {
+  const float d0 = slope2 * static_cast<float>(kt + 4 * g - q);
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const float dt = d0 + slope2 * static_cast<float>(16 * t);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) st[t][r] = fmaf(st[t][r], scale2, -fabsf(dt + slope2 * static_cast<float>(r)));
+  }
+}
+
 // One block = 64 queries of one (sequence, head); wave w owns queries 16w..16w+15.
 // S^T = K Q^T is computed with keys on the MFMA rows, so a lane (q = lane & 15, g = lane >> 4)
 // ends up holding the logits of query q against keys 4g..4g+3 of each 16-key tile: exactly the B
 // operand layout of the following O^T += V^T P^T product — no transpose, no LDS round trip for P.
-template <int DH, bool WIN, bool BIAS>
+template <int DH, bool WIN, int BIAS_KIND>
 __global__ __launch_bounds__(256) void attention_kernel(const float* __restrict__ qkv,
                                                         const int32_t* __restrict__ cu, int seq0,
                                                         int tok_base, int H, int qblocks, float scale,
                                                         float* __restrict__ ctx, half_t* __restrict__ ctx_hi,
                                                         half_t* __restrict__ ctx_lo, int window_arg,
                                                         const float* __restrict__ bias_table, int bias_radius) {
-  static_assert(!(WIN && BIAS), "a window needs pre-norm, a bias post-norm");
+  constexpr bool BIAS = BIAS_KIND == kBiasTable, SLOPES = BIAS_KIND == kBiasSlopes;
+  static_assert(!(WIN && BIAS_KIND != kBiasNone), "a window needs pre-norm, a bias post-norm");
   const int window = WIN ? window_arg : 0;
   constexpr int LDK = DH + 4;
   constexpr int NS = DH / 16;  // 16-wide d blocks
@@ -3204,6 +3235,7 @@ __global__ __launch_bounds__(256) void attention_kernel(const float* __restrict_
     stage_bias(sB, bias_table, head, bias_radius, 1.0f, tid, 256);  // (read behind the key loop's first barriers)
   }
   const BiasRow br(sB, q_tok, BIAS ? bias_radius : 0);
+  const float neg_slope = SLOPES ? -bias_table[head] : 0.0f;
   const bool q_valid = q_tok < len;
   const int64_t row3 = 3 * static_cast<int64_t>(H);
 
@@ -3249,12 +3281,20 @@ __global__ __launch_bounds__(256) void attention_kernel(const float* __restrict_
       }
     }
     float mx = -__builtin_inff();
+    if constexpr (SLOPES) {  // (scaled and biased here; the loop below then takes the logits as they are)
+      const float d0 = static_cast<float>(kt + 4 * g - q_tok);
+#pragma unroll
+      for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) st[t][r] = fmaf(fabsf(d0 + static_cast<float>(16 * t + r)), neg_slope, st[t][r] * scale);
+    }
 #pragma unroll
     for (int t = 0; t < 4; ++t)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int key = kt + t * 16 + 4 * g + r;
-        const float v = key < len && wm.sees(key) ? (BIAS ? st[t][r] * scale + br.at(key) : st[t][r] * scale) : -__builtin_inff();
+        const float v = key < len && wm.sees(key) ? (BIAS ? st[t][r] * scale + br.at(key) : SLOPES ? st[t][r] : st[t][r] * scale)
+                                                  : -__builtin_inff();
         st[t][r] = v;
         mx = fmaxf(mx, v);
       }
@@ -3336,12 +3376,13 @@ __global__ __launch_bounds__(256) void attention_kernel(const float* __restrict_
 // `q_limit`: only queries below it are computed (the last layer of a CLS-pooled model needs token 0 only).
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 
-template <int DH, int NW, bool WIN, bool BIAS>
+template <int DH, int NW, bool WIN, int BIAS_KIND>
 __global__ __launch_bounds__(NW * 64) void attention_seq_kernel(const half_t* __restrict__ qkv, const int32_t* __restrict__ cu,
                                                             int seq0, int tok_base, int H, float scale, int q_limit,
                                                             int lds_keys, half_t* __restrict__ ctx_h, int window_arg,
                                                             const float* __restrict__ bias_table, int bias_radius) {
-  static_assert(!(WIN && BIAS), "a window needs pre-norm, a bias post-norm");
+  constexpr bool BIAS = BIAS_KIND == kBiasTable, SLOPES = BIAS_KIND == kBiasSlopes;
+  static_assert(!(WIN && BIAS_KIND != kBiasNone), "a window needs pre-norm, a bias post-norm");
   const int window = WIN ? window_arg : 0;
   constexpr int LDK = DH;       // halfs per staged row: unpadded, 16-byte chunks XOR-swizzled by the row instead
   constexpr int CH = DH / 8;    // 16-byte chunks per row
@@ -3413,6 +3454,7 @@ __global__ __launch_bounds__(NW * 64) void attention_seq_kernel(const half_t* __
   __syncthreads();
 
   const float scale2 = scale * 1.4426950408889634f;  // logits in the log2 domain: the softmax uses v_exp_f32 directly
+  const float slope2 = SLOPES ? bias_table[head] * 1.4426950408889634f : 0.0f;  // (block-uniform)
   // transposed V reads: lane 4q + p of its 16-lane group -> row (key) q, columns 4p .. 4p + 3 of the block
   // (block rows are key0 + q with key0 a multiple of 4: the swizzle of the row depends on 4 g + q alone)
   const int tr_q = (lane & 15) >> 2, tr_p = lane & 3;
@@ -3451,7 +3493,8 @@ __global__ __launch_bounds__(NW * 64) void attention_seq_kernel(const half_t* __
       float mx = -__builtin_inff();
       // BIAS: scaled and biased ahead of both branches, which then take the logits as they are (a factor of 1)
       if constexpr (BIAS) bias_tile(st, scale2, br, kt, g, qt * 16);
-      const float sc = BIAS ? 1.0f : scale2;
+      if constexpr (SLOPES) slope_tile(st, scale2, slope2, kt, g, q_tok);
+      const float sc = BIAS || SLOPES ? 1.0f : scale2;
       // every key of the tile exists and every query of the tile sees all of them: no masks
       if (kt + 64 <= len && (window <= 0 || (kt + 63 - qt * 16 <= window && qt * 16 + 15 - kt <= window))) {
 #pragma unroll
@@ -3541,12 +3584,13 @@ __global__ __launch_bounds__(NW * 64) void attention_seq_kernel(const half_t* __
 // attention_seq_kernel. Grid: heads fastest, then the 128-query blocks of a sequence (`qblocks` of them per sequence);
 // `q_limit` as in attention_seq_kernel — the host launches query block 0 alone for it, and a wave whose queries all
 // lie at or behind it stages and takes every barrier but skips the products.
-template <int DH, int NW, bool WIN, bool BIAS>
+template <int DH, int NW, bool WIN, int BIAS_KIND>
 __global__ __launch_bounds__(NW * 64) void attention_stream_kernel(const half_t* __restrict__ qkv, const int32_t* __restrict__ cu,
                                                                int seq0, int tok_base, int H, int qblocks, float scale,
                                                                int q_limit, half_t* __restrict__ ctx_h, int window_arg,
                                                                const float* __restrict__ bias_table, int bias_radius) {
-  static_assert(!(WIN && BIAS), "a window needs pre-norm, a bias post-norm");
+  constexpr bool BIAS = BIAS_KIND == kBiasTable, SLOPES = BIAS_KIND == kBiasSlopes;
+  static_assert(!(WIN && BIAS_KIND != kBiasNone), "a window needs pre-norm, a bias post-norm");
   const int window = WIN ? window_arg : 0;
   static_assert(NW == 4 && (DH == 64 || DH == 32), "one 16-byte piece of a 64-key tile per thread and CH / NW rounds");
   constexpr int LDK = DH;       // halfs per staged row: unpadded, 16-byte chunks XOR-swizzled by the row
@@ -3627,6 +3671,7 @@ __global__ __launch_bounds__(NW * 64) void attention_stream_kernel(const half_t*
   __syncthreads();
 
   const float scale2 = scale * 1.4426950408889634f;  // logits in the log2 domain: the softmax uses v_exp_f32 directly
+  const float slope2 = SLOPES ? bias_table[head] * 1.4426950408889634f : 0.0f;  // (block-uniform)
   // transposed V reads: lane 4q + p of its 16-lane group -> row (key) q, columns 4p .. 4p + 3 of the block
   const int tr_q = (lane & 15) >> 2, tr_p = lane & 3;
   const int tr_row = tr_q * LDK, tr_sw = vswz(4 * g + tr_q), tr_in = 4 * (tr_p & 1);
@@ -3667,7 +3712,8 @@ __global__ __launch_bounds__(NW * 64) void attention_stream_kernel(const half_t*
         float mx = -__builtin_inff();
         const int qt0 = qw + 16 * i;  // the tile's first query
         if constexpr (BIAS) bias_tile(st[i], scale2, br[i], kt, g, qt0);  // (as in attention_seq_kernel)
-        const float sc = BIAS ? 1.0f : scale2;
+        if constexpr (SLOPES) slope_tile(st[i], scale2, slope2, kt, g, qt0 + qi);
+        const float sc = BIAS || SLOPES ? 1.0f : scale2;
         // every key of the tile exists and every query of the tile sees all of them: no masks
         if (kt + 64 <= len && (window <= 0 || (kt + 63 - qt0 <= window && qt0 + 15 - kt <= window))) {
 #pragma unroll
@@ -3895,7 +3941,8 @@ static int build_encoder(vr_engine* e, void** slot, const vr_bert_desc* d_in, co
   VR_TRY(read_desc(d_in, &desc));
   const vr_bert_desc* d = &desc;
   const int H = d->hidden, I = d->intermediate, L = d->layers;
-  VR_CHECK(d->position == VR_POS_LEARNED || d->position == VR_POS_ROTARY, "unknown position scheme %d", d->position);
+  VR_CHECK(d->position == VR_POS_LEARNED || d->position == VR_POS_ROTARY || d->position == VR_POS_NONE,
+           "unknown position scheme %d", d->position);
   VR_CHECK(d->ffn == VR_FFN_GELU || d->ffn == VR_FFN_SWIGLU || d->ffn == VR_FFN_GEGLU, "unknown ffn kind %d", d->ffn);
   const bool rotary = d->position == VR_POS_ROTARY, gated = d->ffn != VR_FFN_GELU;
   const int per_layer = gated ? 18 : 16;
@@ -3903,6 +3950,11 @@ static int build_encoder(vr_engine* e, void** slot, const vr_bert_desc* d_in, co
            static_cast<double>(d->rope_theta));
   VR_CHECK(d->norm == VR_NORM_POST || d->norm == VR_NORM_PRE, "unknown norm placement %d", d->norm);
   const bool prenorm = d->norm == VR_NORM_PRE;
+  // (a model without positions: refusals of its own, ahead of the ones that tell a table model what pre-norm needs)
+  VR_CHECK(d->position != VR_POS_NONE || !prenorm, "position VR_POS_NONE needs norm VR_NORM_POST (norm %d): pre-norm encoders "
+           "without positions are not implemented", d->norm);
+  VR_CHECK(d->position != VR_POS_NONE || d->window == 0, "position VR_POS_NONE takes no window (window %d): sliding-window "
+           "attention needs rotary positions", d->window);
   VR_CHECK(!prenorm || rotary, "norm VR_NORM_PRE needs position VR_POS_ROTARY (position %d): pre-norm encoders with a "
            "position table are not implemented", d->position);
   VR_CHECK(!prenorm || gated, "norm VR_NORM_PRE needs a gated ffn (ffn %d): pre-norm encoders with the plain GELU "
@@ -3929,7 +3981,7 @@ static int build_encoder(vr_engine* e, void** slot, const vr_bert_desc* d_in, co
     const int in_layer = i < 5 ? -1 : (i - 5) % per_layer;  // null is allowed for a projection's bias, and for the
     const bool bias = in_layer == 1 || in_layer == 3 || in_layer == 5 || in_layer == 7 || in_layer == 11 ||  // unused table
                       in_layer == 13 || in_layer == 17;
-    VR_CHECK(t[i] != nullptr || bias || (i == 1 && rotary), "tensor %d is null", i);
+    VR_CHECK(t[i] != nullptr || bias || (i == 1 && d->position != VR_POS_LEARNED), "tensor %d is null", i);
   }
   int window_stream_from = kWindowStreamFrom;  // (checked here: nothing is replaced when it is refused)
   if (const char* from = getenv("VR_WINDOW_STREAM_FROM")) {
@@ -3946,7 +3998,7 @@ static int build_encoder(vr_engine* e, void** slot, const vr_bert_desc* d_in, co
   enc->fuse = !(getenv("VR_ENCODE_FUSE") && atoi(getenv("VR_ENCODE_FUSE")) == 0);
   const size_t HH = static_cast<size_t>(H) * H;
   VR_TRY(dev_alloc_copy(e, enc, t[0], static_cast<size_t>(d->vocab) * H, mem, &enc->word));
-  if (!rotary) VR_TRY(dev_alloc_copy(e, enc, t[1], static_cast<size_t>(d->max_pos) * H, mem, &enc->pos));
+  if (d->position == VR_POS_LEARNED) VR_TRY(dev_alloc_copy(e, enc, t[1], static_cast<size_t>(d->max_pos) * H, mem, &enc->pos));
   std::vector<float2> rope_host[2];  // (live until the synchronisation at the end: they are sources of async copies)
   auto rope_table = [&](float theta, std::vector<float2>& host, float2** out) -> int {
     // (cos, sin)(p * theta^(-2i/d_h)) in f64, stored as f32
@@ -4094,6 +4146,8 @@ int encoder_set_attention_bias(vr_engine* e, const float* table, int heads, int 
              "an attention bias needs position VR_POS_LEARNED and norm VR_NORM_POST (position %d, norm %d)", enc->d.position,
              enc->d.norm);
     VR_CHECK(heads == enc->d.heads, "bias table of %d heads for an encoder of %d", heads, enc->d.heads);
+    VR_CHECK(!enc->slopes, "the encoder has attention slopes (vr_encoder_set_attention_slopes): remove them before a "
+             "bias table is set");
     VR_CHECK(radius >= 1 && radius <= kMaxBiasRadius, "radius %d must lie in 1..%d", radius, kMaxBiasRadius);
     const size_t n = static_cast<size_t>(heads) * (2 * static_cast<size_t>(radius) + 1);
     VR_HIP(hipMalloc(reinterpret_cast<void**>(&fresh), n * sizeof(float)));
@@ -4114,6 +4168,49 @@ int encoder_set_attention_bias(vr_engine* e, const float* table, int heads, int 
   }
   enc->bias = fresh;
   enc->bias_radius = fresh ? radius : 0;
+  if (fresh) enc->owned.push_back(fresh);
+  return 0;
+}
+
+// The embedder's linear attention bias (vr_encoder_set_attention_slopes), as encoder_set_attention_bias: every check
+// runs before anything changes, and the captured graphs, which hold the pointer and the kernels' instantiation, go.
+int encoder_set_attention_slopes(vr_engine* e, const float* slopes, int heads, int mem) {
+  Encoder* enc = static_cast<Encoder*>(e->encoder);
+  VR_CHECK(enc, "no encoder loaded");
+  float* fresh = nullptr;
+  if (slopes) {
+    VR_CHECK((enc->d.position == VR_POS_LEARNED || enc->d.position == VR_POS_NONE) && enc->d.norm == VR_NORM_POST,
+             "an attention bias needs position VR_POS_LEARNED and norm VR_NORM_POST (position %d, norm %d)", enc->d.position,
+             enc->d.norm);
+    VR_CHECK(heads == enc->d.heads, "%d attention slopes for an encoder of %d heads", heads, enc->d.heads);
+    VR_CHECK(!enc->bias, "the encoder has an attention bias table (vr_encoder_set_attention_bias): remove it before "
+             "slopes are set");
+    std::vector<float> host(static_cast<size_t>(heads));
+    if (mem == VR_MEM_HOST) {
+      std::copy(slopes, slopes + heads, host.begin());
+    } else {
+      VR_HIP(hipMemcpyAsync(host.data(), slopes, host.size() * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+      VR_HIP(hipStreamSynchronize(e->stream));
+    }
+    for (int h = 0; h < heads; ++h)
+      VR_CHECK(std::isfinite(host[h]) && host[h] >= 0.0f && host[h] <= 1e30f,
+               "attention slope %g of head %d must be finite and lie in 0..1e30", static_cast<double>(host[h]), h);
+    VR_HIP(hipMalloc(reinterpret_cast<void**>(&fresh), host.size() * sizeof(float)));
+    hipError_t err = hipMemcpyAsync(fresh, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice, e->stream);
+    if (err == hipSuccess) err = hipStreamSynchronize(e->stream);  // (`host` may go; passes that read the old slopes are over)
+    if (err != hipSuccess) {
+      (void)hipFree(fresh);
+      VR_HIP(err);
+    }
+  } else {
+    VR_HIP(hipStreamSynchronize(e->stream));
+  }
+  invalidate_graphs(enc);
+  if (enc->slopes) {
+    enc->owned.erase(std::remove(enc->owned.begin(), enc->owned.end(), enc->slopes), enc->owned.end());
+    (void)hipFree(enc->slopes);
+  }
+  enc->slopes = fresh;
   if (fresh) enc->owned.push_back(fresh);
   return 0;
 }
@@ -4211,14 +4308,17 @@ static int launch_attention(vr_engine* e, Encoder* enc, const int32_t* cu_dev, i
   const int qblocks = (max_len + 63) / 64;
   const float scale = 1.0f / sqrtf(static_cast<float>(dh));
   // the kernels' WIN and BIAS flags: a launch without a window or a bias instantiates the code that never knew one
-  // (never both: vr_encoder_set_attention_bias refuses the pre-norm descriptions, and only those have a window)
-  const float* bias = enc->bias;
+  // (never both: vr_encoder_set_attention_bias / _slopes refuse the pre-norm descriptions, and only those have a
+  // window). BIAS: none, the table, or the slopes, which travel in the table's argument (the radius is unused then)
+  const float* bias = enc->bias ? enc->bias : enc->slopes;
+  const bool table = enc->bias != nullptr;
   const int radius = enc->bias_radius;
   VR_CHECK(!(bias && window > 0), "an attention bias and a window %d cannot meet", window);
   auto windowed = [&](auto launch) {
-    if (bias) launch(std::false_type{}, std::true_type{});
-    else if (window > 0) launch(std::true_type{}, std::false_type{});
-    else launch(std::false_type{}, std::false_type{});
+    if (table) launch(std::false_type{}, std::integral_constant<int, kBiasTable>{});
+    else if (bias) launch(std::false_type{}, std::integral_constant<int, kBiasSlopes>{});
+    else if (window > 0) launch(std::true_type{}, std::integral_constant<int, kBiasNone>{});
+    else launch(std::false_type{}, std::integral_constant<int, kBiasNone>{});
   };
   const int qb = tail ? 1 : qblocks;  // tail: only the query block that holds token 0 of every sequence
   dim3 agrid(static_cast<unsigned>(n_seq * qb), static_cast<unsigned>(nh));
@@ -4227,8 +4327,8 @@ static int launch_attention(vr_engine* e, Encoder* enc, const int32_t* cu_dev, i
   // while the longest sequence's rows fit what a workgroup may have on this device; beyond that (max_pos admits up
   // to 8192 tokens) attention_stream_kernel, which streams the keys in 64-row tiles through static LDS
   const int lds_keys = (max_len + 15) & ~15;
-  // (a bias: the head's table behind the staged rows — the staged-or-streamed decision counts it)
-  const size_t lds_bytes = static_cast<size_t>(2) * lds_keys * dh * sizeof(half_t) + (bias ? (2 * radius + 1) * sizeof(float) : 0);
+  // (a bias table: the head's row behind the staged rows — the staged-or-streamed decision counts it; slopes add no byte)
+  const size_t lds_bytes = static_cast<size_t>(2) * lds_keys * dh * sizeof(half_t) + (table ? (2 * radius + 1) * sizeof(float) : 0);
   static size_t lds_limit = 0;
   if (plain && lds_limit == 0) {
     hipDeviceProp_t prop;
@@ -4240,20 +4340,23 @@ static int launch_attention(vr_engine* e, Encoder* enc, const int32_t* cu_dev, i
     static size_t lds_allowed[2] = {0, 0};  // per instantiation: raised above the 64 KiB default when a sequence needs it
     const int which = dh == 64 ? 0 : 1;
     if (lds_bytes > 65536 && lds_bytes > lds_allowed[which]) {
-      for (const void* f : {reinterpret_cast<const void*>(&attention_seq_kernel<64, 4, false, false>),
-                            reinterpret_cast<const void*>(&attention_seq_kernel<64, 4, true, false>),
-                            reinterpret_cast<const void*>(&attention_seq_kernel<64, 4, false, true>)})
+      for (const void* f : {reinterpret_cast<const void*>(&attention_seq_kernel<64, 4, false, kBiasNone>),
+                            reinterpret_cast<const void*>(&attention_seq_kernel<64, 4, true, kBiasNone>),
+                            reinterpret_cast<const void*>(&attention_seq_kernel<64, 4, false, kBiasTable>),
+                            reinterpret_cast<const void*>(&attention_seq_kernel<64, 4, false, kBiasSlopes>)})
         if (dh == 64) VR_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_bytes)));
-      for (const void* f : {reinterpret_cast<const void*>(&attention_seq_kernel<32, 4, false, false>),
-                            reinterpret_cast<const void*>(&attention_seq_kernel<32, 4, true, false>),
-                            reinterpret_cast<const void*>(&attention_seq_kernel<32, 4, false, true>)})
+      for (const void* f : {reinterpret_cast<const void*>(&attention_seq_kernel<32, 4, false, kBiasNone>),
+                            reinterpret_cast<const void*>(&attention_seq_kernel<32, 4, true, kBiasNone>),
+                            reinterpret_cast<const void*>(&attention_seq_kernel<32, 4, false, kBiasTable>),
+                            reinterpret_cast<const void*>(&attention_seq_kernel<32, 4, false, kBiasSlopes>)})
         if (dh != 64) VR_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_bytes)));
       lds_allowed[which] = lds_bytes;
     }
     const dim3 sgrid(static_cast<unsigned>(n_seq) * static_cast<unsigned>(nh));
     const int q_limit = tail ? 16 : max_len;
     windowed([&](auto W, auto B) {
-      constexpr bool kWin = decltype(W)::value, kBias = decltype(B)::value;
+      constexpr bool kWin = decltype(W)::value;
+      constexpr int kBias = decltype(B)::value;
       if (dh == 64)
         hipLaunchKernelGGL((attention_seq_kernel<64, 4, kWin, kBias>), sgrid, dim3(256), lds_bytes, s, reinterpret_cast<const half_t*>(enc->qkv),
                            cu_dev, seq0, tok_base, H, scale, q_limit, lds_keys, ch, window, bias, radius);
@@ -4266,7 +4369,8 @@ static int launch_attention(vr_engine* e, Encoder* enc, const int32_t* cu_dev, i
     const dim3 sgrid(static_cast<unsigned>(n_seq) * static_cast<unsigned>(qb128) * static_cast<unsigned>(nh));
     const int q_limit = tail ? 16 : max_len;
     windowed([&](auto W, auto B) {
-      constexpr bool kWin = decltype(W)::value, kBias = decltype(B)::value;
+      constexpr bool kWin = decltype(W)::value;
+      constexpr int kBias = decltype(B)::value;
       if (dh == 64)
         hipLaunchKernelGGL((attention_stream_kernel<64, 4, kWin, kBias>), sgrid, dim3(256), 0, s, reinterpret_cast<const half_t*>(enc->qkv),
                            cu_dev, seq0, tok_base, H, qb128, scale, q_limit, ch, window, bias, radius);
@@ -4276,7 +4380,8 @@ static int launch_attention(vr_engine* e, Encoder* enc, const int32_t* cu_dev, i
     });
   } else {
     windowed([&](auto W, auto B) {
-      constexpr bool kWin = decltype(W)::value, kBias = decltype(B)::value;
+      constexpr bool kWin = decltype(W)::value;
+      constexpr int kBias = decltype(B)::value;
       if (dh == 64)
         hipLaunchKernelGGL((attention_kernel<64, kWin, kBias>), agrid, dim3(256), 0, s, enc->qkv, cu_dev, seq0, tok_base, H, qb, scale,
                            enc->ctx, ch, cl, window, bias, radius);
@@ -4517,7 +4622,7 @@ static int forward_chunk(vr_engine* e, Encoder* enc, const int32_t* ids_dev, con
     hipLaunchKernelGGL((embed_ln_kernel<true>), dim3(row_blocks), dim3(256), 0, s, ids_dev, cu_dev, n_seq_total,
                        tok_base, T, H, d.vocab, enc->word, enc->pos, enc->type, enc->lng, enc->lnb, d.eps,
                        lnfuse ? nullptr : enc->x, xh, xl, lnfuse ? enc->x : nullptr, lnfuse ? stat_b : nullptr, seg_dev);
-  else if (d.position == VR_POS_ROTARY)
+  else if (d.position != VR_POS_LEARNED)  // rotary, or no positions at all: the body that reads no table
     hipLaunchKernelGGL(embed_ln_rotary_kernel, dim3(row_blocks), dim3(256), 0, s, ids_dev, cu_dev, n_seq_total,
                        tok_base, T, H, d.vocab, enc->word, enc->type, enc->lng, enc->lnb, d.eps, lnfuse ? nullptr : enc->x, xh, xl,
                        lnfuse ? enc->x : nullptr, lnfuse ? stat_b : nullptr);

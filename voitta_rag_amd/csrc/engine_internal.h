@@ -614,6 +614,7 @@ int sparse_lookup_df(vr_engine* e, const int32_t* ids_host, int n, int32_t* out_
 // ---- encoder.hip
 int encoder_load(vr_engine* e, const vr_bert_desc* d, const void* const* tensors, int n_tensors, int mem);
 int encoder_set_attention_bias(vr_engine* e, const float* table, int heads, int radius, int mem);
+int encoder_set_attention_slopes(vr_engine* e, const float* slopes, int heads, int mem);
 int encoder_encode(vr_engine* e, const int32_t* ids, const int32_t* offsets, int n_seq, int mem,
                    float* out, int out_mem);
 // one row per token span instead of per sequence (vr_encode_spans); n_expected >= 0: the span count the caller announced

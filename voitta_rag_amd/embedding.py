@@ -68,6 +68,8 @@ def read_encoder_config(path: str) -> dict:
         return _read_mpnet_config(path, cfg)
     if kind not in ("bert", "xlm-roberta"):
         raise ValueError(f"unsupported model_type {kind}: BERT, XLM-RoBERTa, MPNet, nomic_bert and modernbert encoders only")
+    if kind == "bert" and cfg.get("position_embedding_type", "absolute") == "alibi":
+        return _read_alibi_config(path, cfg)
     if cfg.get("hidden_act", "gelu") != "gelu" or cfg.get("position_embedding_type", "absolute") != "absolute":
         raise ValueError("only exact-erf GELU and absolute position embeddings are implemented")
     pos_start = int(cfg.get("pad_token_id", 1)) + 1 if kind == "xlm-roberta" else 0
@@ -140,6 +142,39 @@ def _read_mpnet_config(path: str, cfg: dict) -> dict:
                          pooling=pooling, normalize=normalize, eps=cfg.get("layer_norm_eps", 1e-5),
                          precision=os.environ.get("VOITTA_ENCODER_PRECISION", "f16"))
     return {"desc": desc, "max_seq": max_seq, "pos_start": pos_start, "config": cfg}
+
+
+def _read_alibi_config(path: str, cfg: dict) -> dict:
+    """model_type bert with position_embedding_type alibi (jina-embeddings-v2-small-en / -base-en, JinaBert): a
+    post-LayerNorm BERT without any position in its embeddings, a GeGLU FFN, and a linear attention bias of
+    -slope_h |key - query| per head (encoder.alibi_slopes), which is what lets it run past its training length.
+    Sequences are capped at seq_cap() (these checkpoints declare 8192): truncation is well defined without a table.
+    The variant with LayerNorms on Q and K (-code, -de, -es, -zh) has the same config; encoder.jina_slots refuses its
+    weights by name."""
+    ffn = cfg.get("feed_forward_type", "original")
+    if ffn != "geglu":
+        raise ValueError(f"feed_forward_type {ffn!r} is not implemented: an alibi encoder's FFN is the gated 'geglu'")
+    act = cfg.get("hidden_act", "gelu")
+    if act != "gelu":
+        raise ValueError(f"hidden_act {act!r} is not implemented: the gate of an alibi encoder's FFN is the exact-erf GELU")
+    heads = int(cfg["num_attention_heads"])
+    declared = int(cfg.get("max_position_embeddings", 8192))
+    pooling, normalize, max_seq = _read_modules(path, declared)
+    max_seq = min(max_seq, declared)
+    cap = seq_cap()
+    if max_seq > cap:
+        logger.warning("%s declares sequences of up to %d tokens; the engine runs at most %d: longer texts are "
+                       "truncated to %d tokens (%s raises the cap, up to %d)", path, max_seq, cap, cap, SEQ_CAP_VARIABLE,
+                       MAX_SEQ_LENGTH_LIMIT)
+        max_seq = cap
+    desc = _enc.BertDesc(layers=cfg["num_hidden_layers"], hidden=cfg["hidden_size"], heads=heads,
+                         intermediate=cfg["intermediate_size"], vocab=cfg["vocab_size"],
+                         max_pos=max_seq,  # no table: the longest accepted sequence
+                         type_vocab=cfg.get("type_vocab_size", 2), pooling=pooling, normalize=normalize,
+                         eps=cfg.get("layer_norm_eps", 1e-12),
+                         precision=os.environ.get("VOITTA_ENCODER_PRECISION", "f16"), position="none", ffn="geglu",
+                         attention_slopes=_enc.alibi_slopes(heads))
+    return {"desc": desc, "max_seq": max_seq, "pos_start": 0, "config": cfg}
 
 
 def _read_rope_config(path: str, cfg: dict) -> dict:

@@ -67,7 +67,9 @@ class BertDesc:
     normalize: bool = True
     eps: float = 1e-12
     precision: str = "f32"  # "f32" (exact f32 MFMA) | "f16x3" (split-precision f16 MFMA, f32-class accuracy)
-    position: str = "learned"  # "learned" (a position table) | "rotary" (max_pos = length of the cos/sin table)
+    # "learned" (a position table) | "rotary" (max_pos = length of the cos/sin table) | "none" (no position in the
+    # embeddings or in Q and K: max_pos = the longest sequence; ALiBi models, whose position is in attention_slopes)
+    position: str = "learned"
     rope_theta: float = 0.0
     ffn: str = "gelu"  # "gelu" | "swiglu" | "geglu" (down(act(gate(x)) * up(x)), act = SiLU / exact GELU)
     norm: str = "post"  # "post" (x = LN(x + f(x))) | "pre" (x = x + f(LN(x)), a final LayerNorm: the ModernBERT family)
@@ -77,6 +79,10 @@ class BertDesc:
     # additive attention bias by relative offset, f32 [heads, 2 * radius + 1] (MPNet: mpnet_bias_table); not a field of
     # vr_bert_desc: load_encoder hands it to vr_encoder_set_attention_bias once the model is loaded
     attention_bias: object = field(default=None, compare=False, repr=False)
+    # linear attention bias, f32 [heads]: the logit of head h loses attention_slopes[h] * |key - query| (ALiBi:
+    # alibi_slopes); like attention_bias not a field of vr_bert_desc: load_encoder hands it to
+    # vr_encoder_set_attention_slopes once the model is loaded
+    attention_slopes: object = field(default=None, compare=False, repr=False)
 
     @property
     def rotary(self) -> bool:
@@ -102,7 +108,7 @@ class BertDesc:
         if self.precision not in codes:
             raise ValueError(f"unknown encoder precision {self.precision!r}")
         d.precision = codes[self.precision]
-        positions = {"learned": _lib.VR_POS_LEARNED, "rotary": _lib.VR_POS_ROTARY}
+        positions = {"learned": _lib.VR_POS_LEARNED, "rotary": _lib.VR_POS_ROTARY, "none": _lib.VR_POS_NONE}
         ffns = {"gelu": _lib.VR_FFN_GELU, "swiglu": _lib.VR_FFN_SWIGLU, "geglu": _lib.VR_FFN_GEGLU}
         if self.position not in positions:
             raise ValueError(f"unknown position scheme {self.position!r}")
@@ -297,6 +303,90 @@ def mpnet_slots(state: dict, desc: "BertDesc", pos_start: int = 2):
     return out, mpnet_bias_table(get("encoder.relative_attention_bias.weight"))
 
 
+def alibi_slopes(heads: int) -> np.ndarray:
+    """The standard ALiBi slope of every head, float32 [heads] (Press et al., as BLOOM's build_alibi_tensor and
+    JinaBert compute them): for a power-of-two n the geometric sequence start^(i + 1), start = 2^(-8/n); otherwise
+    the sequence of the largest power of two below n, followed by every second slope of the sequence for twice that."""
+    if heads < 1:
+        raise ValueError(f"alibi_slopes of {heads} heads")
+
+    def power_of_two(n):
+        start = 2.0 ** (-8.0 / n)
+        return [start ** (i + 1) for i in range(n)]
+
+    closest = 1 << (heads.bit_length() - 1)
+    slopes = power_of_two(closest)
+    if closest != heads:
+        slopes += power_of_two(2 * closest)[0::2][:heads - closest]
+    return np.asarray(slopes, dtype=np.float32)
+
+
+# An ALiBi encoder (jina-embeddings-v2: model_type bert, position_embedding_type alibi) in the slot order of
+# vr_encoder_load: a post-LayerNorm BERT body without a position table whose FFN is gated (GeGLU) and carries a bias
+# on its down projection only. The names jina_slots files a JinaBert state dict under.
+JINA_LAYER_SUFFIXES = [
+    "attention.self.query.weight", "attention.self.query.bias",
+    "attention.self.key.weight", "attention.self.key.bias",
+    "attention.self.value.weight", "attention.self.value.bias",
+    "attention.output.dense.weight", "attention.output.dense.bias",
+    "attention.output.LayerNorm.weight", "attention.output.LayerNorm.bias",
+    "mlp.up_proj.weight", None, "mlp.down_proj.weight", "mlp.down_proj.bias",
+    "mlp.layernorm.weight", "mlp.layernorm.bias",
+    "mlp.gate_proj.weight", None,
+]
+
+
+def jina_slots(state: dict, desc: "BertDesc"):
+    """A JinaBertModel state dict (any key prefix) -> (slot names, state under those names): the 18-slot gated layout
+    with no position table. mlp.gated_layers.weight is [2I, H] without a bias: rows [0, I) are what the activation is
+    applied to (the GATE), rows [I, 2I) the UP projection; mlp.wo is the down projection and mlp.layernorm the output
+    LayerNorm. pooler.*, cls.* and position_ids are ignored; ANY other tensor left over is refused by name — the
+    -code, -de, -es and -zh checkpoints carry LayerNorms on Q and K (layer_norm_q / layer_norm_k), which is another
+    model and must not load as this one."""
+    used = set()
+
+    def get(name):
+        hits = [k for k in state if k == name or k.endswith("." + name)]
+        if len(hits) != 1:
+            raise KeyError(f"weight '{name}' not found (or ambiguous) in state dict: {hits[:3]}")
+        used.add(hits[0])
+        return state[hits[0]]
+
+    out = {}
+    for name in ("embeddings.word_embeddings.weight", "embeddings.token_type_embeddings.weight",
+                 "embeddings.LayerNorm.weight", "embeddings.LayerNorm.bias"):
+        out[name] = get(name)
+    inter = desc.intermediate
+    for i in range(desc.layers):
+        p = f"encoder.layer.{i}."
+        for s in JINA_LAYER_SUFFIXES[:10]:
+            out[p + s] = get(p + s)
+        gated = get(p + "mlp.gated_layers.weight")
+        if tuple(gated.shape) != (2 * inter, desc.hidden):
+            raise ValueError(f"weight '{p}mlp.gated_layers.weight' has shape {tuple(gated.shape)}, the model description "
+                             f"implies {(2 * inter, desc.hidden)}")
+        out[p + "mlp.gate_proj.weight"], out[p + "mlp.up_proj.weight"] = gated[:inter], gated[inter:]
+        out[p + "mlp.down_proj.weight"] = get(p + "mlp.wo.weight")
+        out[p + "mlp.down_proj.bias"] = get(p + "mlp.wo.bias")
+        out[p + "mlp.layernorm.weight"] = get(p + "mlp.layernorm.weight")
+        out[p + "mlp.layernorm.bias"] = get(p + "mlp.layernorm.bias")
+
+    def ignored(key):
+        parts = key.split(".")
+        return "pooler" in parts or "cls" in parts or parts[-1] == "position_ids"
+
+    extra = sorted(k for k in state if k not in used and not ignored(k))
+    if extra:
+        raise ValueError(f"not a JinaBert (jina-embeddings-v2 -small-en / -base-en) state dict: unexpected tensors {extra[:4]}"
+                         f"{' ...' if len(extra) > 4 else ''}; the variant with LayerNorms on Q and K (layer_norm_q / "
+                         "layer_norm_k: the -code, -de, -es and -zh checkpoints) is not implemented")
+    names = ["embeddings.word_embeddings.weight", None, "embeddings.token_type_embeddings.weight",
+             "embeddings.LayerNorm.weight", "embeddings.LayerNorm.bias"]
+    for i in range(desc.layers):
+        names += [None if s is None else f"encoder.layer.{i}.{s}" for s in JINA_LAYER_SUFFIXES]
+    return names, out
+
+
 # a BertForSequenceClassification's head, after the encoder's tensors (vr_reranker_load)
 HEAD_NAMES = ["pooler.dense.weight", "pooler.dense.bias", "classifier.weight", "classifier.bias"]
 # a ModernBertForSequenceClassification's: classifier(norm(gelu(dense(pooled row)))), six tensors
@@ -353,9 +443,16 @@ def _find(state: dict, suffix: str):
 def load_encoder(engine, desc: BertDesc, state: dict) -> None:
     """state: HF BertModel state dict (any key prefix), values NumPy arrays or torch tensors.
     Tensors on the engine's GPU are passed as device pointers, everything else as host memory.
-    A description that carries an attention_bias table (MPNet, see mpnet_slots) sets it once the model is loaded."""
+    A description that carries an attention_bias table (MPNet, see mpnet_slots) or attention_slopes (ALiBi) sets them
+    once the model is loaded. position "none": a gated description reads a JinaBert state dict (jina_slots), a GELU
+    one a BERT state dict without its position table."""
     if desc.prenorm:
         names, state = modernbert_slots(state, desc)
+    elif desc.position == "none":
+        if desc.gated:
+            names, state = jina_slots(state, desc)
+        else:
+            names = [None if n == EMB_SUFFIXES[1] else n for n in tensor_names(desc.layers)]
     else:
         if desc.rotary or desc.gated:
             state = native_rope_state(state)
@@ -364,6 +461,8 @@ def load_encoder(engine, desc: BertDesc, state: dict) -> None:
     engine.encoder_desc = desc
     if desc.attention_bias is not None:
         engine.set_attention_bias(desc.attention_bias)
+    if desc.attention_slopes is not None:
+        engine.set_attention_slopes(desc.attention_slopes)
 
 
 def load_reranker(engine, desc: BertDesc, state: dict) -> None:

@@ -263,6 +263,21 @@ class Engine:
         check(self._lib.vr_encoder_set_attention_bias(self._h, C.c_void_p(table.ctypes.data), table.shape[0],
                                                       (table.shape[1] - 1) // 2, VR_MEM_HOST))
 
+    def set_attention_slopes(self, slopes) -> None:
+        """The loaded encoder's linear attention bias (vr_encoder_set_attention_slopes): slopes[heads], f32, each finite
+        and >= 0; the logit of query i against key j of head h loses slopes[h] * |j - i| in every layer (ALiBi, see
+        encoder.alibi_slopes). None removes them. Loading an encoder resets them; slopes and a table never coexist."""
+        if slopes is None:
+            check(self._lib.vr_encoder_set_attention_slopes(self._h, None, 0, VR_MEM_HOST))
+            return
+        if hasattr(slopes, "detach"):
+            slopes = slopes.detach().cpu().numpy()
+        slopes = np.ascontiguousarray(slopes, dtype=np.float32)
+        if slopes.ndim != 1:
+            raise ValueError(f"attention slopes of shape {slopes.shape}: expected [heads]")
+        check(self._lib.vr_encoder_set_attention_slopes(self._h, C.c_void_p(slopes.ctypes.data), slopes.shape[0],
+                                                        VR_MEM_HOST))
+
     def _index_batch(self, wp_ids, wp_off, spans, bm_ids, bm_off, folder_ids, index_folder_ids, created, modified,
                      k, b, avg_len) -> int:
         dev = _is_device_tensor(wp_ids)
