@@ -217,9 +217,37 @@ int vr_encoder_set_attention_bias(vr_engine* e, const float* table, int32_t head
  * the encoder as it was. NULL slopes removes them. vr_encoder_load resets them. The reranker never has any. */
 int vr_encoder_set_attention_slopes(vr_engine* e, const float* slopes, int32_t heads, int mem);
 
+/* The post-pooling head of the loaded ENCODER: what a sentence-transformers pipeline runs behind Pooling (Dense and
+ * LayerNorm modules, Normalize) and SentenceTransformer(truncate_dim=...). With a head a row is computed as
+ *   1. the pooled row, un-normalised (vr_encode_spans: the span mean);
+ *   2. the stages in order, all f32 whatever desc.precision is;
+ *   3. if desc.normalize: x / max(|x|, 1e-12) over the WHOLE width of the last stage (or of the pooled row);
+ *   4. the leading truncate_dim columns (0: all of them), not normalised again.
+ * The OUTPUT WIDTH of the encoder is then truncate_dim, or else the last stage's out_dim, or else desc.hidden: vr_encode
+ * and vr_encode_spans write rows of that width, and vr_index_batch(_spans) and vr_query_text(_batch), with their
+ * Unigram and BPE variants, compare that width with the store dimension.
+ * With no stages (pure truncation) a row is bit for bit the leading truncate_dim columns of the headless row.
+ * Limits: 0 <= n_stages <= 4; every in_dim / out_dim a multiple of 16 in 16..1024; stages[0].in_dim == desc.hidden;
+ * each stage's in_dim equals its predecessor's out_dim; a LayerNorm stage has in_dim == out_dim and eps > 0;
+ * truncate_dim is 0 or a multiple of 16 not above the last width. weight / bias are f32 in `mem`, copied.
+ * stages == NULL with truncate_dim == 0 removes the head. Every check runs before anything changes: a refused call
+ * leaves the encoder as it was. vr_encoder_load resets the head. The reranker never has one. */
+#define VR_HEAD_DENSE 0      /* y = act(W x + b): weight [out_dim, in_dim] row-major, bias [out_dim] or NULL */
+#define VR_HEAD_LAYERNORM 1  /* y = (x - mean) / sqrt(var + eps) * weight + bias over in_dim (= out_dim) units; bias may be NULL */
+#define VR_ACT_IDENTITY 0
+#define VR_ACT_TANH 1
+typedef struct vr_head_stage {
+  int32_t struct_size, kind, in_dim, out_dim, activation;
+  float eps;
+  const float* weight;
+  const float* bias;
+} vr_head_stage;
+int vr_encoder_set_head(vr_engine* e, const vr_head_stage* stages, int32_t n_stages, int32_t truncate_dim, int mem);
+
 /* ids: concatenated WordPiece ids of n_seq sequences ([CLS] ... [SEP] already added, truncated
  * to max_pos by the tokenizer); offsets: n_seq+1 int32, offsets[0] = 0. Both in `mem`.
- * out: n_seq x H f32 sentence embeddings in `out_mem`. */
+ * out: n_seq x W f32 sentence embeddings in `out_mem`, W the encoder's output width (desc.hidden unless
+ * vr_encoder_set_head changed it). */
 int vr_encode(vr_engine* e, const int32_t* ids, const int32_t* offsets, int32_t n_seq, int mem,
               float* out, int out_mem);
 
@@ -229,11 +257,13 @@ int vr_encode(vr_engine* e, const int32_t* ids, const int32_t* offsets, int32_t 
  *             (possibly none: such a sequence only provides context)
  *   span_tok  2 int32 per span, (begin, end): token positions inside the span's own sequence,
  *             0 <= begin < end <= len. Spans of a sequence may overlap, repeat and come in any order.
- * ids / offsets / span_off / span_tok in `mem`. out: span_off[n_seq] x H f32 in `out_mem`; row s is the mean over
- * t in [begin, end) of the final hidden state of token t, summed in token order, then (desc.normalize) divided by
- * max(|x|, 1e-12). desc.pooling is ignored: the forward pass runs as a mean-pooled model's does, so one span [0, len)
- * on a mean-pooled model gives vr_encode's row bit for bit. Host arrays are checked before any work is queued;
- * vr_last_error names the offending sequence and span. No spans, or n_seq <= 0: returns 0 and writes nothing. */
+ * ids / offsets / span_off / span_tok in `mem`. out: span_off[n_seq] x W f32 in `out_mem` (W: the encoder's output
+ * width, H without a head); row s is the mean over t in [begin, end) of the final hidden state of token t, summed in
+ * token order, then (desc.normalize) divided by max(|x|, 1e-12) — with a head (vr_encoder_set_head) the mean goes
+ * through its stages first and is cut last. desc.pooling is ignored: the forward pass runs as a mean-pooled model's
+ * does, so one span [0, len) on a mean-pooled model gives vr_encode's row bit for bit. Host arrays are checked before
+ * any work is queued; vr_last_error names the offending sequence and span. No spans, or n_seq <= 0: returns 0 and
+ * writes nothing. */
 int vr_encode_spans(vr_engine* e, const int32_t* ids, const int32_t* offsets, int32_t n_seq,
                     const int32_t* span_off, const int32_t* span_tok, int mem,
                     float* out, int out_mem);

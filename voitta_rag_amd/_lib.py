@@ -68,6 +68,23 @@ class VrBertDesc(C.Structure):
     ]
 
 
+class VrHeadStage(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("kind", C.c_int32),
+        ("in_dim", C.c_int32),
+        ("out_dim", C.c_int32),
+        ("activation", C.c_int32),
+        ("eps", C.c_float),
+        ("weight", C.c_void_p),
+        ("bias", C.c_void_p),
+    ]
+
+
+VR_HEAD_DENSE = 0
+VR_HEAD_LAYERNORM = 1
+VR_ACT_IDENTITY = 0
+VR_ACT_TANH = 1
 VR_PRECISION_F32 = 0
 VR_PRECISION_F16X3 = 1
 VR_PRECISION_F16 = 2
@@ -106,6 +123,7 @@ SIGNATURES = {
     "vr_encoder_load": (C.c_int, [_vp, C.POINTER(VrBertDesc), C.POINTER(_vp), C.c_int32, C.c_int]),
     "vr_encoder_set_attention_bias": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int]),
     "vr_encoder_set_attention_slopes": (C.c_int, [_vp, _vp, C.c_int32, C.c_int]),
+    "vr_encoder_set_head": (C.c_int, [_vp, C.POINTER(VrHeadStage), C.c_int32, C.c_int32, C.c_int]),
     "vr_encode": (C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_int, _vp, C.c_int]),
     "vr_encode_spans": (C.c_int, [_vp, _vp, _vp, C.c_int32, _vp, _vp, C.c_int, _vp, C.c_int]),
     "vr_wordpiece_create": (C.c_int, [C.POINTER(C.c_char_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,

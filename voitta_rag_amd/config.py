@@ -43,6 +43,15 @@ class Settings:
         # that expect them and that the reference's e5 rule does not know (nomic: "search_document: " / "search_query: ")
         self.embed_passage_prefix: str = os.getenv("VOITTA_EMBED_PASSAGE_PREFIX", "")
         self.embed_query_prefix: str = os.getenv("VOITTA_EMBED_QUERY_PREFIX", "")
+        # the leading columns of the model's output that are the embedding (opt-in; unset or empty = all of them):
+        # SentenceTransformer's truncate_dim, for models trained so that a prefix of their vector still ranks well
+        # (Matryoshka). A multiple of 16 within the model's width, checked when the model is read; EMBEDDING_DIMENSION
+        # must then be this width
+        trunc = os.getenv("VOITTA_EMBED_TRUNCATE_DIM", "").strip()
+        self.embed_truncate_dim: int = int(trunc) if trunc else 0
+        if trunc and (self.embed_truncate_dim < 16 or self.embed_truncate_dim % 16):
+            raise ValueError(f"VOITTA_EMBED_TRUNCATE_DIM={trunc}: accepted values are the multiples of 16 from 16 to the "
+                             "model's output width (unset = no truncation)")
         # the longest sequence, in tokens, that an embedder or reranker may run (opt-in above 512): a rotary checkpoint
         # that declares more is truncated to it, an XLM-R one is refused; past 640 tokens attention streams its keys
         self.max_seq_length: int = int(os.getenv("VOITTA_MAX_SEQ_LENGTH", str(DEFAULT_MAX_SEQ_LENGTH)))

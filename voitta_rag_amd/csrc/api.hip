@@ -188,6 +188,13 @@ int vr_encoder_set_attention_slopes(vr_engine* e, const float* slopes, int32_t h
   return encoder_set_attention_slopes(e, slopes, heads, mem);
 }
 
+int vr_encoder_set_head(vr_engine* e, const vr_head_stage* stages, int32_t n_stages, int32_t truncate_dim, int mem) {
+  VR_TRY(check_engine(e));
+  if (stages) VR_TRY(check_mem(mem));
+  std::lock_guard<std::mutex> writer(e->wmu);
+  return encoder_set_head(e, stages, n_stages, truncate_dim, mem);
+}
+
 int vr_encode(vr_engine* e, const int32_t* ids, const int32_t* offsets, int32_t n_seq, int mem,
               float* out, int out_mem) {
   VR_TRY(check_engine(e));
@@ -510,7 +517,7 @@ static int index_batch(vr_engine* e, int64_t n, int mem, const int32_t* wp_ids, 
                    nullptr, e->bm_val.p));
   }
   // 2. dense encode into engine-owned rows
-  VR_CHECK(encoder_hidden(e) == e->dim, "encoder width %d != store dimension %d", encoder_hidden(e), e->dim);
+  VR_CHECK(encoder_out_dim(e) == e->dim, "encoder width %d != store dimension %d", encoder_out_dim(e), e->dim);
   VR_TRY(e->enc_out.grow(n * e->dim, 0, e->stream));
   if (span_off)
     VR_TRY(encoder_encode_spans(e, wp_ids, wp_off, n_seq, span_off, span_tok, mem, n, e->enc_out.p, VR_MEM_DEVICE));

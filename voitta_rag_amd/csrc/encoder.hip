@@ -17,6 +17,7 @@
 //   pool_kernel       mean / CLS pooling + L2 normalise              HBM bound
 //   rerank_head_kernel cross-encoder head on the pooled [CLS] rows   one f32 logit per pair (encoder_rerank)
 //   rerank_head_ln_kernel the head of a pre-norm cross-encoder: dense, GELU, LayerNorm, classifier (encoder_rerank)
+//   embed_head_kernel the embedder's post-pooling head: Dense / LayerNorm stages, normalise, truncate (vr_encoder_set_head)
 //   rope_kernel       rotary positions, in place on Q and K            HBM bound (VR_POS_ROTARY models only)
 //   glu_kernel        act(gate) * up of a gated FFN                    HBM bound (VR_FFN_SWIGLU / VR_FFN_GEGLU only)
 // Algorithmic FLOP per token = L * (24 H^2 + 4 S H), of which the GEMMs are
@@ -60,6 +61,18 @@ struct LayerWeights {
   float *cs_1_p = nullptr, *c_1_p = nullptr;
 };
 
+// vr_encoder_set_head: the stages embed_head_kernel runs on the pooled rows (device pointers; a null b: no bias / shift)
+constexpr int kMaxHeadStages = 4;
+struct HeadStage {
+  int kind, in_dim, out_dim, act;
+  float eps;
+  const float *w, *b;
+};
+struct HeadParams {
+  int n_stages;
+  HeadStage st[kMaxHeadStages];
+};
+
 struct Encoder {
   vr_bert_desc d{};
   float *word = nullptr, *pos = nullptr, *type = nullptr, *lng = nullptr, *lnb = nullptr;
@@ -81,7 +94,14 @@ struct Encoder {
   int bias_radius = 0;
   // vr_encoder_set_attention_slopes: [heads] f32, logit -= slopes[h] |key - query|; never set together with `bias`
   float* slopes = nullptr;
-  int window_stream_from = 0;    // windowed layers: sequences from this length on take attention_stream_kernel (build_encoder)
+  // vr_encoder_set_head: the stages behind pooling (weights in `owned`) and the output width they and the truncation
+  // leave; has_head false: out_dim == d.hidden and every launch is the headless one. `pooled`: the un-normalised pooled
+  // rows of a call with stages, one H-wide row per output row — the size of what the caller holds for the result.
+  bool has_head = false;
+  HeadParams head{};
+  int out_dim = 0;
+  DevArray<float> pooled;
+  int window_stream_from = 0;   // windowed layers: sequences from this length on take attention_stream_kernel (build_encoder)
   float* posidx = nullptr;  // rotary: int32 position of every token inside its own sequence (positions_kernel)
   bool fuse = true;         // rotate / gate inside the skinny epilogues; VR_ENCODE_FUSE=0 at load time: separate passes
   DevArray<int32_t> ids, cu, seg;
@@ -106,9 +126,10 @@ struct Encoder {
     const void *ids, *cu, *seg, *out;
     const void *span_tok = nullptr, *span_seq = nullptr;
     int n_spans = 0;
+    const void* pooled = nullptr;  // a head with stages: the scratch the pool kernels write and embed_head_kernel reads
     bool operator<(const GraphKey& o) const {
-      return std::tie(T, n_seq, max_len, ids, cu, seg, out, span_tok, span_seq, n_spans) <
-             std::tie(o.T, o.n_seq, o.max_len, o.ids, o.cu, o.seg, o.out, o.span_tok, o.span_seq, o.n_spans);
+      return std::tie(T, n_seq, max_len, ids, cu, seg, out, span_tok, span_seq, n_spans, pooled) <
+             std::tie(o.T, o.n_seq, o.max_len, o.ids, o.cu, o.seg, o.out, o.span_tok, o.span_seq, o.n_spans, o.pooled);
     }
   };
   struct GraphEntry {
@@ -452,11 +473,13 @@ __global__ __launch_bounds__(256) void layernorm_f16_kernel(const float* __restr
     }
 }
 
-// one block per sequence: mean (sum / max(count, 1e-9)) or CLS pooling, then x / max(|x|, 1e-12)
+// one block per sequence: mean (sum / max(count, 1e-9)) or CLS pooling, then x / max(|x|, 1e-12) over all H columns.
+// The leading ocols columns are stored, in rows of ostride floats (H and H without a head; a truncating head stores
+// fewer, and what it stores are the bits it would have stored in full).
 __global__ __launch_bounds__(256) void pool_kernel(const float* __restrict__ x,
                                                    const int32_t* __restrict__ cu, int seq0,
                                                    int tok_base, int H, int pooling, int normalize,
-                                                   int compact, float* __restrict__ out) {
+                                                   int compact, float* __restrict__ out, int ostride, int ocols) {
   __shared__ float red[4];
   const int seq = seq0 + blockIdx.x;
   // compact: x holds one row per sequence (its [CLS] row), see the last layer of forward_chunk
@@ -488,17 +511,19 @@ __global__ __launch_bounds__(256) void pool_kernel(const float* __restrict__ x,
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     int c = threadIdx.x + 256 * j;
-    if (c < H) out[static_cast<int64_t>(seq) * H + c] = vals[j] / den;
+    if (c < ocols) out[static_cast<int64_t>(seq) * ostride + c] = vals[j] / den;
   }
 }
 
 // one block per span: the mean of the final hidden rows [begin, end) of the span's own sequence, summed in token order,
 // then x / max(|x|, 1e-12) — pool_kernel's mean arithmetic over a token range, so a span [0, len) gives pool_kernel's
 // bits. Block b serves span span0 + b; span_seq holds each span's sequence (no search here), span_tok its (begin, end).
+// ostride / ocols: as pool_kernel's.
 __global__ __launch_bounds__(256) void span_pool_kernel(const float* __restrict__ x, const int32_t* __restrict__ cu,
                                                         const int32_t* __restrict__ span_tok,
                                                         const int32_t* __restrict__ span_seq, int span0, int tok_base,
-                                                        int H, int normalize, float* __restrict__ out) {
+                                                        int H, int normalize, float* __restrict__ out, int ostride,
+                                                        int ocols) {
   __shared__ float red[4];
   const int sp = span0 + blockIdx.x;
   const int begin = span_tok[2 * sp];
@@ -526,7 +551,7 @@ __global__ __launch_bounds__(256) void span_pool_kernel(const float* __restrict_
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     int c = threadIdx.x + 256 * j;
-    if (c < H) out[static_cast<int64_t>(sp) * H + c] = vals[j] / den;
+    if (c < ocols) out[static_cast<int64_t>(sp) * ostride + c] = vals[j] / den;
   }
 }
 
@@ -673,6 +698,158 @@ __global__ __launch_bounds__(256) void rerank_head_ln_kernel(const float* __rest
     for (int i = 0; i < 4; ++i)
       if (p0 + 4 * q + i < n) out[p0 + 4 * q + i] = bc[0] + part[i];
 }
+
+// The embedder's post-pooling head (vr_encoder_set_head) on n un-normalised pooled rows [n, W0], all f32: the stages of
+// hp in order, then (normalize) x / max(|x|, 1e-12) over the whole last width, then the leading ocols columns into rows
+// of ostride floats. One block of 4 waves per 16 rows. Between stages a row lives in registers in the MFMA's D layout:
+// lane (r = lane & 15, q = lane >> 4) of wave w holds, for its 16-column tiles jt = w, w + 4, ... (slot t = jt / 4),
+// column 16 jt + r of the rows 4 q + i; slots past the current width hold zeros.
+//   Dense      the rows are handed over through LDS (abuf, [16][lda], lda = the widest Dense input + 4: the pad of one
+//              b128 access keeps the 16 rows of an A read on different banks) and every wave runs its tiles as
+//              rerank_head_kernel does — v_mfma_f32_16x16x4_f32, the 16 rows as M, A and W read with the same k
+//              permutation — but k outermost: one A read serves all of a wave's tiles, their weight loads are in flight
+//              together and the accumulators are independent. The weight is read once per 16 rows.
+//   LayerNorm  two passes over the registers (mean, then the centred sum of squares: no cancellation).
+// Every sum over a row's columns is in one fixed order — per lane over its tiles, a xor butterfly across the 16 lanes of
+// a row group, then the four waves in order through LDS — with no atomics, and a row's arithmetic never meets another
+// row's: its bits depend neither on n nor on its place among the 16.
+__global__ __launch_bounds__(256) void embed_head_kernel(const float* __restrict__ rows, int n, int W0, HeadParams hp,
+                                                         int normalize, int lda, float* __restrict__ out, int ostride,
+                                                         int ocols) {
+  extern __shared__ __attribute__((aligned(16))) float head_lds[];
+  float* red = head_lds;        // [4][16]
+  float* abuf = head_lds + 64;  // [16][lda]
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int r = lane & 15, q = lane >> 4;
+  const int p0 = blockIdx.x * 16;
+  f32x4 act[kHeadTiles];
+  int W = W0;
+#pragma unroll
+  for (int t = 0; t < kHeadTiles; ++t) {
+    const int col = (wave + 4 * t) * 16 + r;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int row = p0 + 4 * q + i;
+      act[t][i] = (col < W && row < n) ? rows[static_cast<int64_t>(row) * W0 + col] : 0.0f;
+    }
+  }
+  // the sum of part[i] over all columns of row 4 q + i, the same bits in every lane of the block that holds the row
+  auto row_sums = [&](f32x4& part) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int off = 1; off < 16; off <<= 1) part[i] += __shfl_xor(part[i], off);
+    if (r == 0)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) red[wave * 16 + 4 * q + i] = part[i];
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 4; ++i) part[i] = red[4 * q + i] + red[16 + 4 * q + i] + red[32 + 4 * q + i] + red[48 + 4 * q + i];
+    __syncthreads();  // (red is written again by the next sum)
+  };
+  for (int s = 0; s < hp.n_stages; ++s) {
+    const HeadStage st = hp.st[s];
+    if (st.kind == VR_HEAD_DENSE) {
+      const int K = st.in_dim, tiles = st.out_dim / 16;
+#pragma unroll
+      for (int t = 0; t < kHeadTiles; ++t) {
+        const int col = (wave + 4 * t) * 16 + r;
+        if (col < K)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) abuf[(4 * q + i) * lda + col] = act[t][i];
+      }
+      __syncthreads();
+#pragma unroll
+      for (int t = 0; t < kHeadTiles; ++t) act[t] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+      const float* a_row = abuf + r * lda + 4 * q;
+      const float* w_row = st.w + static_cast<int64_t>(wave * 16 + r) * K + 4 * q;  // slot t: 64 t rows further
+      // (issuing four k-steps' weight loads ahead of their products changed nothing measurable: a block is bound by its
+      // 16-row MFMA work and by one CU's share of the weight's bytes)
+      for (int k0 = 0; k0 < K; k0 += 16) {
+        const float4 a = *reinterpret_cast<const float4*>(a_row + k0);
+        float4 w[kHeadTiles];
+#pragma unroll
+        for (int t = 0; t < kHeadTiles; ++t)
+          if (wave + 4 * t < tiles) w[t] = *reinterpret_cast<const float4*>(w_row + static_cast<int64_t>(64 * t) * K + k0);
+#pragma unroll
+        for (int t = 0; t < kHeadTiles; ++t)
+          if (wave + 4 * t < tiles) {
+            act[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, w[t].x, act[t], 0, 0, 0);
+            act[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, w[t].y, act[t], 0, 0, 0);
+            act[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, w[t].z, act[t], 0, 0, 0);
+            act[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, w[t].w, act[t], 0, 0, 0);
+          }
+      }
+#pragma unroll
+      for (int t = 0; t < kHeadTiles; ++t)
+        if (wave + 4 * t < tiles) {  // D: column (unit) lane & 15, row 4 q + i
+          const float bj = st.b ? st.b[(wave + 4 * t) * 16 + r] : 0.0f;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const float v = act[t][i] + bj;
+            act[t][i] = st.act == VR_ACT_TANH ? tanhf(v) : v;
+          }
+        }
+      __syncthreads();  // (abuf is written again by the next Dense stage)
+      W = st.out_dim;
+    } else {
+      const float inv_w = 1.0f / static_cast<float>(W);
+      f32x4 mean = {0.0f, 0.0f, 0.0f, 0.0f}, inv = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+      for (int t = 0; t < kHeadTiles; ++t) mean += act[t];  // (slots past W hold zeros)
+      row_sums(mean);
+      mean *= inv_w;
+#pragma unroll
+      for (int t = 0; t < kHeadTiles; ++t)
+        if ((wave + 4 * t) * 16 < W) {
+          act[t] -= mean;
+          inv += act[t] * act[t];
+        }
+      row_sums(inv);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) inv[i] = 1.0f / sqrtf(inv[i] * inv_w + st.eps);
+#pragma unroll
+      for (int t = 0; t < kHeadTiles; ++t)
+        if ((wave + 4 * t) * 16 < W) {
+          const int col = (wave + 4 * t) * 16 + r;
+          const float g = st.w[col], b = st.b ? st.b[col] : 0.0f;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) act[t][i] = act[t][i] * inv[i] * g + b;
+        }
+    }
+  }
+  if (normalize) {
+    f32x4 ss = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int t = 0; t < kHeadTiles; ++t) ss += act[t] * act[t];
+    row_sums(ss);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) ss[i] = fmaxf(sqrtf(ss[i]), 1e-12f);
+#pragma unroll
+    for (int t = 0; t < kHeadTiles; ++t) act[t] /= ss;
+  }
+#pragma unroll
+  for (int t = 0; t < kHeadTiles; ++t) {
+    const int col = (wave + 4 * t) * 16 + r;
+    if (col < ocols)
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        if (p0 + 4 * q + i < n) out[static_cast<int64_t>(p0 + 4 * q + i) * ostride + col] = act[t][i];
+  }
+}
+
+// embed_head_kernel's LDS: the four waves' partial sums, then 16 rows of the widest Dense input padded by one float4
+static int head_lda(const HeadParams& hp) {
+  int k = 0;
+  for (int s = 0; s < hp.n_stages; ++s)
+    if (hp.st[s].kind == VR_HEAD_DENSE) k = std::max(k, hp.st[s].in_dim);
+  return k + 4;
+}
+static size_t head_lds_bytes(int lda) { return (64 + 16 * static_cast<size_t>(lda)) * sizeof(float); }
+constexpr int kMaxHeadWidth = 1024;  // vr_encoder_set_head's widest stage: head_lds_bytes(kMaxHeadWidth + 4) is 65 KiB
+
+// the width of an output row: the head's (vr_encoder_set_head), without one the model's
+static int out_width(const Encoder* enc) { return enc->has_head ? enc->out_dim : enc->d.hidden; }
 
 // dst[i] = src[first token of sequence seq0 + i]; rows of `row_f4` float4s (an f32 row of H floats and
 // an interleaved (hi, lo) f16 row of 2H halfs have the same 4H bytes). One wave per row.
@@ -3896,6 +4073,7 @@ static void free_encoder(void** slot) {
   invalidate_graphs(enc);
   enc->out.release();
   enc->rows.release();
+  enc->pooled.release();
   delete enc;
   *slot = nullptr;
 }
@@ -4215,6 +4393,88 @@ int encoder_set_attention_slopes(vr_engine* e, const float* slopes, int heads, i
   return 0;
 }
 
+// The embedder's post-pooling head (vr_encoder_set_head), as the two calls above: every check runs, and every weight is
+// on the device, before anything changes; the captured graphs hold the weights' pointers and the launch list, so they go.
+int encoder_set_head(vr_engine* e, const vr_head_stage* stages, int n_stages, int truncate_dim, int mem) {
+  Encoder* enc = static_cast<Encoder*>(e->encoder);
+  VR_CHECK(enc, "no encoder loaded");
+  VR_CHECK(n_stages >= 0 && n_stages <= kMaxHeadStages, "%d head stages (0..%d allowed)", n_stages, kMaxHeadStages);
+  VR_CHECK(n_stages == 0 || stages, "null stages");
+  const bool remove = !stages && truncate_dim == 0;
+  auto width_ok = [](int w) { return w >= 16 && w <= kMaxHeadWidth && w % 16 == 0; };
+  int width = enc->d.hidden;
+  VR_CHECK(remove || width_ok(width), "a head needs an encoder width that is a multiple of 16 in 16..1024 (%d)", width);
+  for (int s = 0; s < n_stages; ++s) {
+    const vr_head_stage& st = stages[s];
+    VR_CHECK(st.struct_size == static_cast<int32_t>(sizeof(vr_head_stage)), "stage %d: vr_head_stage size mismatch", s);
+    VR_CHECK(st.kind == VR_HEAD_DENSE || st.kind == VR_HEAD_LAYERNORM, "stage %d: unknown kind %d", s, st.kind);
+    VR_CHECK(width_ok(st.in_dim) && width_ok(st.out_dim),
+             "stage %d: widths %d -> %d must be multiples of 16 in 16..1024", s, st.in_dim, st.out_dim);
+    VR_CHECK(st.in_dim == width, "stage %d reads %d columns, %s has %d", s, st.in_dim,
+             s == 0 ? "the encoder" : "the stage before it", width);
+    VR_CHECK(st.weight, "stage %d: null weight", s);
+    if (st.kind == VR_HEAD_DENSE) {
+      VR_CHECK(st.activation == VR_ACT_IDENTITY || st.activation == VR_ACT_TANH, "stage %d: unknown activation %d", s,
+               st.activation);
+    } else {
+      VR_CHECK(st.in_dim == st.out_dim, "stage %d: a LayerNorm keeps its width (%d -> %d)", s, st.in_dim, st.out_dim);
+      VR_CHECK(st.eps > 0.0f, "stage %d: LayerNorm eps %g must be positive", s, static_cast<double>(st.eps));
+    }
+    width = st.out_dim;
+  }
+  VR_CHECK(truncate_dim == 0 || (truncate_dim >= 16 && truncate_dim % 16 == 0 && truncate_dim <= width),
+           "truncate_dim %d must be 0 or a multiple of 16 in 16..%d", truncate_dim, width);
+  HeadParams hp{};
+  std::vector<float*> fresh;
+  auto upload = [&](const float* src, size_t n, const float** dst) -> hipError_t {
+    float* p = nullptr;
+    hipError_t err = hipMalloc(reinterpret_cast<void**>(&p), n * sizeof(float));
+    if (err != hipSuccess) return err;
+    fresh.push_back(p);
+    *dst = p;
+    return hipMemcpyAsync(p, src, n * sizeof(float), mem == VR_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice,
+                          e->stream);
+  };
+  hipError_t err = hipSuccess;
+  for (int s = 0; s < n_stages && err == hipSuccess; ++s) {
+    const vr_head_stage& st = stages[s];
+    HeadStage& h = hp.st[s];
+    h = HeadStage{st.kind, st.in_dim, st.out_dim, st.activation, st.eps, nullptr, nullptr};
+    const size_t nw = st.kind == VR_HEAD_DENSE ? static_cast<size_t>(st.in_dim) * st.out_dim : static_cast<size_t>(st.in_dim);
+    err = upload(st.weight, nw, &h.w);
+    if (err == hipSuccess && st.bias) err = upload(st.bias, static_cast<size_t>(st.out_dim), &h.b);
+  }
+  hp.n_stages = n_stages;
+  // (the sources may go; passes that read the old head are over)
+  if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
+  // embed_head_kernel's LDS at the widest Dense is past the 64 KiB a launch gets unasked: allowed once, whatever this head is
+  static const hipError_t lds_allowed =
+      hipFuncSetAttribute(reinterpret_cast<const void*>(&embed_head_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          static_cast<int>(head_lds_bytes(kMaxHeadWidth + 4)));
+  if (err == hipSuccess) err = lds_allowed;
+  if (err != hipSuccess) {
+    for (float* p : fresh) (void)hipFree(p);
+    VR_HIP(err);
+  }
+  invalidate_graphs(enc);
+  for (int s = 0; s < enc->head.n_stages; ++s)
+    for (const float* old : {enc->head.st[s].w, enc->head.st[s].b})
+      if (old) {
+        enc->owned.erase(std::remove(enc->owned.begin(), enc->owned.end(), old), enc->owned.end());
+        (void)hipFree(const_cast<float*>(old));
+      }
+  enc->head = hp;
+  enc->has_head = !remove;
+  enc->out_dim = truncate_dim ? truncate_dim : width;
+  enc->owned.insert(enc->owned.end(), fresh.begin(), fresh.end());
+  return 0;
+}
+
+int encoder_out_dim(vr_engine* e) {
+  Encoder* enc = static_cast<Encoder*>(e->encoder);
+  return enc ? out_width(enc) : 0;
+}
+
 int reranker_load(vr_engine* e, const vr_bert_desc* d_in, const void* const* t, int n_tensors, int mem) {
   vr_bert_desc desc;
   VR_TRY(read_desc(d_in, &desc));
@@ -4403,6 +4663,35 @@ struct Spans {
   const int32_t* seq_dev = nullptr;
 };
 
+// The last launches of a forward chunk: the rows of sequences [seq0, seq1) — or of their spans (sp) — pooled from x
+// into out_dev, one row of out_width() floats each at its sequence's (span's) index. Without a head that is the pool
+// kernel alone, as ever. A head without stages only narrows what the pool kernel stores. With stages the pool kernel
+// leaves the un-normalised rows in enc->pooled (sized by the caller, same row indices) and embed_head_kernel finishes
+// the chunk's rows, 16 per block counted from the chunk's first row.
+static void launch_pool(vr_engine* e, Encoder* enc, const float* x, const int32_t* cu_dev, int seq0, int seq1, int tok_base,
+                        int compact, float* out_dev, const Spans* sp) {
+  const vr_bert_desc& d = enc->d;
+  const int H = d.hidden, W = out_width(enc);
+  const bool staged = enc->head.n_stages > 0;
+  float* dst = staged ? enc->pooled.p : out_dev;
+  const int stride = staged ? H : W, cols = staged ? H : W, normalize = staged ? 0 : d.normalize;
+  int row0 = seq0, n_rows = seq1 - seq0;
+  if (sp) {
+    row0 = sp->off[static_cast<size_t>(seq0)];
+    n_rows = sp->off[static_cast<size_t>(seq1)] - row0;
+    if (n_rows <= 0) return;
+    hipLaunchKernelGGL(span_pool_kernel, dim3(static_cast<unsigned>(n_rows)), dim3(256), 0, e->stream, x, cu_dev, sp->tok_dev,
+                       sp->seq_dev, row0, tok_base, H, normalize, dst, stride, cols);
+  } else {
+    hipLaunchKernelGGL(pool_kernel, dim3(static_cast<unsigned>(n_rows)), dim3(256), 0, e->stream, x, cu_dev, seq0, tok_base, H,
+                       d.pooling, normalize, compact, dst, stride, cols);
+  }
+  if (staged)
+    hipLaunchKernelGGL(embed_head_kernel, dim3(static_cast<unsigned>((n_rows + 15) / 16)), dim3(256),
+                       head_lds_bytes(head_lda(enc->head)), e->stream, enc->pooled.p + static_cast<int64_t>(row0) * H, n_rows, H,
+                       enc->head, d.normalize, head_lda(enc->head), out_dev + static_cast<int64_t>(row0) * W, W, W);
+}
+
 // The forward pass of a pre-norm model (VR_NORM_PRE: rotary positions, a gated FFN, optionally alternating global and
 // windowed attention — the ModernBERT family), forward_chunk's arguments:
 //   h = LN_emb(word[id]);  per layer  h += W_o attn(N_a(h)),  h += W_down(act(gate(N_m(h))) * up(N_m(h)));  out = N_f(h)
@@ -4550,15 +4839,7 @@ static int forward_chunk_prenorm(vr_engine* e, Encoder* enc, const int32_t* ids_
   const LayerWeights& last = enc->layers.back();
   hipLaunchKernelGGL(layernorm_kernel, dim3(row_blocks), dim3(256), 0, s, h, T, H, last.ln2g, last.ln2b, d.eps, other,
                      static_cast<half_t*>(nullptr), static_cast<half_t*>(nullptr), static_cast<float2*>(nullptr));
-  if (sp) {
-    const int span0 = sp->off[static_cast<size_t>(seq0)], n_spans = sp->off[static_cast<size_t>(seq1)] - span0;
-    if (n_spans > 0)
-      hipLaunchKernelGGL(span_pool_kernel, dim3(static_cast<unsigned>(n_spans)), dim3(256), 0, s, other, cu_dev, sp->tok_dev,
-                         sp->seq_dev, span0, tok_base, H, d.normalize, out_dev);
-  } else {
-    hipLaunchKernelGGL(pool_kernel, dim3(static_cast<unsigned>(n_seq)), dim3(256), 0, s, other, cu_dev, seq0, tok_base, H,
-                       d.pooling, d.normalize, 0, out_dev);
-  }
+  launch_pool(e, enc, other, cu_dev, seq0, seq1, tok_base, 0, out_dev, sp);
   VR_HIP(hipGetLastError());
   return 0;
 }
@@ -4770,8 +5051,7 @@ static int forward_chunk(vr_engine* e, Encoder* enc, const int32_t* ids_dev, con
       }
       hipLaunchKernelGGL(layernorm_kernel, dim3(cblocks), dim3(256), 0, s, tmpc, n_seq, H, w.ln2g, w.ln2b, d.eps, xc,
                          static_cast<half_t*>(nullptr), static_cast<half_t*>(nullptr), static_cast<float2*>(nullptr));
-      hipLaunchKernelGGL(pool_kernel, dim3(static_cast<unsigned>(n_seq)), dim3(256), 0, s, xc, cu_dev, seq0, tok_base, H,
-                         d.pooling, d.normalize, 1, out_dev);
+      launch_pool(e, enc, xc, cu_dev, seq0, seq1, tok_base, 1, out_dev, nullptr);
       VR_HIP(hipGetLastError());
       return 0;
     }
@@ -4890,15 +5170,7 @@ static int forward_chunk(vr_engine* e, Encoder* enc, const int32_t* ids_dev, con
     hipLaunchKernelGGL(layernorm_kernel, dim3(row_blocks), dim3(256), 0, s, enc->tmp, T, H, w.ln2g, w.ln2b,
                        d.eps, enc->x, xh, xl, static_cast<float2*>(nullptr));
   }
-  if (sp) {
-    const int span0 = sp->off[static_cast<size_t>(seq0)], n_spans = sp->off[static_cast<size_t>(seq1)] - span0;
-    if (n_spans > 0)
-      hipLaunchKernelGGL(span_pool_kernel, dim3(static_cast<unsigned>(n_spans)), dim3(256), 0, s, final_x, cu_dev,
-                         sp->tok_dev, sp->seq_dev, span0, tok_base, H, d.normalize, out_dev);
-  } else {
-    hipLaunchKernelGGL(pool_kernel, dim3(static_cast<unsigned>(seq1 - seq0)), dim3(256), 0, s, final_x, cu_dev,
-                       seq0, tok_base, H, d.pooling, d.normalize, 0, out_dev);
-  }
+  launch_pool(e, enc, final_x, cu_dev, seq0, seq1, tok_base, 0, out_dev, sp);
   VR_HIP(hipGetLastError());
   return 0;
 }
@@ -4996,7 +5268,8 @@ static int forward_all(vr_engine* e, Encoder* enc, const int32_t* ids, const int
       Encoder::GraphEntry& g =
           enc->graphs[Encoder::GraphKey{static_cast<int>(T), n_seq, max_len, ids_dev, cu_dev, seg_dev, out_dev,
                                         sp ? sp->tok_dev : nullptr, sp ? sp->seq_dev : nullptr,
-                                        sp ? sp->off[static_cast<size_t>(n_seq)] : 0}];
+                                        sp ? sp->off[static_cast<size_t>(n_seq)] : 0,
+                                        enc->head.n_stages > 0 ? enc->pooled.p : nullptr}];
       if (!g.exec && !g.bad && g.seen >= 1) {
         if (hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
           const int rc = forward_chunk(e, enc, ids_dev, cu_dev, seg_dev, n_seq, seq0, seq1, 0, static_cast<int>(T),
@@ -5046,16 +5319,17 @@ int encoder_encode(vr_engine* e, const int32_t* ids, const int32_t* offsets, int
   Encoder* enc = static_cast<Encoder*>(e->encoder);
   VR_CHECK(enc != nullptr, "no encoder loaded (vr_encoder_load)");
   if (n_seq <= 0) return 0;
-  const int H = enc->d.hidden;
+  const int W = out_width(enc);
   std::vector<int32_t> cu_host;
   VR_TRY(read_offsets(e, enc, offsets, nullptr, n_seq, mem, &cu_host));
   float* out_dev = out;
   if (out_mem == VR_MEM_HOST) {
-    VR_TRY(enc->out.grow(static_cast<int64_t>(n_seq) * H, 0, e->stream));
+    VR_TRY(enc->out.grow(static_cast<int64_t>(n_seq) * W, 0, e->stream));
     out_dev = enc->out.p;
   }
+  if (enc->head.n_stages > 0) VR_TRY(enc->pooled.grow(static_cast<int64_t>(n_seq) * enc->d.hidden, 0, e->stream));
   VR_TRY(forward_all(e, enc, ids, offsets, nullptr, n_seq, mem, cu_host, out_dev));
-  return finish(e, out, out_dev, static_cast<int64_t>(n_seq) * H, mem, out_mem);
+  return finish(e, out, out_dev, static_cast<int64_t>(n_seq) * W, mem, out_mem);
 }
 
 // The spans of a span call, checked against the sequences (cu_host) — span_off monotone from 0 (sp->off holds its host
@@ -5111,7 +5385,7 @@ int encoder_encode_spans(vr_engine* e, const int32_t* ids, const int32_t* offset
   Encoder* enc = static_cast<Encoder*>(e->encoder);
   VR_CHECK(enc != nullptr, "no encoder loaded (vr_encoder_load)");
   if (n_seq <= 0) return 0;
-  const int H = enc->d.hidden;
+  const int W = out_width(enc);
   std::vector<int32_t> cu_host;
   Spans sp;
   VR_TRY(read_offsets(e, enc, offsets, nullptr, n_seq, mem, &cu_host, span_off, &sp.off));
@@ -5120,13 +5394,14 @@ int encoder_encode_spans(vr_engine* e, const int32_t* ids, const int32_t* offset
   if (n_spans == 0) return 0;
   float* out_dev = out;
   if (out_mem == VR_MEM_HOST) {
-    VR_TRY(enc->out.grow(n_spans * H, 0, e->stream));
+    VR_TRY(enc->out.grow(n_spans * W, 0, e->stream));
     out_dev = enc->out.p;
   }
+  if (enc->head.n_stages > 0) VR_TRY(enc->pooled.grow(n_spans * enc->d.hidden, 0, e->stream));
   VR_TRY(forward_all(e, enc, ids, offsets, nullptr, n_seq, mem, cu_host, out_dev, &sp));
   // (device arrays in and out: drain here, enc->span_seq_host must outlive its upload)
   if (mem != VR_MEM_HOST && out_mem != VR_MEM_HOST) VR_HIP(hipStreamSynchronize(e->stream));
-  return finish(e, out, out_dev, n_spans * H, mem, out_mem);
+  return finish(e, out, out_dev, n_spans * W, mem, out_mem);
 }
 
 int encoder_rerank(vr_engine* e, const int32_t* ids, const int32_t* offsets, const int32_t* seg_b, int n_seq, int mem,

@@ -615,6 +615,7 @@ int sparse_lookup_df(vr_engine* e, const int32_t* ids_host, int n, int32_t* out_
 int encoder_load(vr_engine* e, const vr_bert_desc* d, const void* const* tensors, int n_tensors, int mem);
 int encoder_set_attention_bias(vr_engine* e, const float* table, int heads, int radius, int mem);
 int encoder_set_attention_slopes(vr_engine* e, const float* slopes, int heads, int mem);
+int encoder_set_head(vr_engine* e, const vr_head_stage* stages, int n_stages, int truncate_dim, int mem);
 int encoder_encode(vr_engine* e, const int32_t* ids, const int32_t* offsets, int n_seq, int mem,
                    float* out, int out_mem);
 // one row per token span instead of per sequence (vr_encode_spans); n_expected >= 0: the span count the caller announced
@@ -626,6 +627,7 @@ bool reranker_loaded(vr_engine* e);
 int encoder_rerank(vr_engine* e, const int32_t* ids, const int32_t* offsets, const int32_t* seg_b, int n_seq, int mem,
                    float* out, int out_mem);  // out: n_seq logits
 int encoder_hidden(vr_engine* e);  // 0 when no encoder is loaded
+int encoder_out_dim(vr_engine* e);  // the width of an embedding row: the head's (vr_encoder_set_head), else encoder_hidden
 
 // ---- profile.hip: HIP-event timing of one launch (no-ops unless vr_profile(e, 1))
 void prof_begin(vr_engine* e, int kernel_class, double work);

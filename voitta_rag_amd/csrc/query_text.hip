@@ -139,7 +139,7 @@ int query_text(vr_engine* e, const Tokenizer* tokenizer, const char* dense_text,
     VR_TRY(question_stems(texts, lens, 1, &off, &stems));
   }
   // 2. the embedding, left in device memory (the encoder is shared with the writers: one forward pass at a time)
-  VR_CHECK(encoder_hidden(e) == e->dim, "encoder width %d != store dimension %d", encoder_hidden(e), e->dim);
+  VR_CHECK(encoder_out_dim(e) == e->dim, "encoder width %d != store dimension %d", encoder_out_dim(e), e->dim);
   float* q_dev = take_query_row(e);
   VR_CHECK(q_dev != nullptr, "no device memory for the query embedding");
   struct Giver {
@@ -210,7 +210,7 @@ int query_text_batch(vr_engine* e, const Tokenizer* tokenizer, int32_t n, const 
     VR_TRY(classify_queries(filters, n_filters, filter_of_query, n, &qc));
   }
   VR_TRY(check_engine(e));
-  VR_CHECK(encoder_hidden(e) == e->dim, "encoder width %d != store dimension %d", encoder_hidden(e), e->dim);
+  VR_CHECK(encoder_out_dim(e) == e->dim, "encoder width %d != store dimension %d", encoder_out_dim(e), e->dim);
   const int dim = e->dim;
   // 1. host: WordPiece ids of every (prefixed) question, the hashed stems of every raw one
   std::vector<int32_t> wp, off32;

@@ -38,6 +38,12 @@ import os
 import numpy as np
 
 
+def embedding_width(desc) -> int:
+    """The width of the rows a model gives: its description's out_dim (the head's or the truncated width), and `hidden`
+    for a description object that knows nothing of heads."""
+    return int(getattr(desc, "out_dim", None) or desc.hidden)
+
+
 def _mode() -> str:
     return os.environ.get("VOITTA_DEFERRED_INDEXING", "sync").strip().lower()
 
@@ -102,7 +108,7 @@ class DeferredEmbeddings(list):
         self.encoder = encoder
         self.ids = ids
         self.off = off
-        self.dim = int(encoder.desc.hidden)
+        self.dim = embedding_width(encoder.desc)
         self._array: np.ndarray | None = None
 
     @property
@@ -163,7 +169,7 @@ class QueryRef:
         return a if dtype is None else a.astype(dtype)
 
     def __len__(self) -> int:
-        return int(self.model.desc.hidden)
+        return embedding_width(self.model.desc)
 
     def __getitem__(self, k):
         v = self.array[k]

@@ -29,6 +29,7 @@ logger = logging.getLogger(__name__)
 # the default cap on a sequence's tokens; VOITTA_MAX_SEQ_LENGTH (1 ... 8192) sets another one, see seq_cap()
 MAX_SEQ = 512
 SEQ_CAP_VARIABLE = "VOITTA_MAX_SEQ_LENGTH"
+TRUNCATE_VARIABLE = "VOITTA_EMBED_TRUNCATE_DIM"
 
 
 def seq_cap() -> int:
@@ -57,8 +58,35 @@ def read_encoder_config(path: str) -> dict:
     description and how to load it: {"desc": BertDesc, "max_seq": int, "pos_start": first position-table row}.
     BERT: max_seq = min(max_seq_length, max_position_embeddings). XLM-RoBERTa (multilingual-e5 and the like): position
     p reads row pad_token_id + 1 + p, so the table is used from that row on (max_pos = max_position_embeddings -
-    pad_token_id - 1); one token type; max_seq = min(max_seq_length, max_pos), refused above seq_cap()."""
+    pad_token_id - 1); one token type; max_seq = min(max_seq_length, max_pos), refused above seq_cap().
+    The description carries the modules behind Pooling as its head (read_head) and VOITTA_EMBED_TRUNCATE_DIM as its
+    truncate_dim (apply_truncate_setting)."""
     cfg = json.load(open(os.path.join(path, "config.json")))
+    rc = _read_family_config(path, cfg)
+    rc["desc"].head = read_head(path, rc["desc"].hidden) or None
+    apply_truncate_setting(rc["desc"])
+    return rc
+
+
+def apply_truncate_setting(desc) -> None:
+    """VOITTA_EMBED_TRUNCATE_DIM (SentenceTransformer's truncate_dim) onto a description: the leading columns of the
+    model's output — its head's, when it has one — are the embedding. Refused unless it is a multiple of 16 within that
+    width, and unless EMBEDDING_DIMENSION, the width of the store, is the width that results."""
+    settings = get_settings()
+    keep = settings.embed_truncate_dim
+    if not keep:
+        return
+    width = desc.out_dim
+    if keep % 16 or not 16 <= keep <= width:
+        raise ValueError(f"{TRUNCATE_VARIABLE}={keep}: accepted values are the multiples of 16 from 16 to the model's "
+                         f"output width {width}")
+    desc.truncate_dim = keep
+    if settings.embedding_dimension != desc.out_dim:
+        raise ValueError(f"EMBEDDING_DIMENSION={settings.embedding_dimension} but {TRUNCATE_VARIABLE}={keep} makes the "
+                         f"embeddings {desc.out_dim} wide: set EMBEDDING_DIMENSION={desc.out_dim}")
+
+
+def _read_family_config(path: str, cfg: dict) -> dict:
     kind = cfg.get("model_type", "bert")
     if kind == "nomic_bert":
         return _read_rope_config(path, cfg)
@@ -66,8 +94,11 @@ def read_encoder_config(path: str) -> dict:
         return _read_modernbert_config(path, cfg)
     if kind == "mpnet":
         return _read_mpnet_config(path, cfg)
+    if kind == "distilbert":
+        return _read_distilbert_config(path, cfg)
     if kind not in ("bert", "xlm-roberta"):
-        raise ValueError(f"unsupported model_type {kind}: BERT, XLM-RoBERTa, MPNet, nomic_bert and modernbert encoders only")
+        raise ValueError(f"unsupported model_type {kind}: BERT, DistilBERT, XLM-RoBERTa, MPNet, nomic_bert and modernbert "
+                         "encoders only")
     if kind == "bert" and cfg.get("position_embedding_type", "absolute") == "alibi":
         return _read_alibi_config(path, cfg)
     if cfg.get("hidden_act", "gelu") != "gelu" or cfg.get("position_embedding_type", "absolute") != "absolute":
@@ -93,12 +124,25 @@ def read_encoder_config(path: str) -> dict:
     return {"desc": desc, "max_seq": max_seq, "pos_start": pos_start, "config": cfg}
 
 
+# modules.json types (sentence_transformers.models.*) by their last component
+_HEAD_MODULES = ("Dense", "LayerNorm")
+_SKIPPED_MODULES = ("Transformer", "Dropout")
+
+
+def _module_kind(m: dict) -> str:
+    return m.get("type", "").rsplit(".", 1)[-1]
+
+
 def _read_modules(path: str, max_seq: int):
-    """modules.json / sentence_bert_config.json of a sentence-transformers directory -> (pooling, normalize, max_seq)."""
+    """modules.json / sentence_bert_config.json of a sentence-transformers directory -> (pooling, normalize, max_seq).
+    The Dense and LayerNorm modules behind Pooling are read_head's. Normalize is the pipeline's last step here
+    (vr_encoder_set_head): one that is not the last module is refused. A module of any other type is ignored, with a
+    warning that names it."""
     pooling, normalize = "mean", False
     mod_path = os.path.join(path, "modules.json")
     if os.path.exists(mod_path):
-        for m in json.load(open(mod_path)):
+        mods = json.load(open(mod_path))
+        for i, m in enumerate(mods):
             k = m.get("type", "")
             if k.endswith("Pooling"):
                 pc = json.load(open(os.path.join(path, m["path"], "config.json")))
@@ -107,11 +151,94 @@ def _read_modules(path: str, max_seq: int):
                 elif not pc.get("pooling_mode_mean_tokens", True):
                     raise ValueError("only CLS and mean pooling are implemented")
             elif k.endswith("Normalize"):
+                if i != len(mods) - 1:
+                    raise ValueError(f"{path}: module {i} is a Normalize followed by {_module_kind(mods[i + 1])}: "
+                                     "normalisation is implemented as the last module only")
                 normalize = True
+            elif _module_kind(m) not in _HEAD_MODULES + _SKIPPED_MODULES:
+                logger.warning("%s: module %d of type %s is not implemented and is ignored: the embeddings are those of "
+                               "the pipeline without it", path, i, k or "(none)")
     sb = os.path.join(path, "sentence_bert_config.json")
     if os.path.exists(sb):
         max_seq = int(json.load(open(sb)).get("max_seq_length", max_seq))
     return pooling, normalize, max_seq
+
+
+def read_head(path: str, hidden: int) -> list:
+    """The Dense and LayerNorm modules that follow Pooling in modules.json -> encoder.HeadStage objects in order.
+    sentence_transformers.models.Dense: <module path>/config.json holds in_features, out_features, bias and
+    activation_function, a dotted torch class name (Tanh and Identity are implemented, anything else is refused by
+    name); the weights are linear.weight / linear.bias in <module path>/model.safetensors or pytorch_model.bin.
+    sentence_transformers.models.LayerNorm: config.json holds dimension; the weights are norm.weight / norm.bias, eps
+    torch's default 1e-5. Dropout does nothing at inference. One of the two in front of Pooling (a per-token
+    projection) is refused. The widths must chain from `hidden`."""
+    mod_path = os.path.join(path, "modules.json")
+    if not os.path.exists(mod_path):
+        return []
+    stages, pooled, width = [], False, hidden
+    for i, m in enumerate(json.load(open(mod_path))):
+        kind = _module_kind(m)
+        if kind == "Pooling":
+            pooled = True
+        if kind not in _HEAD_MODULES:
+            continue
+        if not pooled:
+            raise ValueError(f"{path}: module {i} ({m.get('type')}) stands in front of Pooling: per-token modules are not "
+                             "implemented")
+        mdir = os.path.join(path, m["path"])
+        mc = json.load(open(os.path.join(mdir, "config.json")))
+        weights = NativeSentenceEncoder._load_weights(mdir)
+
+        def tensor(name, shape):
+            if name not in weights:
+                raise KeyError(f"weight '{name}' not found under {mdir}")
+            t = weights[name]
+            t = np.ascontiguousarray(t.detach().cpu().numpy() if hasattr(t, "detach") else t, dtype=np.float32)
+            if t.shape != shape:
+                raise ValueError(f"weight '{name}' under {mdir} has shape {t.shape}, its config.json implies {shape}")
+            return t
+
+        if kind == "Dense":
+            n_in, n_out = int(mc["in_features"]), int(mc["out_features"])
+            act = mc.get("activation_function", "torch.nn.modules.activation.Tanh")
+            acts = {"Tanh": "tanh", "Identity": "identity"}
+            if act.rsplit(".", 1)[-1] not in acts:
+                raise ValueError(f"{mdir}: activation_function {act} is not implemented (Tanh and Identity are)")
+            stage = _enc.HeadStage("dense", tensor("linear.weight", (n_out, n_in)),
+                                   tensor("linear.bias", (n_out,)) if mc.get("bias", True) else None,
+                                   activation=acts[act.rsplit(".", 1)[-1]])
+        else:
+            n_in = n_out = int(mc["dimension"])
+            stage = _enc.HeadStage("layernorm", tensor("norm.weight", (n_in,)), tensor("norm.bias", (n_in,)), eps=1e-5)
+        if n_in != width:
+            raise ValueError(f"{mdir}: the module reads {n_in} columns, the pipeline in front of it gives {width}")
+        width = n_out
+        stages.append(stage)
+    return stages
+
+
+def _read_distilbert_config(path: str, cfg: dict) -> dict:
+    """model_type distilbert (distiluse-base-multilingual-cased, msmarco-distilbert-*): BERT's post-LayerNorm body with
+    exact-erf GELU, learned positions and no token types, under its own config keys (dim, n_heads, n_layers,
+    hidden_dim); LayerNorm eps is 1e-12 in the model's code. The position table is read from the checkpoint whatever
+    sinusoidal_pos_embds says (a sinusoidal table is stored like a learned one). encoder.distilbert_slots maps the
+    weights."""
+    act = cfg.get("activation", "gelu")
+    if act != "gelu":
+        raise ValueError(f"activation {act!r} is not implemented: a distilbert FFN runs the exact-erf GELU")
+    max_pos = int(cfg["max_position_embeddings"])
+    pooling, normalize, max_seq = _read_modules(path, max_pos)
+    max_seq = min(max_seq, max_pos)
+    cap = seq_cap()
+    if max_seq > cap:
+        raise ValueError(f"{path} uses sequences of up to {max_seq} tokens; the engine runs at most {cap}: set "
+                         f"max_seq_length <= {cap} in its sentence_bert_config.json, or raise {SEQ_CAP_VARIABLE} "
+                         f"(up to {MAX_SEQ_LENGTH_LIMIT})")
+    desc = _enc.BertDesc(layers=int(cfg["n_layers"]), hidden=int(cfg["dim"]), heads=int(cfg["n_heads"]),
+                         intermediate=int(cfg["hidden_dim"]), vocab=int(cfg["vocab_size"]), max_pos=max_pos, type_vocab=1,
+                         pooling=pooling, normalize=normalize, eps=1e-12,
+                         precision=os.environ.get("VOITTA_ENCODER_PRECISION", "f16"))
+    return {"desc": desc, "max_seq": max_seq, "pos_start": 0, "config": cfg}
 
 
 def _read_mpnet_config(path: str, cfg: dict) -> dict:
@@ -294,7 +421,6 @@ class NativeSentenceEncoder:
 
     def __init__(self, engine, desc: _enc.BertDesc, state: dict, tokenizer, max_seq_length: int):
         self.engine = engine
-        self.desc = desc
         self.tokenizer = tokenizer
         self.max_seq_length = min(max_seq_length, desc.max_pos)
         if native_tokenizer(tokenizer):
@@ -307,6 +433,12 @@ class NativeSentenceEncoder:
             logger.warning("VOITTA_LATE_CHUNKING=1 with a checkpoint that pools [CLS]: late-chunked vectors are means "
                            "over a chunk's tokens, which this model was not trained to produce; it runs all the same")
 
+    @property
+    def desc(self) -> _enc.BertDesc:
+        """The loaded encoder's description as the engine holds it: Engine.set_encoder_head replaces it there, and the
+        widths read from it here (empty results, deferred embeddings, the one-call text paths) follow."""
+        return self.engine.encoder_desc
+
     # ---- loading ---------------------------------------------------------------------------------
     @classmethod
     def from_pretrained(cls, path: str, engine=None) -> "NativeSentenceEncoder":
@@ -317,6 +449,8 @@ class NativeSentenceEncoder:
         rc = read_encoder_config(path)
         if rc["config"].get("model_type") == "mpnet":
             state, rc["desc"].attention_bias = _enc.mpnet_slots(cls._load_weights(path), rc["desc"], rc["pos_start"])
+        elif rc["config"].get("model_type") == "distilbert":
+            state = _enc.distilbert_slots(cls._load_weights(path), rc["desc"])
         else:
             state = slice_positions(cls._load_weights(path), rc["pos_start"])
         return cls(engine or get_engine(), rc["desc"], state, cls._load_tokenizer(path, rc["config"]), rc["max_seq"])
@@ -410,7 +544,7 @@ class NativeSentenceEncoder:
         single = isinstance(sentences, str)
         texts = [sentences] if single else list(sentences)
         if not texts:
-            return np.zeros((0, self.desc.hidden), np.float32)
+            return np.zeros((0, self.desc.out_dim), np.float32)
         ids, off = self.tokenize(texts)
         out = _enc.encode(self.engine, ids, off)
         return out[0] if single else out
@@ -429,7 +563,7 @@ class NativeSentenceEncoder:
         ONE engine call (vr_encode_spans) for all of them."""
         plan = self.plan_documents(documents, prefix)
         if plan.n_chunks == 0:
-            return np.zeros((0, self.desc.hidden), np.float32)
+            return np.zeros((0, self.desc.out_dim), np.float32)
         return _enc.encode_spans(self.engine, plan.ids, plan.offsets, plan.span_off, plan.span_tok)
 
     def encode_document(self, document: str, chunk_texts, prefix: str = ""):

@@ -55,6 +55,26 @@ HUB_RENAMES = [("encoder.layers.", "layers."), ("emb_ln.", "embeddings.LayerNorm
 
 
 @dataclass
+class HeadStage:
+    """One module behind pooling (vr_head_stage). kind "dense": y = act(weight @ x + bias), weight [out, in], bias [out]
+    or None, activation "identity" | "tanh". kind "layernorm": y = (x - mean) / sqrt(var + eps) * weight + bias over
+    the whole row, weight [width], bias [width] or None."""
+    kind: str
+    weight: object
+    bias: object = None
+    activation: str = "identity"
+    eps: float = 1e-5
+
+    @property
+    def in_dim(self) -> int:
+        return int(self.weight.shape[-1])
+
+    @property
+    def out_dim(self) -> int:
+        return int(self.weight.shape[0])
+
+
+@dataclass
 class BertDesc:
     layers: int
     hidden: int
@@ -83,6 +103,18 @@ class BertDesc:
     # alibi_slopes); like attention_bias not a field of vr_bert_desc: load_encoder hands it to
     # vr_encoder_set_attention_slopes once the model is loaded
     attention_slopes: object = field(default=None, compare=False, repr=False)
+    # the post-pooling head: HeadStage objects in order (sentence-transformers' Dense / LayerNorm modules behind
+    # Pooling) and the number of leading columns kept (SentenceTransformer(truncate_dim=...), 0 = all). Not fields of
+    # vr_bert_desc either: load_encoder hands them to vr_encoder_set_head once the model is loaded
+    head: object = field(default=None, compare=False, repr=False)
+    truncate_dim: int = field(default=0, compare=False)
+
+    @property
+    def out_dim(self) -> int:
+        """The width of an embedding row: truncate_dim, or the last head stage's output, or the model's."""
+        if self.truncate_dim:
+            return int(self.truncate_dim)
+        return self.head[-1].out_dim if self.head else self.hidden
 
     @property
     def rotary(self) -> bool:
@@ -303,6 +335,35 @@ def mpnet_slots(state: dict, desc: "BertDesc", pos_start: int = 2):
     return out, mpnet_bias_table(get("encoder.relative_attention_bias.weight"))
 
 
+def distilbert_slots(state: dict, desc: "BertDesc") -> dict:
+    """A transformers DistilBertModel state dict (with or without the `distilbert.` prefix) -> the state under the BERT
+    names of tensor_names(). DistilBERT is BERT's post-LayerNorm body without token types: the token-type slot is a zero
+    [1, H] row, transformer.layer.N's attention.{q,k,v,out}_lin, sa_layer_norm, ffn.lin1 / lin2 and output_layer_norm
+    are BERT's query / key / value / attention.output.dense, attention.output.LayerNorm, intermediate / output dense
+    and output.LayerNorm."""
+
+    def get(name):
+        hits = [k for k in state if k == name or k.endswith("." + name)]
+        if len(hits) != 1:
+            raise KeyError(f"weight '{name}' not found (or ambiguous) in state dict: {hits[:3]}")
+        return state[hits[0]]
+
+    out = {"embeddings.word_embeddings.weight": get("embeddings.word_embeddings.weight"),
+           "embeddings.position_embeddings.weight": get("embeddings.position_embeddings.weight"),
+           "embeddings.token_type_embeddings.weight": np.zeros((1, desc.hidden), np.float32),
+           "embeddings.LayerNorm.weight": get("embeddings.LayerNorm.weight"),
+           "embeddings.LayerNorm.bias": get("embeddings.LayerNorm.bias")}
+    renames = [("attention.self.query", "attention.q_lin"), ("attention.self.key", "attention.k_lin"),
+               ("attention.self.value", "attention.v_lin"), ("attention.output.dense", "attention.out_lin"),
+               ("attention.output.LayerNorm", "sa_layer_norm"), ("intermediate.dense", "ffn.lin1"),
+               ("output.dense", "ffn.lin2"), ("output.LayerNorm", "output_layer_norm")]
+    for i in range(desc.layers):
+        for dst, src in renames:
+            for kind in ("weight", "bias"):
+                out[f"encoder.layer.{i}.{dst}.{kind}"] = get(f"transformer.layer.{i}.{src}.{kind}")
+    return out
+
+
 def alibi_slopes(heads: int) -> np.ndarray:
     """The standard ALiBi slope of every head, float32 [heads] (Press et al., as BLOOM's build_alibi_tensor and
     JinaBert compute them): for a power-of-two n the geometric sequence start^(i + 1), start = 2^(-8/n); otherwise
@@ -443,9 +504,9 @@ def _find(state: dict, suffix: str):
 def load_encoder(engine, desc: BertDesc, state: dict) -> None:
     """state: HF BertModel state dict (any key prefix), values NumPy arrays or torch tensors.
     Tensors on the engine's GPU are passed as device pointers, everything else as host memory.
-    A description that carries an attention_bias table (MPNet, see mpnet_slots) or attention_slopes (ALiBi) sets them
-    once the model is loaded. position "none": a gated description reads a JinaBert state dict (jina_slots), a GELU
-    one a BERT state dict without its position table."""
+    A description that carries an attention_bias table (MPNet, see mpnet_slots), attention_slopes (ALiBi) or a head /
+    truncate_dim sets them once the model is loaded. position "none": a gated description reads a JinaBert state dict
+    (jina_slots), a GELU one a BERT state dict without its position table."""
     if desc.prenorm:
         names, state = modernbert_slots(state, desc)
     elif desc.position == "none":
@@ -463,6 +524,8 @@ def load_encoder(engine, desc: BertDesc, state: dict) -> None:
         engine.set_attention_bias(desc.attention_bias)
     if desc.attention_slopes is not None:
         engine.set_attention_slopes(desc.attention_slopes)
+    if desc.head or desc.truncate_dim:
+        engine.set_encoder_head(desc.head or [], desc.truncate_dim)
 
 
 def load_reranker(engine, desc: BertDesc, state: dict) -> None:
@@ -518,8 +581,8 @@ def _load(engine, desc: BertDesc, state: dict, names: list[str], load_fn) -> Non
 
 
 def encode(engine, ids, offsets, out=None):
-    """ids/offsets: NumPy int32 (host) or torch int32 tensors on the GPU. Returns an (n, H) f32
-    NumPy array, or fills/returns ``out`` when a device tensor is given."""
+    """ids/offsets: NumPy int32 (host) or torch int32 tensors on the GPU. Returns an (n, W) f32
+    NumPy array (W = the description's out_dim), or fills/returns ``out`` when a device tensor is given."""
     desc = engine.encoder_desc
     dev_in = hasattr(ids, "is_cuda") and ids.is_cuda
     if dev_in:
@@ -534,11 +597,11 @@ def encode(engine, ids, offsets, out=None):
         ip, op_ = C.c_void_p(ids.ctypes.data), C.c_void_p(offsets.ctypes.data)
         mem = VR_MEM_HOST
     if out is not None and hasattr(out, "is_cuda") and out.is_cuda:
-        assert out.is_contiguous() and tuple(out.shape) == (n, desc.hidden)
+        assert out.is_contiguous() and tuple(out.shape) == (n, desc.out_dim)
         engine._follow(out)
         check(engine._lib.vr_encode(engine.handle, ip, op_, n, mem, C.c_void_p(out.data_ptr()), VR_MEM_DEVICE))
         return out
-    res = np.empty((n, desc.hidden), np.float32)
+    res = np.empty((n, desc.out_dim), np.float32)
     check(engine._lib.vr_encode(engine.handle, ip, op_, n, mem, C.c_void_p(res.ctypes.data), VR_MEM_HOST))
     return res
 
@@ -546,7 +609,7 @@ def encode(engine, ids, offsets, out=None):
 def encode_spans(engine, ids, offsets, span_off, span_tok, out=None):
     """``encode`` with one row per token span (late chunking): span_off (n_seq + 1) gives each sequence's range of
     spans, span_tok (n_spans, 2) their (begin, end) token positions inside that sequence. All four arrays NumPy int32
-    (host) or torch int32 tensors on the GPU. Returns an (n_spans, H) f32 NumPy array — the mean of each span's final
+    (host) or torch int32 tensors on the GPU. Returns an (n_spans, out_dim) f32 NumPy array — the mean of each span's final
     hidden states, normalised as the description says — or fills/returns ``out`` when a device tensor is given."""
     desc = engine.encoder_desc
     dev_in = hasattr(ids, "is_cuda") and ids.is_cuda
@@ -568,11 +631,11 @@ def encode_spans(engine, ids, offsets, span_off, span_tok, out=None):
         raise ValueError(f"span_tok holds fewer than the {n_spans} (begin, end) pairs span_off announces")
     ip, op_, sop, stp = ptrs
     if out is not None and hasattr(out, "is_cuda") and out.is_cuda:
-        assert out.is_contiguous() and tuple(out.shape) == (max(n_spans, 0), desc.hidden)
+        assert out.is_contiguous() and tuple(out.shape) == (max(n_spans, 0), desc.out_dim)
         engine._follow(out)
         check(engine._lib.vr_encode_spans(engine.handle, ip, op_, n, sop, stp, mem, C.c_void_p(out.data_ptr()),
                                           VR_MEM_DEVICE))
         return out
-    res = np.empty((max(n_spans, 0), desc.hidden), np.float32)
+    res = np.empty((max(n_spans, 0), desc.out_dim), np.float32)
     check(engine._lib.vr_encode_spans(engine.handle, ip, op_, n, sop, stp, mem, C.c_void_p(res.ctypes.data), VR_MEM_HOST))
     return res

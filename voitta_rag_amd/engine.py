@@ -278,6 +278,48 @@ class Engine:
         check(self._lib.vr_encoder_set_attention_slopes(self._h, C.c_void_p(slopes.ctypes.data), slopes.shape[0],
                                                         VR_MEM_HOST))
 
+    def set_encoder_head(self, stages, truncate_dim: int = 0) -> None:
+        """The loaded encoder's post-pooling head (vr_encoder_set_head): `stages`, encoder.HeadStage objects in order
+        (at most four; Dense with identity or tanh, LayerNorm), run in f32 on the un-normalised pooled rows, then the
+        description's normalisation over the whole last width, then the leading truncate_dim columns (0 = all).
+        None with truncate_dim 0 removes the head. Loading an encoder resets it. The description's out_dim follows."""
+        from dataclasses import replace
+
+        if stages is None and not truncate_dim:
+            check(self._lib.vr_encoder_set_head(self._h, None, 0, 0, VR_MEM_HOST))
+        else:
+            stages = list(stages or [])
+            arr = (_lib.VrHeadStage * max(len(stages), 1))()
+            keep = []
+            kinds = {"dense": _lib.VR_HEAD_DENSE, "layernorm": _lib.VR_HEAD_LAYERNORM}
+            acts = {"identity": _lib.VR_ACT_IDENTITY, "tanh": _lib.VR_ACT_TANH}
+
+            def host(t, shape, what):
+                if hasattr(t, "detach"):
+                    t = t.detach().cpu().numpy()
+                t = np.ascontiguousarray(t, dtype=np.float32)
+                if t.shape != shape:
+                    raise ValueError(f"head stage {i}: {what} of shape {t.shape}, expected {shape}")
+                keep.append(t)
+                return t.ctypes.data
+
+            for i, st in enumerate(stages):
+                if st.kind not in kinds:
+                    raise ValueError(f"head stage {i}: unknown kind {st.kind!r}")
+                if st.activation not in acts:
+                    raise ValueError(f"head stage {i}: unknown activation {st.activation!r}")
+                if np.ndim(st.weight) != (2 if st.kind == "dense" else 1):
+                    raise ValueError(f"head stage {i}: a {st.kind} weight of {np.ndim(st.weight)} dimensions")
+                c = arr[i]
+                c.struct_size, c.kind = C.sizeof(_lib.VrHeadStage), kinds[st.kind]
+                c.in_dim, c.out_dim, c.activation, c.eps = st.in_dim, st.out_dim, acts[st.activation], float(st.eps)
+                c.weight = host(st.weight, (st.out_dim, st.in_dim) if st.kind == "dense" else (st.in_dim,), "weight")
+                c.bias = None if st.bias is None else host(st.bias, (st.out_dim,), "bias")
+            check(self._lib.vr_encoder_set_head(self._h, arr, len(stages), int(truncate_dim), VR_MEM_HOST))
+        if getattr(self, "encoder_desc", None) is not None:
+            self.encoder_desc = replace(self.encoder_desc, head=list(stages) if stages else None,
+                                        truncate_dim=int(truncate_dim))
+
     def _index_batch(self, wp_ids, wp_off, spans, bm_ids, bm_off, folder_ids, index_folder_ids, created, modified,
                      k, b, avg_len) -> int:
         dev = _is_device_tensor(wp_ids)

@@ -959,7 +959,7 @@ class VectorStoreService:
         # a question that is still TEXT (embed_query / sparse embed_query results nobody looked at): one engine call
         # does the tokenising, the encode and the search (vr_query_text) — mcp_server.py:469-485 without the Python in between
         if (isinstance(query_embedding, _deferred.QueryRef) and not query_embedding.materialized
-                and query_embedding.model.engine is self._engine and int(query_embedding.model.desc.hidden) == self.dimension
+                and query_embedding.model.engine is self._engine and _deferred.embedding_width(query_embedding.model.desc) == self.dimension
                 and (sparse_query is None or (isinstance(sparse_query, _deferred.SparseQueryRef) and not sparse_query.materialized))):
             model = query_embedding.model
             sparse_text = sparse_query.text if (sparse_query is not None and self._has_sparse) else None
@@ -1225,7 +1225,7 @@ class VectorStoreService:
         model = emb.model
         queries = [requests[i]["query"] for i in live]
         if not (one_call_text_paths(model) and model.engine is self._engine
-                and int(model.desc.hidden) == self.dimension):
+                and _deferred.embedding_width(model.desc) == self.dimension):
             # (an encoder outside this engine: the two services, then search_requests — the definition of the answer)
             from .sparse_embedding import _query_vector
 
