@@ -137,10 +137,10 @@ typedef struct vr_bert_desc {
    * `precision` (struct_size may still be that shorter size; the missing fields are then read as zero). */
   int32_t position;      /* VR_POS_LEARNED | VR_POS_ROTARY | VR_POS_NONE */
   float   rope_theta;    /* VR_POS_ROTARY: base of the rotary frequencies, inv_freq_i = theta^(-2i/d_h); > 0 */
-  int32_t ffn;           /* VR_FFN_GELU | VR_FFN_SWIGLU | VR_FFN_GEGLU */
+  int32_t ffn;           /* VR_FFN_GELU | VR_FFN_SWIGLU | VR_FFN_GEGLU | VR_FFN_RELU */
   /* Added with the pre-norm family (ModernBERT): again zero in every field is the behaviour of a description that
    * ends at `ffn`, and struct_size may be that shorter size. */
-  int32_t norm;          /* VR_NORM_POST | VR_NORM_PRE */
+  int32_t norm;          /* VR_NORM_POST | VR_NORM_PRE | VR_NORM_PRE_RMS */
   int32_t window;        /* sliding-window attention: the half-width w, 0 .. 4096. 0: every layer attends globally.
                           * Otherwise query i of a windowed layer sees key j of its own sequence iff |i - j| <= w */
   int32_t global_every;  /* window > 0: layer l attends globally iff l % global_every == 0 (>= 1), the rest are windowed */
@@ -151,21 +151,30 @@ typedef struct vr_bert_desc {
  * key of every head are rotated by the token's position inside its own sequence (rotate-half pairing: feature j with
  * j + d_h/2, as in HF apply_rotary_pos_emb; the full head is rotated). NONE has no table and no rotation: the
  * embeddings are word + token type, and the model sees order through vr_encoder_set_attention_slopes alone (ALiBi:
- * jina-embeddings-v2). NONE needs VR_NORM_POST and no window. */
+ * jina-embeddings-v2) or vr_encoder_set_attention_bias (T5). NONE needs VR_NORM_POST or VR_NORM_PRE_RMS, and no window. */
 #define VR_POS_LEARNED 0
 #define VR_POS_ROTARY  1
 #define VR_POS_NONE    2
 /* ffn: GELU is down(gelu(up(x))); the gated forms are down(act(gate(x)) * up(x)) with act = SiLU (SWIGLU) or the
- * exact-erf GELU (GEGLU). */
+ * exact-erf GELU (GEGLU). RELU is down(max(up(x), 0)), T5's DenseReluDense: 16 slots per layer like GELU, and
+ * VR_NORM_PRE_RMS only. */
 #define VR_FFN_GELU   0
 #define VR_FFN_SWIGLU 1
 #define VR_FFN_GEGLU  2
+#define VR_FFN_RELU   3
 /* norm: POST is BERT's x = LN(x + f(x)). PRE is x = x + attn(LN(x)), x = x + mlp(LN(x)) with one final LayerNorm; the
  * embedding LayerNorm stays in the stream and layer 0 has no attention norm. PRE needs VR_POS_ROTARY and a gated ffn;
  * a window needs VR_NORM_PRE (and so rotary positions). A reranker takes them together (a ModernBERT cross-encoder, see
- * vr_reranker_load) or not at all. */
+ * vr_reranker_load) or not at all.
+ * PRE_RMS is the T5 encoder: h = word[id] with NO embedding norm in the stream; per layer h += W_o attn(N_a(h)), then
+ * h += W_down relu(W_up N_m(h)); out = N_f(h). Every N is RMSNorm, x * rsqrt(mean(x^2) + eps) * weight (T5LayerNorm: no
+ * mean subtraction, no shift; the slot's bias is ignored and may be NULL). PRE_RMS needs VR_POS_NONE, VR_FFN_RELU,
+ * window 0 and type_vocab 1 (anything else is refused with the field named); a reranker never takes it.
+ * T5's logits are q.k + bias WITHOUT the 1/sqrt(d_h): the engine keeps its scale, and the loader multiplies the query
+ * weight by sqrt(d_h) instead (exactly x8 at head size 64, one f32 rounding per weight at 32). */
 #define VR_NORM_POST 0
 #define VR_NORM_PRE  1
+#define VR_NORM_PRE_RMS 2
 
 /* arithmetic of the encoder's matrix products:
  *   F32    every product on the f32-input MFMA (exact f32 fma chains) — 157 TFLOP/s peak
@@ -192,8 +201,11 @@ typedef struct vr_bert_desc {
  * layer l's attention.output.LayerNorm = the norm in front of layer l's FFN (ModernBERT: layers.l.mlp_norm); layer l's
  * output.LayerNorm = the norm in front of layer l + 1's attention (layers.l+1.attn_norm), and for the last layer the
  * final norm (final_norm). Layer 0's attention reads the embedding norm's output as it is.
+ * VR_NORM_PRE_RMS: the slots as under VR_NORM_PRE with one difference: embeddings.LayerNorm holds block 0's attention
+ * norm (T5: block.0.layer.0.layer_norm) and the stream bypasses it too. Layer l's attention.output.LayerNorm =
+ * block.l.layer.1.layer_norm, layer l's output.LayerNorm = block.l+1.layer.0.layer_norm, the last = final_layer_norm.
  * NULL slots: any bias (read as zeros), and position_embeddings when position is VR_POS_ROTARY or VR_POS_NONE (ignored
- * then).
+ * then); under VR_NORM_PRE_RMS also every LayerNorm bias (ignored) and token_type_embeddings (read as zeros).
  * Every other slot must be non-NULL.
  * The engine copies (and re-packs) them; the caller's tensors may be freed afterwards.
  * Replaces EmbeddingService.model's lazy SentenceTransformer(...) load (embedding.py:23-42). */
@@ -203,10 +215,11 @@ int vr_encoder_load(vr_engine* e, const vr_bert_desc* desc, const void* const* t
 /* Additive attention bias of the loaded ENCODER, by relative offset: every layer's logit of query i against key j of
  * head h becomes q.k/sqrt(d_h) + table[h][clamp(j - i, -radius, radius) + radius]. table: heads x (2*radius + 1) f32
  * in `mem`, copied. 1 <= radius <= 512; heads must equal the loaded description's. Needs VR_POS_LEARNED and
- * VR_NORM_POST (refused otherwise, and while vr_encoder_set_attention_slopes' slopes are set; the encoder stays as it
+ * VR_NORM_POST, or VR_POS_NONE and VR_NORM_PRE_RMS (refused otherwise, and while vr_encoder_set_attention_slopes' slopes are set; the encoder stays as it
  * was). NULL table removes the bias. vr_encoder_load resets it. The reranker never has one.
  * (MPNet: one T5-style bucketed table shared by all layers; its buckets depend on j - i alone and are constant from
- * |j - i| = 128 on, so radius 128 reproduces the model at any length.) */
+ * |j - i| = 128 on, so radius 128 reproduces the model at any length. T5: block 0's relative_attention_bias, the same
+ * buckets, constant from relative_attention_max_distance on.) */
 int vr_encoder_set_attention_bias(vr_engine* e, const float* table, int32_t heads, int32_t radius, int mem);
 
 /* Linear attention bias of the loaded ENCODER (ALiBi): every layer's logit of query i against key j of head h becomes
@@ -317,6 +330,8 @@ int vr_wordpiece_encode_pairs(const vr_wordpiece* t, const char* const* a_texts,
  *   5. Unigram Viterbi over pieces[n_pieces] (NUL-terminated UTF-8, id = index) with f64 scores; characters no piece
  *      covers become unk_id, consecutive ones fused;
  *   6. bos A eos (single), bos A eos eos B eos (pair); truncation as vr_wordpiece_*, with 2 / 4 specials.
+ *      bos_id -1 (a T5 tokenizer, template "$A </s>"): A eos, right truncation keeps the eos (max_len - 1 ids of A);
+ *      vr_unigram_encode_pairs is refused for such a tokenizer.
  * added[n_added] / added_ids / added_flags: the added tokens (NUL-terminated UTF-8 content, id, flags). Malformed
  * UTF-8 bytes become U+FFFD, as in vr_wordpiece_encode. Read-only after creation and thread-safe. */
 typedef struct vr_unigram vr_unigram;

@@ -94,8 +94,10 @@ VR_POS_NONE = 2
 VR_FFN_GELU = 0
 VR_FFN_SWIGLU = 1
 VR_FFN_GEGLU = 2
+VR_FFN_RELU = 3
 VR_NORM_POST = 0
 VR_NORM_PRE = 1
+VR_NORM_PRE_RMS = 2
 VR_POOL_MEAN = 0
 VR_POOL_CLS = 1
 VR_MEM_HOST = 0

@@ -20,6 +20,10 @@
 //   embed_head_kernel the embedder's post-pooling head: Dense / LayerNorm stages, normalise, truncate (vr_encoder_set_head)
 //   rope_kernel       rotary positions, in place on Q and K            HBM bound (VR_POS_ROTARY models only)
 //   glu_kernel        act(gate) * up of a gated FFN                    HBM bound (VR_FFN_SWIGLU / VR_FFN_GEGLU only)
+//   embed_rms_kernel, rmsnorm_kernel, rmsnorm_f16_kernel  the embedding gather and the norms of an RMSNorm pre-norm
+//                     model (VR_NORM_PRE_RMS, the T5 encoder: forward_chunk_rms); its ReLU FFN is EPI_BIAS_RELU of the GEMMs.
+//                     T5's logits carry no 1/sqrt(d_h): launch_attention keeps its scale, the loader folds sqrt(d_h) into
+//                     the query weights (include/voitta_engine.h)
 // Algorithmic FLOP per token = L * (24 H^2 + 4 S H), of which the GEMMs are
 // 24 H^2 L: the dominant kernel of the indexing path.
 
@@ -272,14 +276,50 @@ __device__ __forceinline__ float ln_apply(float v, float mean, float inv, float 
   return (v - mean) * inv * g + b;
 }
 
+// one element of an RMSNorm output (T5LayerNorm: no mean, no shift), the one expression every kernel that norms so uses
+__device__ __forceinline__ float rms_apply(float v, float inv, float g) { return v * inv * g; }
+
 // LayerNorm of one row held as float2 pairs per lane (biased variance, eps inside the sqrt).
 // out_hi/out_lo (optional): the same row split for the f16x3 GEMMs.
+// RMS (VR_NORM_PRE_RMS): x * rsqrt(mean(x^2) + eps) * g instead — one sum of squares in the same fixed order, no mean
+// pass, and b is never read (it may be null); stat gets (0, 1/rms). RMS = false is the code that never knew the flag.
+template <bool RMS = false>
 __device__ __forceinline__ void row_layernorm(float2 (&v)[kMaxPairs], int pairs, int H,
                                               const float* __restrict__ g,
                                               const float* __restrict__ b, float eps, int lane,
                                               float* __restrict__ out, half_t* __restrict__ out_hi = nullptr,
                                               half_t* __restrict__ out_lo = nullptr,
                                               float2* __restrict__ stat = nullptr) {
+  if constexpr (RMS) {
+    float q = 0.0f;
+#pragma unroll
+    for (int i = 0; i < kMaxPairs; ++i)
+      if (i < pairs) q += v[i].x * v[i].x + v[i].y * v[i].y;
+    const float inv = 1.0f / sqrtf(wave_sum(q) / static_cast<float>(H) + eps);
+    if (stat && lane == 0) *stat = make_float2(0.0f, inv);
+#pragma unroll
+    for (int i = 0; i < kMaxPairs; ++i)
+      if (i < pairs) {
+        int e = (i * 64 + lane) * 2;
+        float2 gg = *reinterpret_cast<const float2*>(g + e);
+        float2 o;
+        o.x = rms_apply(v[i].x, inv, gg.x);
+        o.y = rms_apply(v[i].y, inv, gg.y);
+        if (out) *reinterpret_cast<float2*>(out + e) = o;
+        if (out_hi) {
+          half2_t h, l;
+          split_f16(o.x, h.x, l.x);
+          split_f16(o.y, h.y, l.y);
+          if (out_lo) {
+            *reinterpret_cast<half2_t*>(out_hi + split_at(e)) = h;
+            *reinterpret_cast<half2_t*>(out_lo + split_at(e)) = l;
+          } else {
+            *reinterpret_cast<half2_t*>(out_hi + e) = h;
+          }
+        }
+      }
+    return;
+  }
   float s = 0.0f;
 #pragma unroll
   for (int i = 0; i < kMaxPairs; ++i)
@@ -324,7 +364,8 @@ __device__ __forceinline__ void row_layernorm(float2 (&v)[kMaxPairs], int pairs,
 // one wave per token: x[t] = LayerNorm(word[id] + pos[p] + type[0]); SEG (a cross-encoder's pairs): type[1] for the
 // positions p >= seg_b[sequence], the segment-B tokens. POS = false (a rotary model): word + type only, no table is read.
 // (The body of embed_ln_kernel and embed_ln_rotary_kernel: two kernels, so that the former keeps its signature.)
-template <bool SEG, bool POS>
+// RMS (VR_NORM_PRE_RMS): `pre`, the raw row, is the residual stream; the norm (block 0's attention norm) is row_layernorm<true>.
+template <bool SEG, bool POS, bool RMS = false>
 __device__ __forceinline__ void embed_ln_body(const int32_t* __restrict__ ids,
                                               const int32_t* __restrict__ cu, int n_seq,
                                               int tok_base, int T, int H, int vocab,
@@ -369,8 +410,8 @@ __device__ __forceinline__ void embed_ln_body(const int32_t* __restrict__ ids,
       if (pre) *reinterpret_cast<float2*>(pre + static_cast<int64_t>(t) * H + e) = v[i];  // the pre-LN row
     }
   const int64_t o = static_cast<int64_t>(t) * H;
-  row_layernorm(v, pairs, H, g, b, eps, lane, x ? x + o : nullptr, x_hi ? x_hi + (x_lo ? 2 : 1) * o : nullptr,
-                x_lo ? x_lo + 2 * o : nullptr, stat ? stat + t : nullptr);
+  row_layernorm<RMS>(v, pairs, H, g, b, eps, lane, x ? x + o : nullptr, x_hi ? x_hi + (x_lo ? 2 : 1) * o : nullptr,
+                     x_lo ? x_lo + 2 * o : nullptr, stat ? stat + t : nullptr);
 }
 
 template <bool SEG>
@@ -403,6 +444,20 @@ __global__ __launch_bounds__(256) void embed_ln_rotary_kernel(const int32_t* __r
                               nullptr);
 }
 
+// VR_NORM_PRE_RMS (T5): pre[t] = word[id] + type[0], the residual stream as it is; x / x_hi / x_lo = RMSNorm(pre[t]) by g,
+// the rows block 0's Q/K/V projection reads
+__global__ __launch_bounds__(256) void embed_rms_kernel(const int32_t* __restrict__ ids,
+                                                        const int32_t* __restrict__ cu, int n_seq,
+                                                        int tok_base, int T, int H, int vocab,
+                                                        const float* __restrict__ word,
+                                                        const float* __restrict__ type,
+                                                        const float* __restrict__ g, float eps,
+                                                        float* __restrict__ x, half_t* __restrict__ x_hi,
+                                                        half_t* __restrict__ x_lo, float* __restrict__ pre) {
+  embed_ln_body<false, false, true>(ids, cu, n_seq, tok_base, T, H, vocab, word, nullptr, type, g, nullptr, eps, x, x_hi, x_lo,
+                                    pre, nullptr, nullptr);
+}
+
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ in, int T, int H,
                                                         const float* __restrict__ g,
                                                         const float* __restrict__ b, float eps,
@@ -419,6 +474,25 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
   const int64_t o = static_cast<int64_t>(t) * H;
   row_layernorm(v, pairs, H, g, b, eps, lane, out ? out + o : nullptr, out_hi ? out_hi + (out_lo ? 2 : 1) * o : nullptr,
                 out_lo ? out_lo + 2 * o : nullptr, stat ? stat + t : nullptr);
+}
+
+// the same launch with RMSNorm rows (VR_NORM_PRE_RMS): row_layernorm's RMS state. (A kernel beside layernorm_kernel, not
+// a template state of it: that kernel keeps its name and its bytes.)
+__global__ __launch_bounds__(256) void rmsnorm_kernel(const float* __restrict__ in, int T, int H,
+                                                      const float* __restrict__ g, float eps,
+                                                      float* __restrict__ out, half_t* __restrict__ out_hi,
+                                                      half_t* __restrict__ out_lo) {
+  const int lane = threadIdx.x & 63;
+  const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (t >= T) return;
+  const int pairs = H / 128;
+  float2 v[kMaxPairs];
+#pragma unroll
+  for (int i = 0; i < kMaxPairs; ++i)
+    if (i < pairs) v[i] = *reinterpret_cast<const float2*>(in + static_cast<int64_t>(t) * H + (i * 64 + lane) * 2);
+  const int64_t o = static_cast<int64_t>(t) * H;
+  row_layernorm<true>(v, pairs, H, g, nullptr, eps, lane, out ? out + o : nullptr,
+                      out_hi ? out_hi + (out_lo ? 2 : 1) * o : nullptr, out_lo ? out_lo + 2 * o : nullptr, nullptr);
 }
 
 // f16-mode LayerNorm for H % 256 == 0: the row as float4 per lane (16-byte loads, 8-byte f16 stores —
@@ -469,6 +543,39 @@ __global__ __launch_bounds__(256) void layernorm_f16_kernel(const float* __restr
       split_f16(r.y, h[1], l[1]);
       split_f16(r.z, h[2], l[2]);
       split_f16(r.w, h[3], l[3]);
+      *reinterpret_cast<uint2*>(out_h + o + e) = *reinterpret_cast<const uint2*>(h);
+    }
+}
+
+// layernorm_f16_kernel's RMSNorm twin (VR_NORM_PRE_RMS), the same loads and stores: one fixed-order sum of squares, no
+// mean pass, no shift; the f16 row only. (A kernel of its own for the reason rmsnorm_kernel is one.)
+__global__ __launch_bounds__(256) void rmsnorm_f16_kernel(const float* __restrict__ in, int T, int H,
+                                                          const float* __restrict__ g, float eps,
+                                                          half_t* __restrict__ out_h) {
+  const int lane = threadIdx.x & 63;
+  const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (t >= T) return;
+  const int quads = H / 256;  // <= 4
+  const int64_t o = static_cast<int64_t>(t) * H;
+  float4 v[4];
+  float q = 0.0f;
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    if (i < quads) {
+      v[i] = *reinterpret_cast<const float4*>(in + o + (i * 64 + lane) * 4);
+      q += (v[i].x * v[i].x + v[i].y * v[i].y) + (v[i].z * v[i].z + v[i].w * v[i].w);
+    }
+  const float inv = 1.0f / sqrtf(wave_sum(q) / static_cast<float>(H) + eps);
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    if (i < quads) {
+      const int e = (i * 64 + lane) * 4;
+      const float4 gg = *reinterpret_cast<const float4*>(g + e);
+      half_t h[4], l[4];
+      split_f16(rms_apply(v[i].x, inv, gg.x), h[0], l[0]);
+      split_f16(rms_apply(v[i].y, inv, gg.y), h[1], l[1]);
+      split_f16(rms_apply(v[i].z, inv, gg.z), h[2], l[2]);
+      split_f16(rms_apply(v[i].w, inv, gg.w), h[3], l[3]);
       *reinterpret_cast<uint2*>(out_h + o + e) = *reinterpret_cast<const uint2*>(h);
     }
 }
@@ -1068,7 +1175,9 @@ enum { EPI_BIAS = 0, EPI_BIAS_GELU = 1, EPI_BIAS_RESIDUAL = 2, EPI_BIAS_F16 = 3,
        EPI_ROPE_F16 = 11, EPI_SWIGLU_F16 = 12, EPI_GEGLU_F16 = 13,
        // the direct_epilogue kernels (mid, ping-pong) on the large-batch path: FOLD_F16's folded LayerNorm over the
        // gain-scaled INTERLEAVED matrix, then act(gate) * up of the lane's four (gate, up) column pairs, N/2 f16 columns out
-       EPI_FOLD_SWIGLU = 14, EPI_FOLD_GEGLU = 15 };
+       EPI_FOLD_SWIGLU = 14, EPI_FOLD_GEGLU = 15,
+       // BIAS_GELU with max(x, 0) in the GELU's place (VR_FFN_RELU), in every kernel BIAS_GELU exists for, same output forms
+       EPI_BIAS_RELU = 16 };
 
 // Run-time epilogue id -> template argument: f(std::integral_constant<int, E>{}) for the E of the list that equals
 // `epi`. Every launcher names the epilogues its kernel is instantiated for once, in its call of this; an id outside
@@ -1215,6 +1324,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const float* __restrict__
         if (row < M) {
           float v = acc[i][j][r] + bs;
           if (EPI == EPI_BIAS_GELU) v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
+          if (EPI == EPI_BIAS_RELU) v = fmaxf(v, 0.0f);
           if (EPI == EPI_BIAS_RESIDUAL) v += R[static_cast<int64_t>(row) * N + col];
           C[static_cast<int64_t>(row) * N + col] = v;
         }
@@ -1229,7 +1339,7 @@ static int launch_gemm(vr_engine* e, int epi, const float* A, const float* W, co
   hipStream_t s = e->stream;
   const int grid = ((M + BM - 1) / BM) * (N / BN);
   prof_begin(e, VR_PROF_GEMM, 2.0 * M * static_cast<double>(N) * K);
-  const bool known = with_epi<EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESIDUAL>(epi, [&](auto E) {
+  const bool known = with_epi<EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESIDUAL, EPI_BIAS_RELU>(epi, [&](auto E) {
     hipLaunchKernelGGL((gemm_f32_kernel<decltype(E)::value>), dim3(grid), dim3(256), 0, s, A, W, bias, R, C, M, N, K);
   });
   prof_end(e);
@@ -1248,7 +1358,7 @@ constexpr int HLDT = HBK_ + 8;                     // padded LDS row: 72 halfs =
 // and issues 2*2*3 MFMAs (hi*hi, hi*lo, lo*hi) into one f32 accumulator per tile.
 // Staging moves whole 128-B lines (8 lanes x 16 B per row): the next K-tile is loaded into
 // registers while the current one is multiplied out of the single 72-KiB LDS image (2 blocks/CU).
-// EPI_BIAS: f32 out. EPI_BIAS_GELU: split (hi, lo) out only. EPI_BIAS_RESIDUAL: + R, f32 out.
+// EPI_BIAS: f32 out. EPI_BIAS_GELU / EPI_BIAS_RELU: split (hi, lo) out only. EPI_BIAS_RESIDUAL: + R, f32 out.
 template <int EPI>
 __global__ __launch_bounds__(256) void gemm_f16x3_kernel(
     const half_t* __restrict__ Ah, const half_t* __restrict__ Al, const half_t* __restrict__ Wh,
@@ -1382,12 +1492,12 @@ __global__ __launch_bounds__(256) void gemm_f16x3_kernel(
     v.z = v.z * unscale + b4.z;
     v.w = v.w * unscale + b4.w;
     const int64_t o = static_cast<int64_t>(grow) * N + gcol;
-    if (EPI == EPI_BIAS_GELU) {
+    if (EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_RELU) {
       float g[4] = {v.x, v.y, v.z, v.w};
       half_t h[4], l[4];
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
-        g[c] = gelu_fast(g[c]);
+        g[c] = EPI == EPI_BIAS_RELU ? fmaxf(g[c], 0.0f) : gelu_fast(g[c]);
         split_f16(g[c], h[c], l[c]);
       }
       const int64_t so = static_cast<int64_t>(grow) * (2 * N) + split_at(gcol);
@@ -1644,7 +1754,19 @@ __global__ __launch_bounds__(512) void gemm_f16x3_256_kernel(
         v.w = v.w * unscale + b4.w;
       }
       const int64_t o = static_cast<int64_t>(grow) * N + gcol;
-      if (EPI == EPI_BIAS_GELU || EPI == EPI_FOLD_GELU) {
+      if (EPI == EPI_BIAS_RELU) {  // (split_f16 saturates)
+        const float g[4] = {fmaxf(v.x, 0.0f), fmaxf(v.y, 0.0f), fmaxf(v.z, 0.0f), fmaxf(v.w, 0.0f)};
+        half_t h[4], l[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) split_f16(g[c], h[c], l[c]);
+        if (PASSES == 3) {
+          const int64_t so = static_cast<int64_t>(grow) * (2 * N) + split_at(gcol);
+          *reinterpret_cast<uint2*>(Ch + so) = *reinterpret_cast<const uint2*>(h);
+          *reinterpret_cast<uint2*>(Cl + so) = *reinterpret_cast<const uint2*>(l);
+        } else {
+          *reinterpret_cast<uint2*>(Ch + o) = *reinterpret_cast<const uint2*>(h);
+        }
+      } else if (EPI == EPI_BIAS_GELU || EPI == EPI_FOLD_GELU) {
         const f32x2 g01 = PASSES == 1 ? gelu_poly2(f32x2{v.x, v.y}) : gelu_fast2(f32x2{v.x, v.y});
         const f32x2 g23 = PASSES == 1 ? gelu_poly2(f32x2{v.z, v.w}) : gelu_fast2(f32x2{v.z, v.w});
         float g[4] = {g01.x, g01.y, g23.x, g23.y};
@@ -1794,7 +1916,8 @@ __device__ __forceinline__ void direct_epilogue(f32x4 (&acc)[8][4], int row0, in
   constexpr bool kResidLN = EPI == EPI_BIAS_RESIDUAL_LN || kStats;
   constexpr bool kResidual = EPI == EPI_BIAS_RESIDUAL || kResidLN;
   constexpr bool kGelu = EPI == EPI_BIAS_GELU || EPI == EPI_FOLD_GELU;
-  constexpr bool kHalfOut = kGelu || EPI == EPI_BIAS_F16 || EPI == EPI_FOLD_F16 || kNoOut32;
+  constexpr bool kRelu = EPI == EPI_BIAS_RELU;
+  constexpr bool kHalfOut = kGelu || kRelu || EPI == EPI_BIAS_F16 || EPI == EPI_FOLD_F16 || kNoOut32;
   // fragment pair p2 (features fbase + 32 p2 .. + 7) outside, the eight 16-token pieces inside: the column
   // vectors (bias, LayerNorm gain / shift or column sums) of one pair stay in registers, not those of all four
   // fragments (which, with the residual rows in flight, did not fit next to the 128 accumulators)
@@ -1913,6 +2036,12 @@ __device__ __forceinline__ void direct_epilogue(f32x4 (&acc)[8][4], int row0, in
 #pragma unroll
         for (int q = 0; q < 2; ++q)
           v[q][0] = g[2 * q].x, v[q][1] = g[2 * q].y, v[q][2] = g[2 * q + 1].x, v[q][3] = g[2 * q + 1].y;
+      }
+      if (kRelu) {
+#pragma unroll
+        for (int q = 0; q < 2; ++q)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) v[q][r] = fmaxf(v[q][r], 0.0f);
       }
       if (kGlu) {
         // the lane's eight columns are four (gate, up) pairs of the interleaved matrix: four f16 outputs at column c0 / 2
@@ -2062,6 +2191,10 @@ __device__ __forceinline__ void f16_tile_epilogue(f32x4 (&acc)[8][4], int row0, 
             }
           }
         if (kGelu) gelu_poly2x4(g);
+        if (EPI == EPI_BIAS_RELU) {
+#pragma unroll
+          for (int c = 0; c < 4; ++c) g[c] = f32x2{fmaxf(g[c].x, 0.0f), fmaxf(g[c].y, 0.0f)};
+        }
         f16x8 h;
 #pragma unroll
         for (int q = 0; q < 2; ++q)
@@ -2410,7 +2543,8 @@ __global__ __launch_bounds__(512) void gemm_f16_pp_kernel(
   // in the last two phases of the K loop) are NOT waited for before the epilogue — their latency runs under its arithmetic —
   // but by counted waits in the first two phases of the next K loop that let exactly the younger operations (A hi where
   // it applies, the kEpiStores stores, the phase's own loads) stay in flight. Every other epilogue drains vmcnt first.
-  constexpr bool kTileEpilogue = EPI == EPI_FOLD_F16 || EPI == EPI_FOLD_GELU || EPI == EPI_BIAS_F16 || EPI == EPI_BIAS_GELU;
+  constexpr bool kTileEpilogue = EPI == EPI_FOLD_F16 || EPI == EPI_FOLD_GELU || EPI == EPI_BIAS_F16 || EPI == EPI_BIAS_GELU ||
+                                 EPI == EPI_BIAS_RELU;
   constexpr int kEpiStores = kTileEpilogue ? 16 : -1;
   bool counted_tail = false;  // block-uniform: the previous tile's epilogue left W hi / A hi to the counted waits
 #define VR_PP_VMCNT_TAIL() asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kEpiStores > 0 ? kEpiStores + 4 : 0) : "memory")
@@ -2801,6 +2935,7 @@ __device__ __forceinline__ void skinny_apply(float4 v, int m, int n, int N, floa
     const f32x2 g01 = gelu_poly2(f32x2{v.x, v.y}), g23 = gelu_poly2(f32x2{v.z, v.w});  // f16 mode only
     v = make_float4(g01.x, g01.y, g23.x, g23.y);
   }
+  if (EPI == EPI_BIAS_RELU) v = make_float4(fmaxf(v.x, 0.0f), fmaxf(v.y, 0.0f), fmaxf(v.z, 0.0f), fmaxf(v.w, 0.0f));
   if (EPI == EPI_SWIGLU_F16 || EPI == EPI_GEGLU_F16) {  // columns n .. n + 3 = gate_j, up_j, gate_j+1, up_j+1, j = n / 2
     constexpr int kFfn = EPI == EPI_SWIGLU_F16 ? VR_FFN_SWIGLU : VR_FFN_GEGLU;
     const float o0 = glu_act<false>(v.x, kFfn) * v.y, o1 = glu_act<false>(v.z, kFfn) * v.w;
@@ -2822,7 +2957,7 @@ __device__ __forceinline__ void skinny_apply(float4 v, int m, int n, int N, floa
       v.w = y1 * cs.z + x1 * cs.w;
     }
   }
-  if (EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_F16 || EPI == EPI_ROPE_F16) {
+  if (EPI == EPI_BIAS_GELU || EPI == EPI_BIAS_RELU || EPI == EPI_BIAS_F16 || EPI == EPI_ROPE_F16) {
     half_t h[4] = {static_cast<half_t>(fminf(fmaxf(v.x, -65504.0f), 65504.0f)),
                    static_cast<half_t>(fminf(fmaxf(v.y, -65504.0f), 65504.0f)),
                    static_cast<half_t>(fminf(fmaxf(v.z, -65504.0f), 65504.0f)),
@@ -2991,7 +3126,8 @@ struct GemmArgs {
 // the kernels whose epilogue is direct_epilogue (gemm_f16_mid_kernel, gemm_f16_pp_kernel) exist for these
 #define VR_DIRECT_EPIS                                                                                          \
   EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESIDUAL, EPI_BIAS_F16, EPI_BIAS_RESIDUAL_LN, EPI_FOLD_F16, EPI_FOLD_GELU,  \
-      EPI_FOLD_SWIGLU, EPI_FOLD_GEGLU, EPI_BIAS_RESIDUAL_LN_STATS, EPI_RLS_R32_O16, EPI_RLS_R16_O16, EPI_RLS_R16_O32
+      EPI_FOLD_SWIGLU, EPI_FOLD_GEGLU, EPI_BIAS_RESIDUAL_LN_STATS, EPI_RLS_R32_O16, EPI_RLS_R16_O16, EPI_RLS_R16_O32,     \
+      EPI_BIAS_RELU
 
 // (the launch_* below return false for an epilogue their kernel does not exist for: launch_gemm_f16x3 reports it)
 template <int PASSES>
@@ -3002,9 +3138,9 @@ static bool launch_256(int epi, int grid, hipStream_t s, const GemmArgs& g) {
   };
   if constexpr (PASSES == 1)  // the EPI_FOLD_* / *_STATS variants exist for plain f16 operands only
     return with_epi<EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESIDUAL, EPI_BIAS_F16, EPI_BIAS_RESIDUAL_LN, EPI_FOLD_F16,
-                    EPI_FOLD_GELU, EPI_BIAS_RESIDUAL_LN_STATS>(epi, launch);
+                    EPI_FOLD_GELU, EPI_BIAS_RESIDUAL_LN_STATS, EPI_BIAS_RELU>(epi, launch);
   else
-    return with_epi<EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESIDUAL, EPI_BIAS_F16, EPI_BIAS_RESIDUAL_LN>(epi, launch);
+    return with_epi<EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESIDUAL, EPI_BIAS_F16, EPI_BIAS_RESIDUAL_LN, EPI_BIAS_RELU>(epi, launch);
 }
 
 // the ping-pong kernel serves the f16 mode when K is whole pairs of 64-deep K-tiles and a lane's 8 features are in
@@ -3051,14 +3187,16 @@ static bool launch_pp(int epi, int grid, hipStream_t s, const GemmArgs& g) {
 // the LayerNorm output from the pre-LN row). K = hidden size: each wave holds STEPS * 8 values per row.
 // Two launches fewer per layer for a single query (7 -> 5): its forward pass is launch latency, not work.
 // (gemm_f16_skinny_ln_body: shared by the kernel below and its rotary twin, which has two arguments more)
-template <int EPI, int STEPS, int NW>
+// RMS (VR_NORM_PRE_RMS, gemm_f16_skinny_rms_kernel): the folded norm is RMSNorm — the sum pass and its `part` reduction
+// are gone, the one that is left sums the squares of the values themselves, ln_b is never read, stat_out gets (0, 1/rms).
+template <int EPI, int STEPS, int NW, bool RMS = false>
 __device__ __forceinline__ void gemm_f16_skinny_ln_body(
     const float* __restrict__ pre, const float* __restrict__ ln_g, const float* __restrict__ ln_b, float eps,
     float2* __restrict__ stat_out, const half_t* __restrict__ W, int M, int N, int K, float unscale,
     const float* __restrict__ bias, half_t* __restrict__ Ch, const float2* __restrict__ rope_tab,
     const int32_t* __restrict__ rope_pos) {
   __shared__ float red[NW][16][17];  // [wave][output column][activation row (+1 pad)]
-  __shared__ float part[2][NW][16];  // row sums per wave: [pass][wave][row]
+  __shared__ float part[RMS ? 1 : 2][NW][16];  // row sums per wave: [pass][wave][row]
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   const int n0 = blockIdx.x * 16;
@@ -3078,14 +3216,18 @@ __device__ __forceinline__ void gemm_f16_skinny_ln_body(
     for (int j = 0; j < 8; ++j) sum += x[u][j];
   }
   // a row's values of this wave sit in the four lanes row, row + 16, row + 32, row + 48
-  sum += __shfl_xor(sum, 16);
-  sum += __shfl_xor(sum, 32);
-  if (g == 0) part[0][wave][row] = sum;
-  __syncthreads();
-  float total = part[0][0][row];
+  float mean = 0.0f;  // (RMS: stays 0, and the squares below are the values' own)
+  if constexpr (!RMS) {
+    sum += __shfl_xor(sum, 16);
+    sum += __shfl_xor(sum, 32);
+    if (g == 0) part[0][wave][row] = sum;
+    __syncthreads();
+    float total = part[0][0][row];
 #pragma unroll
-  for (int w = 1; w < NW; ++w) total += part[0][w][row];
-  const float mean = total / static_cast<float>(K);
+    for (int w = 1; w < NW; ++w) total += part[0][w][row];
+    mean = total / static_cast<float>(K);
+  }
+  constexpr int kSq = RMS ? 0 : 1;  // the `part` plane of the squares
   float sq = 0.0f;
 #pragma unroll
   for (int u = 0; u < STEPS; ++u)
@@ -3096,25 +3238,29 @@ __device__ __forceinline__ void gemm_f16_skinny_ln_body(
     }
   sq += __shfl_xor(sq, 16);
   sq += __shfl_xor(sq, 32);
-  if (g == 0) part[1][wave][row] = sq;
+  if (g == 0) part[kSq][wave][row] = sq;
   __syncthreads();
-  float total_sq = part[1][0][row];
+  float total_sq = part[kSq][0][row];
 #pragma unroll
-  for (int w = 1; w < NW; ++w) total_sq += part[1][w][row];
+  for (int w = 1; w < NW; ++w) total_sq += part[kSq][w][row];
   const float inv = 1.0f / sqrtf(total_sq / static_cast<float>(K) + eps);
   if (blockIdx.x == 0 && wave == 0 && g == 0 && row < M) stat_out[row] = make_float2(mean, inv);
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int u = 0; u < STEPS; ++u) {
     const float4 g0 = *reinterpret_cast<const float4*>(ln_g + k0 + 8 * g + 32 * u), g1 = *reinterpret_cast<const float4*>(ln_g + k0 + 8 * g + 32 * u + 4);
-    const float4 b0 = *reinterpret_cast<const float4*>(ln_b + k0 + 8 * g + 32 * u), b1 = *reinterpret_cast<const float4*>(ln_b + k0 + 8 * g + 32 * u + 4);
+    float4 b0 = {}, b1 = {};
+    if constexpr (!RMS) {
+      b0 = *reinterpret_cast<const float4*>(ln_b + k0 + 8 * g + 32 * u), b1 = *reinterpret_cast<const float4*>(ln_b + k0 + 8 * g + 32 * u + 4);
+    }
     const float gg[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
     const float bb[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
     f16x8 af;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       half_t h, l;
-      split_f16(ln_apply(x[u][j], mean, inv, gg[j], bb[j]), h, l);  // as layernorm_f16_kernel rounds its output
+      // as layernorm_f16_kernel (RMS: rmsnorm_f16_kernel) rounds its output
+      split_f16(RMS ? rms_apply(x[u][j], inv, gg[j]) : ln_apply(x[u][j], mean, inv, gg[j], bb[j]), h, l);
       af[j] = h;
     }
     acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf[u], af, acc, 0, 0, 0);
@@ -3146,6 +3292,15 @@ __global__ __launch_bounds__(NW * 64) void gemm_f16_skinny_ln_kernel(
   gemm_f16_skinny_ln_body<EPI, STEPS, NW>(pre, ln_g, ln_b, eps, stat_out, W, M, N, K, unscale, bias, Ch, nullptr, nullptr);
 }
 
+// VR_NORM_PRE_RMS: the folded norm is RMSNorm (no shift argument)
+template <int EPI, int STEPS, int NW>
+__global__ __launch_bounds__(NW * 64) void gemm_f16_skinny_rms_kernel(
+    const float* __restrict__ pre, const float* __restrict__ ln_g, float eps, float2* __restrict__ stat_out,
+    const half_t* __restrict__ W, int M, int N, int K, float unscale, const float* __restrict__ bias,
+    half_t* __restrict__ Ch) {
+  gemm_f16_skinny_ln_body<EPI, STEPS, NW, true>(pre, ln_g, nullptr, eps, stat_out, W, M, N, K, unscale, bias, Ch, nullptr, nullptr);
+}
+
 // EPI_ROPE_F16: the Q/K/V projection of a rotary model, with the cos/sin table and the rows' positions
 template <int STEPS, int NW>
 __global__ __launch_bounds__(NW * 64) void gemm_f16_skinny_ln_rope_kernel(
@@ -3161,11 +3316,24 @@ static bool skinny_ln_supported(int M, int N, int K) { return M <= 16 && N % 16 
 
 // `pre`: the pre-LayerNorm f32 rows, `stat_out`: where block 0 stores their statistics; of `g`: W, bias, Ch, M, N, K,
 // ln_g / ln_b (the folded LayerNorm's gain and shift) and, for EPI_ROPE_F16, rope_tab / rope_pos
-static int launch_skinny_ln(vr_engine* e, int epi, const float* pre, float eps, float2* stat_out, const GemmArgs& g) {
+// rms: the folded norm is RMSNorm by ln_g (EPI_BIAS_F16 and EPI_BIAS_RELU only)
+static int launch_skinny_ln(vr_engine* e, int epi, const float* pre, float eps, float2* stat_out, const GemmArgs& g,
+                            bool rms = false) {
   hipStream_t s = e->stream;
   prof_begin(e, VR_PROF_GEMM, 2.0 * g.M * static_cast<double>(g.N) * g.K);
   const dim3 grid(static_cast<unsigned>(g.N / 16));
-  const bool known = with_epi<EPI_BIAS_F16, EPI_BIAS_GELU, EPI_ROPE_F16, EPI_SWIGLU_F16, EPI_GEGLU_F16>(epi, [&](auto E) {
+  auto rms_launch = [&](auto E) {
+    auto launch = [&](auto ST, auto NWV) {
+      constexpr int kE = decltype(E)::value, kSteps = decltype(ST)::value, kWaves = decltype(NWV)::value;
+      hipLaunchKernelGGL((gemm_f16_skinny_rms_kernel<kE, kSteps, kWaves>), grid, dim3(kWaves * 64), 0, s, pre, g.ln_g, eps,
+                         stat_out, g.W.hi, g.M, g.N, g.K, g.W.unscale, g.bias, g.Ch);
+    };
+    if (g.K == 768) launch(std::integral_constant<int, 3>{}, std::integral_constant<int, 8>{});
+    else if (g.K == 1024) launch(std::integral_constant<int, 4>{}, std::integral_constant<int, 8>{});
+    else launch(std::integral_constant<int, 3>{}, std::integral_constant<int, 4>{});
+  };
+  const bool known = rms ? with_epi<EPI_BIAS_F16, EPI_BIAS_RELU>(epi, rms_launch) :
+                     with_epi<EPI_BIAS_F16, EPI_BIAS_GELU, EPI_ROPE_F16, EPI_SWIGLU_F16, EPI_GEGLU_F16>(epi, [&](auto E) {
     auto launch = [&](auto ST, auto NWV) {
       constexpr int kE = decltype(E)::value, kSteps = decltype(ST)::value, kWaves = decltype(NWV)::value;
       if constexpr (kE == EPI_ROPE_F16)  // (a kernel of its own: two arguments more)
@@ -3196,7 +3364,8 @@ static bool skinny_routed(int M, int N, int K) {
 
 // the skinny kernels (skinny_apply) exist for these
 #define VR_SKINNY_EPIS \
-  EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESIDUAL, EPI_BIAS_F16, EPI_BIAS_RESIDUAL_LN, EPI_ROPE_F16, EPI_SWIGLU_F16, EPI_GEGLU_F16
+  EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESIDUAL, EPI_BIAS_F16, EPI_BIAS_RESIDUAL_LN, EPI_ROPE_F16, EPI_SWIGLU_F16, EPI_GEGLU_F16, \
+      EPI_BIAS_RELU
 
 // g.passes = 3: operands are interleaved (hi, lo) rows (A_lo = A + 8, W.lo = W.hi + 8); 1: plain f16 rows, A_lo / W.lo
 // unused. enc: the model whose forward pass this is (its split-K scratch and graph cache)
@@ -3267,7 +3436,7 @@ static int launch_gemm_f16x3(vr_engine* e, Encoder* enc, int epi, const GemmArgs
   } else {
     VR_CHECK(N % HBN_ == 0, "GEMM shape N=%d must be a multiple of %d", N, HBN_);
     const int grid = ((M + HBM_ - 1) / HBM_) * (N / HBN_);
-    known = with_epi<EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESIDUAL>(epi, [&](auto E) {
+    known = with_epi<EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_RESIDUAL, EPI_BIAS_RELU>(epi, [&](auto E) {
       hipLaunchKernelGGL((gemm_f16x3_kernel<decltype(E)::value>), dim3(grid), dim3(256), 0, s, g.A, g.A_lo, g.W.hi, g.W.lo, g.bias,
                          g.R, g.C, g.Ch, g.Cl, M, N, K, g.W.unscale);
     });
@@ -4121,13 +4290,25 @@ static int build_encoder(vr_engine* e, void** slot, const vr_bert_desc* d_in, co
   const int H = d->hidden, I = d->intermediate, L = d->layers;
   VR_CHECK(d->position == VR_POS_LEARNED || d->position == VR_POS_ROTARY || d->position == VR_POS_NONE,
            "unknown position scheme %d", d->position);
-  VR_CHECK(d->ffn == VR_FFN_GELU || d->ffn == VR_FFN_SWIGLU || d->ffn == VR_FFN_GEGLU, "unknown ffn kind %d", d->ffn);
-  const bool rotary = d->position == VR_POS_ROTARY, gated = d->ffn != VR_FFN_GELU;
+  VR_CHECK(d->ffn == VR_FFN_GELU || d->ffn == VR_FFN_SWIGLU || d->ffn == VR_FFN_GEGLU || d->ffn == VR_FFN_RELU,
+           "unknown ffn kind %d", d->ffn);
+  const bool rotary = d->position == VR_POS_ROTARY, gated = d->ffn == VR_FFN_SWIGLU || d->ffn == VR_FFN_GEGLU;
   const int per_layer = gated ? 18 : 16;
   VR_CHECK(!rotary || (std::isfinite(d->rope_theta) && d->rope_theta > 0.0f), "rope_theta %g must be positive",
            static_cast<double>(d->rope_theta));
-  VR_CHECK(d->norm == VR_NORM_POST || d->norm == VR_NORM_PRE, "unknown norm placement %d", d->norm);
-  const bool prenorm = d->norm == VR_NORM_PRE;
+  VR_CHECK(d->norm == VR_NORM_POST || d->norm == VR_NORM_PRE || d->norm == VR_NORM_PRE_RMS, "unknown norm placement %d",
+           d->norm);
+  const bool prenorm = d->norm == VR_NORM_PRE, rms = d->norm == VR_NORM_PRE_RMS;
+  // (the T5 form: one combination, everything outside it refused by the field that leaves it)
+  VR_CHECK(!rms || d->position == VR_POS_NONE, "norm VR_NORM_PRE_RMS needs position VR_POS_NONE (position %d): RMSNorm "
+           "encoders with a position table or rotary positions are not implemented", d->position);
+  VR_CHECK(!rms || d->ffn == VR_FFN_RELU, "norm VR_NORM_PRE_RMS needs ffn VR_FFN_RELU (ffn %d): RMSNorm encoders with a GELU "
+           "or gated feed-forward block are not implemented", d->ffn);
+  VR_CHECK(!rms || d->window == 0, "norm VR_NORM_PRE_RMS takes no window (window %d): sliding-window attention needs "
+           "rotary positions", d->window);
+  VR_CHECK(!rms || d->type_vocab == 1, "norm VR_NORM_PRE_RMS needs type_vocab 1 (type_vocab %d)", d->type_vocab);
+  VR_CHECK(d->ffn != VR_FFN_RELU || rms, "ffn VR_FFN_RELU needs norm VR_NORM_PRE_RMS (norm %d): the ReLU feed-forward "
+           "block exists in the RMSNorm pre-norm loop only", d->norm);
   // (a model without positions: refusals of its own, ahead of the ones that tell a table model what pre-norm needs)
   VR_CHECK(d->position != VR_POS_NONE || !prenorm, "position VR_POS_NONE needs norm VR_NORM_POST (norm %d): pre-norm encoders "
            "without positions are not implemented", d->norm);
@@ -4159,7 +4340,9 @@ static int build_encoder(vr_engine* e, void** slot, const vr_bert_desc* d_in, co
     const int in_layer = i < 5 ? -1 : (i - 5) % per_layer;  // null is allowed for a projection's bias, and for the
     const bool bias = in_layer == 1 || in_layer == 3 || in_layer == 5 || in_layer == 7 || in_layer == 11 ||  // unused table
                       in_layer == 13 || in_layer == 17;
-    VR_CHECK(t[i] != nullptr || bias || (i == 1 && d->position != VR_POS_LEARNED), "tensor %d is null", i);
+    // (RMSNorm reads no shift, and its stream takes a missing token-type row as zeros)
+    const bool rms_unused = rms && (i == 2 || i == 4 || in_layer == 9 || in_layer == 15);
+    VR_CHECK(t[i] != nullptr || bias || rms_unused || (i == 1 && d->position != VR_POS_LEARNED), "tensor %d is null", i);
   }
   int window_stream_from = kWindowStreamFrom;  // (checked here: nothing is replaced when it is refused)
   if (const char* from = getenv("VR_WINDOW_STREAM_FROM")) {
@@ -4204,9 +4387,10 @@ static int build_encoder(vr_engine* e, void** slot, const vr_bert_desc* d_in, co
   // streamed kernel one per 128 queries. Which is faster was measured at 512 tokens;
   // VR_WINDOW_STREAM_FROM, read when the model is loaded, moves the length from which the streamed kernel runs.
   enc->window_stream_from = window_stream_from;
-  VR_TRY(dev_alloc_copy(e, enc, t[2], static_cast<size_t>(d->type_vocab) * H, mem, &enc->type));
+  if (rms) VR_TRY(dev_alloc_copy_or_zero(e, enc, t[2], H, mem, &enc->type));
+  else VR_TRY(dev_alloc_copy(e, enc, t[2], static_cast<size_t>(d->type_vocab) * H, mem, &enc->type));
   VR_TRY(dev_alloc_copy(e, enc, t[3], H, mem, &enc->lng));
-  VR_TRY(dev_alloc_copy(e, enc, t[4], H, mem, &enc->lnb));
+  if (!rms) VR_TRY(dev_alloc_copy(e, enc, t[4], H, mem, &enc->lnb));  // (RMSNorm: the shifts stay null, no kernel reads one)
   const hipMemcpyKind kind = mem == VR_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
   for (int l = 0; l < L; ++l) {
     // q_w q_b k_w k_b v_w v_b o_w o_b ln1_g ln1_b i_w i_b f_w f_b ln2_g ln2_b (gated: + gate_w gate_b, i_* = up)
@@ -4223,7 +4407,7 @@ static int build_encoder(vr_engine* e, void** slot, const vr_bert_desc* d_in, co
     VR_TRY(dev_alloc_copy(e, enc, w[6], HH, mem, &lw.wo));
     VR_TRY(dev_alloc_copy_or_zero(e, enc, w[7], H, mem, &lw.bo));
     VR_TRY(dev_alloc_copy(e, enc, w[8], H, mem, &lw.ln1g));
-    VR_TRY(dev_alloc_copy(e, enc, w[9], H, mem, &lw.ln1b));
+    if (!rms) VR_TRY(dev_alloc_copy(e, enc, w[9], H, mem, &lw.ln1b));
     if (gated) {
       const size_t IH = static_cast<size_t>(I) * H;
       VR_TRY(dev_alloc_copy(e, enc, nullptr, 2 * IH, mem, &lw.w1));
@@ -4242,7 +4426,7 @@ static int build_encoder(vr_engine* e, void** slot, const vr_bert_desc* d_in, co
     VR_TRY(dev_alloc_copy(e, enc, w[12], static_cast<size_t>(I) * H, mem, &lw.w2));
     VR_TRY(dev_alloc_copy_or_zero(e, enc, w[13], H, mem, &lw.b2));
     VR_TRY(dev_alloc_copy(e, enc, w[14], H, mem, &lw.ln2g));
-    VR_TRY(dev_alloc_copy(e, enc, w[15], H, mem, &lw.ln2b));
+    if (!rms) VR_TRY(dev_alloc_copy(e, enc, w[15], H, mem, &lw.ln2b));
     if (d->precision != VR_PRECISION_F32) {
       const bool plain = d->precision == VR_PRECISION_F16;
       VR_TRY(make_split(e, enc, lw.wqkv, 3 * HH, H, plain, &lw.s_qkv));
@@ -4268,7 +4452,7 @@ static int build_encoder(vr_engine* e, void** slot, const vr_bert_desc* d_in, co
         if (rotary) VR_TRY(reordered(lw.wqkv, lw.bqkv, 3 * H, 0, H, &lw.s_qkv_p, &lw.bqkv_p));
         if (gated) VR_TRY(reordered(lw.w1, lw.b1, 2 * I, 1, I, &lw.s_1_p, &lw.b1_p));
       }
-      if (plain && H % 64 == 0 && !prenorm) {  // operands of the folded-LayerNorm GEMMs (the post-norm loop's)
+      if (plain && H % 64 == 0 && !prenorm && !rms) {  // operands of the folded-LayerNorm GEMMs (the post-norm loop's)
         auto fold = [&](const float* w_dev, int N, const float* g, const float* b, const float* bias, SplitWeight* sw,
                         float** colsum, float** c) -> int {
           const size_t n = static_cast<size_t>(N) * H;
@@ -4320,7 +4504,8 @@ int encoder_set_attention_bias(vr_engine* e, const float* table, int heads, int 
   VR_CHECK(enc, "no encoder loaded");
   float* fresh = nullptr;
   if (table) {
-    VR_CHECK(enc->d.position == VR_POS_LEARNED && enc->d.norm == VR_NORM_POST,
+    VR_CHECK((enc->d.position == VR_POS_LEARNED && enc->d.norm == VR_NORM_POST) ||
+                 (enc->d.position == VR_POS_NONE && enc->d.norm == VR_NORM_PRE_RMS),  // (BERT / MPNet, or T5)
              "an attention bias needs position VR_POS_LEARNED and norm VR_NORM_POST (position %d, norm %d)", enc->d.position,
              enc->d.norm);
     VR_CHECK(heads == enc->d.heads, "bias table of %d heads for an encoder of %d", heads, enc->d.heads);
@@ -4481,6 +4666,8 @@ int reranker_load(vr_engine* e, const vr_bert_desc* d_in, const void* const* t, 
   const vr_bert_desc* d = &desc;
   // a pre-norm, rotary, gated description is a ModernBERT cross-encoder: its own head (6 tensors), CLS or mean pooling
   const bool modern = d->norm == VR_NORM_PRE && d->position == VR_POS_ROTARY && d->ffn != VR_FFN_GELU;
+  VR_CHECK(d->norm != VR_NORM_PRE_RMS, "a reranker with norm VR_NORM_PRE_RMS is not supported (norm %d): T5 cross-encoders "
+           "are not implemented", d->norm);
   if (!modern) {
     VR_CHECK(d->position == VR_POS_LEARNED && d->ffn == VR_FFN_GELU,
              "a reranker with rotary positions or a gated FFN is not supported (position %d, ffn %d): cross-encoders are "
@@ -4568,8 +4755,8 @@ static int launch_attention(vr_engine* e, Encoder* enc, const int32_t* cu_dev, i
   const int qblocks = (max_len + 63) / 64;
   const float scale = 1.0f / sqrtf(static_cast<float>(dh));
   // the kernels' WIN and BIAS flags: a launch without a window or a bias instantiates the code that never knew one
-  // (never both: vr_encoder_set_attention_bias / _slopes refuse the pre-norm descriptions, and only those have a
-  // window). BIAS: none, the table, or the slopes, which travel in the table's argument (the radius is unused then)
+  // (never both: vr_encoder_set_attention_bias / _slopes refuse VR_NORM_PRE, and only that norm has a window; the
+  // table of a VR_NORM_PRE_RMS model, T5's, meets none). BIAS: none, the table, or the slopes, which travel in the table's argument (the radius is unused then)
   const float* bias = enc->bias ? enc->bias : enc->slopes;
   const bool table = enc->bias != nullptr;
   const int radius = enc->bias_radius;
@@ -4844,6 +5031,102 @@ static int forward_chunk_prenorm(vr_engine* e, Encoder* enc, const int32_t* ids_
   return 0;
 }
 
+// The forward pass of an RMSNorm pre-norm model (VR_NORM_PRE_RMS: no positions, a ReLU FFN without a gate — the T5
+// encoder), forward_chunk's arguments:
+//   h = word[id];  per layer  h += W_o attn(N_a(h)),  h += W_down relu(W_up N_m(h));  out = N_f(h)
+// forward_chunk_prenorm's loop with three differences: the embedding launch leaves the RAW row in the stream and writes
+// N_a of layer 0 (the embeddings.LayerNorm slot) for the first projection; there is no rotation; and the FFN is one
+// product with the ReLU in its epilogue (EPI_BIAS_RELU) on whichever GEMM route the shape takes. Every N is RMSNorm — a
+// launch of its own, or for a question (<= 16 rows in f16 mode) folded into the projection that reads it
+// (launch_skinny_ln, rms). The relative-position table reaches the attention kernels through launch_attention as
+// MPNet's does; T5's missing 1/sqrt(d_h) is in the query weights (include/voitta_engine.h).
+static int forward_chunk_rms(vr_engine* e, Encoder* enc, const int32_t* ids_dev, const int32_t* cu_dev, int n_seq_total,
+                             int seq0, int seq1, int tok_base, int T, int max_len, double attn_flop, float* out_dev,
+                             const Spans* sp) {
+  const vr_bert_desc& d = enc->d;
+  const int H = d.hidden, I = d.intermediate;
+  hipStream_t s = e->stream;
+  const unsigned row_blocks = static_cast<unsigned>((T + 3) / 4);
+  const bool split = d.precision != VR_PRECISION_F32;
+  const bool plain = d.precision == VR_PRECISION_F16;
+  const int passes = plain ? 1 : 3;
+  // GEMM inputs as in forward_chunk_prenorm: the normalised rows in xs (f32 mode: in ctx), the context in ctx, the
+  // activation in ffn
+  half_t* xh = split ? reinterpret_cast<half_t*>(enc->xs) : nullptr;
+  half_t* xl = split && !plain ? xh + 8 : nullptr;
+  half_t* ch = split ? reinterpret_cast<half_t*>(enc->ctx) : nullptr;
+  half_t* cl = split && !plain ? ch + 8 : nullptr;
+  half_t* fh = split ? reinterpret_cast<half_t*>(enc->ffn) : nullptr;
+  half_t* fl = split && !plain ? fh + 8 : nullptr;
+  half_t* qkvh = reinterpret_cast<half_t*>(enc->qkv);
+  float2* stat = reinterpret_cast<float2*>(enc->lnstat);  // (launch_skinny_ln stores the rows' 1/rms; nobody reads them)
+  const bool fold_ln = plain && skinny_ln_supported(T, 3 * H, H) && I % 16 == 0;
+  // rows of h normalised by g -> the next product's input
+  auto norm_rows = [&](const float* h, const float* g) {
+    if (plain && H % 256 == 0)
+      hipLaunchKernelGGL(rmsnorm_f16_kernel, dim3(row_blocks), dim3(256), 0, s, h, T, H, g, d.eps, xh);
+    else
+      hipLaunchKernelGGL(rmsnorm_kernel, dim3(row_blocks), dim3(256), 0, s, h, T, H, g, d.eps, split ? nullptr : enc->ctx, xh, xl);
+  };
+  hipLaunchKernelGGL(embed_rms_kernel, dim3(row_blocks), dim3(256), 0, s, ids_dev, cu_dev, n_seq_total, tok_base, T, H, d.vocab,
+                     enc->word, enc->type, enc->lng, d.eps, split ? nullptr : enc->ctx, xh, xl, enc->x);
+  float* h = enc->x;      // the residual stream
+  float* other = enc->tmp;
+  const int n_seq = seq1 - seq0;
+  for (size_t li = 0; li < enc->layers.size(); ++li) {
+    const LayerWeights& w = enc->layers[li];
+    // Q, K, V of N_a(h); layer 0 reads the rows the embedding launch normalised
+    if (fold_ln && li > 0) {
+      VR_TRY(launch_skinny_ln(e, EPI_BIAS_F16, h, d.eps, stat,
+                              {.W = w.s_qkv, .bias = w.bqkv, .Ch = qkvh, .M = T, .N = 3 * H, .K = H, .ln_g = enc->layers[li - 1].ln2g},
+                              true));
+    } else {
+      if (li > 0) norm_rows(h, enc->layers[li - 1].ln2g);
+      if (plain)
+        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_F16, {.A = xh, .W = w.s_qkv, .bias = w.bqkv, .Ch = qkvh, .M = T, .N = 3 * H,
+                                                        .K = H, .passes = 1}));
+      else if (split)
+        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS, {.A = xh, .A_lo = xl, .W = w.s_qkv, .bias = w.bqkv, .C = enc->qkv, .M = T,
+                                                    .N = 3 * H, .K = H, .passes = passes}));
+      else
+        VR_TRY(launch_gemm(e, EPI_BIAS, enc->ctx, w.wqkv, w.bqkv, nullptr, enc->qkv, T, 3 * H, H));
+    }
+    VR_TRY(launch_attention(e, enc, cu_dev, seq0, n_seq, tok_base, max_len, false, 0, attn_flop));
+    // h' = h + W_o ctx
+    if (split)
+      VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_RESIDUAL, {.A = ch, .A_lo = cl, .W = w.s_o, .bias = w.bo, .R = h, .C = other, .M = T,
+                                                           .N = H, .K = H, .passes = passes}));
+    else
+      VR_TRY(launch_gemm(e, EPI_BIAS_RESIDUAL, enc->ctx, w.wo, w.bo, h, other, T, H, H));
+    std::swap(h, other);
+    // relu(W_up N_m(h))
+    if (fold_ln) {
+      VR_TRY(launch_skinny_ln(e, EPI_BIAS_RELU, h, d.eps, stat,
+                              {.W = w.s_1, .bias = w.b1, .Ch = fh, .M = T, .N = I, .K = H, .ln_g = w.ln1g}, true));
+    } else {
+      norm_rows(h, w.ln1g);
+      if (split)
+        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_RELU, {.A = xh, .A_lo = xl, .W = w.s_1, .bias = w.b1, .Ch = fh, .Cl = fl, .M = T,
+                                                         .N = I, .K = H, .passes = passes}));
+      else
+        VR_TRY(launch_gemm(e, EPI_BIAS_RELU, enc->ctx, w.w1, w.b1, nullptr, enc->ffn, T, I, H));
+    }
+    // h' = h + W_down act
+    if (split)
+      VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_RESIDUAL, {.A = fh, .A_lo = fl, .W = w.s_2, .bias = w.b2, .R = h, .C = other, .M = T,
+                                                           .N = H, .K = I, .passes = passes}));
+    else
+      VR_TRY(launch_gemm(e, EPI_BIAS_RESIDUAL, enc->ffn, w.w2, w.b2, h, other, T, H, I));
+    std::swap(h, other);
+  }
+  // the final norm writes the f32 rows pooling reads, into the buffer the stream is not in
+  hipLaunchKernelGGL(rmsnorm_kernel, dim3(row_blocks), dim3(256), 0, s, h, T, H, enc->layers.back().ln2g, d.eps, other,
+                     static_cast<half_t*>(nullptr), static_cast<half_t*>(nullptr));
+  launch_pool(e, enc, other, cu_dev, seq0, seq1, tok_base, 0, out_dev, sp);
+  VR_HIP(hipGetLastError());
+  return 0;
+}
+
 // forward of sequences [seq0, seq1) whose tokens are ids_dev[tok_base .. tok_base + T). sp (or null): pool the spans
 // of these sequences, one row each at out_dev[span], instead of one row per sequence — the pass then runs as a
 // mean-pooled model's does, whatever the description's pooling says.
@@ -4851,6 +5134,8 @@ static int forward_chunk(vr_engine* e, Encoder* enc, const int32_t* ids_dev, con
                          const int32_t* seg_dev, int n_seq_total, int seq0, int seq1, int tok_base, int T, int max_len,
                          double attn_flop, float* out_dev, const Spans* sp = nullptr) {
   const vr_bert_desc& d = enc->d;
+  if (d.norm == VR_NORM_PRE_RMS)  // the T5 form of the routine below
+    return forward_chunk_rms(e, enc, ids_dev, cu_dev, n_seq_total, seq0, seq1, tok_base, T, max_len, attn_flop, out_dev, sp);
   if (d.norm == VR_NORM_PRE)  // a routine of its own: none of the LayerNorm folds below applies to it
     return forward_chunk_prenorm(e, enc, ids_dev, cu_dev, n_seq_total, seq0, seq1, tok_base, T, max_len, attn_flop, out_dev, sp);
   const int H = d.hidden, I = d.intermediate, nh = d.heads, dh = H / nh;

@@ -378,7 +378,7 @@ void pieces(const vr_unigram& t, const char* s, size_t n, size_t cap, std::vecto
 
 void encode_one(const vr_unigram& t, const char* s, size_t n, int32_t max_len, std::vector<int32_t>* ids) {
   ids->clear();
-  ids->push_back(t.bos);
+  if (t.bos >= 0) ids->push_back(t.bos);  // (the template $A </s> of a T5 tokenizer has no <s>)
   const size_t budget = static_cast<size_t>(max_len) - 1;  // ids before </s>
   pieces(t, s, n, budget + 64, ids);  // (+64: a word may add several pieces; trimmed below)
   if (ids->size() > budget) ids->resize(budget);
@@ -402,7 +402,9 @@ int vr_unigram_create(const char* const* pieces_in, const double* scores, int32_
   VR_CHECK(n_added == 0 || (added && added_ids && added_flags), "bad added-token arguments");
   VR_CHECK(charsmap_len == 0 || charsmap, "null charsmap");
   auto valid_id = [&](int32_t i) { return i >= 0 && i < n_pieces; };
-  VR_CHECK(valid_id(unk_id) && valid_id(bos_id) && valid_id(eos_id), "unk / bos / eos id outside the %d pieces", n_pieces);
+  // bos_id -1: the template is $A </s> (T5), not <s> $A </s>
+  VR_CHECK(valid_id(unk_id) && (bos_id == -1 || valid_id(bos_id)) && valid_id(eos_id), "unk / bos / eos id outside the %d pieces",
+           n_pieces);
   VR_CHECK(pre_tokenizer == VR_UNIGRAM_PRE_METASPACE || pre_tokenizer == VR_UNIGRAM_PRE_WHITESPACE_METASPACE,
            "unknown pre-tokenizer %d", pre_tokenizer);
   VR_CHECK(prepend_scheme >= VR_PREPEND_ALWAYS && prepend_scheme <= VR_PREPEND_NEVER, "unknown prepend scheme %d",
@@ -496,6 +498,7 @@ int vr_unigram_encode_pairs(const vr_unigram* t, const char* const* a_texts, con
                             int64_t* out_offsets, int32_t* out_ids, int32_t* out_seg_b, int64_t capacity,
                             int64_t* needed) {
   VR_CHECK(t && n >= 0 && (n == 0 || (a_texts && a_lens && b_texts && b_lens)) && out_offsets && needed, "bad arguments");
+  VR_CHECK(t->bos >= 0, "this tokenizer's template is $A </s>: it has no pair template (<s> $A </s> </s> $B </s>)");
   VR_CHECK(max_len >= 4, "max_len %d cannot hold <s> and three </s>", max_len);
   for (int64_t i = 0; i < n; ++i)
     VR_CHECK(a_texts[i] && b_texts[i] && a_lens[i] >= 0 && b_lens[i] >= 0, "pair %lld: null text or negative length",

@@ -96,9 +96,11 @@ def _read_family_config(path: str, cfg: dict) -> dict:
         return _read_mpnet_config(path, cfg)
     if kind == "distilbert":
         return _read_distilbert_config(path, cfg)
+    if kind == "t5":
+        return _read_t5_config(path, cfg)
     if kind not in ("bert", "xlm-roberta"):
-        raise ValueError(f"unsupported model_type {kind}: BERT, DistilBERT, XLM-RoBERTa, MPNet, nomic_bert and modernbert "
-                         "encoders only")
+        raise ValueError(f"unsupported model_type {kind}: BERT, DistilBERT, XLM-RoBERTa, MPNet, T5, nomic_bert and "
+                         "modernbert encoders only")
     if kind == "bert" and cfg.get("position_embedding_type", "absolute") == "alibi":
         return _read_alibi_config(path, cfg)
     if cfg.get("hidden_act", "gelu") != "gelu" or cfg.get("position_embedding_type", "absolute") != "absolute":
@@ -239,6 +241,49 @@ def _read_distilbert_config(path: str, cfg: dict) -> dict:
                          pooling=pooling, normalize=normalize, eps=1e-12,
                          precision=os.environ.get("VOITTA_ENCODER_PRECISION", "f16"))
     return {"desc": desc, "max_seq": max_seq, "pos_start": 0, "config": cfg}
+
+
+def _read_t5_config(path: str, cfg: dict) -> dict:
+    """model_type t5 (sentence-transformers' gtr-t5-base / -large, sentence-t5-base / -large: the encoder half of T5
+    v1.0): pre-norm blocks with RMSNorm (T5LayerNorm), a ReLU FFN without biases, no position in the embeddings and
+    block 0's bucketed relative-position bias in every layer's attention (encoder.t5_slots / t5_bias_table). There is
+    no position table, so the longest sequence is min(max_seq_length, seq_cap()): VOITTA_MAX_SEQ_LENGTH alone bounds it.
+    T5 v1.1 / flan (feed_forward_proj gated-gelu) is refused: its gate is the tanh-approximate GELU."""
+    ffn = cfg.get("feed_forward_proj", "relu")
+    if ffn == "gated-gelu":
+        raise ValueError("feed_forward_proj 'gated-gelu' (T5 v1.1, flan-t5) is not implemented: its gate is the "
+                         "tanh-approximate GELU; the ReLU FFN of T5 v1.0 (gtr-t5, sentence-t5) is")
+    if ffn != "relu":
+        raise ValueError(f"feed_forward_proj {ffn!r} is not implemented: a t5 encoder's FFN is wo(relu(wi(x)))")
+    H, heads, dkv = int(cfg["d_model"]), int(cfg["num_heads"]), int(cfg["d_kv"])
+    if heads * dkv != H:
+        raise ValueError(f"num_heads * d_kv = {heads} * {dkv} != d_model = {H} is not implemented: the attention's inner "
+                         "width must be the model's")
+    if dkv not in (32, 64):
+        raise ValueError(f"d_kv {dkv} is not implemented: the attention kernels run head sizes 32 and 64")
+    buckets = int(cfg.get("relative_attention_num_buckets", 32))
+    max_distance = int(cfg.get("relative_attention_max_distance", 128))
+    if buckets % 2 or buckets < 4:
+        raise ValueError(f"relative_attention_num_buckets {buckets} is not implemented: the buckets are split in two "
+                         "halves by the sign of the offset")
+    if not 1 <= max_distance <= 512:
+        raise ValueError(f"relative_attention_max_distance {max_distance} > 512 is not implemented: the engine's bias "
+                         "table has a radius of at most 512")
+    cap = seq_cap()
+    pooling, normalize, max_seq = _read_modules(path, int(cfg.get("n_positions", 512)))
+    if max_seq > cap:
+        logger.warning("%s declares sequences of up to %d tokens; the engine runs at most %d: longer texts are "
+                       "truncated to %d tokens (%s raises the cap, up to %d)", path, max_seq, cap, cap, SEQ_CAP_VARIABLE,
+                       MAX_SEQ_LENGTH_LIMIT)
+        max_seq = cap
+    desc = _enc.BertDesc(layers=int(cfg["num_layers"]), hidden=H, heads=heads, intermediate=int(cfg["d_ff"]),
+                         vocab=int(cfg["vocab_size"]), max_pos=max_seq,  # no table: the longest accepted sequence
+                         type_vocab=1, pooling=pooling, normalize=normalize,
+                         eps=float(cfg.get("layer_norm_epsilon", 1e-6)),
+                         precision=os.environ.get("VOITTA_ENCODER_PRECISION", "f16"), position="none", ffn="relu",
+                         norm="rms_pre")
+    return {"desc": desc, "max_seq": max_seq, "pos_start": 0, "config": cfg, "buckets": buckets,
+            "max_distance": max_distance}
 
 
 def _read_mpnet_config(path: str, cfg: dict) -> dict:
@@ -439,6 +484,11 @@ class NativeSentenceEncoder:
         widths read from it here (empty results, deferred embeddings, the one-call text paths) follow."""
         return self.engine.encoder_desc
 
+    @property
+    def leading_specials(self) -> int:
+        """The specials in front of a tokenised text: 1 (<s>, [CLS]) — 0 for a T5 tokenizer, whose template is $A </s>."""
+        return 0 if getattr(self.tokenizer, "bos_id", 0) == -1 else 1
+
     # ---- loading ---------------------------------------------------------------------------------
     @classmethod
     def from_pretrained(cls, path: str, engine=None) -> "NativeSentenceEncoder":
@@ -451,6 +501,15 @@ class NativeSentenceEncoder:
             state, rc["desc"].attention_bias = _enc.mpnet_slots(cls._load_weights(path), rc["desc"], rc["pos_start"])
         elif rc["config"].get("model_type") == "distilbert":
             state = _enc.distilbert_slots(cls._load_weights(path), rc["desc"])
+        elif rc["config"].get("model_type") == "t5":
+            state = cls._load_weights(path)
+            if not any(k.endswith("encoder.block.0.layer.0.SelfAttention.q.weight") for k in state):
+                raise ValueError(f"{path}: model_type t5 (is_encoder_decoder {rc['config'].get('is_encoder_decoder')}) "
+                                 "without encoder weights (encoder.block.*): only the encoder half is run")
+            # (load_encoder's t5_slots maps the weights; the table needs the config's bucket count and distance)
+            rc["desc"].attention_bias = _enc.t5_bias_table(
+                _enc._find(state, "encoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight"),
+                rc["buckets"], rc["max_distance"])
         else:
             state = slice_positions(cls._load_weights(path), rc["pos_start"])
         return cls(engine or get_engine(), rc["desc"], state, cls._load_tokenizer(path, rc["config"]), rc["max_seq"])
@@ -474,11 +533,11 @@ class NativeSentenceEncoder:
         """The native WordPiece (csrc/wordpiece.cpp) for plain BERT tokenizers (an MPNet model's among them: the same
         pipeline wrapped in <s> ... </s>, the names read from tokenizer.json's post_processor), the native Unigram
         (csrc/unigram.cpp)
-        for the XLM-R pipeline of an XLM-R model, the native byte-level BPE (csrc/bpe.cpp) for a ModernBERT model's
-        pipeline; anything else that a tokenizer.json may describe (a BERT model with a Unigram tokenizer.json among
+        for the XLM-R pipeline of an XLM-R model and the same pipeline with the template $A </s> of a T5 model, the
+        native byte-level BPE (csrc/bpe.cpp) for a ModernBERT model's pipeline; anything else that a tokenizer.json may describe (a BERT model with a Unigram tokenizer.json among
         them, as before) goes through the HF `tokenizers` library."""
         tj = os.path.join(path, "tokenizer.json")
-        if os.path.exists(tj) and cfg.get("model_type") == "xlm-roberta":
+        if os.path.exists(tj) and cfg.get("model_type") in ("xlm-roberta", "t5"):
             spec = json.load(open(tj, encoding="utf-8"))
             if (spec.get("model") or {}).get("type") == "Unigram":
                 if is_unigram_pipeline(spec):
@@ -554,9 +613,10 @@ class NativeSentenceEncoder:
         """The late-chunking plan (late_chunking.plan_many) of [(document, chunk_texts), ...] for this model: windows of
         max_seq_length tokens, VOITTA_LATE_CHUNKING_CONTEXT tokens of left context, ``prefix`` (the passage prefix) as
         ids in front of every window. A document that cannot be late-chunked goes the plain way inside the plan."""
+        lead = self.leading_specials
         return _late.plan_many(documents, self.tokenize, self.max_seq_length, get_settings().late_chunking_context,
-                               _late.prefix_ids_of(prefix, self.tokenize), plain_text=lambda t: prefix + t,
-                               pooling=self.desc.pooling)
+                               _late.prefix_ids_of(prefix, self.tokenize, lead), plain_text=lambda t: prefix + t,
+                               pooling=self.desc.pooling, lead=lead)
 
     def encode_documents(self, documents, prefix: str = ""):
         """[(document, chunk_texts), ...] -> (total chunks, D): every chunk embedded in the context of its document,

@@ -7,7 +7,7 @@ Replaces the ``SentenceTransformer(model_name, device)`` object the reference la
 from __future__ import annotations
 
 import ctypes as C
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 
 import numpy as np
 
@@ -91,12 +91,16 @@ class BertDesc:
     # embeddings or in Q and K: max_pos = the longest sequence; ALiBi models, whose position is in attention_slopes)
     position: str = "learned"
     rope_theta: float = 0.0
-    ffn: str = "gelu"  # "gelu" | "swiglu" | "geglu" (down(act(gate(x)) * up(x)), act = SiLU / exact GELU)
-    norm: str = "post"  # "post" (x = LN(x + f(x))) | "pre" (x = x + f(LN(x)), a final LayerNorm: the ModernBERT family)
+    # "gelu" | "swiglu" | "geglu" (down(act(gate(x)) * up(x)), act = SiLU / exact GELU) | "relu" (down(relu(up(x))): T5)
+    ffn: str = "gelu"
+    # "post" (x = LN(x + f(x))) | "pre" (x = x + f(LN(x)), a final LayerNorm: the ModernBERT family) | "rms_pre" (the
+    # same with RMSNorm and no embedding norm in the stream: the T5 encoders; needs position "none" and ffn "relu")
+    norm: str = "post"
     window: int = 0  # sliding-window attention: query i of a windowed layer sees key j iff |i - j| <= window; 0 = none
     global_every: int = 0  # window > 0: layer l attends globally iff l % global_every == 0
     rope_theta_local: float = 0.0  # the rotary base of the windowed layers; 0 = rope_theta
-    # additive attention bias by relative offset, f32 [heads, 2 * radius + 1] (MPNet: mpnet_bias_table); not a field of
+    # additive attention bias by relative offset, f32 [heads, 2 * radius + 1] (MPNet: mpnet_bias_table, T5:
+    # t5_bias_table); not a field of
     # vr_bert_desc: load_encoder hands it to vr_encoder_set_attention_bias once the model is loaded
     attention_bias: object = field(default=None, compare=False, repr=False)
     # linear attention bias, f32 [heads]: the logit of head h loses attention_slopes[h] * |key - query| (ALiBi:
@@ -122,11 +126,15 @@ class BertDesc:
 
     @property
     def gated(self) -> bool:
-        return self.ffn != "gelu"
+        return self.ffn in ("swiglu", "geglu")
 
     @property
     def prenorm(self) -> bool:
         return self.norm == "pre"
+
+    @property
+    def rms(self) -> bool:
+        return self.norm == "rms_pre"
 
     def to_c(self) -> _lib.VrBertDesc:
         d = _lib.VrBertDesc()
@@ -141,13 +149,13 @@ class BertDesc:
             raise ValueError(f"unknown encoder precision {self.precision!r}")
         d.precision = codes[self.precision]
         positions = {"learned": _lib.VR_POS_LEARNED, "rotary": _lib.VR_POS_ROTARY, "none": _lib.VR_POS_NONE}
-        ffns = {"gelu": _lib.VR_FFN_GELU, "swiglu": _lib.VR_FFN_SWIGLU, "geglu": _lib.VR_FFN_GEGLU}
+        ffns = {"gelu": _lib.VR_FFN_GELU, "swiglu": _lib.VR_FFN_SWIGLU, "geglu": _lib.VR_FFN_GEGLU, "relu": _lib.VR_FFN_RELU}
         if self.position not in positions:
             raise ValueError(f"unknown position scheme {self.position!r}")
         if self.ffn not in ffns:
             raise ValueError(f"unknown ffn kind {self.ffn!r}")
         d.position, d.rope_theta, d.ffn = positions[self.position], float(self.rope_theta), ffns[self.ffn]
-        norms = {"post": _lib.VR_NORM_POST, "pre": _lib.VR_NORM_PRE}
+        norms = {"post": _lib.VR_NORM_POST, "pre": _lib.VR_NORM_PRE, "rms_pre": _lib.VR_NORM_PRE_RMS}
         if self.norm not in norms:
             raise ValueError(f"unknown norm placement {self.norm!r}")
         d.norm, d.window, d.global_every = norms[self.norm], int(self.window), int(self.global_every)
@@ -335,6 +343,77 @@ def mpnet_slots(state: dict, desc: "BertDesc", pos_start: int = 2):
     return out, mpnet_bias_table(get("encoder.relative_attention_bias.weight"))
 
 
+def t5_bias_table(weight, num_buckets: int = 32, max_distance: int = 128) -> np.ndarray:
+    """encoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight [num_buckets, heads] -> float32
+    [heads, 2 * max_distance + 1], the table vr_encoder_set_attention_bias takes: entry [h, d + max_distance] is the bias
+    of key - query = d. T5's bidirectional _relative_position_bucket is MPNet's function (MPNet took it from T5), its
+    logarithm in f32 as the library's; the buckets are constant from |d| = max_distance on, so that radius reproduces
+    compute_bias at every length."""
+    import torch
+
+    if hasattr(weight, "detach"):
+        weight = weight.detach().cpu().numpy()
+    w = torch.from_numpy(np.array(weight, dtype=np.float32))
+    if w.ndim != 2 or w.shape[0] != num_buckets or num_buckets % 2:
+        raise ValueError(f"relative_attention_bias.weight of shape {tuple(w.shape)}: expected [relative_attention_num_buckets "
+                         f"= {num_buckets} (even), heads]")
+    if not 1 <= max_distance <= 512:
+        raise ValueError(f"relative_attention_max_distance {max_distance}: the engine's bias table has a radius of 1..512")
+    rel = torch.arange(-max_distance, max_distance + 1, dtype=torch.long)
+    bucket = mpnet_relative_position_bucket(rel, num_buckets=num_buckets, max_distance=max_distance)
+    return np.ascontiguousarray(w[bucket].T.numpy(), dtype=np.float32)
+
+
+def t5_slots(state: dict, desc: "BertDesc", num_buckets: int = 32, max_distance: int = 128, table: bool = True):
+    """A transformers T5EncoderModel (or T5Model / T5ForConditionalGeneration: its encoder half) state dict, any key
+    prefix -> (slot names, state under those names, bias table). The 16-slot layout under BERT's names with every bias,
+    the position table and the token types absent (NULL). Under VR_NORM_PRE_RMS embeddings.LayerNorm holds block 0's
+    attention norm, layer l's attention.output.LayerNorm its layer.1.layer_norm (in front of the FFN) and its
+    output.LayerNorm block l + 1's layer.0.layer_norm, final_layer_norm for the last. T5's logits carry no
+    1/sqrt(d_kv); the engine's do, so q.weight is multiplied by sqrt(d_kv) in f32 here (exactly x8 at d_kv = 64, one
+    rounding per weight at 32). The table is t5_bias_table of block 0's relative_attention_bias (table=False: None, for
+    a caller that has it already)."""
+
+    def get(*names):
+        hits = [k for k in state for name in names if k == name or k.endswith("." + name)]
+        if names[0] == "shared.weight":  # (the tied embedding may be present under both names)
+            hits = hits[:1]
+        if len(hits) != 1:
+            raise KeyError(f"weight '{names[0]}' not found (or ambiguous) in state dict: {hits[:3]}")
+        t = state[hits[0]]
+        return t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
+
+    if not any(k == "encoder.block.0.layer.0.SelfAttention.q.weight" or k.endswith(".encoder.block.0.layer.0.SelfAttention.q.weight")
+               for k in state):
+        raise KeyError("weight 'encoder.block.0.layer.0.SelfAttention.q.weight' not found: the state dict holds no T5 "
+                       "encoder weights")
+    L, dkv = desc.layers, desc.hidden // desc.heads
+    scale = np.sqrt(np.float32(dkv))
+    out = {"embeddings.word_embeddings.weight": get("shared.weight", "encoder.embed_tokens.weight"),
+           "embeddings.LayerNorm.weight": get("encoder.block.0.layer.0.layer_norm.weight")}
+    names = ["embeddings.word_embeddings.weight", None, None, "embeddings.LayerNorm.weight", None]
+    for i in range(L):
+        src, dst = f"encoder.block.{i}.", f"encoder.layer.{i}."
+        nxt = f"encoder.block.{i + 1}.layer.0.layer_norm.weight" if i + 1 < L else "encoder.final_layer_norm.weight"
+        q = np.asarray(get(src + "layer.0.SelfAttention.q.weight"), np.float32)
+        layer = [("attention.self.query.weight", (q * scale).astype(np.float32)),
+                 ("attention.self.key.weight", get(src + "layer.0.SelfAttention.k.weight")),
+                 ("attention.self.value.weight", get(src + "layer.0.SelfAttention.v.weight")),
+                 ("attention.output.dense.weight", get(src + "layer.0.SelfAttention.o.weight")),
+                 ("attention.output.LayerNorm.weight", get(src + "layer.1.layer_norm.weight")),
+                 ("intermediate.dense.weight", get(src + "layer.1.DenseReluDense.wi.weight")),
+                 ("output.dense.weight", get(src + "layer.1.DenseReluDense.wo.weight")),
+                 ("output.LayerNorm.weight", get(nxt))]
+        for name, t in layer:
+            out[dst + name] = t
+            names += [dst + name, None]
+    bias = None
+    if table:
+        bias = t5_bias_table(get("encoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight"), num_buckets,
+                             max_distance)
+    return names, out, bias
+
+
 def distilbert_slots(state: dict, desc: "BertDesc") -> dict:
     """A transformers DistilBertModel state dict (with or without the `distilbert.` prefix) -> the state under the BERT
     names of tensor_names(). DistilBERT is BERT's post-LayerNorm body without token types: the token-type slot is a zero
@@ -509,6 +588,10 @@ def load_encoder(engine, desc: BertDesc, state: dict) -> None:
     (jina_slots), a GELU one a BERT state dict without its position table."""
     if desc.prenorm:
         names, state = modernbert_slots(state, desc)
+    elif desc.rms:  # (a T5 state dict; the description's attention_bias, else the checkpoint's table with T5's defaults)
+        names, state, table = t5_slots(state, desc, table=desc.attention_bias is None)
+        if table is not None:
+            desc = replace(desc, attention_bias=table)
     elif desc.position == "none":
         if desc.gated:
             names, state = jina_slots(state, desc)

@@ -21,7 +21,7 @@ each carry left context) and every chunk's vector is the mean of the final hidde
    L - context gets the left context that still fits; one that alone exceeds L is truncated at the window's end and
    flagged;
 4. each window becomes bos, prefix_ids, the window's tokens, eos; spans are shifted by 1 + len(prefix_ids), so they
-   never cover specials or the prefix.
+   never cover specials or the prefix. (A tokenizer without a bos — T5's "$A </s>" — is planned with lead=0: no bos.)
 
 ``tokenize(texts)`` is the model's: a list of strings -> packed (ids, offsets) WITH the two specials around every
 text, as ``NativeSentenceEncoder.tokenize`` returns them; bos and eos are read off its output."""
@@ -68,28 +68,31 @@ def locate(document: str, chunk_texts) -> list | None:
     return out
 
 
-def strip_specials(ids, off):
-    """Packed (ids, offsets) with specials -> the list of id arrays without them, and (bos, eos) (None without texts)."""
+def strip_specials(ids, off, lead: int = 1):
+    """Packed (ids, offsets) with specials -> the list of id arrays without them, and (bos, eos) (None without texts).
+    lead: the number of specials in front of a text, 1 — or 0 for a tokenizer whose template is "$A </s>" (T5), whose
+    bos is then None."""
     ids, off = np.asarray(ids), np.asarray(off)
-    pieces = [ids[int(off[i]) + 1: int(off[i + 1]) - 1] for i in range(off.shape[0] - 1)]
-    specials = (int(ids[0]), int(ids[int(off[1]) - 1])) if off.shape[0] > 1 else None
+    pieces = [ids[int(off[i]) + lead: int(off[i + 1]) - 1] for i in range(off.shape[0] - 1)]
+    specials = (int(ids[0]) if lead else None, int(ids[int(off[1]) - 1])) if off.shape[0] > 1 else None
     return pieces, specials
 
 
-def prefix_ids_of(prefix: str, tokenize) -> tuple:
+def prefix_ids_of(prefix: str, tokenize, lead: int = 1) -> tuple:
     """The ids of a passage prefix ('passage: ', VOITTA_EMBED_PASSAGE_PREFIX), tokenised once without specials."""
     if not prefix.strip():
         return ()
-    pieces, _ = strip_specials(*tokenize([prefix]))
+    pieces, _ = strip_specials(*tokenize([prefix]), lead)
     return tuple(int(t) for t in pieces[0])
 
 
-def plan(document: str, chunk_texts, tokenize, max_tokens: int, context: int, prefix_ids=()) -> Plan | None:
+def plan(document: str, chunk_texts, tokenize, max_tokens: int, context: int, prefix_ids=(), lead: int = 1) -> Plan | None:
+    """lead: the specials in front of a text (strip_specials): 1, or 0 for a tokenizer without a bos."""
     chunk_texts = list(chunk_texts)
     prefix = [int(t) for t in prefix_ids]
-    L = int(max_tokens) - 2 - len(prefix)
+    L = int(max_tokens) - (lead + 1) - len(prefix)
     if L < 1:
-        raise ValueError(f"max_tokens={max_tokens} leaves no room for text beside 2 specials and {len(prefix)} prefix ids")
+        raise ValueError(f"max_tokens={max_tokens} leaves no room for text beside {lead + 1} specials and {len(prefix)} prefix ids")
     if context < 0:
         raise ValueError(f"context={context} must not be negative")
     where = locate(document, chunk_texts)
@@ -102,7 +105,7 @@ def plan(document: str, chunk_texts, tokenize, max_tokens: int, context: int, pr
     live = [k for k, s in enumerate(segments) if s.strip()]
     if not live:
         return None
-    pieces, specials = strip_specials(*tokenize([segments[k] for k in live]))
+    pieces, specials = strip_specials(*tokenize([segments[k] for k in live]), lead)
     bos, eos = specials
     tok_at = np.zeros(len(cuts), np.int64)  # first token of the segment that starts at cuts[k]
     counts = np.zeros(len(segments), np.int64)
@@ -134,11 +137,11 @@ def plan(document: str, chunk_texts, tokenize, max_tokens: int, context: int, pr
                 we = max(we, min(N, ws + L))  # the document's trailing tokens, as far as the window holds them
             windows.append((ws, we, j, k))
             j = k
-    shift = 1 + len(prefix)
+    shift = lead + len(prefix)
     ids, offsets, span_off = [], [0], [0]
     span_tok = np.zeros((n, 2), np.int32)
     truncated = np.zeros(n, bool)
-    head, tail = np.asarray([bos] + prefix, np.int32), np.asarray([eos], np.int32)
+    head, tail = np.asarray(([bos] if lead else []) + prefix, np.int32), np.asarray([eos], np.int32)
     for ws, we, j, k in windows:
         ids += [head, tokens[ws:we], tail]
         offsets.append(offsets[-1] + shift + (we - ws) + 1)
@@ -180,7 +183,7 @@ def concat(plans) -> Plan:
 
 
 def plan_many(documents, tokenize, max_tokens: int, context: int, prefix_ids=(), plain_text=None,
-              pooling: str = "mean") -> Plan:
+              pooling: str = "mean", lead: int = 1) -> Plan:
     """``plan`` for a list of (document, chunk_texts), concatenated with chunk order kept across documents. A document
     whose plan is None goes the plain way inside the same result (``plain_plan`` of ``plain_text(chunk)``, the chunk as
     the plain route hands it to the tokenizer); ``late`` says which. Documents without chunks contribute nothing."""
@@ -189,7 +192,7 @@ def plan_many(documents, tokenize, max_tokens: int, context: int, prefix_ids=(),
         chunk_texts = list(chunk_texts)
         if not chunk_texts:
             continue
-        p = plan(document, chunk_texts, tokenize, max_tokens, context, prefix_ids)
+        p = plan(document, chunk_texts, tokenize, max_tokens, context, prefix_ids, lead)
         if p is None:
             p = plain_plan([plain_text(t) if plain_text else t for t in chunk_texts], tokenize, pooling)
         plans.append(p)

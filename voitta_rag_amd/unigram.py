@@ -47,7 +47,8 @@ def parse_tokenizer_json(spec: dict) -> dict:
     """The create arguments of vr_unigram_create from a parsed tokenizer.json, or ValueError for a pipeline outside
     the XLM-R shape: Unigram (no byte fallback); normalizer null, Precompiled, or Sequence[Precompiled,
     Replace(" {2,}", " ")]; pre-tokenizer Metaspace or Sequence[WhitespaceSplit, Metaspace]; TemplateProcessing
-    "<s> $A </s>" / "<s> $A </s> </s> $B </s>" or RobertaProcessing; added tokens with normalized=false."""
+    "<s> $A </s>" / "<s> $A </s> </s> $B </s>", "$A </s>" (T5: bos_id -1) or RobertaProcessing; added tokens with
+    normalized=false."""
     model = spec.get("model") or {}
     if model.get("type") != "Unigram":
         raise ValueError(f"tokenizer model {model.get('type')} is not Unigram")
@@ -95,10 +96,16 @@ def parse_tokenizer_json(spec: dict) -> dict:
             return out
 
         single, pair = shape(post["single"]), shape(post.get("pair") or [])
-        if len(single) != 3 or single[1] != "$A" or pair != [single[0], "$A", single[2], single[2], "$B", single[2]]:
-            raise ValueError(f"post-processor template {single} / {pair} is not <s> $A </s> / <s> $A </s> </s> $B </s>")
-        bos = _special_id(post.get("special_tokens") or {}, single[0])
-        eos = _special_id(post.get("special_tokens") or {}, single[2])
+        if len(single) == 2 and single[0] == "$A" and not single[1].startswith("$"):
+            # T5: $A </s> (its pair template, $A </s> $B </s>, is not implemented: encode_pairs is refused). bos -1 = none
+            bos = -1
+            eos = _special_id(post.get("special_tokens") or {}, single[1])
+        elif len(single) != 3 or single[1] != "$A" or pair != [single[0], "$A", single[2], single[2], "$B", single[2]]:
+            raise ValueError(f"post-processor template {single} / {pair} is not <s> $A </s> / <s> $A </s> </s> $B </s> "
+                             "(or $A </s>)")
+        else:
+            bos = _special_id(post.get("special_tokens") or {}, single[0])
+            eos = _special_id(post.get("special_tokens") or {}, single[2])
     else:
         raise ValueError(f"post-processor {post.get('type')} is not TemplateProcessing or RobertaProcessing")
     # ---- added tokens
@@ -112,7 +119,7 @@ def parse_tokenizer_json(spec: dict) -> dict:
                            | (VR_ADDED_SINGLE_WORD if at.get("single_word") else 0))
     n = len(pieces)
     for name, i in (("unk", model["unk_id"]), ("bos", bos), ("eos", eos)):
-        if not 0 <= int(i) < n:
+        if not 0 <= int(i) < n and not (name == "bos" and i == -1):
             raise ValueError(f"{name} id {i} outside the {n} pieces")
     return dict(pieces=pieces, scores=scores, unk_id=int(model["unk_id"]), bos_id=bos, eos_id=eos, charsmap=charsmap,
                 replace_spaces=replace, pre_tokenizer=pre, prepend_scheme=prepend, added=added, added_ids=added_ids,
@@ -133,6 +140,7 @@ class UnigramTokenizer:
                  added: list[str] = (), added_ids: list[int] = (), added_flags: list[int] = (), max_length: int = 512):
         self._lib = load_library()
         self.vocab_size = len(pieces)
+        self.bos_id = int(bos_id)  # -1: the template is $A </s>
         self.max_length = int(max_length)
         raw = [p.encode("utf-8") for p in pieces]
         arr = (C.c_char_p * len(raw))(*raw)
@@ -173,7 +181,7 @@ class UnigramTokenizer:
         return cls.from_tokenizer_json(json.load(open(tj, encoding="utf-8")), max_length)
 
     def encode_batch(self, texts: list[str]) -> tuple[np.ndarray, np.ndarray]:
-        """-> (ids int32[total], offsets int64[n + 1]); every sequence is <s> ... </s>."""
+        """-> (ids int32[total], offsets int64[n + 1]); every sequence is <s> ... </s> (a T5 tokenizer: ... </s>)."""
         n = len(texts)
         raw = [t.encode("utf-8", "replace") for t in texts]
         arr = (C.c_char_p * max(n, 1))(*raw)
@@ -193,6 +201,8 @@ class UnigramTokenizer:
         """Cross-encoder input: sequence i is <s> a_i </s> </s> b_i </s>, truncated LongestFirst to max_length ids.
         -> (ids int32[total], offsets int64[n + 1], seg_b int32[n]: the position of each sequence's first id of b_i)."""
         n = len(a_texts)
+        if self.bos_id < 0:
+            raise ValueError("encode_pairs on a tokenizer whose template is $A </s> (T5): it has no pair template here")
         if len(b_texts) != n:
             raise ValueError(f"{n} first texts, {len(b_texts)} second texts")
         ra = [t.encode("utf-8", "replace") for t in a_texts]
