@@ -115,6 +115,9 @@ int  vr_set_stream(vr_engine* e, void* stream);
 /* ---- dense encode: replaces SentenceTransformer(...).encode (embedding.py:40,53,68-73,85) ----- */
 #define VR_POOL_MEAN 0
 #define VR_POOL_CLS  1
+/* the final hidden row of the sequence's LAST token (decoder-style embedders: under a causal mask the only row that has
+ * seen the whole sequence). Any encoder accepts it; a reranker does not; span calls ignore it as they ignore CLS. */
+#define VR_POOL_LAST 2
 
 /* BERT-family encoder description; values come from the checkpoint's config.json /
  * sentence-transformers modules.json (SURVEY.md §8 model table). */
@@ -129,7 +132,7 @@ typedef struct vr_bert_desc {
                           * the cos/sin table the engine builds, which is again the longest accepted sequence.
                           * VR_POS_NONE: there is no table, the longest accepted sequence alone. 1 .. 8192 */
   int32_t type_vocab;
-  int32_t pooling;       /* VR_POOL_MEAN | VR_POOL_CLS (sentence-transformers Pooling module) */
+  int32_t pooling;       /* VR_POOL_MEAN | VR_POOL_CLS | VR_POOL_LAST (sentence-transformers Pooling module) */
   int32_t normalize;     /* 1 = L2-normalise (sentence-transformers Normalize module) */
   float   eps;           /* layer_norm_eps */
   int32_t precision;     /* VR_PRECISION_F32 | VR_PRECISION_F16X3 | VR_PRECISION_F16 */
@@ -140,12 +143,21 @@ typedef struct vr_bert_desc {
   int32_t ffn;           /* VR_FFN_GELU | VR_FFN_SWIGLU | VR_FFN_GEGLU | VR_FFN_RELU */
   /* Added with the pre-norm family (ModernBERT): again zero in every field is the behaviour of a description that
    * ends at `ffn`, and struct_size may be that shorter size. */
-  int32_t norm;          /* VR_NORM_POST | VR_NORM_PRE | VR_NORM_PRE_RMS */
+  int32_t norm;          /* VR_NORM_POST | VR_NORM_PRE | VR_NORM_PRE_RMS | VR_NORM_PRE_RMS_ROTARY */
   int32_t window;        /* sliding-window attention: the half-width w, 0 .. 4096. 0: every layer attends globally.
                           * Otherwise query i of a windowed layer sees key j of its own sequence iff |i - j| <= w */
   int32_t global_every;  /* window > 0: layer l attends globally iff l % global_every == 0 (>= 1), the rest are windowed */
   float   rope_theta_local; /* the rotary base of the windowed layers; 0 = rope_theta */
 } vr_bert_desc;
+
+/* vr_bert_desc and what was added behind it with the decoder-style embedders (Qwen2). vr_bert_desc itself keeps its
+ * size and its fields; this is the same description one field longer, and vr_encoder_load / vr_reranker_load take either:
+ * pass &v2.base with base.struct_size = sizeof(vr_bert_desc_v2). A vr_bert_desc of any accepted size reads `causal` as 0. */
+typedef struct vr_bert_desc_v2 {
+  vr_bert_desc base;
+  int32_t causal;        /* 0: every query sees every key of its own sequence. 1: query i sees key j of its own sequence
+                          * iff j <= i. VR_NORM_PRE_RMS_ROTARY only: every other norm refuses 1, and so does a reranker */
+} vr_bert_desc_v2;
 
 /* position: LEARNED adds a row of the position table to every token's embedding; ROTARY has no table — the query and
  * key of every head are rotated by the token's position inside its own sequence (rotate-half pairing: feature j with
@@ -171,10 +183,16 @@ typedef struct vr_bert_desc {
  * mean subtraction, no shift; the slot's bias is ignored and may be NULL). PRE_RMS needs VR_POS_NONE, VR_FFN_RELU,
  * window 0 and type_vocab 1 (anything else is refused with the field named); a reranker never takes it.
  * T5's logits are q.k + bias WITHOUT the 1/sqrt(d_h): the engine keeps its scale, and the loader multiplies the query
- * weight by sqrt(d_h) instead (exactly x8 at head size 64, one f32 rounding per weight at 32). */
+ * weight by sqrt(d_h) instead (exactly x8 at head size 64, one f32 rounding per weight at 32).
+ * PRE_RMS_ROTARY is the Llama / Qwen2 block: h = word[id]; per layer h += W_o attn(rope(N_a(h))), then
+ * h += W_down(act(gate(N_m(h))) * up(N_m(h))); out = N_f(h), every N an RMSNorm as under PRE_RMS. It needs
+ * VR_POS_ROTARY, a gated ffn, window 0 and type_vocab 1 (anything else is refused with the field named), takes
+ * vr_bert_desc_v2.causal 0 or 1, refuses vr_encoder_set_attention_bias and _slopes, and a reranker never takes it. PRE_RMS itself
+ * stays the T5 form alone. */
 #define VR_NORM_POST 0
 #define VR_NORM_PRE  1
 #define VR_NORM_PRE_RMS 2
+#define VR_NORM_PRE_RMS_ROTARY 3
 
 /* arithmetic of the encoder's matrix products:
  *   F32    every product on the f32-input MFMA (exact f32 fma chains) — 157 TFLOP/s peak
@@ -204,8 +222,12 @@ typedef struct vr_bert_desc {
  * VR_NORM_PRE_RMS: the slots as under VR_NORM_PRE with one difference: embeddings.LayerNorm holds block 0's attention
  * norm (T5: block.0.layer.0.layer_norm) and the stream bypasses it too. Layer l's attention.output.LayerNorm =
  * block.l.layer.1.layer_norm, layer l's output.LayerNorm = block.l+1.layer.0.layer_norm, the last = final_layer_norm.
+ * VR_NORM_PRE_RMS_ROTARY: the same slots, 18 per layer (the ffn is gated): embeddings.LayerNorm = layers.0.input_layernorm,
+ * layer l's attention.output.LayerNorm = layers.l.post_attention_layernorm, layer l's output.LayerNorm =
+ * layers.l+1.input_layernorm, the last = norm. Grouped-query checkpoints are brought to `heads` full K and V heads by
+ * the loader (HF repeat_kv): the engine sees [Q | K | V] rows of 3 H.
  * NULL slots: any bias (read as zeros), and position_embeddings when position is VR_POS_ROTARY or VR_POS_NONE (ignored
- * then); under VR_NORM_PRE_RMS also every LayerNorm bias (ignored) and token_type_embeddings (read as zeros).
+ * then); under VR_NORM_PRE_RMS and VR_NORM_PRE_RMS_ROTARY also every LayerNorm bias (ignored) and token_type_embeddings (read as zeros).
  * Every other slot must be non-NULL.
  * The engine copies (and re-packs) them; the caller's tensors may be freed afterwards.
  * Replaces EmbeddingService.model's lazy SentenceTransformer(...) load (embedding.py:23-42). */

@@ -68,6 +68,11 @@ class VrBertDesc(C.Structure):
     ]
 
 
+class VrBertDescV2(VrBertDesc):
+    """vr_bert_desc_v2: vr_bert_desc (the base class's fields, at their offsets) and `causal` behind it."""
+    _fields_ = [("causal", C.c_int32)]
+
+
 class VrHeadStage(C.Structure):
     _fields_ = [
         ("struct_size", C.c_int32),
@@ -98,8 +103,10 @@ VR_FFN_RELU = 3
 VR_NORM_POST = 0
 VR_NORM_PRE = 1
 VR_NORM_PRE_RMS = 2
+VR_NORM_PRE_RMS_ROTARY = 3
 VR_POOL_MEAN = 0
 VR_POOL_CLS = 1
+VR_POOL_LAST = 2
 VR_MEM_HOST = 0
 VR_MEM_DEVICE = 1
 VR_TS_ABSENT = -(2**63)

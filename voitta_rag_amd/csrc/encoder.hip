@@ -14,7 +14,7 @@
 //   attention_kernel  softmax(Q K^T / sqrt(d)) V per (sequence, head) MFMA (v_mfma_f32_16x16x4_f32),
 //                     online softmax, keys streamed through LDS 64 at a time
 //   layernorm_kernel  LayerNorm over H                               HBM bound
-//   pool_kernel       mean / CLS pooling + L2 normalise              HBM bound
+//   pool_kernel       mean / CLS / last-token pooling + L2 normalise HBM bound
 //   rerank_head_kernel cross-encoder head on the pooled [CLS] rows   one f32 logit per pair (encoder_rerank)
 //   rerank_head_ln_kernel the head of a pre-norm cross-encoder: dense, GELU, LayerNorm, classifier (encoder_rerank)
 //   embed_head_kernel the embedder's post-pooling head: Dense / LayerNorm stages, normalise, truncate (vr_encoder_set_head)
@@ -24,6 +24,8 @@
 //                     model (VR_NORM_PRE_RMS, the T5 encoder: forward_chunk_rms); its ReLU FFN is EPI_BIAS_RELU of the GEMMs.
 //                     T5's logits carry no 1/sqrt(d_h): launch_attention keeps its scale, the loader folds sqrt(d_h) into
 //                     the query weights (include/voitta_engine.h)
+//                     The same kernels serve VR_NORM_PRE_RMS_ROTARY (the Qwen2 block: forward_chunk_rms_rotary), with rope_kernel,
+//                     glu_kernel and the causal state of the three attention kernels (kMaskCausal)
 // Algorithmic FLOP per token = L * (24 H^2 + 4 S H), of which the GEMMs are
 // 24 H^2 L: the dominant kernel of the indexing path.
 
@@ -105,6 +107,7 @@ struct Encoder {
   HeadParams head{};
   int out_dim = 0;
   DevArray<float> pooled;
+  int causal = 0;               // vr_bert_desc_v2.causal: 1 = the attention kernels' causal state (VR_NORM_PRE_RMS_ROTARY only)
   int window_stream_from = 0;   // windowed layers: sequences from this length on take attention_stream_kernel (build_encoder)
   float* posidx = nullptr;  // rotary: int32 position of every token inside its own sequence (positions_kernel)
   bool fuse = true;         // rotate / gate inside the skinny epilogues; VR_ENCODE_FUSE=0 at load time: separate passes
@@ -580,7 +583,7 @@ __global__ __launch_bounds__(256) void rmsnorm_f16_kernel(const float* __restric
     }
 }
 
-// one block per sequence: mean (sum / max(count, 1e-9)) or CLS pooling, then x / max(|x|, 1e-12) over all H columns.
+// one block per sequence: mean (sum / max(count, 1e-9)), CLS or last-token pooling, then x / max(|x|, 1e-12) over all H columns.
 // The leading ocols columns are stored, in rows of ostride floats (H and H without a head; a truncating head stores
 // fewer, and what it stores are the bits it would have stored in full).
 __global__ __launch_bounds__(256) void pool_kernel(const float* __restrict__ x,
@@ -601,6 +604,8 @@ __global__ __launch_bounds__(256) void pool_kernel(const float* __restrict__ x,
     if (c < H && len > 0) {
       if (pooling == 1) {
         v = x[static_cast<int64_t>(t0) * H + c];
+      } else if (pooling == 2) {  // VR_POOL_LAST: the sequence's last token (never compact: that is the CLS tail's)
+        v = x[static_cast<int64_t>(t0 + len - 1) * H + c];
       } else {
         float acc = 0.0f;
         for (int t = 0; t < len; ++t) acc += x[static_cast<int64_t>(t0 + t) * H + c];
@@ -3311,12 +3316,25 @@ __global__ __launch_bounds__(NW * 64) void gemm_f16_skinny_ln_rope_kernel(
   gemm_f16_skinny_ln_body<EPI_ROPE_F16, STEPS, NW>(pre, ln_g, ln_b, eps, stat_out, W, M, N, K, unscale, bias, Ch, rope_tab, rope_pos);
 }
 
+// ... and its RMSNorm state (VR_NORM_PRE_RMS_ROTARY: the Q/K/V projection of a question to a Qwen2-style model)
+template <int STEPS, int NW>
+__global__ __launch_bounds__(NW * 64) void gemm_f16_skinny_rms_rope_kernel(
+    const float* __restrict__ pre, const float* __restrict__ ln_g, float eps, float2* __restrict__ stat_out,
+    const half_t* __restrict__ W, int M, int N, int K, float unscale, const float* __restrict__ bias,
+    half_t* __restrict__ Ch, const float2* __restrict__ rope_tab, const int32_t* __restrict__ rope_pos) {
+  gemm_f16_skinny_ln_body<EPI_ROPE_F16, STEPS, NW, true>(pre, ln_g, nullptr, eps, stat_out, W, M, N, K, unscale, bias, Ch, rope_tab,
+                                                        rope_pos);
+}
+
 // K = hidden size H: 8 waves x 3 steps (768), 8 x 4 (1024), 4 x 3 (384); anything else keeps the LayerNorm launch
 static bool skinny_ln_supported(int M, int N, int K) { return M <= 16 && N % 16 == 0 && (K == 768 || K == 1024 || K == 384); }
+// forward_chunk_rms_rotary's: also 4 waves x 7 steps (896, the Qwen2-0.5B body). A test of its own, so that the routes
+// of the families that came before do not move.
+static bool skinny_rms_rotary_supported(int M, int N, int K) { return skinny_ln_supported(M, N, K) || (M <= 16 && N % 16 == 0 && K == 896); }
 
 // `pre`: the pre-LayerNorm f32 rows, `stat_out`: where block 0 stores their statistics; of `g`: W, bias, Ch, M, N, K,
 // ln_g / ln_b (the folded LayerNorm's gain and shift) and, for EPI_ROPE_F16, rope_tab / rope_pos
-// rms: the folded norm is RMSNorm by ln_g (EPI_BIAS_F16 and EPI_BIAS_RELU only)
+// rms: the folded norm is RMSNorm by ln_g (EPI_BIAS_F16, EPI_BIAS_RELU, EPI_ROPE_F16 and the two gates)
 static int launch_skinny_ln(vr_engine* e, int epi, const float* pre, float eps, float2* stat_out, const GemmArgs& g,
                             bool rms = false) {
   hipStream_t s = e->stream;
@@ -3325,14 +3343,19 @@ static int launch_skinny_ln(vr_engine* e, int epi, const float* pre, float eps, 
   auto rms_launch = [&](auto E) {
     auto launch = [&](auto ST, auto NWV) {
       constexpr int kE = decltype(E)::value, kSteps = decltype(ST)::value, kWaves = decltype(NWV)::value;
-      hipLaunchKernelGGL((gemm_f16_skinny_rms_kernel<kE, kSteps, kWaves>), grid, dim3(kWaves * 64), 0, s, pre, g.ln_g, eps,
-                         stat_out, g.W.hi, g.M, g.N, g.K, g.W.unscale, g.bias, g.Ch);
+      if constexpr (kE == EPI_ROPE_F16)  // (a kernel of its own: two arguments more)
+        hipLaunchKernelGGL((gemm_f16_skinny_rms_rope_kernel<kSteps, kWaves>), grid, dim3(kWaves * 64), 0, s, pre, g.ln_g, eps,
+                           stat_out, g.W.hi, g.M, g.N, g.K, g.W.unscale, g.bias, g.Ch, g.rope_tab, g.rope_pos);
+      else
+        hipLaunchKernelGGL((gemm_f16_skinny_rms_kernel<kE, kSteps, kWaves>), grid, dim3(kWaves * 64), 0, s, pre, g.ln_g, eps,
+                           stat_out, g.W.hi, g.M, g.N, g.K, g.W.unscale, g.bias, g.Ch);
     };
     if (g.K == 768) launch(std::integral_constant<int, 3>{}, std::integral_constant<int, 8>{});
     else if (g.K == 1024) launch(std::integral_constant<int, 4>{}, std::integral_constant<int, 8>{});
+    else if (g.K == 896) launch(std::integral_constant<int, 7>{}, std::integral_constant<int, 4>{});
     else launch(std::integral_constant<int, 3>{}, std::integral_constant<int, 4>{});
   };
-  const bool known = rms ? with_epi<EPI_BIAS_F16, EPI_BIAS_RELU>(epi, rms_launch) :
+  const bool known = rms ? with_epi<EPI_BIAS_F16, EPI_BIAS_RELU, EPI_ROPE_F16, EPI_SWIGLU_F16, EPI_GEGLU_F16>(epi, rms_launch) :
                      with_epi<EPI_BIAS_F16, EPI_BIAS_GELU, EPI_ROPE_F16, EPI_SWIGLU_F16, EPI_GEGLU_F16>(epi, [&](auto E) {
     auto launch = [&](auto ST, auto NWV) {
       constexpr int kE = decltype(E)::value, kSteps = decltype(ST)::value, kWaves = decltype(NWV)::value;
@@ -3463,6 +3486,9 @@ struct WindowMask {
   __device__ __forceinline__ WindowMask(int q, int window)
       : lo(window > 0 ? q - window : 0), span(window > 0 ? 2u * static_cast<unsigned>(window) : 0xffffffffu) {}
   __device__ __forceinline__ bool sees(int key) const { return static_cast<unsigned>(key - lo) <= span; }
+  // the causal mask (kMaskCausal below) is the same compare: lo = 0, span = q is key <= q
+  struct Causal {};
+  __device__ __forceinline__ WindowMask(int q, Causal) : lo(0), span(static_cast<unsigned>(q)) {}
 };
 // With a window a query can meet a 64-key tile none of whose keys it sees — and that can be the FIRST tile it meets (the
 // last queries of a block against the block's first key tile; query tiles are skipped per wave where the whole tile lies
@@ -3534,6 +3560,18 @@ __device__ __forceinline__ void bias_tile(f32x4 (&st)[4], float scale2, const Bi
 // 2^-24 of a bias whose logit weighs 2^-bias: far below what the f16 rounding of P leaves. Applied ahead of the
 // key-validity mask and the running maximum, for padded queries and in the CLS tail alike, exactly where the table is.
 constexpr int kBiasNone = 0, kBiasTable = 1, kBiasSlopes = 2;
+// A causal mask (vr_bert_desc_v2.causal, VR_NORM_PRE_RMS_ROTARY only: the decoder-style embedders): query i sees key j of
+// its own sequence iff j <= i — an additive bias of 0 or -inf by relative offset, and the fourth state of BIAS_KIND. It
+// meets neither a window nor a table nor slopes (build_encoder and the two setters refuse them under that norm), so
+// <WIN = false, BIAS_KIND = kMaskCausal> is one more instantiation of each kernel, and the other states keep their names
+// and their code. The mask is WindowMask's compare (lo = 0, span = q) beside the key-validity test. What it buys is the
+// key loop's end: a 64-key tile that starts behind a query tile's (a block's) last query is never visited — half the
+// tiles of a long sequence. The loop bounds are block-uniform where a barrier sits inside the loop (attention_kernel,
+// attention_stream_kernel) and wave-uniform elsewhere. Every tile a query DOES meet starts at or before it (tiles start
+// at multiples of 64, query tiles at multiples of 16, a streamed wave's pair of tiles at a multiple of 32, and the loops
+// end at the tile that holds the diagonal), so it sees the tile's first key and its maximum is finite; the
+// softmax_base guard is kept all the same, it costs one compare per tile and query.
+constexpr int kMaskCausal = 3;
 __device__ __forceinline__ void slope_tile(f32x4 (&st)[4], float scale2, float slope2, int kt, int g, int q) {
   const float d0 = slope2 * static_cast<float>(kt + 4 * g - q);
 #pragma unroll
@@ -3555,7 +3593,7 @@ __global__ __launch_bounds__(256) void attention_kernel(const float* __restrict_
                                                         float* __restrict__ ctx, half_t* __restrict__ ctx_hi,
                                                         half_t* __restrict__ ctx_lo, int window_arg,
                                                         const float* __restrict__ bias_table, int bias_radius) {
-  constexpr bool BIAS = BIAS_KIND == kBiasTable, SLOPES = BIAS_KIND == kBiasSlopes;
+  constexpr bool BIAS = BIAS_KIND == kBiasTable, SLOPES = BIAS_KIND == kBiasSlopes, CAUSAL = BIAS_KIND == kMaskCausal;
   static_assert(!(WIN && BIAS_KIND != kBiasNone), "a window needs pre-norm, a bias post-norm");
   const int window = WIN ? window_arg : 0;
   constexpr int LDK = DH + 4;
@@ -3596,9 +3634,14 @@ __global__ __launch_bounds__(256) void attention_kernel(const float* __restrict_
   for (int s = 0; s < NS; ++s) o[s] = f32x4{0.f, 0.f, 0.f, 0.f};
   float m = -__builtin_inff();
   float l = 0.0f;
-  const WindowMask wm(q_tok, window);
+  const WindowMask wm = [&] {
+    if constexpr (CAUSAL) return WindowMask(q_tok, WindowMask::Causal{});
+    else return WindowMask(q_tok, window);
+  }();
 
-  for (int kt = 0; kt < len; kt += 64) {
+  // CAUSAL: the tiles up to the one that holds the block's 64 queries (block-uniform: barriers inside)
+  const int kt_end = CAUSAL ? min(len, qb * 64 + 64) : len;
+  for (int kt = 0; kt < kt_end; kt += 64) {
     __syncthreads();
     for (int idx = tid; idx < 64 * (DH / 4); idx += 256) {
       const int key = idx / (DH / 4), c4 = idx % (DH / 4);
@@ -3647,7 +3690,7 @@ __global__ __launch_bounds__(256) void attention_kernel(const float* __restrict_
     mx = fmaxf(mx, __shfl_xor(mx, 16));
     mx = fmaxf(mx, __shfl_xor(mx, 32));
     const float m_raw = fmaxf(m, mx);  // (no window: finite, key kt < len is always valid)
-    const float m_new = WIN ? softmax_base(m_raw) : m_raw;  // what the exponentials subtract; the maximum kept is m_raw
+    const float m_new = WIN || CAUSAL ? softmax_base(m_raw) : m_raw;  // what the exponentials subtract; the maximum kept is m_raw
     const float alpha = expf(m - m_new);
     float psum = 0.0f;
 #pragma unroll
@@ -3727,7 +3770,7 @@ __global__ __launch_bounds__(NW * 64) void attention_seq_kernel(const half_t* __
                                                             int seq0, int tok_base, int H, float scale, int q_limit,
                                                             int lds_keys, half_t* __restrict__ ctx_h, int window_arg,
                                                             const float* __restrict__ bias_table, int bias_radius) {
-  constexpr bool BIAS = BIAS_KIND == kBiasTable, SLOPES = BIAS_KIND == kBiasSlopes;
+  constexpr bool BIAS = BIAS_KIND == kBiasTable, SLOPES = BIAS_KIND == kBiasSlopes, CAUSAL = BIAS_KIND == kMaskCausal;
   static_assert(!(WIN && BIAS_KIND != kBiasNone), "a window needs pre-norm, a bias post-norm");
   const int window = WIN ? window_arg : 0;
   constexpr int LDK = DH;       // halfs per staged row: unpadded, 16-byte chunks XOR-swizzled by the row instead
@@ -3818,12 +3861,16 @@ __global__ __launch_bounds__(NW * 64) void attention_seq_kernel(const half_t* __
     float m = -__builtin_inff();
     float l = 0.0f;
     // a window: only the 64-key tiles that hold a key some query of this tile sees (wave-uniform bounds)
+    // (CAUSAL: the tiles up to the one that holds this query tile, and inside it the 16-key groups up to the tile's own)
     const int kt0 = window > 0 ? max(0, qt * 16 - window) & ~63 : 0;
-    const int kt1 = window > 0 ? min(keys_pad, qt * 16 + 16 + window) : keys_pad;
-    const WindowMask wm(q_tok, window);
+    const int kt1 = CAUSAL ? min(keys_pad, qt * 16 + 16) : window > 0 ? min(keys_pad, qt * 16 + 16 + window) : keys_pad;
+    const WindowMask wm = [&] {
+      if constexpr (CAUSAL) return WindowMask(q_tok, WindowMask::Causal{});
+      else return WindowMask(q_tok, window);
+    }();
     const BiasRow br(sB, q_tok, BIAS ? bias_radius : 0);
     for (int kt = kt0; kt < kt1; kt += 64) {
-      const int nt = min(4, (keys_pad - kt) >> 4);  // 16-key groups in this tile (block-uniform)
+      const int nt = min(4, ((CAUSAL ? kt1 : keys_pad) - kt) >> 4);  // 16-key groups in this tile (block-uniform; CAUSAL: wave-uniform)
       f32x4 st[4];
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
@@ -3842,7 +3889,8 @@ __global__ __launch_bounds__(NW * 64) void attention_seq_kernel(const half_t* __
       if constexpr (SLOPES) slope_tile(st, scale2, slope2, kt, g, q_tok);
       const float sc = BIAS || SLOPES ? 1.0f : scale2;
       // every key of the tile exists and every query of the tile sees all of them: no masks
-      if (kt + 64 <= len && (window <= 0 || (kt + 63 - qt * 16 <= window && qt * 16 + 15 - kt <= window))) {
+      if (kt + 64 <= len && (!CAUSAL || kt + 63 <= qt * 16) &&
+          (window <= 0 || (kt + 63 - qt * 16 <= window && qt * 16 + 15 - kt <= window))) {
 #pragma unroll
         for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -3864,7 +3912,7 @@ __global__ __launch_bounds__(NW * 64) void attention_seq_kernel(const half_t* __
       mx = fmaxf(mx, __shfl_xor(mx, 16));
       mx = fmaxf(mx, __shfl_xor(mx, 32));
       const float m_raw = fmaxf(m, mx);  // (no window: finite, key kt < len is always valid)
-      const float m_new = WIN ? softmax_base(m_raw) : m_raw;  // what the exponentials subtract; the maximum kept is m_raw
+      const float m_new = WIN || CAUSAL ? softmax_base(m_raw) : m_raw;  // what the exponentials subtract; the maximum kept is m_raw
       const float alpha = __builtin_amdgcn_exp2f(m - m_new);
       float psum = 0.0f;
       f16x8 pb[2];  // pb[u][j]: key kt + 32 u + 16 (j >> 2) + 4 g + (j & 3)
@@ -3935,7 +3983,7 @@ __global__ __launch_bounds__(NW * 64) void attention_stream_kernel(const half_t*
                                                                int seq0, int tok_base, int H, int qblocks, float scale,
                                                                int q_limit, half_t* __restrict__ ctx_h, int window_arg,
                                                                const float* __restrict__ bias_table, int bias_radius) {
-  constexpr bool BIAS = BIAS_KIND == kBiasTable, SLOPES = BIAS_KIND == kBiasSlopes;
+  constexpr bool BIAS = BIAS_KIND == kBiasTable, SLOPES = BIAS_KIND == kBiasSlopes, CAUSAL = BIAS_KIND == kMaskCausal;
   static_assert(!(WIN && BIAS_KIND != kBiasNone), "a window needs pre-norm, a bias post-norm");
   const int window = WIN ? window_arg : 0;
   static_assert(NW == 4 && (DH == 64 || DH == 32), "one 16-byte piece of a 64-key tile per thread and CH / NW rounds");
@@ -4002,7 +4050,8 @@ __global__ __launch_bounds__(NW * 64) void attention_stream_kernel(const half_t*
   // a window: the block's 128 queries see keys q0 - w .. q0 + 127 + w only, so the key loop runs over the tiles that
   // hold those — 128 + 2 w keys and a tile's rounding, whatever the sequence's length (block-uniform bounds)
   const int kt0 = window > 0 ? max(0, q0 - window) & ~63 : 0;
-  const int kt1 = window > 0 ? min(len, q0 + NW * 32 + window) : len;
+  // (CAUSAL: the tiles up to the one that holds the block's last query, block-uniform as well)
+  const int kt1 = CAUSAL ? min(len, q0 + NW * 32) : window > 0 ? min(len, q0 + NW * 32 + window) : len;
   {
     uint4 kr[NLD], vr[NLD];
     request(kt0, kr, vr);
@@ -4029,7 +4078,8 @@ __global__ __launch_bounds__(NW * 64) void attention_stream_kernel(const half_t*
     for (int s = 0; s < NS; ++s) o[i][s] = f32x4{0.f, 0.f, 0.f, 0.f};
   float m[2] = {-__builtin_inff(), -__builtin_inff()};
   float l[2] = {0.0f, 0.0f};
-  const WindowMask wm[2] = {WindowMask(qw + qi, window), WindowMask(qw + 16 + qi, window)};
+  const WindowMask wm[2] = {CAUSAL ? WindowMask(qw + qi, WindowMask::Causal{}) : WindowMask(qw + qi, window),
+                            CAUSAL ? WindowMask(qw + 16 + qi, WindowMask::Causal{}) : WindowMask(qw + 16 + qi, window)};
   const BiasRow br[2] = {BiasRow(sB, qw + qi, BIAS ? bias_radius : 0), BiasRow(sB, qw + 16 + qi, BIAS ? bias_radius : 0)};
   int buf = 0;
   for (int kt = kt0; kt < kt1; kt += 64, buf ^= 1) {
@@ -4037,7 +4087,8 @@ __global__ __launch_bounds__(NW * 64) void attention_stream_kernel(const half_t*
     uint4 kr[NLD], vr[NLD];
     if (more) request(kt + 64, kr, vr);
     // a tile none of the wave's 32 queries sees is skipped (wave-uniform; the wave still stages and takes the barrier)
-    if (active && (window <= 0 || (kt <= qw + 31 + window && kt + 63 >= qw - window))) {
+    // (CAUSAL: a tile behind the wave's last query likewise)
+    if (active && (!CAUSAL || kt <= qw + 31) && (window <= 0 || (kt <= qw + 31 + window && kt + 63 >= qw - window))) {
       const half_t* sK = att_tiles + 2 * buf * TILE;
       const half_t* sV = sK + TILE;
       f32x4 st[2][4];
@@ -4061,7 +4112,8 @@ __global__ __launch_bounds__(NW * 64) void attention_stream_kernel(const half_t*
         if constexpr (SLOPES) slope_tile(st[i], scale2, slope2, kt, g, qt0 + qi);
         const float sc = BIAS || SLOPES ? 1.0f : scale2;
         // every key of the tile exists and every query of the tile sees all of them: no masks
-        if (kt + 64 <= len && (window <= 0 || (kt + 63 - qt0 <= window && qt0 + 15 - kt <= window))) {
+        if (kt + 64 <= len && (!CAUSAL || kt + 63 <= qt0) &&
+            (window <= 0 || (kt + 63 - qt0 <= window && qt0 + 15 - kt <= window))) {
 #pragma unroll
           for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -4083,7 +4135,7 @@ __global__ __launch_bounds__(NW * 64) void attention_stream_kernel(const half_t*
         mx = fmaxf(mx, __shfl_xor(mx, 16));
         mx = fmaxf(mx, __shfl_xor(mx, 32));
         const float m_raw = fmaxf(m[i], mx);  // (no window: finite, key kt < len is always valid)
-        const float m_new = WIN ? softmax_base(m_raw) : m_raw;  // what the exponentials subtract; the maximum kept is m_raw
+        const float m_new = WIN || CAUSAL ? softmax_base(m_raw) : m_raw;  // what the exponentials subtract; the maximum kept is m_raw
         const float alpha = __builtin_amdgcn_exp2f(m[i] - m_new);
         float psum = 0.0f;
 #pragma unroll
@@ -4259,14 +4311,17 @@ int encoder_hidden(vr_engine* e) {
 
 // The caller's description, zero-extended: a caller compiled against the header that ended at `precision` passes that
 // shorter struct_size, and gets what it always got (learned positions, the plain GELU FFN).
-static int read_desc(const vr_bert_desc* src, vr_bert_desc* out) {
+// (vr_bert_desc_v2: the same description one field longer, `causal`; every shorter size reads it as 0)
+static int read_desc(const vr_bert_desc* src, vr_bert_desc* out, int32_t* causal = nullptr) {
   const int32_t short_size = static_cast<int32_t>(offsetof(vr_bert_desc, position));
   const int32_t post_size = static_cast<int32_t>(offsetof(vr_bert_desc, norm));  // ... or at `ffn`: post-norm, no window
+  const bool v2 = src->struct_size == static_cast<int32_t>(sizeof(vr_bert_desc_v2));
   VR_CHECK(src->struct_size == static_cast<int32_t>(sizeof(vr_bert_desc)) || src->struct_size == short_size ||
-               src->struct_size == post_size,
+               src->struct_size == post_size || v2,
            "vr_bert_desc size mismatch");
   *out = vr_bert_desc{};
-  memcpy(out, src, static_cast<size_t>(src->struct_size));
+  memcpy(out, src, v2 ? sizeof(vr_bert_desc) : static_cast<size_t>(src->struct_size));
+  if (causal) *causal = v2 ? reinterpret_cast<const vr_bert_desc_v2*>(src)->causal : 0;
   out->struct_size = static_cast<int32_t>(sizeof(vr_bert_desc));
   return 0;
 }
@@ -4285,7 +4340,8 @@ static const int kWindowStreamFrom = 384;
 // a model from its 5 + 16 L (gated FFN: 5 + 18 L) tensors (vr_encoder_load's order) into *slot, replacing what is there
 static int build_encoder(vr_engine* e, void** slot, const vr_bert_desc* d_in, const void* const* t, int n_tensors, int mem) {
   vr_bert_desc desc;
-  VR_TRY(read_desc(d_in, &desc));
+  int32_t causal = 0;
+  VR_TRY(read_desc(d_in, &desc, &causal));
   const vr_bert_desc* d = &desc;
   const int H = d->hidden, I = d->intermediate, L = d->layers;
   VR_CHECK(d->position == VR_POS_LEARNED || d->position == VR_POS_ROTARY || d->position == VR_POS_NONE,
@@ -4296,9 +4352,18 @@ static int build_encoder(vr_engine* e, void** slot, const vr_bert_desc* d_in, co
   const int per_layer = gated ? 18 : 16;
   VR_CHECK(!rotary || (std::isfinite(d->rope_theta) && d->rope_theta > 0.0f), "rope_theta %g must be positive",
            static_cast<double>(d->rope_theta));
-  VR_CHECK(d->norm == VR_NORM_POST || d->norm == VR_NORM_PRE || d->norm == VR_NORM_PRE_RMS, "unknown norm placement %d",
-           d->norm);
-  const bool prenorm = d->norm == VR_NORM_PRE, rms = d->norm == VR_NORM_PRE_RMS;
+  VR_CHECK(d->norm == VR_NORM_POST || d->norm == VR_NORM_PRE || d->norm == VR_NORM_PRE_RMS || d->norm == VR_NORM_PRE_RMS_ROTARY,
+           "unknown norm placement %d", d->norm);
+  const bool prenorm = d->norm == VR_NORM_PRE, rms = d->norm == VR_NORM_PRE_RMS, rms_rot = d->norm == VR_NORM_PRE_RMS_ROTARY;
+  // (the Qwen2 form: one combination as well, and the only norm that takes the causal mask)
+  VR_CHECK(!rms_rot || rotary, "norm VR_NORM_PRE_RMS_ROTARY needs position VR_POS_ROTARY (position %d)", d->position);
+  VR_CHECK(!rms_rot || gated, "norm VR_NORM_PRE_RMS_ROTARY needs a gated ffn (ffn %d): VR_FFN_SWIGLU or VR_FFN_GEGLU", d->ffn);
+  VR_CHECK(!rms_rot || d->window == 0, "norm VR_NORM_PRE_RMS_ROTARY takes no window (window %d): a causal sliding window is "
+           "not implemented", d->window);
+  VR_CHECK(!rms_rot || d->type_vocab == 1, "norm VR_NORM_PRE_RMS_ROTARY needs type_vocab 1 (type_vocab %d)", d->type_vocab);
+  VR_CHECK(causal == 0 || causal == 1, "causal %d must be 0 or 1", causal);
+  VR_CHECK(causal == 0 || rms_rot, "causal %d needs norm VR_NORM_PRE_RMS_ROTARY (norm %d): the causal mask exists in that "
+           "loop only", causal, d->norm);
   // (the T5 form: one combination, everything outside it refused by the field that leaves it)
   VR_CHECK(!rms || d->position == VR_POS_NONE, "norm VR_NORM_PRE_RMS needs position VR_POS_NONE (position %d): RMSNorm "
            "encoders with a position table or rotary positions are not implemented", d->position);
@@ -4333,7 +4398,8 @@ static int build_encoder(vr_engine* e, void** slot, const vr_bert_desc* d_in, co
   VR_CHECK(d->heads >= 1 && H % d->heads == 0 && (H / d->heads == 32 || H / d->heads == 64),
            "head size %d unsupported (32 or 64)", d->heads ? H / d->heads : 0);
   VR_CHECK(n_tensors == 5 + per_layer * L, "expected %d tensors, got %d", 5 + per_layer * L, n_tensors);
-  VR_CHECK(d->pooling == 0 || d->pooling == 1, "pooling must be 0 (mean) or 1 (cls)");
+  VR_CHECK(d->pooling == VR_POOL_MEAN || d->pooling == VR_POOL_CLS || d->pooling == VR_POOL_LAST,
+           "pooling %d must be 0 (mean), 1 (cls) or 2 (last token)", d->pooling);
   VR_CHECK(d->precision == VR_PRECISION_F32 || d->precision == VR_PRECISION_F16X3 || d->precision == VR_PRECISION_F16,
            "unknown precision %d", d->precision);
   for (int i = 0; i < n_tensors; ++i) {
@@ -4341,7 +4407,7 @@ static int build_encoder(vr_engine* e, void** slot, const vr_bert_desc* d_in, co
     const bool bias = in_layer == 1 || in_layer == 3 || in_layer == 5 || in_layer == 7 || in_layer == 11 ||  // unused table
                       in_layer == 13 || in_layer == 17;
     // (RMSNorm reads no shift, and its stream takes a missing token-type row as zeros)
-    const bool rms_unused = rms && (i == 2 || i == 4 || in_layer == 9 || in_layer == 15);
+    const bool rms_unused = (rms || rms_rot) && (i == 2 || i == 4 || in_layer == 9 || in_layer == 15);
     VR_CHECK(t[i] != nullptr || bias || rms_unused || (i == 1 && d->position != VR_POS_LEARNED), "tensor %d is null", i);
   }
   int window_stream_from = kWindowStreamFrom;  // (checked here: nothing is replaced when it is refused)
@@ -4356,6 +4422,7 @@ static int build_encoder(vr_engine* e, void** slot, const vr_bert_desc* d_in, co
   Encoder* enc = new Encoder();
   *slot = enc;
   enc->d = *d;
+  enc->causal = causal;
   enc->fuse = !(getenv("VR_ENCODE_FUSE") && atoi(getenv("VR_ENCODE_FUSE")) == 0);
   const size_t HH = static_cast<size_t>(H) * H;
   VR_TRY(dev_alloc_copy(e, enc, t[0], static_cast<size_t>(d->vocab) * H, mem, &enc->word));
@@ -4387,10 +4454,10 @@ static int build_encoder(vr_engine* e, void** slot, const vr_bert_desc* d_in, co
   // streamed kernel one per 128 queries. Which is faster was measured at 512 tokens;
   // VR_WINDOW_STREAM_FROM, read when the model is loaded, moves the length from which the streamed kernel runs.
   enc->window_stream_from = window_stream_from;
-  if (rms) VR_TRY(dev_alloc_copy_or_zero(e, enc, t[2], H, mem, &enc->type));
+  if (rms || rms_rot) VR_TRY(dev_alloc_copy_or_zero(e, enc, t[2], H, mem, &enc->type));
   else VR_TRY(dev_alloc_copy(e, enc, t[2], static_cast<size_t>(d->type_vocab) * H, mem, &enc->type));
   VR_TRY(dev_alloc_copy(e, enc, t[3], H, mem, &enc->lng));
-  if (!rms) VR_TRY(dev_alloc_copy(e, enc, t[4], H, mem, &enc->lnb));  // (RMSNorm: the shifts stay null, no kernel reads one)
+  if (!rms && !rms_rot) VR_TRY(dev_alloc_copy(e, enc, t[4], H, mem, &enc->lnb));  // (RMSNorm: the shifts stay null, no kernel reads one)
   const hipMemcpyKind kind = mem == VR_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
   for (int l = 0; l < L; ++l) {
     // q_w q_b k_w k_b v_w v_b o_w o_b ln1_g ln1_b i_w i_b f_w f_b ln2_g ln2_b (gated: + gate_w gate_b, i_* = up)
@@ -4407,7 +4474,7 @@ static int build_encoder(vr_engine* e, void** slot, const vr_bert_desc* d_in, co
     VR_TRY(dev_alloc_copy(e, enc, w[6], HH, mem, &lw.wo));
     VR_TRY(dev_alloc_copy_or_zero(e, enc, w[7], H, mem, &lw.bo));
     VR_TRY(dev_alloc_copy(e, enc, w[8], H, mem, &lw.ln1g));
-    if (!rms) VR_TRY(dev_alloc_copy(e, enc, w[9], H, mem, &lw.ln1b));
+    if (!rms && !rms_rot) VR_TRY(dev_alloc_copy(e, enc, w[9], H, mem, &lw.ln1b));
     if (gated) {
       const size_t IH = static_cast<size_t>(I) * H;
       VR_TRY(dev_alloc_copy(e, enc, nullptr, 2 * IH, mem, &lw.w1));
@@ -4426,7 +4493,7 @@ static int build_encoder(vr_engine* e, void** slot, const vr_bert_desc* d_in, co
     VR_TRY(dev_alloc_copy(e, enc, w[12], static_cast<size_t>(I) * H, mem, &lw.w2));
     VR_TRY(dev_alloc_copy_or_zero(e, enc, w[13], H, mem, &lw.b2));
     VR_TRY(dev_alloc_copy(e, enc, w[14], H, mem, &lw.ln2g));
-    if (!rms) VR_TRY(dev_alloc_copy(e, enc, w[15], H, mem, &lw.ln2b));
+    if (!rms && !rms_rot) VR_TRY(dev_alloc_copy(e, enc, w[15], H, mem, &lw.ln2b));
     if (d->precision != VR_PRECISION_F32) {
       const bool plain = d->precision == VR_PRECISION_F16;
       VR_TRY(make_split(e, enc, lw.wqkv, 3 * HH, H, plain, &lw.s_qkv));
@@ -4452,7 +4519,7 @@ static int build_encoder(vr_engine* e, void** slot, const vr_bert_desc* d_in, co
         if (rotary) VR_TRY(reordered(lw.wqkv, lw.bqkv, 3 * H, 0, H, &lw.s_qkv_p, &lw.bqkv_p));
         if (gated) VR_TRY(reordered(lw.w1, lw.b1, 2 * I, 1, I, &lw.s_1_p, &lw.b1_p));
       }
-      if (plain && H % 64 == 0 && !prenorm && !rms) {  // operands of the folded-LayerNorm GEMMs (the post-norm loop's)
+      if (plain && H % 64 == 0 && !prenorm && !rms && !rms_rot) {  // operands of the folded-LayerNorm GEMMs (the post-norm loop's)
         auto fold = [&](const float* w_dev, int N, const float* g, const float* b, const float* bias, SplitWeight* sw,
                         float** colsum, float** c) -> int {
           const size_t n = static_cast<size_t>(N) * H;
@@ -4662,12 +4729,16 @@ int encoder_out_dim(vr_engine* e) {
 
 int reranker_load(vr_engine* e, const vr_bert_desc* d_in, const void* const* t, int n_tensors, int mem) {
   vr_bert_desc desc;
-  VR_TRY(read_desc(d_in, &desc));
+  int32_t causal = 0;
+  VR_TRY(read_desc(d_in, &desc, &causal));
   const vr_bert_desc* d = &desc;
+  VR_CHECK(causal == 0, "a reranker takes no causal mask (causal %d)", causal);
   // a pre-norm, rotary, gated description is a ModernBERT cross-encoder: its own head (6 tensors), CLS or mean pooling
   const bool modern = d->norm == VR_NORM_PRE && d->position == VR_POS_ROTARY && d->ffn != VR_FFN_GELU;
   VR_CHECK(d->norm != VR_NORM_PRE_RMS, "a reranker with norm VR_NORM_PRE_RMS is not supported (norm %d): T5 cross-encoders "
            "are not implemented", d->norm);
+  VR_CHECK(d->norm != VR_NORM_PRE_RMS_ROTARY, "a reranker with norm VR_NORM_PRE_RMS_ROTARY is not supported (norm %d): decoder "
+           "cross-encoders are not implemented", d->norm);
   if (!modern) {
     VR_CHECK(d->position == VR_POS_LEARNED && d->ffn == VR_FFN_GELU,
              "a reranker with rotary positions or a gated FFN is not supported (position %d, ffn %d): cross-encoders are "
@@ -4677,6 +4748,8 @@ int reranker_load(vr_engine* e, const vr_bert_desc* d_in, const void* const* t, 
              "rotary positions and a gated FFN", d->norm, d->window);
     VR_CHECK(d->pooling == VR_POOL_CLS && d->normalize == 0, "a reranker pools the [CLS] row (pooling 1) without normalising");
   } else {
+    VR_CHECK(d->pooling != VR_POOL_LAST, "a reranker pools the [CLS] row or the mean (pooling %d): last-token pooling is the "
+             "embedder's", d->pooling);
     VR_CHECK(d->normalize == 0, "a reranker pools without normalising (normalize %d)", d->normalize);
     VR_CHECK(d->type_vocab == 1, "a pre-norm reranker has one token type (type_vocab %d)", d->type_vocab);
   }
@@ -4761,8 +4834,11 @@ static int launch_attention(vr_engine* e, Encoder* enc, const int32_t* cu_dev, i
   const bool table = enc->bias != nullptr;
   const int radius = enc->bias_radius;
   VR_CHECK(!(bias && window > 0), "an attention bias and a window %d cannot meet", window);
+  // (the causal mask is BIAS_KIND's fourth state: its norm, VR_NORM_PRE_RMS_ROTARY, has no window and takes no bias)
+  VR_CHECK(!(enc->causal && (bias || window > 0)), "a causal mask meets neither a bias nor a window %d", window);
   auto windowed = [&](auto launch) {
-    if (table) launch(std::false_type{}, std::integral_constant<int, kBiasTable>{});
+    if (enc->causal) launch(std::false_type{}, std::integral_constant<int, kMaskCausal>{});
+    else if (table) launch(std::false_type{}, std::integral_constant<int, kBiasTable>{});
     else if (bias) launch(std::false_type{}, std::integral_constant<int, kBiasSlopes>{});
     else if (window > 0) launch(std::true_type{}, std::integral_constant<int, kBiasNone>{});
     else launch(std::false_type{}, std::integral_constant<int, kBiasNone>{});
@@ -4790,12 +4866,14 @@ static int launch_attention(vr_engine* e, Encoder* enc, const int32_t* cu_dev, i
       for (const void* f : {reinterpret_cast<const void*>(&attention_seq_kernel<64, 4, false, kBiasNone>),
                             reinterpret_cast<const void*>(&attention_seq_kernel<64, 4, true, kBiasNone>),
                             reinterpret_cast<const void*>(&attention_seq_kernel<64, 4, false, kBiasTable>),
-                            reinterpret_cast<const void*>(&attention_seq_kernel<64, 4, false, kBiasSlopes>)})
+                            reinterpret_cast<const void*>(&attention_seq_kernel<64, 4, false, kBiasSlopes>),
+                            reinterpret_cast<const void*>(&attention_seq_kernel<64, 4, false, kMaskCausal>)})
         if (dh == 64) VR_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_bytes)));
       for (const void* f : {reinterpret_cast<const void*>(&attention_seq_kernel<32, 4, false, kBiasNone>),
                             reinterpret_cast<const void*>(&attention_seq_kernel<32, 4, true, kBiasNone>),
                             reinterpret_cast<const void*>(&attention_seq_kernel<32, 4, false, kBiasTable>),
-                            reinterpret_cast<const void*>(&attention_seq_kernel<32, 4, false, kBiasSlopes>)})
+                            reinterpret_cast<const void*>(&attention_seq_kernel<32, 4, false, kBiasSlopes>),
+                            reinterpret_cast<const void*>(&attention_seq_kernel<32, 4, false, kMaskCausal>)})
         if (dh != 64) VR_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_bytes)));
       lds_allowed[which] = lds_bytes;
     }
@@ -5127,6 +5205,146 @@ static int forward_chunk_rms(vr_engine* e, Encoder* enc, const int32_t* ids_dev,
   return 0;
 }
 
+// The forward pass of an RMSNorm pre-norm model with rotary positions and a gated FFN (VR_NORM_PRE_RMS_ROTARY: the Llama /
+// Qwen2 block, the decoder-style embedders), forward_chunk's arguments:
+//   h = word[id];  per layer  h += W_o attn(rope(N_a(h))),  h += W_down(act(gate(N_m(h))) * up(N_m(h)));  out = N_f(h)
+// forward_chunk_rms's stream (the embedding launch leaves the RAW row in it and writes N_a of layer 0; every N is RMSNorm,
+// a launch of its own or, for a question of <= 16 rows in f16 mode, folded into the projection that reads it) with
+// forward_chunk_prenorm's rotation and gate on every route those have: rope_kernel / glu_kernel as passes of their own in
+// f32 and f16x3 (and under VR_ENCODE_FUSE=0), in f16 the gate inside the FFN-up epilogues and the rotation inside the
+// Q/K/V epilogue of the skinny routes. The causal mask (vr_bert_desc_v2.causal) reaches the attention kernels through
+// launch_attention; causal = 0 is the same body run bidirectionally.
+static int forward_chunk_rms_rotary(vr_engine* e, Encoder* enc, const int32_t* ids_dev, const int32_t* cu_dev, int n_seq_total,
+                                    int seq0, int seq1, int tok_base, int T, int max_len, double attn_flop, float* out_dev,
+                                    const Spans* sp) {
+  const vr_bert_desc& d = enc->d;
+  const int H = d.hidden, I = d.intermediate, dh = H / d.heads, N1 = 2 * I;
+  hipStream_t s = e->stream;
+  const unsigned row_blocks = static_cast<unsigned>((T + 3) / 4);
+  const bool split = d.precision != VR_PRECISION_F32;
+  const bool plain = d.precision == VR_PRECISION_F16;
+  const int passes = plain ? 1 : 3;
+  // GEMM inputs as in forward_chunk_prenorm: the normalised rows in xs (f32 mode: in ctx), the context in ctx, the gated
+  // activation in ffn
+  half_t* xh = split ? reinterpret_cast<half_t*>(enc->xs) : nullptr;
+  half_t* xl = split && !plain ? xh + 8 : nullptr;
+  half_t* ch = split ? reinterpret_cast<half_t*>(enc->ctx) : nullptr;
+  half_t* cl = split && !plain ? ch + 8 : nullptr;
+  half_t* fh = split ? reinterpret_cast<half_t*>(enc->ffn) : nullptr;
+  half_t* fl = split && !plain ? fh + 8 : nullptr;
+  half_t* qkvh = reinterpret_cast<half_t*>(enc->qkv);
+  const int32_t* posidx = reinterpret_cast<const int32_t*>(enc->posidx);
+  float2* stat = reinterpret_cast<float2*>(enc->lnstat);  // (launch_skinny_ln stores the rows' 1/rms; nobody reads them)
+  const bool fuse = plain && enc->fuse;
+  const bool fold_ln = plain && skinny_rms_rotary_supported(T, 3 * H, H) && I % 16 == 0;
+  const bool fuse_rope = fuse && skinny_routed(T, 3 * H, H);
+  const bool fuse_glu = fuse && skinny_routed(T, N1, H);
+  const int glu_epi = d.ffn == VR_FFN_SWIGLU ? EPI_SWIGLU_F16 : EPI_GEGLU_F16;
+  // the [T, 2I] pre-activation of the unfused gate (never allocated during a graph capture: a shape runs eagerly first)
+  if (!fuse_glu && !enc->glu) {
+    const size_t rows = static_cast<size_t>(enc->ws_tokens);
+    VR_TRY(dev_alloc_copy(e, enc, nullptr, plain ? rows * I : rows * 2 * I, 0, &enc->glu));
+  }
+  half_t* gluh = reinterpret_cast<half_t*>(enc->glu);
+  // rows of h normalised by g -> the next product's input
+  auto norm_rows = [&](const float* h, const float* g) {
+    if (plain && H % 256 == 0)
+      hipLaunchKernelGGL(rmsnorm_f16_kernel, dim3(row_blocks), dim3(256), 0, s, h, T, H, g, d.eps, xh);
+    else
+      hipLaunchKernelGGL(rmsnorm_kernel, dim3(row_blocks), dim3(256), 0, s, h, T, H, g, d.eps, split ? nullptr : enc->ctx, xh, xl);
+  };
+  hipLaunchKernelGGL(embed_rms_kernel, dim3(row_blocks), dim3(256), 0, s, ids_dev, cu_dev, n_seq_total, tok_base, T, H, d.vocab,
+                     enc->word, enc->type, enc->lng, d.eps, split ? nullptr : enc->ctx, xh, xl, enc->x);
+  hipLaunchKernelGGL(positions_kernel, dim3(static_cast<unsigned>((T + 255) / 256)), dim3(256), 0, s, cu_dev, n_seq_total,
+                     tok_base, T, reinterpret_cast<int32_t*>(enc->posidx));
+  float* h = enc->x;      // the residual stream
+  float* other = enc->tmp;
+  const int n_seq = seq1 - seq0;
+  // (a causal pass multiplies about half the logits)
+  const double layer_flop = enc->causal ? 0.5 * attn_flop : attn_flop;
+  for (size_t li = 0; li < enc->layers.size(); ++li) {
+    const LayerWeights& w = enc->layers[li];
+    // Q, K, V of N_a(h); layer 0 reads the rows the embedding launch normalised
+    if (fold_ln && li > 0) {
+      const float* g = enc->layers[li - 1].ln2g;
+      if (fuse_rope)
+        VR_TRY(launch_skinny_ln(e, EPI_ROPE_F16, h, d.eps, stat,
+                                {.W = w.s_qkv_p, .bias = w.bqkv_p, .Ch = qkvh, .M = T, .N = 3 * H, .K = H, .ln_g = g,
+                                 .rope_tab = enc->rope, .rope_pos = posidx}, true));
+      else
+        VR_TRY(launch_skinny_ln(e, EPI_BIAS_F16, h, d.eps, stat,
+                                {.W = w.s_qkv, .bias = w.bqkv, .Ch = qkvh, .M = T, .N = 3 * H, .K = H, .ln_g = g}, true));
+    } else {
+      if (li > 0) norm_rows(h, enc->layers[li - 1].ln2g);
+      if (fuse_rope)
+        VR_TRY(launch_gemm_f16x3(e, enc, EPI_ROPE_F16, {.A = xh, .W = w.s_qkv_p, .bias = w.bqkv_p, .Ch = qkvh, .M = T, .N = 3 * H,
+                                                        .K = H, .passes = 1, .rope_tab = enc->rope, .rope_pos = posidx}));
+      else if (plain)
+        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_F16, {.A = xh, .W = w.s_qkv, .bias = w.bqkv, .Ch = qkvh, .M = T, .N = 3 * H,
+                                                        .K = H, .passes = 1}));
+      else if (split)
+        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS, {.A = xh, .A_lo = xl, .W = w.s_qkv, .bias = w.bqkv, .C = enc->qkv, .M = T,
+                                                    .N = 3 * H, .K = H, .passes = passes}));
+      else
+        VR_TRY(launch_gemm(e, EPI_BIAS, enc->ctx, w.wqkv, w.bqkv, nullptr, enc->qkv, T, 3 * H, H));
+    }
+    if (!fuse_rope) {  // the rotation as a pass of its own
+      if (plain)
+        hipLaunchKernelGGL(rope_kernel<half_t>, dim3(row_blocks), dim3(256), 0, s, qkvh, posidx, T, H, dh, enc->rope);
+      else
+        hipLaunchKernelGGL(rope_kernel<float>, dim3(row_blocks), dim3(256), 0, s, enc->qkv, posidx, T, H, dh, enc->rope);
+    }
+    VR_TRY(launch_attention(e, enc, cu_dev, seq0, n_seq, tok_base, max_len, false, 0, layer_flop));
+    // h' = h + W_o ctx
+    if (split)
+      VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_RESIDUAL, {.A = ch, .A_lo = cl, .W = w.s_o, .bias = w.bo, .R = h, .C = other, .M = T,
+                                                           .N = H, .K = H, .passes = passes}));
+    else
+      VR_TRY(launch_gemm(e, EPI_BIAS_RESIDUAL, enc->ctx, w.wo, w.bo, h, other, T, H, H));
+    std::swap(h, other);
+    // the gated FFN of N_m(h)
+    if (fold_ln && fuse_glu) {
+      VR_TRY(launch_skinny_ln(e, glu_epi, h, d.eps, stat,
+                              {.W = w.s_1_p, .bias = w.b1_p, .Ch = fh, .M = T, .N = N1, .K = H, .ln_g = w.ln1g}, true));
+    } else if (fold_ln) {
+      VR_TRY(launch_skinny_ln(e, EPI_BIAS_F16, h, d.eps, stat,
+                              {.W = w.s_1, .bias = w.b1, .Ch = gluh, .M = T, .N = N1, .K = H, .ln_g = w.ln1g}, true));
+    } else {
+      norm_rows(h, w.ln1g);
+      if (fuse_glu)
+        VR_TRY(launch_gemm_f16x3(e, enc, glu_epi, {.A = xh, .W = w.s_1_p, .bias = w.b1_p, .Ch = fh, .M = T, .N = N1, .K = H, .passes = 1}));
+      else if (plain)
+        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_F16, {.A = xh, .W = w.s_1, .bias = w.b1, .Ch = gluh, .M = T, .N = N1, .K = H,
+                                                        .passes = 1}));
+      else if (split)
+        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS, {.A = xh, .A_lo = xl, .W = w.s_1, .bias = w.b1, .C = enc->glu, .M = T, .N = N1,
+                                                    .K = H, .passes = passes}));
+      else
+        VR_TRY(launch_gemm(e, EPI_BIAS, enc->ctx, w.w1, w.b1, nullptr, enc->glu, T, N1, H));
+    }
+    if (!fuse_glu) {
+      const int64_t n8 = static_cast<int64_t>(T) * (I / 8);
+      const dim3 grid(static_cast<unsigned>((n8 + 255) / 256));
+      if (plain) hipLaunchKernelGGL((glu_kernel<half_t, 2>), grid, dim3(256), 0, s, gluh, n8, I, d.ffn, static_cast<float*>(nullptr), fh);
+      else if (split) hipLaunchKernelGGL((glu_kernel<float, 1>), grid, dim3(256), 0, s, enc->glu, n8, I, d.ffn, static_cast<float*>(nullptr), fh);
+      else hipLaunchKernelGGL((glu_kernel<float, 0>), grid, dim3(256), 0, s, enc->glu, n8, I, d.ffn, enc->ffn, static_cast<half_t*>(nullptr));
+    }
+    // h' = h + W_down act
+    if (split)
+      VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_RESIDUAL, {.A = fh, .A_lo = fl, .W = w.s_2, .bias = w.b2, .R = h, .C = other, .M = T,
+                                                           .N = H, .K = I, .passes = passes}));
+    else
+      VR_TRY(launch_gemm(e, EPI_BIAS_RESIDUAL, enc->ffn, w.w2, w.b2, h, other, T, H, I));
+    std::swap(h, other);
+  }
+  // the final norm writes the f32 rows pooling reads, into the buffer the stream is not in
+  hipLaunchKernelGGL(rmsnorm_kernel, dim3(row_blocks), dim3(256), 0, s, h, T, H, enc->layers.back().ln2g, d.eps, other,
+                     static_cast<half_t*>(nullptr), static_cast<half_t*>(nullptr));
+  launch_pool(e, enc, other, cu_dev, seq0, seq1, tok_base, 0, out_dev, sp);
+  VR_HIP(hipGetLastError());
+  return 0;
+}
+
 // forward of sequences [seq0, seq1) whose tokens are ids_dev[tok_base .. tok_base + T). sp (or null): pool the spans
 // of these sequences, one row each at out_dev[span], instead of one row per sequence — the pass then runs as a
 // mean-pooled model's does, whatever the description's pooling says.
@@ -5134,6 +5352,8 @@ static int forward_chunk(vr_engine* e, Encoder* enc, const int32_t* ids_dev, con
                          const int32_t* seg_dev, int n_seq_total, int seq0, int seq1, int tok_base, int T, int max_len,
                          double attn_flop, float* out_dev, const Spans* sp = nullptr) {
   const vr_bert_desc& d = enc->d;
+  if (d.norm == VR_NORM_PRE_RMS_ROTARY)  // the Qwen2 form
+    return forward_chunk_rms_rotary(e, enc, ids_dev, cu_dev, n_seq_total, seq0, seq1, tok_base, T, max_len, attn_flop, out_dev, sp);
   if (d.norm == VR_NORM_PRE_RMS)  // the T5 form of the routine below
     return forward_chunk_rms(e, enc, ids_dev, cu_dev, n_seq_total, seq0, seq1, tok_base, T, max_len, attn_flop, out_dev, sp);
   if (d.norm == VR_NORM_PRE)  // a routine of its own: none of the LayerNorm folds below applies to it

@@ -98,9 +98,11 @@ def _read_family_config(path: str, cfg: dict) -> dict:
         return _read_distilbert_config(path, cfg)
     if kind == "t5":
         return _read_t5_config(path, cfg)
+    if kind == "qwen2":
+        return _read_qwen2_config(path, cfg)
     if kind not in ("bert", "xlm-roberta"):
         raise ValueError(f"unsupported model_type {kind}: BERT, DistilBERT, XLM-RoBERTa, MPNet, T5, nomic_bert and "
-                         "modernbert encoders only")
+                         "modernbert encoders only, and Qwen2 decoder embedders (the 0.5B body)")
     if kind == "bert" and cfg.get("position_embedding_type", "absolute") == "alibi":
         return _read_alibi_config(path, cfg)
     if cfg.get("hidden_act", "gelu") != "gelu" or cfg.get("position_embedding_type", "absolute") != "absolute":
@@ -150,6 +152,8 @@ def _read_modules(path: str, max_seq: int):
                 pc = json.load(open(os.path.join(path, m["path"], "config.json")))
                 if pc.get("pooling_mode_cls_token"):
                     pooling = "cls"
+                elif pc.get("pooling_mode_lasttoken"):
+                    pooling = "last"
                 elif not pc.get("pooling_mode_mean_tokens", True):
                     raise ValueError("only CLS and mean pooling are implemented")
             elif k.endswith("Normalize"):
@@ -284,6 +288,56 @@ def _read_t5_config(path: str, cfg: dict) -> dict:
                          norm="rms_pre")
     return {"desc": desc, "max_seq": max_seq, "pos_start": 0, "config": cfg, "buckets": buckets,
             "max_distance": max_distance}
+
+
+def _read_qwen2_config(path: str, cfg: dict) -> dict:
+    """model_type qwen2 (jina-code-embeddings-0.5b, the KaLM-embedding-mini models and other Qwen2.5-0.5B fine-tunes): a
+    decoder body used as an embedder — RMSNorm pre-norm blocks, rotary positions over the whole head, a SwiGLU FFN,
+    biases on q/k/v only, causal self-attention (unless the directory says is_causal false) and grouped-query attention,
+    which encoder.qwen2_slots resolves at load by repeating the K and V heads (HF repeat_kv). The row is pooled as
+    1_Pooling says (pooling_mode_lasttoken for these models); a bare config.json pools the mean. The longest sequence is
+    min(max_seq_length, max_position_embeddings, seq_cap())."""
+    H, heads = int(cfg["hidden_size"]), int(cfg["num_attention_heads"])
+    kv_heads = int(cfg.get("num_key_value_heads") or heads)
+    if kv_heads < 1 or heads % kv_heads:
+        raise ValueError(f"num_attention_heads {heads} is not a multiple of num_key_value_heads {kv_heads}")
+    if heads < 1 or H % heads or cfg.get("head_dim") not in (None, H // heads):
+        raise ValueError(f"head_dim {cfg.get('head_dim')} differs from hidden_size / num_attention_heads = {H} / {heads}: a "
+                         "query width other than the hidden size is not implemented")
+    if H // heads not in (32, 64):
+        raise ValueError(f"head size {H // heads} (hidden_size {H} / num_attention_heads {heads}) is not implemented: the "
+                         "attention kernels run head sizes 32 and 64")
+    if H % 128 or H > 1024:
+        raise ValueError(f"hidden_size {H} is not implemented: the engine runs multiples of 128 up to 1024 (the Qwen2-0.5B "
+                         "body is 896)")
+    act = cfg.get("hidden_act", "silu")
+    if act != "silu":
+        raise ValueError(f"hidden_act {act!r} is not implemented: a qwen2 FFN is down(silu(gate(x)) * up(x))")
+    rp = cfg.get("rope_parameters") or {}
+    rope_type = rp.get("rope_type", rp.get("type", "default"))
+    if cfg.get("rope_scaling") is not None or rope_type != "default":
+        raise ValueError(f"rope_scaling {cfg.get('rope_scaling') or rope_type!r} is not implemented: only the default rotary "
+                         "embedding (no scaling)")
+    if cfg.get("use_sliding_window", False):
+        raise ValueError("use_sliding_window true is not implemented: a causal sliding window is not in the attention "
+                         "kernels")
+    declared = int(cfg.get("max_position_embeddings", 32768))
+    pooling, normalize, max_seq = _read_modules(path, declared)
+    max_seq = min(max_seq, declared)
+    cap = seq_cap()
+    if max_seq > cap:
+        logger.warning("%s declares sequences of up to %d tokens; the engine runs at most %d: longer texts are "
+                       "truncated to %d tokens (%s raises the cap, up to %d)", path, max_seq, cap, cap, SEQ_CAP_VARIABLE,
+                       MAX_SEQ_LENGTH_LIMIT)
+        max_seq = cap
+    desc = _enc.BertDesc(layers=int(cfg["num_hidden_layers"]), hidden=H, heads=heads,
+                         intermediate=int(cfg["intermediate_size"]), vocab=int(cfg["vocab_size"]),
+                         max_pos=max_seq,  # rotary: the length of the cos/sin table
+                         type_vocab=1, pooling=pooling, normalize=normalize, eps=float(cfg.get("rms_norm_eps", 1e-6)),
+                         precision=os.environ.get("VOITTA_ENCODER_PRECISION", "f16"), position="rotary",
+                         rope_theta=float(rp.get("rope_theta", cfg.get("rope_theta", 10000.0))), ffn="swiglu",
+                         norm="rms_pre_rotary", causal=0 if cfg.get("is_causal", True) is False else 1)
+    return {"desc": desc, "max_seq": max_seq, "pos_start": 0, "config": cfg, "kv_heads": kv_heads}
 
 
 def _read_mpnet_config(path: str, cfg: dict) -> dict:
@@ -510,6 +564,8 @@ class NativeSentenceEncoder:
             rc["desc"].attention_bias = _enc.t5_bias_table(
                 _enc._find(state, "encoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight"),
                 rc["buckets"], rc["max_distance"])
+        elif rc["config"].get("model_type") == "qwen2":
+            state = cls._load_weights(path)  # (load_encoder's qwen2_slots maps the weights and repeats the K/V heads)
         else:
             state = slice_positions(cls._load_weights(path), rc["pos_start"])
         return cls(engine or get_engine(), rc["desc"], state, cls._load_tokenizer(path, rc["config"]), rc["max_seq"])
@@ -534,7 +590,8 @@ class NativeSentenceEncoder:
         pipeline wrapped in <s> ... </s>, the names read from tokenizer.json's post_processor), the native Unigram
         (csrc/unigram.cpp)
         for the XLM-R pipeline of an XLM-R model and the same pipeline with the template $A </s> of a T5 model, the
-        native byte-level BPE (csrc/bpe.cpp) for a ModernBERT model's pipeline; anything else that a tokenizer.json may describe (a BERT model with a Unigram tokenizer.json among
+        native byte-level BPE (csrc/bpe.cpp) for a ModernBERT or Qwen2 model's pipeline where it accepts it (Qwen's own
+        pre-tokenizer pattern it refuses); anything else that a tokenizer.json may describe (a BERT model with a Unigram tokenizer.json among
         them, as before) goes through the HF `tokenizers` library."""
         tj = os.path.join(path, "tokenizer.json")
         if os.path.exists(tj) and cfg.get("model_type") in ("xlm-roberta", "t5"):
@@ -543,7 +600,7 @@ class NativeSentenceEncoder:
                 if is_unigram_pipeline(spec):
                     return UnigramTokenizer.from_tokenizer_json(spec)
                 logger.info("native Unigram not applicable; using the tokenizers library")
-        if os.path.exists(tj) and cfg.get("model_type") == "modernbert":
+        if os.path.exists(tj) and cfg.get("model_type") in ("modernbert", "qwen2"):
             spec = json.load(open(tj, encoding="utf-8"))
             if (spec.get("model") or {}).get("type") == "BPE":
                 try:

@@ -12,7 +12,7 @@ from dataclasses import dataclass, field, replace
 import numpy as np
 
 from . import _lib
-from ._lib import VR_MEM_DEVICE, VR_MEM_HOST, VR_POOL_CLS, VR_POOL_MEAN, check
+from ._lib import VR_MEM_DEVICE, VR_MEM_HOST, VR_POOL_CLS, VR_POOL_LAST, VR_POOL_MEAN, check
 
 EMB_SUFFIXES = [
     "embeddings.word_embeddings.weight",
@@ -83,7 +83,7 @@ class BertDesc:
     vocab: int = 30522
     max_pos: int = 512
     type_vocab: int = 2
-    pooling: str = "mean"  # "mean" | "cls"
+    pooling: str = "mean"  # "mean" | "cls" | "last" (the sequence's last token: decoder-style embedders)
     normalize: bool = True
     eps: float = 1e-12
     precision: str = "f32"  # "f32" (exact f32 MFMA) | "f16x3" (split-precision f16 MFMA, f32-class accuracy)
@@ -94,11 +94,13 @@ class BertDesc:
     # "gelu" | "swiglu" | "geglu" (down(act(gate(x)) * up(x)), act = SiLU / exact GELU) | "relu" (down(relu(up(x))): T5)
     ffn: str = "gelu"
     # "post" (x = LN(x + f(x))) | "pre" (x = x + f(LN(x)), a final LayerNorm: the ModernBERT family) | "rms_pre" (the
-    # same with RMSNorm and no embedding norm in the stream: the T5 encoders; needs position "none" and ffn "relu")
+    # same with RMSNorm and no embedding norm in the stream: the T5 encoders; needs position "none" and ffn "relu") |
+    # "rms_pre_rotary" (the Llama / Qwen2 block: RMSNorm pre-norm with rotary positions and a gated ffn)
     norm: str = "post"
     window: int = 0  # sliding-window attention: query i of a windowed layer sees key j iff |i - j| <= window; 0 = none
     global_every: int = 0  # window > 0: layer l attends globally iff l % global_every == 0
     rope_theta_local: float = 0.0  # the rotary base of the windowed layers; 0 = rope_theta
+    causal: int = 0  # 1: query i sees key j iff j <= i (norm "rms_pre_rotary" only)
     # additive attention bias by relative offset, f32 [heads, 2 * radius + 1] (MPNet: mpnet_bias_table, T5:
     # t5_bias_table); not a field of
     # vr_bert_desc: load_encoder hands it to vr_encoder_set_attention_bias once the model is loaded
@@ -136,12 +138,20 @@ class BertDesc:
     def rms(self) -> bool:
         return self.norm == "rms_pre"
 
+    @property
+    def rms_rotary(self) -> bool:
+        return self.norm == "rms_pre_rotary"
+
     def to_c(self) -> _lib.VrBertDesc:
-        d = _lib.VrBertDesc()
-        d.struct_size = C.sizeof(_lib.VrBertDesc)
+        # (a causal description crosses as vr_bert_desc_v2, every other one as the vr_bert_desc it always was)
+        d = _lib.VrBertDescV2() if self.causal else _lib.VrBertDesc()
+        d.struct_size = C.sizeof(type(d))
         d.layers, d.hidden, d.heads, d.intermediate = self.layers, self.hidden, self.heads, self.intermediate
         d.vocab, d.max_pos, d.type_vocab = self.vocab, self.max_pos, self.type_vocab
-        d.pooling = VR_POOL_CLS if self.pooling == "cls" else VR_POOL_MEAN
+        poolings = {"mean": VR_POOL_MEAN, "cls": VR_POOL_CLS, "last": VR_POOL_LAST}
+        if self.pooling not in poolings:
+            raise ValueError(f"unknown pooling {self.pooling!r}")
+        d.pooling = poolings[self.pooling]
         d.normalize = int(self.normalize)
         d.eps = self.eps
         codes = {"f32": _lib.VR_PRECISION_F32, "f16x3": _lib.VR_PRECISION_F16X3, "f16": _lib.VR_PRECISION_F16}
@@ -155,11 +165,14 @@ class BertDesc:
         if self.ffn not in ffns:
             raise ValueError(f"unknown ffn kind {self.ffn!r}")
         d.position, d.rope_theta, d.ffn = positions[self.position], float(self.rope_theta), ffns[self.ffn]
-        norms = {"post": _lib.VR_NORM_POST, "pre": _lib.VR_NORM_PRE, "rms_pre": _lib.VR_NORM_PRE_RMS}
+        norms = {"post": _lib.VR_NORM_POST, "pre": _lib.VR_NORM_PRE, "rms_pre": _lib.VR_NORM_PRE_RMS,
+                 "rms_pre_rotary": _lib.VR_NORM_PRE_RMS_ROTARY}
         if self.norm not in norms:
             raise ValueError(f"unknown norm placement {self.norm!r}")
         d.norm, d.window, d.global_every = norms[self.norm], int(self.window), int(self.global_every)
         d.rope_theta_local = float(self.rope_theta_local)
+        if self.causal:
+            d.causal = int(self.causal)
         return d
 
 
@@ -414,6 +427,69 @@ def t5_slots(state: dict, desc: "BertDesc", num_buckets: int = 32, max_distance:
     return names, out, bias
 
 
+def qwen2_slots(state: dict, desc: "BertDesc", kv_heads: int | None = None):
+    """A transformers Qwen2Model (or Qwen2ForCausalLM) state dict, any key prefix -> (slot names, state under those
+    names): the 18-slot gated layout under the rotary family's native names, with no position table, no token types and
+    no norm shifts (NULL), biases on q/k/v only. Under VR_NORM_PRE_RMS_ROTARY embeddings.LayerNorm holds
+    layers.0.input_layernorm, layer l's post_attention_layernorm its own, and its post_mlp_layernorm
+    layers.l+1.input_layernorm — `norm` for the last.
+    Grouped-query attention is resolved here: k_proj and v_proj (weights and biases) of KV head j are repeated for the
+    query heads j g .. j g + g - 1, g = heads / kv_heads (HF repeat_kv), so the engine sees `heads` full heads. kv_heads:
+    num_key_value_heads, or None to read it off k_proj's rows. lm_head.* is ignored; any other tensor left over is
+    refused by name."""
+    used = set()
+
+    def get(name, optional=False):
+        hits = [k for k in state if k == name or k.endswith("." + name)]
+        if not hits and optional:
+            return None
+        if len(hits) != 1:
+            raise KeyError(f"weight '{name}' not found (or ambiguous) in state dict: {hits[:3]}")
+        used.add(hits[0])
+        t = state[hits[0]]
+        return t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
+
+    H, heads, L = desc.hidden, desc.heads, desc.layers
+    dh = H // heads
+    if kv_heads is None:
+        rows = int(get("layers.0.self_attn.k_proj.weight").shape[0])
+        if rows % dh:
+            raise ValueError(f"weight 'layers.0.self_attn.k_proj.weight' has {rows} rows, not whole heads of {dh}")
+        kv_heads = rows // dh
+    if kv_heads < 1 or heads % kv_heads:
+        raise ValueError(f"num_attention_heads {heads} is not a multiple of num_key_value_heads {kv_heads}")
+    g = heads // kv_heads
+
+    def repeat_kv(t, name):
+        if t.shape[0] != kv_heads * dh:
+            raise ValueError(f"weight '{name}' has {t.shape[0]} rows, num_key_value_heads {kv_heads} of head size {dh} "
+                             f"imply {kv_heads * dh}")
+        if g == 1:
+            return t
+        return np.ascontiguousarray(np.repeat(t.reshape(kv_heads, dh, *t.shape[1:]), g, axis=0).reshape(heads * dh, *t.shape[1:]))
+
+    out = {"embeddings.word_embeddings.weight": get("embed_tokens.weight"),
+           "embeddings.LayerNorm.weight": get("layers.0.input_layernorm.weight")}
+    names = ["embeddings.word_embeddings.weight", None, None, "embeddings.LayerNorm.weight", None]
+    for i in range(L):
+        p = f"layers.{i}."
+        for kind in ("weight", "bias"):
+            out[p + "self_attn.q_proj." + kind] = get(p + "self_attn.q_proj." + kind)
+            for part in ("k_proj", "v_proj"):
+                name = p + "self_attn." + part + "." + kind
+                out[name] = repeat_kv(get(name), name)
+        out[p + "self_attn.o_proj.weight"] = get(p + "self_attn.o_proj.weight")
+        for part in ("gate_proj", "up_proj", "down_proj"):
+            out[p + "mlp." + part + ".weight"] = get(p + "mlp." + part + ".weight")
+        out[p + "post_attention_layernorm.weight"] = get(p + "post_attention_layernorm.weight")
+        out[p + "post_mlp_layernorm.weight"] = get(f"layers.{i + 1}.input_layernorm.weight" if i + 1 < L else "norm.weight")
+        names += [n if n in out else None for n in (p + s for s in PRENORM_LAYER_SUFFIXES)]
+    extra = sorted(k for k in state if k not in used and "lm_head" not in k.split("."))
+    if extra:
+        raise ValueError(f"not a Qwen2 state dict of {L} layers: unexpected tensors {extra[:4]}{' ...' if len(extra) > 4 else ''}")
+    return names, out
+
+
 def distilbert_slots(state: dict, desc: "BertDesc") -> dict:
     """A transformers DistilBertModel state dict (with or without the `distilbert.` prefix) -> the state under the BERT
     names of tensor_names(). DistilBERT is BERT's post-LayerNorm body without token types: the token-type slot is a zero
@@ -588,6 +664,8 @@ def load_encoder(engine, desc: BertDesc, state: dict) -> None:
     (jina_slots), a GELU one a BERT state dict without its position table."""
     if desc.prenorm:
         names, state = modernbert_slots(state, desc)
+    elif desc.rms_rotary:  # (a Qwen2 state dict; the K/V heads of grouped-query attention are repeated here)
+        names, state = qwen2_slots(state, desc)
     elif desc.rms:  # (a T5 state dict; the description's attention_bias, else the checkpoint's table with T5's defaults)
         names, state, table = t5_slots(state, desc, table=desc.attention_bias is None)
         if table is not None:

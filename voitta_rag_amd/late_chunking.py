@@ -161,7 +161,8 @@ def plain_plan(chunk_texts, tokenize, pooling: str = "mean") -> Plan:
     ids, off = np.asarray(ids, np.int32), np.asarray(off, np.int32)
     n = off.shape[0] - 1
     lens = np.diff(off)
-    span_tok = np.stack([np.zeros(n, np.int32), np.ones(n, np.int32) if pooling == "cls" else lens], 1).astype(np.int32)
+    first = np.maximum(lens - 1, 0) if pooling == "last" else np.zeros(n, np.int32)  # ("last": the span of the last token alone)
+    span_tok = np.stack([first, np.ones(n, np.int32) if pooling == "cls" else lens], 1).astype(np.int32)
     return Plan(ids, off, np.arange(n + 1, dtype=np.int32), span_tok, np.zeros(n, bool), [False])
 
 
