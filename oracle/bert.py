@@ -106,9 +106,33 @@ def _ln(x, g, b, eps):
     return (x - mu) / np.sqrt(var + eps) * g + b
 
 
-def encode_one(w: dict, shape: BertShape, ids, dtype=np.float64) -> np.ndarray:
-    """last_hidden_state [S, H] of one unpadded sequence."""
-    W = lambda k: w[k].astype(dtype)  # noqa: E731
+def attend(s, v, bias=None, operand=None):
+    """softmax(s + bias) v over the last axis of the logits s [heads, S, S]; bias: an additive [heads, S, S] array (a
+    relative-position bias, a mask of 0 and -inf, or a deliberate mistake of tests/attention_case.py; [heads, S, S + n]:
+    n zero keys with zero values join behind the sequence's end). operand (e.g.
+    rope_oracle.f16_operand): the probabilities are rounded as an f16 attention kernel rounds them — exp(s - max)
+    unnormalised as the operand of the product with v, the sum over the unrounded ones dividing behind it."""
+    if bias is not None:
+        extra = bias.shape[-1] - s.shape[-1]
+        if extra > 0:  # columns more than keys: phantom keys behind the end, k = 0 and v = 0
+            s = np.concatenate([s, np.zeros(s.shape[:-1] + (extra,), s.dtype)], axis=-1)
+            v = np.concatenate([v, np.zeros(v.shape[:-2] + (extra, v.shape[-1]), v.dtype)], axis=-2)
+        s = s + bias
+    s = s - s.max(axis=-1, keepdims=True)
+    p = np.exp(s)
+    if operand is not None:
+        return (operand(p) @ v) / p.sum(axis=-1, keepdims=True)
+    p = p / p.sum(axis=-1, keepdims=True)
+    return p @ v
+
+
+def encode_one(w: dict, shape: BertShape, ids, dtype=np.float64, bias=None, operand=None) -> np.ndarray:
+    """last_hidden_state [S, H] of one unpadded sequence. bias: an additive [heads, S, S] array on every layer's logits.
+    operand: as rope_oracle.encode_one's — applied to both operands of every matrix product, the probabilities included
+    (attend)."""
+    r = operand or (lambda a: a)  # noqa: E731
+    # (a projection matrix is an operand of a product; biases, embeddings and LayerNorm parameters are not)
+    W = lambda k: r(w[k].astype(dtype)) if w[k].ndim == 2 and k.startswith("encoder.") else w[k].astype(dtype)  # noqa: E731
     ids = np.asarray(ids, dtype=np.int64)
     S, H, nh = len(ids), shape.hidden, shape.heads
     dh = H // nh
@@ -116,16 +140,14 @@ def encode_one(w: dict, shape: BertShape, ids, dtype=np.float64) -> np.ndarray:
     x = _ln(x, W(EMB_KEYS["ln_g"]), W(EMB_KEYS["ln_b"]), dtype(shape.eps))
     for i in range(shape.layers):
         k = layer_keys(i)
-        q = (x @ W(k["q_w"]).T + W(k["q_b"])).reshape(S, nh, dh).transpose(1, 0, 2)
-        kk = (x @ W(k["k_w"]).T + W(k["k_b"])).reshape(S, nh, dh).transpose(1, 0, 2)
-        v = (x @ W(k["v_w"]).T + W(k["v_b"])).reshape(S, nh, dh).transpose(1, 0, 2)
+        xa = r(x)
+        q = r((xa @ W(k["q_w"]).T + W(k["q_b"])).reshape(S, nh, dh).transpose(1, 0, 2))
+        kk = r((xa @ W(k["k_w"]).T + W(k["k_b"])).reshape(S, nh, dh).transpose(1, 0, 2))
+        v = r((xa @ W(k["v_w"]).T + W(k["v_b"])).reshape(S, nh, dh).transpose(1, 0, 2))
         s = q @ kk.transpose(0, 2, 1) / dtype(math.sqrt(dh))
-        s = s - s.max(axis=-1, keepdims=True)
-        p = np.exp(s)
-        p = p / p.sum(axis=-1, keepdims=True)
-        ctx = (p @ v).transpose(1, 0, 2).reshape(S, H)
+        ctx = r(attend(s, v, bias, operand).transpose(1, 0, 2).reshape(S, H))
         x = _ln(ctx @ W(k["o_w"]).T + W(k["o_b"]) + x, W(k["ln1_g"]), W(k["ln1_b"]), dtype(shape.eps))
-        h = _gelu(x @ W(k["i_w"]).T + W(k["i_b"]))
+        h = r(_gelu(r(x) @ W(k["i_w"]).T + W(k["i_b"])))
         x = _ln(h @ W(k["f_w"]).T + W(k["f_b"]) + x, W(k["ln2_g"]), W(k["ln2_b"]), dtype(shape.eps))
     return x
 

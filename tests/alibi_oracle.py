@@ -89,10 +89,12 @@ def distance_bias(slopes, S: int, clamp: int | None = None) -> np.ndarray:
     return -np.asarray(slopes, np.float64)[:, None, None] * d[None]
 
 
-def encode_one(w: dict, shape: AlibiShape, ids, slopes, bias=None) -> np.ndarray:
+def encode_one(w: dict, shape: AlibiShape, ids, slopes, bias=None, operand=None) -> np.ndarray:
     """last_hidden_state [S, H] of one unpadded sequence, f64. slopes: [heads], or None for no bias. bias: a ready
-    [heads, S, S] array instead (distance_bias with a mistake built in)."""
-    W = lambda k: w[k].astype(np.float64)  # noqa: E731
+    [heads, S, S] array instead (distance_bias with a mistake built in). operand: as oracle.bert.encode_one's."""
+    r = operand or (lambda a: a)  # noqa: E731
+    product = lambda k: w[k].ndim == 2 and k.startswith("encoder.layer.")  # noqa: E731  (a projection matrix)
+    W = lambda k: r(w[k].astype(np.float64)) if product(k) else w[k].astype(np.float64)  # noqa: E731
     ids = np.asarray(ids, dtype=np.int64)
     S, H, nh, I = len(ids), shape.hidden, shape.heads, shape.intermediate
     dh = H // nh
@@ -101,20 +103,16 @@ def encode_one(w: dict, shape: AlibiShape, ids, slopes, bias=None) -> np.ndarray
     x = obert._ln(W(EMB_KEYS["word"])[ids] + W(EMB_KEYS["type"])[0], W(EMB_KEYS["ln_g"]), W(EMB_KEYS["ln_b"]), shape.eps)
     for i in range(shape.layers):
         k = layer_keys(i, shape.ffn)
-        q, kk, v = ((x @ W(k[n + "_w"]).T + W(k[n + "_b"])).reshape(S, nh, dh).transpose(1, 0, 2) for n in "qkv")
+        xa = r(x)
+        q, kk, v = (r((xa @ W(k[n + "_w"]).T + W(k[n + "_b"])).reshape(S, nh, dh).transpose(1, 0, 2)) for n in "qkv")
         s = q @ kk.transpose(0, 2, 1) / math.sqrt(dh)
-        if bias is not None:
-            s = s + bias
-        s = s - s.max(axis=-1, keepdims=True)
-        p = np.exp(s)
-        p = p / p.sum(axis=-1, keepdims=True)
-        ctx = (p @ v).transpose(1, 0, 2).reshape(S, H)
+        ctx = r(obert.attend(s, v, bias, operand).transpose(1, 0, 2).reshape(S, H))
         x = obert._ln(ctx @ W(k["o_w"]).T + W(k["o_b"]) + x, W(k["ln1_g"]), W(k["ln1_b"]), shape.eps)
         if shape.ffn == "geglu":
-            g = x @ W(k["gated_w"]).T
-            h = obert._gelu(g[:, :I]) * g[:, I:]
+            g = r(x) @ W(k["gated_w"]).T
+            h = r(obert._gelu(g[:, :I]) * g[:, I:])
         else:
-            h = obert._gelu(x @ W(k["i_w"]).T + W(k["i_b"]))
+            h = r(obert._gelu(r(x) @ W(k["i_w"]).T + W(k["i_b"])))
         x = obert._ln(h @ W(k["f_w"]).T + W(k["f_b"]) + x, W(k["ln2_g"]), W(k["ln2_b"]), shape.eps)
     return x
 

@@ -98,10 +98,14 @@ def _softmax_f32(s):
     return torch.nn.functional.softmax(torch.from_numpy(s), dim=-1, dtype=torch.float32).double().numpy()
 
 
-def encode_one(w: dict, shape: ModernShape, ids, tables=None, operand=None, library_f32: bool = False) -> np.ndarray:
+def encode_one(w: dict, shape: ModernShape, ids, tables=None, operand=None, library_f32: bool = False, bias=None,
+               bias_layer: int | None = None, round_p: bool = False) -> np.ndarray:
     """last_hidden_state [S, H] of one unpadded sequence, f64. tables: ((cos, sin) global, (cos, sin) windowed), each
     [>= S, d_h/2], in place of the exact ones. operand: as rope_oracle.encode_one. library_f32: the rotation and the
-    softmax rounded to f32 as transformers' eager path rounds them (see the module's docstring)."""
+    softmax rounded to f32 as transformers' eager path rounds them (see the module's docstring). bias: an additive
+    [heads, S, S] array on the logits of layer bias_layer (None: of every layer), beside the window's mask (a deliberate
+    mistake of tests/attention_case.py). round_p: with operand, the probabilities are rounded as well, as
+    oracle.bert.attend rounds them."""
     r = operand or (lambda v: v)  # noqa: E731
     W = lambda k: r(w[k].astype(np.float64))  # noqa: E731
     ids = np.asarray(ids, dtype=np.int64)
@@ -125,13 +129,17 @@ def encode_one(w: dict, shape: ModernShape, ids, tables=None, operand=None, libr
         s = q @ kk.transpose(0, 2, 1) * dh ** -0.5
         if not glob:
             s = np.where(outside[None], -np.inf, s)
+        b = bias if bias is not None and bias_layer in (None, i) else None
         if library_f32:
-            p = _softmax_f32(s)
+            ctx = _softmax_f32(s) @ v
+        elif b is not None or (round_p and operand is not None):
+            ctx = obert.attend(s, v, b, operand if round_p else None)
         else:
             s = s - s.max(axis=-1, keepdims=True)
             p = np.exp(s)
             p = p / p.sum(axis=-1, keepdims=True)
-        ctx = r((p @ v).transpose(1, 0, 2).reshape(S, H))
+            ctx = p @ v
+        ctx = r(ctx.transpose(1, 0, 2).reshape(S, H))
         h = h + ctx @ W(k["o_w"]).T + _bias(w, k["o_w"][:-6] + "bias")
         xm = r(_norm(h, w, k["mlp_norm"], shape.eps))
         ab = xm @ W(k["wi_w"]).T + _bias(w, k["wi_w"][:-6] + "bias")

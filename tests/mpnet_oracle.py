@@ -110,11 +110,13 @@ def offset_bias(table, S: int, mirrored: bool = False, clamp: int | None = None)
     return table[:, np.clip(d, -c, c) + R]
 
 
-def encode_one(w: dict, shape: MpnetShape, ids, table="buckets", bias=None) -> np.ndarray:
+def encode_one(w: dict, shape: MpnetShape, ids, table="buckets", bias=None, operand=None) -> np.ndarray:
     """last_hidden_state [S, H] of one unpadded sequence, f64. table: [heads, 2R + 1] offset table, "buckets" for the
     model's own (table_from_buckets of its relative_attention_bias), None for no bias. bias: a ready [heads, S, S]
-    array instead (offset_bias with a mistake built in)."""
-    W = lambda k: w[k].astype(np.float64)  # noqa: E731
+    array instead (offset_bias with a mistake built in). operand: as oracle.bert.encode_one's."""
+    r = operand or (lambda a: a)  # noqa: E731
+    product = lambda k: w[k].ndim == 2 and k.startswith("encoder.layer.")  # noqa: E731  (a projection matrix)
+    W = lambda k: r(w[k].astype(np.float64)) if product(k) else w[k].astype(np.float64)  # noqa: E731
     ids = np.asarray(ids, dtype=np.int64)
     S, H, nh = len(ids), shape.hidden, shape.heads
     dh = H // nh
@@ -124,16 +126,12 @@ def encode_one(w: dict, shape: MpnetShape, ids, table="buckets", bias=None) -> n
     x = obert._ln(x, W(EMB_KEYS["ln_g"]), W(EMB_KEYS["ln_b"]), shape.eps)
     for i in range(shape.layers):
         k = layer_keys(i)
-        q, kk, v = ((x @ W(k[n + "_w"]).T + W(k[n + "_b"])).reshape(S, nh, dh).transpose(1, 0, 2) for n in "qkv")
+        xa = r(x)
+        q, kk, v = (r((xa @ W(k[n + "_w"]).T + W(k[n + "_b"])).reshape(S, nh, dh).transpose(1, 0, 2)) for n in "qkv")
         s = q @ kk.transpose(0, 2, 1) / math.sqrt(dh)
-        if bias is not None:
-            s = s + bias
-        s = s - s.max(axis=-1, keepdims=True)
-        p = np.exp(s)
-        p = p / p.sum(axis=-1, keepdims=True)
-        ctx = (p @ v).transpose(1, 0, 2).reshape(S, H)
+        ctx = r(obert.attend(s, v, bias, operand).transpose(1, 0, 2).reshape(S, H))
         x = obert._ln(ctx @ W(k["o_w"]).T + W(k["o_b"]) + x, W(k["ln1_g"]), W(k["ln1_b"]), shape.eps)
-        h = obert._gelu(x @ W(k["i_w"]).T + W(k["i_b"]))
+        h = r(obert._gelu(r(x) @ W(k["i_w"]).T + W(k["i_b"])))
         x = obert._ln(h @ W(k["f_w"]).T + W(k["f_b"]) + x, W(k["ln2_g"]), W(k["ln2_b"]), shape.eps)
     return x
 

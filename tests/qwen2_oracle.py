@@ -84,9 +84,15 @@ def rope(x, theta):
     return x * np.cos(a) + rot * np.sin(a)
 
 
-def encode_one(w: dict, shape: Qwen2Shape, ids, causal: bool = True) -> np.ndarray:
-    """The final-norm hidden states [S, H] of one unpadded sequence, f64."""
-    W = lambda k: w[k].astype(np.float64)  # noqa: E731
+def encode_one(w: dict, shape: Qwen2Shape, ids, causal: bool = True, bias=None, operand=None) -> np.ndarray:
+    """The final-norm hidden states [S, H] of one unpadded sequence, f64. bias: an additive [heads, S, S] array on every
+    layer's logits, beside the causal mask (a deliberate mistake of tests/attention_case.py). operand (e.g.
+    rope_oracle.f16_operand): applied to both operands of every matrix product, the probabilities included (as
+    oracle.bert.attend rounds them)."""
+    from oracle.bert import attend
+
+    r = operand or (lambda a: a)  # noqa: E731
+    W = lambda k: r(w[k].astype(np.float64)) if k.endswith("_proj.weight") else w[k].astype(np.float64)  # noqa: E731
     ids = np.asarray(ids, dtype=np.int64)
     S, H, nh, nkv = len(ids), shape.hidden, shape.heads, shape.kv_heads
     dh, g = H // nh, nh // nkv
@@ -94,20 +100,17 @@ def encode_one(w: dict, shape: Qwen2Shape, ids, causal: bool = True) -> np.ndarr
     h = W(WORD_KEY)[ids]
     for i in range(shape.layers):
         k = layer_keys(i)
-        a = rms(h, W(k["ln_a"]), shape.eps)
+        a = r(rms(h, W(k["ln_a"]), shape.eps))
         q = (a @ W(k["q"]).T + W(k["qb"])).reshape(S, nh, dh).transpose(1, 0, 2)
         kk = (a @ W(k["k"]).T + W(k["kb"])).reshape(S, nkv, dh).transpose(1, 0, 2)
-        v = (a @ W(k["v"]).T + W(k["vb"])).reshape(S, nkv, dh).transpose(1, 0, 2)
+        v = r((a @ W(k["v"]).T + W(k["vb"])).reshape(S, nkv, dh).transpose(1, 0, 2))
         kk, v = np.repeat(kk, g, axis=0), np.repeat(v, g, axis=0)  # repeat_kv: query head j reads KV head j // g
-        s = rope(q, shape.theta) @ rope(kk, shape.theta).transpose(0, 2, 1) / np.sqrt(dh)
+        s = r(rope(q, shape.theta)) @ r(rope(kk, shape.theta)).transpose(0, 2, 1) / np.sqrt(dh)
         s = np.where(masked, -np.inf, s)
-        s = s - s.max(axis=-1, keepdims=True)
-        p = np.exp(s)
-        p = p / p.sum(axis=-1, keepdims=True)
-        h = h + (p @ v).transpose(1, 0, 2).reshape(S, H) @ W(k["o"]).T
-        m = rms(h, W(k["ln_m"]), shape.eps)
+        h = h + r(attend(s, v, bias, operand).transpose(1, 0, 2).reshape(S, H)) @ W(k["o"]).T
+        m = r(rms(h, W(k["ln_m"]), shape.eps))
         gate = m @ W(k["gate"]).T
-        h = h + (gate / (1.0 + np.exp(-gate)) * (m @ W(k["up"]).T)) @ W(k["down"]).T
+        h = h + r(gate / (1.0 + np.exp(-gate)) * (m @ W(k["up"]).T)) @ W(k["down"]).T
     return rms(h, W(FINAL_KEY), shape.eps)
 
 
