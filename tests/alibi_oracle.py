@@ -89,9 +89,14 @@ def distance_bias(slopes, S: int, clamp: int | None = None) -> np.ndarray:
     return -np.asarray(slopes, np.float64)[:, None, None] * d[None]
 
 
-def encode_one(w: dict, shape: AlibiShape, ids, slopes, bias=None, operand=None) -> np.ndarray:
+def encode_one(w: dict, shape: AlibiShape, ids, slopes, bias=None, operand=None, hooks=None) -> np.ndarray:
     """last_hidden_state [S, H] of one unpadded sequence, f64. slopes: [heads], or None for no bias. bias: a ready
-    [heads, S, S] array instead (distance_bias with a mistake built in). operand: as oracle.bert.encode_one's."""
+    [heads, S, S] array instead (distance_bias with a mistake built in). operand: as oracle.bert.encode_one's. hooks:
+    deliberate mistakes of tests/encoder_family_rows_case.py, a dict of "glu" f(gate, up, layer) in place of
+    gelu(gate) * up and "stale_residual" (the FFN's residual taken from before the attention block's LayerNorm); without
+    it nothing changes."""
+    hk = hooks or {}
+    glu = hk["glu"] if "glu" in hk else (lambda gate, up, layer: obert._gelu(gate) * up)  # noqa: E731
     r = operand or (lambda a: a)  # noqa: E731
     product = lambda k: w[k].ndim == 2 and k.startswith("encoder.layer.")  # noqa: E731  (a projection matrix)
     W = lambda k: r(w[k].astype(np.float64)) if product(k) else w[k].astype(np.float64)  # noqa: E731
@@ -107,13 +112,15 @@ def encode_one(w: dict, shape: AlibiShape, ids, slopes, bias=None, operand=None)
         q, kk, v = (r((xa @ W(k[n + "_w"]).T + W(k[n + "_b"])).reshape(S, nh, dh).transpose(1, 0, 2)) for n in "qkv")
         s = q @ kk.transpose(0, 2, 1) / math.sqrt(dh)
         ctx = r(obert.attend(s, v, bias, operand).transpose(1, 0, 2).reshape(S, H))
+        before = x
         x = obert._ln(ctx @ W(k["o_w"]).T + W(k["o_b"]) + x, W(k["ln1_g"]), W(k["ln1_b"]), shape.eps)
         if shape.ffn == "geglu":
             g = r(x) @ W(k["gated_w"]).T
-            h = r(obert._gelu(g[:, :I]) * g[:, I:])
+            h = r(glu(g[:, :I], g[:, I:], i))
         else:
             h = r(obert._gelu(r(x) @ W(k["i_w"]).T + W(k["i_b"])))
-        x = obert._ln(h @ W(k["f_w"]).T + W(k["f_b"]) + x, W(k["ln2_g"]), W(k["ln2_b"]), shape.eps)
+        x = obert._ln(h @ W(k["f_w"]).T + W(k["f_b"]) + (before if hk.get("stale_residual") else x), W(k["ln2_g"]),
+                      W(k["ln2_b"]), shape.eps)
     return x
 
 

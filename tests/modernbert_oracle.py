@@ -99,13 +99,18 @@ def _softmax_f32(s):
 
 
 def encode_one(w: dict, shape: ModernShape, ids, tables=None, operand=None, library_f32: bool = False, bias=None,
-               bias_layer: int | None = None, round_p: bool = False) -> np.ndarray:
+               bias_layer: int | None = None, round_p: bool = False, hooks=None) -> np.ndarray:
     """last_hidden_state [S, H] of one unpadded sequence, f64. tables: ((cos, sin) global, (cos, sin) windowed), each
     [>= S, d_h/2], in place of the exact ones. operand: as rope_oracle.encode_one. library_f32: the rotation and the
     softmax rounded to f32 as transformers' eager path rounds them (see the module's docstring). bias: an additive
     [heads, S, S] array on the logits of layer bias_layer (None: of every layer), beside the window's mask (a deliberate
     mistake of tests/attention_case.py). round_p: with operand, the probabilities are rounded as well, as
-    oracle.bert.attend rounds them."""
+    oracle.bert.attend rounds them. hooks: deliberate mistakes of tests/encoder_family_rows_case.py, a dict of "rotate"
+    f(x [heads, S, d_h], "q" | "k", layer) in place of the rotation, "glu" f(gate, up, layer) in place of
+    gelu(gate) * up, "stale_residual" (the FFN's residual taken from before the attention block) and "skip_final";
+    without it nothing changes."""
+    hk = hooks or {}
+    glu = hk["glu"] if "glu" in hk else (lambda gate, up, layer: obert._gelu(gate) * up)  # noqa: E731
     r = operand or (lambda v: v)  # noqa: E731
     W = lambda k: r(w[k].astype(np.float64))  # noqa: E731
     ids = np.asarray(ids, dtype=np.int64)
@@ -125,7 +130,10 @@ def encode_one(w: dict, shape: ModernShape, ids, tables=None, operand=None, libr
         qkv = xa @ W(k["qkv_w"]).T + _bias(w, k["qkv_w"][:-6] + "bias")
         q, kk, v = (qkv[:, j * H:(j + 1) * H].reshape(S, nh, dh).transpose(1, 0, 2) for j in range(3))
         rot = _rotate_f32 if library_f32 else _rotate
-        q, kk, v = r(rot(q, cos, sin)), r(rot(kk, cos, sin)), r(v)
+        if "rotate" in hk:
+            q, kk, v = r(hk["rotate"](q, "q", i)), r(hk["rotate"](kk, "k", i)), r(v)
+        else:
+            q, kk, v = r(rot(q, cos, sin)), r(rot(kk, cos, sin)), r(v)
         s = q @ kk.transpose(0, 2, 1) * dh ** -0.5
         if not glob:
             s = np.where(outside[None], -np.inf, s)
@@ -140,12 +148,13 @@ def encode_one(w: dict, shape: ModernShape, ids, tables=None, operand=None, libr
             p = p / p.sum(axis=-1, keepdims=True)
             ctx = p @ v
         ctx = r(ctx.transpose(1, 0, 2).reshape(S, H))
+        before = h
         h = h + ctx @ W(k["o_w"]).T + _bias(w, k["o_w"][:-6] + "bias")
         xm = r(_norm(h, w, k["mlp_norm"], shape.eps))
         ab = xm @ W(k["wi_w"]).T + _bias(w, k["wi_w"][:-6] + "bias")
-        act = r(obert._gelu(ab[:, :I]) * ab[:, I:])
-        h = h + act @ W(k["wo_w"]).T + _bias(w, k["wo_w"][:-6] + "bias")
-    return _norm(h, w, "final_norm.weight", shape.eps)
+        act = r(glu(ab[:, :I], ab[:, I:], i))
+        h = (before if hk.get("stale_residual") else h) + act @ W(k["wo_w"]).T + _bias(w, k["wo_w"][:-6] + "bias")
+    return h if hk.get("skip_final") else _norm(h, w, "final_norm.weight", shape.eps)
 
 
 def pool(h, pooling: str, normalize: bool = True):

@@ -84,13 +84,20 @@ def rope(x, theta):
     return x * np.cos(a) + rot * np.sin(a)
 
 
-def encode_one(w: dict, shape: Qwen2Shape, ids, causal: bool = True, bias=None, operand=None) -> np.ndarray:
+def encode_one(w: dict, shape: Qwen2Shape, ids, causal: bool = True, bias=None, operand=None, hooks=None) -> np.ndarray:
     """The final-norm hidden states [S, H] of one unpadded sequence, f64. bias: an additive [heads, S, S] array on every
     layer's logits, beside the causal mask (a deliberate mistake of tests/attention_case.py). operand (e.g.
     rope_oracle.f16_operand): applied to both operands of every matrix product, the probabilities included (as
-    oracle.bert.attend rounds them)."""
+    oracle.bert.attend rounds them). hooks: deliberate mistakes of tests/encoder_family_rows_case.py, a dict of
+    "rotate" f(x [heads, S, d_h], "q" | "k", layer) in place of rope, "glu" f(gate, up, layer) in place of
+    silu(gate) * up, "rms" in place of rms, "kv_of" (the KV head of every query head), "stale_residual" (the FFN's
+    residual taken from before the attention block) and "skip_final"; without it nothing changes."""
     from oracle.bert import attend
 
+    hk = hooks or {}
+    norm = hk.get("rms", rms)
+    rot = hk["rotate"] if "rotate" in hk else (lambda x, kind, layer: rope(x, shape.theta))  # noqa: E731
+    glu = hk["glu"] if "glu" in hk else (lambda gate, up, layer: gate / (1.0 + np.exp(-gate)) * up)  # noqa: E731
     r = operand or (lambda a: a)  # noqa: E731
     W = lambda k: r(w[k].astype(np.float64)) if k.endswith("_proj.weight") else w[k].astype(np.float64)  # noqa: E731
     ids = np.asarray(ids, dtype=np.int64)
@@ -100,18 +107,22 @@ def encode_one(w: dict, shape: Qwen2Shape, ids, causal: bool = True, bias=None, 
     h = W(WORD_KEY)[ids]
     for i in range(shape.layers):
         k = layer_keys(i)
-        a = r(rms(h, W(k["ln_a"]), shape.eps))
+        a = r(norm(h, W(k["ln_a"]), shape.eps))
         q = (a @ W(k["q"]).T + W(k["qb"])).reshape(S, nh, dh).transpose(1, 0, 2)
         kk = (a @ W(k["k"]).T + W(k["kb"])).reshape(S, nkv, dh).transpose(1, 0, 2)
         v = r((a @ W(k["v"]).T + W(k["vb"])).reshape(S, nkv, dh).transpose(1, 0, 2))
-        kk, v = np.repeat(kk, g, axis=0), np.repeat(v, g, axis=0)  # repeat_kv: query head j reads KV head j // g
-        s = r(rope(q, shape.theta)) @ r(rope(kk, shape.theta)).transpose(0, 2, 1) / np.sqrt(dh)
+        if "kv_of" in hk:
+            kk, v = kk[hk["kv_of"]], v[hk["kv_of"]]
+        else:
+            kk, v = np.repeat(kk, g, axis=0), np.repeat(v, g, axis=0)  # repeat_kv: query head j reads KV head j // g
+        s = r(rot(q, "q", i)) @ r(rot(kk, "k", i)).transpose(0, 2, 1) / np.sqrt(dh)
         s = np.where(masked, -np.inf, s)
+        before = h
         h = h + r(attend(s, v, bias, operand).transpose(1, 0, 2).reshape(S, H)) @ W(k["o"]).T
-        m = r(rms(h, W(k["ln_m"]), shape.eps))
+        m = r(norm(h, W(k["ln_m"]), shape.eps))
         gate = m @ W(k["gate"]).T
-        h = h + r(gate / (1.0 + np.exp(-gate)) * (m @ W(k["up"]).T)) @ W(k["down"]).T
-    return rms(h, W(FINAL_KEY), shape.eps)
+        h = (before if hk.get("stale_residual") else h) + r(glu(gate, m @ W(k["up"]).T, i)) @ W(k["down"]).T
+    return h if hk.get("skip_final") else norm(h, W(FINAL_KEY), shape.eps)
 
 
 def pool(hidden, pooling: str, normalize: bool = True):

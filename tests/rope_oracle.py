@@ -117,11 +117,17 @@ def f16_operand(x):
     return np.asarray(x).astype(np.float16).astype(np.float64)
 
 
-def encode_one(w: dict, shape: RopeShape, ids, table=None, operand=None) -> np.ndarray:
+def encode_one(w: dict, shape: RopeShape, ids, table=None, operand=None, hooks=None) -> np.ndarray:
     """last_hidden_state [S, H] of one unpadded sequence, f64. table: (cos, sin) [>= S, d_h/2] to use instead of
     rope_table's. operand (e.g. f16_operand): applied to both operands of every matrix product (weights, hidden state,
     rotated q / k, v, context, gated activation) while everything else stays f64 — the best an engine whose products
-    read f16 operands can do."""
+    read f16 operands can do. hooks: deliberate mistakes of tests/encoder_family_rows_case.py, a dict of "rotate"
+    f(x [heads, S, d_h], "q" | "k", layer) in place of the rotation, "glu" f(gate, up, layer) in place of
+    act(gate) * up, and "stale_residual" (the FFN's residual taken from before the attention block's LayerNorm); without
+    it nothing changes."""
+    hk = hooks or {}
+    rot = hk["rotate"] if "rotate" in hk else (lambda t, kind, layer: _rotate(t, cos, sin))  # noqa: E731
+    glu = hk["glu"] if "glu" in hk else (lambda gate, up, layer: _act(gate, shape.act) * up)  # noqa: E731
     r = operand or (lambda v: v)  # noqa: E731
     W = lambda k: r(w[k].astype(np.float64))  # noqa: E731  (a projection matrix)
     P = lambda k: w[k].astype(np.float64)  # noqa: E731  (embeddings, LayerNorm parameters: no product reads them)
@@ -134,18 +140,19 @@ def encode_one(w: dict, shape: RopeShape, ids, table=None, operand=None) -> np.n
     for i in range(shape.layers):
         k = layer_keys(i)
         xa = r(x)
-        q = r(_rotate((xa @ W(k["q_w"]).T).reshape(S, nh, dh).transpose(1, 0, 2), cos, sin))
-        kk = r(_rotate((xa @ W(k["k_w"]).T).reshape(S, nh, dh).transpose(1, 0, 2), cos, sin))
+        q = r(rot((xa @ W(k["q_w"]).T).reshape(S, nh, dh).transpose(1, 0, 2), "q", i))
+        kk = r(rot((xa @ W(k["k_w"]).T).reshape(S, nh, dh).transpose(1, 0, 2), "k", i))
         v = r((xa @ W(k["v_w"]).T).reshape(S, nh, dh).transpose(1, 0, 2))
         s = q @ kk.transpose(0, 2, 1) / math.sqrt(dh)
         s = s - s.max(axis=-1, keepdims=True)
         p = np.exp(s)
         p = p / p.sum(axis=-1, keepdims=True)
         ctx = r((p @ v).transpose(1, 0, 2).reshape(S, H))
+        before = x
         x = obert._ln(ctx @ W(k["o_w"]).T + x, P(k["ln1_g"]), P(k["ln1_b"]), shape.eps)
         xa = r(x)
-        h = r(_act(xa @ W(k["gate_w"]).T, shape.act) * (xa @ W(k["up_w"]).T))
-        x = obert._ln(h @ W(k["down_w"]).T + x, P(k["ln2_g"]), P(k["ln2_b"]), shape.eps)
+        h = r(glu(xa @ W(k["gate_w"]).T, xa @ W(k["up_w"]).T, i))
+        x = obert._ln(h @ W(k["down_w"]).T + (before if hk.get("stale_residual") else x), P(k["ln2_g"]), P(k["ln2_b"]), shape.eps)
     return x
 
 

@@ -85,10 +85,19 @@ def rms(x, g, eps):
     return x / np.sqrt((x * x).mean(axis=-1, keepdims=True) + eps) * g
 
 
-def encode_one(w: dict, shape: T5Shape, ids, table="buckets") -> np.ndarray:
+def encode_one(w: dict, shape: T5Shape, ids, table="buckets", operand=None, hooks=None) -> np.ndarray:
     """The final-norm hidden states [S, H] of one unpadded sequence, f64. table: an [heads, 2R + 1] offset table,
-    "buckets" for the model's own, None for no bias."""
-    W = lambda k: w[k].astype(np.float64)  # noqa: E731
+    "buckets" for the model's own, None for no bias. operand (e.g. rope_oracle.f16_operand): applied to both operands of
+    every matrix product, the probabilities included (as oracle.bert.attend rounds them). hooks: deliberate mistakes of
+    tests/encoder_family_rows_case.py, a dict of "act" f(x, layer) in place of relu, "rms" in place of rms,
+    "stale_residual" (the FFN's residual taken from before the attention block) and "skip_final"; without it nothing
+    changes."""
+    hk = hooks or {}
+    norm = hk.get("rms", rms)
+    act = hk["act"] if "act" in hk else (lambda x, layer: np.maximum(x, 0.0))  # noqa: E731
+    r = operand or (lambda a: a)  # noqa: E731
+    product = lambda k: w[k].ndim == 2 and k != BIAS_KEY and k != WORD_KEY  # noqa: E731  (a projection matrix)
+    W = lambda k: r(w[k].astype(np.float64)) if product(k) else w[k].astype(np.float64)  # noqa: E731
     ids = np.asarray(ids, dtype=np.int64)
     S, H, nh = len(ids), shape.hidden, shape.heads
     dh = H // nh
@@ -98,17 +107,19 @@ def encode_one(w: dict, shape: T5Shape, ids, table="buckets") -> np.ndarray:
     h = W(WORD_KEY)[ids]
     for i in range(shape.layers):
         k = layer_keys(i)
-        a = rms(h, W(k["ln_a"]), shape.eps)
-        q, kk, v = ((a @ W(k[n]).T).reshape(S, nh, dh).transpose(1, 0, 2) for n in "qkv")
+        a = r(norm(h, W(k["ln_a"]), shape.eps))
+        q, kk, v = (r((a @ W(k[n]).T).reshape(S, nh, dh).transpose(1, 0, 2)) for n in "qkv")
         s = q @ kk.transpose(0, 2, 1)  # no 1/sqrt(d_kv)
         if bias is not None:
             s = s + bias
         s = s - s.max(axis=-1, keepdims=True)
         p = np.exp(s)
         p = p / p.sum(axis=-1, keepdims=True)
-        h = h + (p @ v).transpose(1, 0, 2).reshape(S, H) @ W(k["o"]).T
-        h = h + np.maximum(rms(h, W(k["ln_m"]), shape.eps) @ W(k["wi"]).T, 0.0) @ W(k["wo"]).T
-    return rms(h, W(FINAL_KEY), shape.eps)
+        before = h
+        h = h + r((r(p) @ v).transpose(1, 0, 2).reshape(S, H)) @ W(k["o"]).T
+        m = r(norm(h, W(k["ln_m"]), shape.eps))
+        h = (before if hk.get("stale_residual") else h) + r(act(m @ W(k["wi"]).T, i)) @ W(k["wo"]).T
+    return h if hk.get("skip_final") else norm(h, W(FINAL_KEY), shape.eps)
 
 
 def sentence_embeddings(w: dict, shape: T5Shape, seqs, pooling: str = "mean", table="buckets", normalize: bool = True):
