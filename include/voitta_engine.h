@@ -303,6 +303,36 @@ int vr_encode_spans(vr_engine* e, const int32_t* ids, const int32_t* offsets, in
                     const int32_t* span_off, const int32_t* span_tok, int mem,
                     float* out, int out_mem);
 
+/* Semantic chunking: chunk boundaries AND the late-chunked vectors of the resulting chunks from one forward pass.
+ * A sequence carries m >= 0 UNITS (sentence-sized token spans), given as vr_encode_spans gives spans (unit_off, unit_tok)
+ * but in order and never overlapping: 0 <= begin_r < end_r <= len and begin_{r+1} >= end_r; at most 2048 per sequence.
+ * Tokens of no unit only provide context. Per sequence, x_t the final hidden row of token t (vr_encode_spans' rows):
+ *   1. S_r = sum of x_t over unit r, f32, token order; n_r = end_r - begin_r
+ *   2. C_r = sum of S_j, j = max(0, r - buffer) .. min(m - 1, r + buffer), unit order
+ *   3. d_r = 1 - (C_r . C_{r+1}) / max(|C_r| |C_{r+1}|, 1e-12), r = 0 .. m - 2, every sum in a fixed order
+ *   4. B = ceil(break_permille (m - 1) / 1000) in integers; rank(r) = the gaps r' with d_r' > d_r, or d_r' == d_r and
+ *      r' < r (f32 compares on the stored values); gap r is a CANDIDATE iff rank(r) < B and d_r >= min_distance
+ *   5. the walk, left to right, acc = n_0: the chunk is closed behind unit r iff (candidate(r) and acc >= min_tokens)
+ *      or acc + n_{r+1} > max_tokens; then acc = n_{r+1}, otherwise acc += n_{r+1}. (A unit above max_tokens is a chunk
+ *      of its own; a sequence's last chunk may be below min_tokens; a chunk never crosses a sequence.)
+ *   6. a chunk's row: (sum of S_r over its units, unit order) / (sum of n_r), finished as vr_encode_spans finishes a span
+ *      mean (head stages, normalize, truncate_dim) — a chunk of one unit is that span's row bit for bit.
+ * params: buffer 0..3, break_permille 0..1000, 0 <= min_tokens <= max_tokens, max_tokens >= 1, min_distance any number
+ * (above 2 no gap is a candidate). ids / offsets / unit_off / unit_tok in `mem`; the three output arrays in `out_mem`:
+ *   out_unit_start  one int32 per unit: 1 where the unit begins a chunk
+ *   out_gap_dist    one f32 per unit: d_r, and 0 for a sequence's last unit
+ *   out_rows        *n_chunks x W f32 in chunk order (sequence by sequence); capacity: one row per unit
+ *   n_chunks        host memory always; the call returns with the stream drained
+ * Host arrays and params are checked before any work is queued; vr_last_error names the offending sequence and unit, and
+ * a refused call leaves the engine as it was. No units, or n_seq <= 0: returns 0 with *n_chunks = 0, writes nothing else. */
+typedef struct vr_semantic_params {
+  int32_t struct_size, buffer, break_permille, min_tokens, max_tokens;
+  float min_distance;
+} vr_semantic_params;
+int vr_encode_semantic(vr_engine* e, const int32_t* ids, const int32_t* offsets, int32_t n_seq,
+                       const int32_t* unit_off, const int32_t* unit_tok, int mem, const vr_semantic_params* params,
+                       float* out_rows, int32_t* out_unit_start, float* out_gap_dist, int32_t* n_chunks, int out_mem);
+
 /* Host-only WordPiece tokenizer (no engine, no GPU): the tokenise step of SentenceTransformer.encode
  * (embedding.py:40,68-73 -> [EXT] HF tokenizers: BertNormalizer, BertPreTokenizer, WordPiece,
  * "[CLS] $A [SEP]", right truncation — SURVEY.md §8 a4 step 2), producing the ids / offsets vr_encode

@@ -86,6 +86,17 @@ class VrHeadStage(C.Structure):
     ]
 
 
+class VrSemanticParams(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("buffer", C.c_int32),
+        ("break_permille", C.c_int32),
+        ("min_tokens", C.c_int32),
+        ("max_tokens", C.c_int32),
+        ("min_distance", C.c_float),
+    ]
+
+
 VR_HEAD_DENSE = 0
 VR_HEAD_LAYERNORM = 1
 VR_ACT_IDENTITY = 0
@@ -135,6 +146,8 @@ SIGNATURES = {
     "vr_encoder_set_head": (C.c_int, [_vp, C.POINTER(VrHeadStage), C.c_int32, C.c_int32, C.c_int]),
     "vr_encode": (C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_int, _vp, C.c_int]),
     "vr_encode_spans": (C.c_int, [_vp, _vp, _vp, C.c_int32, _vp, _vp, C.c_int, _vp, C.c_int]),
+    "vr_encode_semantic": (C.c_int, [_vp, _vp, _vp, C.c_int32, _vp, _vp, C.c_int, C.POINTER(VrSemanticParams), _vp, _vp, _vp,
+                                     _i32p, C.c_int]),
     "vr_wordpiece_create": (C.c_int, [C.POINTER(C.c_char_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                      C.POINTER(_vp)]),
     "vr_wordpiece_create_specials": (C.c_int, [C.POINTER(C.c_char_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,

@@ -4,7 +4,9 @@ in front of the indexing path (services/indexing.py:380,515; SURVEY.md §8 row f
 as it does there). The splitting runs in the native library (vr_chunk_texts, csrc/chunking.cpp), one
 document per host thread; ``chunk_texts`` is the batched form the indexer uses to cut a whole folder
 at once. Parity unpinned: see csrc/chunking.cpp. With VOITTA_LATE_CHUNKING=1 the chunk texts are
-``LateChunkText``: plain strings that also carry their document, which is how ``embed_texts`` finds it."""
+``LateChunkText``: plain strings that also carry their document, which is how ``embed_texts`` finds it. With
+VOITTA_SEMANTIC_CHUNKING=1 the chunks are the encoder's (EmbeddingService.chunk_and_embed_documents) and their texts
+``SemanticChunkText``: plain strings that also carry their vectors."""
 from __future__ import annotations
 
 import ctypes as C
@@ -42,6 +44,16 @@ class ChunkingService:
         return self.chunk_texts([text])[0]
 
     def chunk_texts(self, texts: list[str]) -> list[list[Chunk]]:
+        if get_settings().semantic_chunking:
+            # semantic chunking (VOITTA_SEMANTIC_CHUNKING=1): the boundaries come from the encoder's forward pass, and so
+            # do the chunks' vectors — the texts carry them (SemanticChunkText), which is how embed_texts finds them
+            from .embedding import get_embedding_service
+
+            return [chunks for chunks, _ in get_embedding_service().chunk_and_embed_documents(texts, chunker=self)]
+        return self.cut(texts)
+
+    def cut(self, texts: list[str]) -> list[list[Chunk]]:
+        """The native chunker alone (vr_chunk_texts) at this service's size, overlap and strategy."""
         n = len(texts)
         if n == 0:
             return []

@@ -11,6 +11,9 @@ from functools import lru_cache
 DEFAULT_MAX_SEQ_LENGTH = 512
 MAX_SEQ_LENGTH_LIMIT = 8192  # the longest sequence the engine loads a model for (vr_encoder_load / vr_reranker_load)
 DEFAULT_LATE_CHUNKING_CONTEXT = 256
+DEFAULT_SEMANTIC_UNIT_CHARS = 200   # a sentence or two
+DEFAULT_SEMANTIC_MIN_TOKENS = 32
+DEFAULT_SEMANTIC_MAX_TOKENS = 256
 
 
 class Settings:
@@ -71,6 +74,44 @@ class Settings:
             raise ValueError(f"VOITTA_LATE_CHUNKING_CONTEXT={self.late_chunking_context}: accepted values are 0 ... "
                              f"{self.max_seq_length // 2} (half of VOITTA_MAX_SEQ_LENGTH={self.max_seq_length}; default "
                              f"{DEFAULT_LATE_CHUNKING_CONTEXT})")
+        # semantic chunking (opt-in): a file is cut into sentence-sized units (the `sentence` strategy at
+        # VOITTA_SEMANTIC_UNIT_CHARS characters), goes through the encoder once as late chunking sends it, and the device
+        # breaks where neighbouring units stop resembling each other: at the break_permille/1000 largest distances of a
+        # sequence that are at least min_distance, a chunk holding min_tokens ... max_tokens tokens (vr_encode_semantic).
+        # The chunks come back with their late-chunked vectors. Defaults: the 95th percentile, one unit of buffer
+        semantic = os.getenv("VOITTA_SEMANTIC_CHUNKING", "0").strip() or "0"
+        if semantic not in ("0", "1"):
+            raise ValueError(f"VOITTA_SEMANTIC_CHUNKING={semantic}: accepted values are 0 and 1 (default 0)")
+        self.semantic_chunking: bool = semantic == "1"
+        if self.semantic_chunking and self.late_chunking:
+            raise ValueError("VOITTA_SEMANTIC_CHUNKING=1 together with VOITTA_LATE_CHUNKING=1: semantic chunks are "
+                             "late-chunked already, set one of the two")
+
+        def ranged(name: str, default: int, lo: int, hi: int, note: str = "") -> int:
+            raw = os.getenv(name, str(default)).strip() or str(default)
+            try:
+                value = int(raw)
+            except ValueError:
+                value = lo - 1
+            if not lo <= value <= hi:
+                raise ValueError(f"{name}={raw}: accepted values are {lo} ... {hi}{note} (default {default})")
+            return value
+
+        self.semantic_unit_chars: int = ranged("VOITTA_SEMANTIC_UNIT_CHARS", DEFAULT_SEMANTIC_UNIT_CHARS, 16, 65536)
+        self.semantic_buffer: int = ranged("VOITTA_SEMANTIC_BUFFER", 1, 0, 3)
+        self.semantic_break_permille: int = ranged("VOITTA_SEMANTIC_BREAK_PERMILLE", 50, 0, 1000)
+        self.semantic_max_tokens: int = ranged("VOITTA_SEMANTIC_MAX_TOKENS", min(DEFAULT_SEMANTIC_MAX_TOKENS, self.max_seq_length),
+                                               1, self.max_seq_length, f" (VOITTA_MAX_SEQ_LENGTH={self.max_seq_length})")
+        self.semantic_min_tokens: int = ranged("VOITTA_SEMANTIC_MIN_TOKENS", min(DEFAULT_SEMANTIC_MIN_TOKENS, self.semantic_max_tokens),
+                                               0, self.semantic_max_tokens,
+                                               f" (VOITTA_SEMANTIC_MAX_TOKENS={self.semantic_max_tokens})")
+        raw = os.getenv("VOITTA_SEMANTIC_MIN_DISTANCE", "0").strip() or "0"
+        try:
+            self.semantic_min_distance: float = float(raw)
+        except ValueError:
+            self.semantic_min_distance = float("nan")
+        if not 0.0 <= self.semantic_min_distance <= 2.0:
+            raise ValueError(f"VOITTA_SEMANTIC_MIN_DISTANCE={raw}: accepted values are 0 ... 2, a cosine distance (default 0)")
 
 
 @lru_cache

@@ -218,6 +218,21 @@ int vr_encode_spans(vr_engine* e, const int32_t* ids, const int32_t* offsets, in
   return encoder_encode_spans(e, ids, offsets, n_seq, span_off, span_tok, mem, -1, out, out_mem);
 }
 
+int vr_encode_semantic(vr_engine* e, const int32_t* ids, const int32_t* offsets, int32_t n_seq, const int32_t* unit_off,
+                       const int32_t* unit_tok, int mem, const vr_semantic_params* params, float* out_rows,
+                       int32_t* out_unit_start, float* out_gap_dist, int32_t* n_chunks, int out_mem) {
+  VR_TRY(check_engine(e));
+  VR_CHECK(n_chunks != nullptr, "null n_chunks");
+  *n_chunks = 0;
+  if (n_seq <= 0) return 0;
+  VR_CHECK(ids && offsets && unit_off && params, "bad arguments");
+  VR_CHECK((mem == VR_MEM_HOST || mem == VR_MEM_DEVICE) && (out_mem == VR_MEM_HOST || out_mem == VR_MEM_DEVICE),
+           "bad mem");
+  std::lock_guard<std::mutex> writer(e->wmu);
+  return encoder_encode_semantic(e, ids, offsets, n_seq, unit_off, unit_tok, mem, params, out_rows, out_unit_start,
+                                 out_gap_dist, n_chunks, out_mem);
+}
+
 int vr_reranker_load(vr_engine* e, const vr_bert_desc* desc, const void* const* tensors, int32_t n_tensors, int mem) {
   VR_TRY(check_engine(e));
   VR_CHECK(desc && tensors, "null argument");

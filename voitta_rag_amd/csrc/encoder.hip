@@ -18,6 +18,8 @@
 //   rerank_head_kernel cross-encoder head on the pooled [CLS] rows   one f32 logit per pair (encoder_rerank)
 //   rerank_head_ln_kernel the head of a pre-norm cross-encoder: dense, GELU, LayerNorm, classifier (encoder_rerank)
 //   embed_head_kernel the embedder's post-pooling head: Dense / LayerNorm stages, normalise, truncate (vr_encoder_set_head)
+//   unit_sum_kernel, unit_gap_kernel, unit_boundary_kernel, chunk_base_kernel, chunk_row_kernel, chunk_gather_kernel
+//                     semantic chunking (vr_encode_semantic): unit sums, gap distances, boundaries, chunk rows (launch_semantic)
 //   rope_kernel       rotary positions, in place on Q and K            HBM bound (VR_POS_ROTARY models only)
 //   glu_kernel        act(gate) * up of a gated FFN                    HBM bound (VR_FFN_SWIGLU / VR_FFN_GEGLU only)
 //   embed_rms_kernel, rmsnorm_kernel, rmsnorm_f16_kernel  the embedding gather and the norms of an RMSNorm pre-norm
@@ -116,6 +118,11 @@ struct Encoder {
   // sequence index (built on the host from span_off; its host copy lives here until the upload has run)
   DevArray<int32_t> span_tok, span_seq;
   std::vector<int32_t> span_seq_host;
+  // a semantic call (encoder_encode_semantic): unit_off on the device, the unit sums S_r [units, H], per unit its gap
+  // distance, chunk-start flag and chunk index inside its sequence (-1: no start), per sequence its chunk count and
+  // first chunk row, the running chunk counter, and (a head with stages) the head's rows before they are compacted
+  DevArray<int32_t> sem_off, sem_start, sem_idx, sem_seq_chunks, sem_seq_base, sem_counter;
+  DevArray<float> sem_sums, sem_dist, sem_rows;
   DevArray<float> out;
   // a cross-encoder (the reranker slot): pooler dense [H,H] + bias, classifier [1,H] + bias; the pooled [CLS] rows
   // (a pre-norm one, ModernBertForSequenceClassification: pool_w / pool_b are its head.dense, head_ln_g / head_ln_b its
@@ -665,6 +672,226 @@ __global__ __launch_bounds__(256) void span_pool_kernel(const float* __restrict_
     int c = threadIdx.x + 256 * j;
     if (c < ocols) out[static_cast<int64_t>(sp) * ostride + c] = vals[j] / den;
   }
+}
+
+// ---- semantic chunking (vr_encode_semantic) --------------------------------------------------
+// The stage between "unit sums" and "chunk rows" of a forward chunk, five launches in stream order; a unit is a span
+// of vr_encode_spans (unit_tok, unit_seq as span_pool_kernel's), unit_off[seq] .. unit_off[seq + 1] a sequence's units.
+// Every sum runs in one fixed order and nothing is decided by an atomic: same input, same bits, whatever the batch.
+struct SemanticParams {
+  int buffer, break_permille, min_tokens, max_tokens;
+  float min_distance;
+};
+constexpr int kMaxSemUnits = 2048;  // units of one sequence: unit_boundary_kernel holds their distances in LDS
+
+// one block per unit: S_r, span_pool_kernel's token-order sum without the divide, kept as [unit][H]
+__global__ __launch_bounds__(256) void unit_sum_kernel(const float* __restrict__ x, const int32_t* __restrict__ cu,
+                                                       const int32_t* __restrict__ unit_tok,
+                                                       const int32_t* __restrict__ unit_seq, int unit0, int tok_base,
+                                                       int H, float* __restrict__ sums) {
+  const int u = unit0 + blockIdx.x;
+  const int begin = unit_tok[2 * u];
+  const int len = unit_tok[2 * u + 1] - begin;
+  const int t0 = cu[unit_seq[u]] - tok_base + begin;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int c = threadIdx.x + 256 * j;
+    if (c < H) {
+      float acc = 0.0f;
+      for (int t = 0; t < len; ++t) acc += x[static_cast<int64_t>(t0 + t) * H + c];
+      sums[static_cast<int64_t>(u) * H + c] = acc;
+    }
+  }
+}
+
+// one block per unit r: the distance of the gap behind it, d_r = 1 - C_r . C_{r+1} / max(|C_r| |C_{r+1}|, 1e-12) with
+// C_r the sum of S_j over the units j within `buffer` of r inside the sequence, in unit order; 0 for a sequence's last
+// unit. The three sums over the columns: per thread over its columns, a xor butterfly in the wave, the four waves in order.
+__global__ __launch_bounds__(256) void unit_gap_kernel(const float* __restrict__ sums, const int32_t* __restrict__ unit_off,
+                                                       const int32_t* __restrict__ unit_seq, int unit0, int H, int buffer,
+                                                       float* __restrict__ dist) {
+  __shared__ float red[3][4];
+  const int u = unit0 + blockIdx.x;
+  const int seq = unit_seq[u];
+  const int lo = unit_off[seq], hi = unit_off[seq + 1];
+  if (u + 1 >= hi) {  // (the whole block: u is the block's)
+    if (threadIdx.x == 0) dist[u] = 0.0f;
+    return;
+  }
+  const int a0 = max(lo, u - buffer), a1 = min(hi - 1, u + buffer);
+  const int b0 = max(lo, u + 1 - buffer), b1 = min(hi - 1, u + 1 + buffer);
+  float dot = 0.0f, na = 0.0f, nb = 0.0f;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int c = threadIdx.x + 256 * j;
+    if (c < H) {
+      float ca = 0.0f, cb = 0.0f;
+      for (int v = a0; v <= a1; ++v) ca += sums[static_cast<int64_t>(v) * H + c];
+      for (int v = b0; v <= b1; ++v) cb += sums[static_cast<int64_t>(v) * H + c];
+      dot += ca * cb;
+      na += ca * ca;
+      nb += cb * cb;
+    }
+  }
+  dot = wave_sum(dot);
+  na = wave_sum(na);
+  nb = wave_sum(nb);
+  if ((threadIdx.x & 63) == 0) {
+    red[0][threadIdx.x >> 6] = dot;
+    red[1][threadIdx.x >> 6] = na;
+    red[2][threadIdx.x >> 6] = nb;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    dot = red[0][0] + red[0][1] + red[0][2] + red[0][3];
+    na = red[1][0] + red[1][1] + red[1][2] + red[1][3];
+    nb = red[2][0] + red[2][1] + red[2][2] + red[2][3];
+    dist[u] = 1.0f - dot / fmaxf(sqrtf(na) * sqrtf(nb), 1e-12f);
+  }
+}
+
+// one block per sequence: which of its m - 1 gaps are candidates, then the walk. rank(r) counts the gaps with a larger
+// distance, or an equal one at a lower index (f32 compares on the stored values, all m - 1 of them from LDS); gap r is
+// a candidate iff rank(r) < B = ceil(break_permille (m - 1) / 1000) and d_r >= min_distance. Lane 0 then walks the units
+// left to right: start[u] = 1 and idx[u] = the chunk's index inside the sequence where a chunk begins, 0 and -1
+// elsewhere; seq_chunks[seq] = the sequence's chunks.
+__global__ __launch_bounds__(256) void unit_boundary_kernel(const float* __restrict__ dist, const int32_t* __restrict__ unit_off,
+                                                            const int32_t* __restrict__ unit_tok, int seq0, SemanticParams p,
+                                                            int32_t* __restrict__ start, int32_t* __restrict__ idx,
+                                                            int32_t* __restrict__ seq_chunks) {
+  __shared__ float d[kMaxSemUnits];
+  __shared__ uint8_t cand[kMaxSemUnits];
+  const int seq = seq0 + blockIdx.x;
+  const int lo = unit_off[seq];
+  const int m = min(unit_off[seq + 1] - lo, kMaxSemUnits);  // (the host refuses more: the bound of d[] stands in the kernel too)
+  if (m <= 0) {
+    if (threadIdx.x == 0) seq_chunks[seq] = 0;
+    return;
+  }
+  const int gaps = m - 1;
+  for (int r = threadIdx.x; r < gaps; r += 256) d[r] = dist[lo + r];
+  __syncthreads();
+  const int B = (p.break_permille * gaps + 999) / 1000;
+  for (int r = threadIdx.x; r < gaps; r += 256) {
+    const float dr = d[r];
+    int rank = 0;
+    for (int q = 0; q < gaps; ++q) {
+      const float dq = d[q];
+      rank += (dq > dr || (dq == dr && q < r)) ? 1 : 0;
+    }
+    cand[r] = (rank < B && dr >= p.min_distance) ? 1 : 0;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  int acc = unit_tok[2 * lo + 1] - unit_tok[2 * lo];
+  int chunks = 1;
+  start[lo] = 1;
+  idx[lo] = 0;
+  for (int r = 0; r < gaps; ++r) {
+    const int u = lo + r + 1;
+    const int n = unit_tok[2 * u + 1] - unit_tok[2 * u];
+    const bool close = (cand[r] && acc >= p.min_tokens) || acc + n > p.max_tokens;
+    start[u] = close ? 1 : 0;
+    idx[u] = close ? chunks : -1;
+    chunks += close ? 1 : 0;
+    acc = close ? n : acc + n;
+  }
+  seq_chunks[seq] = chunks;
+}
+
+// one block: seq_base[seq] = the first chunk row of every sequence of the forward chunk — the running counter (chunks of
+// the forward chunks before this one, in stream order) plus the chunk counts of the sequences before it — and the
+// counter moved past them. Thread t adds up a contiguous slice of the sequences, lane 0 the 256 slices in order.
+__global__ __launch_bounds__(256) void chunk_base_kernel(const int32_t* __restrict__ seq_chunks, int seq0, int n,
+                                                         int32_t* __restrict__ seq_base, int32_t* __restrict__ counter) {
+  __shared__ int part[256];
+  const int per = (n + 255) / 256;
+  const int b = min(n, static_cast<int>(threadIdx.x) * per), e = min(n, b + per);
+  int s = 0;
+  for (int i = b; i < e; ++i) s += seq_chunks[seq0 + i];
+  part[threadIdx.x] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int run = counter[0];
+    for (int t = 0; t < 256; ++t) {
+      const int v = part[t];
+      part[t] = run;
+      run += v;
+    }
+    counter[0] = run;
+  }
+  __syncthreads();
+  int run = part[threadIdx.x];
+  for (int i = b; i < e; ++i) {
+    seq_base[seq0 + i] = run;
+    run += seq_chunks[seq0 + i];
+  }
+}
+
+// one block per unit, at work where a chunk starts: (the sum of S_r over the chunk's units, in unit order) / (their
+// tokens), finished as span_pool_kernel finishes a span mean — the same operations, so a chunk of one unit has that
+// span's bits. Row: the chunk's own (seq_base + idx) — or, by_unit, the starting unit's, with zeros in the rows of
+// the other units: the rows embed_head_kernel then reads, a known number of them (chunk_gather_kernel compacts after).
+__global__ __launch_bounds__(256) void chunk_row_kernel(const float* __restrict__ sums, const int32_t* __restrict__ unit_off,
+                                                        const int32_t* __restrict__ unit_tok,
+                                                        const int32_t* __restrict__ unit_seq,
+                                                        const int32_t* __restrict__ start, const int32_t* __restrict__ idx,
+                                                        const int32_t* __restrict__ seq_base, int unit0, int H,
+                                                        int normalize, int by_unit, float* __restrict__ out, int ostride,
+                                                        int ocols) {
+  __shared__ float red[4];
+  const int u = unit0 + blockIdx.x;
+  if (!start[u]) {  // (the whole block)
+    if (by_unit)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int c = threadIdx.x + 256 * j;
+        if (c < ocols) out[static_cast<int64_t>(u) * ostride + c] = 0.0f;
+      }
+    return;
+  }
+  const int seq = unit_seq[u];
+  const int hi = unit_off[seq + 1];
+  int end = u + 1;
+  while (end < hi && !start[end]) ++end;
+  int len = 0;
+  for (int v = u; v < end; ++v) len += unit_tok[2 * v + 1] - unit_tok[2 * v];
+  const int row = by_unit ? u : seq_base[seq] + idx[u];
+  float vals[4];
+  float ss = 0.0f;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    int c = threadIdx.x + 256 * j;
+    float v = 0.0f;
+    if (c < H && len > 0) {
+      float acc = 0.0f;
+      for (int w = u; w < end; ++w) acc += sums[static_cast<int64_t>(w) * H + c];
+      v = acc / fmaxf(static_cast<float>(len), 1e-9f);
+    }
+    vals[j] = v;
+    ss += v * v;
+  }
+  ss = wave_sum(ss);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ss;
+  __syncthreads();
+  const float norm = sqrtf(red[0] + red[1] + red[2] + red[3]);
+  const float den = normalize ? fmaxf(norm, 1e-12f) : 1.0f;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    int c = threadIdx.x + 256 * j;
+    if (c < ocols) out[static_cast<int64_t>(row) * ostride + c] = vals[j] / den;
+  }
+}
+
+// one block per unit: the head's row of a unit that starts a chunk ([unit][W]) to the chunk's own row of out
+__global__ __launch_bounds__(256) void chunk_gather_kernel(const float* __restrict__ rows, const int32_t* __restrict__ unit_seq,
+                                                           const int32_t* __restrict__ start, const int32_t* __restrict__ idx,
+                                                           const int32_t* __restrict__ seq_base, int unit0, int W,
+                                                           float* __restrict__ out) {
+  const int u = unit0 + blockIdx.x;
+  if (!start[u]) return;
+  const int64_t row = seq_base[unit_seq[u]] + idx[u];
+  for (int c = threadIdx.x; c < W; c += 256) out[row * W + c] = rows[static_cast<int64_t>(u) * W + c];
 }
 
 // Cross-encoder head on n pooled [CLS] rows [n, H]: out[i] = wc . tanh(Wp h_i + bp) + bc, all f32. One block of 4 waves
@@ -4290,6 +4517,9 @@ static void free_encoder(void** slot) {
   enc->seg.release();
   enc->span_tok.release();
   enc->span_seq.release();
+  for (DevArray<int32_t>* a : {&enc->sem_off, &enc->sem_start, &enc->sem_idx, &enc->sem_seq_chunks, &enc->sem_seq_base, &enc->sem_counter})
+    a->release();
+  for (DevArray<float>* a : {&enc->sem_sums, &enc->sem_dist, &enc->sem_rows}) a->release();
   enc->skinny_ws.release();
   invalidate_graphs(enc);
   enc->out.release();
@@ -4926,13 +5156,57 @@ struct Spans {
   std::vector<int32_t> off;
   const int32_t* tok_dev = nullptr;
   const int32_t* seq_dev = nullptr;
+  const struct Semantic* sem = nullptr;  // a semantic call: the spans are units, the rows are their chunks'
 };
+
+// What a semantic call (encoder_encode_semantic) adds to its units: the rule's parameters and the device arrays of
+// launch_semantic — unit_off, the outputs per unit (dist, start) and the working arrays (Encoder::sem_*)
+struct Semantic {
+  SemanticParams p;
+  const int32_t* off_dev;
+  float *sums, *dist, *rows;
+  int32_t *start, *idx, *seq_chunks, *seq_base, *counter;
+};
+
+// launch_pool's arm of a semantic call: the units of sequences [seq0, seq1) summed from x, their gap distances, the
+// boundaries of every sequence, and the rows of the chunks that result at out_dev[counter ..], the counter running on
+// through the forward chunks of the call. With stages the means go through enc->pooled and embed_head_kernel as a span
+// call's do — one row per UNIT (the chunk count is the device's to know), the rows of chunk starts gathered after.
+static void launch_semantic(vr_engine* e, Encoder* enc, const float* x, const int32_t* cu_dev, int seq0, int seq1, int tok_base,
+                            float* out_dev, const Spans* sp) {
+  const vr_bert_desc& d = enc->d;
+  const Semantic& m = *sp->sem;
+  const int H = d.hidden, W = out_width(enc);
+  const bool staged = enc->head.n_stages > 0;
+  const int unit0 = sp->off[static_cast<size_t>(seq0)];
+  const int n_units = sp->off[static_cast<size_t>(seq1)] - unit0;
+  if (n_units <= 0) return;
+  const dim3 per_unit(static_cast<unsigned>(n_units)), block(256);
+  hipStream_t s = e->stream;
+  hipLaunchKernelGGL(unit_sum_kernel, per_unit, block, 0, s, x, cu_dev, sp->tok_dev, sp->seq_dev, unit0, tok_base, H, m.sums);
+  hipLaunchKernelGGL(unit_gap_kernel, per_unit, block, 0, s, m.sums, m.off_dev, sp->seq_dev, unit0, H, m.p.buffer, m.dist);
+  hipLaunchKernelGGL(unit_boundary_kernel, dim3(static_cast<unsigned>(seq1 - seq0)), block, 0, s, m.dist, m.off_dev, sp->tok_dev,
+                     seq0, m.p, m.start, m.idx, m.seq_chunks);
+  hipLaunchKernelGGL(chunk_base_kernel, dim3(1), block, 0, s, m.seq_chunks, seq0, seq1 - seq0, m.seq_base, m.counter);
+  if (!staged) {
+    hipLaunchKernelGGL(chunk_row_kernel, per_unit, block, 0, s, m.sums, m.off_dev, sp->tok_dev, sp->seq_dev, m.start, m.idx,
+                       m.seq_base, unit0, H, d.normalize, 0, out_dev, W, W);
+    return;
+  }
+  hipLaunchKernelGGL(chunk_row_kernel, per_unit, block, 0, s, m.sums, m.off_dev, sp->tok_dev, sp->seq_dev, m.start, m.idx,
+                     m.seq_base, unit0, H, 0, 1, enc->pooled.p, H, H);
+  hipLaunchKernelGGL(embed_head_kernel, dim3(static_cast<unsigned>((n_units + 15) / 16)), block, head_lds_bytes(head_lda(enc->head)),
+                     s, enc->pooled.p + static_cast<int64_t>(unit0) * H, n_units, H, enc->head, d.normalize, head_lda(enc->head),
+                     m.rows + static_cast<int64_t>(unit0) * W, W, W);
+  hipLaunchKernelGGL(chunk_gather_kernel, per_unit, block, 0, s, m.rows, sp->seq_dev, m.start, m.idx, m.seq_base, unit0, W, out_dev);
+}
 
 // The last launches of a forward chunk: the rows of sequences [seq0, seq1) — or of their spans (sp) — pooled from x
 // into out_dev, one row of out_width() floats each at its sequence's (span's) index. Without a head that is the pool
 // kernel alone, as ever. A head without stages only narrows what the pool kernel stores. With stages the pool kernel
 // leaves the un-normalised rows in enc->pooled (sized by the caller, same row indices) and embed_head_kernel finishes
-// the chunk's rows, 16 per block counted from the chunk's first row.
+// the chunk's rows, 16 per block counted from the chunk's first row. Spans that are the units of a semantic call
+// (sp->sem) become the rows of their chunks instead: launch_semantic.
 static void launch_pool(vr_engine* e, Encoder* enc, const float* x, const int32_t* cu_dev, int seq0, int seq1, int tok_base,
                         int compact, float* out_dev, const Spans* sp) {
   const vr_bert_desc& d = enc->d;
@@ -4941,6 +5215,7 @@ static void launch_pool(vr_engine* e, Encoder* enc, const float* x, const int32_
   float* dst = staged ? enc->pooled.p : out_dev;
   const int stride = staged ? H : W, cols = staged ? H : W, normalize = staged ? 0 : d.normalize;
   int row0 = seq0, n_rows = seq1 - seq0;
+  if (sp && sp->sem) return launch_semantic(e, enc, x, cu_dev, seq0, seq1, tok_base, out_dev, sp);
   if (sp) {
     row0 = sp->off[static_cast<size_t>(seq0)];
     n_rows = sp->off[static_cast<size_t>(seq1)] - row0;
@@ -5763,10 +6038,11 @@ static int forward_all(vr_engine* e, Encoder* enc, const int32_t* ids, const int
     VR_TRY(ensure_workspace(e, enc, std::max<int64_t>(T, 1024)));
     // A small forward pass (one chunk, <= 1024 tokens) is launch-bound: the second time a shape is seen
     // it is captured into a hipGraph and replayed from then on. Only on the engine's own stream (a
-    // caller's stream may be under capture itself) and with the HIP-event profiler off.
+    // caller's stream may be under capture itself) and with the HIP-event profiler off. Never a semantic call: its
+    // parameters are launch arguments and its chunk counter is zeroed per call, neither of which the key knows.
     static const bool graphs_on = !(getenv("VR_ENCODE_GRAPH") && atoi(getenv("VR_ENCODE_GRAPH")) == 0);
     const bool graphable = graphs_on && seq0 == 0 && seq1 == n_seq && T <= 1024 && e->stream == e->own_stream &&
-                           !prof_on(e);
+                           !prof_on(e) && !(sp && sp->sem);
     bool done = false;
     if (graphable) {
       if (enc->graphs.size() > 256) invalidate_graphs(enc);  // (shapes are few in practice; start over rather than track recency)
@@ -5841,18 +6117,25 @@ int encoder_encode(vr_engine* e, const int32_t* ids, const int32_t* offsets, int
 // copy already), every span non-empty and inside its sequence — and made ready for span_pool_kernel: sp->tok_dev is
 // the caller's array or its staged copy, sp->seq_dev the sequence index of every span. n_expected >= 0: the span count
 // the caller announced. Nothing is queued before the checks when the arrays are in host memory.
+// units (a semantic call, the messages then say "unit"): a sequence's spans are also in order and never overlap, and
+// there are at most kMaxSemUnits of them.
 static int read_spans(vr_engine* e, Encoder* enc, const int32_t* span_tok, int n_seq, int mem,
-                      const std::vector<int32_t>& cu_host, int64_t n_expected, Spans* sp) {
-  VR_CHECK(sp->off[0] == 0, "span_off must start at 0");
-  for (int i = 0; i < n_seq; ++i)
+                      const std::vector<int32_t>& cu_host, int64_t n_expected, Spans* sp, bool units = false) {
+  const char* what = units ? "unit" : "span";
+  VR_CHECK(sp->off[0] == 0, "%s_off must start at 0", what);
+  for (int i = 0; i < n_seq; ++i) {
     VR_CHECK(sp->off[static_cast<size_t>(i) + 1] >= sp->off[static_cast<size_t>(i)],
-             "span_off decreases at sequence %d (%d spans before it, %d after)", i, sp->off[static_cast<size_t>(i)],
+             "%s_off decreases at sequence %d (%d %ss before it, %d after)", what, i, sp->off[static_cast<size_t>(i)], what,
              sp->off[static_cast<size_t>(i) + 1]);
+    VR_CHECK(!units || sp->off[static_cast<size_t>(i) + 1] - sp->off[static_cast<size_t>(i)] <= kMaxSemUnits,
+             "sequence %d has %d units (at most %d allowed)", i,
+             sp->off[static_cast<size_t>(i) + 1] - sp->off[static_cast<size_t>(i)], kMaxSemUnits);
+  }
   const int64_t n_spans = sp->off[static_cast<size_t>(n_seq)];
   VR_CHECK(n_expected < 0 || n_spans == n_expected, "%lld rows announced, span_off holds %lld spans",
            static_cast<long long>(n_expected), static_cast<long long>(n_spans));
   if (n_spans == 0) return 0;
-  VR_CHECK(span_tok != nullptr, "null span_tok");
+  VR_CHECK(span_tok != nullptr, "null %s_tok", what);
   std::vector<int32_t> tok_copy;
   const int32_t* tok = span_tok;
   if (mem != VR_MEM_HOST) {
@@ -5866,8 +6149,11 @@ static int read_spans(vr_engine* e, Encoder* enc, const int32_t* span_tok, int n
     const int len = cu_host[static_cast<size_t>(i) + 1] - cu_host[static_cast<size_t>(i)];
     for (int r = sp->off[static_cast<size_t>(i)]; r < sp->off[static_cast<size_t>(i) + 1]; ++r) {
       const int begin = tok[2 * static_cast<size_t>(r)], end = tok[2 * static_cast<size_t>(r) + 1];
-      VR_CHECK(begin >= 0 && begin < end && end <= len, "sequence %d span %d: [%d, %d) is empty or outside its %d tokens", i,
-               r, begin, end, len);
+      VR_CHECK(begin >= 0 && begin < end && end <= len, "sequence %d %s %d: [%d, %d) is empty or outside its %d tokens", i,
+               what, r, begin, end, len);
+      VR_CHECK(!units || r == sp->off[static_cast<size_t>(i)] || begin >= tok[2 * static_cast<size_t>(r) - 1],
+               "sequence %d unit %d: [%d, %d) begins before the end of unit %d (%d): units are in order and never overlap",
+               i, r, begin, end, r - 1, r > 0 ? tok[2 * static_cast<size_t>(r) - 1] : 0);
       enc->span_seq_host[static_cast<size_t>(r)] = i;
     }
   }
@@ -5907,6 +6193,80 @@ int encoder_encode_spans(vr_engine* e, const int32_t* ids, const int32_t* offset
   // (device arrays in and out: drain here, enc->span_seq_host must outlive its upload)
   if (mem != VR_MEM_HOST && out_mem != VR_MEM_HOST) VR_HIP(hipStreamSynchronize(e->stream));
   return finish(e, out, out_dev, n_spans * W, mem, out_mem);
+}
+
+int encoder_encode_semantic(vr_engine* e, const int32_t* ids, const int32_t* offsets, int n_seq, const int32_t* unit_off,
+                            const int32_t* unit_tok, int mem, const vr_semantic_params* p, float* out_rows,
+                            int32_t* out_unit_start, float* out_gap_dist, int32_t* n_chunks, int out_mem) {
+  Encoder* enc = static_cast<Encoder*>(e->encoder);
+  VR_CHECK(enc != nullptr, "no encoder loaded (vr_encoder_load)");
+  *n_chunks = 0;
+  if (n_seq <= 0) return 0;
+  VR_CHECK(p->struct_size == static_cast<int32_t>(sizeof(vr_semantic_params)), "vr_semantic_params.struct_size is %d, %d expected",
+           p->struct_size, static_cast<int>(sizeof(vr_semantic_params)));
+  VR_CHECK(p->buffer >= 0 && p->buffer <= 3, "semantic buffer %d not in 0..3", p->buffer);
+  VR_CHECK(p->break_permille >= 0 && p->break_permille <= 1000, "semantic break_permille %d not in 0..1000", p->break_permille);
+  VR_CHECK(p->min_tokens >= 0, "semantic min_tokens %d is negative", p->min_tokens);
+  VR_CHECK(p->max_tokens >= 1 && p->max_tokens >= p->min_tokens, "semantic max_tokens %d is below 1 or below min_tokens %d",
+           p->max_tokens, p->min_tokens);
+  VR_CHECK(p->min_distance == p->min_distance, "semantic min_distance is not a number");
+  const int H = enc->d.hidden, W = out_width(enc);
+  std::vector<int32_t> cu_host;
+  Spans sp;
+  VR_TRY(read_offsets(e, enc, offsets, nullptr, n_seq, mem, &cu_host, unit_off, &sp.off));
+  VR_TRY(read_spans(e, enc, unit_tok, n_seq, mem, cu_host, -1, &sp, true));
+  const int64_t n_units = sp.off[static_cast<size_t>(n_seq)];
+  if (n_units == 0) return 0;
+  VR_CHECK(out_rows && out_unit_start && out_gap_dist, "null output");
+  const bool staged = enc->head.n_stages > 0;
+  hipStream_t s = e->stream;
+  VR_TRY(enc->sem_sums.grow(n_units * H, 0, s));
+  VR_TRY(enc->sem_idx.grow(n_units, 0, s));
+  VR_TRY(enc->sem_seq_chunks.grow(n_seq, 0, s));
+  VR_TRY(enc->sem_seq_base.grow(n_seq, 0, s));
+  VR_TRY(enc->sem_counter.grow(1, 0, s));
+  if (staged) {
+    VR_TRY(enc->pooled.grow(n_units * H, 0, s));
+    VR_TRY(enc->sem_rows.grow(n_units * W, 0, s));
+  }
+  Semantic m{};
+  m.p = SemanticParams{p->buffer, p->break_permille, p->min_tokens, p->max_tokens, p->min_distance};
+  m.off_dev = unit_off;
+  if (mem == VR_MEM_HOST) {
+    VR_TRY(enc->sem_off.grow(n_seq + 1, 0, s));
+    VR_HIP(hipMemcpyAsync(enc->sem_off.p, unit_off, sizeof(int32_t) * sp.off.size(), hipMemcpyHostToDevice, s));
+    m.off_dev = enc->sem_off.p;
+  }
+  float* rows_dev = out_rows;
+  m.start = out_unit_start;
+  m.dist = out_gap_dist;
+  if (out_mem == VR_MEM_HOST) {
+    VR_TRY(enc->out.grow(n_units * W, 0, s));
+    VR_TRY(enc->sem_start.grow(n_units, 0, s));
+    VR_TRY(enc->sem_dist.grow(n_units, 0, s));
+    rows_dev = enc->out.p;
+    m.start = enc->sem_start.p;
+    m.dist = enc->sem_dist.p;
+  }
+  m.sums = enc->sem_sums.p;
+  m.rows = enc->sem_rows.p;
+  m.idx = enc->sem_idx.p;
+  m.seq_chunks = enc->sem_seq_chunks.p;
+  m.seq_base = enc->sem_seq_base.p;
+  m.counter = enc->sem_counter.p;
+  sp.sem = &m;
+  VR_HIP(hipMemsetAsync(m.counter, 0, sizeof(int32_t), s));
+  VR_TRY(forward_all(e, enc, ids, offsets, nullptr, n_seq, mem, cu_host, rows_dev, &sp));
+  // the chunk count decides how many rows there are to copy: the stream is drained here in every case
+  VR_HIP(hipMemcpyAsync(n_chunks, m.counter, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  VR_HIP(hipStreamSynchronize(s));
+  if (out_mem == VR_MEM_HOST) {
+    VR_HIP(hipMemcpyAsync(out_rows, rows_dev, sizeof(float) * static_cast<size_t>(*n_chunks) * W, hipMemcpyDeviceToHost, s));
+    VR_HIP(hipMemcpyAsync(out_unit_start, m.start, sizeof(int32_t) * static_cast<size_t>(n_units), hipMemcpyDeviceToHost, s));
+    VR_HIP(hipMemcpyAsync(out_gap_dist, m.dist, sizeof(float) * static_cast<size_t>(n_units), hipMemcpyDeviceToHost, s));
+    VR_HIP(hipStreamSynchronize(s));
+  }
+  return 0;
 }
 
 int encoder_rerank(vr_engine* e, const int32_t* ids, const int32_t* offsets, const int32_t* seg_b, int n_seq, int mem,

@@ -621,6 +621,10 @@ int encoder_encode(vr_engine* e, const int32_t* ids, const int32_t* offsets, int
 // one row per token span instead of per sequence (vr_encode_spans); n_expected >= 0: the span count the caller announced
 int encoder_encode_spans(vr_engine* e, const int32_t* ids, const int32_t* offsets, int n_seq, const int32_t* span_off,
                          const int32_t* span_tok, int mem, int64_t n_expected, float* out, int out_mem);
+// the spans as units: boundaries by the semantic rule and one row per resulting chunk (vr_encode_semantic)
+int encoder_encode_semantic(vr_engine* e, const int32_t* ids, const int32_t* offsets, int n_seq, const int32_t* unit_off,
+                            const int32_t* unit_tok, int mem, const vr_semantic_params* p, float* out_rows,
+                            int32_t* out_unit_start, float* out_gap_dist, int32_t* n_chunks, int out_mem);
 void encoder_release(vr_engine* e);  // the embedder and the reranker
 int reranker_load(vr_engine* e, const vr_bert_desc* d, const void* const* tensors, int n_tensors, int mem);
 bool reranker_loaded(vr_engine* e);

@@ -18,6 +18,7 @@ import numpy as np
 from . import deferred as _deferred
 from . import encoder as _enc
 from . import late_chunking as _late
+from . import semantic_chunking as _semantic
 from .bpe import BpeTokenizer
 from .config import MAX_SEQ_LENGTH_LIMIT, get_settings
 from .store_registry import get_engine
@@ -754,9 +755,62 @@ class EmbeddingService:
         """embed_document for [(document, chunk_texts), ...] in one engine call; the rows in chunk order."""
         return self.model.encode_documents(documents, self._passage("")).tolist()
 
+    def chunk_and_embed_documents(self, texts: list[str], chunker=None) -> list:
+        """Semantic chunking: per document ``(chunks, vectors)`` — its chunks (``chunking.Chunk``, the
+        texts ``SemanticChunkText`` that carry the vectors) and their late-chunked rows (n, D) f32 — from ONE forward pass
+        over all the documents (vr_encode_semantic): units by the native ``sentence`` strategy, boundaries where
+        neighbouring units stop resembling each other, by the VOITTA_SEMANTIC_* settings. A document that cannot be
+        planned (semantic_chunking.plan_units) is cut by ``chunker`` (default: the configured ChunkingService) and
+        embedded the plain way."""
+        from .chunking import Chunk, ChunkingService
+
+        s = get_settings()
+        texts = [t or "" for t in texts]
+        if not texts:
+            return []
+        splitter = ChunkingService(chunk_size=s.semantic_unit_chars, strategy="sentence")
+        splitter.chunk_overlap = 0  # (the constructor reads 0 as "the setting's")
+        units = [[str(c.text) for c in own] for own in splitter.cut(texts)]
+        model = self.model
+        lead = model.leading_specials
+        prefix = self._passage("")
+        up = _semantic.plan_units(list(zip(texts, units)), model.tokenize, model.max_seq_length, s.late_chunking_context,
+                                  _late.prefix_ids_of(prefix, model.tokenize, lead), lead)
+        out: list = [None] * len(texts)
+        if up.plan.n_chunks:
+            p = up.plan
+            rows, start, _ = _enc.encode_semantic(model.engine, p.ids, p.offsets, p.span_off, p.span_tok,
+                                                  buffer=s.semantic_buffer, break_permille=s.semantic_break_permille,
+                                                  min_distance=s.semantic_min_distance, min_tokens=s.semantic_min_tokens,
+                                                  max_tokens=s.semantic_max_tokens)
+            u0 = r0 = 0
+            for k, where in zip(up.planned, up.where):
+                own = start[u0:u0 + len(where)]
+                pieces = _semantic.rebuild(texts[k], where, own)
+                vectors = rows[r0:r0 + len(pieces)]
+                wrapped = _semantic.wrap_chunks([t for t, _, _ in pieces], vectors)
+                out[k] = ([Chunk(w, i, a, b) for i, (w, (_, a, b)) in enumerate(zip(wrapped, pieces))], vectors)
+                u0, r0 = u0 + len(where), r0 + len(pieces)
+            assert r0 == len(rows) and u0 == len(start)
+        if up.plain:
+            cutter = chunker or ChunkingService()
+            for k, chunks in zip(up.plain, cutter.cut([texts[k] for k in up.plain])):
+                plain = [str(c.text) for c in chunks]
+                vectors = (model.encode([self._passage(t) for t in plain]) if plain
+                           else np.zeros((0, model.desc.out_dim), np.float32))
+                wrapped = _semantic.wrap_chunks(plain, vectors)
+                out[k] = ([Chunk(w, c.index, c.start_char, c.end_char) for w, c in zip(wrapped, chunks)], vectors)
+        return out
+
     def embed_texts(self, texts: list[str], batch_size: int = 32) -> list[list[float]]:
         if not texts:
             return []
+        if get_settings().semantic_chunking:
+            # chunk texts that ChunkingService returned under the flag (SemanticChunkText), whole documents of them in
+            # order: their vectors came out of the pass that chose their boundaries and travel with them
+            carried = _semantic.carried_vectors(texts)
+            if carried is not None:
+                return carried.tolist()
         if get_settings().late_chunking:
             # chunk texts that ChunkingService cut (LateChunkText), whole documents of them in order: embedded in the
             # context of their documents, plain floats at once (no deferred references in this mode)

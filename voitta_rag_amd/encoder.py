@@ -800,3 +800,40 @@ def encode_spans(engine, ids, offsets, span_off, span_tok, out=None):
     res = np.empty((max(n_spans, 0), desc.out_dim), np.float32)
     check(engine._lib.vr_encode_spans(engine.handle, ip, op_, n, sop, stp, mem, C.c_void_p(res.ctypes.data), VR_MEM_HOST))
     return res
+
+
+def encode_semantic(engine, ids, offsets, unit_off, unit_tok, *, buffer=1, break_permille=50, min_distance=0.0,
+                    min_tokens=0, max_tokens=2**31 - 1):
+    """Semantic chunking in one forward pass (vr_encode_semantic): the spans of ``encode_spans`` as UNITS —
+    in order, never overlapping — of which the device joins neighbours into chunks and returns the chunks' late-chunked
+    rows. Arrays as ``encode_spans`` takes them. Returns ``(rows, unit_start, gap_dist)``: (n_chunks, out_dim) f32 in chunk
+    order, per unit an int32 1 where it begins a chunk, and per unit the f32 distance of the gap behind it (0 for a
+    sequence's last unit) — the values the device decided on."""
+    desc = engine.encoder_desc
+    dev_in = hasattr(ids, "is_cuda") and ids.is_cuda
+    if dev_in:
+        engine._follow(ids)
+        arrays = [ids, offsets, unit_off, unit_tok.contiguous()]
+        ptrs = [C.c_void_p(a.data_ptr()) for a in arrays]
+        n_units = int(unit_off[-1].item()) if int(unit_off.shape[0]) else 0
+        mem = VR_MEM_DEVICE
+    else:
+        arrays = [np.ascontiguousarray(a, dtype=np.int32) for a in (ids, offsets, unit_off, unit_tok)]
+        ptrs = [C.c_void_p(a.ctypes.data) for a in arrays]
+        n_units = int(arrays[2][-1]) if arrays[2].shape[0] else 0
+        mem = VR_MEM_HOST
+    n = int(arrays[1].shape[0]) - 1
+    if int(arrays[2].shape[0]) != n + 1:
+        raise ValueError(f"unit_off has {int(arrays[2].shape[0])} entries for {n} sequences ({n + 1} expected)")
+    if int(arrays[3].numel() if dev_in else arrays[3].size) < 2 * max(n_units, 0):
+        raise ValueError(f"unit_tok holds fewer than the {n_units} (begin, end) pairs unit_off announces")
+    params = _lib.VrSemanticParams(C.sizeof(_lib.VrSemanticParams), int(buffer), int(break_permille), int(min_tokens),
+                                   int(max_tokens), float(min_distance))
+    rows = np.empty((max(n_units, 0), desc.out_dim), np.float32)
+    start = np.zeros(max(n_units, 0), np.int32)
+    dist = np.zeros(max(n_units, 0), np.float32)
+    n_chunks = C.c_int32(0)
+    check(engine._lib.vr_encode_semantic(engine.handle, *ptrs[:2], n, *ptrs[2:], mem, C.byref(params),
+                                         C.c_void_p(rows.ctypes.data), C.c_void_p(start.ctypes.data),
+                                         C.c_void_p(dist.ctypes.data), C.byref(n_chunks), VR_MEM_HOST))
+    return rows[:n_chunks.value].copy(), start, dist

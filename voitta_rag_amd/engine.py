@@ -248,6 +248,12 @@ class Engine:
 
         return encoder.encode_spans(self, ids, offsets, span_off, span_tok, out)
 
+    def encode_semantic(self, ids, offsets, unit_off, unit_tok, **params):
+        """Chunk boundaries and the chunks' late-chunked rows from one forward pass: ``encoder.encode_semantic``."""
+        from . import encoder
+
+        return encoder.encode_semantic(self, ids, offsets, unit_off, unit_tok, **params)
+
     def set_attention_bias(self, table) -> None:
         """The loaded encoder's additive attention bias by relative offset (vr_encoder_set_attention_bias):
         table[heads, 2 * radius + 1], f32; the logit of query i against key j of head h gains

@@ -9,7 +9,9 @@ stream of files with the same stored result (same chunks, payload fields, vector
 * cut into batches of ``batch_chunks`` chunks regardless of file boundaries (a 3-chunk file does not
   pay a GPU launch sequence of its own) — with VOITTA_LATE_CHUNKING=1, into batches of whole files until
   ``batch_chunks`` is reached: a file's chunks are token spans of the file's own sequences
-  (late_chunking.plan_many, vr_index_batch_spans), so a batch never holds half a file,
+  (late_chunking.plan_many, vr_index_batch_spans), so a batch never holds half a file; with
+  VOITTA_SEMANTIC_CHUNKING=1 a group of whole files is chunked AND embedded by one forward pass
+  (vr_encode_semantic) and stored with store_chunks,
 * the host stages — chunking (vr_chunk_texts), WordPiece (vr_wordpiece_encode) and the BM25 tokeniser
   (vr_bm25_tokenize), all on every host thread — run on a producer thread for batch i+1 while
 * point ids and payload dicts of batch i+1 are made there too (VectorStoreService.prepare_rows), and
@@ -73,6 +75,49 @@ class BulkIndexer:
         self.files_per_cut = int(files_per_cut)
         # late chunking (VOITTA_LATE_CHUNKING=1): a batch is whole files, their contents kept beside the chunks
         self.late = get_settings().late_chunking
+        # semantic chunking (VOITTA_SEMANTIC_CHUNKING=1): chunks and vectors come out of one pass per group of whole files
+        self.semantic = get_settings().semantic_chunking
+
+    @staticmethod
+    def _metadata(f: ParsedFile, c, total: int, indexed_at: str) -> ChunkMetadata:
+        return ChunkMetadata(
+            file_path=f.file_path, folder_path=f.folder_path, index_folder=f.index_folder,
+            file_name=f.file_name, chunk_index=c.index, total_chunks=total,
+            start_char=c.start_char, end_char=c.end_char, indexed_at=indexed_at,
+            source_created_at=f.source_created_at, source_modified_at=f.source_modified_at,
+            allowed_users=f.allowed_users, source_url=f.source_url)
+
+    # ---- semantic chunking: the chunks are only known after the forward pass -------------------------
+    def _index_files_semantic(self, files: Iterable[ParsedFile]) -> dict[str, int]:
+        """VOITTA_SEMANTIC_CHUNKING=1: per group of ``files_per_cut`` whole files ONE forward pass gives the chunks and
+        their vectors (EmbeddingService.chunk_and_embed_documents); they are stored with store_chunks, the sparse
+        vectors from the chunk texts as the per-file sequence makes them. The fused vr_index_batch cannot serve here:
+        it needs the row count before the pass."""
+        from .sparse_embedding import SparseEmbeddingService
+
+        sparse_embedder = SparseEmbeddingService() if self.sparse else None
+        done: dict[str, int] = {}
+
+        def flush(group: list[ParsedFile]):
+            indexed_at = datetime.now(timezone.utc).isoformat()
+            rows = []
+            results = self.embedder.chunk_and_embed_documents([f.content for f in group], chunker=self.chunker)
+            for f, (chunks, vectors) in zip(group, results):
+                done[f.file_path] = len(chunks)
+                rows += [(str(c.text), v, self._metadata(f, c, len(chunks), indexed_at)) for c, v in zip(chunks, vectors)]
+            if rows:
+                sparse = sparse_embedder.embed_texts([r[0] for r in rows]) if sparse_embedder else None
+                self.vector_store.store_chunks(rows, sparse)
+
+        group: list[ParsedFile] = []
+        for f in files:
+            group.append(f)
+            if len(group) >= self.files_per_cut:
+                flush(group)
+                group = []
+        if group:
+            flush(group)
+        return done
 
     # ---- host stages (producer thread) -------------------------------------------------------------
     def _tokenise(self, texts: list[str], metadatas: list[ChunkMetadata], counts: dict[str, int],
@@ -108,12 +153,7 @@ class BulkIndexer:
                     documents.append((f.content, [str(c.text) for c in chunks]))
                 for c in chunks:
                     texts.append(str(c.text) if self.late else c.text)
-                    metadatas.append(ChunkMetadata(
-                        file_path=f.file_path, folder_path=f.folder_path, index_folder=f.index_folder,
-                        file_name=f.file_name, chunk_index=c.index, total_chunks=len(chunks),
-                        start_char=c.start_char, end_char=c.end_char, indexed_at=indexed_at,
-                        source_created_at=f.source_created_at, source_modified_at=f.source_modified_at,
-                        allowed_users=f.allowed_users, source_url=f.source_url))
+                    metadatas.append(self._metadata(f, c, len(chunks), indexed_at))
 
         def drain(everything: bool):
             nonlocal texts, metadatas, counts, documents
@@ -150,6 +190,8 @@ class BulkIndexer:
         ``return False, 0`` cases at indexing.py:509-522). A file's count is reported with the batch that
         holds its last chunk."""
         self.embedder.model  # noqa: B018  load the encoder before the threads start
+        if self.semantic:
+            return self._index_files_semantic(files)
         q: queue.Queue = queue.Queue(maxsize=2)
         failure: list[BaseException] = []
 
