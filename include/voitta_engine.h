@@ -125,7 +125,7 @@ typedef struct vr_bert_desc {
   int32_t struct_size;
   int32_t layers;
   int32_t hidden;        /* H: multiple of 128, <= 1024 */
-  int32_t heads;         /* H / heads must be 32 or 64 */
+  int32_t heads;         /* H / heads must be 32 or 64 (vr_bert_desc_v3.head_dim sets the head size on its own) */
   int32_t intermediate;  /* multiple of 128 */
   int32_t vocab;
   int32_t max_pos;       /* max_position_embeddings; also the longest accepted sequence. VR_POS_ROTARY: the length of
@@ -159,6 +159,20 @@ typedef struct vr_bert_desc_v2 {
                           * iff j <= i. VR_NORM_PRE_RMS_ROTARY only: every other norm refuses 1, and so does a reranker */
 } vr_bert_desc_v2;
 
+/* ... and what was added behind that with Qwen3: a head size that is not hidden / heads, and a per-head RMSNorm on the
+ * query and the key. Passed as &v3.v2.base with base.struct_size = sizeof(vr_bert_desc_v3); every shorter accepted size
+ * reads both fields as 0. VR_NORM_PRE_RMS_ROTARY only: every other norm refuses a non-zero value, and so does a reranker. */
+typedef struct vr_bert_desc_v3 {
+  vr_bert_desc_v2 v2;
+  int32_t head_dim;      /* 0: the head size is hidden / heads. 32, 64 or 128: the head size, whatever hidden is; the
+                          * attention width A = heads * head_dim must then be a multiple of 128 and at most 2048. The
+                          * query / key / value weights are [A, H], their biases [A], attention.output.dense is [H, A],
+                          * and the engine's rows are [Q | K | V] of 3 A */
+  int32_t qk_norm;       /* 0 or 1. 1: every head of the query and of the key is RMS-normalised over its head_dim values
+                          * (eps as every other norm) and scaled by q_norm.weight / k_norm.weight before the rotation; a
+                          * layer then has 20 slots, 18: q_norm.weight, 19: k_norm.weight, [head_dim] f32 each */
+} vr_bert_desc_v3;
+
 /* position: LEARNED adds a row of the position table to every token's embedding; ROTARY has no table — the query and
  * key of every head are rotated by the token's position inside its own sequence (rotate-half pairing: feature j with
  * j + d_h/2, as in HF apply_rotary_pos_emb; the full head is rotated). NONE has no table and no rotation: the
@@ -188,7 +202,8 @@ typedef struct vr_bert_desc_v2 {
  * h += W_down(act(gate(N_m(h))) * up(N_m(h))); out = N_f(h), every N an RMSNorm as under PRE_RMS. It needs
  * VR_POS_ROTARY, a gated ffn, window 0 and type_vocab 1 (anything else is refused with the field named), takes
  * vr_bert_desc_v2.causal 0 or 1, refuses vr_encoder_set_attention_bias and _slopes, and a reranker never takes it. PRE_RMS itself
- * stays the T5 form alone. */
+ * stays the T5 form alone. PRE_RMS_ROTARY is also the one norm that takes vr_bert_desc_v3 (Qwen3): head sizes 32, 64
+ * and 128 set by head_dim, rope(N_q(q)) and rope(N_k(k)) per head with qk_norm. */
 #define VR_NORM_POST 0
 #define VR_NORM_PRE  1
 #define VR_NORM_PRE_RMS 2
@@ -225,7 +240,8 @@ typedef struct vr_bert_desc_v2 {
  * VR_NORM_PRE_RMS_ROTARY: the same slots, 18 per layer (the ffn is gated): embeddings.LayerNorm = layers.0.input_layernorm,
  * layer l's attention.output.LayerNorm = layers.l.post_attention_layernorm, layer l's output.LayerNorm =
  * layers.l+1.input_layernorm, the last = norm. Grouped-query checkpoints are brought to `heads` full K and V heads by
- * the loader (HF repeat_kv): the engine sees [Q | K | V] rows of 3 H.
+ * the loader (HF repeat_kv): the engine sees [Q | K | V] rows of 3 H (3 A with vr_bert_desc_v3.head_dim, and with
+ * vr_bert_desc_v3.qk_norm two slots more per layer: q_norm.weight, k_norm.weight).
  * NULL slots: any bias (read as zeros), and position_embeddings when position is VR_POS_ROTARY or VR_POS_NONE (ignored
  * then); under VR_NORM_PRE_RMS and VR_NORM_PRE_RMS_ROTARY also every LayerNorm bias (ignored) and token_type_embeddings (read as zeros).
  * Every other slot must be non-NULL.

@@ -73,6 +73,11 @@ class VrBertDescV2(VrBertDesc):
     _fields_ = [("causal", C.c_int32)]
 
 
+class VrBertDescV3(VrBertDescV2):
+    """vr_bert_desc_v3: vr_bert_desc_v2 (the base classes' fields, at their offsets) and `head_dim`, `qk_norm` behind it."""
+    _fields_ = [("head_dim", C.c_int32), ("qk_norm", C.c_int32)]
+
+
 class VrHeadStage(C.Structure):
     _fields_ = [
         ("struct_size", C.c_int32),

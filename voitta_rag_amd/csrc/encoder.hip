@@ -67,6 +67,8 @@ struct LayerWeights {
   // sums and folded bias (what s_1_f, cs_1, c_1 are to the stacked matrix)
   SplitWeight s_1_fp{};
   float *cs_1_p = nullptr, *c_1_p = nullptr;
+  // vr_bert_desc_v3.qk_norm: q_norm.weight / k_norm.weight, [head_dim] each, shared by the heads (qk_norm_rope_kernel)
+  float *qn = nullptr, *kn = nullptr;
 };
 
 // vr_encoder_set_head: the stages embed_head_kernel runs on the pooled rows (device pointers; a null b: no bias / shift)
@@ -110,6 +112,9 @@ struct Encoder {
   int out_dim = 0;
   DevArray<float> pooled;
   int causal = 0;               // vr_bert_desc_v2.causal: 1 = the attention kernels' causal state (VR_NORM_PRE_RMS_ROTARY only)
+  // vr_bert_desc_v3: the head size (head_dim, or hidden / heads), the attention width A = heads * dh of the [Q | K | V]
+  // rows and of the context (== hidden for every family but Qwen3), and whether Q and K are RMS-normalised per head
+  int dh = 0, attn = 0, qk_norm = 0;
   int window_stream_from = 0;   // windowed layers: sequences from this length on take attention_stream_kernel (build_encoder)
   float* posidx = nullptr;  // rotary: int32 position of every token inside its own sequence (positions_kernel)
   bool fuse = true;         // rotate / gate inside the skinny epilogues; VR_ENCODE_FUSE=0 at load time: separate passes
@@ -1293,6 +1298,62 @@ __global__ __launch_bounds__(256) void rope_kernel(T* __restrict__ qkv, const in
       const float co = k < 4 ? cs0[2 * k] : cs1[2 * k - 8], si = k < 4 ? cs0[2 * k + 1] : cs1[2 * k - 7];
       ra[k] = a[k] * co - b[k] * si;
       rb[k] = b[k] * co + a[k] * si;
+    }
+    store8(at, ra);
+    store8(at + half, rb);
+  }
+}
+
+// The per-head RMSNorm of the query and the key (vr_bert_desc_v3.qk_norm, Qwen3) and the rotation behind it, in one
+// pass: rope_kernel's walk (one wave per token, a lane takes 8 pairs of one head of the query or the key, `H` the
+// width A of a third), with every value first scaled by rsqrt(mean_d(x^2) + eps) of its head and by the gain of its
+// feature (gq for the query third, gk for the key third, [d_h] each, shared by the heads):
+//   n[j] = x[j] r g[j];  x[j] <- n[j] cos - n[j + d_h/2] sin,  x[j + d_h/2] <- n[j + d_h/2] cos + n[j] sin
+// A head's d_h values lie in d_h/16 neighbouring lanes (2, 4 or 8, aligned: c advances by 64 and the loop's bound is a
+// multiple of d_h/16, so a group is active or idle as a whole). Each lane sums its 16 squares in index order, the
+// group adds them with a butterfly of __shfl_xor (1, 2, 4): a fixed order that depends on the head alone, so a row's
+// bits do not depend on the batch it travels in. Everything is f32; T = half_t rounds once, at the store.
+template <typename T>
+__global__ __launch_bounds__(256) void qk_norm_rope_kernel(T* __restrict__ qkv, const int32_t* __restrict__ pos, int Tn, int H,
+                                                           int dh, const float2* __restrict__ table,
+                                                           const float* __restrict__ gq, const float* __restrict__ gk,
+                                                           float eps) {
+  const int lane = threadIdx.x & 63;
+  const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (t >= Tn) return;
+  const int half = dh >> 1;          // 16, 32 or 64
+  const int groups = half >> 3;      // lanes per head: groups of 8 pairs
+  const int per_third = (H / dh) * groups;
+  const float inv_dh = 1.0f / static_cast<float>(dh);
+  T* row = qkv + static_cast<int64_t>(t) * 3 * H;
+  const float2* cs_row = table + static_cast<int64_t>(pos[t]) * (H >> 1);  // (the first head's entries serve every head)
+  for (int c = lane; c < 2 * per_third; c += 64) {
+    const int third = c >= per_third ? 1 : 0;
+    const int w = c - third * per_third;
+    const int head = w / groups, i8 = (w - head * groups) << 3;
+    T* at = row + third * H + head * dh + i8;
+    const float* gain = (third ? gk : gq) + i8;
+    float a[8], b[8], ga[8], gb[8], cs0[8], cs1[8];  // cs0 / cs1: (cos, sin) of pairs 0..3 / 4..7
+    load8(at, a);
+    load8(at + half, b);
+    load8(gain, ga);
+    load8(gain + half, gb);
+    load8(reinterpret_cast<const float*>(cs_row + i8), cs0);
+    load8(reinterpret_cast<const float*>(cs_row + i8 + 4), cs1);
+    float ss = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) ss = fmaf(a[k], a[k], ss);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) ss = fmaf(b[k], b[k], ss);
+    for (int o = 1; o < groups; o <<= 1) ss += __shfl_xor(ss, o);
+    const float r = rsqrtf(ss * inv_dh + eps);
+    float ra[8], rb[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const float co = k < 4 ? cs0[2 * k] : cs1[2 * k - 8], si = k < 4 ? cs0[2 * k + 1] : cs1[2 * k - 7];
+      const float na = a[k] * r * ga[k], nb = b[k] * r * gb[k];
+      ra[k] = na * co - nb * si;
+      rb[k] = nb * co + na * si;
     }
     store8(at, ra);
     store8(at + half, rb);
@@ -3809,6 +3870,8 @@ __device__ __forceinline__ void slope_tile(f32x4 (&st)[4], float scale2, float s
   }
 }
 
+// (attention_kernel<128, ...>: the bytes of its K and V tiles, dynamic LDS — see the kernel)
+constexpr size_t kAttnF32Lds128 = 2 * 64 * (128 + 4) * sizeof(float);
 // One block = 64 queries of one (sequence, head); wave w owns queries 16w..16w+15.
 // S^T = K Q^T is computed with keys on the MFMA rows, so a lane (q = lane & 15, g = lane >> 4)
 // ends up holding the logits of query q against keys 4g..4g+3 of each 16-key tile: exactly the B
@@ -3825,8 +3888,19 @@ __global__ __launch_bounds__(256) void attention_kernel(const float* __restrict_
   const int window = WIN ? window_arg : 0;
   constexpr int LDK = DH + 4;
   constexpr int NS = DH / 16;  // 16-wide d blocks
-  __shared__ float sK[64 * LDK];
-  __shared__ float sV[64 * LDK];
+  // (d_h = 128: two tiles of 64 x 132 floats are 67,584 bytes, above the 64 KiB a kernel may declare: that
+  // instantiation alone takes them as dynamic LDS, kAttnF32Lds128 bytes that launch_attention asks for)
+  float *sK, *sV;
+  if constexpr (DH == 128) {
+    extern __shared__ __attribute__((aligned(16))) float att_f32_lds[];
+    sK = att_f32_lds;
+    sV = att_f32_lds + 64 * LDK;
+  } else {
+    __shared__ float sK_tile[64 * LDK];
+    __shared__ float sV_tile[64 * LDK];
+    sK = sK_tile;
+    sV = sV_tile;
+  }
   const int seq = seq0 + blockIdx.x / qblocks;
   const int qb = blockIdx.x % qblocks;
   const int head = blockIdx.y;
@@ -4004,8 +4078,22 @@ __global__ __launch_bounds__(NW * 64) void attention_seq_kernel(const half_t* __
   constexpr int CH = DH / 8;    // 16-byte chunks per row
   // chunk c of K row r sits at c ^ kswz(r): the 16 rows x one chunk of a ds_read_b128 fragment read then cover all 64
   // banks once; chunk c of V row r at c ^ vswz(r): the 8 rows x 32 bytes of a transposed read (per 32-lane half) do
-  auto kswz = [](int r) { return DH == 64 ? (r >> 1) & 7 : (r >> 1) & 3; };
-  auto vswz = [](int r) { return DH == 64 ? ((r >> 1) & 3) << 1 : ((r >> 2) & 1) << 1; };
+  // d_h = 128: a row is 256 bytes, the whole bank row (bank = (a / 4) mod 64 for both reads), so every row starts at
+  // bank 0 and the chunk position alone decides the banks: position p covers banks 4p .. 4p + 3.
+  //  K: lane (qi, g) reads chunk 4u + g of row 16t + qi, and a ds_read_b128 is served in four 16-lane groups, lanes
+  //  {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same + 32: in each, qi takes all 16 values once, g one value on
+  //  the eight lanes qi in {0-3, 12-15} and its neighbour g ^ 1 on the eight qi in {4-11}. kswz(r) = r & 15 puts the
+  //  lane at position (4u + g) ^ qi: the first eight cover (4u + g) ^ {0-3, 12-15}, the others (4u + g) ^ 1 ^ {4-11} =
+  //  (4u + g) ^ {4-11} (x ^ 1 maps {4-11} onto itself) — all 16 positions, every bank once.
+  //  V: a transposed read is served per 32-lane half: 8 rows (4g + q, g in {0, 1} or {2, 3}: 0-7 or 8-15, behind a
+  //  multiple of 16) x the chunk pair (2s, 2s + 1) of each, 32 bytes. The swizzle must keep a pair together (bit 0
+  //  clear) and send the eight rows to eight different pairs: vswz(r) = (r & 7) << 1, pair s ^ (r & 7) — 8 x 32 bytes
+  //  over 256, every bank once. It depends on (4g + q) & 7 alone, as tr_sw below assumes.
+  //  The 16-byte stores are served in groups of 8 neighbouring lanes with bank = (a / 4) mod 32: the 8 chunks of one
+  //  half row, which either swizzle sends to the 8 positions of one half row again (bit 3 of the swizzle picks the
+  //  half, bits 0-2 permute inside it) — 128 bytes, 32 banks once.
+  auto kswz = [](int r) { return DH == 128 ? r & 15 : DH == 64 ? (r >> 1) & 7 : (r >> 1) & 3; };
+  auto vswz = [](int r) { return DH == 128 ? (r & 7) << 1 : DH == 64 ? ((r >> 1) & 3) << 1 : ((r >> 2) & 1) << 1; };
   constexpr int NS = DH / 16;   // 16-wide d blocks of the output
   constexpr int NKB = DH / 32;  // 32-deep MFMA steps over d
   extern __shared__ __attribute__((aligned(16))) half_t att_lds[];
@@ -4213,7 +4301,10 @@ __global__ __launch_bounds__(NW * 64) void attention_stream_kernel(const half_t*
   constexpr bool BIAS = BIAS_KIND == kBiasTable, SLOPES = BIAS_KIND == kBiasSlopes, CAUSAL = BIAS_KIND == kMaskCausal;
   static_assert(!(WIN && BIAS_KIND != kBiasNone), "a window needs pre-norm, a bias post-norm");
   const int window = WIN ? window_arg : 0;
-  static_assert(NW == 4 && (DH == 64 || DH == 32), "one 16-byte piece of a 64-key tile per thread and CH / NW rounds");
+  static_assert(NW == 4 && (DH == 128 || DH == 64 || DH == 32), "one 16-byte piece of a 64-key tile per thread and CH / NW rounds");
+  // (d_h = 128: the ring below is 4 x 64 x 128 halfs = 65,536 bytes, exactly the static limit; its two instantiations,
+  // kBiasNone and kMaskCausal, put nothing else in LDS — a table would)
+  static_assert(DH != 128 || BIAS_KIND == kBiasNone || BIAS_KIND == kMaskCausal, "head size 128 takes no table and no slopes");
   constexpr int LDK = DH;       // halfs per staged row: unpadded, 16-byte chunks XOR-swizzled by the row
   constexpr int CH = DH / 8;    // 16-byte chunks per row
   constexpr int NS = DH / 16;   // 16-wide d blocks of the output
@@ -4221,8 +4312,8 @@ __global__ __launch_bounds__(NW * 64) void attention_stream_kernel(const half_t*
   constexpr int NT = NW * 64;
   constexpr int NLD = 64 * CH / NT;  // 16-byte loads of K and of V per thread and tile
   constexpr int TILE = 64 * LDK;     // halfs of one K or V tile
-  auto kswz = [](int r) { return DH == 64 ? (r >> 1) & 7 : (r >> 1) & 3; };
-  auto vswz = [](int r) { return DH == 64 ? ((r >> 1) & 3) << 1 : ((r >> 2) & 1) << 1; };
+  auto kswz = [](int r) { return DH == 128 ? r & 15 : DH == 64 ? (r >> 1) & 7 : (r >> 1) & 3; };
+  auto vswz = [](int r) { return DH == 128 ? (r & 7) << 1 : DH == 64 ? ((r >> 1) & 3) << 1 : ((r >> 2) & 1) << 1; };
   __shared__ __attribute__((aligned(16))) half_t att_tiles[4 * TILE];  // buffer b: K at 2 b TILE, V at (2 b + 1) TILE
   const int n_heads = H / DH;
   const int head = static_cast<int>(blockIdx.x) % n_heads;
@@ -4542,16 +4633,21 @@ int encoder_hidden(vr_engine* e) {
 // The caller's description, zero-extended: a caller compiled against the header that ended at `precision` passes that
 // shorter struct_size, and gets what it always got (learned positions, the plain GELU FFN).
 // (vr_bert_desc_v2: the same description one field longer, `causal`; every shorter size reads it as 0)
-static int read_desc(const vr_bert_desc* src, vr_bert_desc* out, int32_t* causal = nullptr) {
+// (vr_bert_desc_v3: two fields more, `head_dim` and `qk_norm`, read as 0 from every shorter size as well)
+static int read_desc(const vr_bert_desc* src, vr_bert_desc* out, int32_t* causal = nullptr, int32_t* head_dim = nullptr,
+                     int32_t* qk_norm = nullptr) {
   const int32_t short_size = static_cast<int32_t>(offsetof(vr_bert_desc, position));
   const int32_t post_size = static_cast<int32_t>(offsetof(vr_bert_desc, norm));  // ... or at `ffn`: post-norm, no window
-  const bool v2 = src->struct_size == static_cast<int32_t>(sizeof(vr_bert_desc_v2));
+  const bool v3 = src->struct_size == static_cast<int32_t>(sizeof(vr_bert_desc_v3));
+  const bool v2 = v3 || src->struct_size == static_cast<int32_t>(sizeof(vr_bert_desc_v2));
   VR_CHECK(src->struct_size == static_cast<int32_t>(sizeof(vr_bert_desc)) || src->struct_size == short_size ||
                src->struct_size == post_size || v2,
            "vr_bert_desc size mismatch");
   *out = vr_bert_desc{};
   memcpy(out, src, v2 ? sizeof(vr_bert_desc) : static_cast<size_t>(src->struct_size));
   if (causal) *causal = v2 ? reinterpret_cast<const vr_bert_desc_v2*>(src)->causal : 0;
+  if (head_dim) *head_dim = v3 ? reinterpret_cast<const vr_bert_desc_v3*>(src)->head_dim : 0;
+  if (qk_norm) *qk_norm = v3 ? reinterpret_cast<const vr_bert_desc_v3*>(src)->qk_norm : 0;
   out->struct_size = static_cast<int32_t>(sizeof(vr_bert_desc));
   return 0;
 }
@@ -4570,8 +4666,8 @@ static const int kWindowStreamFrom = 384;
 // a model from its 5 + 16 L (gated FFN: 5 + 18 L) tensors (vr_encoder_load's order) into *slot, replacing what is there
 static int build_encoder(vr_engine* e, void** slot, const vr_bert_desc* d_in, const void* const* t, int n_tensors, int mem) {
   vr_bert_desc desc;
-  int32_t causal = 0;
-  VR_TRY(read_desc(d_in, &desc, &causal));
+  int32_t causal = 0, head_dim = 0, qk_norm = 0;
+  VR_TRY(read_desc(d_in, &desc, &causal, &head_dim, &qk_norm));
   const vr_bert_desc* d = &desc;
   const int H = d->hidden, I = d->intermediate, L = d->layers;
   VR_CHECK(d->position == VR_POS_LEARNED || d->position == VR_POS_ROTARY || d->position == VR_POS_NONE,
@@ -4579,7 +4675,7 @@ static int build_encoder(vr_engine* e, void** slot, const vr_bert_desc* d_in, co
   VR_CHECK(d->ffn == VR_FFN_GELU || d->ffn == VR_FFN_SWIGLU || d->ffn == VR_FFN_GEGLU || d->ffn == VR_FFN_RELU,
            "unknown ffn kind %d", d->ffn);
   const bool rotary = d->position == VR_POS_ROTARY, gated = d->ffn == VR_FFN_SWIGLU || d->ffn == VR_FFN_GEGLU;
-  const int per_layer = gated ? 18 : 16;
+  const int per_layer = (gated ? 18 : 16) + (qk_norm == 1 ? 2 : 0);  // (qk_norm: VR_NORM_PRE_RMS_ROTARY only, which is gated)
   VR_CHECK(!rotary || (std::isfinite(d->rope_theta) && d->rope_theta > 0.0f), "rope_theta %g must be positive",
            static_cast<double>(d->rope_theta));
   VR_CHECK(d->norm == VR_NORM_POST || d->norm == VR_NORM_PRE || d->norm == VR_NORM_PRE_RMS || d->norm == VR_NORM_PRE_RMS_ROTARY,
@@ -4594,6 +4690,14 @@ static int build_encoder(vr_engine* e, void** slot, const vr_bert_desc* d_in, co
   VR_CHECK(causal == 0 || causal == 1, "causal %d must be 0 or 1", causal);
   VR_CHECK(causal == 0 || rms_rot, "causal %d needs norm VR_NORM_PRE_RMS_ROTARY (norm %d): the causal mask exists in that "
            "loop only", causal, d->norm);
+  // (vr_bert_desc_v3: a head size of its own and the Q/K norms, Qwen3's, in that loop only as well)
+  VR_CHECK(head_dim == 0 || rms_rot, "head_dim %d needs norm VR_NORM_PRE_RMS_ROTARY (norm %d): a head size other than "
+           "hidden / heads exists in that loop only", head_dim, d->norm);
+  VR_CHECK(head_dim == 0 || head_dim == 32 || head_dim == 64 || head_dim == 128, "head_dim %d must be 0 (hidden / heads), 32, "
+           "64 or 128", head_dim);
+  VR_CHECK(qk_norm == 0 || qk_norm == 1, "qk_norm %d must be 0 or 1", qk_norm);
+  VR_CHECK(qk_norm == 0 || rms_rot, "qk_norm %d needs norm VR_NORM_PRE_RMS_ROTARY (norm %d): the query / key norms exist in "
+           "that loop only", qk_norm, d->norm);
   // (the T5 form: one combination, everything outside it refused by the field that leaves it)
   VR_CHECK(!rms || d->position == VR_POS_NONE, "norm VR_NORM_PRE_RMS needs position VR_POS_NONE (position %d): RMSNorm "
            "encoders with a position table or rotary positions are not implemented", d->position);
@@ -4625,8 +4729,16 @@ static int build_encoder(vr_engine* e, void** slot, const vr_bert_desc* d_in, co
            d->max_pos);
   VR_CHECK(L >= 1 && H >= 128 && H % 128 == 0 && H <= 1024, "hidden %d must be a multiple of 128 in 128..1024", H);
   VR_CHECK(I % 128 == 0 && I % BK == 0, "intermediate %d must be a multiple of 128", I);
-  VR_CHECK(d->heads >= 1 && H % d->heads == 0 && (H / d->heads == 32 || H / d->heads == 64),
-           "head size %d unsupported (32 or 64)", d->heads ? H / d->heads : 0);
+  if (head_dim == 0)
+    VR_CHECK(d->heads >= 1 && H % d->heads == 0 && (H / d->heads == 32 || H / d->heads == 64),
+             "head size %d unsupported (32 or 64)", d->heads ? H / d->heads : 0);
+  VR_CHECK(d->heads >= 1, "heads %d must be >= 1", d->heads);
+  // the attention width: the [Q | K | V] rows are 3 A wide, the context A (A == H unless head_dim says otherwise)
+  const int dh = head_dim ? head_dim : H / d->heads;
+  const int64_t A64 = static_cast<int64_t>(d->heads) * dh;
+  VR_CHECK(A64 % 128 == 0 && A64 <= 2048, "heads %d x head_dim %d = %lld: the attention width must be a multiple of 128 and at "
+           "most 2048", d->heads, dh, static_cast<long long>(A64));
+  const int A = static_cast<int>(A64);
   VR_CHECK(n_tensors == 5 + per_layer * L, "expected %d tensors, got %d", 5 + per_layer * L, n_tensors);
   VR_CHECK(d->pooling == VR_POOL_MEAN || d->pooling == VR_POOL_CLS || d->pooling == VR_POOL_LAST,
            "pooling %d must be 0 (mean), 1 (cls) or 2 (last token)", d->pooling);
@@ -4638,6 +4750,7 @@ static int build_encoder(vr_engine* e, void** slot, const vr_bert_desc* d_in, co
                       in_layer == 13 || in_layer == 17;
     // (RMSNorm reads no shift, and its stream takes a missing token-type row as zeros)
     const bool rms_unused = (rms || rms_rot) && (i == 2 || i == 4 || in_layer == 9 || in_layer == 15);
+    // (in_layer 18, 19: the Q/K norm weights, never null)
     VR_CHECK(t[i] != nullptr || bias || rms_unused || (i == 1 && d->position != VR_POS_LEARNED), "tensor %d is null", i);
   }
   int window_stream_from = kWindowStreamFrom;  // (checked here: nothing is replaced when it is refused)
@@ -4653,14 +4766,17 @@ static int build_encoder(vr_engine* e, void** slot, const vr_bert_desc* d_in, co
   *slot = enc;
   enc->d = *d;
   enc->causal = causal;
+  enc->dh = dh;
+  enc->attn = A;
+  enc->qk_norm = qk_norm;
   enc->fuse = !(getenv("VR_ENCODE_FUSE") && atoi(getenv("VR_ENCODE_FUSE")) == 0);
-  const size_t HH = static_cast<size_t>(H) * H;
+  const size_t HH = static_cast<size_t>(A) * H;  // a projection's weights: [A, H] (query, key, value) or [H, A] (output)
   VR_TRY(dev_alloc_copy(e, enc, t[0], static_cast<size_t>(d->vocab) * H, mem, &enc->word));
   if (d->position == VR_POS_LEARNED) VR_TRY(dev_alloc_copy(e, enc, t[1], static_cast<size_t>(d->max_pos) * H, mem, &enc->pos));
   std::vector<float2> rope_host[2];  // (live until the synchronisation at the end: they are sources of async copies)
   auto rope_table = [&](float theta, std::vector<float2>& host, float2** out) -> int {
     // (cos, sin)(p * theta^(-2i/d_h)) in f64, stored as f32
-    const int half = H / d->heads / 2, row = H / 2;  // a row repeats the d_h/2 frequencies for every head
+    const int half = dh / 2, row = A / 2;  // a row repeats the d_h/2 frequencies for every head
     host.resize(static_cast<size_t>(d->max_pos) * row);
     for (int i = 0; i < half; ++i) {
       const double inv_freq = std::pow(static_cast<double>(theta), -2.0 * i / (2.0 * half));
@@ -4695,11 +4811,15 @@ static int build_encoder(vr_engine* e, void** slot, const vr_bert_desc* d_in, co
     const int N1 = gated ? 2 * I : I;  // rows of the FFN-up matrix: gated = the gate's I rows, then the up projection's
     LayerWeights lw{};
     VR_TRY(dev_alloc_copy(e, enc, nullptr, 3 * HH, mem, &lw.wqkv));
-    VR_TRY(dev_alloc_copy(e, enc, nullptr, 3 * static_cast<size_t>(H), mem, &lw.bqkv));
-    for (int p = 0; p < 3; ++p) {  // fused QKV projection: rows [0,H) = query, [H,2H) = key, [2H,3H) = value
+    VR_TRY(dev_alloc_copy(e, enc, nullptr, 3 * static_cast<size_t>(A), mem, &lw.bqkv));
+    for (int p = 0; p < 3; ++p) {  // fused QKV projection: rows [0,A) = query, [A,2A) = key, [2A,3A) = value (A = H but for head_dim)
       VR_HIP(hipMemcpyAsync(lw.wqkv + p * HH, w[2 * p], HH * sizeof(float), kind, e->stream));
-      if (w[2 * p + 1]) VR_HIP(hipMemcpyAsync(lw.bqkv + p * H, w[2 * p + 1], H * sizeof(float), kind, e->stream));
-      else VR_HIP(hipMemsetAsync(lw.bqkv + p * H, 0, H * sizeof(float), e->stream));
+      if (w[2 * p + 1]) VR_HIP(hipMemcpyAsync(lw.bqkv + p * A, w[2 * p + 1], A * sizeof(float), kind, e->stream));
+      else VR_HIP(hipMemsetAsync(lw.bqkv + p * A, 0, A * sizeof(float), e->stream));
+    }
+    if (qk_norm) {
+      VR_TRY(dev_alloc_copy(e, enc, w[18], dh, mem, &lw.qn));
+      VR_TRY(dev_alloc_copy(e, enc, w[19], dh, mem, &lw.kn));
     }
     VR_TRY(dev_alloc_copy(e, enc, w[6], HH, mem, &lw.wo));
     VR_TRY(dev_alloc_copy_or_zero(e, enc, w[7], H, mem, &lw.bo));
@@ -4727,7 +4847,7 @@ static int build_encoder(vr_engine* e, void** slot, const vr_bert_desc* d_in, co
     if (d->precision != VR_PRECISION_F32) {
       const bool plain = d->precision == VR_PRECISION_F16;
       VR_TRY(make_split(e, enc, lw.wqkv, 3 * HH, H, plain, &lw.s_qkv));
-      VR_TRY(make_split(e, enc, lw.wo, HH, H, plain, &lw.s_o));
+      VR_TRY(make_split(e, enc, lw.wo, HH, A, plain, &lw.s_o));
       VR_TRY(make_split(e, enc, lw.w1, static_cast<size_t>(N1) * H, H, plain, &lw.s_1));
       VR_TRY(make_split(e, enc, lw.w2, static_cast<size_t>(I) * H, I, plain, &lw.s_2));
       if (plain && (rotary || gated) && enc->fuse) {  // the re-ordered matrices and biases of the fused epilogues
@@ -4746,7 +4866,8 @@ static int build_encoder(vr_engine* e, void** slot, const vr_bert_desc* d_in, co
           (void)hipFree(tmp);
           return rc;
         };
-        if (rotary) VR_TRY(reordered(lw.wqkv, lw.bqkv, 3 * H, 0, H, &lw.s_qkv_p, &lw.bqkv_p));
+        // (the rotating epilogues: not behind a Q/K norm, which needs a whole head first, nor at a width other than H)
+        if (rotary && !qk_norm && A == H) VR_TRY(reordered(lw.wqkv, lw.bqkv, 3 * H, 0, H, &lw.s_qkv_p, &lw.bqkv_p));
         if (gated) VR_TRY(reordered(lw.w1, lw.b1, 2 * I, 1, I, &lw.s_1_p, &lw.b1_p));
       }
       if (plain && H % 64 == 0 && !prenorm && !rms && !rms_rot) {  // operands of the folded-LayerNorm GEMMs (the post-norm loop's)
@@ -4959,10 +5080,12 @@ int encoder_out_dim(vr_engine* e) {
 
 int reranker_load(vr_engine* e, const vr_bert_desc* d_in, const void* const* t, int n_tensors, int mem) {
   vr_bert_desc desc;
-  int32_t causal = 0;
-  VR_TRY(read_desc(d_in, &desc, &causal));
+  int32_t causal = 0, head_dim = 0, qk_norm = 0;
+  VR_TRY(read_desc(d_in, &desc, &causal, &head_dim, &qk_norm));
   const vr_bert_desc* d = &desc;
   VR_CHECK(causal == 0, "a reranker takes no causal mask (causal %d)", causal);
+  VR_CHECK(head_dim == 0, "a reranker takes no head size of its own (head_dim %d)", head_dim);
+  VR_CHECK(qk_norm == 0, "a reranker takes no query / key norms (qk_norm %d)", qk_norm);
   // a pre-norm, rotary, gated description is a ModernBERT cross-encoder: its own head (6 tensors), CLS or mean pooling
   const bool modern = d->norm == VR_NORM_PRE && d->position == VR_POS_ROTARY && d->ffn != VR_FFN_GELU;
   VR_CHECK(d->norm != VR_NORM_PRE_RMS, "a reranker with norm VR_NORM_PRE_RMS is not supported (norm %d): T5 cross-encoders "
@@ -5028,10 +5151,12 @@ static int ensure_workspace(vr_engine* e, Encoder* enc, int64_t tokens) {
     }
   }
   const size_t H = static_cast<size_t>(enc->d.hidden), I = static_cast<size_t>(enc->d.intermediate);
+  const size_t A = static_cast<size_t>(enc->attn);  // the attention width: H for every family but Qwen3 (vr_bert_desc_v3.head_dim)
   const size_t T = static_cast<size_t>(tokens);
   VR_TRY(dev_alloc_copy(e, enc, nullptr, T * H, 0, &enc->x));
-  VR_TRY(dev_alloc_copy(e, enc, nullptr, T * 3 * H, 0, &enc->qkv));
-  VR_TRY(dev_alloc_copy(e, enc, nullptr, T * H, 0, &enc->ctx));
+  VR_TRY(dev_alloc_copy(e, enc, nullptr, T * 3 * A, 0, &enc->qkv));
+  // (the context, A wide — and in f32 mode the normalised rows a projection reads, H wide)
+  VR_TRY(dev_alloc_copy(e, enc, nullptr, T * std::max(A, H), 0, &enc->ctx));
   VR_TRY(dev_alloc_copy(e, enc, nullptr, T * H, 0, &enc->tmp));
   VR_TRY(dev_alloc_copy(e, enc, nullptr, T * I, 0, &enc->ffn));
   if (enc->d.precision != VR_PRECISION_F32) VR_TRY(dev_alloc_copy(e, enc, nullptr, T * H, 0, &enc->xs));
@@ -5049,7 +5174,9 @@ static int ensure_workspace(vr_engine* e, Encoder* enc, int64_t tokens) {
 static int launch_attention(vr_engine* e, Encoder* enc, const int32_t* cu_dev, int seq0, int n_seq, int tok_base,
                             int max_len, bool tail, int window, double attn_flop) {
   const vr_bert_desc& d = enc->d;
-  const int H = d.hidden, nh = d.heads, dh = H / nh;
+  // (H: the width of a third of the Q/K/V row and of the context row — the attention width, the hidden size for
+  // every family but Qwen3; dh: the head size, hidden / heads unless vr_bert_desc_v3.head_dim says otherwise)
+  const int H = enc->attn, nh = d.heads, dh = enc->dh;
   hipStream_t s = e->stream;
   const bool split = d.precision != VR_PRECISION_F32;
   const bool plain = d.precision == VR_PRECISION_F16;
@@ -5066,6 +5193,12 @@ static int launch_attention(vr_engine* e, Encoder* enc, const int32_t* cu_dev, i
   VR_CHECK(!(bias && window > 0), "an attention bias and a window %d cannot meet", window);
   // (the causal mask is BIAS_KIND's fourth state: its norm, VR_NORM_PRE_RMS_ROTARY, has no window and takes no bias)
   VR_CHECK(!(enc->causal && (bias || window > 0)), "a causal mask meets neither a bias nor a window %d", window);
+  // head size 128 (vr_bert_desc_v3.head_dim: VR_NORM_PRE_RMS_ROTARY alone reaches it) exists in that norm's two states
+  VR_CHECK(dh != 128 || !(bias || window > 0), "head size 128 meets neither a bias nor a window %d", window);
+  auto plain_or_causal = [&](auto launch) {
+    if (enc->causal) launch(std::integral_constant<int, kMaskCausal>{});
+    else launch(std::integral_constant<int, kBiasNone>{});
+  };
   auto windowed = [&](auto launch) {
     if (enc->causal) launch(std::false_type{}, std::integral_constant<int, kMaskCausal>{});
     else if (table) launch(std::false_type{}, std::integral_constant<int, kBiasTable>{});
@@ -5090,9 +5223,12 @@ static int launch_attention(vr_engine* e, Encoder* enc, const int32_t* cu_dev, i
   }
   // (a windowed layer: the streamed kernel from enc->window_stream_from tokens on, see build_encoder)
   if (plain && lds_bytes <= lds_limit && !(window > 0 && max_len >= enc->window_stream_from)) {
-    static size_t lds_allowed[2] = {0, 0};  // per instantiation: raised above the 64 KiB default when a sequence needs it
-    const int which = dh == 64 ? 0 : 1;
+    static size_t lds_allowed[3] = {0, 0, 0};  // per instantiation: raised above the 64 KiB default when a sequence needs it
+    const int which = dh == 64 ? 0 : dh == 32 ? 1 : 2;
     if (lds_bytes > 65536 && lds_bytes > lds_allowed[which]) {
+      for (const void* f : {reinterpret_cast<const void*>(&attention_seq_kernel<128, 4, false, kBiasNone>),
+                            reinterpret_cast<const void*>(&attention_seq_kernel<128, 4, false, kMaskCausal>)})
+        if (dh == 128) VR_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_bytes)));
       for (const void* f : {reinterpret_cast<const void*>(&attention_seq_kernel<64, 4, false, kBiasNone>),
                             reinterpret_cast<const void*>(&attention_seq_kernel<64, 4, true, kBiasNone>),
                             reinterpret_cast<const void*>(&attention_seq_kernel<64, 4, false, kBiasTable>),
@@ -5104,12 +5240,17 @@ static int launch_attention(vr_engine* e, Encoder* enc, const int32_t* cu_dev, i
                             reinterpret_cast<const void*>(&attention_seq_kernel<32, 4, false, kBiasTable>),
                             reinterpret_cast<const void*>(&attention_seq_kernel<32, 4, false, kBiasSlopes>),
                             reinterpret_cast<const void*>(&attention_seq_kernel<32, 4, false, kMaskCausal>)})
-        if (dh != 64) VR_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_bytes)));
+        if (dh == 32) VR_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds_bytes)));
       lds_allowed[which] = lds_bytes;
     }
     const dim3 sgrid(static_cast<unsigned>(n_seq) * static_cast<unsigned>(nh));
     const int q_limit = tail ? 16 : max_len;
-    windowed([&](auto W, auto B) {
+    if (dh == 128)
+      plain_or_causal([&](auto B) {
+        hipLaunchKernelGGL((attention_seq_kernel<128, 4, false, decltype(B)::value>), sgrid, dim3(256), lds_bytes, s,
+                           reinterpret_cast<const half_t*>(enc->qkv), cu_dev, seq0, tok_base, H, scale, q_limit, lds_keys, ch, 0, bias, radius);
+      });
+    else windowed([&](auto W, auto B) {
       constexpr bool kWin = decltype(W)::value;
       constexpr int kBias = decltype(B)::value;
       if (dh == 64)
@@ -5123,7 +5264,12 @@ static int launch_attention(vr_engine* e, Encoder* enc, const int32_t* cu_dev, i
     const int qb128 = tail ? 1 : (max_len + 127) / 128;
     const dim3 sgrid(static_cast<unsigned>(n_seq) * static_cast<unsigned>(qb128) * static_cast<unsigned>(nh));
     const int q_limit = tail ? 16 : max_len;
-    windowed([&](auto W, auto B) {
+    if (dh == 128)
+      plain_or_causal([&](auto B) {
+        hipLaunchKernelGGL((attention_stream_kernel<128, 4, false, decltype(B)::value>), sgrid, dim3(256), 0, s,
+                           reinterpret_cast<const half_t*>(enc->qkv), cu_dev, seq0, tok_base, H, qb128, scale, q_limit, ch, 0, bias, radius);
+      });
+    else windowed([&](auto W, auto B) {
       constexpr bool kWin = decltype(W)::value;
       constexpr int kBias = decltype(B)::value;
       if (dh == 64)
@@ -5134,6 +5280,19 @@ static int launch_attention(vr_engine* e, Encoder* enc, const int32_t* cu_dev, i
                            cu_dev, seq0, tok_base, H, qb128, scale, q_limit, ch, window, bias, radius);
     });
   } else {
+    if (dh == 128) {  // its two tiles as dynamic LDS, above the 64 KiB default: allowed once per instantiation
+      static bool lds128_allowed = false;
+      if (!lds128_allowed) {
+        for (const void* f : {reinterpret_cast<const void*>(&attention_kernel<128, false, kBiasNone>),
+                              reinterpret_cast<const void*>(&attention_kernel<128, false, kMaskCausal>)})
+          VR_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kAttnF32Lds128)));
+        lds128_allowed = true;
+      }
+      plain_or_causal([&](auto B) {
+        hipLaunchKernelGGL((attention_kernel<128, false, decltype(B)::value>), agrid, dim3(256), kAttnF32Lds128, s, enc->qkv, cu_dev, seq0,
+                           tok_base, H, qb, scale, enc->ctx, ch, cl, 0, bias, radius);
+      });
+    } else
     windowed([&](auto W, auto B) {
       constexpr bool kWin = decltype(W)::value;
       constexpr int kBias = decltype(B)::value;
@@ -5493,7 +5652,9 @@ static int forward_chunk_rms_rotary(vr_engine* e, Encoder* enc, const int32_t* i
                                     int seq0, int seq1, int tok_base, int T, int max_len, double attn_flop, float* out_dev,
                                     const Spans* sp) {
   const vr_bert_desc& d = enc->d;
-  const int H = d.hidden, I = d.intermediate, dh = H / d.heads, N1 = 2 * I;
+  // A: the attention width — the [Q | K | V] row is 3 A, the context A (A == H but for vr_bert_desc_v3.head_dim)
+  const int H = d.hidden, I = d.intermediate, dh = enc->dh, A = enc->attn, N1 = 2 * I;
+  const bool qk_norm = enc->qk_norm != 0;
   hipStream_t s = e->stream;
   const unsigned row_blocks = static_cast<unsigned>((T + 3) / 4);
   const bool split = d.precision != VR_PRECISION_F32;
@@ -5511,8 +5672,10 @@ static int forward_chunk_rms_rotary(vr_engine* e, Encoder* enc, const int32_t* i
   const int32_t* posidx = reinterpret_cast<const int32_t*>(enc->posidx);
   float2* stat = reinterpret_cast<float2*>(enc->lnstat);  // (launch_skinny_ln stores the rows' 1/rms; nobody reads them)
   const bool fuse = plain && enc->fuse;
-  const bool fold_ln = plain && skinny_rms_rotary_supported(T, 3 * H, H) && I % 16 == 0;
-  const bool fuse_rope = fuse && skinny_routed(T, 3 * H, H);
+  const bool fold_ln = plain && skinny_rms_rotary_supported(T, 3 * A, H) && I % 16 == 0;
+  // (the rotating Q/K/V epilogues: not behind a Q/K norm, which needs a whole head before the rotation — those models
+  // take the plain epilogues and qk_norm_rope_kernel at every size — and, as they are, at A == H only)
+  const bool fuse_rope = fuse && !qk_norm && A == H && skinny_routed(T, 3 * H, H);
   const bool fuse_glu = fuse && skinny_routed(T, N1, H);
   const int glu_epi = d.ffn == VR_FFN_SWIGLU ? EPI_SWIGLU_F16 : EPI_GEGLU_F16;
   // the [T, 2I] pre-activation of the unfused gate (never allocated during a graph capture: a shape runs eagerly first)
@@ -5548,34 +5711,41 @@ static int forward_chunk_rms_rotary(vr_engine* e, Encoder* enc, const int32_t* i
                                  .rope_tab = enc->rope, .rope_pos = posidx}, true));
       else
         VR_TRY(launch_skinny_ln(e, EPI_BIAS_F16, h, d.eps, stat,
-                                {.W = w.s_qkv, .bias = w.bqkv, .Ch = qkvh, .M = T, .N = 3 * H, .K = H, .ln_g = g}, true));
+                                {.W = w.s_qkv, .bias = w.bqkv, .Ch = qkvh, .M = T, .N = 3 * A, .K = H, .ln_g = g}, true));
     } else {
       if (li > 0) norm_rows(h, enc->layers[li - 1].ln2g);
       if (fuse_rope)
         VR_TRY(launch_gemm_f16x3(e, enc, EPI_ROPE_F16, {.A = xh, .W = w.s_qkv_p, .bias = w.bqkv_p, .Ch = qkvh, .M = T, .N = 3 * H,
                                                         .K = H, .passes = 1, .rope_tab = enc->rope, .rope_pos = posidx}));
       else if (plain)
-        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_F16, {.A = xh, .W = w.s_qkv, .bias = w.bqkv, .Ch = qkvh, .M = T, .N = 3 * H,
+        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_F16, {.A = xh, .W = w.s_qkv, .bias = w.bqkv, .Ch = qkvh, .M = T, .N = 3 * A,
                                                         .K = H, .passes = 1}));
       else if (split)
         VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS, {.A = xh, .A_lo = xl, .W = w.s_qkv, .bias = w.bqkv, .C = enc->qkv, .M = T,
-                                                    .N = 3 * H, .K = H, .passes = passes}));
+                                                    .N = 3 * A, .K = H, .passes = passes}));
       else
-        VR_TRY(launch_gemm(e, EPI_BIAS, enc->ctx, w.wqkv, w.bqkv, nullptr, enc->qkv, T, 3 * H, H));
+        VR_TRY(launch_gemm(e, EPI_BIAS, enc->ctx, w.wqkv, w.bqkv, nullptr, enc->qkv, T, 3 * A, H));
     }
-    if (!fuse_rope) {  // the rotation as a pass of its own
+    if (qk_norm) {  // the per-head norm of Q and K and the rotation, one pass
       if (plain)
-        hipLaunchKernelGGL(rope_kernel<half_t>, dim3(row_blocks), dim3(256), 0, s, qkvh, posidx, T, H, dh, enc->rope);
+        hipLaunchKernelGGL(qk_norm_rope_kernel<half_t>, dim3(row_blocks), dim3(256), 0, s, qkvh, posidx, T, A, dh, enc->rope, w.qn,
+                           w.kn, d.eps);
       else
-        hipLaunchKernelGGL(rope_kernel<float>, dim3(row_blocks), dim3(256), 0, s, enc->qkv, posidx, T, H, dh, enc->rope);
+        hipLaunchKernelGGL(qk_norm_rope_kernel<float>, dim3(row_blocks), dim3(256), 0, s, enc->qkv, posidx, T, A, dh, enc->rope, w.qn,
+                           w.kn, d.eps);
+    } else if (!fuse_rope) {  // the rotation as a pass of its own
+      if (plain)
+        hipLaunchKernelGGL(rope_kernel<half_t>, dim3(row_blocks), dim3(256), 0, s, qkvh, posidx, T, A, dh, enc->rope);
+      else
+        hipLaunchKernelGGL(rope_kernel<float>, dim3(row_blocks), dim3(256), 0, s, enc->qkv, posidx, T, A, dh, enc->rope);
     }
     VR_TRY(launch_attention(e, enc, cu_dev, seq0, n_seq, tok_base, max_len, false, 0, layer_flop));
     // h' = h + W_o ctx
     if (split)
       VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_RESIDUAL, {.A = ch, .A_lo = cl, .W = w.s_o, .bias = w.bo, .R = h, .C = other, .M = T,
-                                                           .N = H, .K = H, .passes = passes}));
+                                                           .N = H, .K = A, .passes = passes}));
     else
-      VR_TRY(launch_gemm(e, EPI_BIAS_RESIDUAL, enc->ctx, w.wo, w.bo, h, other, T, H, H));
+      VR_TRY(launch_gemm(e, EPI_BIAS_RESIDUAL, enc->ctx, w.wo, w.bo, h, other, T, H, A));
     std::swap(h, other);
     // the gated FFN of N_m(h)
     if (fold_ln && fuse_glu) {

@@ -101,9 +101,18 @@ def _read_family_config(path: str, cfg: dict) -> dict:
         return _read_t5_config(path, cfg)
     if kind == "qwen2":
         return _read_qwen2_config(path, cfg)
+    unsupported = (f"unsupported model_type {kind}: BERT, DistilBERT, XLM-RoBERTa, MPNet, T5, nomic_bert and "
+                   "modernbert encoders only, and Qwen2 decoder embedders (the 0.5B body) and Qwen3 decoder "
+                   "embedders (the 0.6B body)")
+    if kind == "qwen3":
+        # a directory that names its classes must name Qwen3 ones (Qwen3Model, Qwen3ForCausalLM): another family's
+        # weights under this model_type have no q_norm / k_norm and would be refused tensor by tensor much later
+        archs = [str(a) for a in cfg.get("architectures") or []]
+        if archs and not any(a.startswith("Qwen3") for a in archs):
+            raise ValueError(f"{unsupported}; architectures {archs} is not a Qwen3 model")
+        return _read_qwen3_config(path, cfg)
     if kind not in ("bert", "xlm-roberta"):
-        raise ValueError(f"unsupported model_type {kind}: BERT, DistilBERT, XLM-RoBERTa, MPNet, T5, nomic_bert and "
-                         "modernbert encoders only, and Qwen2 decoder embedders (the 0.5B body)")
+        raise ValueError(unsupported)
     if kind == "bert" and cfg.get("position_embedding_type", "absolute") == "alibi":
         return _read_alibi_config(path, cfg)
     if cfg.get("hidden_act", "gelu") != "gelu" or cfg.get("position_embedding_type", "absolute") != "absolute":
@@ -341,6 +350,57 @@ def _read_qwen2_config(path: str, cfg: dict) -> dict:
     return {"desc": desc, "max_seq": max_seq, "pos_start": 0, "config": cfg, "kv_heads": kv_heads}
 
 
+def _read_qwen3_config(path: str, cfg: dict) -> dict:
+    """model_type qwen3 (Qwen3-Embedding-0.6B and its fine-tunes): the Qwen2 body with a head size of its own — head_dim,
+    128 for the 0.6B body, so that q_proj is hidden -> heads * head_dim and o_proj the way back — and an RMSNorm over
+    every head of the query and of the key ahead of the rotation (q_norm / k_norm, [head_dim], shared by the heads).
+    attention_bias (false for these models) says whether q/k/v carry biases. Grouped-query attention is resolved at load
+    (encoder.qwen3_slots), pooling, causality and the longest sequence are read as for qwen2."""
+    H, heads = int(cfg["hidden_size"]), int(cfg["num_attention_heads"])
+    kv_heads = int(cfg.get("num_key_value_heads") or heads)
+    if heads < 1 or kv_heads < 1 or heads % kv_heads:
+        raise ValueError(f"num_attention_heads {heads} is not a multiple of num_key_value_heads {kv_heads}")
+    head_dim = int(cfg["head_dim"]) if cfg.get("head_dim") is not None else (H // heads if H % heads == 0 else 0)
+    if head_dim not in (32, 64, 128):
+        raise ValueError(f"head_dim {head_dim} is not implemented: the attention kernels run head sizes 32, 64 and 128")
+    if heads * head_dim > 2048 or (heads * head_dim) % 128:
+        raise ValueError(f"num_attention_heads {heads} x head_dim {head_dim} = {heads * head_dim} is not implemented: the "
+                         "attention width must be a multiple of 128 and at most 2048")
+    if H % 128 or H > 1024:
+        raise ValueError(f"hidden_size {H} is not implemented: the engine runs multiples of 128 up to 1024 (the "
+                         "Qwen3-Embedding-0.6B body is 1024)")
+    act = cfg.get("hidden_act", "silu")
+    if act != "silu":
+        raise ValueError(f"hidden_act {act!r} is not implemented: a qwen3 FFN is down(silu(gate(x)) * up(x))")
+    rp = cfg.get("rope_parameters") or {}
+    rope_type = rp.get("rope_type", rp.get("type", "default"))
+    if cfg.get("rope_scaling") is not None or rope_type != "default":
+        raise ValueError(f"rope_scaling {cfg.get('rope_scaling') or rope_type!r} is not implemented: only the default rotary "
+                         "embedding (no scaling)")
+    if cfg.get("use_sliding_window", False):
+        raise ValueError("use_sliding_window true is not implemented: a causal sliding window is not in the attention "
+                         "kernels")
+    declared = int(cfg.get("max_position_embeddings", 32768))
+    pooling, normalize, max_seq = _read_modules(path, declared)
+    max_seq = min(max_seq, declared)
+    cap = seq_cap()
+    if max_seq > cap:
+        logger.warning("%s declares sequences of up to %d tokens; the engine runs at most %d: longer texts are "
+                       "truncated to %d tokens (%s raises the cap, up to %d)", path, max_seq, cap, cap, SEQ_CAP_VARIABLE,
+                       MAX_SEQ_LENGTH_LIMIT)
+        max_seq = cap
+    desc = _enc.BertDesc(layers=int(cfg["num_hidden_layers"]), hidden=H, heads=heads,
+                         intermediate=int(cfg["intermediate_size"]), vocab=int(cfg["vocab_size"]),
+                         max_pos=max_seq,  # rotary: the length of the cos/sin table
+                         type_vocab=1, pooling=pooling, normalize=normalize, eps=float(cfg.get("rms_norm_eps", 1e-6)),
+                         precision=os.environ.get("VOITTA_ENCODER_PRECISION", "f16"), position="rotary",
+                         rope_theta=float(rp.get("rope_theta", cfg.get("rope_theta", 10000.0))), ffn="swiglu",
+                         norm="rms_pre_rotary", causal=0 if cfg.get("is_causal", True) is False else 1,
+                         head_dim=head_dim, qk_norm=1)
+    return {"desc": desc, "max_seq": max_seq, "pos_start": 0, "config": cfg, "kv_heads": kv_heads,
+            "attention_bias": bool(cfg.get("attention_bias", False))}
+
+
 def _read_mpnet_config(path: str, cfg: dict) -> dict:
     """model_type mpnet (all-mpnet-base-v2, multi-qa-mpnet-*, paraphrase-mpnet-*): a post-LayerNorm BERT with exact-erf
     GELU, no token types, learned positions from row padding_idx + 1 = 2 on (as XLM-R's), and one relative-position
@@ -565,8 +625,8 @@ class NativeSentenceEncoder:
             rc["desc"].attention_bias = _enc.t5_bias_table(
                 _enc._find(state, "encoder.block.0.layer.0.SelfAttention.relative_attention_bias.weight"),
                 rc["buckets"], rc["max_distance"])
-        elif rc["config"].get("model_type") == "qwen2":
-            state = cls._load_weights(path)  # (load_encoder's qwen2_slots maps the weights and repeats the K/V heads)
+        elif rc["config"].get("model_type") in ("qwen2", "qwen3"):
+            state = cls._load_weights(path)  # (load_encoder's qwen2_slots / qwen3_slots maps the weights and repeats the K/V heads)
         else:
             state = slice_positions(cls._load_weights(path), rc["pos_start"])
         return cls(engine or get_engine(), rc["desc"], state, cls._load_tokenizer(path, rc["config"]), rc["max_seq"])
@@ -591,7 +651,7 @@ class NativeSentenceEncoder:
         pipeline wrapped in <s> ... </s>, the names read from tokenizer.json's post_processor), the native Unigram
         (csrc/unigram.cpp)
         for the XLM-R pipeline of an XLM-R model and the same pipeline with the template $A </s> of a T5 model, the
-        native byte-level BPE (csrc/bpe.cpp) for a ModernBERT or Qwen2 model's pipeline where it accepts it (Qwen's own
+        native byte-level BPE (csrc/bpe.cpp) for a ModernBERT, Qwen2 or Qwen3 model's pipeline where it accepts it (Qwen's own
         pre-tokenizer pattern it refuses); anything else that a tokenizer.json may describe (a BERT model with a Unigram tokenizer.json among
         them, as before) goes through the HF `tokenizers` library."""
         tj = os.path.join(path, "tokenizer.json")
@@ -601,7 +661,7 @@ class NativeSentenceEncoder:
                 if is_unigram_pipeline(spec):
                     return UnigramTokenizer.from_tokenizer_json(spec)
                 logger.info("native Unigram not applicable; using the tokenizers library")
-        if os.path.exists(tj) and cfg.get("model_type") in ("modernbert", "qwen2"):
+        if os.path.exists(tj) and cfg.get("model_type") in ("modernbert", "qwen2", "qwen3"):
             spec = json.load(open(tj, encoding="utf-8"))
             if (spec.get("model") or {}).get("type") == "BPE":
                 try:

@@ -101,6 +101,11 @@ class BertDesc:
     global_every: int = 0  # window > 0: layer l attends globally iff l % global_every == 0
     rope_theta_local: float = 0.0  # the rotary base of the windowed layers; 0 = rope_theta
     causal: int = 0  # 1: query i sees key j iff j <= i (norm "rms_pre_rotary" only)
+    # the head size when it is not hidden / heads (32, 64 or 128; 0 = hidden / heads): q/k/v are then [heads * head_dim,
+    # hidden] and o_proj [hidden, heads * head_dim]; and whether every head of Q and K is RMS-normalised and scaled by
+    # q_norm / k_norm [head_dim] before the rotation (two slots more per layer). Qwen3; norm "rms_pre_rotary" only
+    head_dim: int = 0
+    qk_norm: int = 0
     # additive attention bias by relative offset, f32 [heads, 2 * radius + 1] (MPNet: mpnet_bias_table, T5:
     # t5_bias_table); not a field of
     # vr_bert_desc: load_encoder hands it to vr_encoder_set_attention_bias once the model is loaded
@@ -123,6 +128,15 @@ class BertDesc:
         return self.head[-1].out_dim if self.head else self.hidden
 
     @property
+    def head_size(self) -> int:
+        return int(self.head_dim) if self.head_dim else self.hidden // self.heads
+
+    @property
+    def attn_width(self) -> int:
+        """The width of the query, key and value rows and of the context: heads * head size (hidden unless head_dim says otherwise)."""
+        return self.heads * self.head_size
+
+    @property
     def rotary(self) -> bool:
         return self.position == "rotary"
 
@@ -143,8 +157,10 @@ class BertDesc:
         return self.norm == "rms_pre_rotary"
 
     def to_c(self) -> _lib.VrBertDesc:
-        # (a causal description crosses as vr_bert_desc_v2, every other one as the vr_bert_desc it always was)
-        d = _lib.VrBertDescV2() if self.causal else _lib.VrBertDesc()
+        # (a causal description crosses as vr_bert_desc_v2, one with a head_dim or Q/K norms as vr_bert_desc_v3, every
+        # other one as the vr_bert_desc it always was)
+        v3 = bool(self.head_dim or self.qk_norm)
+        d = _lib.VrBertDescV3() if v3 else _lib.VrBertDescV2() if self.causal else _lib.VrBertDesc()
         d.struct_size = C.sizeof(type(d))
         d.layers, d.hidden, d.heads, d.intermediate = self.layers, self.hidden, self.heads, self.intermediate
         d.vocab, d.max_pos, d.type_vocab = self.vocab, self.max_pos, self.type_vocab
@@ -173,6 +189,8 @@ class BertDesc:
         d.rope_theta_local = float(self.rope_theta_local)
         if self.causal:
             d.causal = int(self.causal)
+        if v3:
+            d.head_dim, d.qk_norm = int(self.head_dim), int(self.qk_norm)
         return d
 
 
@@ -427,7 +445,7 @@ def t5_slots(state: dict, desc: "BertDesc", num_buckets: int = 32, max_distance:
     return names, out, bias
 
 
-def qwen2_slots(state: dict, desc: "BertDesc", kv_heads: int | None = None):
+def qwen2_slots(state: dict, desc: "BertDesc", kv_heads: int | None = None, *, family: str = "Qwen2"):
     """A transformers Qwen2Model (or Qwen2ForCausalLM) state dict, any key prefix -> (slot names, state under those
     names): the 18-slot gated layout under the rotary family's native names, with no position table, no token types and
     no norm shifts (NULL), biases on q/k/v only. Under VR_NORM_PRE_RMS_ROTARY embeddings.LayerNorm holds
@@ -449,8 +467,9 @@ def qwen2_slots(state: dict, desc: "BertDesc", kv_heads: int | None = None):
         t = state[hits[0]]
         return t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
 
-    H, heads, L = desc.hidden, desc.heads, desc.layers
-    dh = H // heads
+    heads, L = desc.heads, desc.layers
+    dh = desc.head_size
+    qwen3 = family == "Qwen3"  # (q/k/v biases only where the checkpoint has them, and the two per-head norm weights)
     if kv_heads is None:
         rows = int(get("layers.0.self_attn.k_proj.weight").shape[0])
         if rows % dh:
@@ -474,20 +493,41 @@ def qwen2_slots(state: dict, desc: "BertDesc", kv_heads: int | None = None):
     for i in range(L):
         p = f"layers.{i}."
         for kind in ("weight", "bias"):
-            out[p + "self_attn.q_proj." + kind] = get(p + "self_attn.q_proj." + kind)
+            optional = qwen3 and kind == "bias"
+            t = get(p + "self_attn.q_proj." + kind, optional)
+            if t is not None:
+                out[p + "self_attn.q_proj." + kind] = t
             for part in ("k_proj", "v_proj"):
                 name = p + "self_attn." + part + "." + kind
-                out[name] = repeat_kv(get(name), name)
+                t = get(name, optional)
+                if t is not None:
+                    out[name] = repeat_kv(t, name)
         out[p + "self_attn.o_proj.weight"] = get(p + "self_attn.o_proj.weight")
         for part in ("gate_proj", "up_proj", "down_proj"):
             out[p + "mlp." + part + ".weight"] = get(p + "mlp." + part + ".weight")
         out[p + "post_attention_layernorm.weight"] = get(p + "post_attention_layernorm.weight")
         out[p + "post_mlp_layernorm.weight"] = get(f"layers.{i + 1}.input_layernorm.weight" if i + 1 < L else "norm.weight")
         names += [n if n in out else None for n in (p + s for s in PRENORM_LAYER_SUFFIXES)]
+        if desc.qk_norm:  # slots 18 and 19
+            for part in QK_NORM_SUFFIXES:
+                out[p + part] = get(p + part)
+                names.append(p + part)
     extra = sorted(k for k in state if k not in used and "lm_head" not in k.split("."))
     if extra:
-        raise ValueError(f"not a Qwen2 state dict of {L} layers: unexpected tensors {extra[:4]}{' ...' if len(extra) > 4 else ''}")
+        raise ValueError(f"not a {family} state dict of {L} layers: unexpected tensors {extra[:4]}{' ...' if len(extra) > 4 else ''}")
     return names, out
+
+
+QK_NORM_SUFFIXES = ["self_attn.q_norm.weight", "self_attn.k_norm.weight"]
+
+
+def qwen3_slots(state: dict, desc: "BertDesc", kv_heads: int | None = None):
+    """A transformers Qwen3Model (or Qwen3ForCausalLM) state dict, any key prefix -> (slot names, state under those
+    names): qwen2_slots' layout with heads of desc.head_dim (q_proj is [heads * head_dim, hidden], o_proj its transpose
+    shape, repeat_kv runs over KV heads of head_dim rows), q/k/v biases only where the checkpoint has them
+    (attention_bias), and with desc.qk_norm two slots more per layer, 18: self_attn.q_norm.weight, 19:
+    self_attn.k_norm.weight, [head_dim] each. lm_head.* is ignored; any other tensor left over is refused by name."""
+    return qwen2_slots(state, desc, kv_heads, family="Qwen3")
 
 
 def distilbert_slots(state: dict, desc: "BertDesc") -> dict:
@@ -631,6 +671,12 @@ def modernbert_head(state: dict, desc: "BertDesc") -> dict:
 def expected_shape(desc: BertDesc, name: str) -> tuple:
     """Shape of a state-dict entry as the description implies it ([out, in] layout, as HF stores it)."""
     H, inter = desc.hidden, desc.intermediate
+    if desc.head_dim or desc.qk_norm:  # (vr_bert_desc_v3: the attention width and the per-head norm weights)
+        A = desc.attn_width
+        if name.endswith(("self_attn.q_norm.weight", "self_attn.k_norm.weight")): return (desc.head_size,)
+        if name.endswith(("self_attn.q_proj.weight", "self_attn.k_proj.weight", "self_attn.v_proj.weight")): return (A, H)
+        if name.endswith(("self_attn.q_proj.bias", "self_attn.k_proj.bias", "self_attn.v_proj.bias")): return (A,)
+        if name.endswith("self_attn.o_proj.weight"): return (H, A)
     if name == "classifier.weight": return (1, H)
     if name == "classifier.bias": return (1,)
     if name.startswith("head.norm."): return (H,)
@@ -664,6 +710,8 @@ def load_encoder(engine, desc: BertDesc, state: dict) -> None:
     (jina_slots), a GELU one a BERT state dict without its position table."""
     if desc.prenorm:
         names, state = modernbert_slots(state, desc)
+    elif desc.rms_rotary and (desc.head_dim or desc.qk_norm):  # (a Qwen3 state dict: a head size of its own, Q/K norms)
+        names, state = qwen3_slots(state, desc)
     elif desc.rms_rotary:  # (a Qwen2 state dict; the K/V heads of grouped-query attention are repeated here)
         names, state = qwen2_slots(state, desc)
     elif desc.rms:  # (a T5 state dict; the description's attention_bias, else the checkpoint's table with T5's defaults)
