@@ -69,6 +69,8 @@ struct LayerWeights {
   float *cs_1_p = nullptr, *c_1_p = nullptr;
   // vr_bert_desc_v3.qk_norm: q_norm.weight / k_norm.weight, [head_dim] each, shared by the heads (qk_norm_rope_kernel)
   float *qn = nullptr, *kn = nullptr;
+  // the last layer of a [CLS]-pooled f16 model (cls_attend_kernel): the key third of s_qkv_f transposed, [H (in)][H (out)]
+  _Float16* wk_t = nullptr;
 };
 
 // vr_encoder_set_head: the stages embed_head_kernel runs on the pooled rows (device pointers; a null b: no bias / shift)
@@ -117,6 +119,7 @@ struct Encoder {
   int dh = 0, attn = 0, qk_norm = 0;
   int window_stream_from = 0;   // windowed layers: sequences from this length on take attention_stream_kernel (build_encoder)
   float* posidx = nullptr;  // rotary: int32 position of every token inside its own sequence (positions_kernel)
+  bool cls_collapse = true;  // the last layer attends from [CLS] on the hidden rows; VR_CLS_COLLAPSE=0 at load time: it projects K and V
   bool fuse = true;         // rotate / gate inside the skinny epilogues; VR_ENCODE_FUSE=0 at load time: separate passes
   DevArray<int32_t> ids, cu, seg;
   // a span call (encoder_encode_spans): the caller's (begin, end) pairs when they come from the host, and every span's
@@ -1233,15 +1236,19 @@ __global__ __launch_bounds__(256) void gather_first_rows_ln16_kernel(const half_
                                                                      const float* __restrict__ b,
                                                                      const int32_t* __restrict__ cu, int seq0,
                                                                      int tok_base, int n, int T, int H,
-                                                                     float* __restrict__ dst) {
+                                                                     float* __restrict__ dst,
+                                                                     half_t* __restrict__ dst16) {
   const int lane = threadIdx.x & 63;
   const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (i >= n) return;
   const int t = min(cu[seq0 + i] - tok_base, T - 1);
   const float2 st = stat[t];
-  for (int c = lane; c < H; c += 64)
-    dst[static_cast<int64_t>(i) * H + c] =
-        ln_apply(static_cast<float>(pre[static_cast<int64_t>(t) * H + c]), st.x, st.y, g[c], b[c]);
+  for (int c = lane; c < H; c += 64) {
+    const float v = ln_apply(static_cast<float>(pre[static_cast<int64_t>(t) * H + c]), st.x, st.y, g[c], b[c]);
+    dst[static_cast<int64_t>(i) * H + c] = v;
+    // (or null) the same rows as a GEMM's f16 input: the [CLS] query projection of cls_attend_kernel's route
+    if (dst16) dst16[static_cast<int64_t>(i) * H + c] = static_cast<half_t>(fminf(fmaxf(v, -65504.0f), 65504.0f));
+  }
 }
 
 // ---- rotary positions and the gated FFN, as passes of their own ------------------------------------
@@ -4508,6 +4515,238 @@ __global__ __launch_bounds__(NW * 64) void attention_stream_kernel(const half_t*
   }
 }
 
+// ---- the last layer of a [CLS]-pooled model, attended from the [CLS] rows alone ---------------------
+//
+// Behind the last layer's attention only the [CLS] rows are read (the cls_tail of forward_chunk), so that layer needs
+// no query but the [CLS] one, and its keys and values only contracted with it. With the conventions of EPI_FOLD_F16,
+// k_jc = inv_j (W'_k[c,:] . x_j - mean_j cs_k[c]) + c_k[c] over the f16 pre-LayerNorm rows x_j, for a head h
+//   q_h . k_j = inv_j (u_h . x_j - mean_j alpha_h) + const,   u_h[d] = sum_{c in h} q_c W'_k[c,d],  alpha_h = sum_d u_h[d]
+//   sum_j p_j v_j = W'_v,h z_h - cs_v gamma_h + c_v,          z_h = sum_j p_j inv_j x_j,  gamma_h = sum_j p_j inv_j mean_j
+// (the constant is the same for every key and leaves the softmax; the weights p_j sum to 1, so c_v passes through).
+// The K and V projections of the T rows become two H-wide dot products per (token, head): cls_head_gemm_kernel makes
+// u from the [CLS] queries, cls_attend_kernel the logits, the softmax, z and gamma with one block per sequence, and
+// cls_head_gemm_kernel again the context rows of the [CLS] tokens. u, p_j inv_j and z are rounded to f16 (the MFMA
+// operands) where the ordinary route rounds the K and V rows; alpha and gamma are sums over those ROUNDED values —
+// what the MFMAs really multiply by, as fold_vectors_kernel's column sums are — so the mean terms cancel exactly.
+constexpr int kClsHeads = 16;  // heads per sequence: one 16-row MFMA operand (fewer: zero rows)
+constexpr int kClsGroup = 16;  // keys per logit MFMA: a wave takes 16 keys of its sequence at a time
+constexpr int kClsStep = 32;   // keys per context MFMA (its K dimension): the staged key count is padded to whole steps
+using f16x4 = __attribute__((ext_vector_type(4))) _Float16;
+
+// The LDS of cls_attend_kernel for hidden size H and lpad staged keys: the u rows, later the f16 weights (the larger of
+// the two), the f32 logits and alpha. The launch is refused (the ordinary route runs) above the 64 KiB every kernel may have.
+static size_t cls_attend_lds(int H, int lpad) {
+  return static_cast<size_t>(kClsHeads) * (static_cast<size_t>(std::max(H, lpad)) + 8) * sizeof(half_t) +
+         static_cast<size_t>(kClsHeads) * (static_cast<size_t>(lpad) + 4) * sizeof(float) + kClsHeads * sizeof(float);
+}
+
+// out[d][c] = in[c][d], H x H halfs: the last layer's gain-folded K weights with the contraction index of u contiguous
+__global__ void transpose_f16_kernel(const half_t* __restrict__ in, int H, half_t* __restrict__ out) {
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (i >= static_cast<int64_t>(H) * H) return;
+  const int d = static_cast<int>(i / H), c = static_cast<int>(i % H);
+  out[i] = in[static_cast<int64_t>(c) * H + d];
+}
+
+// Per head (blockIdx.z): out[m][n] = unscale * sum_k W[n][k] A[m][k], M rows, N columns, K deep, as
+// gemm_f16_skinny_kernel computes it (W rows are the MFMA rows, 64 activation rows per block its columns, both
+// operands 16-byte global loads). A head's operands start w_head / a_head / o_head halfs behind the previous head's;
+// ldw / lda / ldo are the row strides. N % 16 == 0, K % 32 == 0.
+// CTX = false: u — W the transposed K weights (row d, k = the head's 64 or 32 query columns), A the [CLS] queries.
+// CTX = true: the context rows — W the head's V weights, A = z, and the epilogue adds - cs[col] gamma[m][head] + c[col].
+template <bool CTX>
+__global__ __launch_bounds__(256) void cls_head_gemm_kernel(const half_t* __restrict__ W, int ldw, int64_t w_head,
+                                                            const half_t* __restrict__ A, int lda, int a_head, int M, int N,
+                                                            int K, float unscale, const float* __restrict__ cs,
+                                                            const float* __restrict__ c, const float* __restrict__ gamma,
+                                                            half_t* __restrict__ out, int ldo, int o_head) {
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int head = blockIdx.z, nh = gridDim.z;
+  const int n0 = blockIdx.x * 64 + wave * 16;  // this wave's 16 output columns
+  const int row = lane & 15, g = lane >> 4;
+  const int m0 = blockIdx.y * 64;
+  if (n0 >= N) return;
+  const half_t* wp = W + head * w_head + static_cast<int64_t>(n0 + row) * ldw + 8 * g;
+  const half_t* ap[4];
+#pragma unroll
+  for (int mb = 0; mb < 4; ++mb)
+    ap[mb] = A + static_cast<int64_t>(min(m0 + mb * 16 + row, M - 1)) * lda + static_cast<int64_t>(head) * a_head + 8 * g;
+  f32x4 acc[4];
+#pragma unroll
+  for (int mb = 0; mb < 4; ++mb) acc[mb] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const int mblocks = (min(M - m0, 64) + 15) / 16;
+  auto step = [&](int k) {
+    const f16x8 wf = *reinterpret_cast<const f16x8*>(wp + k);
+#pragma unroll
+    for (int mb = 0; mb < 4; ++mb)
+      if (mb < mblocks) {
+        const f16x8 af = *reinterpret_cast<const f16x8*>(ap[mb] + k);
+        acc[mb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wf, af, acc[mb], 0, 0, 0);
+      }
+  };
+  int k = 0;
+  for (; k + 64 <= K; k += 64) {  // (two steps' loads in flight)
+    step(k);
+    step(k + 32);
+  }
+  if (k < K) step(k);
+  // C layout: column (lane & 15) = activation row m, rows 4g + r = output columns n0 + 4g + r
+  const int n = n0 + 4 * g;
+#pragma unroll
+  for (int mb = 0; mb < 4; ++mb) {
+    const int m = m0 + mb * 16 + row;
+    if (mb < mblocks && m < M) {
+      half_t h[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float v = acc[mb][r] * unscale;
+        if (CTX) {
+          const int col = head * N + n + r;
+          v = (v - cs[col] * gamma[static_cast<int64_t>(m) * nh + head]) + c[col];
+        }
+        h[r] = static_cast<half_t>(fminf(fmaxf(v, -65504.0f), 65504.0f));
+      }
+      *reinterpret_cast<uint2*>(out + static_cast<int64_t>(m) * ldo + static_cast<int64_t>(head) * o_head + n) =
+          *reinterpret_cast<const uint2*>(h);
+    }
+  }
+}
+
+// One block (4 waves) per sequence: the [CLS] query's attention over the sequence's own f16 pre-LayerNorm rows x_j
+// (H wide, their (mean, 1/sigma) in stat), all heads at once as the 16 rows of one MFMA operand.
+//   pass 1: logits s_hj = scale2 inv_j (u_h . x_j - mean_j alpha_h) (log2 domain), 16 keys per wave and MFMA chain, u from LDS
+//   softmax per head in f32 over the sequence's len keys; w_hj = p_hj inv_j as f16 into LDS, gamma_h = sum_j w_hj mean_j
+//   pass 2: z_h = sum_j w_hj x_j, the rows read a second time (from L2: a sequence's rows are at most a few hundred KB),
+//           64 columns per wave and step — a lane loads 4 neighbouring columns of a key, one for each of 4 MFMA chains
+// Every sum runs over the sequence's own rows in an order fixed by len alone, so a sequence's bits do not depend on
+// its place in the batch. U, Z: [n_seq][nh][H] halfs; gamma: [n_seq][nh]. nh <= kClsHeads, H % 64 == 0,
+// lpad = the batch's longest sequence rounded up to kClsStep; dynamic LDS: cls_attend_lds(H, lpad).
+__global__ __launch_bounds__(256) void cls_attend_kernel(const half_t* __restrict__ x, const float2* __restrict__ stat,
+                                                         const half_t* __restrict__ U, const int32_t* __restrict__ cu,
+                                                         int seq0, int tok_base, int T, int H, int nh, float scale2, int lpad,
+                                                         half_t* __restrict__ Z, float* __restrict__ gamma) {
+  extern __shared__ __align__(16) unsigned char cls_lds[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int row = lane & 15, g = lane >> 4;
+  const int seq = blockIdx.x;
+  const int us = H + 8;     // halfs per u row
+  const int ps = lpad + 8;  // halfs per weight row
+  const int ls = lpad + 4;  // floats per logit row
+  half_t* sU = reinterpret_cast<half_t*>(cls_lds);
+  half_t* sP = sU;  // the weights take the u rows' place once pass 1 is done
+  float* sS = reinterpret_cast<float*>(cls_lds + static_cast<size_t>(kClsHeads) * (max(H, lpad) + 8) * sizeof(half_t));
+  float* sA = sS + kClsHeads * ls;
+  const int t0 = cu[seq0 + seq] - tok_base;
+  const int len = min(min(cu[seq0 + seq + 1] - cu[seq0 + seq], T - t0), lpad);
+  half_t* zrow = Z + static_cast<int64_t>(seq) * nh * H;
+  if (len <= 0) {  // (block-uniform; read_offsets admits no empty sequence) zero rows, as pooling ignores them
+    for (int i = tid; i < nh * H; i += 256) zrow[i] = static_cast<half_t>(0.0f);
+    if (tid < nh) gamma[static_cast<int64_t>(seq) * nh + tid] = 0.0f;
+    return;
+  }
+  // u rows into LDS (rows nh .. 15: zeros), then alpha_h = sum_d u_h[d] over the rounded values
+  const int h8 = H >> 3;
+  for (int i = tid; i < kClsHeads * h8; i += 256) {
+    const int h = i / h8, c8 = i - h * h8;
+    f16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (h < nh) v = *reinterpret_cast<const f16x8*>(U + (static_cast<int64_t>(seq) * nh + h) * H + 8 * c8);
+    *reinterpret_cast<f16x8*>(sU + h * us + 8 * c8) = v;
+  }
+  __syncthreads();
+  for (int h = wave; h < kClsHeads; h += 4) {
+    float a = 0.0f;
+    for (int d = lane; d < H; d += 64) a += static_cast<float>(sU[h * us + d]);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) a += __shfl_xor(a, off);
+    if (lane == 0) sA[h] = a;
+  }
+  __syncthreads();
+  // pass 1
+  const int groups = (len + kClsGroup - 1) / kClsGroup;
+  for (int gi = wave; gi < groups; gi += 4) {
+    const int tok = gi * kClsGroup + row;
+    const int tc = min(tok, len - 1);  // (keys past the end: a valid row, its logit is not stored)
+    const half_t* xp = x + static_cast<int64_t>(t0 + tc) * H + 8 * g;
+    const half_t* up = sU + row * us + 8 * g;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (int k = 0; k < H; k += 64) {  // (H % 64 == 0: two steps' loads in flight)
+      const f16x8 x0 = *reinterpret_cast<const f16x8*>(xp + k), x1 = *reinterpret_cast<const f16x8*>(xp + k + 32);
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(*reinterpret_cast<const f16x8*>(up + k), x0, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(*reinterpret_cast<const f16x8*>(up + k + 32), x1, acc, 0, 0, 0);
+    }
+    // C layout: column (lane & 15) = key, rows 4g + r = heads
+    const float2 st = stat[t0 + tc];
+    if (tok < len) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) sS[(4 * g + r) * ls + tok] = scale2 * st.y * (acc[r] - st.x * sA[4 * g + r]);
+    }
+  }
+  __syncthreads();
+  // softmax, one wave per head; rows nh .. 15 and keys len .. lpad - 1: zero weights
+  for (int h = wave; h < kClsHeads; h += 4) {
+    if (h >= nh) {
+      for (int j = lane; j < lpad; j += 64) sP[h * ps + j] = static_cast<half_t>(0.0f);
+      continue;
+    }
+    float m = -INFINITY;
+    for (int j = lane; j < len; j += 64) m = fmaxf(m, sS[h * ls + j]);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
+    float sum = 0.0f;
+    for (int j = lane; j < len; j += 64) sum += __builtin_amdgcn_exp2f(sS[h * ls + j] - m);
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) sum += __shfl_xor(sum, off);
+    const float inv_sum = 1.0f / sum;
+    float gm = 0.0f;
+    for (int j = lane; j < lpad; j += 64) {
+      half_t wh = static_cast<half_t>(0.0f);
+      if (j < len) {
+        const float2 st = stat[t0 + j];
+        wh = static_cast<half_t>(__builtin_amdgcn_exp2f(sS[h * ls + j] - m) * inv_sum * st.y);
+        gm += static_cast<float>(wh) * st.x;
+      }
+      sP[h * ps + j] = wh;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) gm += __shfl_xor(gm, off);
+    if (lane == 0) gamma[static_cast<int64_t>(seq) * nh + h] = gm;
+  }
+  __syncthreads();
+  // pass 2: columns 64 dg + 4 row + q belong to chain q; its rows 4g + r are the columns 64 dg + 16 g + 4 r + q
+  const half_t* pp = sP + row * ps + 8 * g;
+  for (int dg = wave; dg < (H >> 6); dg += 4) {
+    f32x4 acc[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) acc[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const half_t* xc = x + static_cast<int64_t>(t0) * H + 64 * dg + 4 * row;
+    for (int j0 = 0; j0 < lpad; j0 += kClsStep) {
+      f16x4 v[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i)  // (keys past the end: a valid row times a zero weight)
+        v[i] = *reinterpret_cast<const f16x4*>(xc + static_cast<int64_t>(min(j0 + 8 * g + i, len - 1)) * H);
+      const f16x8 pf = *reinterpret_cast<const f16x8*>(pp + j0);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const f16x8 xf = {v[0][q], v[1][q], v[2][q], v[3][q], v[4][q], v[5][q], v[6][q], v[7][q]};
+        acc[q] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xf, pf, acc[q], 0, 0, 0);
+      }
+    }
+    // C layout: column (lane & 15) = head, this lane's 16 values = 16 consecutive columns from 64 dg + 16 g
+    if (row < nh) {
+      f16x8 o[2];
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+          o[(4 * r + q) >> 3][(4 * r + q) & 7] = static_cast<half_t>(fminf(fmaxf(acc[q][r], -65504.0f), 65504.0f));
+      half_t* zp = zrow + static_cast<int64_t>(row) * H + 64 * dg + 16 * g;
+      *reinterpret_cast<f16x8*>(zp) = o[0];
+      *reinterpret_cast<f16x8*>(zp + 8) = o[1];
+    }
+  }
+}
+
 // ---- host side -----------------------------------------------------------------------------------
 
 static int dev_alloc_copy(vr_engine* e, Encoder* enc, const void* src, size_t n_floats, int mem, float** out) {
@@ -4770,6 +5009,9 @@ static int build_encoder(vr_engine* e, void** slot, const vr_bert_desc* d_in, co
   enc->attn = A;
   enc->qk_norm = qk_norm;
   enc->fuse = !(getenv("VR_ENCODE_FUSE") && atoi(getenv("VR_ENCODE_FUSE")) == 0);
+  // (the embedder alone: a cross-encoder's unnormalised logits keep the bits of the ordinary last layer, which
+  // tests/golden/textpath_bert.npz pins)
+  enc->cls_collapse = slot == &e->encoder && !(getenv("VR_CLS_COLLAPSE") && atoi(getenv("VR_CLS_COLLAPSE")) == 0);
   const size_t HH = static_cast<size_t>(A) * H;  // a projection's weights: [A, H] (query, key, value) or [H, A] (output)
   VR_TRY(dev_alloc_copy(e, enc, t[0], static_cast<size_t>(d->vocab) * H, mem, &enc->word));
   if (d->position == VR_POS_LEARNED) VR_TRY(dev_alloc_copy(e, enc, t[1], static_cast<size_t>(d->max_pos) * H, mem, &enc->pos));
@@ -4902,6 +5144,14 @@ static int build_encoder(vr_engine* e, void** slot, const vr_bert_desc* d_in, co
         if (!enc->layers.empty()) {
           const LayerWeights& prev = enc->layers.back();
           VR_TRY(fold(lw.wqkv, 3 * H, prev.ln2g, prev.ln2b, lw.bqkv, &lw.s_qkv_f, &lw.cs_qkv, &lw.c_qkv));
+          if (l + 1 == L && enc->cls_collapse && d->pooling == VR_POOL_CLS && A == H) {  // see cls_attend_kernel
+            float* kt = nullptr;
+            VR_TRY(dev_alloc_copy(e, enc, nullptr, HH / 2, 0, &kt));
+            lw.wk_t = reinterpret_cast<_Float16*>(kt);
+            hipLaunchKernelGGL(transpose_f16_kernel, dim3(static_cast<unsigned>((HH + 255) / 256)), dim3(256), 0, e->stream,
+                               lw.s_qkv_f.hi + HH, H, lw.wk_t);
+            VR_HIP(hipGetLastError());
+          }
         }
       }
     }
@@ -5906,8 +6156,9 @@ static int forward_chunk(vr_engine* e, Encoder* enc, const int32_t* ids_dev, con
   // matrices carved out of the qkv buffer (free once attention has run), and the output projection,
   // both LayerNorms and the FFN run on n_seq rows instead of T. Every row's arithmetic is unchanged
   // (a GEMM row does not depend on its neighbours), so the embeddings are bit-identical; for
-  // bge-base this removes 10/12 of the last layer's GEMM work. The Q projection of the other
-  // tokens is still computed (it is one GEMM with K and V).
+  // bge-base this removes 10/12 of the last layer's GEMM work. The Q/K/V projection of all T rows
+  // (one GEMM) and the attention over them remain on this route; the large f16 batches of `collapse`
+  // below replace both.
   const int n_seq = seq1 - seq0;
   const bool cls_tail = !sp && d.pooling == VR_POOL_CLS && !enc->layers.empty() &&
                         static_cast<int64_t>(n_seq) * (4 * H + I) <= static_cast<int64_t>(T) * 3 * H;
@@ -5924,10 +6175,57 @@ static int forward_chunk(vr_engine* e, Encoder* enc, const int32_t* ids_dev, con
   float* xsc = tmpc + static_cast<int64_t>(n_seq) * H;        // [n_seq, 2H] halfs (split) = n_seq*H floats
   float* ctxc = xsc + static_cast<int64_t>(n_seq) * H;        // [n_seq, H] f32 or [n_seq, 2H] halfs
   float* ffnc = ctxc + static_cast<int64_t>(n_seq) * H;       // [n_seq, I] f32 or [n_seq, 2I] halfs
+  // `collapse`: the last layer of such a model attends from the [CLS] rows on the hidden rows themselves — no Q/K/V
+  // projection of the T rows, no attention launch over them (see cls_attend_kernel). The route exists for the f16
+  // residual stream of large batches (the hidden state is the f16 pre-LayerNorm rows in xh with their statistics),
+  // plain bidirectional attention of the hidden width (learned or no positions, no bias, slopes, window, mask or Q/K
+  // norm), head size 32 or 64, at most kClsHeads heads, a longest sequence whose logits and weights fit the 64 KiB of
+  // LDS beside the u rows (cls_attend_lds: 608 tokens at H = 768, 480 at H = 1024), and T / n_seq large enough that
+  // its workspace fits the qkv buffer behind the tail's (no kernel writes that buffer in the last layer then).
+  // Everything else, a cross-encoder (build_encoder) and every model loaded under VR_CLS_COLLAPSE=0 keep the route above.
+  const int cls_lpad = (max_len + kClsStep - 1) / kClsStep * kClsStep;
+  auto up4 = [](int64_t n) { return (n + 3) / 4 * 4; };  // (16-byte aligned pieces)
+  half_t* x16c = reinterpret_cast<half_t*>(ffnc + up4(static_cast<int64_t>(n_seq) * I));  // [n_seq, H] f16 LN(x) of the [CLS] rows
+  half_t* q16c = x16c + up4(static_cast<int64_t>(n_seq) * H);                              // [n_seq, H] their queries
+  half_t* u16c = q16c + up4(static_cast<int64_t>(n_seq) * H);                              // [n_seq, nh, H] u
+  half_t* z16c = u16c + up4(static_cast<int64_t>(n_seq) * nh * H);                         // [n_seq, nh, H] z
+  float* gammac = reinterpret_cast<float*>(z16c + up4(static_cast<int64_t>(n_seq) * nh * H));  // [n_seq, nh]
+  const int64_t cls_ws_floats = (gammac + static_cast<int64_t>(n_seq) * nh) - enc->qkv;
+  const bool collapse = cls_tail && enc->cls_collapse && plain && fold_big && res16 && enc->layers.size() > 1 &&
+                        enc->layers.back().wk_t != nullptr && d.position != VR_POS_ROTARY && !enc->bias && !enc->slopes &&
+                        !enc->causal && !enc->qk_norm && enc->attn == H && (dh == 32 || dh == 64) && nh <= kClsHeads &&
+                        cls_attend_lds(H, cls_lpad) <= 65536 && cls_ws_floats <= static_cast<int64_t>(T) * 3 * H;
   for (size_t li = 0; li < enc->layers.size(); ++li) {
     const LayerWeights& w = enc->layers[li];
     const bool tail = cls_tail && li + 1 == enc->layers.size();
-    if (plain && fold_ln && li > 0 && fuse_rope)  // ... and the rotation in its epilogue
+    if (tail && collapse) {
+      // (cur16 holds: res16 and li > 0) steps 1-4 of cls_attend_kernel's comment; ctxc is what the tail below reads
+      const unsigned gblocks = static_cast<unsigned>((n_seq + 3) / 4);
+      const unsigned mblocks = static_cast<unsigned>((n_seq + 63) / 64);
+      hipLaunchKernelGGL(gather_first_rows_ln16_kernel, dim3(gblocks), dim3(256), 0, s, xh, cur.stat, cur.g, cur.b, cu_dev,
+                         seq0, tok_base, n_seq, T, H, xc, x16c);
+      VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_F16, {.A = x16c, .W = w.s_qkv, .bias = w.bqkv, .Ch = q16c, .M = n_seq, .N = H,
+                                                      .K = H, .passes = 1}));
+      const double head_flop = 2.0 * n_seq * static_cast<double>(H) * H;  // nh products of [n_seq, dh] x [dh, H]
+      prof_begin(e, VR_PROF_GEMM, head_flop);
+      hipLaunchKernelGGL((cls_head_gemm_kernel<false>), dim3(static_cast<unsigned>(H / 64), mblocks, static_cast<unsigned>(nh)),
+                         dim3(256), 0, s, w.wk_t, H, static_cast<int64_t>(dh), q16c, H, dh, n_seq, H, dh, w.s_qkv_f.unscale,
+                         static_cast<const float*>(nullptr), static_cast<const float*>(nullptr),
+                         static_cast<const float*>(nullptr), u16c, nh * H, H);
+      prof_end(e);
+      // two passes over the T rows, 2 H multiply-adds per (token, head) each
+      prof_begin(e, VR_PROF_ATTENTION, 4.0 * nh * static_cast<double>(H) * T);
+      hipLaunchKernelGGL(cls_attend_kernel, dim3(static_cast<unsigned>(n_seq)), dim3(256), cls_attend_lds(H, cls_lpad), s, xh,
+                         cur.stat, u16c, cu_dev, seq0, tok_base, T, H, nh, 1.4426950408889634f / sqrtf(static_cast<float>(dh)),
+                         cls_lpad, z16c, gammac);
+      prof_end(e);
+      prof_begin(e, VR_PROF_GEMM, head_flop);
+      hipLaunchKernelGGL((cls_head_gemm_kernel<true>), dim3(static_cast<unsigned>((dh + 63) / 64), mblocks, static_cast<unsigned>(nh)),
+                         dim3(256), 0, s, w.s_qkv_f.hi + static_cast<int64_t>(2) * H * H, H, static_cast<int64_t>(dh) * H, z16c,
+                         nh * H, H, n_seq, dh, H, w.s_qkv_f.unscale, w.cs_qkv + 2 * H, w.c_qkv + 2 * H, gammac,
+                         reinterpret_cast<half_t*>(ctxc), H, dh);
+      prof_end(e);
+    } else if (plain && fold_ln && li > 0 && fuse_rope)  // ... and the rotation in its epilogue
       VR_TRY(launch_skinny_ln(e, EPI_ROPE_F16, cur.pre, d.eps, const_cast<float2*>(cur.stat),
                               {.W = w.s_qkv_p, .bias = w.bqkv_p, .Ch = qkvh, .M = T, .N = 3 * H, .K = H, .ln_g = cur.g,
                                .ln_b = cur.b, .rope_tab = enc->rope, .rope_pos = posidx}));
@@ -5948,16 +6246,21 @@ static int forward_chunk(vr_engine* e, Encoder* enc, const int32_t* ids_dev, con
                                                   .N = 3 * H, .K = H, .passes = passes}));
     else
       VR_TRY(launch_gemm(e, EPI_BIAS, enc->x, w.wqkv, w.bqkv, nullptr, enc->qkv, T, 3 * H, H));
-    rope();
-    VR_TRY(launch_attention(e, enc, cu_dev, seq0, n_seq, tok_base, max_len, tail, 0, attn_flop));
+    if (!(tail && collapse)) {
+      rope();
+      VR_TRY(launch_attention(e, enc, cu_dev, seq0, n_seq, tok_base, max_len, tail, 0, attn_flop));
+    }
     if (tail) {
       const unsigned gblocks = static_cast<unsigned>((n_seq + 3) / 4);
       const unsigned cblocks = gblocks;
-      hipLaunchKernelGGL(gather_first_rows_kernel, dim3(gblocks), dim3(256), 0, s, reinterpret_cast<const float4*>(enc->ctx),
-                         cu_dev, seq0, tok_base, n_seq, T, plain ? H / 8 : H / 4, reinterpret_cast<float4*>(ctxc));
-      if (plain && cur16)
+      if (!collapse)  // (collapse: ctxc and xc are written above)
+        hipLaunchKernelGGL(gather_first_rows_kernel, dim3(gblocks), dim3(256), 0, s, reinterpret_cast<const float4*>(enc->ctx),
+                           cu_dev, seq0, tok_base, n_seq, T, plain ? H / 8 : H / 4, reinterpret_cast<float4*>(ctxc));
+      if (collapse)
+        ;
+      else if (plain && cur16)
         hipLaunchKernelGGL(gather_first_rows_ln16_kernel, dim3(gblocks), dim3(256), 0, s, xh, cur.stat, cur.g, cur.b,
-                           cu_dev, seq0, tok_base, n_seq, T, H, xc);
+                           cu_dev, seq0, tok_base, n_seq, T, H, xc, static_cast<half_t*>(nullptr));
       else if (plain)
         hipLaunchKernelGGL(gather_first_rows_ln_kernel, dim3(gblocks), dim3(256), 0, s, cur.pre, cur.stat, cur.g, cur.b,
                            cu_dev, seq0, tok_base, n_seq, T, H, xc);
