@@ -4,7 +4,7 @@ Without arguments: builds the build_small() corpus of tests/test_batch_filters_g
 search_dense (1, 16 and 300 queries), search_sparse, search_hybrid, search_sparse_batch, search_hybrid_batch,
 search_dense_multi and search_hybrid_batch_multi. Run it under `rocprofv3 --kernel-trace --output-format csv -d DIR --`.
 
---compare DIR_A DIR_B: reads the *kernel_trace.csv of two such runs and checks that the launch count, the multiset of
+--compare DIR_A DIR_B: reads the *kernel_trace.csv of two such runs (one per process of a run) and checks that the launch count, the multiset of
 (kernel, grid, workgroup) and, per queue / stream (numbered by first appearance), the order of launches are equal.
 Exit status 1 when they are not."""
 import collections
@@ -38,18 +38,23 @@ def run():
 
 
 def launches(d):
-    files = glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True)
-    assert len(files) == 1, (d, files)
-    with open(files[0], newline="") as f:
-        rows = list(csv.DictReader(f))
-    order = "Dispatch_Id" if "Dispatch_Id" in rows[0] else "Start_Timestamp"
-    rows.sort(key=lambda r: int(r[order]))
-    lane = next((c for c in ("Stream_Id", "Queue_Id") if c in rows[0]), None)
-    seen, out = {}, []
-    for r in rows:
-        shape = tuple(int(r[f"{a}_Size_{x}"]) for a in ("Grid", "Workgroup") for x in "XYZ")
-        s = seen.setdefault(r[lane], len(seen)) if lane else 0
-        out.append((s, r["Kernel_Name"], shape))
+    """The launches of a run as (stream, kernel, (grid, workgroup)) in dispatch order. A run that started child processes
+    left one trace per process: their streams are told apart, and compare() matches streams by what they launched."""
+    files = sorted(glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True))
+    assert files, d
+    seen, out, lane = {}, [], None
+    for path in files:
+        with open(path, newline="") as f:
+            rows = list(csv.DictReader(f))
+        if not rows:  # (a process that launched nothing)
+            continue
+        order = "Dispatch_Id" if "Dispatch_Id" in rows[0] else "Start_Timestamp"
+        rows.sort(key=lambda r: int(r[order]))
+        lane = next((c for c in ("Stream_Id", "Queue_Id") if c in rows[0]), None)
+        for r in rows:
+            shape = tuple(int(r[f"{a}_Size_{x}"]) for a in ("Grid", "Workgroup") for x in "XYZ")
+            s = seen.setdefault((path, r[lane] if lane else 0), len(seen))
+            out.append((s, r["Kernel_Name"], shape))
     return out, lane
 
 

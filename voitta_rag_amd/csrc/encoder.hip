@@ -5641,6 +5641,210 @@ static void launch_pool(vr_engine* e, Encoder* enc, const float* x, const int32_
                        enc->head, d.normalize, head_lda(enc->head), out_dev + static_cast<int64_t>(row0) * W, W, W);
 }
 
+// ---- the steps of a forward pass ---------------------------------------------------------------------------------------
+// The four forward routines below are built from these: each step chooses its kernel by the model's precision in one
+// place. They are host code that only picks a launch; none allocates but Pass::need_glu.
+
+// One activation matrix as a product reads or writes it. f16x3 mode: every GEMM input also exists as interleaved
+// (hi, lo) f16 rows (lo = hi + 8, see split_at); f16 mode: plain f16 rows and no lo half; f32 mode: both null, the rows
+// are the f32 rows at f. The context and the FFN intermediate are ONLY needed split, so those reuse the f32 buffer.
+struct Rows {
+  float* f = nullptr;
+  half_t *hi = nullptr, *lo = nullptr;
+};
+
+// What every step of one forward pass over T packed tokens needs: where it launches, the precision, and the workspace.
+struct Pass {
+  vr_engine* e;
+  Encoder* enc;
+  hipStream_t s;
+  int T;
+  unsigned row_blocks;  // of the kernels that take four rows per block
+  bool split, plain;    // f16x3 or f16; f16
+  int passes;
+  bool rms;             // the pre-norm routines' N: RMSNorm (T5, Qwen) or LayerNorm (ModernBERT)
+  int glu_epi;          // the gate of a fused FFN-up epilogue
+  Rows ctx, ffn;        // the context and the activation, as the residual projections read them
+  half_t *xh, *xl;      // the hidden (or normalised) rows as a product's input, in xs
+  half_t* qkvh;         // f16 mode: the Q/K/V rows
+  half_t* gluh;         // f16 mode: the [T, 2I] pre-activation of the unfused gate (f16x3, f32: enc->glu as it is)
+  const int32_t* posidx;
+  float2* stat;         // lnstat. (launch_skinny_ln stores the rows' statistics there; no pre-norm routine reads them)
+
+  Pass(vr_engine* e_, Encoder* enc_, int T_)
+      : e(e_), enc(enc_), s(e_->stream), T(T_), row_blocks(blocks4(T_)), split(enc_->d.precision != VR_PRECISION_F32),
+        plain(enc_->d.precision == VR_PRECISION_F16), passes(plain ? 1 : 3),
+        rms(enc_->d.norm == VR_NORM_PRE_RMS || enc_->d.norm == VR_NORM_PRE_RMS_ROTARY),
+        glu_epi(enc_->d.ffn == VR_FFN_SWIGLU ? EPI_SWIGLU_F16 : EPI_GEGLU_F16), ctx(rows(enc_->ctx)), ffn(rows(enc_->ffn)),
+        xh(rows(enc_->xs).hi), xl(rows(enc_->xs).lo), qkvh(reinterpret_cast<half_t*>(enc_->qkv)),
+        gluh(reinterpret_cast<half_t*>(enc_->glu)), posidx(reinterpret_cast<const int32_t*>(enc_->posidx)),
+        stat(reinterpret_cast<float2*>(enc_->lnstat)) {}
+
+  static unsigned blocks4(int M) { return static_cast<unsigned>((M + 3) / 4); }
+  // a buffer's rows by precision; f32: where the f32 rows are when they are not in the buffer itself
+  Rows rows(float* buf, float* f32 = nullptr) const {
+    half_t* hi = split ? reinterpret_cast<half_t*>(buf) : nullptr;
+    return {f32 ? f32 : buf, hi, split && !plain ? hi + 8 : nullptr};
+  }
+  // a product's input in xs; f32 mode: the caller's f32 rows (the hidden state, or the rows a norm wrote into ctx)
+  Rows x(float* f32) const { return {f32, xh, xl}; }
+
+  // The [rows, 2I] pre-activation workspace of the unfused gate exists only once a pass really stores one. (Never
+  // allocated during a graph capture: a shape runs eagerly first, and a reallocation of the workspace drops both this
+  // buffer and the graphs.)
+  int need_glu() {
+    if (enc->glu) return 0;
+    const size_t n = static_cast<size_t>(enc->ws_tokens), I = static_cast<size_t>(enc->d.intermediate);
+    VR_TRY(dev_alloc_copy(e, enc, nullptr, plain ? n * I : n * 2 * I, 0, &enc->glu));
+    gluh = reinterpret_cast<half_t*>(enc->glu);
+    return 0;
+  }
+};
+
+// out = a W^T + bias, M rows: plain f16 rows in f16 mode, f32 rows otherwise (`out` is the buffer in both cases)
+static int project_bias(const Pass& p, const float* w32, const SplitWeight& W, const float* bias, int M, int N, int K, Rows a,
+                        float* out) {
+  if (p.plain)
+    return launch_gemm_f16x3(p.e, p.enc, EPI_BIAS_F16, {.A = a.hi, .W = W, .bias = bias, .Ch = reinterpret_cast<half_t*>(out),
+                                                        .M = M, .N = N, .K = K, .passes = 1});
+  if (p.split)
+    return launch_gemm_f16x3(p.e, p.enc, EPI_BIAS, {.A = a.hi, .A_lo = a.lo, .W = W, .bias = bias, .C = out, .M = M, .N = N,
+                                                    .K = K, .passes = p.passes});
+  return launch_gemm(p.e, EPI_BIAS, a.f, w32, bias, nullptr, out, M, N, K);
+}
+
+// C = R + a W^T + bias, f32 rows (f16x3 and f32 mode, and the pre-norm routines in every mode)
+static int project_residual(const Pass& p, const float* w32, const SplitWeight& W, const float* bias, int M, int N, int K, Rows a,
+                            const float* R, float* C) {
+  if (p.split)
+    return launch_gemm_f16x3(p.e, p.enc, EPI_BIAS_RESIDUAL, {.A = a.hi, .A_lo = a.lo, .W = W, .bias = bias, .R = R, .C = C, .M = M,
+                                                             .N = N, .K = K, .passes = p.passes});
+  return launch_gemm(p.e, EPI_BIAS_RESIDUAL, a.f, w32, bias, R, C, M, N, K);
+}
+
+// out = act(a W^T + bias), epi = EPI_BIAS_GELU or EPI_BIAS_RELU: the rows the FFN-down projection reads
+static int project_act(const Pass& p, int epi, const float* w32, const SplitWeight& W, const float* bias, int M, int N, int K,
+                       Rows a, Rows out) {
+  if (p.split)
+    return launch_gemm_f16x3(p.e, p.enc, epi, {.A = a.hi, .A_lo = a.lo, .W = W, .bias = bias, .Ch = out.hi, .Cl = out.lo, .M = M,
+                                               .N = N, .K = K, .passes = p.passes});
+  return launch_gemm(p.e, epi, a.f, w32, bias, nullptr, out.f, M, N, K);
+}
+
+// LayerNorm of M f32 rows -> out: the f32 rows and, where out has them, the f16 / (hi, lo) rows
+static void layernorm_rows(const Pass& p, const float* in, int M, const float* g, const float* b, Rows out) {
+  hipLaunchKernelGGL(layernorm_kernel, dim3(Pass::blocks4(M)), dim3(256), 0, p.s, in, M, p.enc->d.hidden, g, b, p.enc->d.eps,
+                     out.f, out.hi, out.lo, static_cast<float2*>(nullptr));
+}
+
+// f16 mode: LayerNorm of the T rows -> the plain f16 rows in xs and, where the pointers are not null, the f32 rows and the
+// rows' (mean, 1/sigma). (layernorm_f16_kernel and rmsnorm_f16_kernel exist for whole 256-column steps.)
+static void layernorm_f16_rows(const Pass& p, const float* in, const float* g, const float* b, float* f32, float2* stat) {
+  const int H = p.enc->d.hidden;
+  if (H % 256 == 0)
+    hipLaunchKernelGGL(layernorm_f16_kernel, dim3(p.row_blocks), dim3(256), 0, p.s, in, p.T, H, g, b, p.enc->d.eps, f32, p.xh, stat);
+  else
+    hipLaunchKernelGGL(layernorm_kernel, dim3(p.row_blocks), dim3(256), 0, p.s, in, p.T, H, g, b, p.enc->d.eps, f32, p.xh,
+                       static_cast<half_t*>(nullptr), stat);
+}
+
+// The T rows of h normalised by (g, b) — by g alone under p.rms — as the next product's input: p.x(enc->ctx)
+static void norm_rows(const Pass& p, const float* h, const float* g, const float* b) {
+  const int H = p.enc->d.hidden;
+  float* f32 = p.split ? nullptr : p.enc->ctx;
+  if (!p.rms && p.plain)
+    layernorm_f16_rows(p, h, g, b, nullptr, nullptr);
+  else if (!p.rms)
+    layernorm_rows(p, h, p.T, g, b, {f32, p.xh, p.xl});
+  else if (p.plain && H % 256 == 0)
+    hipLaunchKernelGGL(rmsnorm_f16_kernel, dim3(p.row_blocks), dim3(256), 0, p.s, h, p.T, H, g, p.enc->d.eps, p.xh);
+  else
+    hipLaunchKernelGGL(rmsnorm_kernel, dim3(p.row_blocks), dim3(256), 0, p.s, h, p.T, H, g, p.enc->d.eps, f32, p.xh, p.xl);
+}
+
+// The rotation as a pass of its own: in place on the Q and K parts (`width` columns each) of the T qkv rows
+static void rotate_rows(const Pass& p, const float2* table, int width, int dh) {
+  if (p.plain)
+    hipLaunchKernelGGL(rope_kernel<half_t>, dim3(p.row_blocks), dim3(256), 0, p.s, p.qkvh, p.posidx, p.T, width, dh, table);
+  else
+    hipLaunchKernelGGL(rope_kernel<float>, dim3(p.row_blocks), dim3(256), 0, p.s, p.enc->qkv, p.posidx, p.T, width, dh, table);
+}
+
+// Qwen3: the per-head RMSNorm of Q and K by (qn, kn) and the rotation, one pass over the T qkv rows
+static void qk_norm_rotate_rows(const Pass& p, const LayerWeights& w, int width, int dh) {
+  if (p.plain)
+    hipLaunchKernelGGL(qk_norm_rope_kernel<half_t>, dim3(p.row_blocks), dim3(256), 0, p.s, p.qkvh, p.posidx, p.T, width, dh,
+                       p.enc->rope, w.qn, w.kn, p.enc->d.eps);
+  else
+    hipLaunchKernelGGL(qk_norm_rope_kernel<float>, dim3(p.row_blocks), dim3(256), 0, p.s, p.enc->qkv, p.posidx, p.T, width, dh,
+                       p.enc->rope, w.qn, w.kn, p.enc->d.eps);
+}
+
+// The unfused gate: M rows of enc->glu -> the FFN-down input, f16 rows (f16), (hi, lo) rows (f16x3) or f32 rows of `out`
+static void gate_rows(const Pass& p, int M, Rows out) {
+  const int I = p.enc->d.intermediate, ffn = p.enc->d.ffn;
+  const int64_t n8 = static_cast<int64_t>(M) * (I / 8);
+  const dim3 grid(static_cast<unsigned>((n8 + 255) / 256));
+  if (p.plain)
+    hipLaunchKernelGGL((glu_kernel<half_t, 2>), grid, dim3(256), 0, p.s, p.gluh, n8, I, ffn, static_cast<float*>(nullptr), out.hi);
+  else if (p.split)
+    hipLaunchKernelGGL((glu_kernel<float, 1>), grid, dim3(256), 0, p.s, p.enc->glu, n8, I, ffn, static_cast<float*>(nullptr), out.hi);
+  else
+    hipLaunchKernelGGL((glu_kernel<float, 0>), grid, dim3(256), 0, p.s, p.enc->glu, n8, I, ffn, out.f, static_cast<half_t*>(nullptr));
+}
+
+// The gated FFN-up of M input rows -> out. fuse_glu (f16 mode, a product that goes to a skinny kernel): over the
+// re-ordered matrix, the gate in the epilogue; otherwise the bias-only product into enc->glu, then the gate pass.
+static int gated_up_rows(const Pass& p, const LayerWeights& w, bool fuse_glu, int M, Rows a, Rows out) {
+  const int H = p.enc->d.hidden, N1 = 2 * p.enc->d.intermediate;
+  if (fuse_glu)
+    return launch_gemm_f16x3(p.e, p.enc, p.glu_epi, {.A = a.hi, .W = w.s_1_p, .bias = w.b1_p, .Ch = out.hi, .M = M, .N = N1, .K = H,
+                                                     .passes = 1});
+  VR_TRY(project_bias(p, w.w1, w.s_1, w.b1, M, N1, H, a, p.enc->glu));
+  gate_rows(p, M, out);
+  return 0;
+}
+
+// The gated FFN-up of N(h) by (g, b) -> p.ffn, pre-norm routines. fold_ln (a question): the norm runs inside the
+// projection (launch_skinny_ln); otherwise as a launch of its own ahead of gated_up_rows.
+static int gated_up_of_norm(const Pass& p, const LayerWeights& w, bool fold_ln, bool fuse_glu, const float* h, const float* g,
+                            const float* b) {
+  const int H = p.enc->d.hidden, N1 = 2 * p.enc->d.intermediate;
+  const float eps = p.enc->d.eps;
+  if (fold_ln && fuse_glu)
+    return launch_skinny_ln(p.e, p.glu_epi, h, eps, p.stat,
+                            {.W = w.s_1_p, .bias = w.b1_p, .Ch = p.ffn.hi, .M = p.T, .N = N1, .K = H, .ln_g = g, .ln_b = b}, p.rms);
+  if (fold_ln) {
+    VR_TRY(launch_skinny_ln(p.e, EPI_BIAS_F16, h, eps, p.stat,
+                            {.W = w.s_1, .bias = w.b1, .Ch = p.gluh, .M = p.T, .N = N1, .K = H, .ln_g = g, .ln_b = b}, p.rms));
+    gate_rows(p, p.T, p.ffn);
+    return 0;
+  }
+  norm_rows(p, h, g, b);
+  return gated_up_rows(p, w, fuse_glu, p.T, p.x(p.enc->ctx), p.ffn);
+}
+
+// Q, K, V (N columns) of N(h) by (g, b) -> the qkv rows, pre-norm routines; g null (layer 0): the embedding launch
+// wrote the normalised rows, f32 mode at a32. fold_ln as above; fuse_rope (f16 mode, a skinny route): the rotation by
+// `table` in the epilogue, over the re-ordered matrix — otherwise the caller rotates in a pass of its own.
+static int project_qkv(const Pass& p, const LayerWeights& w, int N, bool fold_ln, bool fuse_rope, const float2* table,
+                       const float* h, const float* g, const float* b, float* a32) {
+  const int H = p.enc->d.hidden;
+  if (fold_ln && g) {
+    if (fuse_rope)
+      return launch_skinny_ln(p.e, EPI_ROPE_F16, h, p.enc->d.eps, p.stat,
+                              {.W = w.s_qkv_p, .bias = w.bqkv_p, .Ch = p.qkvh, .M = p.T, .N = N, .K = H, .ln_g = g, .ln_b = b,
+                               .rope_tab = table, .rope_pos = p.posidx}, p.rms);
+    return launch_skinny_ln(p.e, EPI_BIAS_F16, h, p.enc->d.eps, p.stat,
+                            {.W = w.s_qkv, .bias = w.bqkv, .Ch = p.qkvh, .M = p.T, .N = N, .K = H, .ln_g = g, .ln_b = b}, p.rms);
+  }
+  if (g) norm_rows(p, h, g, b);
+  if (fuse_rope)
+    return launch_gemm_f16x3(p.e, p.enc, EPI_ROPE_F16, {.A = p.xh, .W = w.s_qkv_p, .bias = w.bqkv_p, .Ch = p.qkvh, .M = p.T, .N = N,
+                                                        .K = H, .passes = 1, .rope_tab = table, .rope_pos = p.posidx});
+  return project_bias(p, w.wqkv, w.s_qkv, w.bqkv, p.T, N, H, p.x(a32), p.enc->qkv);
+}
+
 // The forward pass of a pre-norm model (VR_NORM_PRE: rotary positions, a gated FFN, optionally alternating global and
 // windowed attention — the ModernBERT family), forward_chunk's arguments:
 //   h = LN_emb(word[id]);  per layer  h += W_o attn(N_a(h)),  h += W_down(act(gate(N_m(h))) * up(N_m(h)));  out = N_f(h)
@@ -5658,136 +5862,45 @@ static int forward_chunk_prenorm(vr_engine* e, Encoder* enc, const int32_t* ids_
                                  const Spans* sp) {
   const vr_bert_desc& d = enc->d;
   const int H = d.hidden, I = d.intermediate, dh = H / d.heads, N1 = 2 * I;
-  hipStream_t s = e->stream;
-  const unsigned row_blocks = static_cast<unsigned>((T + 3) / 4);
-  const bool split = d.precision != VR_PRECISION_F32;
-  const bool plain = d.precision == VR_PRECISION_F16;
-  const int passes = plain ? 1 : 3;
   // GEMM inputs, as in forward_chunk: the normalised rows in xs (f32 mode: in ctx, free until attention writes it and
   // again behind the output projection), the context in ctx, the gated activation in ffn
-  half_t* xh = split ? reinterpret_cast<half_t*>(enc->xs) : nullptr;
-  half_t* xl = split && !plain ? xh + 8 : nullptr;
-  half_t* ch = split ? reinterpret_cast<half_t*>(enc->ctx) : nullptr;
-  half_t* cl = split && !plain ? ch + 8 : nullptr;
-  half_t* fh = split ? reinterpret_cast<half_t*>(enc->ffn) : nullptr;
-  half_t* fl = split && !plain ? fh + 8 : nullptr;
-  half_t* qkvh = reinterpret_cast<half_t*>(enc->qkv);
-  const int32_t* posidx = reinterpret_cast<const int32_t*>(enc->posidx);
-  float2* stat = reinterpret_cast<float2*>(enc->lnstat);  // (launch_skinny_ln stores the rows' statistics; nobody reads them)
-  const bool fuse = plain && enc->fuse;
-  const bool fold_ln = plain && skinny_ln_supported(T, 3 * H, H) && I % 16 == 0;
+  Pass p(e, enc, T);
+  const bool fuse = p.plain && enc->fuse;
+  const bool fold_ln = p.plain && skinny_ln_supported(T, 3 * H, H) && I % 16 == 0;
   const bool fuse_rope = fuse && skinny_routed(T, 3 * H, H);
   const bool fuse_glu = fuse && skinny_routed(T, N1, H);
-  const int glu_epi = d.ffn == VR_FFN_SWIGLU ? EPI_SWIGLU_F16 : EPI_GEGLU_F16;
-  // the [T, 2I] pre-activation of the unfused gate (never allocated during a graph capture: a shape runs eagerly first)
-  if (!fuse_glu && !enc->glu) {
-    const size_t rows = static_cast<size_t>(enc->ws_tokens);
-    VR_TRY(dev_alloc_copy(e, enc, nullptr, plain ? rows * I : rows * 2 * I, 0, &enc->glu));
-  }
-  half_t* gluh = reinterpret_cast<half_t*>(enc->glu);
-  // rows of h normalised by (g, b) -> the next product's input
-  auto norm_rows = [&](const float* h, const float* g, const float* b) {
-    if (plain && H % 256 == 0)
-      hipLaunchKernelGGL(layernorm_f16_kernel, dim3(row_blocks), dim3(256), 0, s, h, T, H, g, b, d.eps, static_cast<float*>(nullptr),
-                         xh, static_cast<float2*>(nullptr));
-    else
-      hipLaunchKernelGGL(layernorm_kernel, dim3(row_blocks), dim3(256), 0, s, h, T, H, g, b, d.eps, split ? nullptr : enc->ctx, xh,
-                         xl, static_cast<float2*>(nullptr));
-  };
-  hipLaunchKernelGGL(embed_ln_rotary_kernel, dim3(row_blocks), dim3(256), 0, s, ids_dev, cu_dev, n_seq_total, tok_base, T, H,
-                     d.vocab, enc->word, enc->type, enc->lng, enc->lnb, d.eps, enc->x, xh, xl, static_cast<float*>(nullptr),
+  if (!fuse_glu) VR_TRY(p.need_glu());
+  hipLaunchKernelGGL(embed_ln_rotary_kernel, dim3(p.row_blocks), dim3(256), 0, p.s, ids_dev, cu_dev, n_seq_total, tok_base, T, H,
+                     d.vocab, enc->word, enc->type, enc->lng, enc->lnb, d.eps, enc->x, p.xh, p.xl, static_cast<float*>(nullptr),
                      static_cast<float2*>(nullptr));
-  hipLaunchKernelGGL(positions_kernel, dim3(static_cast<unsigned>((T + 255) / 256)), dim3(256), 0, s, cu_dev, n_seq_total,
+  hipLaunchKernelGGL(positions_kernel, dim3(static_cast<unsigned>((T + 255) / 256)), dim3(256), 0, p.s, cu_dev, n_seq_total,
                      tok_base, T, reinterpret_cast<int32_t*>(enc->posidx));
   float* h = enc->x;      // the residual stream
   float* other = enc->tmp;
   const int n_seq = seq1 - seq0;
   for (size_t li = 0; li < enc->layers.size(); ++li) {
     const LayerWeights& w = enc->layers[li];
+    const LayerWeights* prev = li > 0 ? &enc->layers[li - 1] : nullptr;
     const bool global = d.window == 0 || li % static_cast<size_t>(d.global_every) == 0;
     const float2* table = !global && enc->rope_local ? enc->rope_local : enc->rope;
-    // Q, K, V of N_a(h); layer 0 reads the embedding LayerNorm's rows as they are
-    const float* a32 = li == 0 ? h : enc->ctx;  // f32 mode: the product's input rows
-    const bool fold_a = fold_ln && li > 0;
-    if (fold_a) {
-      const LayerWeights& prev = enc->layers[li - 1];
-      if (fuse_rope)
-        VR_TRY(launch_skinny_ln(e, EPI_ROPE_F16, h, d.eps, stat,
-                                {.W = w.s_qkv_p, .bias = w.bqkv_p, .Ch = qkvh, .M = T, .N = 3 * H, .K = H, .ln_g = prev.ln2g,
-                                 .ln_b = prev.ln2b, .rope_tab = table, .rope_pos = posidx}));
-      else
-        VR_TRY(launch_skinny_ln(e, EPI_BIAS_F16, h, d.eps, stat,
-                                {.W = w.s_qkv, .bias = w.bqkv, .Ch = qkvh, .M = T, .N = 3 * H, .K = H, .ln_g = prev.ln2g,
-                                 .ln_b = prev.ln2b}));
-    } else {
-      if (li > 0) norm_rows(h, enc->layers[li - 1].ln2g, enc->layers[li - 1].ln2b);
-      if (fuse_rope)
-        VR_TRY(launch_gemm_f16x3(e, enc, EPI_ROPE_F16, {.A = xh, .W = w.s_qkv_p, .bias = w.bqkv_p, .Ch = qkvh, .M = T, .N = 3 * H,
-                                                        .K = H, .passes = 1, .rope_tab = table, .rope_pos = posidx}));
-      else if (plain)
-        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_F16, {.A = xh, .W = w.s_qkv, .bias = w.bqkv, .Ch = qkvh, .M = T, .N = 3 * H,
-                                                        .K = H, .passes = 1}));
-      else if (split)
-        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS, {.A = xh, .A_lo = xl, .W = w.s_qkv, .bias = w.bqkv, .C = enc->qkv, .M = T,
-                                                    .N = 3 * H, .K = H, .passes = passes}));
-      else
-        VR_TRY(launch_gemm(e, EPI_BIAS, a32, w.wqkv, w.bqkv, nullptr, enc->qkv, T, 3 * H, H));
-    }
-    if (!fuse_rope) {  // the rotation as a pass of its own, with the table of the layer's kind
-      if (plain)
-        hipLaunchKernelGGL(rope_kernel<half_t>, dim3(row_blocks), dim3(256), 0, s, qkvh, posidx, T, H, dh, table);
-      else
-        hipLaunchKernelGGL(rope_kernel<float>, dim3(row_blocks), dim3(256), 0, s, enc->qkv, posidx, T, H, dh, table);
-    }
+    // Q, K, V of N_a(h); layer 0 reads the embedding LayerNorm's rows as they are (f32 mode: h itself)
+    VR_TRY(project_qkv(p, w, 3 * H, fold_ln, fuse_rope, table, h, prev ? prev->ln2g : nullptr, prev ? prev->ln2b : nullptr,
+                       prev ? enc->ctx : h));
+    if (!fuse_rope) rotate_rows(p, table, H, dh);  // with the table of the layer's kind
     // (the profiler's flop count of a windowed layer: at most 2 w + 1 keys per query, instead of the sequence's length)
     const double layer_flop = global ? attn_flop : std::min(attn_flop, 4.0 * H * T * (2.0 * d.window + 1.0));
     VR_TRY(launch_attention(e, enc, cu_dev, seq0, n_seq, tok_base, max_len, false, global ? 0 : d.window, layer_flop));
     // h' = h + W_o ctx
-    if (split)
-      VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_RESIDUAL, {.A = ch, .A_lo = cl, .W = w.s_o, .bias = w.bo, .R = h, .C = other, .M = T,
-                                                           .N = H, .K = H, .passes = passes}));
-    else
-      VR_TRY(launch_gemm(e, EPI_BIAS_RESIDUAL, enc->ctx, w.wo, w.bo, h, other, T, H, H));
+    VR_TRY(project_residual(p, w.wo, w.s_o, w.bo, T, H, H, p.ctx, h, other));
     std::swap(h, other);
     // the gated FFN of N_m(h)
-    if (fold_ln && fuse_glu) {
-      VR_TRY(launch_skinny_ln(e, glu_epi, h, d.eps, stat,
-                              {.W = w.s_1_p, .bias = w.b1_p, .Ch = fh, .M = T, .N = N1, .K = H, .ln_g = w.ln1g, .ln_b = w.ln1b}));
-    } else if (fold_ln) {
-      VR_TRY(launch_skinny_ln(e, EPI_BIAS_F16, h, d.eps, stat,
-                              {.W = w.s_1, .bias = w.b1, .Ch = gluh, .M = T, .N = N1, .K = H, .ln_g = w.ln1g, .ln_b = w.ln1b}));
-    } else {
-      norm_rows(h, w.ln1g, w.ln1b);
-      if (fuse_glu)
-        VR_TRY(launch_gemm_f16x3(e, enc, glu_epi, {.A = xh, .W = w.s_1_p, .bias = w.b1_p, .Ch = fh, .M = T, .N = N1, .K = H, .passes = 1}));
-      else if (plain)
-        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_F16, {.A = xh, .W = w.s_1, .bias = w.b1, .Ch = gluh, .M = T, .N = N1, .K = H,
-                                                        .passes = 1}));
-      else if (split)
-        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS, {.A = xh, .A_lo = xl, .W = w.s_1, .bias = w.b1, .C = enc->glu, .M = T, .N = N1,
-                                                    .K = H, .passes = passes}));
-      else
-        VR_TRY(launch_gemm(e, EPI_BIAS, enc->ctx, w.w1, w.b1, nullptr, enc->glu, T, N1, H));
-    }
-    if (!fuse_glu) {
-      const int64_t n8 = static_cast<int64_t>(T) * (I / 8);
-      const dim3 grid(static_cast<unsigned>((n8 + 255) / 256));
-      if (plain) hipLaunchKernelGGL((glu_kernel<half_t, 2>), grid, dim3(256), 0, s, gluh, n8, I, d.ffn, static_cast<float*>(nullptr), fh);
-      else if (split) hipLaunchKernelGGL((glu_kernel<float, 1>), grid, dim3(256), 0, s, enc->glu, n8, I, d.ffn, static_cast<float*>(nullptr), fh);
-      else hipLaunchKernelGGL((glu_kernel<float, 0>), grid, dim3(256), 0, s, enc->glu, n8, I, d.ffn, enc->ffn, static_cast<half_t*>(nullptr));
-    }
+    VR_TRY(gated_up_of_norm(p, w, fold_ln, fuse_glu, h, w.ln1g, w.ln1b));
     // h' = h + W_down act
-    if (split)
-      VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_RESIDUAL, {.A = fh, .A_lo = fl, .W = w.s_2, .bias = w.b2, .R = h, .C = other, .M = T,
-                                                           .N = H, .K = I, .passes = passes}));
-    else
-      VR_TRY(launch_gemm(e, EPI_BIAS_RESIDUAL, enc->ffn, w.w2, w.b2, h, other, T, H, I));
+    VR_TRY(project_residual(p, w.w2, w.s_2, w.b2, T, H, I, p.ffn, h, other));
     std::swap(h, other);
   }
   // the final norm writes the f32 rows pooling reads, into the buffer the stream is not in
-  const LayerWeights& last = enc->layers.back();
-  hipLaunchKernelGGL(layernorm_kernel, dim3(row_blocks), dim3(256), 0, s, h, T, H, last.ln2g, last.ln2b, d.eps, other,
-                     static_cast<half_t*>(nullptr), static_cast<half_t*>(nullptr), static_cast<float2*>(nullptr));
+  layernorm_rows(p, h, T, enc->layers.back().ln2g, enc->layers.back().ln2b, {other});
   launch_pool(e, enc, other, cu_dev, seq0, seq1, tok_base, 0, out_dev, sp);
   VR_HIP(hipGetLastError());
   return 0;
@@ -5807,82 +5920,37 @@ static int forward_chunk_rms(vr_engine* e, Encoder* enc, const int32_t* ids_dev,
                              const Spans* sp) {
   const vr_bert_desc& d = enc->d;
   const int H = d.hidden, I = d.intermediate;
-  hipStream_t s = e->stream;
-  const unsigned row_blocks = static_cast<unsigned>((T + 3) / 4);
-  const bool split = d.precision != VR_PRECISION_F32;
-  const bool plain = d.precision == VR_PRECISION_F16;
-  const int passes = plain ? 1 : 3;
   // GEMM inputs as in forward_chunk_prenorm: the normalised rows in xs (f32 mode: in ctx), the context in ctx, the
   // activation in ffn
-  half_t* xh = split ? reinterpret_cast<half_t*>(enc->xs) : nullptr;
-  half_t* xl = split && !plain ? xh + 8 : nullptr;
-  half_t* ch = split ? reinterpret_cast<half_t*>(enc->ctx) : nullptr;
-  half_t* cl = split && !plain ? ch + 8 : nullptr;
-  half_t* fh = split ? reinterpret_cast<half_t*>(enc->ffn) : nullptr;
-  half_t* fl = split && !plain ? fh + 8 : nullptr;
-  half_t* qkvh = reinterpret_cast<half_t*>(enc->qkv);
-  float2* stat = reinterpret_cast<float2*>(enc->lnstat);  // (launch_skinny_ln stores the rows' 1/rms; nobody reads them)
-  const bool fold_ln = plain && skinny_ln_supported(T, 3 * H, H) && I % 16 == 0;
-  // rows of h normalised by g -> the next product's input
-  auto norm_rows = [&](const float* h, const float* g) {
-    if (plain && H % 256 == 0)
-      hipLaunchKernelGGL(rmsnorm_f16_kernel, dim3(row_blocks), dim3(256), 0, s, h, T, H, g, d.eps, xh);
-    else
-      hipLaunchKernelGGL(rmsnorm_kernel, dim3(row_blocks), dim3(256), 0, s, h, T, H, g, d.eps, split ? nullptr : enc->ctx, xh, xl);
-  };
-  hipLaunchKernelGGL(embed_rms_kernel, dim3(row_blocks), dim3(256), 0, s, ids_dev, cu_dev, n_seq_total, tok_base, T, H, d.vocab,
-                     enc->word, enc->type, enc->lng, d.eps, split ? nullptr : enc->ctx, xh, xl, enc->x);
+  Pass p(e, enc, T);
+  const bool fold_ln = p.plain && skinny_ln_supported(T, 3 * H, H) && I % 16 == 0;
+  hipLaunchKernelGGL(embed_rms_kernel, dim3(p.row_blocks), dim3(256), 0, p.s, ids_dev, cu_dev, n_seq_total, tok_base, T, H, d.vocab,
+                     enc->word, enc->type, enc->lng, d.eps, p.split ? nullptr : enc->ctx, p.xh, p.xl, enc->x);
   float* h = enc->x;      // the residual stream
   float* other = enc->tmp;
   const int n_seq = seq1 - seq0;
   for (size_t li = 0; li < enc->layers.size(); ++li) {
     const LayerWeights& w = enc->layers[li];
     // Q, K, V of N_a(h); layer 0 reads the rows the embedding launch normalised
-    if (fold_ln && li > 0) {
-      VR_TRY(launch_skinny_ln(e, EPI_BIAS_F16, h, d.eps, stat,
-                              {.W = w.s_qkv, .bias = w.bqkv, .Ch = qkvh, .M = T, .N = 3 * H, .K = H, .ln_g = enc->layers[li - 1].ln2g},
-                              true));
-    } else {
-      if (li > 0) norm_rows(h, enc->layers[li - 1].ln2g);
-      if (plain)
-        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_F16, {.A = xh, .W = w.s_qkv, .bias = w.bqkv, .Ch = qkvh, .M = T, .N = 3 * H,
-                                                        .K = H, .passes = 1}));
-      else if (split)
-        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS, {.A = xh, .A_lo = xl, .W = w.s_qkv, .bias = w.bqkv, .C = enc->qkv, .M = T,
-                                                    .N = 3 * H, .K = H, .passes = passes}));
-      else
-        VR_TRY(launch_gemm(e, EPI_BIAS, enc->ctx, w.wqkv, w.bqkv, nullptr, enc->qkv, T, 3 * H, H));
-    }
+    VR_TRY(project_qkv(p, w, 3 * H, fold_ln, false, nullptr, h, li > 0 ? enc->layers[li - 1].ln2g : nullptr, nullptr, enc->ctx));
     VR_TRY(launch_attention(e, enc, cu_dev, seq0, n_seq, tok_base, max_len, false, 0, attn_flop));
     // h' = h + W_o ctx
-    if (split)
-      VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_RESIDUAL, {.A = ch, .A_lo = cl, .W = w.s_o, .bias = w.bo, .R = h, .C = other, .M = T,
-                                                           .N = H, .K = H, .passes = passes}));
-    else
-      VR_TRY(launch_gemm(e, EPI_BIAS_RESIDUAL, enc->ctx, w.wo, w.bo, h, other, T, H, H));
+    VR_TRY(project_residual(p, w.wo, w.s_o, w.bo, T, H, H, p.ctx, h, other));
     std::swap(h, other);
     // relu(W_up N_m(h))
     if (fold_ln) {
-      VR_TRY(launch_skinny_ln(e, EPI_BIAS_RELU, h, d.eps, stat,
-                              {.W = w.s_1, .bias = w.b1, .Ch = fh, .M = T, .N = I, .K = H, .ln_g = w.ln1g}, true));
+      VR_TRY(launch_skinny_ln(e, EPI_BIAS_RELU, h, d.eps, p.stat,
+                              {.W = w.s_1, .bias = w.b1, .Ch = p.ffn.hi, .M = T, .N = I, .K = H, .ln_g = w.ln1g}, true));
     } else {
-      norm_rows(h, w.ln1g);
-      if (split)
-        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_RELU, {.A = xh, .A_lo = xl, .W = w.s_1, .bias = w.b1, .Ch = fh, .Cl = fl, .M = T,
-                                                         .N = I, .K = H, .passes = passes}));
-      else
-        VR_TRY(launch_gemm(e, EPI_BIAS_RELU, enc->ctx, w.w1, w.b1, nullptr, enc->ffn, T, I, H));
+      norm_rows(p, h, w.ln1g, nullptr);
+      VR_TRY(project_act(p, EPI_BIAS_RELU, w.w1, w.s_1, w.b1, T, I, H, p.x(enc->ctx), p.ffn));
     }
     // h' = h + W_down act
-    if (split)
-      VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_RESIDUAL, {.A = fh, .A_lo = fl, .W = w.s_2, .bias = w.b2, .R = h, .C = other, .M = T,
-                                                           .N = H, .K = I, .passes = passes}));
-    else
-      VR_TRY(launch_gemm(e, EPI_BIAS_RESIDUAL, enc->ffn, w.w2, w.b2, h, other, T, H, I));
+    VR_TRY(project_residual(p, w.w2, w.s_2, w.b2, T, H, I, p.ffn, h, other));
     std::swap(h, other);
   }
   // the final norm writes the f32 rows pooling reads, into the buffer the stream is not in
-  hipLaunchKernelGGL(rmsnorm_kernel, dim3(row_blocks), dim3(256), 0, s, h, T, H, enc->layers.back().ln2g, d.eps, other,
+  hipLaunchKernelGGL(rmsnorm_kernel, dim3(p.row_blocks), dim3(256), 0, p.s, h, T, H, enc->layers.back().ln2g, d.eps, other,
                      static_cast<half_t*>(nullptr), static_cast<half_t*>(nullptr));
   launch_pool(e, enc, other, cu_dev, seq0, seq1, tok_base, 0, out_dev, sp);
   VR_HIP(hipGetLastError());
@@ -5905,45 +5973,19 @@ static int forward_chunk_rms_rotary(vr_engine* e, Encoder* enc, const int32_t* i
   // A: the attention width — the [Q | K | V] row is 3 A, the context A (A == H but for vr_bert_desc_v3.head_dim)
   const int H = d.hidden, I = d.intermediate, dh = enc->dh, A = enc->attn, N1 = 2 * I;
   const bool qk_norm = enc->qk_norm != 0;
-  hipStream_t s = e->stream;
-  const unsigned row_blocks = static_cast<unsigned>((T + 3) / 4);
-  const bool split = d.precision != VR_PRECISION_F32;
-  const bool plain = d.precision == VR_PRECISION_F16;
-  const int passes = plain ? 1 : 3;
   // GEMM inputs as in forward_chunk_prenorm: the normalised rows in xs (f32 mode: in ctx), the context in ctx, the gated
   // activation in ffn
-  half_t* xh = split ? reinterpret_cast<half_t*>(enc->xs) : nullptr;
-  half_t* xl = split && !plain ? xh + 8 : nullptr;
-  half_t* ch = split ? reinterpret_cast<half_t*>(enc->ctx) : nullptr;
-  half_t* cl = split && !plain ? ch + 8 : nullptr;
-  half_t* fh = split ? reinterpret_cast<half_t*>(enc->ffn) : nullptr;
-  half_t* fl = split && !plain ? fh + 8 : nullptr;
-  half_t* qkvh = reinterpret_cast<half_t*>(enc->qkv);
-  const int32_t* posidx = reinterpret_cast<const int32_t*>(enc->posidx);
-  float2* stat = reinterpret_cast<float2*>(enc->lnstat);  // (launch_skinny_ln stores the rows' 1/rms; nobody reads them)
-  const bool fuse = plain && enc->fuse;
-  const bool fold_ln = plain && skinny_rms_rotary_supported(T, 3 * A, H) && I % 16 == 0;
+  Pass p(e, enc, T);
+  const bool fuse = p.plain && enc->fuse;
+  const bool fold_ln = p.plain && skinny_rms_rotary_supported(T, 3 * A, H) && I % 16 == 0;
   // (the rotating Q/K/V epilogues: not behind a Q/K norm, which needs a whole head before the rotation — those models
   // take the plain epilogues and qk_norm_rope_kernel at every size — and, as they are, at A == H only)
   const bool fuse_rope = fuse && !qk_norm && A == H && skinny_routed(T, 3 * H, H);
   const bool fuse_glu = fuse && skinny_routed(T, N1, H);
-  const int glu_epi = d.ffn == VR_FFN_SWIGLU ? EPI_SWIGLU_F16 : EPI_GEGLU_F16;
-  // the [T, 2I] pre-activation of the unfused gate (never allocated during a graph capture: a shape runs eagerly first)
-  if (!fuse_glu && !enc->glu) {
-    const size_t rows = static_cast<size_t>(enc->ws_tokens);
-    VR_TRY(dev_alloc_copy(e, enc, nullptr, plain ? rows * I : rows * 2 * I, 0, &enc->glu));
-  }
-  half_t* gluh = reinterpret_cast<half_t*>(enc->glu);
-  // rows of h normalised by g -> the next product's input
-  auto norm_rows = [&](const float* h, const float* g) {
-    if (plain && H % 256 == 0)
-      hipLaunchKernelGGL(rmsnorm_f16_kernel, dim3(row_blocks), dim3(256), 0, s, h, T, H, g, d.eps, xh);
-    else
-      hipLaunchKernelGGL(rmsnorm_kernel, dim3(row_blocks), dim3(256), 0, s, h, T, H, g, d.eps, split ? nullptr : enc->ctx, xh, xl);
-  };
-  hipLaunchKernelGGL(embed_rms_kernel, dim3(row_blocks), dim3(256), 0, s, ids_dev, cu_dev, n_seq_total, tok_base, T, H, d.vocab,
-                     enc->word, enc->type, enc->lng, d.eps, split ? nullptr : enc->ctx, xh, xl, enc->x);
-  hipLaunchKernelGGL(positions_kernel, dim3(static_cast<unsigned>((T + 255) / 256)), dim3(256), 0, s, cu_dev, n_seq_total,
+  if (!fuse_glu) VR_TRY(p.need_glu());
+  hipLaunchKernelGGL(embed_rms_kernel, dim3(p.row_blocks), dim3(256), 0, p.s, ids_dev, cu_dev, n_seq_total, tok_base, T, H, d.vocab,
+                     enc->word, enc->type, enc->lng, d.eps, p.split ? nullptr : enc->ctx, p.xh, p.xl, enc->x);
+  hipLaunchKernelGGL(positions_kernel, dim3(static_cast<unsigned>((T + 255) / 256)), dim3(256), 0, p.s, cu_dev, n_seq_total,
                      tok_base, T, reinterpret_cast<int32_t*>(enc->posidx));
   float* h = enc->x;      // the residual stream
   float* other = enc->tmp;
@@ -5953,89 +5995,134 @@ static int forward_chunk_rms_rotary(vr_engine* e, Encoder* enc, const int32_t* i
   for (size_t li = 0; li < enc->layers.size(); ++li) {
     const LayerWeights& w = enc->layers[li];
     // Q, K, V of N_a(h); layer 0 reads the rows the embedding launch normalised
-    if (fold_ln && li > 0) {
-      const float* g = enc->layers[li - 1].ln2g;
-      if (fuse_rope)
-        VR_TRY(launch_skinny_ln(e, EPI_ROPE_F16, h, d.eps, stat,
-                                {.W = w.s_qkv_p, .bias = w.bqkv_p, .Ch = qkvh, .M = T, .N = 3 * H, .K = H, .ln_g = g,
-                                 .rope_tab = enc->rope, .rope_pos = posidx}, true));
-      else
-        VR_TRY(launch_skinny_ln(e, EPI_BIAS_F16, h, d.eps, stat,
-                                {.W = w.s_qkv, .bias = w.bqkv, .Ch = qkvh, .M = T, .N = 3 * A, .K = H, .ln_g = g}, true));
-    } else {
-      if (li > 0) norm_rows(h, enc->layers[li - 1].ln2g);
-      if (fuse_rope)
-        VR_TRY(launch_gemm_f16x3(e, enc, EPI_ROPE_F16, {.A = xh, .W = w.s_qkv_p, .bias = w.bqkv_p, .Ch = qkvh, .M = T, .N = 3 * H,
-                                                        .K = H, .passes = 1, .rope_tab = enc->rope, .rope_pos = posidx}));
-      else if (plain)
-        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_F16, {.A = xh, .W = w.s_qkv, .bias = w.bqkv, .Ch = qkvh, .M = T, .N = 3 * A,
-                                                        .K = H, .passes = 1}));
-      else if (split)
-        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS, {.A = xh, .A_lo = xl, .W = w.s_qkv, .bias = w.bqkv, .C = enc->qkv, .M = T,
-                                                    .N = 3 * A, .K = H, .passes = passes}));
-      else
-        VR_TRY(launch_gemm(e, EPI_BIAS, enc->ctx, w.wqkv, w.bqkv, nullptr, enc->qkv, T, 3 * A, H));
-    }
-    if (qk_norm) {  // the per-head norm of Q and K and the rotation, one pass
-      if (plain)
-        hipLaunchKernelGGL(qk_norm_rope_kernel<half_t>, dim3(row_blocks), dim3(256), 0, s, qkvh, posidx, T, A, dh, enc->rope, w.qn,
-                           w.kn, d.eps);
-      else
-        hipLaunchKernelGGL(qk_norm_rope_kernel<float>, dim3(row_blocks), dim3(256), 0, s, enc->qkv, posidx, T, A, dh, enc->rope, w.qn,
-                           w.kn, d.eps);
-    } else if (!fuse_rope) {  // the rotation as a pass of its own
-      if (plain)
-        hipLaunchKernelGGL(rope_kernel<half_t>, dim3(row_blocks), dim3(256), 0, s, qkvh, posidx, T, A, dh, enc->rope);
-      else
-        hipLaunchKernelGGL(rope_kernel<float>, dim3(row_blocks), dim3(256), 0, s, enc->qkv, posidx, T, A, dh, enc->rope);
-    }
+    VR_TRY(project_qkv(p, w, 3 * A, fold_ln, fuse_rope, enc->rope, h, li > 0 ? enc->layers[li - 1].ln2g : nullptr, nullptr,
+                       enc->ctx));
+    if (qk_norm) qk_norm_rotate_rows(p, w, A, dh);
+    else if (!fuse_rope) rotate_rows(p, enc->rope, A, dh);
     VR_TRY(launch_attention(e, enc, cu_dev, seq0, n_seq, tok_base, max_len, false, 0, layer_flop));
     // h' = h + W_o ctx
-    if (split)
-      VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_RESIDUAL, {.A = ch, .A_lo = cl, .W = w.s_o, .bias = w.bo, .R = h, .C = other, .M = T,
-                                                           .N = H, .K = A, .passes = passes}));
-    else
-      VR_TRY(launch_gemm(e, EPI_BIAS_RESIDUAL, enc->ctx, w.wo, w.bo, h, other, T, H, A));
+    VR_TRY(project_residual(p, w.wo, w.s_o, w.bo, T, H, A, p.ctx, h, other));
     std::swap(h, other);
     // the gated FFN of N_m(h)
-    if (fold_ln && fuse_glu) {
-      VR_TRY(launch_skinny_ln(e, glu_epi, h, d.eps, stat,
-                              {.W = w.s_1_p, .bias = w.b1_p, .Ch = fh, .M = T, .N = N1, .K = H, .ln_g = w.ln1g}, true));
-    } else if (fold_ln) {
-      VR_TRY(launch_skinny_ln(e, EPI_BIAS_F16, h, d.eps, stat,
-                              {.W = w.s_1, .bias = w.b1, .Ch = gluh, .M = T, .N = N1, .K = H, .ln_g = w.ln1g}, true));
-    } else {
-      norm_rows(h, w.ln1g);
-      if (fuse_glu)
-        VR_TRY(launch_gemm_f16x3(e, enc, glu_epi, {.A = xh, .W = w.s_1_p, .bias = w.b1_p, .Ch = fh, .M = T, .N = N1, .K = H, .passes = 1}));
-      else if (plain)
-        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_F16, {.A = xh, .W = w.s_1, .bias = w.b1, .Ch = gluh, .M = T, .N = N1, .K = H,
-                                                        .passes = 1}));
-      else if (split)
-        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS, {.A = xh, .A_lo = xl, .W = w.s_1, .bias = w.b1, .C = enc->glu, .M = T, .N = N1,
-                                                    .K = H, .passes = passes}));
-      else
-        VR_TRY(launch_gemm(e, EPI_BIAS, enc->ctx, w.w1, w.b1, nullptr, enc->glu, T, N1, H));
-    }
-    if (!fuse_glu) {
-      const int64_t n8 = static_cast<int64_t>(T) * (I / 8);
-      const dim3 grid(static_cast<unsigned>((n8 + 255) / 256));
-      if (plain) hipLaunchKernelGGL((glu_kernel<half_t, 2>), grid, dim3(256), 0, s, gluh, n8, I, d.ffn, static_cast<float*>(nullptr), fh);
-      else if (split) hipLaunchKernelGGL((glu_kernel<float, 1>), grid, dim3(256), 0, s, enc->glu, n8, I, d.ffn, static_cast<float*>(nullptr), fh);
-      else hipLaunchKernelGGL((glu_kernel<float, 0>), grid, dim3(256), 0, s, enc->glu, n8, I, d.ffn, enc->ffn, static_cast<half_t*>(nullptr));
-    }
+    VR_TRY(gated_up_of_norm(p, w, fold_ln, fuse_glu, h, w.ln1g, nullptr));
     // h' = h + W_down act
-    if (split)
-      VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_RESIDUAL, {.A = fh, .A_lo = fl, .W = w.s_2, .bias = w.b2, .R = h, .C = other, .M = T,
-                                                           .N = H, .K = I, .passes = passes}));
-    else
-      VR_TRY(launch_gemm(e, EPI_BIAS_RESIDUAL, enc->ffn, w.w2, w.b2, h, other, T, H, I));
+    VR_TRY(project_residual(p, w.w2, w.s_2, w.b2, T, H, I, p.ffn, h, other));
     std::swap(h, other);
   }
   // the final norm writes the f32 rows pooling reads, into the buffer the stream is not in
-  hipLaunchKernelGGL(rmsnorm_kernel, dim3(row_blocks), dim3(256), 0, s, h, T, H, enc->layers.back().ln2g, d.eps, other,
+  hipLaunchKernelGGL(rmsnorm_kernel, dim3(p.row_blocks), dim3(256), 0, p.s, h, T, H, enc->layers.back().ln2g, d.eps, other,
                      static_cast<half_t*>(nullptr), static_cast<half_t*>(nullptr));
   launch_pool(e, enc, other, cu_dev, seq0, seq1, tok_base, 0, out_dev, sp);
+  VR_HIP(hipGetLastError());
+  return 0;
+}
+
+// forward_chunk's hidden state in f16 mode: LayerNorm by (g, b) of the pre-LN rows `pre`, with the rows' (mean, 1/sigma)
+struct Hidden {
+  const float* pre;
+  const float2* stat;
+  const float* g;
+  const float* b;
+};
+
+// CLS pooling reads one row per sequence, so everything after the LAST layer's attention is needed
+// for those rows only: their context rows (and residual rows) are gathered into compact [n_seq, *]
+// matrices carved out of the qkv buffer (free once attention has run), and the output projection,
+// both LayerNorms and the FFN run on n_seq rows instead of T (cls_tail). Every row's arithmetic is unchanged
+// (a GEMM row does not depend on its neighbours), so the embeddings are bit-identical; for
+// bge-base this removes 10/12 of the last layer's GEMM work. The Q/K/V projection of all T rows
+// (one GEMM) and the attention over them remain on this route; the large f16 batches of `collapse`
+// (cls_collapse_attend) replace both, with a workspace behind the tail's.
+struct ClsRows {
+  float *x, *tmp, *xs, *ctx, *ffn;  // the tail's [n_seq, *] x, tmp, xs, ctx and ffn
+  half_t *x16, *q16, *u16, *z16;    // collapse: f16 LN(x) of the [CLS] rows, their queries, u and z [n_seq, nh, H]
+  float* gamma;                     // collapse: [n_seq, nh]
+  int64_t floats;                   // all of it, from the start of the qkv buffer
+
+  ClsRows(const Encoder* enc, int n_seq) {
+    const int64_t n = n_seq, H = enc->d.hidden, I = enc->d.intermediate, nh = enc->d.heads;
+    auto up4 = [](int64_t k) { return (k + 3) / 4 * 4; };  // (16-byte aligned pieces)
+    x = enc->qkv;        // [n_seq, H] hidden state of the [CLS] rows
+    tmp = x + n * H;     // [n_seq, H]
+    xs = tmp + n * H;    // [n_seq, 2H] halfs (split) = n_seq*H floats
+    ctx = xs + n * H;    // [n_seq, H] f32 or [n_seq, 2H] halfs
+    ffn = ctx + n * H;   // [n_seq, I] f32 or [n_seq, 2I] halfs
+    x16 = reinterpret_cast<half_t*>(ffn + up4(n * I));
+    q16 = x16 + up4(n * H);
+    u16 = q16 + up4(n * H);
+    z16 = u16 + up4(n * nh * H);
+    gamma = reinterpret_cast<float*>(z16 + up4(n * nh * H));
+    floats = (gamma + n * nh) - enc->qkv;
+  }
+};
+
+// `collapse`: the last layer of a [CLS]-pooled model attends from the [CLS] rows on the hidden rows themselves — no Q/K/V
+// projection of the T rows, no attention launch over them: steps 1-4 of cls_attend_kernel's comment. Reads the f16
+// pre-LayerNorm rows in xs with their statistics (forward_chunk's cur16 state); writes c.x and c.ctx, which cls_tail reads.
+static int cls_collapse_attend(const Pass& p, const LayerWeights& w, const Hidden& cur, const ClsRows& c, const int32_t* cu_dev,
+                               int seq0, int n_seq, int tok_base, int cls_lpad) {
+  vr_engine* e = p.e;
+  const int T = p.T, H = p.enc->d.hidden, nh = p.enc->d.heads, dh = H / nh;
+  const unsigned mblocks = static_cast<unsigned>((n_seq + 63) / 64);
+  hipLaunchKernelGGL(gather_first_rows_ln16_kernel, dim3(Pass::blocks4(n_seq)), dim3(256), 0, p.s, p.xh, cur.stat, cur.g, cur.b,
+                     cu_dev, seq0, tok_base, n_seq, T, H, c.x, c.x16);
+  VR_TRY(launch_gemm_f16x3(e, p.enc, EPI_BIAS_F16, {.A = c.x16, .W = w.s_qkv, .bias = w.bqkv, .Ch = c.q16, .M = n_seq, .N = H,
+                                                    .K = H, .passes = 1}));
+  const double head_flop = 2.0 * n_seq * static_cast<double>(H) * H;  // nh products of [n_seq, dh] x [dh, H]
+  prof_begin(e, VR_PROF_GEMM, head_flop);
+  hipLaunchKernelGGL((cls_head_gemm_kernel<false>), dim3(static_cast<unsigned>(H / 64), mblocks, static_cast<unsigned>(nh)),
+                     dim3(256), 0, p.s, w.wk_t, H, static_cast<int64_t>(dh), c.q16, H, dh, n_seq, H, dh, w.s_qkv_f.unscale,
+                     static_cast<const float*>(nullptr), static_cast<const float*>(nullptr),
+                     static_cast<const float*>(nullptr), c.u16, nh * H, H);
+  prof_end(e);
+  // two passes over the T rows, 2 H multiply-adds per (token, head) each
+  prof_begin(e, VR_PROF_ATTENTION, 4.0 * nh * static_cast<double>(H) * T);
+  hipLaunchKernelGGL(cls_attend_kernel, dim3(static_cast<unsigned>(n_seq)), dim3(256), cls_attend_lds(H, cls_lpad), p.s, p.xh,
+                     cur.stat, c.u16, cu_dev, seq0, tok_base, T, H, nh, 1.4426950408889634f / sqrtf(static_cast<float>(dh)),
+                     cls_lpad, c.z16, c.gamma);
+  prof_end(e);
+  prof_begin(e, VR_PROF_GEMM, head_flop);
+  hipLaunchKernelGGL((cls_head_gemm_kernel<true>), dim3(static_cast<unsigned>((dh + 63) / 64), mblocks, static_cast<unsigned>(nh)),
+                     dim3(256), 0, p.s, w.s_qkv_f.hi + static_cast<int64_t>(2) * H * H, H, static_cast<int64_t>(dh) * H, c.z16,
+                     nh * H, H, n_seq, dh, H, w.s_qkv_f.unscale, w.cs_qkv + 2 * H, w.c_qkv + 2 * H, c.gamma,
+                     reinterpret_cast<half_t*>(c.ctx), H, dh);
+  prof_end(e);
+  return 0;
+}
+
+// The rest of the last layer of a [CLS]-pooled post-norm model, on the n_seq [CLS] rows only (ClsRows), and the pooling:
+//   x = LN_1(x + W_o ctx);  x = LN_2(x + W_down act(W_up x))  — forward_chunk's f32 / f16x3 layer at M = n_seq, in every
+// mode. `gathered` (collapse): c.x and c.ctx are written already; otherwise the context rows come from enc->ctx and the
+// hidden rows from wherever the mode keeps them (f16: LayerNorm of the pre-LN rows — f32 ones, or with cur16 the f16 rows in xs).
+static int cls_tail(const Pass& p, const LayerWeights& w, const ClsRows& c, bool gathered, const Hidden& cur, bool cur16,
+                    const int32_t* cu_dev, int seq0, int seq1, int tok_base, float* out_dev) {
+  Encoder* enc = p.enc;
+  const vr_bert_desc& d = enc->d;
+  const int T = p.T, H = d.hidden, I = d.intermediate, n_seq = seq1 - seq0;
+  const dim3 gblocks(Pass::blocks4(n_seq));
+  if (!gathered) {
+    hipLaunchKernelGGL(gather_first_rows_kernel, gblocks, dim3(256), 0, p.s, reinterpret_cast<const float4*>(enc->ctx), cu_dev,
+                       seq0, tok_base, n_seq, T, p.plain ? H / 8 : H / 4, reinterpret_cast<float4*>(c.ctx));
+    if (p.plain && cur16)
+      hipLaunchKernelGGL(gather_first_rows_ln16_kernel, gblocks, dim3(256), 0, p.s, p.xh, cur.stat, cur.g, cur.b, cu_dev, seq0,
+                         tok_base, n_seq, T, H, c.x, static_cast<half_t*>(nullptr));
+    else if (p.plain)
+      hipLaunchKernelGGL(gather_first_rows_ln_kernel, gblocks, dim3(256), 0, p.s, cur.pre, cur.stat, cur.g, cur.b, cu_dev, seq0,
+                         tok_base, n_seq, T, H, c.x);
+    else
+      hipLaunchKernelGGL(gather_first_rows_kernel, gblocks, dim3(256), 0, p.s, reinterpret_cast<const float4*>(enc->x), cu_dev,
+                         seq0, tok_base, n_seq, T, H / 4, reinterpret_cast<float4*>(c.x));
+  }
+  const Rows x = p.rows(c.xs, c.x), ctx = p.rows(c.ctx), ffn = p.rows(c.ffn);
+  VR_TRY(project_residual(p, w.wo, w.s_o, w.bo, n_seq, H, H, ctx, c.x, c.tmp));
+  layernorm_rows(p, c.tmp, n_seq, w.ln1g, w.ln1b, x);
+  if (d.ffn != VR_FFN_GELU)
+    VR_TRY(gated_up_rows(p, w, p.plain && enc->fuse && skinny_routed(n_seq, 2 * I, H), n_seq, x, ffn));
+  else
+    VR_TRY(project_act(p, EPI_BIAS_GELU, w.w1, w.s_1, w.b1, n_seq, I, H, x, ffn));
+  VR_TRY(project_residual(p, w.w2, w.s_2, w.b2, n_seq, H, I, ffn, c.x, c.tmp));
+  layernorm_rows(p, c.tmp, n_seq, w.ln2g, w.ln2b, {c.x});
+  launch_pool(p.e, enc, c.x, cu_dev, seq0, seq1, tok_base, 1, out_dev, nullptr);
   VR_HIP(hipGetLastError());
   return 0;
 }
@@ -6054,33 +6141,20 @@ static int forward_chunk(vr_engine* e, Encoder* enc, const int32_t* ids_dev, con
   if (d.norm == VR_NORM_PRE)  // a routine of its own: none of the LayerNorm folds below applies to it
     return forward_chunk_prenorm(e, enc, ids_dev, cu_dev, n_seq_total, seq0, seq1, tok_base, T, max_len, attn_flop, out_dev, sp);
   const int H = d.hidden, I = d.intermediate, nh = d.heads, dh = H / nh;
-  hipStream_t s = e->stream;
-  const unsigned row_blocks = static_cast<unsigned>((T + 3) / 4);
   // f16x3 mode: every GEMM input also exists as (hi, lo) f16. The split hidden state lives in xs;
   // the context and the FFN intermediate are ONLY needed split, so they reuse the f32 buffers.
   // f16 mode: the same, with plain f16 rows and no lo half (the lo pointers are null).
-  const bool split = d.precision != VR_PRECISION_F32;
-  const bool plain = d.precision == VR_PRECISION_F16;
-  const int passes = plain ? 1 : 3;
-  half_t* xh = split ? reinterpret_cast<half_t*>(enc->xs) : nullptr;
-  half_t* xl = split && !plain ? xh + 8 : nullptr;  // interleaved (hi, lo) layout, see split_at
-  half_t* ch = split ? reinterpret_cast<half_t*>(enc->ctx) : nullptr;
-  half_t* cl = split && !plain ? ch + 8 : nullptr;
-  half_t* fh = split ? reinterpret_cast<half_t*>(enc->ffn) : nullptr;
-  half_t* fl = split && !plain ? fh + 8 : nullptr;
+  Pass p(e, enc, T);
+  hipStream_t s = p.s;
+  const bool plain = p.plain;
+  half_t *xh = p.xh, *xl = p.xl, *ch = p.ctx.hi, *fh = p.ffn.hi;
   // f16 mode does not store the f32 hidden state at all. A LayerNorm writes its f16 output (the next
   // GEMM's input) and the row's (mean, 1/sigma); the only other reader of the hidden state is the
   // residual add of the next projection's epilogue, which already reads 4 bytes per element — it
   // reads the PRE-LN row instead and re-derives the LayerNorm output (ln_apply: same operations,
   // same bits). That takes 4 of the 10 bytes per element out of every LayerNorm pass. The pre-LN
   // rows alternate between enc->tmp and enc->x; `cur` describes the current hidden state.
-  struct Hidden {
-    const float* pre;
-    const float2* stat;
-    const float* g;
-    const float* b;
-  };
-  float2* stat_a = reinterpret_cast<float2*>(enc->lnstat);
+  float2* stat_a = p.stat;
   float2* stat_b = plain ? stat_a + T : nullptr;
   Hidden cur{enc->x, stat_b, enc->lng, enc->lnb};
   bool cur16 = false;  // f16 residual stream: the current pre-LN rows are the f16 rows in xh (cur.pre is stale)
@@ -6100,214 +6174,83 @@ static int forward_chunk(vr_engine* e, Encoder* enc, const int32_t* ids_dev, con
   const int segs = H / 64;
   const unsigned fin_blocks = static_cast<unsigned>((T + 255) / 256);
   if (seg_dev)
-    hipLaunchKernelGGL((embed_ln_kernel<true>), dim3(row_blocks), dim3(256), 0, s, ids_dev, cu_dev, n_seq_total,
+    hipLaunchKernelGGL((embed_ln_kernel<true>), dim3(p.row_blocks), dim3(256), 0, s, ids_dev, cu_dev, n_seq_total,
                        tok_base, T, H, d.vocab, enc->word, enc->pos, enc->type, enc->lng, enc->lnb, d.eps,
                        lnfuse ? nullptr : enc->x, xh, xl, lnfuse ? enc->x : nullptr, lnfuse ? stat_b : nullptr, seg_dev);
   else if (d.position != VR_POS_LEARNED)  // rotary, or no positions at all: the body that reads no table
-    hipLaunchKernelGGL(embed_ln_rotary_kernel, dim3(row_blocks), dim3(256), 0, s, ids_dev, cu_dev, n_seq_total,
+    hipLaunchKernelGGL(embed_ln_rotary_kernel, dim3(p.row_blocks), dim3(256), 0, s, ids_dev, cu_dev, n_seq_total,
                        tok_base, T, H, d.vocab, enc->word, enc->type, enc->lng, enc->lnb, d.eps, lnfuse ? nullptr : enc->x, xh, xl,
                        lnfuse ? enc->x : nullptr, lnfuse ? stat_b : nullptr);
   else
-    hipLaunchKernelGGL((embed_ln_kernel<false>), dim3(row_blocks), dim3(256), 0, s, ids_dev, cu_dev, n_seq_total,
+    hipLaunchKernelGGL((embed_ln_kernel<false>), dim3(p.row_blocks), dim3(256), 0, s, ids_dev, cu_dev, n_seq_total,
                        tok_base, T, H, d.vocab, enc->word, enc->pos, enc->type, enc->lng, enc->lnb, d.eps,
                        lnfuse ? nullptr : enc->x, xh, xl, lnfuse ? enc->x : nullptr, lnfuse ? stat_b : nullptr,
                        static_cast<const int32_t*>(nullptr));
   // Rotary positions and the gated FFN. UNFUSED: passes of their own behind the projections' existing epilogues —
-  // rope_kernel in place on the Q and K thirds of the qkv rows, and the FFN-up projection (N = 2I, bias only) into
-  // enc->glu followed by glu_kernel, which writes the rows the FFN-down projection reads. FUSED (f16 mode, products that
-  // launch_gemm_f16x3 / launch_skinny_ln send to a skinny kernel, i.e. at most 256 rows — a question, a few chunks):
-  // the projection runs over the re-ordered matrix and its epilogue rotates / gates (EPI_ROPE_F16, EPI_*GLU_F16), no
-  // further launch and no second f16 rounding. VR_ENCODE_FUSE=0 when the model is loaded keeps the unfused form
-  // everywhere for that model (A/B runs in one process, tests); its cached graphs then hold that form too.
+  // rope_kernel in place on the Q and K thirds of the qkv rows (rotate_rows), and the FFN-up projection (N = 2I, bias
+  // only) into enc->glu followed by glu_kernel (gate_rows), which writes the rows the FFN-down projection reads. FUSED
+  // (f16 mode, products that launch_gemm_f16x3 / launch_skinny_ln send to a skinny kernel, i.e. at most 256 rows — a
+  // question, a few chunks): the projection runs over the re-ordered matrix and its epilogue rotates / gates
+  // (EPI_ROPE_F16, EPI_*GLU_F16), no further launch and no second f16 rounding. VR_ENCODE_FUSE=0 when the model is loaded
+  // keeps the unfused form everywhere for that model (A/B runs in one process, tests); its cached graphs then hold that
+  // form too.
   const bool rotary = d.position == VR_POS_ROTARY, gated = d.ffn != VR_FFN_GELU;
   const int N1 = gated ? 2 * I : I;
-  half_t* gluh = reinterpret_cast<half_t*>(enc->glu);
   const bool fuse_enabled = enc->fuse;
   const bool fuse_rope = rotary && plain && fuse_enabled && skinny_routed(T, 3 * H, H);
   auto fuse_glu = [&](int M) { return gated && plain && fuse_enabled && skinny_routed(M, N1, H); };
-  const int glu_epi = d.ffn == VR_FFN_SWIGLU ? EPI_SWIGLU_F16 : EPI_GEGLU_F16;
   // large batches: the gate in the epilogue of the folded-LayerNorm projection (mid / ping-pong kernel, EPI_FOLD_*GLU)
   const bool fuse_glu_big = gated && fuse_enabled && !fuse_glu(T) && fold_big && pp_usable(N1, H) &&
                             enc->layers[0].cs_1_p != nullptr;
-  const int32_t* posidx = reinterpret_cast<const int32_t*>(enc->posidx);
-  half_t* qkvh = reinterpret_cast<half_t*>(enc->qkv);  // f16 mode: the Q/K/V rows
-  half_t* parth = reinterpret_cast<half_t*>(part);     // the folded LayerNorms' partial sums, in an epilogue's Cl slot
+  half_t* parth = reinterpret_cast<half_t*>(part);  // the folded LayerNorms' partial sums, in an epilogue's Cl slot
   if (rotary)
     hipLaunchKernelGGL(positions_kernel, dim3(static_cast<unsigned>((T + 255) / 256)), dim3(256), 0, s, cu_dev, n_seq_total,
                        tok_base, T, reinterpret_cast<int32_t*>(enc->posidx));
-  auto rope = [&]() {
-    if (!rotary || fuse_rope) return;
-    if (plain)
-      hipLaunchKernelGGL(rope_kernel<half_t>, dim3(row_blocks), dim3(256), 0, s, reinterpret_cast<half_t*>(enc->qkv), posidx, T,
-                         H, dh, enc->rope);
-    else
-      hipLaunchKernelGGL(rope_kernel<float>, dim3(row_blocks), dim3(256), 0, s, enc->qkv, posidx, T, H, dh, enc->rope);
-  };
-  // M rows of enc->glu -> the FFN-down input: f16 mode plain f16 rows at out_h, f16x3 (hi, lo) rows at out_h, f32 at out
-  auto glu = [&](int M, float* out, half_t* out_h) {
-    const int64_t n8 = static_cast<int64_t>(M) * (I / 8);
-    const dim3 grid(static_cast<unsigned>((n8 + 255) / 256));
-    if (plain) hipLaunchKernelGGL((glu_kernel<half_t, 2>), grid, dim3(256), 0, s, gluh, n8, I, d.ffn, static_cast<float*>(nullptr), out_h);
-    else if (split) hipLaunchKernelGGL((glu_kernel<float, 1>), grid, dim3(256), 0, s, enc->glu, n8, I, d.ffn, static_cast<float*>(nullptr), out_h);
-    else hipLaunchKernelGGL((glu_kernel<float, 0>), grid, dim3(256), 0, s, enc->glu, n8, I, d.ffn, out, static_cast<half_t*>(nullptr));
-  };
-  // CLS pooling reads one row per sequence, so everything after the LAST layer's attention is needed
-  // for those rows only: their context rows (and residual rows) are gathered into compact [n_seq, *]
-  // matrices carved out of the qkv buffer (free once attention has run), and the output projection,
-  // both LayerNorms and the FFN run on n_seq rows instead of T. Every row's arithmetic is unchanged
-  // (a GEMM row does not depend on its neighbours), so the embeddings are bit-identical; for
-  // bge-base this removes 10/12 of the last layer's GEMM work. The Q/K/V projection of all T rows
-  // (one GEMM) and the attention over them remain on this route; the large f16 batches of `collapse`
-  // below replace both.
+  // the last layer of a [CLS]-pooled model runs on the [CLS] rows only behind its attention (ClsRows, cls_tail)
   const int n_seq = seq1 - seq0;
-  const bool cls_tail = !sp && d.pooling == VR_POOL_CLS && !enc->layers.empty() &&
+  const bool cls_rows = !sp && d.pooling == VR_POOL_CLS && !enc->layers.empty() &&
                         static_cast<int64_t>(n_seq) * (4 * H + I) <= static_cast<int64_t>(T) * 3 * H;
-  // The [rows, 2I] pre-activation workspace exists only once a pass really stores one: an unfused FFN-up over the T
-  // rows, or over the CLS tail's n_seq rows. (Never during a graph capture: a shape runs eagerly first, and a
-  // reallocation of the workspace drops both this buffer and the graphs.)
-  if (gated && !enc->glu && ((!fuse_glu(T) && !fuse_glu_big) || (cls_tail && !fuse_glu(n_seq)))) {
-    const size_t rows = static_cast<size_t>(enc->ws_tokens);
-    VR_TRY(dev_alloc_copy(e, enc, nullptr, plain ? rows * I : rows * 2 * I, 0, &enc->glu));
-    gluh = reinterpret_cast<half_t*>(enc->glu);
-  }
-  float* xc = enc->qkv;                                       // [n_seq, H] hidden state of the [CLS] rows
-  float* tmpc = xc + static_cast<int64_t>(n_seq) * H;         // [n_seq, H]
-  float* xsc = tmpc + static_cast<int64_t>(n_seq) * H;        // [n_seq, 2H] halfs (split) = n_seq*H floats
-  float* ctxc = xsc + static_cast<int64_t>(n_seq) * H;        // [n_seq, H] f32 or [n_seq, 2H] halfs
-  float* ffnc = ctxc + static_cast<int64_t>(n_seq) * H;       // [n_seq, I] f32 or [n_seq, 2I] halfs
-  // `collapse`: the last layer of such a model attends from the [CLS] rows on the hidden rows themselves — no Q/K/V
-  // projection of the T rows, no attention launch over them (see cls_attend_kernel). The route exists for the f16
-  // residual stream of large batches (the hidden state is the f16 pre-LayerNorm rows in xh with their statistics),
-  // plain bidirectional attention of the hidden width (learned or no positions, no bias, slopes, window, mask or Q/K
-  // norm), head size 32 or 64, at most kClsHeads heads, a longest sequence whose logits and weights fit the 64 KiB of
-  // LDS beside the u rows (cls_attend_lds: 608 tokens at H = 768, 480 at H = 1024), and T / n_seq large enough that
-  // its workspace fits the qkv buffer behind the tail's (no kernel writes that buffer in the last layer then).
-  // Everything else, a cross-encoder (build_encoder) and every model loaded under VR_CLS_COLLAPSE=0 keep the route above.
+  // the unfused gate's workspace: for an unfused FFN-up over the T rows, or over the CLS tail's n_seq rows
+  if (gated && ((!fuse_glu(T) && !fuse_glu_big) || (cls_rows && !fuse_glu(n_seq)))) VR_TRY(p.need_glu());
+  const ClsRows cls(enc, n_seq);
+  // `collapse` (cls_collapse_attend) exists for the f16 residual stream of large batches (the hidden state is the f16
+  // pre-LayerNorm rows in xh with their statistics), plain bidirectional attention of the hidden width (learned or no
+  // positions, no bias, slopes, window, mask or Q/K norm), head size 32 or 64, at most kClsHeads heads, a longest
+  // sequence whose logits and weights fit the 64 KiB of LDS beside the u rows (cls_attend_lds: 608 tokens at H = 768,
+  // 480 at H = 1024), and T / n_seq large enough that its workspace fits the qkv buffer behind the tail's (no kernel
+  // writes that buffer in the last layer then). Everything else, a cross-encoder (build_encoder) and every model loaded
+  // under VR_CLS_COLLAPSE=0 keep the Q/K/V projection and the attention over the T rows.
   const int cls_lpad = (max_len + kClsStep - 1) / kClsStep * kClsStep;
-  auto up4 = [](int64_t n) { return (n + 3) / 4 * 4; };  // (16-byte aligned pieces)
-  half_t* x16c = reinterpret_cast<half_t*>(ffnc + up4(static_cast<int64_t>(n_seq) * I));  // [n_seq, H] f16 LN(x) of the [CLS] rows
-  half_t* q16c = x16c + up4(static_cast<int64_t>(n_seq) * H);                              // [n_seq, H] their queries
-  half_t* u16c = q16c + up4(static_cast<int64_t>(n_seq) * H);                              // [n_seq, nh, H] u
-  half_t* z16c = u16c + up4(static_cast<int64_t>(n_seq) * nh * H);                         // [n_seq, nh, H] z
-  float* gammac = reinterpret_cast<float*>(z16c + up4(static_cast<int64_t>(n_seq) * nh * H));  // [n_seq, nh]
-  const int64_t cls_ws_floats = (gammac + static_cast<int64_t>(n_seq) * nh) - enc->qkv;
-  const bool collapse = cls_tail && enc->cls_collapse && plain && fold_big && res16 && enc->layers.size() > 1 &&
+  const bool collapse = cls_rows && enc->cls_collapse && plain && fold_big && res16 && enc->layers.size() > 1 &&
                         enc->layers.back().wk_t != nullptr && d.position != VR_POS_ROTARY && !enc->bias && !enc->slopes &&
                         !enc->causal && !enc->qk_norm && enc->attn == H && (dh == 32 || dh == 64) && nh <= kClsHeads &&
-                        cls_attend_lds(H, cls_lpad) <= 65536 && cls_ws_floats <= static_cast<int64_t>(T) * 3 * H;
+                        cls_attend_lds(H, cls_lpad) <= 65536 && cls.floats <= static_cast<int64_t>(T) * 3 * H;
   for (size_t li = 0; li < enc->layers.size(); ++li) {
     const LayerWeights& w = enc->layers[li];
-    const bool tail = cls_tail && li + 1 == enc->layers.size();
-    if (tail && collapse) {
-      // (cur16 holds: res16 and li > 0) steps 1-4 of cls_attend_kernel's comment; ctxc is what the tail below reads
-      const unsigned gblocks = static_cast<unsigned>((n_seq + 3) / 4);
-      const unsigned mblocks = static_cast<unsigned>((n_seq + 63) / 64);
-      hipLaunchKernelGGL(gather_first_rows_ln16_kernel, dim3(gblocks), dim3(256), 0, s, xh, cur.stat, cur.g, cur.b, cu_dev,
-                         seq0, tok_base, n_seq, T, H, xc, x16c);
-      VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_F16, {.A = x16c, .W = w.s_qkv, .bias = w.bqkv, .Ch = q16c, .M = n_seq, .N = H,
-                                                      .K = H, .passes = 1}));
-      const double head_flop = 2.0 * n_seq * static_cast<double>(H) * H;  // nh products of [n_seq, dh] x [dh, H]
-      prof_begin(e, VR_PROF_GEMM, head_flop);
-      hipLaunchKernelGGL((cls_head_gemm_kernel<false>), dim3(static_cast<unsigned>(H / 64), mblocks, static_cast<unsigned>(nh)),
-                         dim3(256), 0, s, w.wk_t, H, static_cast<int64_t>(dh), q16c, H, dh, n_seq, H, dh, w.s_qkv_f.unscale,
-                         static_cast<const float*>(nullptr), static_cast<const float*>(nullptr),
-                         static_cast<const float*>(nullptr), u16c, nh * H, H);
-      prof_end(e);
-      // two passes over the T rows, 2 H multiply-adds per (token, head) each
-      prof_begin(e, VR_PROF_ATTENTION, 4.0 * nh * static_cast<double>(H) * T);
-      hipLaunchKernelGGL(cls_attend_kernel, dim3(static_cast<unsigned>(n_seq)), dim3(256), cls_attend_lds(H, cls_lpad), s, xh,
-                         cur.stat, u16c, cu_dev, seq0, tok_base, T, H, nh, 1.4426950408889634f / sqrtf(static_cast<float>(dh)),
-                         cls_lpad, z16c, gammac);
-      prof_end(e);
-      prof_begin(e, VR_PROF_GEMM, head_flop);
-      hipLaunchKernelGGL((cls_head_gemm_kernel<true>), dim3(static_cast<unsigned>((dh + 63) / 64), mblocks, static_cast<unsigned>(nh)),
-                         dim3(256), 0, s, w.s_qkv_f.hi + static_cast<int64_t>(2) * H * H, H, static_cast<int64_t>(dh) * H, z16c,
-                         nh * H, H, n_seq, dh, H, w.s_qkv_f.unscale, w.cs_qkv + 2 * H, w.c_qkv + 2 * H, gammac,
-                         reinterpret_cast<half_t*>(ctxc), H, dh);
-      prof_end(e);
-    } else if (plain && fold_ln && li > 0 && fuse_rope)  // ... and the rotation in its epilogue
+    const bool tail = cls_rows && li + 1 == enc->layers.size();
+    const bool fold_prev = fold_ln && li > 0;  // the previous layer's closing LayerNorm runs inside this projection
+    if (tail && collapse)  // (cur16 holds: res16 and li > 0)
+      VR_TRY(cls_collapse_attend(p, w, cur, cls, cu_dev, seq0, n_seq, tok_base, cls_lpad));
+    else if (fold_prev && fuse_rope)  // ... and the rotation in its epilogue
       VR_TRY(launch_skinny_ln(e, EPI_ROPE_F16, cur.pre, d.eps, const_cast<float2*>(cur.stat),
-                              {.W = w.s_qkv_p, .bias = w.bqkv_p, .Ch = qkvh, .M = T, .N = 3 * H, .K = H, .ln_g = cur.g,
-                               .ln_b = cur.b, .rope_tab = enc->rope, .rope_pos = posidx}));
-    else if (plain && fold_ln && li > 0)  // the previous layer's closing LayerNorm runs inside this projection
+                              {.W = w.s_qkv_p, .bias = w.bqkv_p, .Ch = p.qkvh, .M = T, .N = 3 * H, .K = H, .ln_g = cur.g,
+                               .ln_b = cur.b, .rope_tab = enc->rope, .rope_pos = p.posidx}));
+    else if (fold_prev)
       VR_TRY(launch_skinny_ln(e, EPI_BIAS_F16, cur.pre, d.eps, const_cast<float2*>(cur.stat),
-                              {.W = w.s_qkv, .bias = w.bqkv, .Ch = qkvh, .M = T, .N = 3 * H, .K = H, .ln_g = cur.g, .ln_b = cur.b}));
-    else if (plain && fold_big && li > 0)  // xh holds the f16 PRE-LN rows the previous FFN-down epilogue stored
-      VR_TRY(launch_gemm_f16x3(e, enc, EPI_FOLD_F16, {.A = xh, .W = w.s_qkv_f, .bias = w.c_qkv, .Ch = qkvh, .M = T, .N = 3 * H,
+                              {.W = w.s_qkv, .bias = w.bqkv, .Ch = p.qkvh, .M = T, .N = 3 * H, .K = H, .ln_g = cur.g, .ln_b = cur.b}));
+    else if (fold_big && li > 0)  // xh holds the f16 PRE-LN rows the previous FFN-down epilogue stored
+      VR_TRY(launch_gemm_f16x3(e, enc, EPI_FOLD_F16, {.A = xh, .W = w.s_qkv_f, .bias = w.c_qkv, .Ch = p.qkvh, .M = T, .N = 3 * H,
                                                       .K = H, .passes = 1, .ln_stat = cur.stat, .ln_g = w.cs_qkv}));
-    else if (plain && fuse_rope)
-      VR_TRY(launch_gemm_f16x3(e, enc, EPI_ROPE_F16, {.A = xh, .W = w.s_qkv_p, .bias = w.bqkv_p, .Ch = qkvh, .M = T, .N = 3 * H,
-                                                      .K = H, .passes = 1, .rope_tab = enc->rope, .rope_pos = posidx}));
-    else if (plain)  // Q, K, V as plain f16 rows for the f16 attention kernels
-      VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_F16, {.A = xh, .A_lo = xl, .W = w.s_qkv, .bias = w.bqkv, .Ch = qkvh, .M = T,
-                                                      .N = 3 * H, .K = H, .passes = passes}));
-    else if (split)
-      VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS, {.A = xh, .A_lo = xl, .W = w.s_qkv, .bias = w.bqkv, .C = enc->qkv, .M = T,
-                                                  .N = 3 * H, .K = H, .passes = passes}));
-    else
-      VR_TRY(launch_gemm(e, EPI_BIAS, enc->x, w.wqkv, w.bqkv, nullptr, enc->qkv, T, 3 * H, H));
+    else if (fuse_rope)
+      VR_TRY(launch_gemm_f16x3(e, enc, EPI_ROPE_F16, {.A = xh, .W = w.s_qkv_p, .bias = w.bqkv_p, .Ch = p.qkvh, .M = T, .N = 3 * H,
+                                                      .K = H, .passes = 1, .rope_tab = enc->rope, .rope_pos = p.posidx}));
+    else  // (f16 mode: Q, K, V as plain f16 rows for the f16 attention kernels)
+      VR_TRY(project_bias(p, w.wqkv, w.s_qkv, w.bqkv, T, 3 * H, H, p.x(enc->x), enc->qkv));
     if (!(tail && collapse)) {
-      rope();
+      if (rotary && !fuse_rope) rotate_rows(p, enc->rope, H, dh);
       VR_TRY(launch_attention(e, enc, cu_dev, seq0, n_seq, tok_base, max_len, tail, 0, attn_flop));
     }
-    if (tail) {
-      const unsigned gblocks = static_cast<unsigned>((n_seq + 3) / 4);
-      const unsigned cblocks = gblocks;
-      if (!collapse)  // (collapse: ctxc and xc are written above)
-        hipLaunchKernelGGL(gather_first_rows_kernel, dim3(gblocks), dim3(256), 0, s, reinterpret_cast<const float4*>(enc->ctx),
-                           cu_dev, seq0, tok_base, n_seq, T, plain ? H / 8 : H / 4, reinterpret_cast<float4*>(ctxc));
-      if (collapse)
-        ;
-      else if (plain && cur16)
-        hipLaunchKernelGGL(gather_first_rows_ln16_kernel, dim3(gblocks), dim3(256), 0, s, xh, cur.stat, cur.g, cur.b,
-                           cu_dev, seq0, tok_base, n_seq, T, H, xc, static_cast<half_t*>(nullptr));
-      else if (plain)
-        hipLaunchKernelGGL(gather_first_rows_ln_kernel, dim3(gblocks), dim3(256), 0, s, cur.pre, cur.stat, cur.g, cur.b,
-                           cu_dev, seq0, tok_base, n_seq, T, H, xc);
-      else
-        hipLaunchKernelGGL(gather_first_rows_kernel, dim3(gblocks), dim3(256), 0, s, reinterpret_cast<const float4*>(enc->x),
-                           cu_dev, seq0, tok_base, n_seq, T, H / 4, reinterpret_cast<float4*>(xc));
-      half_t* xch = reinterpret_cast<half_t*>(xsc);
-      half_t* cch = reinterpret_cast<half_t*>(ctxc);
-      half_t* fch = reinterpret_cast<half_t*>(ffnc);
-      if (split)
-        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_RESIDUAL, {.A = cch, .A_lo = plain ? nullptr : cch + 8, .W = w.s_o, .bias = w.bo,
-                                                             .R = xc, .C = tmpc, .M = n_seq, .N = H, .K = H, .passes = passes}));
-      else
-        VR_TRY(launch_gemm(e, EPI_BIAS_RESIDUAL, ctxc, w.wo, w.bo, xc, tmpc, n_seq, H, H));
-      hipLaunchKernelGGL(layernorm_kernel, dim3(cblocks), dim3(256), 0, s, tmpc, n_seq, H, w.ln1g, w.ln1b, d.eps, xc,
-                         split ? xch : nullptr, split && !plain ? xch + 8 : nullptr, static_cast<float2*>(nullptr));
-      if (gated && fuse_glu(n_seq)) {
-        VR_TRY(launch_gemm_f16x3(e, enc, glu_epi, {.A = xch, .W = w.s_1_p, .bias = w.b1_p, .Ch = fch, .M = n_seq, .N = N1, .K = H,
-                                                   .passes = 1}));
-      } else if (gated) {
-        if (plain)
-          VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_F16, {.A = xch, .W = w.s_1, .bias = w.b1, .Ch = gluh, .M = n_seq, .N = N1, .K = H,
-                                                          .passes = 1}));
-        else if (split)
-          VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS, {.A = xch, .A_lo = xch + 8, .W = w.s_1, .bias = w.b1, .C = enc->glu, .M = n_seq,
-                                                      .N = N1, .K = H, .passes = passes}));
-        else
-          VR_TRY(launch_gemm(e, EPI_BIAS, xc, w.w1, w.b1, nullptr, enc->glu, n_seq, N1, H));
-        glu(n_seq, ffnc, fch);
-      } else if (split) {
-        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_GELU, {.A = xch, .A_lo = plain ? nullptr : xch + 8, .W = w.s_1, .bias = w.b1, .Ch = fch,
-                                                         .Cl = plain ? nullptr : fch + 8, .M = n_seq, .N = I, .K = H, .passes = passes}));
-      } else {
-        VR_TRY(launch_gemm(e, EPI_BIAS_GELU, xc, w.w1, w.b1, nullptr, ffnc, n_seq, I, H));
-      }
-      if (split) {
-        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_RESIDUAL, {.A = fch, .A_lo = plain ? nullptr : fch + 8, .W = w.s_2, .bias = w.b2,
-                                                             .R = xc, .C = tmpc, .M = n_seq, .N = H, .K = I, .passes = passes}));
-      } else {
-        VR_TRY(launch_gemm(e, EPI_BIAS_RESIDUAL, ffnc, w.w2, w.b2, xc, tmpc, n_seq, H, I));
-      }
-      hipLaunchKernelGGL(layernorm_kernel, dim3(cblocks), dim3(256), 0, s, tmpc, n_seq, H, w.ln2g, w.ln2b, d.eps, xc,
-                         static_cast<half_t*>(nullptr), static_cast<half_t*>(nullptr), static_cast<float2*>(nullptr));
-      launch_pool(e, enc, xc, cu_dev, seq0, seq1, tok_base, 1, out_dev, nullptr);
-      VR_HIP(hipGetLastError());
-      return 0;
-    }
+    if (tail) return cls_tail(p, w, cls, collapse, cur, cur16, cu_dev, seq0, seq1, tok_base, out_dev);
     if (plain) {
       // hidden state = LN(cur.pre): pre-LN rows alternate between the two buffers
       float* t1 = cur.pre == enc->x ? enc->tmp : enc->x;
@@ -6329,25 +6272,19 @@ static int forward_chunk(vr_engine* e, Encoder* enc, const int32_t* ids_dev, con
         VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_RESIDUAL_LN,
                                  {.A = ch, .W = w.s_o, .bias = w.bo, .R = cur.pre, .C = t1, .M = T, .N = H, .K = H, .passes = 1,
                                   .ln_stat = cur.stat, .ln_g = cur.g, .ln_b = cur.b}));
-      if (fold_ln || fold_big)
-        ;  // the attention-output LayerNorm runs inside the FFN-up projection below
-      else if (H % 256 == 0)
-        hipLaunchKernelGGL(layernorm_f16_kernel, dim3(row_blocks), dim3(256), 0, s, t1, T, H, w.ln1g, w.ln1b, d.eps,
-                           static_cast<float*>(nullptr), xh, s1);
-      else
-        hipLaunchKernelGGL(layernorm_kernel, dim3(row_blocks), dim3(256), 0, s, t1, T, H, w.ln1g, w.ln1b, d.eps,
-                           static_cast<float*>(nullptr), xh, static_cast<half_t*>(nullptr), s1);
+      // the attention-output LayerNorm: a launch of its own unless it runs inside the FFN-up projection below
+      if (!fold_ln && !fold_big) layernorm_f16_rows(p, t1, w.ln1g, w.ln1b, nullptr, s1);
       const Hidden mid{t1, s1, w.ln1g, w.ln1b};
       float* t2 = const_cast<float*>(cur.pre);  // its last reader (the epilogue above) is done
       float2* s2 = const_cast<float2*>(cur.stat);
-      half_t* up_out = gated ? gluh : fh;  // gated: the same projections with the bias-only f16 epilogues, then glu_kernel
+      half_t* up_out = gated ? p.gluh : fh;  // gated: the same projections with the bias-only f16 epilogues, then glu_kernel
       const bool fg = fuse_glu(T);      // ... or, fused, the gate in the projection's epilogue over the re-ordered matrix
       const bool fgb = fuse_glu_big;
       if (fg && fold_ln)
-        VR_TRY(launch_skinny_ln(e, glu_epi, t1, d.eps, s1,
+        VR_TRY(launch_skinny_ln(e, p.glu_epi, t1, d.eps, s1,
                                 {.W = w.s_1_p, .bias = w.b1_p, .Ch = fh, .M = T, .N = N1, .K = H, .ln_g = w.ln1g, .ln_b = w.ln1b}));
       else if (fg)
-        VR_TRY(launch_gemm_f16x3(e, enc, glu_epi, {.A = xh, .W = w.s_1_p, .bias = w.b1_p, .Ch = fh, .M = T, .N = N1, .K = H, .passes = 1}));
+        VR_TRY(gated_up_rows(p, w, true, T, p.x(nullptr), p.ffn));
       else if (fgb)
         VR_TRY(launch_gemm_f16x3(e, enc, d.ffn == VR_FFN_SWIGLU ? EPI_FOLD_SWIGLU : EPI_FOLD_GEGLU,
                                  {.A = xh, .W = w.s_1_fp, .bias = w.c_1_p, .Ch = fh, .M = T, .N = N1, .K = H, .passes = 1, .ln_stat = s1,
@@ -6362,7 +6299,7 @@ static int forward_chunk(vr_engine* e, Encoder* enc, const int32_t* ids_dev, con
       else
         VR_TRY(launch_gemm_f16x3(e, enc, gated ? EPI_BIAS_F16 : EPI_BIAS_GELU,
                                  {.A = xh, .W = w.s_1, .bias = w.b1, .Ch = up_out, .M = T, .N = N1, .K = H, .passes = 1}));
-      if (gated && !fg && !fgb) glu(T, nullptr, fh);
+      if (gated && !fg && !fgb) gate_rows(p, T, p.ffn);
       if (res16)  // (the last layer of a mean-pooled model also writes f32 rows: the final LayerNorm reads them)
         VR_TRY(launch_gemm_f16x3(e, enc, last ? EPI_RLS_R16_O32 : EPI_RLS_R16_O16,
                                  {.A = fh, .W = w.s_2, .bias = w.b2, .R = reinterpret_cast<const float*>(xh), .C = last ? t2 : nullptr,
@@ -6376,52 +6313,27 @@ static int forward_chunk(vr_engine* e, Encoder* enc, const int32_t* ids_dev, con
         VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_RESIDUAL_LN,
                                  {.A = fh, .W = w.s_2, .bias = w.b2, .R = mid.pre, .C = t2, .M = T, .N = H, .K = I, .passes = 1,
                                   .ln_stat = mid.stat, .ln_g = mid.g, .ln_b = mid.b}));
-      // the last LayerNorm of the network also stores its f32 rows (into the free buffer): pooling reads them
-      if (fold_ln && !last)
-        ;  // this layer's closing LayerNorm runs inside the next layer's Q/K/V projection
-      else if (fold_big && !last)  // ... its statistics only
+      // The closing LayerNorm. Folded and not the last: inside the next layer's Q/K/V projection (fold_ln: all of it,
+      // fold_big: but for its statistics). The last LayerNorm of the network is always a launch of its own and also
+      // stores its f32 rows (into the free buffer): pooling reads them
+      if (fold_big && !last)
         hipLaunchKernelGGL(ln_finalize_kernel, dim3(fin_blocks), dim3(256), 0, s, part, T, segs, H, d.eps, s2);
-      else if (H % 256 == 0)
-        hipLaunchKernelGGL(layernorm_f16_kernel, dim3(row_blocks), dim3(256), 0, s, t2, T, H, w.ln2g, w.ln2b, d.eps,
-                           last ? t1 : static_cast<float*>(nullptr), xh, s2);
-      else
-        hipLaunchKernelGGL(layernorm_kernel, dim3(row_blocks), dim3(256), 0, s, t2, T, H, w.ln2g, w.ln2b, d.eps,
-                           last ? t1 : static_cast<float*>(nullptr), xh, static_cast<half_t*>(nullptr), s2);
+      else if (!fold_ln || last)
+        layernorm_f16_rows(p, t2, w.ln2g, w.ln2b, last ? t1 : nullptr, s2);
       cur16 = res16;
       cur = Hidden{t2, s2, w.ln2g, w.ln2b};
       if (last) final_x = t1;
       continue;
     }
-    if (split)
-      VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_RESIDUAL, {.A = ch, .A_lo = cl, .W = w.s_o, .bias = w.bo, .R = enc->x, .C = enc->tmp,
-                                                           .M = T, .N = H, .K = H, .passes = passes}));
+    // f16x3 and f32 mode: the hidden state is the f32 rows in enc->x (and their halves in xs)
+    VR_TRY(project_residual(p, w.wo, w.s_o, w.bo, T, H, H, p.ctx, enc->x, enc->tmp));
+    layernorm_rows(p, enc->tmp, T, w.ln1g, w.ln1b, p.x(enc->x));
+    if (gated)
+      VR_TRY(gated_up_rows(p, w, false, T, p.x(enc->x), p.ffn));
     else
-      VR_TRY(launch_gemm(e, EPI_BIAS_RESIDUAL, enc->ctx, w.wo, w.bo, enc->x, enc->tmp, T, H, H));
-    hipLaunchKernelGGL(layernorm_kernel, dim3(row_blocks), dim3(256), 0, s, enc->tmp, T, H, w.ln1g, w.ln1b,
-                       d.eps, enc->x, xh, xl, static_cast<float2*>(nullptr));
-    if (gated) {
-      if (split)
-        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS, {.A = xh, .A_lo = xl, .W = w.s_1, .bias = w.b1, .C = enc->glu, .M = T, .N = N1,
-                                                    .K = H, .passes = passes}));
-      else
-        VR_TRY(launch_gemm(e, EPI_BIAS, enc->x, w.w1, w.b1, nullptr, enc->glu, T, N1, H));
-      glu(T, enc->ffn, fh);
-    }
-    if (split) {
-      if (!gated) {
-        VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_GELU, {.A = xh, .A_lo = xl, .W = w.s_1, .bias = w.b1, .Ch = fh, .Cl = fl, .M = T,
-                                                         .N = I, .K = H, .passes = passes}));
-      }
-      VR_TRY(launch_gemm_f16x3(e, enc, EPI_BIAS_RESIDUAL, {.A = fh, .A_lo = fl, .W = w.s_2, .bias = w.b2, .R = enc->x, .C = enc->tmp,
-                                                           .M = T, .N = H, .K = I, .passes = passes}));
-    } else {
-      if (!gated) {
-        VR_TRY(launch_gemm(e, EPI_BIAS_GELU, enc->x, w.w1, w.b1, nullptr, enc->ffn, T, I, H));
-      }
-      VR_TRY(launch_gemm(e, EPI_BIAS_RESIDUAL, enc->ffn, w.w2, w.b2, enc->x, enc->tmp, T, H, I));
-    }
-    hipLaunchKernelGGL(layernorm_kernel, dim3(row_blocks), dim3(256), 0, s, enc->tmp, T, H, w.ln2g, w.ln2b,
-                       d.eps, enc->x, xh, xl, static_cast<float2*>(nullptr));
+      VR_TRY(project_act(p, EPI_BIAS_GELU, w.w1, w.s_1, w.b1, T, I, H, p.x(enc->x), p.ffn));
+    VR_TRY(project_residual(p, w.w2, w.s_2, w.b2, T, H, I, p.ffn, enc->x, enc->tmp));
+    layernorm_rows(p, enc->tmp, T, w.ln2g, w.ln2b, p.x(enc->x));
   }
   launch_pool(e, enc, final_x, cu_dev, seq0, seq1, tok_base, 0, out_dev, sp);
   VR_HIP(hipGetLastError());
