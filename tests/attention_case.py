@@ -19,7 +19,9 @@ operands leave the rows within half of TOL[f16]: the GPU suite would fail on a k
 Kernel states and their oracles: none — oracle.bert; window — modernbert_oracle (two layers, global_every = 2: layer 1
 is the windowed one and the dominant one, layer 0 is kept quiet by a small W_o so that layer 1 still sees distinct
 tokens); table — mpnet_oracle; slopes — alibi_oracle; causal — qwen2_oracle. Each at head size 64 (2 heads) and 32
-(4 heads), H = 128, the narrowest model the engine loads."""
+(4 heads), H = 128, the narrowest model the engine loads. Head size 128 exists in the states none and causal alone
+(launch_attention refuses it a window, a table and slopes): both are the Qwen3 body of qwen3_oracle with causal = 0 or 1,
+H = 128 and two heads of 128 (an attention width of 256, not H), through the Q/K RMSNorm as real checkpoints run it."""
 from __future__ import annotations
 
 import dataclasses
@@ -30,12 +32,15 @@ import alibi_oracle as ao
 import modernbert_oracle as mo
 import mpnet_oracle as mp
 import qwen2_oracle as qo
+import qwen3_oracle as q3
 from oracle import bert as obert
 from rope_oracle import f16_operand
 
 H, I = 128, 128
 STATES = ("none", "window", "table", "slopes", "causal")
-HEAD_SIZES = (64, 32)
+HEAD_SIZES = (64, 32)  # the head sizes of all five states
+WIDE, WIDE_STATES = 128, ("none", "causal")  # head size 128: the two states launch_attention has an instantiation for
+PAIRS = [(state, dh) for state in STATES for dh in HEAD_SIZES] + [(state, WIDE) for state in WIDE_STATES]  # the models
 VOCAB = 1408     # >= the longest sequence: all ids of a sequence are distinct
 MAX_POS = 1408
 NEG = -np.inf
@@ -54,11 +59,23 @@ F32_LONGEST = 257  # the one longer length of the f32 and f16x3 ladders
 #   320 / 321               d_h = 32: the same round holds 320 keys
 #   256 / 257, 512 / 513    4 lds_keys d_h bytes cross the 64 KiB default (the hipFuncSetAttribute opt-in)
 #   639 / 640, 1280         the last staged lengths: 4 * 640 * 64 = 4 * 1280 * 32 = 160 KiB of LDS
-STAGED = {64: (79, 80, 81, 159, 160, 161, 256, 257, 639, 640), 32: (79, 80, 81, 320, 321, 512, 513, 1280)}
+#   d_h = 128 (CH = 16 chunks per 256-byte row, its own swizzle: kswz = r & 15, vswz = (r & 7) << 1):
+#   79 / 80 / 81            one staging round holds NST * NT / CH = 5 * 256 / 16 = 80 keys: 81 tokens (keys_pad = 96) take
+#                           a second round; and wave 0's second query tile as above
+#   160 / 161               keys_pad = 160 is two rounds, 176 a third
+#   128 / 129               (of ALL_KERNELS) 4 lds_keys * 128 bytes: 65,536 at 128 keys, 73,728 at lds_keys = 144 — the opt-in
+#   319 / 320               the last staged lengths: 4 * 320 * 128 = 160 KiB
+STAGED = {64: (79, 80, 81, 159, 160, 161, 256, 257, 639, 640), 32: (79, 80, 81, 320, 321, 512, 513, 1280),
+          128: (79, 80, 81, 160, 161, 319, 320)}
 #   641 / 705 / 769         attention_stream_kernel at d_h = 64: the first streamed length (a sixth 128-query block and an
 #                           eleventh key tile that hold one token), 705 = 11 * 64 + 1, 769 = 6 * 128 + 1 = 12 * 64 + 1
 #   1281 / 1345             the same at d_h = 32 (1281 = 10 * 128 + 1 = 20 * 64 + 1, 1345 = 21 * 64 + 1)
-STREAMED = {64: (641, 705, 769), 32: (1281, 1345)}
+#   321 / 337 / 385 / 449   the same at d_h = 128 (a ring of 4 * 64 * 128 halfs = 65,536 bytes of static LDS, NLD = 64 CH / NT
+#                           = 4 loads per thread and tile): 321 = 2 * 128 + 65 = 5 * 64 + 1, a third block and a sixth key
+#                           tile that hold one token past a full tile; 337 = 2 * 128 + 64 + 17: wave 2 of the third block
+#                           (qw = 320), whose second query tile holds one query; 385 = 3 * 128 + 1 = 6 * 64 + 1;
+#                           449 = 7 * 64 + 1
+STREAMED = {64: (641, 705, 769), 32: (1281, 1345), 128: (321, 337, 385, 449)}
 #   383 / 384 / 385 / 449   kWindowStreamFrom = 384: a windowed layer takes attention_stream_kernel from there on;
 #                           449 = 7 * 64 + 1: with w = 8 the block's last query meets tiles in which it sees nothing
 #                           (the softmax_base guard)
@@ -68,6 +85,7 @@ WINDOWS = (8, 64, 100)
 #   640 at d_h = 64, R = 512: 4 * 640 * 64 + 4 * 1025 bytes exceed the LDS — the table tips the launch to the streamed kernel
 RADII = (5, 64, 128, 512)
 SLOPES = {64: (0.5, 0.1), 32: (0.5, 0.1, 0.25, 0.02)}
+WIDE_GAIN = 0.5  # on the Q and K gains of the head-size-128 models (Model)
 KERNEL_SPLIT = 262144  # kMaxChunkTokens: forward_all starts another chunk (seq0, tok_base > 0) beyond this many tokens
 
 
@@ -138,10 +156,26 @@ class Model:
     o_scale: float = 32.0
 
     def __post_init__(self):
-        self.heads = H // self.dh
+        self.heads = 2 if self.dh == WIDE else H // self.dh
         seed = 7000 + 10 * STATES.index(self.state) + self.dh + RESEED.get((self.state, self.dh), 0)
         s = self.state
-        if s == "none":
+        if self.dh == WIDE:
+            # the Qwen3 body, causal or not: hidden 128, two heads of 128 (A = 256, not H) each with K/V rows of its own
+            # (the two heads' value rows share nothing, FAULT_HEAD exists), Q/K RMSNorm on. Made to dominate as the
+            # causal model below; no q/k/v biases exist
+            assert s in WIDE_STATES, (s, self.dh)
+            self.shape = q3.Qwen3Shape(1, H, self.heads, self.heads, I, WIDE, qk_norm=True, vocab=VOCAB)
+            w = q3.random_weights(self.shape, seed)
+            k = q3.layer_keys(0)
+            # (behind the norm the gains alone size the logits, about g_q g_k sqrt(d_h) cos(q, k) with cos of order
+            # d_h^-1/2: qwen3_oracle's gains around 0.9 give logits of order one; WIDE_GAIN times them a quarter of that,
+            # oracle.bert's seeded scale as for the causal model below — a key's weight within a small factor of 1 / S)
+            for name in ("qn", "kn"):
+                w[k[name]] = w[k[name]] * np.float32(WIDE_GAIN)
+            w[k["v"]] = w[k["v"]] * np.float32(self.v_scale)
+            w[k["o"]] = w[k["o"]] * np.float32(self.o_scale)
+            w[k["down"]] = np.zeros_like(w[k["down"]])
+        elif s == "none":
             self.shape = obert.BertShape(1, H, self.heads, I, vocab=VOCAB, max_pos=MAX_POS)
             w = obert.random_weights(self.shape, seed)
             k = obert.layer_keys(0)
@@ -222,6 +256,8 @@ class Model:
         if bias is None:
             bias = self.own_bias(S, param)
         s = self.state
+        if self.dh == WIDE:  # (the mask is the bias's alone, as for the causal model)
+            return q3.encode_one(self.w, self.shape, seq, causal=False, bias=bias, operand=operand)
         if s == "none":
             return obert.encode_one(self.w, self.shape, seq, bias=bias, operand=operand)
         if s == "table":
@@ -247,6 +283,8 @@ class Model:
     # -- the engine --
     def desc(self, precision, pooling="mean", param=None, **over):
         s = self.state
+        if self.dh == WIDE:
+            return q3.desc_for(self.shape, pooling, precision, max_pos=MAX_POS, causal=int(s == "causal"), **over)
         if s == "none":
             sh = self.shape
             from voitta_rag_amd import encoder as enc
@@ -422,6 +460,21 @@ def causal_strict(m, S, param):
     return b
 
 
+def causal_diagonal_group_dropped(m, S, param):
+    """The 16-key group that holds a query tile's own diagonal, keys 16 qt .. 16 qt + 15, dropped for that tile: a causal
+    key loop that ends one group early (kt1 or nt of attention_seq_kernel, `kt <= qw + 31` of attention_stream_kernel).
+    Planted in the last-but-one query tile and in tile 4 (queries 64 .. 79: wave 0's second tile in the staged kernel,
+    wave 2's first in the streamed one) where the sequence reaches it; only in tiles qt >= 1, whose queries keep the
+    keys below 16 qt."""
+    tiles = {qt for qt in ((S - 1) // 16 - 1, 4) if qt >= 1 and 16 * qt < S}
+    if not tiles:
+        return None
+    b = _own(m, S, param)
+    for qt in tiles:
+        b[FAULT_HEAD, 16 * qt:16 * qt + 16, 16 * qt:16 * qt + 16] = NEG
+    return b
+
+
 def _table_fault(m, S, param, **how):
     b = _own(m, S, param)
     b[FAULT_HEAD] = table_bias(m.tables[param], S, **how)[FAULT_HEAD]
@@ -472,7 +525,8 @@ def slope_group_start(m, S, param):
 
 GEOMETRY_FAULTS = (last_key_invisible, phantom_key, first_key_of_tile_dropped, last_group_dropped,
                    first_tile_last_group_dropped, neighbour_rows)
-STATE_FAULTS = {"none": (), "window": (window_too_wide, window_too_narrow), "causal": (causal_one_ahead, causal_strict),
+STATE_FAULTS = {"none": (), "window": (window_too_wide, window_too_narrow),
+                "causal": (causal_one_ahead, causal_strict, causal_diagonal_group_dropped),
                 "table": (table_mirrored, table_clamp_short, table_shifted, table_far_tile_early),
                 "slopes": (slope_distance_off_by_one, slope_group_start)}
 

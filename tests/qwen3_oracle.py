@@ -84,10 +84,13 @@ def random_weights(shape: Qwen3Shape, seed: int) -> dict[str, np.ndarray]:
     return {k: v.astype(np.float32) for k, v in w.items()}
 
 
-def encode_one(w: dict, shape: Qwen3Shape, ids, causal: bool = True, operand=None, probe=None) -> np.ndarray:
-    """The final-norm hidden states [S, H] of one unpadded sequence, f64. operand (e.g. rope_oracle.f16_operand): applied
-    to both operands of every matrix product, the probabilities included (as oracle.bert.attend rounds them). probe: a
-    list that receives every layer's attention weights [heads, S, S] (unrounded)."""
+def encode_one(w: dict, shape: Qwen3Shape, ids, causal: bool = True, bias=None, operand=None, probe=None) -> np.ndarray:
+    """The final-norm hidden states [S, H] of one unpadded sequence, f64. bias: an additive [heads, S, S] array on every
+    layer's logits, beside the causal mask (a deliberate mistake of tests/attention_case.py, which passes causal=False
+    and the complete array; [heads, S, S + n]: n zero keys behind the end, see oracle.bert.attend). operand (e.g.
+    rope_oracle.f16_operand): applied to both operands of every matrix product, the probabilities included (as
+    oracle.bert.attend rounds them). probe: a list that receives every layer's attention weights [heads, S, S]
+    (unrounded, without the bias)."""
     from oracle.bert import attend
 
     r = operand or (lambda a: a)  # noqa: E731
@@ -114,7 +117,7 @@ def encode_one(w: dict, shape: Qwen3Shape, ids, causal: bool = True, operand=Non
         if probe is not None:
             e = np.exp(s - s.max(axis=-1, keepdims=True))
             probe.append(e / e.sum(axis=-1, keepdims=True))
-        h = h + r(attend(s, v, None, operand).transpose(1, 0, 2).reshape(S, nh * dh)) @ W(k["o"]).T
+        h = h + r(attend(s, v, bias, operand).transpose(1, 0, 2).reshape(S, nh * dh)) @ W(k["o"]).T
         m = r(rms(h, W(k["ln_m"]), shape.eps))
         gate = m @ W(k["gate"]).T
         h = h + r(gate / (1.0 + np.exp(-gate)) * (m @ W(k["up"]).T)) @ W(k["down"]).T

@@ -1,5 +1,6 @@
 """The inputs of test_attention_gpu.py, checked on the CPU with the oracles alone: for every exposing model of
-attention_case.py, every length it is used at and every catalogue mistake that applies there,
+attention_case.py (attention_case.PAIRS: five states at head sizes 64 and 32, none and causal at 128), every length it is
+used at and every catalogue mistake that applies there,
   (a) sensitivity: in each 16-query tile the mistake touches, at least one exposed row moves by more than
       2 x test_encoder_gpu.TOL[precision] — in the absolute deviation or in |1 - cos| — for all three precisions, so the GPU
       suite fails on a kernel that makes the mistake;
@@ -42,8 +43,7 @@ def margin(m, S, param, bias, tiles):
     return min(float(factor[16 * t:16 * t + 16].max()) for t in tiles)
 
 
-@pytest.mark.parametrize("dh", ac.HEAD_SIZES)
-@pytest.mark.parametrize("state", ac.STATES)
+@pytest.mark.parametrize("state, dh", ac.PAIRS)
 def test_every_mistake_shows_and_f16_noise_does_not(state, dh):
     m = ac.model(state, dh)
     failures = []

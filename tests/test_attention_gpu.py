@@ -1,6 +1,7 @@
 """The three attention kernels (attention_kernel: f32 and f16x3; attention_seq_kernel and attention_stream_kernel: f16) in
-their five mask / bias states at both head sizes, through load_encoder, set_attention_bias, set_attention_slopes, encode
-and encode_spans alone, on the models of attention_case.py in which one attention layer IS the token row: every query row
+their five mask / bias states at head sizes 64 and 32, and in the two states head size 128 has (none and causal: the
+Qwen3 body, its own swizzle, staging round and LDS opt-ins), through load_encoder, set_attention_bias,
+set_attention_slopes, encode and encode_spans alone, on the models of attention_case.py in which one attention layer IS the token row: every query row
 of every length that crosses a kernel's edge against the f64 oracle at test_encoder_gpu.TOL. test_attention_cpu.py proves
 that each of the catalogue's mistakes would move a row of every query tile it touches by more than twice that bar."""
 import numpy as np
@@ -10,7 +11,7 @@ import attention_case as ac
 from test_encoder_gpu import TOL
 
 pytestmark = pytest.mark.gpu
-MODELS = [(state, dh) for state in ac.STATES for dh in ac.HEAD_SIZES]
+MODELS = ac.PAIRS  # every (state, head size) launch_attention has an instantiation for
 
 
 def _bits(x):
@@ -105,7 +106,8 @@ def test_a_sequence_beside_others(gpu, state, dh, precision):
     report(m, precision)
 
 
-@pytest.mark.parametrize("state, dh, precision", [("none", 64, "f16"), ("causal", 32, "f16"), ("table", 64, "f16"),
+@pytest.mark.parametrize("state, dh, precision", [("none", 64, "f16"), ("causal", 32, "f16"), ("causal", 128, "f16"),
+                                                  ("table", 64, "f16"),
                                                   ("slopes", 32, "f32"), ("window", 64, "f32")])
 def test_a_batch_that_forward_all_splits(gpu, state, dh, precision):
     """More than kMaxChunkTokens = 262144 tokens: the second chunk's launches run with seq0 and tok_base behind the first.
@@ -155,7 +157,8 @@ def test_replayed_calls_give_the_first_calls_bits(gpu, state, dh, precision):
     """forward_all captures a shape of at most 1024 tokens the second time it sees it and replays the graph from the third
     call on: three calls of one shape, the same bits."""
     m, param = ac.model(state, dh), _param(ac.model(state, dh))
-    lens = (129, 257) if precision != "f16" else (129, 641 if dh == 64 else 1024)
+    # (f16: a streamed length where one of at most 1024 tokens exists — d_h = 32 streams from 1281 on)
+    lens = (129, 257) if precision != "f16" else (129, {64: 641, 32: 1024, 128: 449}[dh])
     for _, e in engines(m, precision, [param]):
         for S in lens:
             runs = [ac.token_rows(e, [ac.sequence(S)]) for _ in range(3)]
