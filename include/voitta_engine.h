@@ -803,10 +803,28 @@ int vr_query_text_batch_bpe(vr_engine* e, const vr_bpe* tokenizer, int32_t n, co
  * mix of norm, window, position and ffn is refused. */
 int vr_reranker_load(vr_engine* e, const vr_bert_desc* desc, const void* const* tensors, int32_t n_tensors, int mem);
 
+/* A decoder cross-encoder in the same reranker slot (Qwen3-Reranker-0.6B, one-label Qwen3ForSequenceClassification /
+ * Qwen2ForSequenceClassification): the body vr_encoder_load takes under VR_NORM_PRE_RMS_ROTARY — position
+ * VR_POS_ROTARY, a gated ffn, causal 0 or 1, head_dim and qk_norm as vr_encoder_load takes them (vr_bert_desc_v2 / _v3),
+ * type_vocab 1, any precision — with pooling VR_POOL_LAST and normalize 0. Its tensors are vr_encoder_load's 5 + 18 L
+ * (5 + 20 L with qk_norm) followed by ONE head tensor, score.weight [1, H] f32, never NULL. The logit of a pair is
+ * score.weight . N_f(h_last): h_last the residual row of the pair's LAST token, N_f the final RMSNorm; no bias.
+ * Qwen3-Reranker's published score, softmax over (lm_head[no] . h, lm_head[yes] . h) taken at "yes", is the sigmoid of
+ * that logit with score.weight = lm_head[yes] - lm_head[no], which the caller computes (embed_tokens where tied).
+ * Everything outside this description is refused with the field and its value named; a refused load leaves a loaded
+ * reranker as it was. vr_rerank, replacement by the next load of either kind and freeing are vr_reranker_load's;
+ * vr_reranker_load itself keeps refusing this norm.
+ * The prompt is the caller's job: the ids of a pair are prefix + body + suffix of the model's chat template (system
+ * instruction, "<Instruct>: .. <Query>: .. <Document>: ..", the assistant turn with its empty think block), so that
+ * the last token is the one the model answers "yes" or "no" behind. Only the last row of each pair is computed behind
+ * the last layer's attention (the output projection, the FFN and the final norm run on n_seq rows). */
+int vr_reranker_load_decoder(vr_engine* e, const vr_bert_desc* desc, const void* const* tensors, int32_t n_tensors, int mem);
+
 /* One logit per (question, passage) pair: logit = wc . tanh(Wp h_CLS + bp) + bc, h_CLS the last hidden state of the
  * pair's [CLS] token (a ModernBERT cross-encoder: its own head, see vr_reranker_load). ids / offsets as vr_encode (pair sequences, e.g. from vr_wordpiece_encode_pairs); seg_b[n_seq]
  * int32: tokens at positions >= seg_b[i] of sequence i are segment B (token type 1), 1 <= seg_b[i] <= its length. A
- * model with one token type (type_vocab 1, XLM-R) has no segment B: seg_b may be NULL and is ignored. All three in
+ * model with one token type (type_vocab 1, XLM-R) has no segment B: seg_b may be NULL and is ignored. A decoder
+ * cross-encoder (vr_reranker_load_decoder) has one token type too; its logit is score.weight . N_f(h_last). All three in
  * `mem`; out_logits: n_seq f32 in `out_mem`. The head runs in f32 whatever the precision, in a fixed order:
  * the same input gives the same bits. Arguments are checked before any device work. */
 int vr_rerank(vr_engine* e, const int32_t* ids, const int32_t* offsets, const int32_t* seg_b, int32_t n_seq, int mem,

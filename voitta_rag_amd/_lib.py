@@ -242,6 +242,7 @@ SIGNATURES = {
                                           _i64p, C.c_int32, _i32p, _dp, C.c_int32, C.POINTER(VrFilter), C.c_int32,
                                           _i32p, C.c_int32, _i64p, _dp, _i32p, _i32p, _i32p, _fp]),
     "vr_reranker_load": (C.c_int, [_vp, C.POINTER(VrBertDesc), C.POINTER(_vp), C.c_int32, C.c_int]),
+    "vr_reranker_load_decoder": (C.c_int, [_vp, C.POINTER(VrBertDesc), C.POINTER(_vp), C.c_int32, C.c_int]),
     "vr_rerank": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, C.c_int, _vp, C.c_int]),
     "vr_rerank_text": (C.c_int, [_vp, _vp, C.c_int32, C.POINTER(C.c_char_p), _i64p, _i64p, C.POINTER(C.c_char_p), _i64p,
                                  C.c_int32, _fp]),

@@ -32,11 +32,14 @@ class Settings:
         self.initial_rows: int = int(os.getenv("VOITTA_INITIAL_ROWS", "0"))
         # directory of the persisted index (VectorStoreService.save / load); loaded on first use when present
         self.index_dir: str = os.getenv("VOITTA_INDEX_DIR", "")
-        # second-stage reranking (opt-in): a local one-label cross-encoder checkpoint (BERT, XLM-R or ModernBERT); a
-        # search fetches this many hybrid candidates (clamped to [limit, 341]), rescores them on the GPU and returns the
-        # best `limit`
+        # second-stage reranking (opt-in): a local cross-encoder checkpoint (one-label BERT, XLM-R or ModernBERT, or a
+        # Qwen3-Reranker); a search fetches this many hybrid candidates (clamped to [limit, 341]), rescores them on the
+        # GPU and returns the best `limit`
         self.rerank_model: str = os.getenv("VOITTA_RERANK_MODEL", "")
         self.rerank_candidates: int = int(os.getenv("VOITTA_RERANK_CANDIDATES", "50"))
+        # the task instruction a decoder cross-encoder (Qwen3-Reranker) reads in front of every pair; empty = the
+        # model card's default (reranker.DEFAULT_INSTRUCTION). Other rerankers ignore it
+        self.rerank_instruction: str = os.getenv("VOITTA_RERANK_INSTRUCTION", "")
         # MMR diversification of search results (opt-in): unset = off; a value in [0, 1] is the diversity d of every
         # search. The first stage then fetches VOITTA_MMR_CANDIDATES (clamped to [limit, 341]) and MMR selects `limit`
         mmr = os.getenv("VOITTA_MMR_DIVERSITY", "")

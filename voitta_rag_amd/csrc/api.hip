@@ -241,6 +241,14 @@ int vr_reranker_load(vr_engine* e, const vr_bert_desc* desc, const void* const* 
   return reranker_load(e, desc, tensors, n_tensors, mem);
 }
 
+int vr_reranker_load_decoder(vr_engine* e, const vr_bert_desc* desc, const void* const* tensors, int32_t n_tensors, int mem) {
+  VR_TRY(check_engine(e));
+  VR_CHECK(desc && tensors, "null argument");
+  VR_TRY(check_mem(mem));
+  std::lock_guard<std::mutex> writer(e->wmu);
+  return reranker_load_decoder(e, desc, tensors, n_tensors, mem);
+}
+
 int vr_rerank(vr_engine* e, const int32_t* ids, const int32_t* offsets, const int32_t* seg_b, int32_t n_seq, int mem,
               float* out_logits, int out_mem) {
   VR_CHECK(n_seq >= 0 && (n_seq == 0 || (ids && offsets && out_logits)), "bad arguments");

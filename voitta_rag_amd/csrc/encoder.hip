@@ -17,6 +17,9 @@
 //   pool_kernel       mean / CLS / last-token pooling + L2 normalise HBM bound
 //   rerank_head_kernel cross-encoder head on the pooled [CLS] rows   one f32 logit per pair (encoder_rerank)
 //   rerank_head_ln_kernel the head of a pre-norm cross-encoder: dense, GELU, LayerNorm, classifier (encoder_rerank)
+//   gather_last_rows_kernel, rerank_head_rms_kernel  a decoder cross-encoder (vr_reranker_load_decoder): the last token's
+//                     context and residual rows into [n_seq, .] matrices behind the last layer's attention, and the final
+//                     RMSNorm with the dot product against score.weight, one f32 logit per pair (rerank_tail)
 //   embed_head_kernel the embedder's post-pooling head: Dense / LayerNorm stages, normalise, truncate (vr_encoder_set_head)
 //   unit_sum_kernel, unit_gap_kernel, unit_boundary_kernel, chunk_base_kernel, chunk_row_kernel, chunk_gather_kernel
 //                     semantic chunking (vr_encode_semantic): unit sums, gap distances, boundaries, chunk rows (launch_semantic)
@@ -138,6 +141,10 @@ struct Encoder {
   float *pool_w = nullptr, *pool_b = nullptr, *cls_w = nullptr, *cls_b = nullptr;
   float *head_ln_g = nullptr, *head_ln_b = nullptr;
   DevArray<float> rows;
+  // a decoder cross-encoder (vr_reranker_load_decoder): score.weight [H], and the [n_seq, *] matrices of the last layer's
+  // tail (RerankRows), grown by encoder_rerank before the pass — never inside a capture — and dropped with the graphs
+  float* score_w = nullptr;
+  DevArray<float> tail_ws;
   DevArray<float> skinny_ws;  // K-slice partial sums of gemm_f16_skinny_kernel
   // hipGraphs of small forward passes (a query, a handful of sequences): ~135 launches of a few
   // microseconds of work each are launch-bound; replayed as one graph they are not
@@ -1209,6 +1216,56 @@ __global__ __launch_bounds__(256) void gather_first_rows_kernel(const float4* __
   if (i >= n) return;
   const int t = min(cu[seq0 + i] - tok_base, T - 1);  // an empty sequence reads a neighbour's row; pooling ignores it
   for (int c = lane; c < row_f4; c += 64) dst[static_cast<int64_t>(i) * row_f4 + c] = src[static_cast<int64_t>(t) * row_f4 + c];
+}
+
+// The same for a decoder cross-encoder, which reads the LAST token of every pair (rerank_tail): the context row
+// (`ctx_f4` float4s: f32, (hi, lo) or plain f16 rows, A wide) and the residual row (`x_f4` float4s, f32) of token
+// cu[seq0 + i + 1] - 1, both in one launch. One wave per row.
+__global__ __launch_bounds__(256) void gather_last_rows_kernel(const float4* __restrict__ ctx, const float4* __restrict__ x,
+                                                               const int32_t* __restrict__ cu, int seq0, int tok_base, int n,
+                                                               int T, int ctx_f4, int x_f4, float4* __restrict__ ctx_dst,
+                                                               float4* __restrict__ x_dst) {
+  const int lane = threadIdx.x & 63;
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= n) return;
+  const int t = min(max(cu[seq0 + i + 1] - 1 - tok_base, 0), T - 1);  // (lengths are checked >= 1; never outside the pass)
+  for (int c = lane; c < ctx_f4; c += 64) ctx_dst[static_cast<int64_t>(i) * ctx_f4 + c] = ctx[static_cast<int64_t>(t) * ctx_f4 + c];
+  for (int c = lane; c < x_f4; c += 64) x_dst[static_cast<int64_t>(i) * x_f4 + c] = x[static_cast<int64_t>(t) * x_f4 + c];
+}
+
+// The head of a decoder cross-encoder on n residual rows [n, H]: out[i] = w . rms(x_i, g), the final RMSNorm and the dot
+// product with score.weight in one launch, f32 whatever the model's precision. One wave per row, the row as float2
+// pairs per lane (rmsnorm_kernel's layout and its sum of squares, so the normalised values are that kernel's bits);
+// each lane sums its squares and then its products in index order, a fixed xor butterfly finishes both. No atomics, no
+// LDS: a row's logit bits depend on that row alone, not on n or on the row's place in the launch.
+__global__ __launch_bounds__(256) void rerank_head_rms_kernel(const float* __restrict__ x, int n, int H,
+                                                              const float* __restrict__ g, float eps,
+                                                              const float* __restrict__ w, float* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= n) return;
+  const int pairs = H / 128;
+  float2 v[kMaxPairs];
+  float q = 0.0f;
+#pragma unroll
+  for (int k = 0; k < kMaxPairs; ++k)
+    if (k < pairs) {
+      v[k] = *reinterpret_cast<const float2*>(x + static_cast<int64_t>(i) * H + (k * 64 + lane) * 2);
+      q += v[k].x * v[k].x + v[k].y * v[k].y;
+    }
+  const float inv = 1.0f / sqrtf(wave_sum(q) / static_cast<float>(H) + eps);
+  float dot = 0.0f;
+#pragma unroll
+  for (int k = 0; k < kMaxPairs; ++k)
+    if (k < pairs) {
+      const int e = (k * 64 + lane) * 2;
+      const float2 gg = *reinterpret_cast<const float2*>(g + e);
+      const float2 ww = *reinterpret_cast<const float2*>(w + e);
+      dot += rms_apply(v[k].x, inv, gg.x) * ww.x;
+      dot += rms_apply(v[k].y, inv, gg.y) * ww.y;
+    }
+  dot = wave_sum(dot);
+  if (lane == 0) out[i] = dot;
 }
 
 // dst[i] = LayerNorm output of the first token of sequence seq0 + i, re-derived from the pre-LN rows
@@ -4854,6 +4911,7 @@ static void free_encoder(void** slot) {
   invalidate_graphs(enc);
   enc->out.release();
   enc->rows.release();
+  enc->tail_ws.release();
   enc->pooled.release();
   delete enc;
   *slot = nullptr;
@@ -5376,6 +5434,37 @@ int reranker_load(vr_engine* e, const vr_bert_desc* d_in, const void* const* t, 
     }
     VR_TRY(dev_alloc_copy(e, enc, h[n_head - 2], H, mem, &enc->cls_w));
     VR_TRY(dev_alloc_copy(e, enc, h[n_head - 1], 1, mem, &enc->cls_b));
+    VR_HIP(hipStreamSynchronize(e->stream));
+    return 0;
+  }();
+  if (rc != 0) free_encoder(&e->reranker);
+  return rc;
+}
+
+// vr_reranker_load_decoder: the VR_NORM_PRE_RMS_ROTARY body as build_encoder takes it, pooled at the last token, and one
+// head tensor, score.weight [1, H]. Every check — these and build_encoder's own — runs before the slot is touched.
+int reranker_load_decoder(vr_engine* e, const vr_bert_desc* d_in, const void* const* t, int n_tensors, int mem) {
+  vr_bert_desc desc;
+  int32_t causal = 0, head_dim = 0, qk_norm = 0;
+  VR_TRY(read_desc(d_in, &desc, &causal, &head_dim, &qk_norm));
+  const vr_bert_desc* d = &desc;
+  VR_CHECK(d->norm == VR_NORM_PRE_RMS_ROTARY, "a decoder reranker needs norm VR_NORM_PRE_RMS_ROTARY (norm %d): every other "
+           "cross-encoder loads through vr_reranker_load", d->norm);
+  VR_CHECK(d->position == VR_POS_ROTARY, "a decoder reranker needs position VR_POS_ROTARY (position %d)", d->position);
+  VR_CHECK(d->ffn == VR_FFN_SWIGLU || d->ffn == VR_FFN_GEGLU, "a decoder reranker needs a gated ffn (ffn %d): VR_FFN_SWIGLU or "
+           "VR_FFN_GEGLU", d->ffn);
+  VR_CHECK(d->pooling == VR_POOL_LAST, "a decoder reranker reads the last token's row (pooling %d): VR_POOL_LAST", d->pooling);
+  VR_CHECK(d->normalize == 0, "a decoder reranker pools without normalising (normalize %d)", d->normalize);
+  VR_CHECK(d->type_vocab == 1, "a decoder reranker has one token type (type_vocab %d)", d->type_vocab);
+  VR_CHECK(qk_norm == 0 || qk_norm == 1, "qk_norm %d must be 0 or 1", qk_norm);
+  const int per_layer = qk_norm == 1 ? 20 : 18;
+  VR_CHECK(d->layers >= 1 && n_tensors == 5 + per_layer * d->layers + 1, "expected %d tensors, got %d",
+           5 + per_layer * d->layers + 1, n_tensors);
+  VR_CHECK(t[n_tensors - 1] != nullptr, "tensor %d is null", n_tensors - 1);
+  VR_TRY(build_encoder(e, &e->reranker, d_in, t, n_tensors - 1, mem));
+  Encoder* enc = static_cast<Encoder*>(e->reranker);
+  const int rc = [&]() -> int {
+    VR_TRY(dev_alloc_copy(e, enc, t[n_tensors - 1], d->hidden, mem, &enc->score_w));
     VR_HIP(hipStreamSynchronize(e->stream));
     return 0;
   }();
@@ -5957,6 +6046,60 @@ static int forward_chunk_rms(vr_engine* e, Encoder* enc, const int32_t* ids_dev,
   return 0;
 }
 
+// A decoder cross-encoder's logit reads one row per pair, the last token's, so everything behind the LAST layer's
+// attention runs on n_seq rows instead of T — cls_tail's idea for the pre-norm decoder block. The [n_seq, *] matrices live
+// in enc->tail_ws (encoder_rerank sizes it: at one-token pairs they are larger than the qkv buffer cls_tail carves up).
+struct RerankRows {
+  float *x, *tmp, *xs, *ctx, *ffn;  // residual rows, the stream's other buffer, N(x) as a product reads it, context, activation
+  static int64_t floats(const Encoder* enc, int64_t n) {
+    return n * (3 * static_cast<int64_t>(enc->d.hidden) + enc->attn + enc->d.intermediate);
+  }
+  RerankRows(const Encoder* enc, int n_seq) {
+    const int64_t n = n_seq, H = enc->d.hidden, A = enc->attn;
+    x = enc->tail_ws.p;  // [n_seq, H] f32
+    tmp = x + n * H;     // [n_seq, H] f32
+    xs = tmp + n * H;    // [n_seq, H] f32, [n_seq, 2H] halfs (f16x3) or [n_seq, H] halfs (f16)
+    ctx = xs + n * H;    // [n_seq, A] f32, [n_seq, 2A] halfs or [n_seq, A] halfs
+    ffn = ctx + n * A;   // [n_seq, I] likewise
+  }
+};
+
+// The rest of the last layer of a decoder cross-encoder on the last row of every pair, and the head (vr_reranker_load_decoder):
+//   x = h_last + W_o ctx_last;  x = x + W_down(act(gate(N_m(x))) * up(N_m(x)));  logit = score . N_f(x)
+// forward_chunk_rms_rotary's steps at M = n_seq: the norm as a launch of its own in every mode, the gate in the FFN-up
+// epilogue where that routine fuses it (f16, a skinny product). h: the residual stream going into the last layer, whose
+// attention has just written enc->ctx. Writes one logit per sequence at out_dev[seq0 ..].
+static int rerank_tail(const Pass& p, const LayerWeights& w, const float* h, const int32_t* cu_dev, int seq0, int seq1,
+                       int tok_base, float* out_dev) {
+  Encoder* enc = p.enc;
+  const vr_bert_desc& d = enc->d;
+  const int T = p.T, H = d.hidden, I = d.intermediate, A = enc->attn, n_seq = seq1 - seq0;
+  VR_CHECK(enc->tail_ws.cap >= RerankRows::floats(enc, n_seq), "the reranker's tail workspace holds %lld floats, %d pairs need "
+           "%lld", static_cast<long long>(enc->tail_ws.cap), n_seq, static_cast<long long>(RerankRows::floats(enc, n_seq)));
+  const RerankRows c(enc, n_seq);
+  const dim3 gblocks(Pass::blocks4(n_seq));
+  hipLaunchKernelGGL(gather_last_rows_kernel, gblocks, dim3(256), 0, p.s, reinterpret_cast<const float4*>(enc->ctx),
+                     reinterpret_cast<const float4*>(h), cu_dev, seq0, tok_base, n_seq, T, p.plain ? A / 8 : A / 4, H / 4,
+                     reinterpret_cast<float4*>(c.ctx), reinterpret_cast<float4*>(c.x));
+  const Rows x = p.rows(c.xs), ctx = p.rows(c.ctx), ffn = p.rows(c.ffn);
+  // x' = x + W_o ctx
+  VR_TRY(project_residual(p, w.wo, w.s_o, w.bo, n_seq, H, A, ctx, c.x, c.tmp));
+  // the gated FFN of N_m(x')
+  if (p.plain && H % 256 == 0)
+    hipLaunchKernelGGL(rmsnorm_f16_kernel, gblocks, dim3(256), 0, p.s, c.tmp, n_seq, H, w.ln1g, d.eps, x.hi);
+  else
+    hipLaunchKernelGGL(rmsnorm_kernel, gblocks, dim3(256), 0, p.s, c.tmp, n_seq, H, w.ln1g, d.eps, p.split ? nullptr : x.f, x.hi,
+                       x.lo);
+  VR_TRY(gated_up_rows(p, w, p.plain && enc->fuse && skinny_routed(n_seq, 2 * I, H), n_seq, x, ffn));
+  // x'' = x' + W_down act
+  VR_TRY(project_residual(p, w.w2, w.s_2, w.b2, n_seq, H, I, ffn, c.tmp, c.x));
+  // the final norm and the dot product with score.weight, one wave per pair
+  hipLaunchKernelGGL(rerank_head_rms_kernel, gblocks, dim3(256), 0, p.s, c.x, n_seq, H, w.ln2g, d.eps, enc->score_w,
+                     out_dev + seq0);
+  VR_HIP(hipGetLastError());
+  return 0;
+}
+
 // The forward pass of an RMSNorm pre-norm model with rotary positions and a gated FFN (VR_NORM_PRE_RMS_ROTARY: the Llama /
 // Qwen2 block, the decoder-style embedders), forward_chunk's arguments:
 //   h = word[id];  per layer  h += W_o attn(rope(N_a(h))),  h += W_down(act(gate(N_m(h))) * up(N_m(h)));  out = N_f(h)
@@ -6000,6 +6143,8 @@ static int forward_chunk_rms_rotary(vr_engine* e, Encoder* enc, const int32_t* i
     if (qk_norm) qk_norm_rotate_rows(p, w, A, dh);
     else if (!fuse_rope) rotate_rows(p, enc->rope, A, dh);
     VR_TRY(launch_attention(e, enc, cu_dev, seq0, n_seq, tok_base, max_len, false, 0, layer_flop));
+    // (a decoder cross-encoder, vr_reranker_load_decoder: the rest of its last layer on the pairs' last rows, and the head)
+    if (enc->score_w && li + 1 == enc->layers.size()) return rerank_tail(p, w, h, cu_dev, seq0, seq1, tok_base, out_dev);
     // h' = h + W_o ctx
     VR_TRY(project_residual(p, w.wo, w.s_o, w.bo, T, H, A, p.ctx, h, other));
     std::swap(h, other);
@@ -6664,11 +6809,18 @@ int encoder_rerank(vr_engine* e, const int32_t* ids, const int32_t* offsets, con
   const int H = enc->d.hidden;
   std::vector<int32_t> cu_host;
   VR_TRY(read_offsets(e, enc, offsets, seg_b, n_seq, mem, &cu_host));
-  VR_TRY(enc->rows.grow(static_cast<int64_t>(n_seq) * H, 0, e->stream));
+  if (!enc->score_w) VR_TRY(enc->rows.grow(static_cast<int64_t>(n_seq) * H, 0, e->stream));
   float* out_dev = out;
   if (out_mem == VR_MEM_HOST) {
     VR_TRY(enc->out.grow(n_seq, 0, e->stream));
     out_dev = enc->out.p;
+  }
+  if (enc->score_w) {  // a decoder cross-encoder: the pass itself ends in the logits (rerank_tail)
+    const float* before = enc->tail_ws.p;
+    VR_TRY(enc->tail_ws.grow(RerankRows::floats(enc, n_seq), 0, e->stream));
+    if (enc->tail_ws.p != before) invalidate_graphs(enc);  // (captured tails hold its pointers)
+    VR_TRY(forward_all(e, enc, ids, offsets, nullptr, n_seq, mem, cu_host, out_dev));
+    return finish(e, out, out_dev, n_seq, mem, out_mem);
   }
   VR_TRY(forward_all(e, enc, ids, offsets, seg_b, n_seq, mem, cu_host, enc->rows.p));
   const dim3 head_grid(static_cast<unsigned>((n_seq + 15) / 16));

@@ -627,6 +627,7 @@ int encoder_encode_semantic(vr_engine* e, const int32_t* ids, const int32_t* off
                             int32_t* out_unit_start, float* out_gap_dist, int32_t* n_chunks, int out_mem);
 void encoder_release(vr_engine* e);  // the embedder and the reranker
 int reranker_load(vr_engine* e, const vr_bert_desc* d, const void* const* tensors, int n_tensors, int mem);
+int reranker_load_decoder(vr_engine* e, const vr_bert_desc* d, const void* const* tensors, int n_tensors, int mem);
 bool reranker_loaded(vr_engine* e);
 int encoder_rerank(vr_engine* e, const int32_t* ids, const int32_t* offsets, const int32_t* seg_b, int n_seq, int mem,
                    float* out, int out_mem);  // out: n_seq logits

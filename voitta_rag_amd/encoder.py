@@ -650,6 +650,49 @@ PRENORM_HEAD_NAMES = ["head.dense.weight", "head.dense.bias", "head.norm.weight"
                       "classifier.bias"]
 
 
+# a decoder cross-encoder's (vr_reranker_load_decoder): one row, no bias — Qwen3ForSequenceClassification's score.weight,
+# or lm_head[yes] - lm_head[no] of a Qwen3ForCausalLM reranker (qwen3_rerank_head)
+DECODER_HEAD_NAMES = ["score.weight"]
+
+
+def qwen3_rerank_head(state: dict, desc: "BertDesc", yes_id: int | None = None, no_id: int | None = None) -> np.ndarray:
+    """The head row of a decoder cross-encoder, [1, H] f32. A state dict with `score.weight` (a one-label
+    Qwen3ForSequenceClassification / Qwen2ForSequenceClassification): that tensor as stored. Otherwise (Qwen3ForCausalLM /
+    Qwen2ForCausalLM, Qwen3-Reranker's published form) W[yes_id] - W[no_id], W = lm_head.weight or, where the embeddings
+    are tied and the checkpoint holds no lm_head, embed_tokens.weight: softmax over (W[no] . h, W[yes] . h) taken at
+    "yes" is sigmoid((W[yes] - W[no]) . h). The difference is taken in f64 and rounded once."""
+
+    def find(name):
+        hits = [k for k in state if k == name or k.endswith("." + name)]
+        if len(hits) > 1:
+            raise KeyError(f"weight '{name}' is ambiguous in state dict: {hits[:3]}")
+        if not hits:
+            return None
+        t = state[hits[0]]
+        return t.detach().cpu().float().numpy() if hasattr(t, "detach") else np.asarray(t)
+
+    score = find("score.weight")
+    if score is not None:
+        if tuple(score.shape) != (1, desc.hidden):
+            raise ValueError(f"weight 'score.weight' has shape {tuple(score.shape)}: a one-label head is {(1, desc.hidden)}")
+        return np.ascontiguousarray(score, np.float32)
+    W = find("lm_head.weight")
+    name = "lm_head.weight"
+    if W is None:
+        W, name = find("embed_tokens.weight"), "embed_tokens.weight"
+    if W is None:
+        raise KeyError("weight 'score.weight', 'lm_head.weight' or 'embed_tokens.weight' not found in state dict")
+    if W.ndim != 2 or W.shape[1] != desc.hidden:
+        raise ValueError(f"weight '{name}' has shape {tuple(W.shape)}, the model description implies (vocab, {desc.hidden})")
+    for what, i in (("yes", yes_id), ("no", no_id)):
+        if i is None:
+            raise ValueError(f"the id of the token '{what}' is missing: a causal-LM reranker scores lm_head[yes] - lm_head[no]")
+        if not 0 <= int(i) < W.shape[0]:
+            raise ValueError(f"the id {int(i)} of the token '{what}' is outside the {W.shape[0]} rows of '{name}'")
+    row = W[int(yes_id)].astype(np.float64) - W[int(no_id)].astype(np.float64)
+    return np.ascontiguousarray(row.astype(np.float32)[None, :])
+
+
 def modernbert_head(state: dict, desc: "BertDesc") -> dict:
     """The six head tensors of a ModernBertForSequenceClassification state dict (any key prefix) under
     PRENORM_HEAD_NAMES; zeros for an absent head.dense.bias (classifier_bias false) or head.norm.bias (norm_bias
@@ -677,7 +720,7 @@ def expected_shape(desc: BertDesc, name: str) -> tuple:
         if name.endswith(("self_attn.q_proj.weight", "self_attn.k_proj.weight", "self_attn.v_proj.weight")): return (A, H)
         if name.endswith(("self_attn.q_proj.bias", "self_attn.k_proj.bias", "self_attn.v_proj.bias")): return (A,)
         if name.endswith("self_attn.o_proj.weight"): return (H, A)
-    if name == "classifier.weight": return (1, H)
+    if name == "classifier.weight" or name == "score.weight": return (1, H)
     if name == "classifier.bias": return (1,)
     if name.startswith("head.norm."): return (H,)
     if name.endswith("word_embeddings.weight"): return (desc.vocab, H)
@@ -737,11 +780,25 @@ def load_encoder(engine, desc: BertDesc, state: dict) -> None:
         engine.set_encoder_head(desc.head or [], desc.truncate_dim)
 
 
-def load_reranker(engine, desc: BertDesc, state: dict) -> None:
+def load_reranker(engine, desc: BertDesc, state: dict, *, yes_id: int | None = None, no_id: int | None = None) -> None:
     """state: a one-label HF BertForSequenceClassification state dict (any key prefix), the encoder's tensors plus the
     pooler and the classifier. desc: CLS pooling, no normalisation. A pre-norm, rotary, gated description: a one-label
     ModernBertForSequenceClassification state dict (modernbert_slots' body, modernbert_head's head), pooling "cls" or
-    "mean" (config.json's classifier_pooling), no normalisation."""
+    "mean" (config.json's classifier_pooling), no normalisation. norm "rms_pre_rotary": a decoder cross-encoder
+    (vr_reranker_load_decoder) — a Qwen3 / Qwen2 state dict, its body through qwen3_slots / qwen2_slots (grouped-query
+    attention resolved here), pooling "last", no normalisation, and qwen3_rerank_head's row: score.weight, or
+    lm_head[yes_id] - lm_head[no_id] of a causal-LM checkpoint."""
+    if desc.rms_rotary:
+        if desc.pooling != "last" or desc.normalize:
+            raise ValueError("a decoder reranker reads the last token's row without normalising it")
+        head = qwen3_rerank_head(state, desc, yes_id, no_id)
+        body = {k: v for k, v in state.items() if "score" not in k.split(".")}
+        slots = qwen3_slots if (desc.head_dim or desc.qk_norm) else qwen2_slots
+        names, body = slots(body, desc)
+        body[DECODER_HEAD_NAMES[0]] = head
+        _load(engine, desc, body, names + DECODER_HEAD_NAMES, engine._lib.vr_reranker_load_decoder)
+        engine.reranker_desc = desc
+        return
     if desc.prenorm and desc.rotary and desc.gated:
         if desc.normalize:
             raise ValueError("a reranker pools without normalising")
